@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the RayTracinGO hot path on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W          (default: N=1, K=20, W=5)
+  python bench.py --gpus 1 --steps K --warmup W          (default: N=1, K=200, W=10)
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     (+ the last step's frame as .npy files, see dump_outputs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): cornell 1920x1080 --mode=path --sample=4 (16 spp), progressive frames.
@@ -93,6 +94,28 @@ def parity_against(ref_accum, win, gpu_accum):
             "mean_rel_diff": float(abs(g.mean() - r.mean()) / max(r.mean(), 1e-30))}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each [H, W, C] array as out_dir/<name>.npy in float32.  When they do not fit DUMP_BUDGET_BYTES together, the same
+    fixed, seeded sample of pixels is taken from each ([K, C]), and its flat pixel indices (y * W + x) go to pixel_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = next(iter(arrays.values())).shape[:2]
+    n_px = h * w
+    bytes_per_px = sum(4 * a.shape[2] for a in arrays.values())
+    slack = 4096 * (len(arrays) + 1)                                      # .npy headers
+    if n_px * bytes_per_px + slack > DUMP_BUDGET_BYTES:
+        k = (DUMP_BUDGET_BYTES - slack) // (bytes_per_px + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_px, size=k, replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+        arrays = {name: a.reshape(n_px, -1)[idx] for name, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -115,7 +138,14 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="developer rehearsal of the N>1 code path on a 1-GPU box: every rank uses cuda:0 and the gather goes "
                          "through gloo on host copies. The JSON line is marked and is NOT a measurement.")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="1 GPU: after the timed steps, write what the last step handed back -- the float accumulation buffer "
+                         "(accum.npy) and the 8-bit image (image.npy), [H, W, 4] in frame row order, as float32 -- under DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # stdout carries exactly one JSON line: libraries that print there (RCCL's version banner at start-up) go to stderr
     sys.stdout.flush()
@@ -132,6 +162,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run for N>1)" % (args.gpus, world))
+    if args.dump_outputs and world > 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (the accumulation buffer stays spread over the ranks)")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py: no GPU visible; the hot path has no CPU fallback")
     rehearse = args.rehearse_on_one_gpu
@@ -296,6 +328,11 @@ def main():
         step(args.warmup + k)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # (world == 1: the V = S sub-shares are stacked in one buffer; full_row_index puts the rows back in frame order)
+        rows = bands.full_row_index(H, band_h, V, rows_pad, dev)
+        last_image = images[(args.warmup + args.steps - 1) % NBUF if multi else 0]
+        dump_outputs(args.dump_outputs, {"accum": accum[rows].cpu().numpy(), "image": last_image[rows].cpu().numpy()})
     st = stats_sum()
     tt = torch.tensor([dt], dtype=torch.float64, device=rdev)
     rr = torch.tensor([float(st["rays_total"]), float(st["rays_culled"])], dtype=torch.float64, device=rdev)
