@@ -112,7 +112,8 @@ typedef struct rtgo_stats {
                                  bounds -- to the primitive; s: its axis scales) -- the guard's second quantity; 0 without quadrics */
     uint32_t last_variant;    /* last launch: bit 0 streaming loop, bit 1 the second fast-walk structure, bit 2 canonical walk, bit 3 the
                                  launch was one of the launch-time trial's (the first launches of a job time the candidate
-                                 (loop, structure) pairs -- same pixels either way -- and the fastest keeps the job) */
+                                 (loop, structure) pairs -- same pixels either way -- and the fastest keeps the job), bit 4 the fast walk
+                                 over the uniform grid instead of a tree */
     uint32_t launches_trial;  /* launches since rtgo_reset_stats that were trial launches */
 } rtgo_stats;
 
@@ -157,7 +158,9 @@ int rtgo_resize(rtgo_ctx* ctx, size_t pixels);
    RCCL): d_accum = float4[pixels], d_image = uchar4[pixels].  The caller keeps ownership. */
 int rtgo_bind_output(rtgo_ctx* ctx, void* d_accum, void* d_image, size_t pixels);
 
-/* optixLaunch(pipeline, stream, params, ..., width, height, 1) (renderer.cpp:749-774).  Asynchronous. */
+/* optixLaunch(pipeline, stream, params, ..., width, height, 1) (renderer.cpp:749-774).  Asynchronous, with one exception: once
+   the launch-time trial of a job (same frame geometry, spp and mode) has all its timed launches in flight, the next launch of that
+   job waits for them to finish, once, to pick the fastest candidate. */
 int rtgo_launch(rtgo_ctx* ctx, const rtgo_frame* frame);
 
 /* cudaStreamSynchronize + CUDA_SYNC_CHECK (CUDAOutputBuffer.h:247-250, renderer.cpp:773) */

@@ -30,7 +30,7 @@ struct rtgo_ctx {
     static constexpr int kEvRing = 64;
     hipEvent_t ev_start[kEvRing] = {}, ev_stop[kEvRing] = {};
     int ev_head = 0, ev_pending = 0;
-    unsigned char ev_tag[kEvRing] = {};    // 1 / 2: a trial launch of the streaming / the lock-step loop (see `trial` below)
+    unsigned char ev_tag[kEvRing] = {};    // a trial launch of candidate k carries k + 1, any other launch 0 (see `trial` below)
     // Frames of several passes per pixel (> 16 spp) have two kernels with bitwise the same output: lanes streaming through their
     // samples (open scenes, where path lengths differ: plateau 3840x2160 spp 256 18.8 ms against 20.5) or the wave running pass by
     // pass in lock-step (closed scenes, where nearly every path runs to the depth limit and regeneration only costs: cornell spp 64
@@ -46,7 +46,6 @@ struct rtgo_ctx {
     struct Trial {
         std::vector<uint32_t> key;
         int issued = 0, done = 0;
-        int n_cand = 0;
         float best[8] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
         int choice = -1;                   // index of the winning candidate, -1 = undecided
     } trial;
@@ -54,46 +53,38 @@ struct rtgo_ctx {
     // the boxes build_kernel reports.  Scenes of many small primitives spread evenly (balls: 256 spheres in a room) walk it in a third of
     // the tree's instructions; where it is slower the trial drops it after two launches.
     struct Grid {
-        void* d = nullptr;                 // n_cells words (first item | count << 16), then 16-bit items: positions into d_fprims
+        void* d = nullptr;                 // [table: n_cells words, 0 = empty cell, else 1 + its record][records: 32 B per listing cell, its box
+                                           // and (first item | count << 16)][items: 16-bit positions into d_fprims] (GridParams' offsets)
         int n_nodes = 0;                   // its size in 32-byte units (what LaunchParams::n_fnodes counts)
         int entries = 0;                   // list entries (rtgo_debug_grid)
         rtgo::GridParams gp = {};
         float reach_max = 0.0f;            // the pad of the binning covers the walk's rounding for rays that start within this reach
         bool have = false;
     } grid;
-    struct FastTree {                      // what build_kernel makes for one big_frac (see the fields of the same names below)
-        float4* d_fnodes = nullptr;
-        float4* d_fprims = nullptr;
-        int fast_depth = 0, n_small = 0, n_fnodes = 0, cuboid_groups = 0, tree_spheres = 0, list_cub = 0, n_big_pairs = 0;
-        float cub_a = 0.0f, cub_b = 0.0f;
-    } alt;                                 // the second structure (15 %); the first one lives in the fields below
-    bool have_alt = false;                 // false: the two builds came out the same, or RTGO_BIG_PERCENT pins one
-    int* d_meta_alt = nullptr;
+    struct FastTree {                      // what build_kernel makes for one big_frac
+        float4* d_fnodes = nullptr;        // collapsed LBVH of the fast walk
+        float4* d_fprims = nullptr;        // Morton-ordered traversal records of the fast walk
+        int fast_depth = 0, n_small = 0, n_fnodes = 0;   // its depth, primitives (the rest are tested up front) and nodes
+        int cuboid_groups = 0;             // certified groups in the scene (leaves + the list's)
+        int tree_spheres = 0;              // every primitive of the tree is a sphere
+        int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
+        float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
+        bool sane(uint32_t n) const { return n_fnodes >= 0 && n_fnodes <= 2 * (int)n - 1 && !(n_small > 0 && n_fnodes < 1); }
+    } tree[2];                             // the structures of 36 % and 15 %
+    bool have_alt = false;                 // tree[1] is a candidate: false when the two builds came out the same, or RTGO_BIG_PERCENT pins one
     // scene
     uint32_t n_prims = 0;
     PrimIn* d_prims_in = nullptr;
     float* d_aabb = nullptr;
     float4* d_nodes = nullptr;
     float4* d_prims = nullptr;
-    float4* d_fnodes = nullptr;   // collapsed LBVH of the fast walk
-    float4* d_fprims = nullptr;   // Morton-ordered traversal records of the fast walk
     float4* d_frames = nullptr;   // shading frames of the flat primitives (2 float4 per primitive, SBT order)
-    int* d_meta = nullptr;
+    int* d_meta = nullptr;        // build_kernel's meta words (one build at a time)
     int lbvh_depth = 0;
-    int fast_depth = 0;
-    int n_small = 0;
-    int n_fnodes = 0;             // nodes of the fast walk's tree
-    int cuboid_groups = 0;        // certified groups in the scene (leaves + the list's)
-    int tree_spheres = 0;         // every primitive of the fast walk's tree is a sphere
-    int list_cub = 0;             // the up-front list starts with a certified box (1) / room (2): cuboid_range
-    float cub_a = 0.0f, cub_b = 0.0f;   // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
-    int n_big_pairs = 0;
     float bounds[6] = {0, 0, 0, 0, 0, 0};  // tight world bounds of the scene (min xyz, max xyz)
     // far-field guard (rtgo_launch): per sphere / cylinder its centre and smax / smin^2 of its model matrix' axis scales -- the
     // reported hit of a quadric seen from distance D lies up to ~2^-25 D^2 smax / smin^2 off its surface (b^2 - 4ac cancels)
-    struct Quadric {
-        float c[3], w;
-    };
+    struct Quadric { float c[3], w; };
     std::vector<Quadric> quadrics;
     float guard_reach = 0.0f, guard_quadric = 0.0f;   // of the last launch (rtgo_stats)
     float* d_tight = nullptr;              // the fast walk's box of every primitive (device), and its host copy
@@ -214,6 +205,13 @@ static int fail(rtgo_ctx* c, int code, const std::string& msg)
     return code;
 }
 
+template <class T>
+static void release(T*& d)
+{
+    (void)hipFree(d);
+    d = nullptr;
+}
+
 #define RTGO_HIP(ctx, call)                                                                                       \
     do {                                                                                                          \
         hipError_t e_ = (call);                                                                                   \
@@ -267,7 +265,8 @@ static inline uint32_t passes_of(uint32_t nn) { return (nn + (uint32_t)kSamplesP
 static constexpr float kGuardReach = 500.0f;
 static constexpr float kGuardQuadric = 8000.0f;
 
-// tuning knobs for experiments (results never depend on them)
+// Environment knobs for tests and experiments (no result depends on them; DESIGN.md, "Knobs"): each rtgo_set_scene and rtgo_launch
+// reads them afresh into a Knobs
 static float env_float(const char* name, float dflt)
 {
     const char* v = std::getenv(name);
@@ -280,47 +279,70 @@ static unsigned int env_uint(const char* name, unsigned int dflt)
     const long k = std::strtol(v, nullptr, 10);
     return k > 0 ? (unsigned int)k : dflt;
 }
+struct Knobs {
+    bool debug = std::getenv("RTGO_DEBUG") != nullptr;              // a line per scene and launch on stderr
+    bool no_frames = std::getenv("RTGO_NO_FRAMES") != nullptr;      // flat scenes compute N and the sampling tangent per hit
+    bool no_cuboid = std::getenv("RTGO_NO_CUBOID") != nullptr;      // the build certifies no cuboids
+    bool pin_big = std::getenv("RTGO_BIG_PERCENT") != nullptr;      // one fast-walk structure, of big_percent (else 36 % and 15 %)
+    unsigned int big_percent = env_uint("RTGO_BIG_PERCENT", 36);
+    unsigned int max_wpe = env_uint("RTGO_MAX_WPE", 0);             // cap of the waves-per-SIMD variant; 0: by the work
+    unsigned int grid_min = env_uint("RTGO_GRID_MIN", 64);          // no grid for fewer small primitives ...
+    float grid_max_dup = env_float("RTGO_GRID_MAX_DUP", 3.0f);      // ... or more list entries per primitive
+    float guard_quadric;                                            // RTGO_GUARD_QUADRIC: the far-field guard's threshold
+    int tree = -1, stream = -1;   // RTGO_TREE=0/1/2, RTGO_STREAM=0/1: pin the 36 % / 15 % tree / the grid, the lock-step / streaming loop
+    int leaf_budget = -1;         // RTGO_LEAF_BUDGET, -1: unset or out of range
+    int grid_dims[3] = {0, 0, 0}; // RTGO_GRID_DIMS=nx,ny,nz instead of the cost model's resolution
+    Knobs()
+    {
+        static const float quadric = env_float("RTGO_GUARD_QUADRIC", kGuardQuadric);   // (read once per process)
+        guard_quadric = quadric;
+        if (const char* v = std::getenv("RTGO_TREE")) tree = v[0] == '1' ? 1 : (v[0] == '2' ? 2 : 0);
+        if (const char* v = std::getenv("RTGO_STREAM")) stream = v[0] != '0' ? 1 : 0;
+        if (const char* v = std::getenv("RTGO_LEAF_BUDGET")) leaf_budget = std::atoi(v) >= 0 && std::atoi(v) <= 16 * kMaxPrims ? std::atoi(v) : -1;
+        int d[3];
+        if (const char* v = std::getenv("RTGO_GRID_DIMS"))
+            if (std::sscanf(v, "%d,%d,%d", &d[0], &d[1], &d[2]) == 3)
+                for (int a = 0; a < 3; ++a) grid_dims[a] = d[a] < 1 ? 1 : (d[a] > 32 ? 32 : d[a]);
+    }
+};
 
 // Window rectangle [wx0, wx1) x [wy0, wy1) that can contain geometry: the 8 corners of the scene's tight bounds through the
 // pinhole camera of the raygen program (d = dx*U + dy*V + W, kernel.cu:214-220; a sample of pixel (x, y) has dx, dy inside
 // that pixel's square).  Conservative: padded by two pixels, and the whole window whenever a corner is not in front of the
 // eye.  The kernel traces nothing for pixels outside it (their primary rays cannot reach the bounds: they are misses).
-static void box_screen_rect(const float* bounds, const LaunchParams& p, uint32_t& wx0, uint32_t& wx1, uint32_t& wy0, uint32_t& wy1)
+struct Rect { uint32_t x0, x1, y0, y1; };
+static Rect box_screen_rect(const float* bounds, const LaunchParams& p)
 {
-    wx0 = 0;
-    wy0 = 0;
-    wx1 = p.w;
-    wy1 = p.h;
+    const Rect whole = {0, p.w, 0, p.h};
     const double uu = (double)p.U.x * p.U.x + (double)p.U.y * p.U.y + (double)p.U.z * p.U.z;
     const double vv = (double)p.V.x * p.V.x + (double)p.V.y * p.V.y + (double)p.V.z * p.V.z;
     const double ww = (double)p.Wv.x * p.Wv.x + (double)p.Wv.y * p.Wv.y + (double)p.Wv.z * p.Wv.z;
-    if (!(uu > 0 && vv > 0 && ww > 0)) return;
+    if (!(uu > 0 && vv > 0 && ww > 0)) return whole;
     // the three axes must be orthogonal for the projection below (they are for every Camera: Camera.cpp:55-69); else: no culling
     const double uv = (double)p.U.x * p.V.x + (double)p.U.y * p.V.y + (double)p.U.z * p.V.z;
     const double uw = (double)p.U.x * p.Wv.x + (double)p.U.y * p.Wv.y + (double)p.U.z * p.Wv.z;
     const double vw = (double)p.V.x * p.Wv.x + (double)p.V.y * p.Wv.y + (double)p.V.z * p.Wv.z;
     const double tol = 1e-5;
-    if (uv * uv > tol * tol * uu * vv || uw * uw > tol * tol * uu * ww || vw * vw > tol * tol * vv * ww) return;
+    if (uv * uv > tol * tol * uu * vv || uw * uw > tol * tol * uu * ww || vw * vw > tol * tol * vv * ww) return whole;
     double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
     for (int k = 0; k < 8; ++k) {
         const double px = bounds[(k & 1) ? 3 : 0] - p.eye.x, py = bounds[(k & 2) ? 4 : 1] - p.eye.y, pz = bounds[(k & 4) ? 5 : 2] - p.eye.z;
         const double a = (px * p.U.x + py * p.U.y + pz * p.U.z) / uu, b = (px * p.V.x + py * p.V.y + pz * p.V.z) / vv;
         const double w = (px * p.Wv.x + py * p.Wv.y + pz * p.Wv.z) / ww;
-        if (!(w > 1e-3)) return;  // a corner beside or behind the eye: no useful rectangle
+        if (!(w > 1e-3)) return whole;  // a corner beside or behind the eye: no useful rectangle
         const double sx = (a / w + 1.0) * 0.5 * p.W, sy = (b / w + 1.0) * 0.5 * p.H;
         x0 = sx < x0 ? sx : x0;
         x1 = sx > x1 ? sx : x1;
         y0 = sy < y0 ? sy : y0;
         y1 = sy > y1 ? sy : y1;
     }
-    if (!(x0 <= x1 && y0 <= y1)) return;   // NaN bounds
+    if (!(x0 <= x1 && y0 <= y1)) return whole;   // NaN bounds
     // to window pixels, padded, clamped
     auto clampd = [](double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    wx0 = (uint32_t)clampd(x0 - 2.0 - p.x0, 0.0, p.w);
-    wx1 = (uint32_t)clampd(x1 + 3.0 - p.x0, 0.0, p.w);
-    wy0 = (uint32_t)clampd(y0 - 2.0 - p.y0, 0.0, p.h);
-    wy1 = (uint32_t)clampd(y1 + 3.0 - p.y0, 0.0, p.h);
-    if (wx1 <= wx0 || wy1 <= wy0) wx0 = wx1 = wy0 = wy1 = 0;   // the scene is off screen
+    Rect r = {(uint32_t)clampd(x0 - 2.0 - p.x0, 0.0, p.w), (uint32_t)clampd(x1 + 3.0 - p.x0, 0.0, p.w),
+              (uint32_t)clampd(y0 - 2.0 - p.y0, 0.0, p.h), (uint32_t)clampd(y1 + 3.0 - p.y0, 0.0, p.h)};
+    if (r.x1 <= r.x0 || r.y1 <= r.y0) r = Rect{0, 0, 0, 0};   // the scene is off screen
+    return r;
 }
 
 extern "C" {
@@ -440,51 +462,80 @@ int rtgo_create(int device, rtgo_ctx** out)
     return RTGO_OK;
 }
 
+// the scene's device buffers: both fast-walk structures, the grid, the canonical LBVH, boxes and frames (rtgo_set_scene, rtgo_destroy)
+static void free_scene(rtgo_ctx* c)
+{
+    for (rtgo_ctx::FastTree& t : c->tree) {
+        release(t.d_fnodes);
+        release(t.d_fprims);
+        t = rtgo_ctx::FastTree();
+    }
+    c->have_alt = false;
+    release(c->grid.d);
+    c->grid = rtgo_ctx::Grid();
+    release(c->d_prims_in);
+    release(c->d_aabb);
+    release(c->d_nodes);
+    release(c->d_prims);
+    release(c->d_frames);
+    release(c->d_tight);
+    c->n_prims = 0;
+}
+
+// the output buffers, when the context owns them (rtgo_resize, rtgo_bind_output, rtgo_destroy)
+static void free_output(rtgo_ctx* c)
+{
+    if (c->own_output) {
+        release(c->d_accum);
+        release(c->d_image);
+    }
+    c->d_accum = nullptr;
+    c->d_image = nullptr;
+    c->own_output = false;
+    c->pixels = 0;
+}
+
+// the whitted mesh's device buffers (rtgo_whitted_set_mesh, rtgo_destroy; the lights and tile-queue heads outlive a mesh)
+static void free_mesh(rtgo_ctx* c)
+{
+    release(c->w_positions);
+    release(c->w_normals);
+    release(c->w_indices);
+    release(c->w_tri_material);
+    release(c->w_materials);
+    release(c->w_texcoords);
+    release(c->w_mat_tex);
+    for (void* t : c->w_texels) (void)hipFree(t);
+    c->w_texels.clear();
+    c->w_mat_tex_host.clear();
+    release(c->w_nodes);
+    release(c->w_recs);
+    release(c->w_tris);
+    release(c->w_qrecs);
+    release(c->w_tidx);
+    release(c->w_scratch);
+    c->w_triangles = 0;
+}
+
 int rtgo_destroy(rtgo_ctx* c)
 {
     if (!c) return RTGO_OK;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    (void)hipFree(c->d_prims_in);
-    (void)hipFree(c->d_aabb);
-    (void)hipFree(c->d_nodes);
-    (void)hipFree(c->d_prims);
-    (void)hipFree(c->d_fnodes);
-    (void)hipFree(c->d_fprims);
-    (void)hipFree(c->alt.d_fnodes);
-    (void)hipFree(c->alt.d_fprims);
-    (void)hipFree(c->d_meta_alt);
-    (void)hipFree(c->d_frames);
+    free_scene(c);
     (void)hipFree(c->d_meta);
     (void)hipFree(c->d_lights);
-    if (c->own_output) {
-        (void)hipFree(c->d_accum);
-        (void)hipFree(c->d_image);
-    }
+    free_output(c);
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_counters);
-    (void)hipFree(c->d_tight);
     (void)hipFree(c->d_mask);
     for (int k = 0; k < 2; ++k) {
         if (c->h_mask[k]) (void)hipHostFree(c->h_mask[k]);
         if (c->mask_copied[k]) (void)hipEventDestroy(c->mask_copied[k]);
     }
-    (void)hipFree(c->w_positions);
-    (void)hipFree(c->w_normals);
-    (void)hipFree(c->w_indices);
-    (void)hipFree(c->w_tri_material);
-    (void)hipFree(c->w_materials);
-    (void)hipFree(c->w_texcoords);
-    (void)hipFree(c->w_mat_tex);
-    for (void* t : c->w_texels) (void)hipFree(t);
+    free_mesh(c);
     (void)hipFree(c->w_lights);
     (void)hipFree(c->w_tile_counters);
-    (void)hipFree(c->w_nodes);
-    (void)hipFree(c->w_recs);
-    (void)hipFree(c->w_tris);
-    (void)hipFree(c->w_qrecs);
-    (void)hipFree(c->w_tidx);
-    (void)hipFree(c->w_scratch);
     for (int i = 0; i < rtgo_ctx::kEvRing; ++i) {
         if (c->ev_start[i]) (void)hipEventDestroy(c->ev_start[i]);
         if (c->ev_stop[i]) (void)hipEventDestroy(c->ev_stop[i]);
@@ -510,13 +561,13 @@ int rtgo_set_stream(rtgo_ctx* c, void* hip_stream)
 // late: the walk's own rounding (entry point, 96 accumulated steps: <= ~2e-5 of the rays' reach) stays an order of magnitude inside.
 // Cells: <= 32 per axis; table, cell records and lists within 40 KB of LDS; no grid for fewer than 64 small primitives (RTGO_GRID_MIN) or when
 // every resolution with at least half as many cells as primitives lists more than 3 entries per primitive (RTGO_GRID_MAX_DUP; a few big shapes among small ones: the tree's job).
-static int build_grid(rtgo_ctx* c, uint32_t n)
+static int build_grid(rtgo_ctx* c, uint32_t n, const Knobs& kn)
 {
     c->grid.have = false;
-    const int ns = c->n_small;
-    if (ns < (int)env_uint("RTGO_GRID_MIN", 64) || std::getenv("RTGO_NO_GRID")) return RTGO_OK;
+    const int ns = c->tree[0].n_small;
+    if (ns < (int)kn.grid_min) return RTGO_OK;
     std::vector<float4> fp((size_t)n * 4);
-    RTGO_HIP(c, hipMemcpyAsync(fp.data(), c->d_fprims, fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(fp.data(), c->tree[0].d_fprims, fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     std::vector<const float*> box((size_t)ns);
     float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f}, scene_reach = 0.0f;
@@ -543,7 +594,8 @@ static int build_grid(rtgo_ctx* c, uint32_t n)
     // up to 32 per axis, with the entries counted exactly (a primitive's span of cells is separable per axis).  The entries term is what
     // matters: a resolution that cuts through the shapes lists them two to eight times (balls, profiles/r03r: 16 x 4 x 16, one sphere per
     // column, 321 entries, 10.1 ms; 13 x 6 x 13, 754 entries, 13.8 ms; 32 x 1 x 32, 1024 entries, 19.1 ms; the tree 13.5).  kTest: 1.7 fitted there; 1.0 since the walk tests a cell's box before its list (16 x 3 x 16, 9.7 ms).
-    const float kTest = env_float("RTGO_GRID_KTEST", 1.0f), max_dup = env_float("RTGO_GRID_MAX_DUP", 3.0f);
+    constexpr float kTest = 1.0f;
+    const float max_dup = kn.grid_max_dup;
     const float pad0 = 2e-3f * (max_ext / 8.0f) + 1e-4f * reach_max;   // (the pad of the binning below depends on the cell size: close enough for counting)
     std::vector<uint8_t> span[3];
     for (int a = 0; a < 3; ++a) {
@@ -583,11 +635,8 @@ static int build_grid(rtgo_ctx* c, uint32_t n)
             }
         }
     if (best_cost >= 1e300) return RTGO_OK;
-    if (const char* want = std::getenv("RTGO_GRID_DIMS")) {   // "nx,ny,nz": experiments
-        int d[3];
-        if (std::sscanf(want, "%d,%d,%d", &d[0], &d[1], &d[2]) == 3)
-            for (int a = 0; a < 3; ++a) dim[a] = d[a] < 1 ? 1 : (d[a] > 32 ? 32 : d[a]);
-    }
+    if (kn.grid_dims[0])   // (experiments)
+        for (int a = 0; a < 3; ++a) dim[a] = kn.grid_dims[a];
     rtgo::GridParams g = {};
     float max_cs = 0.0f;
     for (int a = 0; a < 3; ++a) max_cs = std::fmax(max_cs, ext[a] / (float)dim[a]);
@@ -675,9 +724,32 @@ static int build_grid(rtgo_ctx* c, uint32_t n)
     c->grid.gp = g;
     c->grid.reach_max = reach_max;
     c->grid.have = true;
-    if (std::getenv("RTGO_DEBUG"))
+    if (kn.debug)
         std::fprintf(stderr, "rtgo_set_scene: grid %d x %d x %d over %d primitives, %zu list entries, %zu bytes, pad %g, for rays within %g\n", dim[0], dim[1], dim[2], ns,
                      total, bytes, pad, reach_max);
+    return RTGO_OK;
+}
+
+// build_kernel for one big_frac into a structure of its own (the canonical LBVH, boxes and frames it also writes are the same for every
+// big_frac), and its 15 meta words decoded
+static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_frac, const Knobs& kn, rtgo_ctx::FastTree& t, int meta[15])
+{
+    RTGO_HIP(c, hipMalloc(&t.d_fnodes, (2 * n - 1) * 2 * sizeof(float4)));
+    RTGO_HIP(c, hipMalloc(&t.d_fprims, n * 4 * sizeof(float4)));
+    hipLaunchKernelGGL(build_kernel, dim3(1), dim3(kMaxPrims), kBuildDynLds, c->stream, c->d_prims_in, c->d_aabb, have_aabbs, (int)n,
+                       c->d_nodes, c->d_prims, t.d_fnodes, t.d_fprims, c->leaf_budget, big_frac, c->d_meta, c->d_tight, kn.no_cuboid ? 0 : 1, c->d_frames);
+    RTGO_HIP(c, hipGetLastError());
+    RTGO_HIP(c, hipMemcpyAsync(meta, c->d_meta, 15 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    t.fast_depth = meta[1];
+    t.n_small = meta[2];
+    t.n_big_pairs = meta[9] & 0xFF;
+    t.list_cub = meta[9] >> 8;
+    t.cuboid_groups = meta[13] + (t.list_cub ? 1 : 0);
+    t.tree_spheres = (t.n_small > 0 && meta[14] == (1 << 3)) ? 1 : 0;   // (type 3 = sphere)
+    std::memcpy(&t.cub_a, &meta[11], sizeof(float));
+    std::memcpy(&t.cub_b, &meta[12], sizeof(float));
+    t.n_fnodes = meta[10];
     return RTGO_OK;
 }
 
@@ -704,100 +776,44 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
                 return fail(c, RTGO_E_INVALID, "rtgo_set_scene: box " + std::to_string(i) + " is empty or not finite");
         }
     }
+    const Knobs kn;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_prims_in);
-    (void)hipFree(c->d_aabb);
-    (void)hipFree(c->d_nodes);
-    (void)hipFree(c->d_prims);
-    (void)hipFree(c->d_fnodes);
-    (void)hipFree(c->d_fprims);
-    (void)hipFree(c->alt.d_fnodes);
-    (void)hipFree(c->alt.d_fprims);
-    c->alt = rtgo_ctx::FastTree();
-    c->have_alt = false;
-    (void)hipFree(c->grid.d);
-    c->grid = rtgo_ctx::Grid();
-    (void)hipFree(c->d_frames);
-    (void)hipFree(c->d_tight);
-    c->d_frames = nullptr;
-    c->d_tight = nullptr;
+    free_scene(c);
     c->mask_key.clear();
     c->trial = rtgo_ctx::Trial();
-    c->d_fnodes = nullptr;
-    c->d_fprims = nullptr;
-    c->d_prims_in = nullptr;
-    c->d_aabb = nullptr;
-    c->d_nodes = nullptr;
-    c->d_prims = nullptr;
-    c->n_prims = 0;
     RTGO_HIP(c, hipMalloc(&c->d_prims_in, n * sizeof(PrimIn)));
     RTGO_HIP(c, hipMalloc(&c->d_aabb, n * 6 * sizeof(float)));
     RTGO_HIP(c, hipMalloc(&c->d_nodes, (2 * n - 1) * 2 * sizeof(float4)));
     RTGO_HIP(c, hipMalloc(&c->d_prims, n * 6 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_fnodes, (2 * n - 1) * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_fprims, n * 4 * sizeof(float4)));
     RTGO_HIP(c, hipMalloc(&c->d_frames, n * 2 * sizeof(float4)));
     RTGO_HIP(c, hipMalloc(&c->d_tight, n * 6 * sizeof(float)));
-    if (const char* k = std::getenv("RTGO_LEAF_BUDGET")) {  // tuning knob for experiments; results do not depend on it
-        const int v = std::atoi(k);
-        if (v >= 0 && v <= 16 * kMaxPrims) c->leaf_budget = v;
-    }
+    if (kn.leaf_budget >= 0) c->leaf_budget = kn.leaf_budget;
     RTGO_HIP(c, hipMemcpyAsync(c->d_prims_in, prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
     if (aabbs) RTGO_HIP(c, hipMemcpyAsync(c->d_aabb, aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(build_kernel, dim3(1), dim3(kMaxPrims), kBuildDynLds, c->stream, c->d_prims_in, c->d_aabb, aabbs ? 1 : 0, (int)n,
-                       c->d_nodes, c->d_prims, c->d_fnodes, c->d_fprims, c->leaf_budget,
-                       (float)env_uint("RTGO_BIG_PERCENT", 36) * 0.01f, c->d_meta, c->d_tight, std::getenv("RTGO_NO_CUBOID") ? 0 : 1, c->d_frames);
-    RTGO_HIP(c, hipGetLastError());
-    int meta[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    RTGO_HIP(c, hipMemcpyAsync(meta, c->d_meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
+    int meta[15];
+    if (const int rc = build_fast_tree(c, n, aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, c->tree[0], meta)) return rc;
     c->tight.assign((size_t)n * 6, 0.0f);
     RTGO_HIP(c, hipMemcpyAsync(c->tight.data(), c->d_tight, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    const rtgo_ctx::FastTree& t0 = c->tree[0];
     const int depth = meta[0];
     c->lbvh_depth = depth;
-    c->fast_depth = meta[1];
-    c->n_small = meta[2];
-    c->n_big_pairs = meta[9] & 0xFF;
-    c->list_cub = meta[9] >> 8;
-    c->cuboid_groups = meta[13] + (c->list_cub ? 1 : 0);
-    c->tree_spheres = (c->n_small > 0 && meta[14] == (1 << 3) && !std::getenv("RTGO_NO_SPHERE_LEAVES")) ? 1 : 0;   // (type 3 = sphere)
-    std::memcpy(&c->cub_a, &meta[11], sizeof(float));
-    std::memcpy(&c->cub_b, &meta[12], sizeof(float));
-    c->n_fnodes = meta[10];
-    if (c->n_fnodes < 0 || c->n_fnodes > 2 * (int)n - 1 || (c->n_small > 0 && c->n_fnodes < 1))
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: the fast walk's tree has " + std::to_string(c->n_fnodes) + " nodes");
+    if (!t0.sane(n)) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: the fast walk's tree has " + std::to_string(t0.n_fnodes) + " nodes");
     std::memcpy(c->bounds, &meta[3], sizeof c->bounds);
-    if (!std::getenv("RTGO_BIG_PERCENT") && !std::getenv("RTGO_ONE_TREE")) {
+    if (!kn.pin_big) {
         // the alternative structure: big_frac 15 % (the canonical outputs, boxes and frames are rewritten with the same values)
-        RTGO_HIP(c, hipMalloc(&c->alt.d_fnodes, (2 * n - 1) * 2 * sizeof(float4)));
-        RTGO_HIP(c, hipMalloc(&c->alt.d_fprims, n * 4 * sizeof(float4)));
-        if (!c->d_meta_alt) RTGO_HIP(c, hipMalloc(&c->d_meta_alt, 16 * sizeof(int)));
-        hipLaunchKernelGGL(build_kernel, dim3(1), dim3(kMaxPrims), kBuildDynLds, c->stream, c->d_prims_in, c->d_aabb, 1, (int)n,
-                           c->d_nodes, c->d_prims, c->alt.d_fnodes, c->alt.d_fprims, c->leaf_budget, 0.15f, c->d_meta_alt, c->d_tight,
-                           std::getenv("RTGO_NO_CUBOID") ? 0 : 1, c->d_frames);
-        RTGO_HIP(c, hipGetLastError());
-        int m2[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        RTGO_HIP(c, hipMemcpyAsync(m2, c->d_meta_alt, sizeof m2, hipMemcpyDeviceToHost, c->stream));
-        RTGO_HIP(c, hipStreamSynchronize(c->stream));
-        rtgo_ctx::FastTree& a = c->alt;
-        a.fast_depth = m2[1];
-        a.n_small = m2[2];
-        a.n_big_pairs = m2[9] & 0xFF;
-        a.list_cub = m2[9] >> 8;
-        a.cuboid_groups = m2[13] + (a.list_cub ? 1 : 0);
-        a.tree_spheres = (a.n_small > 0 && m2[14] == (1 << 3) && !std::getenv("RTGO_NO_SPHERE_LEAVES")) ? 1 : 0;
-        std::memcpy(&a.cub_a, &m2[11], sizeof(float));
-        std::memcpy(&a.cub_b, &m2[12], sizeof(float));
-        a.n_fnodes = m2[10];
-        const bool sane = m2[0] == meta[0] && a.n_fnodes >= 0 && a.n_fnodes <= 2 * (int)n - 1 && !(a.n_small > 0 && a.n_fnodes < 1);
+        int m2[15];
+        if (const int rc = build_fast_tree(c, n, 1, 0.15f, kn, c->tree[1], m2)) return rc;
+        const rtgo_ctx::FastTree& t1 = c->tree[1];
         // (the same split of primitives = the same structure: nothing to try)
-        c->have_alt = sane && !(a.n_small == c->n_small && a.n_fnodes == c->n_fnodes && a.n_big_pairs == c->n_big_pairs && a.list_cub == c->list_cub);
+        c->have_alt = m2[0] == meta[0] && t1.sane(n) &&
+                      !(t1.n_small == t0.n_small && t1.n_fnodes == t0.n_fnodes && t1.n_big_pairs == t0.n_big_pairs && t1.list_cub == t0.list_cub);
     }
-    if (const int rc = build_grid(c, n)) return rc;
-    if (std::getenv("RTGO_DEBUG"))
+    if (const int rc = build_grid(c, n, kn)) return rc;
+    if (kn.debug)
         std::fprintf(stderr, "rtgo_set_scene: %d primitives, %d in the fast walk's tree (%d nodes, depth %d), %d up front (%d pairs, cuboid certificate %d), %d cuboid leaves, margin coefficients %g %g, canonical LBVH depth %d\n",
-                     (int)n, c->n_small, c->n_fnodes, c->fast_depth, (int)n - c->n_small, c->n_big_pairs, c->list_cub, meta[13], c->cub_a, c->cub_b, depth);
+                     (int)n, t0.n_small, t0.n_fnodes, t0.fast_depth, (int)n - t0.n_small, t0.n_big_pairs, t0.list_cub, meta[13], t0.cub_a, t0.cub_b, depth);
     if (depth > kStackDepth)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
                                                std::to_string(kStackDepth) + ")");
@@ -858,14 +874,7 @@ int rtgo_resize(rtgo_ctx* c, size_t pixels)
     if (!c || pixels == 0) return fail(c, RTGO_E_INVALID, "rtgo_resize: bad argument");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->own_output) {
-        (void)hipFree(c->d_accum);
-        (void)hipFree(c->d_image);
-    }
-    c->d_accum = nullptr;
-    c->d_image = nullptr;
-    c->own_output = false;
-    c->pixels = 0;
+    free_output(c);
     RTGO_HIP(c, hipMalloc(&c->d_accum, pixels * sizeof(float4)));
     RTGO_HIP(c, hipMalloc(&c->d_image, pixels * sizeof(uchar4)));
     RTGO_HIP(c, hipMemsetAsync(c->d_accum, 0, pixels * sizeof(float4), c->stream));
@@ -880,18 +889,15 @@ int rtgo_bind_output(rtgo_ctx* c, void* d_accum, void* d_image, size_t pixels)
     if (!c || !d_accum || !d_image || pixels == 0) return fail(c, RTGO_E_INVALID, "rtgo_bind_output: bad argument");
     if (((uintptr_t)d_accum & 15u) || ((uintptr_t)d_image & 3u))
         return fail(c, RTGO_E_INVALID, "rtgo_bind_output: accum must be 16-byte aligned, image 4-byte aligned");
-    if (c->own_output) {
-        (void)hipFree(c->d_accum);
-        (void)hipFree(c->d_image);
-    }
+    free_output(c);
     c->d_accum = (float4*)d_accum;
     c->d_image = (uchar4*)d_image;
-    c->own_output = false;
     c->pixels = pixels;
     return RTGO_OK;
 }
 
-int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
+// The frame's checks, its window and bands, what it binds (outputs, lights, queues) and the value of a pixel whose samples all miss
+static int frame_params(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p)
 {
     if (!c || !f) return fail(c, RTGO_E_INVALID, "rtgo_launch: NULL argument");
     if (c->n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_launch: no scene (call rtgo_set_scene)");
@@ -903,7 +909,6 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: max_trace_depth must be in [0, 5] (reference uses 5, renderer.cpp:616)");
     if (!f->path_tracing && c->n_lights < 1)
         return fail(c, RTGO_E_STATE, "rtgo_launch: distributed mode needs at least one surface light");
-    LaunchParams p;
     std::memset(&p, 0, sizeof p);
     p.W = f->image_width;
     p.H = f->image_height;
@@ -923,15 +928,7 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     p.V = c->V;
     p.Wv = c->W;
     p.bg = c->bg;
-    const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
-    bool frames = false;   // (set once the walk is chosen)
-    // scheduling: units of 64 paths = the N*N samples of `unit_px` neighbouring pixels of one row; the queue hands out STRIPS of
-    // `grab` units side by side (<= 64 pixels) from the rectangle that can contain geometry.  Strips are long when there is
-    // plenty of work (their pixel seeds are hashed once per strip) and short when units are scarce (small windows, one GPU's
-    // share of a tiled frame), so that every resident wave still gets >= ~32 turns
-    // (the last strips in flight set the tail of the launch: cornell 1080p spp 16 runs 6 % faster on 1-unit strips than on 4-unit ones).
     const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
-    const uint32_t unit_px = 64u / (nn < (uint32_t)kSamplesPerPass ? nn : (uint32_t)kSamplesPerPass);
     {
         // the same float additions, in the same order, as the kernel's in-order sum over samples that all miss (kernel.cu:232-237)
         volatile float sx = 0.0f, sy = 0.0f, sz = 0.0f;
@@ -943,277 +940,6 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
         const float inv = 1.0f / (float)nn;
         p.bg_pixel = v3{sx * inv, sy * inv, sz * inv};
     }
-    uint32_t wx0 = 0, wx1 = p.w, wy0 = 0, wy1 = p.h;
-    // collect_stats 1: the instrumented kernel traces every pixel (V, T, h over ALL rays, SURVEY 8d); 2: it culls like the timed
-    // kernel, so that the counters describe the traversed rays only
-    const bool cull = f->collect_stats != 1 && !std::getenv("RTGO_NO_CULL");
-    if (cull) box_screen_rect(c->bounds, p, wx0, wx1, wy0, wy1);
-    // The fast walk's tight boxes carry 1e-3 of padding against the rounding of the intersection programs, which grows with
-    // the coordinates involved (~1e-7 of them for a rectangle's hit point).  Beyond 500 units -- the reference's scenes stay
-    // within 20, its camera at 14 -- the launch takes the canonical walk instead: slower, and equal to it by definition.
-    bool canon = stats;
-    {
-        float reach = 0.0f;
-        for (int k = 0; k < 6; ++k) reach = std::fabs(c->bounds[k]) > reach ? std::fabs(c->bounds[k]) : reach;
-        const float e[3] = {p.eye.x, p.eye.y, p.eye.z};
-        for (int k = 0; k < 3; ++k) reach = std::fabs(e[k]) > reach ? std::fabs(e[k]) : reach;
-        // ... and a sphere's or cylinder's reported hit leaves its surface as the ray origin recedes: b^2 - 4ac cancels to the last
-        // bits of b^2 ~ D^2 / s^4, i.e. the hit lies up to ~2^-25 D^2 smax / smin^2 off the surface (D: origin to the primitive, s: its
-        // axis scales) -- outside the reference's own box when that exceeds AABB_EPSILON.  From there on no two traversals agree on
-        // grazing rays (the canonical LBVH culls such a hit by the primitive's box, a multi-primitive leaf's box lets it through, and
-        // OptiX promises neither), so what is bounded is Q = max over quadrics of D^2 smax / smin^2, D over the eye and the scene's
-        // tight bounds (where bounce rays start).  Thresholds: kGuardReach / kGuardQuadric, set from tools/fuzz_farfield.py's table
-        // (profiles/r03a) with the safety factors stated at their definition.
-        float quad = 0.0f;
-        for (const rtgo_ctx::Quadric& qd : c->quadrics) {
-            float d2 = 0.0f, e2 = 0.0f;
-            for (int k = 0; k < 3; ++k) {
-                const float lo = std::fabs(c->bounds[k] - qd.c[k]), hi = std::fabs(c->bounds[3 + k] - qd.c[k]);
-                const float far_k = lo > hi ? lo : hi;
-                d2 += far_k * far_k;
-                e2 += (e[k] - qd.c[k]) * (e[k] - qd.c[k]);
-            }
-            const float q2 = (d2 > e2 ? d2 : e2) * qd.w;
-            quad = q2 > quad ? q2 : quad;
-        }
-        c->guard_reach = reach;
-        c->guard_quadric = quad;
-        static const float guard_reach_max = env_float("RTGO_GUARD_REACH", kGuardReach), guard_quadric_max = env_float("RTGO_GUARD_QUADRIC", kGuardQuadric);
-        if (!(reach <= guard_reach_max) || !(quad <= guard_quadric_max)) canon = true;
-    }
-    // ---- which loop and which structure (rtgo_ctx::Trial).  More than 16 spp = several passes per pixel: the streaming variant
-    // (render_kernel, STREAM) lets a lane start its next sample when its path has ended instead of waiting for the wave's longest path,
-    // pass after pass; and where rtgo_set_scene's two builds differ, either structure can be the faster one.  Candidate k = loop (k & 1:
-    // 0 = streaming when there is a choice) | structure (k >> 1 when both loops are candidates, else k).
-    bool stream = false;
-    int structure = 0;   // 0 / 1: the trees of 36 % / 15 %, 2: the grid
-    unsigned char trial_tag = 0;
-    if (!canon) {
-        const bool multi_pass = passes_of(nn) > 1;
-        const char* force_loop = std::getenv("RTGO_STREAM");   // "0" / "1": experiment and test knobs, no trial over that dimension
-        const char* force_tree = std::getenv("RTGO_TREE");     // "0" / "1" / "2": the 36 % tree / the 15 % tree / the grid (when the scene has it)
-        // (the grid: where rtgo_set_scene built one, for rays that start within the reach its pad was sized for, and in the instantiations
-        // that exist -- not the flat-primitives one)
-        const bool flat_only = path && c->quadrics.empty() && !std::getenv("RTGO_NO_FRAMES");
-        const bool grid_ok = c->grid.have && c->guard_reach <= c->grid.reach_max && !flat_only;
-        int structs[3], n_structs = 0;
-        structs[n_structs++] = 0;
-        if (c->have_alt) structs[n_structs++] = 1;
-        if (grid_ok) structs[n_structs++] = 2;
-        if (force_tree) {
-            const int want = force_tree[0] - '0';
-            structure = 0;
-            for (int k = 0; k < n_structs; ++k)
-                if (structs[k] == want) structure = want;
-            n_structs = 1;
-            structs[0] = structure;
-        }
-        const bool loops = multi_pass && !force_loop;
-        if (multi_pass && force_loop) stream = force_loop[0] != '0';
-        const int n_loops = loops ? 2 : 1;
-        const int n_cand = n_loops * n_structs;
-        auto decode = [&](int k) {
-            if (loops) stream = (k % n_loops) == 0;
-            structure = structs[k / n_loops];
-        };
-        if (n_cand > 1) {
-            rtgo_ctx::Trial& t = c->trial;
-            const std::vector<uint32_t> key = {p.W, p.H, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, nn, (uint32_t)path, (uint32_t)f->max_trace_depth,
-                                               (uint32_t)(f->use_ambient != 0), (uint32_t)n_cand, (uint32_t)stream, (uint32_t)structure, (uint32_t)grid_ok};
-            if (key != t.key) {
-                // (event tags of an unfinished trial of the old key stay where they are: they are counted into the old minima nobody reads)
-                t = rtgo_ctx::Trial();
-                t.key = key;
-                t.n_cand = n_cand;
-                for (unsigned char& tag : c->ev_tag) tag = 0;
-            }
-            if (t.choice < 0 && t.issued >= 2 * n_cand) {
-                // all are in flight or done: WAIT for them.  A caller that enqueues a whole job without synchronising (bench.py's spin-up,
-                // a batch render) would otherwise run it to the end on whatever stands in for an undecided trial -- profiles/r03p caught
-                // 90 of 100 launches of C4 on its slowest candidate that way.  One stall of at most 2 * n_cand launches per job.
-                while (t.done < 2 * n_cand && c->ev_pending > 0) {
-                    const int rc = harvest_events(c, 1);
-                    if (rc) return rc;
-                }
-                if (t.done >= 2 * n_cand) {
-                    t.choice = 0;
-                    for (int k = 1; k < n_cand; ++k)
-                        if (t.best[k] < t.best[t.choice]) t.choice = k;
-                }
-            }
-            if (t.choice >= 0) decode(t.choice);
-            else if (t.issued < 2 * n_cand) {
-                const int k = t.issued % n_cand;
-                decode(k);
-                trial_tag = (unsigned char)(k + 1);
-                t.issued++;
-            } else decode(0);   // (the trial's events were lost to a key change: start over with the first candidate)
-        } else if (n_structs == 1) structure = structs[0];
-    }
-#ifdef RTGO_CMPWALK
-    if (canon)   // (diagnostic build: the instrumented launch also runs the pinned fast structure on every ray, rtgo_ray_trace.inc)
-        if (const char* want = std::getenv("RTGO_TREE")) {
-            if (want[0] == '1' && c->have_alt) structure = 1;
-            if (want[0] == '2' && c->grid.have && c->guard_reach <= c->grid.reach_max) structure = 2;
-        }
-#endif
-    const bool use_alt = structure == 1, use_grid = structure == 2;
-    // the structure this launch walks
-    const rtgo_ctx::FastTree ft = use_alt ? c->alt : [&] {
-        rtgo_ctx::FastTree m;
-        m.d_fnodes = c->d_fnodes; m.d_fprims = c->d_fprims; m.fast_depth = c->fast_depth; m.n_small = c->n_small; m.n_fnodes = c->n_fnodes;
-        m.cuboid_groups = c->cuboid_groups; m.tree_spheres = c->tree_spheres; m.list_cub = c->list_cub; m.n_big_pairs = c->n_big_pairs;
-        m.cub_a = c->cub_a; m.cub_b = c->cub_b;
-        return m;
-    }();
-    {
-        float reach = c->guard_reach;
-        // cuboid_range's margin, in the object-space y units of a face g: the certificate's tolerance plus the rounding of what is
-        // compared -- the reference's (u, v) on a face f, carried into y_g units by L_fg, and y_g(t_f) itself.  Each is a handful of
-        // float operations on terms no larger than |row| (|o| + t |d|) + |w| <= |row|_1 * 3 reach + |w| (origins within `reach`, hit
-        // points within the scene: t |d| <= 2 reach), i.e. <= 12 * 2^-24 of them; K = 64 * 2^-24 leaves five times that, and the
-        // build's A, B = max over (f, g) of L_fg |row_f|_1 + |row_g|_1 and of L_fg |w_f| + |w_g|.
-        p.cub_mu = kCuboidTol + 64.0f * 5.9604645e-8f * (ft.cub_a * 3.0f * reach + ft.cub_b);
-        p.list_cub = ft.list_cub;
-        p.tree_spheres = ft.tree_spheres;
-        if (!(p.cub_mu < 0.02f)) {   // (tiny faces far from the origin: the margin would let two faces through too often to pay)
-            p.list_cub = 0;
-            p.cub_mu = -1.0f;        // tree leaves: cuboid_range is not taken either (see render_kernel)
-        }
-    }
-    const uint32_t lr0 = owned_rows_below(wy0, p.band_h, p.n_ranks, p.rank), lr1 = owned_rows_below(wy1, p.band_h, p.n_ranks, p.rank);
-    const uint64_t units_hot = (uint64_t)((wx1 - wx0 + unit_px - 1) / unit_px) * (lr1 - lr0);
-    {
-        const uint64_t waves_guess = (uint64_t)c->num_cus * 16u;
-        uint32_t grab = (uint32_t)(units_hot / (waves_guess * 32u));
-        const uint32_t grab_cap = env_uint("RTGO_GRAB_MAX", (uint32_t)kUnitsPerGrab);
-        const uint32_t grab_max = (64u / unit_px) < grab_cap ? (64u / unit_px) : grab_cap;
-        const uint32_t grab_min = env_uint("RTGO_GRAB_MIN", 1u);   // (experiment knob)
-        grab = grab < grab_min ? grab_min : grab;
-        grab = grab < 1u ? 1u : (grab > grab_max ? grab_max : grab);
-        p.grab = grab;
-    }
-    const uint32_t strip_px = unit_px * p.grab;
-    p.hot_x0 = wx0 / strip_px;
-    p.hot_w = (wx1 + strip_px - 1) / strip_px - p.hot_x0;
-    p.hot_y0 = lr0;
-    p.hot_h = lr1 - lr0;
-    if (p.hot_w == 0 || p.hot_h == 0) p.hot_x0 = p.hot_y0 = p.hot_w = p.hot_h = 0;
-    if ((uint64_t)p.hot_w * p.hot_h > 0x7FFFFF00ull) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: window too large");
-    p.n_hot = p.hot_w * p.hot_h;
-    p.cold_x0 = p.hot_x0 * strip_px;
-    p.cold_x1 = (p.hot_x0 + p.hot_w) * strip_px < p.w ? (p.hot_x0 + p.hot_w) * strip_px : p.w;
-    p.rows_above = p.local_rows - p.hot_y0 - p.hot_h;
-    p.segs_full = (p.w + 63u) / 64u;
-    p.segs_l = p.n_hot ? (p.cold_x0 + 63u) / 64u : 0u;
-    p.segs_r = p.n_hot ? (p.w - p.cold_x1 + 63u) / 64u : 0u;
-    const uint64_t cold_segs = (uint64_t)(p.hot_y0 + p.rows_above) * p.segs_full + (uint64_t)p.hot_h * (p.segs_l + p.segs_r);
-    if (cold_segs > 0x7FFFFF00ull) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: window too large");
-    p.n_cold_segs = (uint32_t)cold_segs;
-    // cold chunks: about two per resident wave
-    p.cold_cs = (uint32_t)((cold_segs + (uint64_t)c->num_cus * 32u - 1) / ((uint64_t)c->num_cus * 32u));
-    if (p.cold_cs == 0) p.cold_cs = 1;
-    const uint32_t n_cold = (p.n_cold_segs + p.cold_cs - 1) / p.cold_cs;
-    p.n_tiles = p.n_hot + n_cold;
-    // Inside the rectangle, strip by strip: does any primitive's own screen rectangle (its box as the fast walk culls with it,
-    // through the same pinhole projection, padded) reach the strip?  Scenes that do not fill their rectangle -- plateau: a plate and
-    // a few objects -- have most of it empty.  The mask depends on the launch geometry only; it is rebuilt when that changes.
-    p.hot_mask = nullptr;
-    unsigned long long mask_cold_pixels = 0;
-    if (cull && p.n_hot > 0 && !std::getenv("RTGO_NO_MASK")) {
-        std::vector<uint32_t> key = {p.W, p.H, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, p.grab, strip_px, p.hot_x0, p.hot_y0, p.hot_w, p.hot_h};
-        const float cam[12] = {p.eye.x, p.eye.y, p.eye.z, p.U.x, p.U.y, p.U.z, p.V.x, p.V.y, p.V.z, p.Wv.x, p.Wv.y, p.Wv.z};
-        for (float v : cam) {
-            uint32_t bits;
-            std::memcpy(&bits, &v, 4);
-            key.push_back(bits);
-        }
-        const size_t words = ((size_t)p.n_hot + 31) / 32;
-        if (key != c->mask_key) {
-            std::vector<uint32_t> mask(words, 0u);
-            bool all_hot = false;
-            for (uint32_t i = 0; i < c->n_prims && !all_hot; ++i) {
-                uint32_t rx0, rx1, ry0, ry1;
-                box_screen_rect(&c->tight[6 * (size_t)i], p, rx0, rx1, ry0, ry1);
-                if (rx0 == 0 && rx1 == p.w && ry0 == 0 && ry1 == p.h) {   // a primitive whose rectangle is the whole window (or unknown)
-                    all_hot = true;
-                    break;
-                }
-                if (rx1 <= rx0 || ry1 <= ry0) continue;
-                const uint32_t sa = rx0 / strip_px, sb = (rx1 - 1) / strip_px;   // strip columns the rectangle touches
-                const uint32_t ca = sa > p.hot_x0 ? sa : p.hot_x0, cb = sb < p.hot_x0 + p.hot_w - 1 ? sb : p.hot_x0 + p.hot_w - 1;
-                if (ca > cb) continue;
-                for (uint32_t wrow = ry0; wrow < ry1; ++wrow) {
-                    if (p.n_ranks > 1 && (wrow / p.band_h) % p.n_ranks != p.rank) continue;
-                    const uint32_t lrow = owned_rows_below(wrow, p.band_h, p.n_ranks, p.rank);
-                    if (lrow < p.hot_y0 || lrow >= p.hot_y0 + p.hot_h) continue;
-                    const size_t base = (size_t)(lrow - p.hot_y0) * p.hot_w;
-                    for (uint32_t sc = ca; sc <= cb; ++sc) {
-                        const size_t bit = base + (sc - p.hot_x0);
-                        mask[bit >> 5] |= 1u << (bit & 31u);
-                    }
-                }
-            }
-            unsigned long long cold_px = 0;
-            if (!all_hot) {
-                size_t hot_bits = 0;
-                for (size_t b = 0; b < (size_t)p.n_hot; ++b) {
-                    if ((mask[b >> 5] >> (b & 31u)) & 1u) {
-                        ++hot_bits;
-                    } else {
-                        const uint32_t sc = p.hot_x0 + (uint32_t)(b % p.hot_w);
-                        const uint32_t xa = sc * strip_px, xb = xa + strip_px < p.w ? xa + strip_px : p.w;
-                        cold_px += xb > xa ? xb - xa : 0;
-                    }
-                }
-                all_hot = hot_bits == (size_t)p.n_hot;
-            }
-            if (!all_hot) {
-                if (words > c->mask_capacity) {
-                    (void)hipFree(c->d_mask);
-                    c->d_mask = nullptr;
-                    c->mask_capacity = 0;
-                    RTGO_HIP(c, hipMalloc(&c->d_mask, words * sizeof(uint32_t)));
-                    c->mask_capacity = words;
-                }
-                // (the previous launch may still be reading the old mask: stream order takes care of it.)  The copy leaves from pinned
-                // memory the context keeps, so nothing here waits for the stream; a slot is reused two rebuilds later, by when its copy
-                // has long completed (the event wait is a formality)
-                const int slot = c->mask_slot;
-                c->mask_slot = 1 - slot;
-                if (!c->mask_copied[slot]) RTGO_HIP(c, hipEventCreateWithFlags(&c->mask_copied[slot], hipEventDisableTiming));
-                else RTGO_HIP(c, hipEventSynchronize(c->mask_copied[slot]));
-                if (words > c->h_mask_capacity[slot]) {
-                    if (c->h_mask[slot]) (void)hipHostFree(c->h_mask[slot]);
-                    c->h_mask[slot] = nullptr;
-                    c->h_mask_capacity[slot] = 0;
-                    RTGO_HIP(c, hipHostMalloc((void**)&c->h_mask[slot], words * sizeof(uint32_t), hipHostMallocDefault));
-                    c->h_mask_capacity[slot] = words;
-                }
-                std::memcpy(c->h_mask[slot], mask.data(), words * sizeof(uint32_t));
-                RTGO_HIP(c, hipMemcpyAsync(c->d_mask, c->h_mask[slot], words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-                RTGO_HIP(c, hipEventRecord(c->mask_copied[slot], c->stream));
-            }
-            c->mask_all_hot = all_hot;
-            c->mask_cold_pixels = all_hot ? 0 : cold_px;
-            c->mask_key = key;
-        }
-        if (!c->mask_all_hot) {
-            p.hot_mask = c->d_mask;
-            mask_cold_pixels = c->mask_cold_pixels;
-        }
-    }
-    p.nodes = c->d_nodes;
-    p.prims = c->d_prims;
-    p.fnodes = use_grid ? (const float4*)c->grid.d : ft.d_fnodes;
-    p.n_fnodes = use_grid ? c->grid.n_nodes : ft.n_fnodes;
-    p.grid = rtgo::GridParams();
-    if (use_grid) p.grid = c->grid.gp;
-    p.fprims = ft.d_fprims;
-    p.frames = c->d_frames;
-    p.n_small = ft.n_small;
-    p.n_big_pairs = ft.n_big_pairs;
-    p.stack_depth = canon ? kStackDepth : ((ft.fast_depth > 0 && !use_grid) ? ft.fast_depth : 1) + 1;   // (+1: fast_tree writes the slot past the top before it knows whether it pushes)
     p.lights = c->d_lights;
     p.accum = c->d_accum;
     p.image = c->d_image;
@@ -1239,19 +965,298 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     p.max_depth = f->max_trace_depth;
     p.frame = f->frame_count;
     p.ambient = f->use_ambient ? 1 : 0;
-    p.count_stats = stats ? 1 : 0;
-    if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
+    p.count_stats = f->collect_stats ? 1 : 0;
+    return RTGO_OK;
+}
 
-    // LDS image of the chosen kernel (see render_kernel): canonical = nodes + 6/prim; fast = fnodes + 4/prim + 3/prim.
-    // The scene copy is per workgroup and the stack per lane, so bigger scenes want bigger workgroups: pick the size that
-    // puts the most waves on a CU (at most 16 = 4 per SIMD, what the kernel's VGPR budget admits), smallest size on ties.
+// The fast walk's tight boxes carry 1e-3 of padding against the rounding of the intersection programs, which grows with
+// the coordinates involved (~1e-7 of them for a rectangle's hit point).  Beyond 500 units -- the reference's scenes stay
+// within 20, its camera at 14 -- the launch takes the canonical walk instead: slower, and equal to it by definition.
+// Returns whether the launch is beyond the guard; records both quantities for rtgo_get_stats.
+static bool far_field_guard(rtgo_ctx* c, const LaunchParams& p, const Knobs& kn)
+{
+    float reach = 0.0f;
+    for (int k = 0; k < 6; ++k) reach = std::fabs(c->bounds[k]) > reach ? std::fabs(c->bounds[k]) : reach;
+    const float e[3] = {p.eye.x, p.eye.y, p.eye.z};
+    for (int k = 0; k < 3; ++k) reach = std::fabs(e[k]) > reach ? std::fabs(e[k]) : reach;
+    // ... and a sphere's or cylinder's reported hit leaves its surface as the ray origin recedes: b^2 - 4ac cancels to the last
+    // bits of b^2 ~ D^2 / s^4, i.e. the hit lies up to ~2^-25 D^2 smax / smin^2 off the surface (D: origin to the primitive, s: its
+    // axis scales) -- outside the reference's own box when that exceeds AABB_EPSILON.  From there on no two traversals agree on
+    // grazing rays (the canonical LBVH culls such a hit by the primitive's box, a multi-primitive leaf's box lets it through, and
+    // OptiX promises neither), so what is bounded is Q = max over quadrics of D^2 smax / smin^2, D over the eye and the scene's
+    // tight bounds (where bounce rays start).  Thresholds: kGuardReach / kGuardQuadric, set from tools/fuzz_farfield.py's table
+    // (profiles/r03a) with the safety factors stated at their definition.
+    float quad = 0.0f;
+    for (const rtgo_ctx::Quadric& qd : c->quadrics) {
+        float d2 = 0.0f, e2 = 0.0f;
+        for (int k = 0; k < 3; ++k) {
+            const float lo = std::fabs(c->bounds[k] - qd.c[k]), hi = std::fabs(c->bounds[3 + k] - qd.c[k]);
+            const float far_k = lo > hi ? lo : hi;
+            d2 += far_k * far_k;
+            e2 += (e[k] - qd.c[k]) * (e[k] - qd.c[k]);
+        }
+        const float q2 = (d2 > e2 ? d2 : e2) * qd.w;
+        quad = q2 > quad ? q2 : quad;
+    }
+    c->guard_reach = reach;
+    c->guard_quadric = quad;
+    return !(reach <= kGuardReach) || !(quad <= kn.guard_quadric);
+}
+
+// What choose_candidate decided.  The trial's part of it (a new key, the choice, the timed launch) is committed by enqueue once the
+// kernel is in the stream, so that a launch that fails before that leaves the trial as it was.
+struct Pick {
+    bool stream = false;
+    int structure = 0;              // 0 / 1: the trees of 36 % / 15 %, 2: the grid
+    int trial_k = -1, choice = -1;  // the candidate this launch times (-1: none); the trial's winner, once decided
+    int n_cand = 1;
+    std::vector<uint32_t> new_key;  // non-empty: this launch starts a new trial, for this key
+};
+
+// ---- which loop and which structure (rtgo_ctx::Trial).  More than 16 spp = several passes per pixel: the streaming variant
+// (render_kernel, STREAM) lets a lane start its next sample when its path has ended instead of waiting for the wave's longest path,
+// pass after pass; and where rtgo_set_scene's two builds differ, either structure can be the faster one.  Candidate k = loop (k & 1:
+// 0 = streaming when there is a choice) | structure (k >> 1 when both loops are candidates, else k).
+static int choose_candidate(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, const Knobs& kn, bool canon, Pick& pk)
+{
+    if (canon) {
+#ifdef RTGO_CMPWALK
+        // (diagnostic build: the instrumented launch also runs the pinned fast structure on every ray, rtgo_ray_trace.inc)
+        if (kn.tree == 1 && c->have_alt) pk.structure = 1;
+        if (kn.tree == 2 && c->grid.have && c->guard_reach <= c->grid.reach_max) pk.structure = 2;
+#endif
+        return RTGO_OK;
+    }
+    const bool path = f->path_tracing != 0, multi_pass = passes_of(nn) > 1;
+    // (the grid: where rtgo_set_scene built one, for rays that start within the reach its pad was sized for, and in the instantiations
+    // that exist -- not the flat-primitives one)
+    const bool flat_only = path && c->quadrics.empty() && !kn.no_frames;
+    const bool grid_ok = c->grid.have && c->guard_reach <= c->grid.reach_max && !flat_only;
+    int structs[3], n_structs = 0;
+    structs[n_structs++] = 0;
+    if (c->have_alt) structs[n_structs++] = 1;
+    if (grid_ok) structs[n_structs++] = 2;
+    if (kn.tree >= 0) {   // (RTGO_TREE, RTGO_STREAM: experiment and test knobs, no trial over that dimension)
+        pk.structure = 0;
+        for (int k = 0; k < n_structs; ++k)
+            if (structs[k] == kn.tree) pk.structure = kn.tree;
+        n_structs = 1;
+        structs[0] = pk.structure;
+    }
+    const bool loops = multi_pass && kn.stream < 0;
+    if (multi_pass && kn.stream >= 0) pk.stream = kn.stream != 0;
+    const int n_loops = loops ? 2 : 1;
+    const int n_cand = n_loops * n_structs;
+    auto decode = [&](int k) {
+        if (loops) pk.stream = (k % n_loops) == 0;
+        pk.structure = structs[k / n_loops];
+    };
+    if (n_cand == 1) {
+        decode(0);
+        return RTGO_OK;
+    }
+    rtgo_ctx::Trial& t = c->trial;
+    std::vector<uint32_t> key = {p.W, p.H, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, nn, (uint32_t)path, (uint32_t)f->max_trace_depth,
+                                 (uint32_t)(f->use_ambient != 0), (uint32_t)n_cand, (uint32_t)pk.stream, (uint32_t)pk.structure, (uint32_t)grid_ok};
+    const bool fresh = key != t.key;
+    const int issued = fresh ? 0 : t.issued;
+    int choice = fresh ? -1 : t.choice;
+    pk.n_cand = n_cand;
+    if (fresh) pk.new_key = std::move(key);
+    else if (choice < 0 && issued >= 2 * n_cand) {
+        // all are in flight or done: WAIT for them.  A caller that enqueues a whole job without synchronising (bench.py's spin-up,
+        // a batch render) would otherwise run it to the end on whatever stands in for an undecided trial -- profiles/r03p caught
+        // 90 of 100 launches of C4 on its slowest candidate that way.  One stall of at most 2 * n_cand launches per job.
+        while (t.done < 2 * n_cand && c->ev_pending > 0)
+            if (const int rc = harvest_events(c, 1)) return rc;
+        if (t.done >= 2 * n_cand) {
+            choice = 0;
+            for (int k = 1; k < n_cand; ++k)
+                if (t.best[k] < t.best[choice]) choice = k;
+        }
+    }
+    pk.choice = choice;
+    if (choice >= 0) decode(choice);
+    else if (issued < 2 * n_cand) {
+        pk.trial_k = issued % n_cand;
+        decode(pk.trial_k);
+    } else decode(0);   // (the trial's events were lost to a key change: start over with the first candidate)
+    return RTGO_OK;
+}
+
+// what the walk reads: the canonical LBVH, and the chosen fast structure (`ft`, or the grid over ft's small primitives)
+static void walk_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool canon, bool use_grid, LaunchParams& p)
+{
+    // cuboid_range's margin, in the object-space y units of a face g: the certificate's tolerance plus the rounding of what is
+    // compared -- the reference's (u, v) on a face f, carried into y_g units by L_fg, and y_g(t_f) itself.  Each is a handful of
+    // float operations on terms no larger than |row| (|o| + t |d|) + |w| <= |row|_1 * 3 reach + |w| (origins within `reach`, hit
+    // points within the scene: t |d| <= 2 reach), i.e. <= 12 * 2^-24 of them; K = 64 * 2^-24 leaves five times that, and the
+    // build's A, B = max over (f, g) of L_fg |row_f|_1 + |row_g|_1 and of L_fg |w_f| + |w_g|.
+    p.cub_mu = kCuboidTol + 64.0f * 5.9604645e-8f * (ft.cub_a * 3.0f * c->guard_reach + ft.cub_b);
+    p.list_cub = ft.list_cub;
+    p.tree_spheres = ft.tree_spheres;
+    if (!(p.cub_mu < 0.02f)) {   // (tiny faces far from the origin: the margin would let two faces through too often to pay)
+        p.list_cub = 0;
+        p.cub_mu = -1.0f;        // tree leaves: cuboid_range is not taken either (see render_kernel)
+    }
+    p.nodes = c->d_nodes;
+    p.prims = c->d_prims;
+    p.fnodes = use_grid ? (const float4*)c->grid.d : ft.d_fnodes;
+    p.n_fnodes = use_grid ? c->grid.n_nodes : ft.n_fnodes;
+    p.grid = use_grid ? c->grid.gp : rtgo::GridParams();
+    p.fprims = ft.d_fprims;
+    p.frames = c->d_frames;
+    p.n_small = ft.n_small;
+    p.n_big_pairs = ft.n_big_pairs;
+    p.stack_depth = canon ? kStackDepth : ((ft.fast_depth > 0 && !use_grid) ? ft.fast_depth : 1) + 1;   // (+1: fast_tree writes the slot past the top before it knows whether it pushes)
+}
+
+// Scheduling: units of 64 paths = the N*N samples of `unit_px` neighbouring pixels of one row; the queue hands out STRIPS of
+// `grab` units side by side (<= 64 pixels) from the rectangle that can contain geometry.  Strips are long when there is
+// plenty of work (their pixel seeds are hashed once per strip) and short when units are scarce (small windows, one GPU's
+// share of a tiled frame), so that every resident wave still gets >= ~32 turns
+// (the last strips in flight set the tail of the launch: cornell 1080p spp 16 runs 6 % faster on 1-unit strips than on 4-unit ones).
+// The pixels outside the rectangle `r` are cold: 64-pixel row segments, handed out in chunks.
+static int schedule(rtgo_ctx* c, uint32_t nn, const Rect& r, LaunchParams& p, uint32_t& strip_px, uint64_t& units_hot)
+{
+    const uint32_t unit_px = 64u / (nn < (uint32_t)kSamplesPerPass ? nn : (uint32_t)kSamplesPerPass);
+    const uint32_t lr0 = owned_rows_below(r.y0, p.band_h, p.n_ranks, p.rank), lr1 = owned_rows_below(r.y1, p.band_h, p.n_ranks, p.rank);
+    units_hot = (uint64_t)((r.x1 - r.x0 + unit_px - 1) / unit_px) * (lr1 - lr0);
+    const uint64_t waves_guess = (uint64_t)c->num_cus * 16u;
+    const uint32_t grab = (uint32_t)(units_hot / (waves_guess * 32u));
+    const uint32_t grab_max = (64u / unit_px) < (uint32_t)kUnitsPerGrab ? (64u / unit_px) : (uint32_t)kUnitsPerGrab;
+    p.grab = grab < 1u ? 1u : (grab > grab_max ? grab_max : grab);
+    strip_px = unit_px * p.grab;
+    p.hot_x0 = r.x0 / strip_px;
+    p.hot_w = (r.x1 + strip_px - 1) / strip_px - p.hot_x0;
+    p.hot_y0 = lr0;
+    p.hot_h = lr1 - lr0;
+    if (p.hot_w == 0 || p.hot_h == 0) p.hot_x0 = p.hot_y0 = p.hot_w = p.hot_h = 0;
+    if ((uint64_t)p.hot_w * p.hot_h > 0x7FFFFF00ull) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: window too large");
+    p.n_hot = p.hot_w * p.hot_h;
+    p.cold_x0 = p.hot_x0 * strip_px;
+    p.cold_x1 = (p.hot_x0 + p.hot_w) * strip_px < p.w ? (p.hot_x0 + p.hot_w) * strip_px : p.w;
+    p.rows_above = p.local_rows - p.hot_y0 - p.hot_h;
+    p.segs_full = (p.w + 63u) / 64u;
+    p.segs_l = p.n_hot ? (p.cold_x0 + 63u) / 64u : 0u;
+    p.segs_r = p.n_hot ? (p.w - p.cold_x1 + 63u) / 64u : 0u;
+    const uint64_t cold_segs = (uint64_t)(p.hot_y0 + p.rows_above) * p.segs_full + (uint64_t)p.hot_h * (p.segs_l + p.segs_r);
+    if (cold_segs > 0x7FFFFF00ull) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: window too large");
+    p.n_cold_segs = (uint32_t)cold_segs;
+    // cold chunks: about two per resident wave
+    p.cold_cs = (uint32_t)((cold_segs + (uint64_t)c->num_cus * 32u - 1) / ((uint64_t)c->num_cus * 32u));
+    if (p.cold_cs == 0) p.cold_cs = 1;
+    const uint32_t n_cold = (p.n_cold_segs + p.cold_cs - 1) / p.cold_cs;
+    p.n_tiles = p.n_hot + n_cold;
+    return RTGO_OK;
+}
+
+// Inside the rectangle, strip by strip: does any primitive's own screen rectangle (its box as the fast walk culls with it,
+// through the same pinhole projection, padded) reach the strip?  Scenes that do not fill their rectangle -- plateau: a plate and
+// a few objects -- have most of it empty.  The mask depends on the launch geometry only; it is rebuilt when that changes.
+// Sets p.hot_mask unless every strip is hot; cold_pixels: the pixels of the masked strips.
+static int update_hot_mask(rtgo_ctx* c, uint32_t strip_px, LaunchParams& p, unsigned long long& cold_pixels)
+{
+    std::vector<uint32_t> key = {p.W, p.H, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, p.grab, strip_px, p.hot_x0, p.hot_y0, p.hot_w, p.hot_h};
+    const float cam[12] = {p.eye.x, p.eye.y, p.eye.z, p.U.x, p.U.y, p.U.z, p.V.x, p.V.y, p.V.z, p.Wv.x, p.Wv.y, p.Wv.z};
+    for (float v : cam) {
+        uint32_t bits;
+        std::memcpy(&bits, &v, 4);
+        key.push_back(bits);
+    }
+    const size_t words = ((size_t)p.n_hot + 31) / 32;
+    if (key != c->mask_key) {
+        std::vector<uint32_t> mask(words, 0u);
+        bool all_hot = false;
+        for (uint32_t i = 0; i < c->n_prims && !all_hot; ++i) {
+            const Rect q = box_screen_rect(&c->tight[6 * (size_t)i], p);
+            if (q.x0 == 0 && q.x1 == p.w && q.y0 == 0 && q.y1 == p.h) {   // a primitive whose rectangle is the whole window (or unknown)
+                all_hot = true;
+                break;
+            }
+            if (q.x1 <= q.x0 || q.y1 <= q.y0) continue;
+            const uint32_t sa = q.x0 / strip_px, sb = (q.x1 - 1) / strip_px;   // strip columns the rectangle touches
+            const uint32_t ca = sa > p.hot_x0 ? sa : p.hot_x0, cb = sb < p.hot_x0 + p.hot_w - 1 ? sb : p.hot_x0 + p.hot_w - 1;
+            if (ca > cb) continue;
+            for (uint32_t wrow = q.y0; wrow < q.y1; ++wrow) {
+                if (p.n_ranks > 1 && (wrow / p.band_h) % p.n_ranks != p.rank) continue;
+                const uint32_t lrow = owned_rows_below(wrow, p.band_h, p.n_ranks, p.rank);
+                if (lrow < p.hot_y0 || lrow >= p.hot_y0 + p.hot_h) continue;
+                const size_t base = (size_t)(lrow - p.hot_y0) * p.hot_w;
+                for (uint32_t sc = ca; sc <= cb; ++sc) {
+                    const size_t bit = base + (sc - p.hot_x0);
+                    mask[bit >> 5] |= 1u << (bit & 31u);
+                }
+            }
+        }
+        unsigned long long cold_px = 0;
+        if (!all_hot) {
+            size_t hot_bits = 0;
+            for (size_t b = 0; b < (size_t)p.n_hot; ++b) {
+                if ((mask[b >> 5] >> (b & 31u)) & 1u) {
+                    ++hot_bits;
+                } else {
+                    const uint32_t sc = p.hot_x0 + (uint32_t)(b % p.hot_w);
+                    const uint32_t xa = sc * strip_px, xb = xa + strip_px < p.w ? xa + strip_px : p.w;
+                    cold_px += xb > xa ? xb - xa : 0;
+                }
+            }
+            all_hot = hot_bits == (size_t)p.n_hot;
+        }
+        if (!all_hot) {
+            if (words > c->mask_capacity) {
+                release(c->d_mask);
+                c->mask_capacity = 0;
+                RTGO_HIP(c, hipMalloc(&c->d_mask, words * sizeof(uint32_t)));
+                c->mask_capacity = words;
+            }
+            // (the previous launch may still be reading the old mask: stream order takes care of it.)  The copy leaves from pinned
+            // memory the context keeps, so nothing here waits for the stream; a slot is reused two rebuilds later, by when its copy
+            // has long completed (the event wait is a formality)
+            const int slot = c->mask_slot;
+            c->mask_slot = 1 - slot;
+            if (!c->mask_copied[slot]) RTGO_HIP(c, hipEventCreateWithFlags(&c->mask_copied[slot], hipEventDisableTiming));
+            else RTGO_HIP(c, hipEventSynchronize(c->mask_copied[slot]));
+            if (words > c->h_mask_capacity[slot]) {
+                if (c->h_mask[slot]) (void)hipHostFree(c->h_mask[slot]);
+                c->h_mask[slot] = nullptr;
+                c->h_mask_capacity[slot] = 0;
+                RTGO_HIP(c, hipHostMalloc((void**)&c->h_mask[slot], words * sizeof(uint32_t), hipHostMallocDefault));
+                c->h_mask_capacity[slot] = words;
+            }
+            std::memcpy(c->h_mask[slot], mask.data(), words * sizeof(uint32_t));
+            RTGO_HIP(c, hipMemcpyAsync(c->d_mask, c->h_mask[slot], words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            RTGO_HIP(c, hipEventRecord(c->mask_copied[slot], c->stream));
+        }
+        c->mask_all_hot = all_hot;
+        c->mask_cold_pixels = all_hot ? 0 : cold_px;
+        c->mask_key = key;
+    }
+    if (!c->mask_all_hot) {
+        p.hot_mask = c->d_mask;
+        cold_pixels = c->mask_cold_pixels;
+    }
+    return RTGO_OK;
+}
+
+struct Block {
+    int block = 0, blocks_per_cu = 0, wpe = 4;   // threads per workgroup, workgroups per CU, waves per SIMD of the variant
+    size_t lds = 0;
+    unsigned int grid = 0;                       // workgroups
+};
+
+// LDS image of the chosen kernel (see render_kernel): canonical = nodes + 6/prim; fast = fnodes + 4/prim + 3/prim.
+// The scene copy is per workgroup and the stack per lane, so bigger scenes want bigger workgroups: pick the size that
+// puts the most waves on a CU (at most 16 = 4 per SIMD, what the kernel's VGPR budget admits), smallest size on ties.
+static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, bool canon, bool stream, bool frames,
+                      uint64_t units_hot, const Knobs& kn, Block& b)
+{
+    const bool path = f->path_tracing != 0;
     const int fast_nodes = p.n_fnodes;   // (the tree's nodes, or the grid in their place)
-    frames = path && !canon && c->quadrics.empty() && !std::getenv("RTGO_NO_FRAMES");   // scenes of flat primitives only: N and the sampling tangent from LDS
     const size_t scene_lds = (size_t)(2 * (canon ? p.n_nodes : fast_nodes) + (canon ? 6 : 7) * p.n_prims + (frames ? 2 * p.n_prims : 0) /* shading frames */) * sizeof(float4) +
                              (size_t)kMaxLights * sizeof(LightRec) + 16 * sizeof(float) +   // + the raygen constants
                              (size_t)(nn < (uint32_t)kSampleTab ? nn : (uint32_t)kSampleTab) * sizeof(uint4);   // + the per-sample start table
-    int block = 0, blocks_per_cu = 0, best_waves = 0, wpe = 4;
-    size_t lds = 0;
+    int best_waves = 0;
     // Waves per SIMD the kernel variant is compiled for: 4 (<= 128 VGPRs) or 5 (<= 96, level records in LDS; 1-2 spilled dwords).
     // More resident waves fill more of the vector issue slots (cornell 1080p: 1.32 ms at 4, 1.22 at 5), but every wave then runs
     // slower and the launch ends one unit-duration after the queue runs dry: with few units per wave the shorter tail of fewer
@@ -1260,60 +1265,103 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     // (profiles/r02d) -- and was dropped: the kernel should not pay HBM for registers.
     const uint64_t units_per_wave4 = units_hot * (passes_of(nn)) / ((uint64_t)c->num_cus * 16u);
     const int max_wpe_work = units_per_wave4 >= 3 ? 5 : 4;
-    int max_wpe = canon ? 4 : (int)env_uint("RTGO_MAX_WPE", (unsigned int)max_wpe_work);   // (experiment knob, clamped to what exists)
+    int max_wpe = canon ? 4 : (kn.max_wpe ? (int)kn.max_wpe : max_wpe_work);   // (RTGO_MAX_WPE: experiment knob, clamped to what exists)
     max_wpe = max_wpe < 4 ? 4 : (max_wpe > 5 ? 5 : max_wpe);
-    int min_block = (int)env_uint("RTGO_MIN_BLOCK", 256);   // (experiment knob: 256 / 512 / 1024)
-    min_block = min_block >= 1024 ? 1024 : (min_block >= 512 ? 512 : 256);
     for (int w = 4; w <= max_wpe; ++w)
-        for (int b = min_block; b <= kMaxBlock; b *= 2) {
-            const size_t l = scene_lds + (stream ? (size_t)(b / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * b * (canon ? sizeof(float2) : sizeof(unsigned int)) + (w >= 5 ? (size_t)b * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0);
+        for (int bs = 256; bs <= kMaxBlock; bs *= 2) {
+            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + (w >= 5 ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0);
             int per_cu = (int)((160 * 1024) / l);
-            if (per_cu * (b / 64) > 4 * w) per_cu = (4 * w) / (b / 64);
-            const int waves = per_cu * (b / 64);
+            if (per_cu * (bs / 64) > 4 * w) per_cu = (4 * w) / (bs / 64);
+            const int waves = per_cu * (bs / 64);
             if (waves > best_waves) {
                 best_waves = waves;
-                block = b;
-                blocks_per_cu = per_cu;
-                lds = l;
-                wpe = w;
+                b.block = bs;
+                b.blocks_per_cu = per_cu;
+                b.lds = l;
+                b.wpe = w;
             }
         }
     if (best_waves == 0) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: scene does not fit in LDS");
     int cus = c->num_cus - (int)(f->reserve_cus < (uint32_t)c->num_cus / 2 ? f->reserve_cus : (uint32_t)c->num_cus / 2);
-    unsigned int grid = (unsigned int)(cus * blocks_per_cu);
-    const unsigned int need = (p.n_tiles + (block / 64) - 1) / (block / 64);
-    if (grid > need) grid = need;
+    b.grid = (unsigned int)(cus * b.blocks_per_cu);
+    const unsigned int need = (p.n_tiles + (b.block / 64) - 1) / (b.block / 64);
+    if (b.grid > need) b.grid = need;
+    return RTGO_OK;
+}
 
-    if (std::getenv("RTGO_DEBUG"))
-        std::fprintf(stderr, "rtgo_launch: %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g\n",
-                     canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", grid, block, lds, wpe, blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric);
+// The launch between its two events on the context's stream, then its bookkeeping: only now does the trial (rtgo_ctx::Trial) learn of it
+static int enqueue(rtgo_ctx* c, RenderKernel kernel, const LaunchParams& p, const Block& b, Pick& pk, bool canon, uint64_t rays_culled)
+{
 #ifdef RTGO_TIMELINE
-    c->timeline_waves = grid * (unsigned int)(block / 64);
+    c->timeline_waves = b.grid * (unsigned int)(b.block / 64);
     if (c->timeline_waves > 16384) return fail(c, RTGO_E_UNSUPPORTED, "timeline buffer too small");
 #endif
     RTGO_HIP(c, hipSetDevice(c->device));
-    if (c->ev_pending == rtgo_ctx::kEvRing) {
-        int rc = harvest_events(c, 1);
-        if (rc) return rc;
-    }
+    if (c->ev_pending == rtgo_ctx::kEvRing)
+        if (const int rc = harvest_events(c, 1)) return rc;
     const int slot = c->ev_head;
-    c->ev_tag[slot] = trial_tag;
     RTGO_HIP(c, hipEventRecord(c->ev_start[slot], c->stream));
-    const float4* fp = (const float4*)ft.d_fprims;
-    const RenderKernel kernel = find_kernel(path, canon, wpe, stream, stats, frames, use_grid);
-    if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, c->stream, p, fp);
+    hipLaunchKernelGGL(kernel, dim3(b.grid), dim3(b.block), b.lds, c->stream, p, p.fprims);
     RTGO_HIP(c, hipGetLastError());
     RTGO_HIP(c, hipEventRecord(c->ev_stop[slot], c->stream));
+    if (pk.n_cand > 1) {
+        rtgo_ctx::Trial& t = c->trial;
+        if (!pk.new_key.empty()) {
+            // (event tags of an unfinished trial of the old key are dropped: nothing reads its minima)
+            t = rtgo_ctx::Trial();
+            t.key = std::move(pk.new_key);
+            for (unsigned char& tag : c->ev_tag) tag = 0;
+        }
+        t.choice = pk.choice;
+        if (pk.trial_k >= 0) {
+            c->ev_tag[slot] = (unsigned char)(pk.trial_k + 1);
+            t.issued++;
+            c->launches_trial++;
+        }
+    }
     c->queue_set = 1 - c->queue_set;
-    c->rays_culled += ((unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels) * nn;
+    c->rays_culled += rays_culled;
     c->ev_head = (c->ev_head + 1) % rtgo_ctx::kEvRing;
     c->ev_pending++;
     c->launches++;
     if (canon) c->launches_canonical++;
-    if (trial_tag) c->launches_trial++;
-    c->last_variant = (stream ? 1u : 0u) | (use_alt ? 2u : 0u) | (canon ? 4u : 0u) | (trial_tag ? 8u : 0u) | (use_grid ? 16u : 0u);
+    c->last_variant = (pk.stream ? 1u : 0u) | (pk.structure == 1 ? 2u : 0u) | (canon ? 4u : 0u) | (pk.trial_k >= 0 ? 8u : 0u) | (pk.structure == 2 ? 16u : 0u);
     return RTGO_OK;
+}
+
+int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
+{
+    const Knobs kn;
+    LaunchParams p;
+    if (const int rc = frame_params(c, f, p)) return rc;
+    const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
+    const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
+    // collect_stats 1: the instrumented kernel traces every pixel (V, T, h over ALL rays, SURVEY 8d); 2: it culls like the timed
+    // kernel, so that the counters describe the traversed rays only
+    const bool cull = f->collect_stats != 1;
+    const Rect r = cull ? box_screen_rect(c->bounds, p) : Rect{0, p.w, 0, p.h};
+    const bool canon = far_field_guard(c, p, kn) || stats;
+    Pick pk;
+    if (const int rc = choose_candidate(c, f, p, nn, kn, canon, pk)) return rc;
+    const bool use_alt = pk.structure == 1, use_grid = pk.structure == 2;
+    walk_params(c, c->tree[use_alt ? 1 : 0], canon, use_grid, p);
+    uint32_t strip_px = 0;
+    uint64_t units_hot = 0;
+    if (const int rc = schedule(c, nn, r, p, strip_px, units_hot)) return rc;
+    unsigned long long mask_cold_pixels = 0;
+    if (cull && p.n_hot > 0)
+        if (const int rc = update_hot_mask(c, strip_px, p, mask_cold_pixels)) return rc;
+    if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
+    const bool frames = path && !canon && c->quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
+    Block b;
+    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, units_hot, kn, b)) return rc;
+    if (kn.debug)
+        std::fprintf(stderr, "rtgo_launch: %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g\n",
+                     canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric);
+    const RenderKernel kernel = find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid);
+    if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
+    const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels;
+    return enqueue(c, kernel, p, b, pk, canon, culled * nn);
 }
 
 int rtgo_assemble_bands(rtgo_ctx* c, void* hip_stream, const void* d_gathered, void* d_full, uint32_t w, uint32_t h, uint32_t band_h,
@@ -1358,33 +1406,7 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
             if (material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_mesh: material index beyond the material array");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->w_positions);
-    (void)hipFree(c->w_normals);
-    (void)hipFree(c->w_indices);
-    (void)hipFree(c->w_tri_material);
-    (void)hipFree(c->w_materials);
-    (void)hipFree(c->w_texcoords);
-    (void)hipFree(c->w_mat_tex);
-    for (void* t : c->w_texels) (void)hipFree(t);
-    c->w_texels.clear();
-    c->w_mat_tex_host.clear();
-    c->w_texcoords = nullptr;
-    c->w_mat_tex = nullptr;
-    (void)hipFree(c->w_nodes);
-    (void)hipFree(c->w_recs);
-    (void)hipFree(c->w_tris);
-    (void)hipFree(c->w_qrecs);
-    (void)hipFree(c->w_tidx);
-    (void)hipFree(c->w_scratch);
-    c->w_positions = c->w_normals = nullptr;
-    c->w_indices = c->w_tri_material = nullptr;
-    c->w_materials = nullptr;
-    c->w_nodes = nullptr;
-    c->w_recs = c->w_tris = nullptr;
-    c->w_qrecs = nullptr;
-    c->w_tidx = nullptr;
-    c->w_scratch = nullptr;
-    c->w_triangles = 0;
+    free_mesh(c);
     const size_t vb = (size_t)n_vertices * 3 * sizeof(float), ib = (size_t)n_triangles * 3 * sizeof(unsigned int);
     RTGO_HIP(c, hipMalloc(&c->w_positions, vb));
     RTGO_HIP(c, hipMemcpyAsync(c->w_positions, positions, vb, hipMemcpyHostToDevice, c->stream));
@@ -1671,7 +1693,7 @@ int rtgo_get_stats(rtgo_ctx* c, rtgo_stats* out)
     out->dbg_fast_tests = h[6];
     out->rays_culled = c->rays_culled;
     out->launches_canonical = c->launches_canonical;
-    out->cuboid_groups = (uint32_t)c->cuboid_groups;
+    out->cuboid_groups = (uint32_t)c->tree[0].cuboid_groups;
     out->guard_reach = c->guard_reach;
     out->guard_quadric = c->guard_quadric;
     out->last_variant = c->last_variant;
