@@ -183,6 +183,7 @@ static const RenderKernelEntry kRenderKernels[] = {
     {true, true, false, 4, false, false, render_kernel<true, true, 4, false, false>},     // canonical walk alone: launches beyond the far-field guard
     {false, true, false, 4, false, false, render_kernel<false, true, 4, false, false>},
     RTGO_KF(4, false), RTGO_KF(5, false), RTGO_KF(4, true), RTGO_KF(5, true),               // path mode, fast walk, scenes of flat primitives only: shading frames from LDS
+    RTGO_KF(6, false),                                                                      // ... at 6 waves/SIMD: the only combination that fits 80 VGPRs without scratch
     RTGO_KG(true, 4, false), RTGO_KG(true, 5, false), RTGO_KG(true, 4, true), RTGO_KG(true, 5, true),       // fast walk over the uniform grid instead of the tree (fast_grid)
     RTGO_KG(false, 4, false), RTGO_KG(false, 5, false), RTGO_KG(false, 4, true), RTGO_KG(false, 5, true),
 };
@@ -1239,6 +1240,8 @@ static int update_hot_mask(rtgo_ctx* c, uint32_t strip_px, LaunchParams& p, unsi
     return RTGO_OK;
 }
 
+static constexpr uint64_t kUnitsPerWave4For6 = 8;   // launches with fewer units per wave (counted at 4 waves/SIMD) take at most 5 waves (pick_block)
+
 struct Block {
     int block = 0, blocks_per_cu = 0, wpe = 4;   // threads per workgroup, workgroups per CU, waves per SIMD of the variant
     size_t lds = 0;
@@ -1247,29 +1250,31 @@ struct Block {
 
 // LDS image of the chosen kernel (see render_kernel): canonical = nodes + 6/prim; fast = fnodes + 4/prim + 3/prim.
 // The scene copy is per workgroup and the stack per lane, so bigger scenes want bigger workgroups: pick the size that
-// puts the most waves on a CU (at most 16 = 4 per SIMD, what the kernel's VGPR budget admits), smallest size on ties.
-static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, bool canon, bool stream, bool frames,
+// puts the most waves on a CU (4, 5 or 6 per SIMD, what the variant's VGPR budget admits), smallest size on ties.
+static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, bool canon, bool stream, bool frames, bool grid,
                       uint64_t units_hot, const Knobs& kn, Block& b)
 {
     const bool path = f->path_tracing != 0;
     const int fast_nodes = p.n_fnodes;   // (the tree's nodes, or the grid in their place)
     const size_t scene_lds = (size_t)(2 * (canon ? p.n_nodes : fast_nodes) + (canon ? 6 : 7) * p.n_prims + (frames ? 2 * p.n_prims : 0) /* shading frames */) * sizeof(float4) +
-                             (size_t)kMaxLights * sizeof(LightRec) + 16 * sizeof(float) +   // + the raygen constants
+                             (size_t)kMaxLights * sizeof(LightRec) + kCamWords * sizeof(float) +   // + the raygen constants (kCamWordsLean at 6 waves: below)
                              (size_t)(nn < (uint32_t)kSampleTab ? nn : (uint32_t)kSampleTab) * sizeof(uint4);   // + the per-sample start table
     int best_waves = 0;
-    // Waves per SIMD the kernel variant is compiled for: 4 (<= 128 VGPRs) or 5 (<= 96, level records in LDS; 1-2 spilled dwords).
-    // More resident waves fill more of the vector issue slots (cornell 1080p: 1.32 ms at 4, 1.22 at 5), but every wave then runs
+    // Waves per SIMD the kernel variant is compiled for: 4 (<= 128 VGPRs), 5 (<= 96, level records in LDS) or 6 (<= 80; path mode
+    // over flat scenes only, the FRAMES lock-step kernel -- the one combination that fits without scratch).  More resident waves fill
+    // more of the vector issue slots (cornell 1080p: 1.32 ms at 4, 1.22 at 5; 0.89 -> 0.86 at 5 -> 6), but every wave then runs
     // slower and the launch ends one unit-duration after the queue runs dry: with few units per wave the shorter tail of fewer
-    // waves wins (a 1/16 share: 0.127 / 0.137 ms at 4 / 5).  A 6-waves variant (<= 80 VGPRs) ran 1 % faster still (1.209 ms) but
-    // spilled 25-32 registers to scratch -- 472 MB of HBM traffic per launch against 94 MB at 5 waves and 74.6 MB of framebuffer
-    // (profiles/r02d) -- and was dropped: the kernel should not pay HBM for registers.
+    // waves wins (a 1/16 share: 0.127 / 0.137 ms at 4 / 5).  Round 1's 6-waves kernel spilled 25-32 registers to scratch (472 MB of
+    // HBM per launch, profiles/r02d) and was dropped; today's fits because the per-lane values derived from the lane index are
+    // derived where they are used (opaque_lane in rtgo_device.h) instead of being held through every ray loop.
     const uint64_t units_per_wave4 = units_hot * (passes_of(nn)) / ((uint64_t)c->num_cus * 16u);
-    const int max_wpe_work = units_per_wave4 >= 3 ? 5 : 4;
+    const int top_wpe = find_kernel(path, canon, 6, stream, false, frames, grid) ? 6 : 5;   // the 6-waves variant exists for some combinations only
+    const int max_wpe_work = units_per_wave4 >= kUnitsPerWave4For6 ? 6 : (units_per_wave4 >= 3 ? 5 : 4);
     int max_wpe = canon ? 4 : (kn.max_wpe ? (int)kn.max_wpe : max_wpe_work);   // (RTGO_MAX_WPE: experiment knob, clamped to what exists)
-    max_wpe = max_wpe < 4 ? 4 : (max_wpe > 5 ? 5 : max_wpe);
+    max_wpe = max_wpe < 4 ? 4 : (max_wpe > top_wpe ? top_wpe : max_wpe);
     for (int w = 4; w <= max_wpe; ++w)
         for (int bs = 256; bs <= kMaxBlock; bs *= 2) {
-            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + (w >= 5 ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0);
+            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + (w >= 5 ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0) + (w >= 6 ? (size_t)(kCamWordsLean - kCamWords) * sizeof(float) : 0);
             int per_cu = (int)((160 * 1024) / l);
             if (per_cu * (bs / 64) > 4 * w) per_cu = (4 * w) / (bs / 64);
             const int waves = per_cu * (bs / 64);
@@ -1354,7 +1359,7 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
     const bool frames = path && !canon && c->quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
     Block b;
-    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, units_hot, kn, b)) return rc;
+    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b)) return rc;
     if (kn.debug)
         std::fprintf(stderr, "rtgo_launch: %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g\n",
                      canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric);

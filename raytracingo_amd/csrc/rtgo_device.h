@@ -23,6 +23,8 @@ constexpr int kQueues = 32;          // work-queue heads (power of two <= 64; 8 
 constexpr unsigned int kQueueStride = 16;   // words between two heads: one 64-byte line each
 constexpr int kUnitsPerGrab = 4;     // most units (64 paths each) in one strip = one queue entry (longer strips: seeds cheaper, balance worse)
 constexpr int kSampleTab = 256;     // samples per pixel whose start (LCG skip, jitter cell) comes from a table in LDS (16 B each); beyond: computed
+constexpr int kCamWords = 16;        // raygen constants in LDS (render_kernel's s_cam) ...
+constexpr int kCamWordsLean = 20;    // ... + the launch's two reciprocals in the 6-waves variant (a multiple of 4: s_tab follows)
 constexpr int kMaxLevels = 5;        // bounce records kept per path (maxTraceDepth <= 5)
 constexpr float kPi = 3.14159265358979323846f;  // M_PIf, sutil/vec_math.h:43
 
@@ -1111,13 +1113,24 @@ __device__ __forceinline__ unsigned int wave_sum(unsigned int v)
     return v;
 }
 
+// The lane's index within its wave, as a value the compiler cannot hoist out of the loop it is read in.  What render_kernel derives
+// from the lane (the pixel and sample of a unit, per-lane queue addresses, the tea<16> input) is cheap to derive again; hoisted to
+// the kernel's start, it sat in VGPRs through every ray loop, which the 6-waves-per-SIMD budget (80 VGPRs) cannot afford.
+__device__ __forceinline__ unsigned int opaque_lane()
+{
+    unsigned int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(l));
+    return l;
+}
+
 // running average + 8-bit image of one pixel: kernel.cu:236-246
-__device__ __forceinline__ void write_pixel(const LaunchParams& p, size_t idx, v3 cur)
+// ratio = 1.0f / (float)(p.frame + 1): the 6-waves variant reads it from LDS (s_cam) where it writes, instead of holding the
+// VALU division's result in a VGPR for the whole kernel
+__device__ __forceinline__ void write_pixel(const LaunchParams& p, size_t idx, v3 cur, float ratio)
 {
     if (p.frame > 0) {
         const float4 prev4 = p.accum[idx];
         const v3 prev = mk(prev4.x, prev4.y, prev4.z);
-        const float ratio = 1.0f / (float)(p.frame + 1);
         cur = vadd(prev, vscale(vsub(cur, prev), ratio));  // lerp, vec_math.h:496-499
     }
     p.accum[idx] = make_float4(cur.x, cur.y, cur.z, 1.0f);
@@ -1171,7 +1184,8 @@ __device__ __forceinline__ void cold_segment(const LaunchParams& p, unsigned int
 // =====================================================================================================================
 // WPE = waves per SIMD the register allocation targets: 4 (<= 128 VGPRs) for scenes whose LDS image limits a CU to 16 waves
 // anyway, 5 (<= 96 VGPRs, per-level path records in LDS) for small scenes, where the fifth wave buys more than the tighter
-// budget costs (rtgo_capi.hip picks per launch; kRenderKernels there lists every instantiation).
+// budget costs, and 6 (<= 80 VGPRs) for the path-mode FRAMES lock-step kernel, which fits that without scratch (rtgo_capi.hip
+// picks per launch; kRenderKernels there lists every instantiation).
 #ifndef RTGO_STREAM_WINDOW
 #define RTGO_STREAM_WINDOW 4
 #endif
@@ -1202,22 +1216,23 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     // (entries x workgroup size x 8 bytes for the canonical walk, x 4 for the fast walk's packed words: a multiple of 1 KiB either way)
     LightRec* s_lights = reinterpret_cast<LightRec*>(reinterpret_cast<unsigned char*>(s_stack_base) + (size_t)stack_depth * kBlock * (STATS ? 8 : 4));
     const float4* s_mat = s_mat_w;
-    // small scenes (the 5-waves-per-SIMD variant): per-level path records live in LDS, [4 words x kMaxLevels][lane], instead of
+    // small scenes (the 5- and 6-waves-per-SIMD variants): per-level path records live in LDS, [4 words x kMaxLevels][lane], instead of
     // 15-20 VGPRs -- that is what lets the allocation fit 96 registers without spilling to scratch
     constexpr bool LVLDS = (WPE >= 5);
     constexpr int LVW = PATH ? 3 : 4;   // words per level record: the weight (path) / the term and the primitive (distributed)
     // raygen constants (eye, U, V, W, image size, sample step): read from LDS where a sample starts, instead of sitting in
     // registers through the ray loop
     float* s_cam = reinterpret_cast<float*>(s_lights + kMaxLights);
+    constexpr int CAMW = WPE >= 6 ? kCamWordsLean : kCamWords;
     // per sample k of a pixel (the first kSampleTab of them): the LCG's 2k-step map (A, C) -- the sample's jitter starts from A * seed + C,
     // the pixel's tea<16> seed advanced by 2k draws -- and the sample's cell (i, j) = (k / N, k % N) of the N x N jitter grid.  They depend on
     // k alone: a table instead of ~70 instructions of squaring loop and an integer division wherever a sample starts (most of a primary ray's
     // cost where primary rays are most rays: plateau 4K spp 256 17.2 -> 16.4 ms, mirror_spheres 4K spp 64 14.6 -> 14.3, cornell -1 %)
-    uint4* s_tab = reinterpret_cast<uint4*>(s_cam + 16);
+    uint4* s_tab = reinterpret_cast<uint4*>(s_cam + CAMW);
     const unsigned int n_tab = (unsigned int)(p.sqrt_spp * p.sqrt_spp) < (unsigned int)kSampleTab ? (unsigned int)(p.sqrt_spp * p.sqrt_spp) : (unsigned int)kSampleTab;
-    float* s_lv = s_cam + 16 + 4 * n_tab + threadIdx.x;
+    float* s_lv = s_cam + CAMW + 4 * n_tab + threadIdx.x;
     // STREAM: the payload window of this wave (4 passes x 3 channels x 64 lanes), behind the level records
-    float* s_win_base = s_cam + 16 + 4 * n_tab + (LVLDS ? (int)blockDim.x * LVW * kMaxLevels : 0) + 192 * kStreamWindow * (threadIdx.x >> 6);
+    float* s_win_base = s_cam + CAMW + 4 * n_tab + (LVLDS ? (int)blockDim.x * LVW * kMaxLevels : 0) + 192 * kStreamWindow * (threadIdx.x >> 6);
 
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid < kQueues) p.queue_next[kQueueStride * (unsigned int)tid] = 0u;
@@ -1248,6 +1263,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         s_cam[4] = p.U.x; s_cam[5] = p.U.y; s_cam[6] = p.U.z; s_cam[7] = (float)p.H;
         s_cam[8] = p.V.x; s_cam[9] = p.V.y; s_cam[10] = p.V.z; s_cam[11] = 1.0f / (float)p.sqrt_spp;
         s_cam[12] = p.Wv.x; s_cam[13] = p.Wv.y; s_cam[14] = p.Wv.z; s_cam[15] = 0.0f;
+        if constexpr (CAMW > 16) {   // (6-waves variant: write_pixel's ratio and 1 / nn)
+            s_cam[16] = 1.0f / (float)(p.frame + 1); s_cam[17] = 1.0f / (float)(p.sqrt_spp * p.sqrt_spp); s_cam[18] = 0.0f; s_cam[19] = 0.0f;
+        }
     }
     {
         const float* src = reinterpret_cast<const float*>(p.lights);
@@ -1262,7 +1280,14 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     float2* s_stack = s_stack_base + tid;                                                 // canonical walk: (distance, node) entries
     unsigned int* s_stack4 = reinterpret_cast<unsigned int*>(s_stack_base) + tid;         // fast walk: one packed word per entry
     const int lane = tid & 63;
+    // LEAN (the 6-waves variant): values derived from the lane index, and the two reciprocals write_pixel needs, are derived
+    // where they are used (opaque_lane, s_cam) instead of being held in VGPRs through every ray loop -- what fits 80 VGPRs without
+    // scratch.  The other variants keep the hoisted values, which their budgets afford and which are cheaper.
+    constexpr bool LEAN = (WPE >= 6);
+    auto lane_index = [&]() { return LEAN ? opaque_lane() : (unsigned int)lane; };
+    auto frame_ratio = [&]() { return LEAN ? s_cam[16] : 1.0f / (float)(p.frame + 1); };
     const unsigned int nn = (unsigned int)(p.sqrt_spp * p.sqrt_spp);
+    auto inv_nn = [&]() { return LEAN ? s_cam[17] : 1.0f / (float)nn; };
     // Work decomposition: ONE LANE = ONE PATH.  A wave takes "units" of 64/nn_eff neighbouring pixels of a row and runs
     // nn_eff = min(nn, 16) samples of each side by side, in ceil(nn / nn_eff) passes.  The samples of a pixel are independent
     // given the LCG state their jitter starts from (trace passes the seed by value, kernel.cu:46-79), which is the pixel's
@@ -1273,9 +1298,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     const unsigned int nn_eff = nn < (unsigned int)kSamplesPerPass ? nn : (unsigned int)kSamplesPerPass;  // samples of one pixel that share a pass
     const unsigned int P = 64u / nn_eff;                        // pixels per unit
     const unsigned int passes = (nn + nn_eff - 1u) / nn_eff;
-    const unsigned int pl = (unsigned int)lane / nn_eff;        // this lane's pixel within the unit
-    const unsigned int kl = (unsigned int)lane - pl * nn_eff;   // this lane's sample within the pass
-    const unsigned int group_base = (pl < P ? pl : 0u) * nn_eff;
+    const unsigned int pl0 = (unsigned int)lane / nn_eff;        // this lane's pixel within the unit (LEAN: derived where used)
+    const unsigned int kl0 = (unsigned int)lane - pl0 * nn_eff;  // this lane's sample within the pass
+    const unsigned int group_base0 = (pl0 < P ? pl0 : 0u) * nn_eff;
 
     unsigned int c_rays = 0, c_occl = 0, c_nodes = 0, c_tests = 0, c_hits = 0;
 #ifdef RTGO_STREAM_STATS
@@ -1295,6 +1320,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     // (the head's offset is added when the value is USED: arithmetic on it here would make the wave wait for the atomic at once)
     unsigned int pending = (blockIdx.x / (unsigned int)kQueues) * wpb + ((unsigned int)tid >> 6), pending_off = 0u;
     for (;;) {
+        const unsigned int lane_q = lane_index();
         const unsigned int q_count = (p.n_tiles + (unsigned int)kQueues - 1u - q) / (unsigned int)kQueues;   // units in queue q
 #ifdef RTGO_TIMELINE
         const unsigned long long tl_q0 = wall_clock64();
@@ -1308,9 +1334,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
             // own head is past its end: look at all heads at once (one load, lanes 0..7) and move to one that still has work.
             // Heads only grow, so "none has work" is final: the wave leaves and the grid drains.
             unsigned int head = 0xFFFFFFFFu, cnt_l = 0u;
-            if (lane < kQueues) {
-                head = __hip_atomic_load(p.queue + kQueueStride * (unsigned int)lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + n_static((unsigned int)lane);
-                cnt_l = (p.n_tiles + (unsigned int)kQueues - 1u - (unsigned int)lane) / (unsigned int)kQueues;
+            if (lane_q < (unsigned int)kQueues) {
+                head = __hip_atomic_load(p.queue + kQueueStride * lane_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + n_static(lane_q);
+                cnt_l = (p.n_tiles + (unsigned int)kQueues - 1u - lane_q) / (unsigned int)kQueues;
             }
             const unsigned long long open = __ballot(head < cnt_l);
             if (open == 0ull) break;
@@ -1337,9 +1363,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
             for (unsigned int s = s0; s < s1; ++s) {
                 unsigned int clr, cx, clim;
                 cold_segment(p, s, clr, cx, clim);
-                const unsigned int lx = cx + (unsigned int)lane;
+                const unsigned int lx = cx + lane_q;
                 if (lx < clim) {
-                    write_pixel(p, (size_t)clr * p.w + lx, p.bg_pixel);
+                    write_pixel(p, (size_t)clr * p.w + lx, p.bg_pixel, frame_ratio());
                     c_rays += nn;
                 }
             }
@@ -1349,9 +1375,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         const unsigned int sx = p.hot_x0 + (strip - (lr - p.hot_y0) * p.hot_w);   // strip column
         if (p.hot_mask != nullptr && ((p.hot_mask[strip >> 5] >> (strip & 31u)) & 1u) == 0u) {
             // a strip of the rectangle that no primitive's own screen rectangle reaches (the word is wave-uniform: a scalar load)
-            const unsigned int lx0 = sx * p.grab * P + (unsigned int)lane;
-            if ((unsigned int)lane < p.grab * P && lx0 < p.w) {
-                write_pixel(p, (size_t)lr * p.w + lx0, p.bg_pixel);
+            const unsigned int lx0 = sx * p.grab * P + lane_q;
+            if (lane_q < p.grab * P && lx0 < p.w) {
+                write_pixel(p, (size_t)lr * p.w + lx0, p.bg_pixel, frame_ratio());
                 c_rays += nn;
             }
             continue;
@@ -1362,24 +1388,30 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         const unsigned int gy = p.y0 + wrow;
         const float fy = (float)gy;
         const unsigned int strip_x0 = sx * p.grab * P;
-        const unsigned int strip_seed = tea16(p.W * gy + (p.x0 + strip_x0 + (unsigned int)lane), p.frame);
+        const unsigned int strip_seed = tea16(p.W * gy + (p.x0 + strip_x0 + lane_q), p.frame);
 #ifdef RTGO_TIMELINE
         if (tl_b == 0) tl_b = wall_clock64() + (strip_seed == 0x12345u ? 1 : 0);
 #endif
 #pragma unroll 1
         for (unsigned int ui = 0; ui < p.grab; ++ui) {
-        const unsigned int lx = strip_x0 + ui * P + pl;
+        const unsigned int lx_u = strip_x0 + ui * P + pl0;
         if (strip_x0 + ui * P >= p.w) break;
-        const bool in_range = pl < P && lx < p.w;
-        const unsigned int gx = p.x0 + lx;
-        const float fx = (float)gx;
-
+        const bool in_range_u = pl0 < P && lx_u < p.w;
+        const float fx_u = (float)(p.x0 + lx_u);
         // __raygen__rg (kernel.cu:184-247)
-        const unsigned int pix0 = (unsigned int)__shfl((int)strip_seed, (int)((ui * P + pl) & 63u), 64);
+        const unsigned int pix0_u = (unsigned int)__shfl((int)strip_seed, (int)((ui * P + pl0) & 63u), 64);
         v3 color = mk(0.0f, 0.0f, 0.0f);
         if constexpr (!STREAM) {
 #pragma unroll 1
         for (unsigned int pass = 0; pass < passes; ++pass) {
+        // the lane's pixel and sample, its first jitter input and its LCG seed: held through the unit (the values above), or
+        // derived again per pass (LEAN; the *_u values are then dead)
+        const unsigned int lane_p = lane_index();
+        const unsigned int pl = LEAN ? lane_p / nn_eff : pl0, kl = LEAN ? lane_p - pl * nn_eff : kl0;
+        const unsigned int lx = LEAN ? strip_x0 + ui * P + pl : lx_u;
+        const bool in_range = LEAN ? (pl < P && lx < p.w) : in_range_u;
+        const float fx = LEAN ? (float)(p.x0 + lx) : fx_u;
+        const unsigned int pix0 = LEAN ? (unsigned int)__shfl((int)strip_seed, (int)((ui * P + pl) & 63u), 64) : pix0_u;
         const unsigned int k = pass * nn_eff + kl;   // sample index: i-major, k = i*N + j (kernel.cu:206-208)
         bool active;
         int depth;
@@ -1426,6 +1458,8 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
             // every primary ray of the unit missed: all payloads are the background colour, no lane exchange needed
             for (unsigned int q = 0; q < cnt; ++q) color = vadd(color, p.bg);
         } else {
+            const unsigned int lane_f = lane_index(), pl_f = LEAN ? lane_f / nn_eff : pl0;
+            const unsigned int group_base = LEAN ? (pl_f < P ? pl_f : 0u) * nn_eff : group_base0;
             for (unsigned int q = 0; q < cnt; ++q) {
                 const int src = (int)(group_base + q);
                 color = vadd(color, mk(__shfl(result.x, src, 64), __shfl(result.y, src, 64), __shfl(result.z, src, 64)));
@@ -1575,13 +1609,16 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
             tls_regen += ts_regen; tls_trace += ts_trace; tls_shade += ts_shade; tls_lanes_trace += ts_lanes_trace; tls_lanes_regen += ts_lanes_regen; tls_regens += ts_regens;
             tl_units += 1;
 #endif
-            if ((unsigned int)lane < npx) write_pixel(p, (size_t)lr * p.w + strip_x0 + ui * P + (unsigned int)lane, vscale(color, 1.0f / (float)nn));
+            if ((unsigned int)lane < npx) write_pixel(p, (size_t)lr * p.w + strip_x0 + ui * P + (unsigned int)lane, vscale(color, inv_nn()), frame_ratio());
         }
 
-        if constexpr (!STREAM)
-        if (in_range && kl == 0) {
-            // kernel.cu:236-246.  float3 / float multiplies by the reciprocal (vec_math.h:479-483)
-            write_pixel(p, (size_t)lr * p.w + lx, vscale(color, 1.0f / (float)nn));
+        if constexpr (!STREAM) {
+            const unsigned int lane_w = lane_index(), pl = LEAN ? lane_w / nn_eff : pl0, kl = LEAN ? lane_w - pl * nn_eff : kl0;
+            const unsigned int lx = LEAN ? strip_x0 + ui * P + pl : lx_u;
+            if ((LEAN ? (pl < P && lx < p.w) : in_range_u) && kl == 0) {
+                // kernel.cu:236-246.  float3 / float multiplies by the reciprocal (vec_math.h:479-483)
+                write_pixel(p, (size_t)lr * p.w + lx, vscale(color, inv_nn()), frame_ratio());
+            }
         }
 #ifdef RTGO_TIMELINE
         if (tl_d == 0) tl_d = wall_clock64();
