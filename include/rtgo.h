@@ -219,7 +219,8 @@ int rtgo_whitted_set_mesh(rtgo_ctx* ctx, const float* positions, const float* no
                           const uint32_t* material_of_triangle, uint32_t n_triangles, const rtgo_pbr* materials, uint32_t n_materials);
 
 /* GeometryData::TriangleMesh::texcoords (cuda/GeometryData.h:46-52): one (u, v) per vertex of the mesh set by rtgo_whitted_set_mesh, or
-   NULL for none -- getLocalGeometry then takes the barycentrics as UV (cuda/LocalGeometry.h:88-102).  Call after rtgo_whitted_set_mesh. */
+   NULL for none -- getLocalGeometry then takes the barycentrics as UV (cuda/LocalGeometry.h:88-102).  Call after rtgo_whitted_set_mesh
+   (an instanced scene takes its texture coordinates per mesh in rtgo_whitted_set_scene: RTGO_E_STATE). */
 int rtgo_whitted_set_texcoords(rtgo_ctx* ctx, const float* uv, uint32_t n_vertices);
 
 /* One image of sutil::Scene::addImage + addSampler (sutil/Scene.cpp:478-538): 8-bit RGBA texels in HOST memory, row 0 first (glTF's
@@ -232,8 +233,8 @@ typedef struct rtgo_texture {
 } rtgo_texture;
 
 /* MaterialData::Pbr::base_color_tex / metallic_roughness_tex / normal_tex (cuda/MaterialData.h:43-52) of material `material` of the table
-   given to rtgo_whitted_set_mesh; NULL = the material has no such texture (whitted.cu:264, 272, 288 test the handle).  The texels are
-   copied.  Call after rtgo_whitted_set_mesh (which clears every texture). */
+   given to rtgo_whitted_set_mesh or rtgo_whitted_set_scene; NULL = the material has no such texture (whitted.cu:264, 272, 288 test the
+   handle).  The texels are copied.  Call after rtgo_whitted_set_mesh / rtgo_whitted_set_scene (which clear every texture). */
 int rtgo_whitted_set_material_textures(rtgo_ctx* ctx, uint32_t material, const rtgo_texture* base_color,
                                        const rtgo_texture* metallic_roughness, const rtgo_texture* normal);
 
@@ -244,8 +245,46 @@ int rtgo_whitted_set_lights(rtgo_ctx* ctx, const rtgo_point_light* lights, uint3
 int rtgo_whitted_set_miss_color(rtgo_ctx* ctx, const float rgb[3]);
 
 /* optixLaunch of the whitted pipeline over width x height pixels for subframe `subframe_index` (whitted::LaunchParams,
-   cuda/whitted.h:59-74).  Asynchronous on the context's stream; rays are added to rtgo_stats (rays_total, rays_occlusion). */
+   cuda/whitted.h:59-74), over whichever scene the context holds (rtgo_whitted_set_mesh or rtgo_whitted_set_scene).  Asynchronous on
+   the context's stream; rays are added to rtgo_stats (rays_total, rays_occlusion). */
 int rtgo_whitted_launch(rtgo_ctx* ctx, uint32_t width, uint32_t height, uint32_t subframe_index);
+
+/* ---- instanced meshes: sutil::Scene's two levels (one GAS per MeshGroup, buildMeshAccels; one OptixInstance per group in an IAS,
+   buildInstanceAccel, sutil/Scene.cpp:985-1010) ---- */
+#define RTGO_WHITTED_MAX_MESHES 256
+#define RTGO_WHITTED_MAX_INSTANCES 8192
+
+/* one GAS: GeometryData::TriangleMesh (cuda/GeometryData.h:46-52) in OBJECT space */
+typedef struct rtgo_whitted_mesh {
+    const float* positions;                /* 3 floats per vertex */
+    const float* normals;                  /* 3 floats per vertex, or NULL (then N = Ng, LocalGeometry.h:113-116) */
+    const float* texcoords;                /* 2 floats per vertex, or NULL (then UV = the barycentrics) */
+    uint32_t n_vertices;
+    const uint32_t* indices;               /* 3 per triangle */
+    const uint32_t* material_of_triangle;  /* NULL: 0 */
+    uint32_t n_triangles;                  /* <= RTGO_MAX_TRIANGLES */
+} rtgo_whitted_mesh;
+
+/* one OptixInstance as Scene::buildInstanceAccel fills it (sutil/Scene.cpp:995-1005) */
+typedef struct rtgo_whitted_instance {
+    float transform[12];        /* row-major 3x4 object-to-world matrix (OptixInstance::transform) */
+    uint32_t mesh;              /* index into the meshes array (the instance's traversableHandle) */
+    uint32_t material_offset;   /* sbtOffset: a triangle's material is material_offset + material_of_triangle[t] */
+} rtgo_whitted_instance;
+
+/* A scene of n_meshes meshes drawn by n_instances instances, and one material table for all of them.  Checks every mesh as
+   rtgo_whitted_set_mesh does, and every instance: a mesh index inside the array, material_offset + the mesh's largest material index
+   inside the table, a finite and invertible transform (RTGO_E_INVALID).  More than RTGO_WHITTED_MAX_MESHES meshes or
+   RTGO_WHITTED_MAX_INSTANCES instances, a mesh beyond RTGO_MAX_TRIANGLES, or a structure deeper than the walk's stack:
+   RTGO_E_UNSUPPORTED.  Builds both levels on the device; replaces the scene of rtgo_whitted_set_mesh (and that call replaces this
+   one); clears every texture.  The closest hit is the smallest t, then the lowest (instance, triangle): an instanced scene renders
+   like the concatenation of its instances.  Synchronous. */
+int rtgo_whitted_set_scene(rtgo_ctx* ctx, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances,
+                           uint32_t n_instances, const rtgo_pbr* materials, uint32_t n_materials);
+
+/* New transforms, mesh choices or material offsets over the meshes and materials of the last rtgo_whitted_set_scene: rebuilds the top
+   level only.  Same checks and limits as rtgo_whitted_set_scene; textures stay.  Synchronous. */
+int rtgo_whitted_set_instances(rtgo_ctx* ctx, const rtgo_whitted_instance* instances, uint32_t n_instances);
 
 /* number of window rows a rank owns under the band interleave (pure host arithmetic) */
 uint32_t rtgo_local_rows(uint32_t h, uint32_t band_h, uint32_t n_ranks, uint32_t rank);

@@ -23,8 +23,10 @@ SYMBOLS = [
     "rtgo_read_image", "rtgo_read_accum", "rtgo_write_accum", "rtgo_get_stats", "rtgo_reset_stats", "rtgo_read_bvh",
     "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands",
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
-    "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures",
+    "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
 ]
+RTGO_WHITTED_MAX_MESHES = 256
+RTGO_WHITTED_MAX_INSTANCES = 8192
 
 
 class RtgoError(RuntimeError):
@@ -56,6 +58,15 @@ class Frame(C.Structure):
 
 class Texture(C.Structure):
     _fields_ = [("rgba8", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class WhittedMesh(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("texcoords", C.c_void_p), ("n_vertices", C.c_uint32),
+                ("indices", C.c_void_p), ("material_of_triangle", C.c_void_p), ("n_triangles", C.c_uint32)]
+
+
+class WhittedInstance(C.Structure):
+    _fields_ = [("transform", C.c_float * 12), ("mesh", C.c_uint32), ("material_offset", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -114,6 +125,8 @@ def load():
     L.rtgo_whitted_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_set_texcoords.argtypes = [vp, vp, C.c_uint32]
     L.rtgo_whitted_set_material_textures.argtypes = [vp, C.c_uint32, C.POINTER(Texture), C.POINTER(Texture), C.POINTER(Texture)]
+    L.rtgo_whitted_set_scene.argtypes = [vp, C.POINTER(WhittedMesh), C.c_uint32, C.POINTER(WhittedInstance), C.c_uint32, vp, C.c_uint32]
+    L.rtgo_whitted_set_instances.argtypes = [vp, C.POINTER(WhittedInstance), C.c_uint32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtgo_last_error", "rtgo_local_rows", "rtgo_abi_version"):
@@ -244,6 +257,33 @@ class Context:
                                                     idx.ctypes.data, tm.ctypes.data if tm is not None else None, len(idx),
                                                     mats.ctypes.data, len(mats)), "rtgo_whitted_set_mesh")
 
+    def whitted_set_scene(self, meshes, instances, materials):
+        """meshes: list of dicts shaped like tests/whitted_scene.build()'s output (positions, normals or None, indices, tri_material or None)
+        plus an optional texcoords [nv, 2]; instances: see whitted_instances(); materials [n, 6] (base colour rgba, metallic, roughness)"""
+        keep = []
+
+        def arr(a, dt, cols):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt).reshape((-1, cols) if cols else -1)
+            keep.append(a)
+            return a
+
+        ms = (WhittedMesh * max(len(meshes), 1))()
+        for k, m in enumerate(meshes):
+            pos, nrm, uv = arr(m["positions"], np.float32, 3), arr(m.get("normals"), np.float32, 3), arr(m.get("texcoords"), np.float32, 2)
+            idx, tm = arr(m["indices"], np.uint32, 3), arr(m.get("tri_material"), np.uint32, 0)
+            ms[k] = WhittedMesh(pos.ctypes.data, nrm.ctypes.data if nrm is not None else None, uv.ctypes.data if uv is not None else None,
+                                len(pos), idx.ctypes.data, tm.ctypes.data if tm is not None else None, len(idx))
+        inst = whitted_instances(instances)
+        mats = np.ascontiguousarray(materials, dtype=np.float32).reshape(-1, 6)
+        self._check(self._lib.rtgo_whitted_set_scene(self._h, ms, len(meshes), inst, len(instances), mats.ctypes.data, len(mats)),
+                    "rtgo_whitted_set_scene")
+
+    def whitted_set_instances(self, instances):
+        inst = whitted_instances(instances)
+        self._check(self._lib.rtgo_whitted_set_instances(self._h, inst, len(instances)), "rtgo_whitted_set_instances")
+
     def whitted_set_texcoords(self, uv):
         if uv is None:
             self._check(self._lib.rtgo_whitted_set_texcoords(self._h, None, 0), "rtgo_whitted_set_texcoords")
@@ -293,6 +333,19 @@ class Context:
         links = nodes.view(np.int32)[:, [3, 7]].copy()
         boxes = nodes[:, [0, 1, 2, 4, 5, 6]].copy()
         return boxes, links, inv, aabb
+
+
+def whitted_instances(instances):
+    """instances: a list of (transform, mesh, material_offset) -- transform a row-major 3 x 4 (or 4 x 4, last row ignored) object-to-world
+    matrix -- or a structured array with those fields.  Returns a ctypes array of WhittedInstance."""
+    n = len(instances)
+    arr = (WhittedInstance * max(n, 1))()
+    for i in range(n):
+        tr, mesh, off = instances[i][0], instances[i][1], instances[i][2]
+        arr[i].transform[:] = np.asarray(tr, dtype=np.float32).reshape(-1)[:12].tolist()
+        arr[i].mesh = int(mesh)
+        arr[i].material_offset = int(off)
+    return arr
 
 
 def make_frame(width, height, sqrt_spp=1, frame_count=0, path=True, ambient=False, window=None, bands=(4, 1, 0),

@@ -3,8 +3,9 @@
 // There is no CPU fallback anywhere in this file: every path ends in a HIP launch or an error code.
 #include "../../include/rtgo.h"
 #include "rtgo_device.h"
-#include "rtgo_whitted.h"
+#include "rtgo_whitted_inst.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +20,16 @@ static_assert(sizeof(rtgo_prim) == 108, "rtgo_prim is type + HitGroupData (104 B
 static_assert(sizeof(rtgo_light) == sizeof(LightRec) && sizeof(rtgo_light) == 64, "SurfaceLight is 64 B");
 static_assert(sizeof(rtgo_aabb) == 24, "OptixAabb is 24 B");
 static_assert(RTGO_MAX_PRIMS == kMaxPrims && RTGO_MAX_LIGHTS == kMaxLights, "limits");
+
+// one mesh of an instanced whitted scene (rtgo_whitted_set_scene), host side
+struct WhittedMeshInfo {
+    float lo[3], hi[3];        // a box around the mesh's root record (the padded triangle bounds, padded once more)
+    int rec_base, tri_base, vert_base;   // where its records / triangles / vertices start in the context's arrays
+    int root;                  // InstWalk::root
+    int flags;                 // whitted::kHasNormals | kHasTexcoords
+    int depth;                 // stack entries its walk needs
+    uint32_t max_material;     // its largest material_of_triangle
+};
 
 struct rtgo_ctx {
     int device = 0;
@@ -150,12 +161,23 @@ struct rtgo_ctx {
     int w_n_recs = 0, w_walk_depth = 0, w_launch_parity = 0;
     int w_triangles = 0, w_n_lights = 0, w_n_materials = 0;
     v3 w_miss{0, 0, 0};
+    // an instanced scene (rtgo_whitted_set_scene): the mesh buffers above hold every mesh back to back in object space (w_nodes,
+    // w_scratch: the largest mesh's build), plus the top level
+    bool w_instanced = false;
+    std::vector<WhittedMeshInfo> w_meshes;
+    int w_mesh_depth = 0;                      // the deepest mesh walk
+    float4* w_top_recs = nullptr;
+    whitted::InstWalk* w_inst = nullptr;       // in the top level's leaf order
+    whitted::InstShade* w_inst_shade = nullptr;   // in the caller's order
+    int w_n_top_recs = 0, w_n_instances = 0;
     std::string err;
 };
 
 static_assert(sizeof(rtgo_pbr) == sizeof(whitted::Pbr) && sizeof(rtgo_point_light) == sizeof(whitted::PointLight) && sizeof(rtgo_point_light) == 32,
               "whitted records");
 static_assert(RTGO_MAX_TRIANGLES == whitted::kMaxTriangles, "limits");
+static_assert(RTGO_WHITTED_MAX_MESHES == whitted::kMaxMeshes && RTGO_WHITTED_MAX_INSTANCES == whitted::kMaxInstances, "instance limits");
+static_assert(sizeof(rtgo_whitted_instance) == 56 && sizeof(whitted::InstWalk) == 64 && sizeof(whitted::InstShade) == 112, "instance records");
 
 static std::string g_create_error;
 
@@ -452,6 +474,8 @@ int rtgo_create(int device, rtgo_ctx** out)
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kAllInL2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kRecordsInLds>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kAllInLds>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err == hipSuccess) err = hipDeviceSynchronize();  // the null-stream memsets above must land before any launch
     if (err != hipSuccess) {
         std::string m = std::string("rtgo_create: ") + hipGetErrorString(err);
@@ -496,7 +520,18 @@ static void free_output(rtgo_ctx* c)
     c->pixels = 0;
 }
 
-// the whitted mesh's device buffers (rtgo_whitted_set_mesh, rtgo_destroy; the lights and tile-queue heads outlive a mesh)
+// an instanced scene's top level (rtgo_whitted_set_instances replaces it alone)
+static void free_top(rtgo_ctx* c)
+{
+    release(c->w_top_recs);
+    release(c->w_inst);
+    release(c->w_inst_shade);
+    c->w_n_top_recs = 0;
+    c->w_n_instances = 0;
+}
+
+// the whitted scene's device buffers (rtgo_whitted_set_mesh, rtgo_whitted_set_scene, rtgo_destroy; the lights and tile-queue heads
+// outlive a scene)
 static void free_mesh(rtgo_ctx* c)
 {
     release(c->w_positions);
@@ -515,6 +550,10 @@ static void free_mesh(rtgo_ctx* c)
     release(c->w_qrecs);
     release(c->w_tidx);
     release(c->w_scratch);
+    free_top(c);
+    c->w_meshes.clear();
+    c->w_instanced = false;
+    c->w_mesh_depth = 0;
     c->w_triangles = 0;
 }
 
@@ -1396,6 +1435,65 @@ int rtgo_assemble_bands(rtgo_ctx* c, void* hip_stream, const void* d_gathered, v
     return RTGO_OK;
 }
 
+// the two sets of tile-queue heads of the whitted launches (allocated once, zero)
+static int whitted_tile_heads(rtgo_ctx* c)
+{
+    if (!c->w_tile_counters) {
+        const size_t heads_bytes = 2 * (size_t)whitted::kTileHeads * whitted::kTileHeadStride * sizeof(unsigned int);
+        RTGO_HIP(c, hipMalloc(&c->w_tile_counters, heads_bytes));
+        RTGO_HIP(c, hipMemsetAsync(c->w_tile_counters, 0, heads_bytes, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return RTGO_OK;
+}
+
+// One structure of the whitted path, built on the device over n triangles (positions, indices: device memory): build_kernel's Morton
+// hierarchy, its records rebuilt top-down with the surface-area heuristic (sah_kernel) when the leaves fit its LDS, and the Morton
+// records again when the surface-area tree comes out deeper than the walk's stack.  nodes: (2n - 1) x 2 float4; scratch: 38 n + 16
+// ints; recs: n x 4 float4; tris: n x 3 float4; qrecs: n x 2 uint4; tidx: n uint2.  m = build_kernel's out_meta.  Synchronous.
+static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int* indices, int n, float4* nodes, int* scratch, float4* recs, float4* tris,
+                         uint4* qrecs, uint2* tidx, int m[9], const char* what)
+{
+    int* parent = scratch;   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
+    int* visit = parent + (2 * n - 1);
+    int* first_of = visit + n;
+    int* count_of = first_of + n;
+    int* rec_of = count_of + n;
+    int* meta = rec_of + n;
+    const size_t keys_lds = (size_t)whitted::kMaxTriangles * sizeof(unsigned long long);
+    hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, nodes,
+                       parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, meta);
+    RTGO_HIP(c, hipGetLastError());
+    // the records over the same leaves, rebuilt top-down with the surface-area heuristic (leaf boxes, links, order arrays in LDS: 33 B per
+    // triangle, so meshes beyond ~4650 triangles keep the Morton records)
+    const size_t sah_lds = (size_t)n * (6 * sizeof(float) + sizeof(int) + 2 * sizeof(short) + 1) + 16;
+    const bool sah = !std::getenv("RTGO_WHITTED_NO_SAH") && sah_lds <= 150 * 1024;
+    if (sah) {
+        hipLaunchKernelGGL(whitted::sah_kernel, dim3(1), dim3(whitted::kBuildThreads), sah_lds, c->stream, n, (const float4*)nodes, (const int*)parent,
+                           (const int*)first_of, (const int*)count_of, meta + 16, recs, qrecs, meta);
+        RTGO_HIP(c, hipGetLastError());
+    }
+    for (int k = 0; k < 9; ++k) m[k] = 0;
+    RTGO_HIP(c, hipMemcpyAsync(m, meta, 9 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (m[2] > whitted::kMaxWalkDepth && sah) {
+        // the surface-area tree came out deeper than the walk's stack (it has no depth bound of its own): back to the Morton records,
+        // whose depth is bounded by the code length
+        hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, nodes,
+                           parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, meta);
+        RTGO_HIP(c, hipGetLastError());
+        RTGO_HIP(c, hipMemcpyAsync(m, meta, 9 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (m[0] > 2 * whitted::kStack)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": triangle LBVH depth " + std::to_string(m[0]) + " exceeds what the build handles (" +
+                                               std::to_string(2 * whitted::kStack) + ")");
+    if (m[2] > whitted::kMaxWalkDepth)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the walk needs " + std::to_string(m[2]) + " stack entries (limit " +
+                                               std::to_string(whitted::kMaxWalkDepth) + ")");
+    return RTGO_OK;
+}
+
 int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* normals, uint32_t n_vertices, const uint32_t* indices,
                           const uint32_t* material_of_triangle, uint32_t n_triangles, const rtgo_pbr* materials, uint32_t n_materials)
 {
@@ -1433,63 +1531,324 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
     RTGO_HIP(c, hipMalloc(&c->w_qrecs, (size_t)n_triangles * 2 * sizeof(uint4)));
     RTGO_HIP(c, hipMalloc(&c->w_tidx, (size_t)n_triangles * sizeof(uint2)));
     RTGO_HIP(c, hipMalloc(&c->w_scratch, (size_t)(6 * n_triangles + 16 + 32 * n_triangles) * sizeof(int)));   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
-    int* parent = c->w_scratch;
-    int* visit = parent + (2 * n_triangles - 1);
-    int* first_of = visit + n_triangles;
-    int* count_of = first_of + n_triangles;
-    int* rec_of = count_of + n_triangles;
-    int* meta = rec_of + n_triangles;
-    const size_t keys_lds = (size_t)whitted::kMaxTriangles * sizeof(unsigned long long);
-    hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, c->w_positions, c->w_indices, (int)n_triangles, c->w_nodes,
-                       parent, visit, first_of, count_of, rec_of, c->w_recs, c->w_tris, c->w_qrecs, c->w_tidx, meta);
-    RTGO_HIP(c, hipGetLastError());
-    // the records over the same leaves, rebuilt top-down with the surface-area heuristic (leaf boxes, links, order arrays in LDS: 33 B per
-    // triangle, so meshes beyond ~4650 triangles keep the Morton records)
-    const size_t sah_lds = (size_t)n_triangles * (6 * sizeof(float) + sizeof(int) + 2 * sizeof(short) + 1) + 16;
-    const bool sah = !std::getenv("RTGO_WHITTED_NO_SAH") && sah_lds <= 150 * 1024;
-    if (sah) {
-        hipLaunchKernelGGL(whitted::sah_kernel, dim3(1), dim3(whitted::kBuildThreads), sah_lds, c->stream, (int)n_triangles, (const float4*)c->w_nodes, (const int*)parent,
-                           (const int*)first_of, (const int*)count_of, meta + 16, c->w_recs, c->w_qrecs, meta);
-        RTGO_HIP(c, hipGetLastError());
-    }
-    int m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    RTGO_HIP(c, hipMemcpyAsync(m, meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (m[2] > whitted::kMaxWalkDepth && sah) {
-        // the surface-area tree came out deeper than the walk's stack (it has no depth bound of its own): back to the Morton records,
-        // whose depth is bounded by the code length
-        hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, c->w_positions, c->w_indices, (int)n_triangles, c->w_nodes,
-                           parent, visit, first_of, count_of, rec_of, c->w_recs, c->w_tris, c->w_qrecs, c->w_tidx, meta);
-        RTGO_HIP(c, hipGetLastError());
-        RTGO_HIP(c, hipMemcpyAsync(m, meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
-        RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    if (m[0] > 2 * whitted::kStack)
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_mesh: triangle LBVH depth " + std::to_string(m[0]) + " exceeds what the build handles (" +
-                                               std::to_string(2 * whitted::kStack) + ")");
-    if (m[2] > whitted::kMaxWalkDepth)
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_mesh: the walk needs " + std::to_string(m[2]) + " stack entries (limit " +
-                                               std::to_string(whitted::kMaxWalkDepth) + ")");
+    int m[9];
+    const int rc = whitted_build(c, c->w_positions, c->w_indices, (int)n_triangles, c->w_nodes, c->w_scratch, c->w_recs, c->w_tris, c->w_qrecs, c->w_tidx, m,
+                                 "rtgo_whitted_set_mesh");
+    if (rc) return rc;
     c->w_n_recs = m[1];
     c->w_n_vertices = (int)n_vertices;
     std::memcpy(&c->w_grid_lo, &m[3], 3 * sizeof(float));
     std::memcpy(&c->w_grid_step, &m[6], 3 * sizeof(float));
     c->w_walk_depth = m[2] < 1 ? 1 : m[2];
-    if (!c->w_tile_counters) {
-        const size_t heads_bytes = 2 * (size_t)whitted::kTileHeads * whitted::kTileHeadStride * sizeof(unsigned int);
-        RTGO_HIP(c, hipMalloc(&c->w_tile_counters, heads_bytes));
-        RTGO_HIP(c, hipMemsetAsync(c->w_tile_counters, 0, heads_bytes, c->stream));
-        RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    }
+    const int rc2 = whitted_tile_heads(c);
+    if (rc2) return rc2;
     c->w_triangles = (int)n_triangles;
     c->w_n_materials = (int)n_materials;
     return RTGO_OK;
+}
+
+// ---- instanced scenes ----------------------------------------------------------------------------------------------------
+// The instances' side, checked and laid out on the host before anything on the device changes: per instance its InstShade record
+// (o2w as given, W2O = its inverse in double, rounded once) and its world box (the 8 corners of its mesh's box through o2w in double,
+// rounded outwards), which the top-level build takes as the degenerate triangle (lo, hi, lo).
+static int whitted_prepare_instances(rtgo_ctx* c, const std::vector<WhittedMeshInfo>& meshes, uint32_t n_materials, const rtgo_whitted_instance* inst,
+                                     uint32_t n, std::vector<whitted::InstShade>& shade, std::vector<float>& box_pos, const char* what)
+{
+    const std::string w(what);
+    if (!inst) return fail(c, RTGO_E_INVALID, w + ": NULL instance array");
+    if (n == 0 || n > RTGO_WHITTED_MAX_INSTANCES)
+        return fail(c, RTGO_E_UNSUPPORTED, w + ": instance count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_INSTANCES) + "]");
+    shade.assign(n, whitted::InstShade{});
+    box_pos.assign((size_t)6 * n, 0.0f);
+    for (uint32_t i = 0; i < n; ++i) {
+        const rtgo_whitted_instance& q = inst[i];
+        const std::string at = w + ": instance " + std::to_string(i);
+        if (q.mesh >= meshes.size()) return fail(c, RTGO_E_INVALID, at + " names a mesh beyond the meshes array");
+        const WhittedMeshInfo& mi = meshes[q.mesh];
+        if ((uint64_t)q.material_offset + mi.max_material >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material offset + material index beyond the material array");
+        bool finite = true;
+        for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(q.transform[k]);
+        // the walk takes rays to object space through the inverse: the transform must be finite and invertible (the analytic path's
+        // test of a model matrix, rtgo_set_scene)
+        double A[3][4];
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 4; ++k) A[r][k] = q.transform[4 * r + k];
+        const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                           A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+        if (!finite || !std::isfinite(det) || std::fabs(det) < 1e-30) return fail(c, RTGO_E_INVALID, at + " has a non-finite or singular transform");
+        double B[3][4];   // the inverse: adj(A) / det, then -A^-1 t
+        B[0][0] = (A[1][1] * A[2][2] - A[1][2] * A[2][1]) / det;
+        B[0][1] = (A[0][2] * A[2][1] - A[0][1] * A[2][2]) / det;
+        B[0][2] = (A[0][1] * A[1][2] - A[0][2] * A[1][1]) / det;
+        B[1][0] = (A[1][2] * A[2][0] - A[1][0] * A[2][2]) / det;
+        B[1][1] = (A[0][0] * A[2][2] - A[0][2] * A[2][0]) / det;
+        B[1][2] = (A[0][2] * A[1][0] - A[0][0] * A[1][2]) / det;
+        B[2][0] = (A[1][0] * A[2][1] - A[1][1] * A[2][0]) / det;
+        B[2][1] = (A[0][1] * A[2][0] - A[0][0] * A[2][1]) / det;
+        B[2][2] = (A[0][0] * A[1][1] - A[0][1] * A[1][0]) / det;
+        for (int r = 0; r < 3; ++r) B[r][3] = -(B[r][0] * A[0][3] + B[r][1] * A[1][3] + B[r][2] * A[2][3]);
+        whitted::InstShade& sh = shade[i];
+        float* o2w = &sh.o2w[0].x;
+        float* w2o = &sh.w2o[0].x;
+        for (int k = 0; k < 12; ++k) {
+            o2w[k] = q.transform[k];
+            w2o[k] = (float)B[k / 4][k % 4];
+            if (!std::isfinite(w2o[k])) return fail(c, RTGO_E_INVALID, at + " has a non-finite or singular transform");
+        }
+        sh.material_offset = (int)q.material_offset;
+        sh.vert_base = mi.vert_base;
+        sh.tri_base = mi.tri_base;
+        sh.flags = mi.flags;
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int corner = 0; corner < 8; ++corner) {
+            const double x = (corner & 1) ? mi.hi[0] : mi.lo[0], y = (corner & 2) ? mi.hi[1] : mi.lo[1], z = (corner & 4) ? mi.hi[2] : mi.lo[2];
+            for (int r = 0; r < 3; ++r) {
+                const double v = A[r][0] * x + A[r][1] * y + A[r][2] * z + A[r][3];
+                lo[r] = std::fmin(lo[r], v);
+                hi[r] = std::fmax(hi[r], v);
+            }
+        }
+        for (int r = 0; r < 3; ++r) {
+            float l = (float)lo[r], h = (float)hi[r];
+            if ((double)l > lo[r]) l = std::nextafter(l, -INFINITY);
+            if ((double)h < hi[r]) h = std::nextafter(h, INFINITY);
+            if (!std::isfinite(l) || !std::isfinite(h)) return fail(c, RTGO_E_INVALID, at + " places its mesh beyond the float range");
+            box_pos[6 * i + r] = l;
+            box_pos[6 * i + 3 + r] = h;
+        }
+    }
+    return RTGO_OK;
+}
+
+// the top level over prepared instances: build_kernel + sah_kernel over the instance boxes, the InstWalk records in leaf order, and the
+// stack both levels need.  Replaces the context's top level only once all of it succeeded.
+static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos, const rtgo_whitted_instance* inst,
+                             const char* what)
+{
+    const int n = (int)shade.size();
+    std::vector<unsigned int> box_idx((size_t)3 * n);
+    for (int i = 0; i < n; ++i) {
+        box_idx[3 * i + 0] = 2 * i;
+        box_idx[3 * i + 1] = 2 * i + 1;
+        box_idx[3 * i + 2] = 2 * i;
+    }
+    float* d_pos = nullptr;
+    unsigned int* d_idx = nullptr;
+    float4 *d_nodes = nullptr, *d_recs = nullptr, *d_tris = nullptr;
+    int* d_scratch = nullptr;
+    uint4* d_qrecs = nullptr;
+    uint2* d_tidx = nullptr;
+    whitted::InstWalk* d_inst = nullptr;
+    whitted::InstShade* d_shade = nullptr;
+    auto cleanup = [&]() {
+        release(d_pos);
+        release(d_idx);
+        release(d_nodes);
+        release(d_tris);
+        release(d_scratch);
+        release(d_qrecs);
+        release(d_tidx);
+    };
+    auto fail_all = [&](int rc) {
+        cleanup();
+        release(d_recs);
+        release(d_inst);
+        release(d_shade);
+        return rc;
+    };
+#define RTGO_TOP_HIP(x)                                                                                                    \
+    do {                                                                                                                   \
+        const hipError_t e_ = (x);                                                                                         \
+        if (e_ != hipSuccess) return fail_all(fail(c, RTGO_E_HIP_BASE + (int)e_, std::string(what) + ": " + hipGetErrorString(e_))); \
+    } while (0)
+    RTGO_TOP_HIP(hipMalloc(&d_pos, box_pos.size() * sizeof(float)));
+    RTGO_TOP_HIP(hipMalloc(&d_idx, box_idx.size() * sizeof(unsigned int)));
+    RTGO_TOP_HIP(hipMalloc(&d_nodes, (size_t)(2 * n - 1) * 2 * sizeof(float4)));
+    RTGO_TOP_HIP(hipMalloc(&d_recs, (size_t)n * 4 * sizeof(float4)));
+    RTGO_TOP_HIP(hipMalloc(&d_tris, (size_t)n * 3 * sizeof(float4)));
+    RTGO_TOP_HIP(hipMalloc(&d_qrecs, (size_t)n * 2 * sizeof(uint4)));
+    RTGO_TOP_HIP(hipMalloc(&d_tidx, (size_t)n * sizeof(uint2)));
+    RTGO_TOP_HIP(hipMalloc(&d_scratch, (size_t)(38 * n + 16) * sizeof(int)));
+    RTGO_TOP_HIP(hipMemcpyAsync(d_pos, box_pos.data(), box_pos.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RTGO_TOP_HIP(hipMemcpyAsync(d_idx, box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+    int m[9];
+    const int rc = whitted_build(c, d_pos, d_idx, n, d_nodes, d_scratch, d_recs, d_tris, d_qrecs, d_tidx, m, what);
+    if (rc) return fail_all(rc);
+    // leaf order: build_kernel's Morton-ordered "triangles" carry the instance index in .w of their first corner
+    std::vector<float4> order((size_t)3 * n);
+    RTGO_TOP_HIP(hipMemcpyAsync(order.data(), d_tris, order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_TOP_HIP(hipStreamSynchronize(c->stream));
+    const int top_depth = m[1] > 0 ? m[2] : 0;
+    const int depth = top_depth + c->w_mesh_depth;
+    if (depth > whitted::kMaxInstWalkDepth)
+        return fail_all(fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
+                                                        std::to_string(whitted::kMaxInstWalkDepth) + ")"));
+    std::vector<whitted::InstWalk> walk((size_t)n);
+    for (int pos = 0; pos < n; ++pos) {
+        int i;
+        std::memcpy(&i, &order[3 * pos].w, sizeof i);
+        const WhittedMeshInfo& mi = c->w_meshes[inst[i].mesh];
+        walk[pos] = whitted::InstWalk{{shade[i].w2o[0], shade[i].w2o[1], shade[i].w2o[2]}, mi.rec_base, mi.tri_base, mi.root, i};
+    }
+    RTGO_TOP_HIP(hipMalloc(&d_inst, walk.size() * sizeof(whitted::InstWalk)));
+    RTGO_TOP_HIP(hipMalloc(&d_shade, shade.size() * sizeof(whitted::InstShade)));
+    RTGO_TOP_HIP(hipMemcpyAsync(d_inst, walk.data(), walk.size() * sizeof(whitted::InstWalk), hipMemcpyHostToDevice, c->stream));
+    RTGO_TOP_HIP(hipMemcpyAsync(d_shade, shade.data(), shade.size() * sizeof(whitted::InstShade), hipMemcpyHostToDevice, c->stream));
+    RTGO_TOP_HIP(hipStreamSynchronize(c->stream));
+#undef RTGO_TOP_HIP
+    cleanup();
+    free_top(c);
+    c->w_top_recs = d_recs;
+    c->w_inst = d_inst;
+    c->w_inst_shade = d_shade;
+    c->w_n_top_recs = m[1];
+    c->w_n_instances = n;
+    c->w_walk_depth = depth < 1 ? 1 : depth;
+    return RTGO_OK;
+}
+
+int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances, uint32_t n_instances,
+                           const rtgo_pbr* materials, uint32_t n_materials)
+{
+    if (!c || !meshes || !instances || !materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_scene: NULL argument");
+    if (n_meshes == 0 || n_meshes > RTGO_WHITTED_MAX_MESHES || n_materials == 0)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_scene: mesh count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESHES) + "], materials non-empty");
+    // every mesh as rtgo_whitted_set_mesh checks it, and where it will sit in the arrays
+    std::vector<WhittedMeshInfo> info(n_meshes);
+    size_t n_vert = 0, n_tri = 0;
+    int max_tri = 0;
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        const rtgo_whitted_mesh& q = meshes[k];
+        const std::string at = "rtgo_whitted_set_scene: mesh " + std::to_string(k);
+        if (!q.positions || !q.indices) return fail(c, RTGO_E_INVALID, at + ": NULL positions or indices");
+        if (q.n_triangles == 0 || q.n_triangles > RTGO_MAX_TRIANGLES || q.n_vertices == 0)
+            return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_MAX_TRIANGLES) + "], vertices non-empty");
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (uint32_t i = 0; i < 3 * q.n_triangles; ++i) {
+            if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
+        }
+        for (uint32_t i = 0; i < 3 * q.n_vertices; ++i)
+            if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
+        if (q.texcoords)
+            for (uint32_t i = 0; i < 2 * q.n_vertices; ++i)
+                if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + ": non-finite texture coordinate");
+        for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::fmin(lo[a], q.positions[3 * q.indices[i] + a]);
+                hi[a] = std::fmax(hi[a], q.positions[3 * q.indices[i] + a]);
+            }
+        WhittedMeshInfo& mi = info[k];
+        mi.max_material = 0;
+        if (q.material_of_triangle)
+            for (uint32_t i = 0; i < q.n_triangles; ++i) {
+                if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material index beyond the material array");
+                mi.max_material = std::max(mi.max_material, q.material_of_triangle[i]);
+            }
+        // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
+        float maxext = 0.0f;
+        for (int a = 0; a < 3; ++a) maxext = std::fmax(maxext, hi[a] - lo[a]);
+        const float pad = 2.0f * (maxext * 1e-4f + 1e-6f);
+        for (int a = 0; a < 3; ++a) {
+            mi.lo[a] = lo[a] - pad;
+            mi.hi[a] = hi[a] + pad;
+        }
+        mi.rec_base = (int)n_tri;   // (a mesh of n triangles has fewer than n records)
+        mi.tri_base = (int)n_tri;
+        mi.vert_base = (int)n_vert;
+        mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
+        mi.root = 0;
+        mi.depth = 0;
+        n_vert += q.n_vertices;
+        n_tri += q.n_triangles;
+        max_tri = std::max(max_tri, (int)q.n_triangles);
+    }
+    std::vector<whitted::InstShade> shade;
+    std::vector<float> box_pos;
+    int rc = whitted_prepare_instances(c, info, n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_scene");
+    if (rc) return rc;
+    // the meshes back to back (indices stay relative to their mesh's vertices: each build reads its own slice)
+    std::vector<float> pos(3 * n_vert), nrm(3 * n_vert, 0.0f), uv(2 * n_vert, 0.0f);
+    std::vector<unsigned int> idx(3 * n_tri), tmat(n_tri, 0u);
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        const rtgo_whitted_mesh& q = meshes[k];
+        const WhittedMeshInfo& mi = info[k];
+        std::memcpy(&pos[3 * (size_t)mi.vert_base], q.positions, (size_t)q.n_vertices * 3 * sizeof(float));
+        if (q.normals) std::memcpy(&nrm[3 * (size_t)mi.vert_base], q.normals, (size_t)q.n_vertices * 3 * sizeof(float));
+        if (q.texcoords) std::memcpy(&uv[2 * (size_t)mi.vert_base], q.texcoords, (size_t)q.n_vertices * 2 * sizeof(float));
+        std::memcpy(&idx[3 * (size_t)mi.tri_base], q.indices, (size_t)q.n_triangles * 3 * sizeof(unsigned int));
+        if (q.material_of_triangle) std::memcpy(&tmat[mi.tri_base], q.material_of_triangle, (size_t)q.n_triangles * sizeof(unsigned int));
+    }
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    free_mesh(c);
+    auto upload = [&](auto*& d, const auto& v) -> hipError_t {
+        hipError_t e = hipMalloc(&d, v.size() * sizeof(v[0]));
+        if (e == hipSuccess) e = hipMemcpyAsync(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream);
+        return e;
+    };
+    RTGO_HIP(c, upload(c->w_positions, pos));
+    RTGO_HIP(c, upload(c->w_normals, nrm));
+    RTGO_HIP(c, upload(c->w_texcoords, uv));
+    RTGO_HIP(c, upload(c->w_indices, idx));
+    RTGO_HIP(c, upload(c->w_tri_material, tmat));
+    RTGO_HIP(c, hipMalloc(&c->w_materials, (size_t)n_materials * sizeof(whitted::Pbr)));
+    RTGO_HIP(c, hipMemcpyAsync(c->w_materials, materials, (size_t)n_materials * sizeof(whitted::Pbr), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMalloc(&c->w_nodes, (size_t)(2 * max_tri - 1) * 2 * sizeof(float4)));
+    RTGO_HIP(c, hipMalloc(&c->w_scratch, (size_t)(38 * max_tri + 16) * sizeof(int)));
+    RTGO_HIP(c, hipMalloc(&c->w_recs, n_tri * 4 * sizeof(float4)));
+    RTGO_HIP(c, hipMalloc(&c->w_tris, n_tri * 3 * sizeof(float4)));
+    RTGO_HIP(c, hipMalloc(&c->w_qrecs, n_tri * 2 * sizeof(uint4)));
+    RTGO_HIP(c, hipMalloc(&c->w_tidx, n_tri * sizeof(uint2)));
+    // bottom level: each mesh's own structure, as rtgo_whitted_set_mesh builds it, in its slice of the arrays
+    int mesh_depth = 0;
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        WhittedMeshInfo& mi = info[k];
+        const int nt = (int)meshes[k].n_triangles;
+        int m[9];
+        rc = whitted_build(c, c->w_positions + 3 * (size_t)mi.vert_base, c->w_indices + 3 * (size_t)mi.tri_base, nt, c->w_nodes, c->w_scratch,
+                           c->w_recs + 4 * (size_t)mi.rec_base, c->w_tris + 3 * (size_t)mi.tri_base, c->w_qrecs + 2 * (size_t)mi.tri_base,
+                           c->w_tidx + mi.tri_base, m, "rtgo_whitted_set_scene");
+        if (rc) {
+            free_mesh(c);
+            return rc;
+        }
+        mi.root = m[1] > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
+        mi.depth = m[1] > 0 ? m[2] : 0;
+        mesh_depth = std::max(mesh_depth, mi.depth);
+    }
+    c->w_meshes = info;
+    c->w_mesh_depth = mesh_depth;
+    c->w_n_materials = (int)n_materials;
+    rc = whitted_build_top(c, shade, box_pos, instances, "rtgo_whitted_set_scene");
+    if (rc == RTGO_OK) rc = whitted_tile_heads(c);
+    if (rc) {
+        free_mesh(c);
+        return rc;
+    }
+    c->w_n_vertices = (int)n_vert;
+    c->w_instanced = true;
+    c->w_triangles = (int)std::min(n_tri, (size_t)0x7FFFFFFF);
+    return RTGO_OK;
+}
+
+int rtgo_whitted_set_instances(rtgo_ctx* c, const rtgo_whitted_instance* instances, uint32_t n_instances)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (!c->w_instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_instances: no instanced scene (call rtgo_whitted_set_scene first)");
+    std::vector<whitted::InstShade> shade;
+    std::vector<float> box_pos;
+    int rc = whitted_prepare_instances(c, c->w_meshes, (uint32_t)c->w_n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_instances");
+    if (rc) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    return whitted_build_top(c, shade, box_pos, instances, "rtgo_whitted_set_instances");
 }
 
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
 {
     if (!c) return RTGO_E_INVALID;
     if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: no mesh (call rtgo_whitted_set_mesh first)");
+    if (c->w_instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: an instanced scene takes its texture coordinates per mesh (rtgo_whitted_set_scene)");
     if (uv && n_vertices != (uint32_t)c->w_n_vertices) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_texcoords: one (u, v) per vertex of the mesh");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
@@ -1556,10 +1915,61 @@ int rtgo_whitted_set_miss_color(rtgo_ctx* c, const float rgb[3])
     return RTGO_OK;
 }
 
+// the launch of an instanced scene: rtgo_whitted_launch's frame, tile queue and buffers over the two-level structure.  The top level's
+// records and InstWalk array go to LDS beside the stacks when they fit (and RTGO_WHITTED_MODE allows any LDS residency); the meshes'
+// records and triangles are read through L2 (kAllInL2's way).
+static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Params& p, int mode_cap, unsigned int blocks)
+{
+    whitted::InstParams q;
+    std::memset(&q, 0, sizeof q);
+    q.top_recs = c->w_top_recs;
+    q.inst = c->w_inst;
+    q.shade = c->w_inst_shade;
+    q.n_top_recs = c->w_n_top_recs;
+    q.n_instances = c->w_n_instances;
+    q.recs = c->w_recs;
+    q.tris = c->w_tris;
+    q.positions = c->w_positions;
+    q.normals = c->w_normals;
+    q.texcoords = c->w_texcoords;
+    q.indices = c->w_indices;
+    q.tri_material = c->w_tri_material;
+    q.stack_depth = c->w_walk_depth;
+    q.tile_counter = p.tile_counter;
+    q.tile_counter_next = p.tile_counter_next;
+    q.tiles_x = p.tiles_x;
+    q.tiles_y = p.tiles_y;
+    q.tile_stride = p.tile_stride;
+    q.mat_tex = p.mat_tex;
+    q.materials = p.materials;
+    q.lights = p.lights;
+    q.n_lights = p.n_lights;
+    q.accum = p.accum;
+    q.image = p.image;
+    q.width = p.width;
+    q.height = p.height;
+    q.subframe = p.subframe;
+    q.eye = p.eye;
+    q.U = p.U;
+    q.V = p.V;
+    q.W = p.W;
+    q.miss = p.miss;
+    q.counters = p.counters;
+    const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)q.stack_depth * sizeof(unsigned short);
+    const size_t top_bytes = (size_t)q.n_top_recs * 4 * sizeof(float4) + (size_t)q.n_instances * sizeof(whitted::InstWalk);
+    const size_t lds_cap = 160 * 1024;
+    if (mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= lds_cap)
+        hipLaunchKernelGGL(whitted::render_inst_kernel<true>, dim3(blocks), dim3(whitted::kRenderBlock), top_bytes + stack_bytes, c->stream, q);
+    else
+        hipLaunchKernelGGL(whitted::render_inst_kernel<false>, dim3(blocks), dim3(whitted::kRenderBlock), stack_bytes, c->stream, q);
+    RTGO_HIP(c, hipGetLastError());
+    return RTGO_OK;
+}
+
 int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t subframe_index)
 {
     if (!c) return RTGO_E_INVALID;
-    if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no mesh (call rtgo_whitted_set_mesh)");
+    if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene)");
     if (!c->have_camera) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no camera (call rtgo_set_camera)");
     if (!c->d_accum || !c->d_image) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no output (call rtgo_resize or rtgo_bind_output)");
     if (width == 0 || height == 0 || (uint64_t)width * height > c->pixels) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image empty or larger than the output buffers");
@@ -1630,7 +2040,10 @@ int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t s
     const unsigned int n_tiles = p.tiles_x * p.tiles_y;
     unsigned int blocks = (n_tiles + (whitted::kRenderBlock / 64) - 1) / (whitted::kRenderBlock / 64);
     if (blocks > (unsigned int)c->num_cus) blocks = (unsigned int)c->num_cus;
-    if (mode == whitted::kAllInLds) hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
+    if (c->w_instanced) {
+        const int rc = whitted_enqueue_instanced(c, p, mode_cap, blocks);
+        if (rc) return rc;
+    } else if (mode == whitted::kAllInLds) hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
     else if (mode == whitted::kRecordsInLds) hipLaunchKernelGGL(whitted::render_kernel<whitted::kRecordsInLds>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
     else hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInL2>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
     RTGO_HIP(c, hipGetLastError());
