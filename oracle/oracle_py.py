@@ -64,6 +64,22 @@ class WhittedScene(C.Structure):
                 ("V", C.c_float * 3), ("W", C.c_float * 3), ("miss", C.c_float * 3), ("texcoords", C.c_void_p), ("mat_tex", C.c_void_p)]
 
 
+class WhittedMesh(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("texcoords", C.c_void_p), ("indices", C.c_void_p),
+                ("tri_material", C.c_void_p), ("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32)]
+
+
+class WhittedInstance(C.Structure):
+    _fields_ = [("transform", C.c_float * 12), ("mesh", C.c_uint32), ("material_offset", C.c_uint32)]
+
+
+class WhittedIScene(C.Structure):
+    _fields_ = [("meshes", C.c_void_p), ("instances", C.c_void_p), ("materials", C.c_void_p), ("lights", C.c_void_p), ("mat_tex", C.c_void_p),
+                ("n_meshes", C.c_uint32), ("n_instances", C.c_uint32), ("n_materials", C.c_uint32), ("n_lights", C.c_uint32),
+                ("eye", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3), ("miss", C.c_float * 3),
+                ("cull", C.c_int32)]
+
+
 class Tex(C.Structure):
     _fields_ = [("px", C.c_void_p), ("w", C.c_uint32), ("h", C.c_uint32)]
 
@@ -123,6 +139,12 @@ def lib():
         L.oracle_whitted_render.restype = C.c_int
         L.oracle_whitted_render.argtypes = [C.POINTER(WhittedScene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_uint64), C.c_int]
+        L.oracle_whitted_render_instanced.restype = C.c_int
+        L.oracle_whitted_render_instanced.argtypes = [C.POINTER(WhittedIScene), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_uint64), C.c_int]
+        L.oracle_whitted_trace_instanced.restype = C.c_int
+        L.oracle_whitted_trace_instanced.argtypes = [C.POINTER(WhittedIScene), fp, fp, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                     fp, fp, fp]
         L.oracle_tex2d.restype = None
         L.oracle_tex2d.argtypes = [C.POINTER(Tex), C.c_float, C.c_float, fp]
         L.oracle_material.restype = C.c_int
@@ -285,23 +307,100 @@ def whitted_render(mesh, cam12, width, height, subframes=1, threads=0):
     uv = None if mesh.get("texcoords") is None else np.ascontiguousarray(mesh["texcoords"], dtype=np.float32)
     s.texcoords = uv.ctypes.data if uv is not None else None
     keep = []
-    mt = None
-    if mesh.get("textures"):
-        mt = (MatTex * len(mats))()
-        for mi, triple in mesh["textures"].items():
-            for name, t in zip(("base_color", "metallic_roughness", "normal"), triple):
-                if t is None:
-                    continue
-                a = np.ascontiguousarray(t, dtype=np.uint8)
-                keep.append(a)
-                setattr(mt[mi], name, Tex(a.ctypes.data, a.shape[1], a.shape[0]))
+    mt = _mat_tex(mesh.get("textures"), len(mats), keep)
+    if mt is not None:
         s.mat_tex = C.addressof(mt)
+    return _whitted_frames(lib().oracle_whitted_render, s, width, height, subframes, threads)
+
+
+def _threads(threads):
+    if threads <= 0:
+        threads = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 1
+    return threads
+
+
+def _whitted_frames(fn, s, width, height, subframes, threads):
     acc = np.zeros((height, width, 4), dtype=np.float32)
     img = np.zeros((height, width, 4), dtype=np.uint8)
     rays = (C.c_uint64 * 2)(0, 0)
-    if threads <= 0:
-        threads = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 1
     for sf in range(subframes):
-        rc = lib().oracle_whitted_render(C.byref(s), width, height, sf, acc.ctypes.data, img.ctypes.data, rays, threads)
+        rc = fn(C.byref(s), width, height, sf, acc.ctypes.data, img.ctypes.data, rays, _threads(threads))
         assert rc == 0
     return acc, img, {"rays_total": int(rays[0]), "rays_occlusion": int(rays[1])}
+
+
+def _mat_tex(textures, n_materials, keep):
+    """{material index: (base_color, metallic_roughness, normal)}, each uint8 [h, w, 4] or None -> MatTex array (or None)"""
+    if not textures:
+        return None
+    mt = (MatTex * n_materials)()
+    for mi, triple in textures.items():
+        for name, t in zip(("base_color", "metallic_roughness", "normal"), triple):
+            if t is None:
+                continue
+            a = np.ascontiguousarray(t, dtype=np.uint8)
+            keep.append(a)
+            setattr(mt[mi], name, Tex(a.ctypes.data, a.shape[1], a.shape[0]))
+    keep.append(mt)
+    return mt
+
+
+class InstancedScene:
+    """an oracle_whitted_iscene over what Context.whitted_set_scene takes -- meshes (dicts: positions, normals or None, indices,
+    tri_material or None, optional texcoords), instances [(3x4 transform, mesh, material_offset)], materials [n, 6] -- plus `extra`
+    (lights [nl, 8], miss (3,), optional textures {material: (base_color, metallic_roughness, normal)}) and a camera (eye, U, V, W)"""
+
+    def __init__(self, meshes, instances, materials, extra=None, cam12=None, cull=True):
+        keep = self._keep = []
+
+        def arr(a, dt, cols):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt).reshape((-1, cols) if cols else -1)
+            keep.append(a)
+            return a
+
+        ms = (WhittedMesh * len(meshes))()
+        for k, m in enumerate(meshes):
+            pos, nrm, uv = arr(m["positions"], np.float32, 3), arr(m.get("normals"), np.float32, 3), arr(m.get("texcoords"), np.float32, 2)
+            idx, tm = arr(m["indices"], np.uint32, 3), arr(m.get("tri_material"), np.uint32, 0)
+            ms[k] = WhittedMesh(pos.ctypes.data, nrm.ctypes.data if nrm is not None else None, uv.ctypes.data if uv is not None else None,
+                                idx.ctypes.data, tm.ctypes.data if tm is not None else None, len(pos), len(idx))
+        ins = (WhittedInstance * max(len(instances), 1))()
+        for k, (tr, mi, off) in enumerate(instances):
+            ins[k].transform[:] = np.asarray(tr, dtype=np.float32).reshape(-1)[:12].tolist()
+            ins[k].mesh, ins[k].material_offset = int(mi), int(off)
+        mats = arr(materials, np.float32, 6)
+        extra = extra or {}
+        lights = arr(extra.get("lights", np.zeros((0, 8), np.float32)), np.float32, 8)
+        keep += [ms, ins]
+        s = self.s = WhittedIScene()
+        s.meshes, s.instances, s.materials = C.addressof(ms), C.addressof(ins), mats.ctypes.data
+        s.lights = lights.ctypes.data if len(lights) else None
+        mt = _mat_tex(extra.get("textures"), len(mats), keep)
+        s.mat_tex = C.addressof(mt) if mt is not None else None
+        s.n_meshes, s.n_instances, s.n_materials, s.n_lights = len(meshes), len(instances), len(mats), len(lights)
+        if cam12 is not None:
+            cam = f32(cam12)
+            s.eye[:], s.U[:], s.V[:], s.W[:] = cam[0:3].tolist(), cam[3:6].tolist(), cam[6:9].tolist(), cam[9:12].tolist()
+        s.miss[:] = f32(extra.get("miss", np.zeros(3, np.float32))).tolist()
+        s.cull = 1 if cull else 0
+
+    def render(self, width, height, subframes=1, threads=0):
+        return _whitted_frames(lib().oracle_whitted_render_instanced, self.s, width, height, subframes, threads)
+
+    def trace(self, o, d, tmin=0.01, tmax=1e16):
+        """oracle_whitted_trace_instanced: (instance, triangle, t, u, v) of the closest hit of the world ray, or None"""
+        o, d = f32(o), f32(d)
+        ii, tri = C.c_int(-1), C.c_int(-1)
+        t, u, v = C.c_float(0), C.c_float(0), C.c_float(0)
+        rc = lib().oracle_whitted_trace_instanced(C.byref(self.s), fptr(o), fptr(d), tmin, tmax, C.byref(ii), C.byref(tri), C.byref(t), C.byref(u),
+                                                  C.byref(v))
+        assert rc >= 0, "invalid instanced scene"
+        return (ii.value, tri.value, t.value, u.value, v.value) if rc else None
+
+
+def whitted_render_instanced(meshes, instances, materials, extra, cam12, width, height, subframes=1, threads=0, cull=True):
+    """the oracle's whitted path over an instanced scene (oracle_whitted_render_instanced), `subframes` accumulated: what
+    Context.whitted_set_scene takes, `extra` as InstancedScene.  Returns (accum [h,w,4] f32, image [h,w,4] u8, {rays_total, rays_occlusion})."""
+    return InstancedScene(meshes, instances, materials, extra, cam12, cull).render(width, height, subframes, threads)

@@ -161,6 +161,33 @@ int oracle_tri_intersect(const float* p0, const float* p1, const float* p2, cons
 int oracle_whitted_render(const oracle_whitted_scene* s, uint32_t width, uint32_t height, uint32_t subframe, float* accum, uint8_t* image,
                           uint64_t* rays, int threads);
 
+/* instanced meshes: object-space meshes drawn by instances in instance order */
+typedef struct {
+    const float* positions;          /* 3 per vertex, object space */
+    const float* normals;            /* 3 per vertex or NULL (N = W2O^T Ng) */
+    const float* texcoords;          /* 2 per vertex or NULL (UV = barycentrics) */
+    const uint32_t* indices;         /* 3 per triangle, relative to this mesh */
+    const uint32_t* tri_material;    /* per triangle or NULL (0), before the instance's material offset */
+    uint32_t n_vertices, n_triangles;
+} oracle_whitted_mesh;
+typedef struct { float transform[12]; uint32_t mesh, material_offset; } oracle_whitted_instance;   /* row-major 3x4 object-to-world */
+typedef struct {
+    const oracle_whitted_mesh* meshes;
+    const oracle_whitted_instance* instances;
+    const oracle_pbr* materials;
+    const oracle_point_light* lights;
+    const oracle_mat_tex* mat_tex;   /* per material or NULL */
+    uint32_t n_meshes, n_instances, n_materials, n_lights;
+    float eye[3], U[3], V[3], W[3], miss[3];
+    int32_t cull;                    /* 1: skip instances whose object-space box (grown) the ray's line misses; 0: brute force */
+} oracle_whitted_iscene;
+/* oracle_whitted_render over an instanced scene; -1 on an invalid scene (mesh index, material range, singular transform) */
+int oracle_whitted_render_instanced(const oracle_whitted_iscene* s, uint32_t width, uint32_t height, uint32_t subframe, float* accum,
+                                    uint8_t* image, uint64_t* rays, int threads);
+/* one closest-hit ray in world space: 1 and (instance, triangle, t, u, v) on a hit, 0 on a miss, -1 on an invalid scene */
+int oracle_whitted_trace_instanced(const oracle_whitted_iscene* s, const float* o, const float* d, float tmin, float tmax, int* instance,
+                                   int* triangle, float* t, float* u, float* v);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,10 @@
 """Instanced scenes for the whitted path (rtgo_whitted_set_scene) and their flattened equivalents.
 
-There is no instanced oracle: the independent reference for an instanced scene is the same scene flattened here -- every instance's
-mesh taken to world space in float64 (positions through the object-to-world matrix, vertex normals through W2O^T without
-renormalisation: the oracle normalises after interpolating, as LocalGeometry.h:112 does after transforming), rounded to float32 and
-concatenated in instance order -- and rendered by oracle.whitted_render.  Concatenating in instance order keeps the tie rule: the
-lowest (instance, triangle) is the lowest index of the flattened mesh."""
+The instanced oracle (oracle_py.whitted_render_instanced) draws an instanced scene with the kernel's own arithmetic.  The flattened
+scene is a second, independent formulation: every instance's mesh taken to world space in float64 (positions through the object-to-world
+matrix, vertex normals through W2O^T without renormalisation: the oracle normalises after interpolating, as LocalGeometry.h:112 does after
+transforming), rounded to float32 and concatenated in instance order -- and rendered by oracle.whitted_render.  Concatenating in instance
+order keeps the tie rule: the lowest (instance, triangle) is the lowest index of the flattened mesh."""
 import numpy as np
 
 
@@ -114,3 +114,86 @@ def rotation(rng):
 
 def transform(A, t):
     return np.concatenate([np.asarray(A, np.float64), np.asarray(t, np.float64).reshape(3, 1)], axis=1).astype(np.float32)
+
+
+def materials():
+    """four materials: dielectric rough, dielectric glossy, mixed, metal"""
+    return np.array([[0.8, 0.8, 0.75, 1.0, 0.0, 0.9], [0.9, 0.25, 0.2, 1.0, 0.1, 0.35], [0.3, 0.5, 0.9, 1.0, 0.6, 0.3],
+                     [0.95, 0.8, 0.3, 1.0, 1.0, 0.25]], np.float32)
+
+
+def lights():
+    """two point lights and a miss colour (the `extra` of oracle_py.whitted_render_instanced)"""
+    ls = np.zeros((2, 8), dtype=np.float32)
+    ls[0] = [1.0, 0.95, 0.9, 2.5, 1.0, 6.0, 2.0, 0]
+    ls[1] = [0.6, 0.7, 1.0, 1.0, -4.0, 3.0, -1.0, 0]
+    return {"lights": ls, "miss": np.array([0.1, 0.15, 0.25], np.float32)}
+
+
+def tori_scene():
+    """20 instances of a 900-triangle torus with vertex normals under random rotations and translations, five of them uniformly and five
+    non-uniformly scaled, over a ground with normals (21 instances, 18 002 triangles)"""
+    rng = np.random.RandomState(7)
+    meshes = [torus(), ground(normals=True)]
+    inst = [(transform(np.eye(3), [0, 0, 0]), 1, 0)]
+    for k in range(20):
+        A = rotation(rng)
+        if 5 <= k < 10:
+            A = 0.7 * A
+        elif 10 <= k < 15:
+            A = A @ np.diag([1.4, 0.6, 1.0]) @ rotation(rng)
+        t = [-2.4 + 1.2 * (k % 5), 0.45 + 0.35 * (k // 10), -2.0 + 1.0 * (k // 5)]
+        inst.append((transform(A, t), 0, 1 + k % 2))
+    return meshes, inst
+
+
+def octahedra_scene(n=4095):
+    """n rigid instances of an 8-triangle octahedron without vertex normals on a 64-wide grid over a ground"""
+    rng = np.random.RandomState(11)
+    meshes = [octahedron(0.09), ground(8.0)]
+    inst = [(transform(np.eye(3), [0, 0, 0]), 1, 0)]
+    for k in range(n):
+        t = [-3.2 + 0.1 * (k % 64), 0.15 + 0.4 * rng.rand(), -3.2 + 0.1 * (k // 64)]
+        inst.append((transform(rotation(rng), t), 0, 1 + k % 3))
+    return meshes, inst
+
+
+def mirror(rng):
+    """a random rotation composed with a reflection (det -1)"""
+    return rotation(rng) @ np.diag([1.0, -1.0, 1.0])
+
+
+def mirrored_scene(smooth, n=12, scale=None, seed=5):
+    """n tori (smooth: with vertex normals) or octahedra (faceted) under rotation x reflection transforms (det < 0), optionally scaled by
+    diag(scale) before the rotation, over a ground (instance 0, identity)"""
+    rng = np.random.RandomState(seed)
+    meshes = [torus() if smooth else octahedron(0.35), ground(normals=smooth)]
+    inst = [(transform(np.eye(3), [0, 0, 0]), 1, 0)]
+    for k in range(n):
+        A = mirror(rng)
+        if scale is not None:
+            A = A @ np.diag(scale)
+        t = [-2.4 + 1.2 * (k % 5), 0.5 + 0.2 * (k % 3), -1.5 + 1.1 * (k // 5)]
+        inst.append((transform(A, t), 0, 1 + k % 2))
+    return meshes, inst
+
+
+def swap_winding(mesh):
+    """the same triangles with their second and third corners exchanged (the geometric normal flips)"""
+    ix = np.asarray(mesh["indices"], np.uint32)
+    return dict(mesh, indices=np.ascontiguousarray(ix[:, [0, 2, 1]]))
+
+
+def small_scene():
+    """a few tori (with normals) and octahedra (faceted) under rotations, uniform and non-uniform scales and reflections, over a ground:
+    the float64 hit reference's scene and oracle_whitted_instances.npz's"""
+    rng = np.random.RandomState(23)
+    meshes = [torus(16, 8), octahedron(0.3), ground(3.0)]
+    inst = [(transform(np.eye(3), [0, 0, 0]), 2, 0)]
+    shapes = [np.eye(3), 0.6 * np.eye(3), np.diag([1.5, 0.5, 1.0]), np.diag([1.0, -1.0, 1.0]), np.diag([-0.7, 1.3, 0.9]), np.diag([2.0, 1.0, 0.4])]
+    for k, S in enumerate(shapes):
+        for mi in (0, 1):
+            A = rotation(rng) @ S
+            t = [-1.5 + 0.6 * k, 0.45 + 0.5 * mi, -0.4 + 0.8 * mi - 0.1 * k]
+            inst.append((transform(A, t), mi, 1 + k % (2 + mi)))
+    return meshes, inst
