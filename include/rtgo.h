@@ -214,7 +214,7 @@ typedef struct rtgo_point_light {
 /* sutil::Scene::addMesh + buildMeshAccels (sutil/Scene.cpp): one triangle mesh in world space = GeometryData::TriangleMesh
    (cuda/GeometryData.h:46-52; positions and optional vertex normals, 3 floats per vertex; 32-bit indices, 3 per triangle) with
    one material per triangle (material_of_triangle may be NULL: material 0).  Builds the triangle LBVH on the device.
-   n_triangles <= RTGO_MAX_TRIANGLES.  Synchronous. */
+   n_triangles <= RTGO_MAX_TRIANGLES (a larger mesh goes through rtgo_whitted_set_scene as one identity instance).  Synchronous. */
 int rtgo_whitted_set_mesh(rtgo_ctx* ctx, const float* positions, const float* normals, uint32_t n_vertices, const uint32_t* indices,
                           const uint32_t* material_of_triangle, uint32_t n_triangles, const rtgo_pbr* materials, uint32_t n_materials);
 
@@ -253,6 +253,11 @@ int rtgo_whitted_launch(rtgo_ctx* ctx, uint32_t width, uint32_t height, uint32_t
    buildInstanceAccel, sutil/Scene.cpp:985-1010) ---- */
 #define RTGO_WHITTED_MAX_MESHES 256
 #define RTGO_WHITTED_MAX_INSTANCES 8192
+/* triangles of one mesh of an instanced scene, and of all its meshes together.  A mesh beyond RTGO_MAX_TRIANGLES is built as a
+   clustered mesh: sorted in Morton order on the device, cut into clusters of consecutive triangles, and joined by a mid level over the
+   clusters' boxes.  It renders bit for bit like the same triangles cut into contiguous identity instances of at most RTGO_MAX_TRIANGLES. */
+#define RTGO_WHITTED_MAX_MESH_TRIANGLES (1 << 24)
+#define RTGO_WHITTED_MAX_SCENE_TRIANGLES (1 << 26)
 
 /* one GAS: GeometryData::TriangleMesh (cuda/GeometryData.h:46-52) in OBJECT space */
 typedef struct rtgo_whitted_mesh {
@@ -262,7 +267,7 @@ typedef struct rtgo_whitted_mesh {
     uint32_t n_vertices;
     const uint32_t* indices;               /* 3 per triangle */
     const uint32_t* material_of_triangle;  /* NULL: 0 */
-    uint32_t n_triangles;                  /* <= RTGO_MAX_TRIANGLES */
+    uint32_t n_triangles;                  /* <= RTGO_WHITTED_MAX_MESH_TRIANGLES (beyond RTGO_MAX_TRIANGLES: a clustered mesh) */
 } rtgo_whitted_mesh;
 
 /* one OptixInstance as Scene::buildInstanceAccel fills it (sutil/Scene.cpp:995-1005) */
@@ -275,15 +280,19 @@ typedef struct rtgo_whitted_instance {
 /* A scene of n_meshes meshes drawn by n_instances instances, and one material table for all of them.  Checks every mesh as
    rtgo_whitted_set_mesh does, and every instance: a mesh index inside the array, material_offset + the mesh's largest material index
    inside the table, a finite and invertible transform (RTGO_E_INVALID).  More than RTGO_WHITTED_MAX_MESHES meshes or
-   RTGO_WHITTED_MAX_INSTANCES instances, a mesh beyond RTGO_MAX_TRIANGLES, or a structure deeper than the walk's stack:
+   RTGO_WHITTED_MAX_INSTANCES instances, a mesh beyond RTGO_WHITTED_MAX_MESH_TRIANGLES, meshes beyond RTGO_WHITTED_MAX_SCENE_TRIANGLES
+   together, or a structure deeper than the walk's stack (top level + mid level + deepest cluster of a clustered mesh):
    RTGO_E_UNSUPPORTED.  Builds both levels on the device; replaces the scene of rtgo_whitted_set_mesh (and that call replaces this
    one); clears every texture.  The closest hit is the smallest t, then the lowest (instance, triangle): an instanced scene renders
-   like the concatenation of its instances.  Synchronous. */
+   like the concatenation of its instances.  Synchronous; a clustered mesh (beyond RTGO_MAX_TRIANGLES) is built cluster by cluster, so the
+   call takes time in proportion to its triangles (about 6 s per million on an MI355X: some 100 s for one mesh at
+   RTGO_WHITTED_MAX_MESH_TRIANGLES). */
 int rtgo_whitted_set_scene(rtgo_ctx* ctx, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances,
                            uint32_t n_instances, const rtgo_pbr* materials, uint32_t n_materials);
 
 /* New transforms, mesh choices or material offsets over the meshes and materials of the last rtgo_whitted_set_scene: rebuilds the top
-   level only.  Same checks and limits as rtgo_whitted_set_scene; textures stay.  Synchronous. */
+   level only (meshes and clustered meshes stay as built).  Same checks and limits as rtgo_whitted_set_scene; a refused call leaves the
+   scene as it was; textures stay.  Synchronous. */
 int rtgo_whitted_set_instances(rtgo_ctx* ctx, const rtgo_whitted_instance* instances, uint32_t n_instances);
 
 /* number of window rows a rank owns under the band interleave (pure host arithmetic) */

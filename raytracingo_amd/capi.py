@@ -27,6 +27,8 @@ SYMBOLS = [
 ]
 RTGO_WHITTED_MAX_MESHES = 256
 RTGO_WHITTED_MAX_INSTANCES = 8192
+RTGO_WHITTED_MAX_MESH_TRIANGLES = 1 << 24     # per mesh of rtgo_whitted_set_scene (beyond RTGO_MAX_TRIANGLES: a clustered mesh)
+RTGO_WHITTED_MAX_SCENE_TRIANGLES = 1 << 26    # all meshes of a scene together
 
 
 class RtgoError(RuntimeError):

@@ -3,6 +3,7 @@
 // There is no CPU fallback anywhere in this file: every path ends in a HIP launch or an error code.
 #include "../../include/rtgo.h"
 #include "rtgo_device.h"
+#include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
 
 #include <algorithm>
@@ -27,8 +28,9 @@ struct WhittedMeshInfo {
     int rec_base, tri_base, vert_base;   // where its records / triangles / vertices start in the context's arrays
     int root;                  // InstWalk::root
     int flags;                 // whitted::kHasNormals | kHasTexcoords
-    int depth;                 // stack entries its walk needs
+    int depth;                 // stack entries its walk needs (a clustered mesh: its mid level's + its deepest cluster's)
     uint32_t max_material;     // its largest material_of_triangle
+    bool clustered;            // beyond kMaxTriangles triangles: a mid level over clusters (rtgo_whitted_big.h)
 };
 
 struct rtgo_ctx {
@@ -170,6 +172,7 @@ struct rtgo_ctx {
     whitted::InstWalk* w_inst = nullptr;       // in the top level's leaf order
     whitted::InstShade* w_inst_shade = nullptr;   // in the caller's order
     int w_n_top_recs = 0, w_n_instances = 0;
+    int4* w_clusters = nullptr;                // the clustered meshes' cluster tables (InstParams::clusters), or null when there are none
     std::string err;
 };
 
@@ -177,6 +180,8 @@ static_assert(sizeof(rtgo_pbr) == sizeof(whitted::Pbr) && sizeof(rtgo_point_ligh
               "whitted records");
 static_assert(RTGO_MAX_TRIANGLES == whitted::kMaxTriangles, "limits");
 static_assert(RTGO_WHITTED_MAX_MESHES == whitted::kMaxMeshes && RTGO_WHITTED_MAX_INSTANCES == whitted::kMaxInstances, "instance limits");
+static_assert(RTGO_WHITTED_MAX_MESH_TRIANGLES == whitted::kBigMaxMeshTriangles && RTGO_WHITTED_MAX_SCENE_TRIANGLES == whitted::kBigMaxSceneTriangles,
+              "clustered mesh limits");
 static_assert(sizeof(rtgo_whitted_instance) == 56 && sizeof(whitted::InstWalk) == 64 && sizeof(whitted::InstShade) == 112, "instance records");
 
 static std::string g_create_error;
@@ -301,6 +306,15 @@ static unsigned int env_uint(const char* name, unsigned int dflt)
     if (!v || !*v) return dflt;
     const long k = std::strtol(v, nullptr, 10);
     return k > 0 ? (unsigned int)k : dflt;
+}
+// RTGO_WHITTED_MODE (test and experiment knob): 0 / 1 / 2 = at most that much of the whitted structure in LDS (kAllInL2 / kRecordsInLds /
+// kAllInLds); unset, empty or negative: kAllInLds, above 2: 2.  (env_uint cannot carry it: 0 is a value here.)
+static int env_whitted_mode()
+{
+    const char* v = std::getenv("RTGO_WHITTED_MODE");
+    if (!v || !*v) return whitted::kAllInLds;
+    const long k = std::strtol(v, nullptr, 10);
+    return k < 0 ? whitted::kAllInLds : (int)std::min<long>(k, whitted::kAllInLds);
 }
 struct Knobs {
     bool debug = std::getenv("RTGO_DEBUG") != nullptr;              // a line per scene and launch on stderr
@@ -476,6 +490,8 @@ int rtgo_create(int device, rtgo_ctx** out)
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kAllInLds>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (err == hipSuccess) err = hipDeviceSynchronize();  // the null-stream memsets above must land before any launch
     if (err != hipSuccess) {
         std::string m = std::string("rtgo_create: ") + hipGetErrorString(err);
@@ -551,6 +567,7 @@ static void free_mesh(rtgo_ctx* c)
     release(c->w_tidx);
     release(c->w_scratch);
     free_top(c);
+    release(c->w_clusters);
     c->w_meshes.clear();
     c->w_instanced = false;
     c->w_mesh_depth = 0;
@@ -1707,6 +1724,125 @@ static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>&
     return RTGO_OK;
 }
 
+// Device scratch of the clustered builds of one rtgo_whitted_set_scene, sized for its largest clustered mesh (freed on every return).
+struct WhittedBigScratch {
+    unsigned long long *keys = nullptr, *keys_alt = nullptr;
+    unsigned int *hist = nullptr, *cidx = nullptr, *mid_idx = nullptr;
+    float *partial = nullptr, *bounds = nullptr, *mid_pos = nullptr;
+    int* crec = nullptr;
+    float4* mid_tris = nullptr;
+    uint4* mid_qrecs = nullptr;
+    uint2* mid_tidx = nullptr;
+    ~WhittedBigScratch()
+    {
+        release(keys);
+        release(keys_alt);
+        release(hist);
+        release(cidx);
+        release(mid_idx);
+        release(partial);
+        release(bounds);
+        release(mid_pos);
+        release(crec);
+        release(mid_tris);
+        release(mid_qrecs);
+        release(mid_tidx);
+    }
+};
+
+// One clustered mesh (n > kMaxTriangles triangles; rtgo_whitted_big.h), in its slices of the context's arrays: Morton order over the
+// whole mesh on the device, clusters of consecutive sorted triangles each built by whitted_build (tris[].w then remapped to the mesh's
+// own indices), and a mid level over the clusters' boxes whose records take the first ncl - 1 record slots of the mesh (the clusters
+// follow: a mesh of n triangles has at most n slots, and a cluster of m triangles fewer than m records).  Appends the mesh's clusters,
+// in the mid level's leaf order, to `table`; sets mi.root, mi.depth, and widens mi.lo / hi over every box the walk can reach from the
+// mesh's root, so the instance boxes built from it contain them by construction.  Synchronous.
+static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, WhittedBigScratch& bs, std::vector<int4>& table, const char* what)
+{
+    using namespace whitted;
+    const int ncl = (n + kClusterTris - 1) / kClusterTris;
+    const float* positions = c->w_positions + 3 * (size_t)mi.vert_base;
+    const unsigned int* indices = c->w_indices + 3 * (size_t)mi.tri_base;
+    // Morton keys over the mesh's bounds, sorted by four stable passes over the code's bytes
+    const int nbb = std::min(1024, (n + 1023) / 1024);
+    hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, positions, indices, n, bs.partial);
+    hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)bs.partial, nbb, bs.bounds);
+    hipLaunchKernelGGL(big_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, positions, indices, n, (const float*)bs.bounds, bs.keys);
+    const int nb = (n + kRadixTile - 1) / kRadixTile;
+    unsigned long long *src = bs.keys, *dst = bs.keys_alt;
+    for (int shift = 32; shift < 64; shift += 8) {
+        hipLaunchKernelGGL(radix_count_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift, bs.hist);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bs.hist, 256 * nb);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift,
+                           (const unsigned int*)bs.hist, dst);
+        std::swap(src, dst);
+    }
+    const unsigned long long* sorted = src;   // (four passes: back in bs.keys)
+    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, sorted, n, indices, bs.cidx);
+    RTGO_HIP(c, hipGetLastError());
+    // the clusters
+    std::vector<int> crec(ncl), croot(ncl);
+    int rec = mi.rec_base + ncl - 1, cdepth = 0;
+    for (int k = 0; k < ncl; ++k) {
+        const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
+        int m[9];
+        const int rc = whitted_build(c, positions, bs.cidx + 3 * (size_t)s, nc, c->w_nodes, c->w_scratch, c->w_recs + 4 * (size_t)rec,
+                                     c->w_tris + 3 * ((size_t)mi.tri_base + s), c->w_qrecs + 2 * ((size_t)mi.tri_base + s), c->w_tidx + mi.tri_base + s, m, what);
+        if (rc) return rc;
+        crec[k] = rec;
+        croot[k] = m[1] > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
+        cdepth = std::max(cdepth, m[1] > 0 ? m[2] : 0);
+        rec += m[1];
+    }
+    hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->w_tris + 3 * (size_t)mi.tri_base, sorted, n, ncl);
+    RTGO_HIP(c, hipGetLastError());
+    // the mid level: the clusters' boxes as the degenerate triangles (lo, hi, lo), the top level's recipe
+    std::vector<unsigned int> box_idx((size_t)3 * ncl);
+    for (int k = 0; k < ncl; ++k) {
+        box_idx[3 * k + 0] = 2 * k;
+        box_idx[3 * k + 1] = 2 * k + 1;
+        box_idx[3 * k + 2] = 2 * k;
+    }
+    RTGO_HIP(c, hipMemcpyAsync(bs.crec, crec.data(), ncl * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(bs.mid_idx, box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)c->w_recs, (const int*)bs.crec, ncl,
+                       bs.mid_pos);
+    RTGO_HIP(c, hipGetLastError());
+    int m[9];
+    const int rc = whitted_build(c, bs.mid_pos, bs.mid_idx, ncl, c->w_nodes, c->w_scratch, c->w_recs + 4 * (size_t)mi.rec_base, bs.mid_tris, bs.mid_qrecs,
+                                 bs.mid_tidx, m, what);
+    if (rc) return rc;
+    // leaf order: the mid level's Morton-ordered "triangles" carry the cluster in .w of their first corner
+    std::vector<float4> order((size_t)3 * ncl), root_rec(4);
+    std::vector<float> boxes((size_t)6 * ncl);
+    RTGO_HIP(c, hipMemcpyAsync(order.data(), bs.mid_tris, order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.mid_pos, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (m[1] > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), c->w_recs + 4 * (size_t)mi.rec_base, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    const int tbase = (int)table.size();
+    for (int pos = 0; pos < ncl; ++pos) {
+        int k;
+        std::memcpy(&k, &order[3 * pos].w, sizeof k);
+        table.push_back(make_int4(crec[k], mi.tri_base + cluster_start(n, ncl, k), croot[k], 0));
+    }
+    // what the walk can reach first below an instance: the mid root's two child boxes, or (a mid level of one leaf) the clusters' root
+    // records, whose boxes are the ones big_cluster_boxes_kernel took
+    auto widen = [&](float l0, float l1, float l2, float h0, float h1, float h2) {
+        const float l[3] = {l0, l1, l2}, h[3] = {h0, h1, h2};
+        for (int a = 0; a < 3; ++a) {
+            mi.lo[a] = std::fmin(mi.lo[a], l[a]);
+            mi.hi[a] = std::fmax(mi.hi[a], h[a]);
+        }
+    };
+    if (m[1] > 0) {
+        widen(root_rec[0].x, root_rec[0].y, root_rec[0].z, root_rec[1].x, root_rec[1].y, root_rec[1].z);
+        widen(root_rec[2].x, root_rec[2].y, root_rec[2].z, root_rec[3].x, root_rec[3].y, root_rec[3].z);
+    }
+    for (int k = 0; k < ncl; ++k) widen(boxes[6 * k + 0], boxes[6 * k + 1], boxes[6 * k + 2], boxes[6 * k + 3], boxes[6 * k + 4], boxes[6 * k + 5]);
+    mi.root = 1 + ((tbase << 3) | (m[1] > 0 ? kMidHasRecords : ncl - 1));
+    mi.depth = (m[1] > 0 ? m[2] : 0) + cdepth;
+    return RTGO_OK;
+}
+
 int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances, uint32_t n_instances,
                            const rtgo_pbr* materials, uint32_t n_materials)
 {
@@ -1716,13 +1852,15 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
     // every mesh as rtgo_whitted_set_mesh checks it, and where it will sit in the arrays
     std::vector<WhittedMeshInfo> info(n_meshes);
     size_t n_vert = 0, n_tri = 0;
-    int max_tri = 0;
+    int max_tri = 0, max_big = 0;   // the largest single build, the largest clustered mesh
     for (uint32_t k = 0; k < n_meshes; ++k) {
         const rtgo_whitted_mesh& q = meshes[k];
         const std::string at = "rtgo_whitted_set_scene: mesh " + std::to_string(k);
         if (!q.positions || !q.indices) return fail(c, RTGO_E_INVALID, at + ": NULL positions or indices");
-        if (q.n_triangles == 0 || q.n_triangles > RTGO_MAX_TRIANGLES || q.n_vertices == 0)
-            return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_MAX_TRIANGLES) + "], vertices non-empty");
+        if (q.n_triangles == 0 || q.n_triangles > RTGO_WHITTED_MAX_MESH_TRIANGLES || q.n_vertices == 0)
+            return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESH_TRIANGLES) + "], vertices non-empty");
+        if (n_tri + q.n_triangles > RTGO_WHITTED_MAX_SCENE_TRIANGLES)
+            return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
         for (uint32_t i = 0; i < 3 * q.n_triangles; ++i) {
             if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
@@ -1758,9 +1896,17 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
         mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
         mi.root = 0;
         mi.depth = 0;
+        mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
         n_vert += q.n_vertices;
         n_tri += q.n_triangles;
-        max_tri = std::max(max_tri, (int)q.n_triangles);
+        if (mi.clustered) {
+            // one workgroup's builds: clusters of at most kClusterTris triangles and a mid level of ncl boxes
+            const int ncl = ((int)q.n_triangles + whitted::kClusterTris - 1) / whitted::kClusterTris;
+            max_tri = std::max(max_tri, std::max(whitted::kClusterTris, ncl));
+            max_big = std::max(max_big, (int)q.n_triangles);
+        } else {
+            max_tri = std::max(max_tri, (int)q.n_triangles);
+        }
     }
     std::vector<whitted::InstShade> shade;
     std::vector<float> box_pos;
@@ -1799,11 +1945,38 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
     RTGO_HIP(c, hipMalloc(&c->w_tris, n_tri * 3 * sizeof(float4)));
     RTGO_HIP(c, hipMalloc(&c->w_qrecs, n_tri * 2 * sizeof(uint4)));
     RTGO_HIP(c, hipMalloc(&c->w_tidx, n_tri * sizeof(uint2)));
-    // bottom level: each mesh's own structure, as rtgo_whitted_set_mesh builds it, in its slice of the arrays
+    WhittedBigScratch bs;
+    if (max_big > 0) {
+        const int ncl = (max_big + whitted::kClusterTris - 1) / whitted::kClusterTris, nb = (max_big + whitted::kRadixTile - 1) / whitted::kRadixTile;
+        RTGO_HIP(c, hipMalloc(&bs.keys, (size_t)max_big * sizeof(unsigned long long)));
+        RTGO_HIP(c, hipMalloc(&bs.keys_alt, (size_t)max_big * sizeof(unsigned long long)));
+        RTGO_HIP(c, hipMalloc(&bs.hist, (size_t)256 * nb * sizeof(unsigned int)));
+        RTGO_HIP(c, hipMalloc(&bs.cidx, (size_t)3 * max_big * sizeof(unsigned int)));
+        RTGO_HIP(c, hipMalloc(&bs.partial, (size_t)6 * 1024 * sizeof(float)));
+        RTGO_HIP(c, hipMalloc(&bs.bounds, 6 * sizeof(float)));
+        RTGO_HIP(c, hipMalloc(&bs.crec, (size_t)ncl * sizeof(int)));
+        RTGO_HIP(c, hipMalloc(&bs.mid_pos, (size_t)6 * ncl * sizeof(float)));
+        RTGO_HIP(c, hipMalloc(&bs.mid_idx, (size_t)3 * ncl * sizeof(unsigned int)));
+        RTGO_HIP(c, hipMalloc(&bs.mid_tris, (size_t)3 * ncl * sizeof(float4)));
+        RTGO_HIP(c, hipMalloc(&bs.mid_qrecs, (size_t)2 * ncl * sizeof(uint4)));
+        RTGO_HIP(c, hipMalloc(&bs.mid_tidx, (size_t)ncl * sizeof(uint2)));
+    }
+    std::vector<int4> table;
+    // bottom level: each mesh's own structure, as rtgo_whitted_set_mesh builds it, in its slice of the arrays (a clustered mesh: its
+    // clusters and mid level)
     int mesh_depth = 0;
     for (uint32_t k = 0; k < n_meshes; ++k) {
         WhittedMeshInfo& mi = info[k];
         const int nt = (int)meshes[k].n_triangles;
+        if (mi.clustered) {
+            rc = whitted_build_clustered(c, mi, nt, bs, table, "rtgo_whitted_set_scene");
+            if (rc) {
+                free_mesh(c);
+                return rc;
+            }
+            mesh_depth = std::max(mesh_depth, mi.depth);
+            continue;
+        }
         int m[9];
         rc = whitted_build(c, c->w_positions + 3 * (size_t)mi.vert_base, c->w_indices + 3 * (size_t)mi.tri_base, nt, c->w_nodes, c->w_scratch,
                            c->w_recs + 4 * (size_t)mi.rec_base, c->w_tris + 3 * (size_t)mi.tri_base, c->w_qrecs + 2 * (size_t)mi.tri_base,
@@ -1815,6 +1988,16 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
         mi.root = m[1] > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
         mi.depth = m[1] > 0 ? m[2] : 0;
         mesh_depth = std::max(mesh_depth, mi.depth);
+    }
+    if (!table.empty()) {
+        RTGO_HIP(c, hipMalloc(&c->w_clusters, table.size() * sizeof(int4)));
+        RTGO_HIP(c, hipMemcpyAsync(c->w_clusters, table.data(), table.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream));
+        // the clustered meshes' boxes took in their mid levels' boxes: the instance boxes again from them (the checks passed above)
+        rc = whitted_prepare_instances(c, info, n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_scene");
+        if (rc) {
+            free_mesh(c);
+            return rc;
+        }
     }
     c->w_meshes = info;
     c->w_mesh_depth = mesh_depth;
@@ -1955,10 +2138,17 @@ static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Params& p, int 
     q.W = p.W;
     q.miss = p.miss;
     q.counters = p.counters;
+    q.clusters = c->w_clusters;
     const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)q.stack_depth * sizeof(unsigned short);
     const size_t top_bytes = (size_t)q.n_top_recs * 4 * sizeof(float4) + (size_t)q.n_instances * sizeof(whitted::InstWalk);
     const size_t lds_cap = 160 * 1024;
-    if (mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= lds_cap)
+    const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= lds_cap;
+    if (c->w_clusters) {   // a clustered mesh in the scene: the three-level walk
+        if (in_lds)
+            hipLaunchKernelGGL((whitted::render_inst_kernel<true, true>), dim3(blocks), dim3(whitted::kRenderBlock), top_bytes + stack_bytes, c->stream, q);
+        else
+            hipLaunchKernelGGL((whitted::render_inst_kernel<false, true>), dim3(blocks), dim3(whitted::kRenderBlock), stack_bytes, c->stream, q);
+    } else if (in_lds)
         hipLaunchKernelGGL(whitted::render_inst_kernel<true>, dim3(blocks), dim3(whitted::kRenderBlock), top_bytes + stack_bytes, c->stream, q);
     else
         hipLaunchKernelGGL(whitted::render_inst_kernel<false>, dim3(blocks), dim3(whitted::kRenderBlock), stack_bytes, c->stream, q);
@@ -2032,7 +2222,7 @@ int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t s
     const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
     const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
     const size_t lds_cap = 160 * 1024;
-    const int mode_cap = (int)env_uint("RTGO_WHITTED_MODE", (unsigned int)whitted::kAllInLds);   // (test and experiment knob: 0 / 1 / 2 = at most that much in LDS)
+    const int mode_cap = env_whitted_mode();
     int mode = whitted::kAllInL2;
     if (mode_cap >= whitted::kAllInLds && p.n_vertices <= 65535 && compact_bytes + stack_bytes <= lds_cap) mode = whitted::kAllInLds;
     else if (mode_cap >= whitted::kRecordsInLds && rec_bytes + stack_bytes <= lds_cap) mode = whitted::kRecordsInLds;

@@ -1,0 +1,244 @@
+// rtgo_whitted_big.h -- the device-wide build steps of a clustered mesh (a mesh of an instanced whitted scene beyond kMaxTriangles
+// triangles, rtgo_whitted_set_scene).  build_kernel sorts one mesh in one workgroup's LDS; a bigger mesh is first put in Morton order
+// here, over the whole device, and then cut into clusters of at most kClusterTris consecutive triangles, each built by the single-mesh
+// pair (build_kernel + sah_kernel) and joined by a mid level over the clusters' boxes (rtgo_whitted_inst.h walks the three levels).
+//
+// Steps, one launch each (kernel boundaries are the only grid-wide synchronisation: nothing waits on another workgroup):
+//   big_bounds_kernel (grid-stride partial boxes) -> big_bounds_final_kernel (one workgroup) -> big_keys_kernel (Morton code of the
+//   centroid on build_kernel's 10-bit grid, key = code << 32 | triangle) -> four LSD radix passes over the code's bytes
+//   (radix_count_kernel, radix_scan_kernel, radix_scatter_kernel; stable, and the keys start in triangle order, so the order is
+//   (code, triangle): unique keys, one deterministic order) -> big_gather_kernel (each sorted triangle's index triple) -> per cluster
+//   whitted_build -> big_remap_kernel (cluster-local triangle numbers in tris[].w back to the mesh's own).
+#pragma once
+
+#include "rtgo_whitted.h"
+
+namespace rtgo {
+namespace whitted {
+
+#ifndef RTGO_CLUSTER_TRIS
+#define RTGO_CLUSTER_TRIS 4096
+#endif
+constexpr int kClusterTris = RTGO_CLUSTER_TRIS;   // sah_kernel's LDS (33 B per triangle, <= 150 KiB) holds a cluster: surface-area records
+static_assert(kClusterTris > 4 * kLeafTris && kClusterTris <= kMaxTriangles, "cluster size");
+constexpr int kBigMaxMeshTriangles = 1 << 24;      // per mesh: at most kBigMaxMeshTriangles / (kClusterTris / 2) clusters, a mid level
+constexpr int kBigMaxSceneTriangles = 1 << 26;     //   that build_kernel can sort; over a scene: int indices into the arrays stay far from 2^31
+static_assert(kBigMaxMeshTriangles / (kClusterTris / 2) <= kMaxTriangles, "mid level");
+constexpr int kRadixThreads = 1024;
+constexpr int kRadixTile = 8 * kRadixThreads;      // keys per workgroup of the count and scatter passes
+
+// the clusters of a mesh of n triangles in sorted order: ncl = ceil(n / kClusterTris) runs as even as they come, the first n % ncl one
+// triangle longer (so none is shorter than kClusterTris / 2, and every one has records)
+__host__ __device__ __forceinline__ int cluster_start(long long n, int ncl, int c)
+{
+    const long long q = n / ncl, r = n % ncl;
+    return (int)(c * q + (c < r ? c : r));
+}
+
+__global__ __launch_bounds__(1024) void big_bounds_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
+                                                          float* __restrict__ partial)
+{
+    __shared__ float s_red[6][1024];
+    const int tid = threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long long i = (long long)blockIdx.x * 1024 + tid; i < n; i += (long long)gridDim.x * 1024)
+        for (int k = 0; k < 3; ++k) {
+            const unsigned int vi = indices[3 * i + k];
+            for (int a = 0; a < 3; ++a) {
+                const float c = positions[3 * (size_t)vi + a];
+                lo[a] = fminf(lo[a], c);
+                hi[a] = fmaxf(hi[a], c);
+            }
+        }
+    for (int a = 0; a < 3; ++a) {
+        s_red[a][tid] = lo[a];
+        s_red[3 + a][tid] = hi[a];
+    }
+    __syncthreads();
+    for (int stride = 512; stride > 0; stride >>= 1) {
+        if (tid < stride)
+            for (int a = 0; a < 3; ++a) {
+                s_red[a][tid] = fminf(s_red[a][tid], s_red[a][tid + stride]);
+                s_red[3 + a][tid] = fmaxf(s_red[3 + a][tid], s_red[3 + a][tid + stride]);
+            }
+        __syncthreads();
+    }
+    if (tid < 6) partial[6 * blockIdx.x + tid] = s_red[tid][0];
+}
+
+// one workgroup: the partial boxes of big_bounds_kernel's n_parts workgroups -> bounds[6] = lo xyz, hi xyz
+__global__ __launch_bounds__(1024) void big_bounds_final_kernel(const float* __restrict__ partial, int n_parts, float* __restrict__ bounds)
+{
+    __shared__ float s_red[6][1024];
+    const int tid = threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = tid; i < n_parts; i += 1024)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], partial[6 * i + a]);
+            hi[a] = fmaxf(hi[a], partial[6 * i + 3 + a]);
+        }
+    for (int a = 0; a < 3; ++a) {
+        s_red[a][tid] = lo[a];
+        s_red[3 + a][tid] = hi[a];
+    }
+    __syncthreads();
+    for (int stride = 512; stride > 0; stride >>= 1) {
+        if (tid < stride)
+            for (int a = 0; a < 3; ++a) {
+                s_red[a][tid] = fminf(s_red[a][tid], s_red[a][tid + stride]);
+                s_red[3 + a][tid] = fmaxf(s_red[3 + a][tid], s_red[3 + a][tid + stride]);
+            }
+        __syncthreads();
+    }
+    if (tid < 6) bounds[tid] = s_red[tid][0];
+}
+
+// build_kernel's Morton key of every triangle, over the whole mesh's bounds
+__global__ __launch_bounds__(256) void big_keys_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
+                                                       const float* __restrict__ bounds, unsigned long long* __restrict__ keys)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    unsigned int q[3];
+    for (int a = 0; a < 3; ++a) {
+        const float blo = bounds[a], ext = bounds[3 + a] - bounds[a];
+        const float c = (positions[3 * (size_t)indices[3 * (size_t)i + 0] + a] + positions[3 * (size_t)indices[3 * (size_t)i + 1] + a] +
+                         positions[3 * (size_t)indices[3 * (size_t)i + 2] + a]) * (1.0f / 3.0f);
+        const float u = ext > 0.0f ? (c - blo) / ext : 0.0f;
+        q[a] = (unsigned int)fminf(fmaxf(u * 1024.0f, 0.0f), 1023.0f);
+    }
+    keys[i] = ((unsigned long long)((expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2])) << 32) | (unsigned int)i;
+}
+
+// radix pass, step 1: how many keys of workgroup b's tile have digit d at `shift` -> hist[d * n_blocks + b]
+__global__ __launch_bounds__(kRadixThreads) void radix_count_kernel(const unsigned long long* __restrict__ keys, int n, int shift,
+                                                                    unsigned int* __restrict__ hist)
+{
+    __shared__ unsigned int s_h[256];
+    const int tid = threadIdx.x;
+    if (tid < 256) s_h[tid] = 0u;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * kRadixTile;
+    for (int k = tid; k < kRadixTile; k += kRadixThreads) {
+        const long long i = base + k;
+        if (i < n) atomicAdd(&s_h[(unsigned int)(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 256) hist[(size_t)tid * gridDim.x + blockIdx.x] = s_h[tid];
+}
+
+// step 2, one workgroup: exclusive prefix sum of the m counts in place (digit-major: every key of digit d goes after all of d - 1)
+__global__ __launch_bounds__(1024) void radix_scan_kernel(unsigned int* __restrict__ hist, int m)
+{
+    __shared__ unsigned int s_sum[1024];
+    const int tid = threadIdx.x;
+    const int per = (m + 1023) / 1024;
+    const long long a = (long long)tid * per, b = a + per < m ? a + per : m;
+    unsigned int s = 0u;
+    for (long long i = a; i < b; ++i) s += hist[i];
+    s_sum[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned int run = 0u;
+        for (int k = 0; k < 1024; ++k) {
+            const unsigned int v = s_sum[k];
+            s_sum[k] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    unsigned int run = s_sum[tid];
+    for (long long i = a; i < b; ++i) {
+        const unsigned int v = hist[i];
+        hist[i] = run;
+        run += v;
+    }
+}
+
+// step 3: every key to its place, stably: the tile goes 1024 keys at a time in order; within a wave a key's rank among the lanes
+// below it with the same digit comes from eight ballots, and the waves of the workgroup follow each other through LDS
+__global__ __launch_bounds__(kRadixThreads) void radix_scatter_kernel(const unsigned long long* __restrict__ keys, int n, int shift,
+                                                                      const unsigned int* __restrict__ offs, unsigned long long* __restrict__ out)
+{
+    constexpr int kWaves = kRadixThreads / 64;
+    __shared__ unsigned int s_base[256], s_total[256];
+    __shared__ unsigned int s_wave[kWaves][256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 256) s_base[tid] = offs[(size_t)tid * gridDim.x + blockIdx.x];
+    const long long base = (long long)blockIdx.x * kRadixTile;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int chunk = 0; chunk < kRadixTile; chunk += kRadixThreads) {
+        for (int k = tid; k < kWaves * 256; k += kRadixThreads) (&s_wave[0][0])[k] = 0u;
+        __syncthreads();
+        const long long i = base + chunk + tid;
+        const bool valid = i < n;
+        const unsigned long long key = valid ? keys[i] : 0ull;
+        const unsigned int dig = (unsigned int)(key >> shift) & 255u;
+        unsigned long long same = __builtin_amdgcn_ballot_w64(valid);
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long ones = __builtin_amdgcn_ballot_w64(valid && ((dig >> bit) & 1u));
+            same &= ((dig >> bit) & 1u) ? ones : ~ones;
+        }
+        const unsigned int rank = (unsigned int)__popcll(same & below);
+        if (valid && rank == 0u) s_wave[wave][dig] = (unsigned int)__popcll(same);   // the lowest lane of each digit speaks for it
+        __syncthreads();
+        if (tid < 256) {
+            unsigned int run = 0u;
+            for (int w = 0; w < kWaves; ++w) {
+                const unsigned int v = s_wave[w][tid];
+                s_wave[w][tid] = run;
+                run += v;
+            }
+            s_total[tid] = run;
+        }
+        __syncthreads();
+        if (valid) out[s_base[dig] + s_wave[wave][dig] + rank] = key;
+        __syncthreads();
+        if (tid < 256) s_base[tid] += s_total[tid];
+        // (the next chunk's first barrier orders this update before any read of s_base)
+    }
+}
+
+// each sorted triangle's index triple (relative to the mesh's vertices, as the caller gave it)
+__global__ __launch_bounds__(256) void big_gather_kernel(const unsigned long long* __restrict__ sorted, int n, const unsigned int* __restrict__ indices,
+                                                         unsigned int* __restrict__ out)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const size_t t = (size_t)(sorted[j] & 0xFFFFFFFFull);
+    out[3 * (size_t)j + 0] = indices[3 * t + 0];
+    out[3 * (size_t)j + 1] = indices[3 * t + 1];
+    out[3 * (size_t)j + 2] = indices[3 * t + 2];
+}
+
+// tris[].w of every cluster: build_kernel wrote the triangle's number within its cluster (its place in the cluster's slice of the
+// gathered triples); the mesh's own index is the sorted key at the cluster's start + that number
+__global__ __launch_bounds__(256) void big_remap_kernel(float4* __restrict__ tris, const unsigned long long* __restrict__ sorted, int n, int ncl)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int q = n / ncl, r = n % ncl;
+    const int c = p < r * (q + 1) ? p / (q + 1) : r + (p - r * (q + 1)) / q;
+    const int local = __float_as_int(tris[3 * (size_t)p].w);
+    tris[3 * (size_t)p].w = __int_as_float((int)(sorted[cluster_start(n, ncl, c) + local] & 0xFFFFFFFFull));
+}
+
+// the mid level's input: cluster c's box (the union of its root record's two child boxes) as the degenerate triangle (lo, hi, lo)
+// of the top level's recipe -> pos[6 c .. 6 c + 5]
+__global__ __launch_bounds__(256) void big_cluster_boxes_kernel(const float4* __restrict__ recs, const int* __restrict__ rec_base, int ncl,
+                                                                float* __restrict__ pos)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncl) return;
+    const float4* r = recs + 4 * (size_t)rec_base[c];
+    const float4 a0 = r[0], a1 = r[1], b0 = r[2], b1 = r[3];
+    pos[6 * c + 0] = fminf(a0.x, b0.x);
+    pos[6 * c + 1] = fminf(a0.y, b0.y);
+    pos[6 * c + 2] = fminf(a0.z, b0.z);
+    pos[6 * c + 3] = fmaxf(a1.x, b1.x);
+    pos[6 * c + 4] = fmaxf(a1.y, b1.y);
+    pos[6 * c + 5] = fmaxf(a1.z, b1.z);
+}
+
+}  // namespace whitted
+}  // namespace rtgo

@@ -13,6 +13,8 @@
 
 #include "rtgo_whitted.h"
 
+#include <type_traits>
+
 namespace rtgo {
 namespace whitted {
 
@@ -26,7 +28,8 @@ struct InstWalk {      // what the walk reads of an instance, 64 B, in the top l
     float4 w2o[3];     // rows of the world-to-object 3x4 matrix (the inverse of the instance transform, computed in double on the host)
     int rec_base;      // the mesh's first record in InstParams::recs
     int tri_base;      // its first triangle in InstParams::tris (Morton order), indices and tri_material
-    int root;          // 0: record 0 of the mesh; < 0: the leaf code of a mesh of at most kLeafTris triangles (no records)
+    int root;          // 0: record 0 of the mesh; < 0: the leaf code of a mesh of at most kLeafTris triangles (no records);
+                       // > 0: a clustered mesh (rec_base: its mid level's records), 1 + (cluster table base << 3 | mid_root_bits)
     int instance;      // the instance's index in the caller's array
 };
 struct InstShade {     // what shading reads of an instance, 112 B, in the caller's order
@@ -62,6 +65,7 @@ struct InstParams {
     unsigned int width, height, subframe;
     v3 eye, U, V, W, miss;
     unsigned long long* counters;
+    const int4* clusters;       // clustered meshes: (record base, triangle base, root, 0) per cluster, each mesh's in its mid level's leaf order
 };
 
 // M (p, 1) and M (d, 0) for a row-major 3x4 M; one rounding per operation in row order
@@ -82,9 +86,10 @@ __device__ __forceinline__ v3 xform_normal(const float4 m0, const float4 m1, con
 // the triangles of one leaf of one instance's mesh (leaf_tris with the two-level key).  The closest-hit walk asks for the whole leaf
 // before testing it, as leaf_tris does; the occlusion walk, which runs with the shading state live beside it, one triangle at a time
 // (the 48 VGPRs of a whole leaf would not fit next to that state without scratch).
-template <bool ANY>
-__device__ __forceinline__ bool leaf_tris_inst(const float4* __restrict__ tris, int first, int cnt, v3 o, v3 d, float tmin, float tmax, int kbase,
-                                               int pos_base, int& best, int& best_pos, float& bt, float& bu, float& bv)
+// Key: int (instance << kInstShift | triangle) or, in a scene with clustered meshes, long long (instance << 32 | triangle).
+template <bool ANY, typename Key>
+__device__ __forceinline__ bool leaf_tris_inst(const float4* __restrict__ tris, int first, int cnt, v3 o, v3 d, float tmin, float tmax, Key kbase,
+                                               int pos_base, Key& best, int& best_pos, float& bt, float& bu, float& bv)
 {
     if constexpr (ANY) {
         for (int k = 0; k < cnt; ++k) {
@@ -94,7 +99,7 @@ __device__ __forceinline__ bool leaf_tris_inst(const float4* __restrict__ tris, 
                 bt = t;
                 bu = u;
                 bv = v;
-                best = kbase | __float_as_int(a.w);
+                best = kbase | (Key)__float_as_int(a.w);
                 best_pos = pos_base + first + k;
                 return true;
             }
@@ -114,7 +119,7 @@ __device__ __forceinline__ bool leaf_tris_inst(const float4* __restrict__ tris, 
 #pragma unroll
     for (int k = 0; k < kLeafTris; ++k) {
         if (k < cnt) {
-            const int key = kbase | __float_as_int(a[k].w);
+            const Key key = kbase | (Key)__float_as_int(a[k].w);
             float t, u, v;
             if (tri_intersect(mk(a[k].x, a[k].y, a[k].z), mk(b[k].x, b[k].y, b[k].z), mk(c[k].x, c[k].y, c[k].z), o, d, tmin, tmax, t, u, v) &&
                 (t < bt || (t == bt && best >= 0 && key < best))) {
@@ -215,10 +220,90 @@ __device__ __forceinline__ bool trace_inst(const InstParams& p, Top top, Inst in
     return best >= 0;
 }
 
+// trace_inst over scenes that hold clustered meshes (render_inst_kernel<*, true>): a mesh beyond kMaxTriangles triangles is a mid level
+// over clusters of at most kClusterTris triangles, each with the single-mesh structure (rtgo_whitted_big.h).  At an instance the ray is
+// taken to object space once; a clustered mesh's mid records are walked, and at a mid leaf each of its clusters' records with that
+// cluster's bases.  A mesh of today's structure is walked as a mid level of one leaf holding one cluster (the instance's own bases).
+// Each level keeps its stack entries above the one it came from, on the same lane stack, with its own floor; record indices and leaf
+// codes stay local to their level.  The hit key is (instance << 32 | the mesh's own triangle index), 64 bits: the same order as
+// trace_inst's key, so a clustered mesh renders like the same triangles cut into contiguous identity instances.
+constexpr int kMidHasRecords = 4;   // mid_root_bits: the mid level has records (root record 0); else the count - 1 of its one leaf's clusters
+template <bool ANY, typename Top, typename Inst>
+__device__ __forceinline__ bool trace_inst_big(const InstParams& p, Top top, Inst inst, unsigned short* __restrict__ s_stack, int stride, v3 o, v3 d,
+                                               float tmin, float tmax, long long& key_out, int& pos_out, float& t_out, float& u_out, float& v_out)
+{
+    auto safe_inv = [](float x) { return fabsf(x) < 1e-30f ? copysignf(1e30f, x) : 1.0f / x; };
+    const v3 id = mk(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+    long long best = -1;
+    int best_pos = 0;
+    float bt = tmax, bu = 0.0f, bv = 0.0f;
+    int sp = 0;
+    int cur = p.n_top_recs > 0 ? 0 : -1 - ((p.n_instances - 1) << kLeafShift);
+    bool done = false;
+    for (;;) {
+        bool pop = true;
+        if (cur >= 0) {
+            pop = !record_step(top, cur, s_stack, stride, sp, o, id, tmin, bt);
+        } else {
+            const int code = -1 - cur, first = code & ((1 << kLeafShift) - 1), cnt = (code >> kLeafShift) + 1;
+            for (int k = 0; k < cnt && !done; ++k) {
+                const InstWalk w = inst[first + k];
+                const v3 oo = xform_point(w.w2o[0], w.w2o[1], w.w2o[2], o), od = xform_vector(w.w2o[0], w.w2o[1], w.w2o[2], d);
+                const v3 oid = mk(safe_inv(od.x), safe_inv(od.y), safe_inv(od.z));
+                const long long kbase = (long long)w.instance << 32;
+                const bool big = w.root > 0;
+                const int bits = w.root - 1, tbase = bits >> 3;
+                const float4* __restrict__ mrecs = p.recs + 4 * w.rec_base;
+                const int gfloor = sp;
+                int g = (big && (bits & kMidHasRecords)) ? 0 : -1 - ((big ? (bits & 3) : 0) << kLeafShift);
+                for (;;) {
+                    bool gpop = true;
+                    if (g >= 0) {
+                        gpop = !record_step(mrecs, g, s_stack, stride, sp, oo, oid, tmin, bt);
+                    } else {
+                        const int gc = -1 - g, gfirst = gc & ((1 << kLeafShift) - 1), gcnt = (gc >> kLeafShift) + 1;
+                        for (int q = 0; q < gcnt && !done; ++q) {
+                            const int4 cl = big ? p.clusters[tbase + gfirst + q] : make_int4(w.rec_base, w.tri_base, w.root, 0);
+                            const float4* __restrict__ recs = p.recs + 4 * cl.x;
+                            const float4* __restrict__ tris = p.tris + 3 * cl.y;
+                            const int floor = sp;
+                            int m = cl.z;
+                            for (;;) {
+                                bool mpop = true;
+                                if (m >= 0) {
+                                    mpop = !record_step(recs, m, s_stack, stride, sp, oo, oid, tmin, bt);
+                                } else {
+                                    const int mc = -1 - m;
+                                    if (leaf_tris_inst<ANY>(tris, mc & ((1 << kLeafShift) - 1), (mc >> kLeafShift) + 1, oo, od, tmin, tmax, kbase, cl.y, best,
+                                                            best_pos, bt, bu, bv)) {   // (true only when ANY)
+                                        done = true;
+                                        break;
+                                    }
+                                }
+                                if (mpop && !pop_entry(s_stack, stride, sp, floor, m)) break;
+                            }
+                        }
+                        if (done) break;
+                    }
+                    if (gpop && !pop_entry(s_stack, stride, sp, gfloor, g)) break;
+                }
+            }
+            if (done) break;
+        }
+        if (pop && !pop_entry(s_stack, stride, sp, 0, cur)) break;
+    }
+    key_out = best;
+    pos_out = best_pos;
+    t_out = bt;
+    u_out = bu;
+    v_out = bv;
+    return best >= 0;
+}
+
 // render_kernel's pipeline (same tile queue, __raygen__pinhole, accumulation and make_color) over the two-level structure.
 // TOP_IN_LDS: the top level's records and the InstWalk array are copied into LDS ahead of the lanes' stacks; otherwise they are read
-// through L2 like the meshes' records.
-template <bool TOP_IN_LDS>
+// through L2 like the meshes' records.  CLUSTERED: the scene holds a clustered mesh (trace_inst_big and its 64-bit hit key).
+template <bool TOP_IN_LDS, bool CLUSTERED = false>
 __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char wi_smem[];
@@ -281,12 +366,16 @@ __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstPar
             const v3 rd = vnormalize(vadd(vadd(vscale(p.U, dx), vscale(p.V, dy)), p.W));
             const v3 ro = p.eye;
             v3 result = p.miss;
-            int key, tpos;
+            std::conditional_t<CLUSTERED, long long, int> key;
+            int tpos;
             float t, bu, bv;
             rays += 1;
-            if (trace_inst<false>(p, top, inst, s_stack, stride, ro, rd, 0.01f, 1e16f, key, tpos, t, bu, bv)) {
+            bool hit;
+            if constexpr (CLUSTERED) hit = trace_inst_big<false>(p, top, inst, s_stack, stride, ro, rd, 0.01f, 1e16f, key, tpos, t, bu, bv);
+            else hit = trace_inst<false>(p, top, inst, s_stack, stride, ro, rd, 0.01f, 1e16f, key, tpos, t, bu, bv);
+            if (hit) {
                 // __closesthit__radiance, :255-337, with getLocalGeometry (LocalGeometry.h:55-141) of an instanced mesh
-                const int ii = key >> kInstShift, tri = key & ((1 << kInstShift) - 1);
+                const int ii = CLUSTERED ? (int)(key >> 32) : (int)(key >> kInstShift), tri = CLUSTERED ? (int)(key & 0xFFFFFFFF) : (int)(key & ((1 << kInstShift) - 1));
                 const InstShade sh = p.shade[ii];
                 const float4 c0 = p.tris[3 * tpos + 0], c1 = p.tris[3 * tpos + 1], c2 = p.tris[3 * tpos + 2];   // object space
                 unsigned int i0 = 0, i1 = 0, i2 = 0;
@@ -360,9 +449,13 @@ __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstPar
                     if (NdotL > 0.0f && NdotV > 0.0f) {
                         rays += 1;
                         occl += 1;
-                        int ok;
+                        std::conditional_t<CLUSTERED, long long, int> ok;
+                        int opos;
                         float ot, ou, ov;
-                        if (!trace_inst<true>(p, top, inst, s_stack, stride, P, Lv, 0.001f, Ldist - 0.001f, ok, ok, ot, ou, ov)) {
+                        bool occluded;
+                        if constexpr (CLUSTERED) occluded = trace_inst_big<true>(p, top, inst, s_stack, stride, P, Lv, 0.001f, Ldist - 0.001f, ok, opos, ot, ou, ov);
+                        else occluded = trace_inst<true>(p, top, inst, s_stack, stride, P, Lv, 0.001f, Ldist - 0.001f, ok, ok, ot, ou, ov);
+                        if (!occluded) {
                             const v3 F = schlick(spec_color, VdotH);
                             const float G = vis(NdotL, NdotV, alpha);
                             const float D = ggx_normal(NdotH, alpha);

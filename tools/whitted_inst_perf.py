@@ -1,13 +1,17 @@
 """developer tool: time the whitted path over instanced meshes (rtgo_whitted_set_scene)
    python tools/whitted_inst_perf.py one [W] [H]     one identity instance of tests/whitted_scene.build(40, 48) (3758 triangles) against
                                                      rtgo_whitted_set_mesh on the same mesh
-   python tools/whitted_inst_perf.py field [W] [H]   1024 instances of a 1120-triangle torus (1.15 M triangles) on a ground"""
+   python tools/whitted_inst_perf.py field [W] [H]   1024 instances of a 1120-triangle torus (1.15 M triangles) on a ground
+   python tools/whitted_inst_perf.py big [W] [H]     a 1 M-triangle displaced torus on a ground: one clustered instance against the caller's
+                                                     cut into contiguous 8192-triangle identity instances; set_scene wall time at 1 M and 4 M"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import whitted_scene
 import whitted_instances as WI
+import whitted_big_meshes as BM
+import time
 from raytracingo_amd import capi
 
 what = sys.argv[1] if len(sys.argv) > 1 else "one"
@@ -54,6 +58,36 @@ if what == "one":
     ms2, r2 = time_ctx(ctx, mesh["lights"], mesh["miss"], cam)
     print("whitted %dx%d, %d triangles: single mesh %.3f ms (%.0f Mray/s), one identity instance %.3f ms (%.0f Mray/s): %.2fx" %
           (W, H, len(mesh["indices"]), ms1, r1 / ms1 / 1e3, ms2, r2 / ms2 / 1e3, ms2 / ms1))
+elif what == "big":
+    big = BM.displaced_torus(1000, 500, R=1.0, r=0.35, amp=0.04, freq=(23, 11), texcoords=False)   # 1 000 000 triangles
+    meshes = [WI.ground(4.0, -0.5, normals=True), big]
+    inst = [(np.eye(3, 4, dtype=np.float32), 0, 0), (np.eye(3, 4, dtype=np.float32), 1, 1)]
+    mats = WI.materials()
+    lt = WI.lights()
+    cam = frame([0.4, 1.6, 2.6], [0.0, -0.1, 0.0], 45.0)
+    ctx = capi.Context(0)
+    t0 = time.perf_counter()
+    ctx.whitted_set_scene(meshes, inst, mats)
+    t_big = time.perf_counter() - t0
+    ms1, r1 = time_ctx(ctx, lt["lights"], lt["miss"], cam)
+    ctx.close()
+    cm, ci = BM.chunked_scene(meshes, inst, big={1})
+    ctx = capi.Context(0)
+    t0 = time.perf_counter()
+    ctx.whitted_set_scene(cm, ci, mats)
+    t_cut = time.perf_counter() - t0
+    ms2, r2 = time_ctx(ctx, lt["lights"], lt["miss"], cam)
+    ctx.close()
+    print("whitted %dx%d, 1 000 002 triangles: one clustered instance %.3f ms/subframe (%.2f Gray/s, set_scene %.2f s); caller's cut into %d "
+          "instances %.3f ms/subframe (%.2f Gray/s, set_scene %.2f s): clustered/cut %.3f" %
+          (W, H, ms1, r1 / ms1 / 1e6, t_big, len(ci), ms2, r2 / ms2 / 1e6, t_cut, ms1 / ms2))
+    if len(sys.argv) > 4 and sys.argv[4] == "build4m":
+        big4 = BM.displaced_torus(2000, 1000, R=1.0, r=0.35, amp=0.04, freq=(23, 11), texcoords=False)
+        ctx = capi.Context(0)
+        t0 = time.perf_counter()
+        ctx.whitted_set_scene([meshes[0], big4], inst, mats)
+        print("set_scene of a 4 000 000-triangle mesh: %.2f s" % (time.perf_counter() - t0))
+        ctx.close()
 else:
     tor = WI.torus(n_u=40, n_v=14, R=0.35, r=0.12)
     meshes = [tor, WI.ground(20.0, normals=True)]
