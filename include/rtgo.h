@@ -246,8 +246,28 @@ int rtgo_whitted_set_miss_color(rtgo_ctx* ctx, const float rgb[3]);
 
 /* optixLaunch of the whitted pipeline over width x height pixels for subframe `subframe_index` (whitted::LaunchParams,
    cuda/whitted.h:59-74), over whichever scene the context holds (rtgo_whitted_set_mesh or rtgo_whitted_set_scene).  Asynchronous on
-   the context's stream; rays are added to rtgo_stats (rays_total, rays_occlusion). */
+   the context's stream; rays are added to rtgo_stats (rays_total, rays_occlusion).  = rtgo_whitted_launch_frame over the full image
+   and one rank. */
 int rtgo_whitted_launch(rtgo_ctx* ctx, uint32_t width, uint32_t height, uint32_t subframe_index);
+
+/* One subframe of a window / row band of the image (no reference counterpart: whitted.cu's launch renders the whole image, one GPU).
+   The fields mean what rtgo_frame's do.  Pixels are independent (seed tea<4>(y * image_width + x, subframe), the ray from the full
+   image_width x image_height: whitted.cu:196-206), so the shares of a split put back together are the full frame bit for bit. */
+typedef struct rtgo_whitted_frame {
+    uint32_t image_width;      /* optixGetLaunchDimensions().x of the full image (seeds and ray directions) */
+    uint32_t image_height;     /* optixGetLaunchDimensions().y */
+    uint32_t subframe_index;   /* whitted::LaunchParams::subframe_index */
+    uint32_t x0, y0, w, h;     /* window in global pixel coordinates; w = h = 0 means the full image */
+    uint32_t band_h;           /* row-band height of the interleave inside the window (0 = 4) */
+    uint32_t n_ranks, rank;    /* this context renders window rows r with (r / band_h) % n_ranks == rank; 0/1 = all.  Its k-th
+                                  owned row is row k of a w-pixel-wide output (rtgo_assemble_bands puts the ranks' rows back) */
+    uint32_t reserve_cus;      /* leave this many CUs' worth of workgroup slots to other streams (at most half of them, as rtgo_launch) */
+} rtgo_whitted_frame;
+
+/* optixLaunch of the whitted pipeline over the frame's share of the image, as rtgo_whitted_launch.  RTGO_E_INVALID: a window outside
+   the image, rank >= n_ranks, w x rtgo_local_rows(h, band_h, n_ranks, rank) pixels beyond the output, or reserve_cus >= the device's
+   CUs (nothing is enqueued).  A rank that owns no row of the window enqueues nothing and returns RTGO_OK.  Asynchronous. */
+int rtgo_whitted_launch_frame(rtgo_ctx* ctx, const rtgo_whitted_frame* frame);
 
 /* ---- instanced meshes: sutil::Scene's two levels (one GAS per MeshGroup, buildMeshAccels; one OptixInstance per group in an IAS,
    buildInstanceAccel, sutil/Scene.cpp:985-1010) ---- */

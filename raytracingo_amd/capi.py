@@ -24,6 +24,7 @@ SYMBOLS = [
     "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands",
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
+    "rtgo_whitted_launch_frame",
 ]
 RTGO_WHITTED_MAX_MESHES = 256
 RTGO_WHITTED_MAX_INSTANCES = 8192
@@ -56,6 +57,12 @@ class Frame(C.Structure):
                 ("use_ambient", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32),
                 ("h", C.c_uint32), ("band_h", C.c_uint32), ("n_ranks", C.c_uint32), ("rank", C.c_uint32),
                 ("collect_stats", C.c_uint32), ("reserve_cus", C.c_uint32)]
+
+
+class WhittedFrame(C.Structure):
+    _fields_ = [("image_width", C.c_uint32), ("image_height", C.c_uint32), ("subframe_index", C.c_uint32),
+                ("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("band_h", C.c_uint32),
+                ("n_ranks", C.c_uint32), ("rank", C.c_uint32), ("reserve_cus", C.c_uint32)]
 
 
 class Texture(C.Structure):
@@ -129,6 +136,7 @@ def load():
     L.rtgo_whitted_set_material_textures.argtypes = [vp, C.c_uint32, C.POINTER(Texture), C.POINTER(Texture), C.POINTER(Texture)]
     L.rtgo_whitted_set_scene.argtypes = [vp, C.POINTER(WhittedMesh), C.c_uint32, C.POINTER(WhittedInstance), C.c_uint32, vp, C.c_uint32]
     L.rtgo_whitted_set_instances.argtypes = [vp, C.POINTER(WhittedInstance), C.c_uint32]
+    L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtgo_last_error", "rtgo_local_rows", "rtgo_abi_version"):
@@ -317,6 +325,10 @@ class Context:
     def whitted_launch(self, width, height, subframe):
         self._check(self._lib.rtgo_whitted_launch(self._h, width, height, subframe), "rtgo_whitted_launch")
 
+    def whitted_launch_frame(self, frame):
+        """one subframe of a window / row band of the image (make_whitted_frame): the output holds the share's compact rows"""
+        self._check(self._lib.rtgo_whitted_launch_frame(self._h, C.byref(frame)), "rtgo_whitted_launch_frame")
+
     def stats(self):
         s = Stats()
         self._check(self._lib.rtgo_get_stats(self._h, C.byref(s)), "rtgo_get_stats")
@@ -356,3 +368,11 @@ def make_frame(width, height, sqrt_spp=1, frame_count=0, path=True, ambient=Fals
     band_h, n_ranks, rank = bands
     return Frame(width, height, sqrt_spp, max_depth, frame_count, int(path), int(ambient), x0, y0, w, h, band_h,
                  n_ranks, rank, int(stats), int(reserve_cus))
+
+
+def make_whitted_frame(width, height, subframe, window=None, bands=(4, 1, 0), reserve_cus=0):
+    """rtgo_whitted_frame: subframe `subframe` of the window (x0, y0, w, h) of a width x height image (None: all of it), the rows of
+    band interleave (band_h, n_ranks, rank)"""
+    x0, y0, w, h = window if window is not None else (0, 0, width, height)
+    band_h, n_ranks, rank = bands
+    return WhittedFrame(width, height, subframe, x0, y0, w, h, band_h, n_ranks, rank, int(reserve_cus))

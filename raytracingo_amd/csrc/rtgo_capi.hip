@@ -2132,6 +2132,7 @@ static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Params& p, int 
     q.width = p.width;
     q.height = p.height;
     q.subframe = p.subframe;
+    q.share = p.share;
     q.eye = p.eye;
     q.U = p.U;
     q.V = p.V;
@@ -2158,11 +2159,38 @@ static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Params& p, int 
 
 int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t subframe_index)
 {
+    rtgo_whitted_frame f;
+    std::memset(&f, 0, sizeof f);
+    f.image_width = width;
+    f.image_height = height;
+    f.subframe_index = subframe_index;
+    return rtgo_whitted_launch_frame(c, &f);
+}
+
+int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
+{
     if (!c) return RTGO_E_INVALID;
+    if (!f) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: NULL frame");
     if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene)");
     if (!c->have_camera) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no camera (call rtgo_set_camera)");
     if (!c->d_accum || !c->d_image) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no output (call rtgo_resize or rtgo_bind_output)");
-    if (width == 0 || height == 0 || (uint64_t)width * height > c->pixels) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image empty or larger than the output buffers");
+    const uint32_t width = f->image_width, height = f->image_height;
+    if (width == 0 || height == 0) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image empty");
+    // the window and band of rtgo_launch's frame (rtgo_frame's fields, the same defaults)
+    whitted::Share s;
+    s.x0 = f->x0;
+    s.y0 = f->y0;
+    const uint32_t win_w = f->w ? f->w : width, win_h = f->h ? f->h : height;
+    if ((uint64_t)s.x0 + win_w > width || (uint64_t)s.y0 + win_h > height) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: window outside the image");
+    s.band_h = f->band_h ? f->band_h : 4;
+    s.n_ranks = f->n_ranks ? f->n_ranks : 1;
+    s.rank = f->rank;
+    if (s.rank >= s.n_ranks) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: rank >= n_ranks");
+    s.lw = win_w;
+    s.lh = rtgo_local_rows(win_h, s.band_h, s.n_ranks, s.rank);
+    if ((uint64_t)s.lh * s.lw > c->pixels) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image larger than the output buffers");
+    if (f->reserve_cus >= (uint32_t)c->num_cus) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: reserve_cus leaves no CU");
+    if (s.lh == 0) return RTGO_OK;   // a rank that owns no row of the window: nothing to enqueue
     RTGO_HIP(c, hipSetDevice(c->device));
     if (!c->w_lights) RTGO_HIP(c, hipMalloc(&c->w_lights, RTGO_MAX_LIGHTS * sizeof(whitted::PointLight)));
     whitted::Params p;
@@ -2178,8 +2206,8 @@ int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t s
     p.stack_depth = c->w_walk_depth;
     p.tile_counter = c->w_tile_counters + (size_t)c->w_launch_parity * whitted::kTileHeads * whitted::kTileHeadStride;
     p.tile_counter_next = c->w_tile_counters + (size_t)(1 - c->w_launch_parity) * whitted::kTileHeads * whitted::kTileHeadStride;
-    p.tiles_x = (width + 7) / 8;
-    p.tiles_y = (height + 7) / 8;
+    p.tiles_x = (s.lw + 7) / 8;
+    p.tiles_y = (s.lh + 7) / 8;
     {
         const uint64_t nt = (uint64_t)p.tiles_x * p.tiles_y;
         auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
@@ -2203,7 +2231,8 @@ int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t s
     p.image = c->d_image;
     p.width = width;
     p.height = height;
-    p.subframe = subframe_index;
+    p.subframe = f->subframe_index;
+    p.share = s;
     p.eye = c->eye;
     p.U = c->U;
     p.V = c->V;
@@ -2229,7 +2258,9 @@ int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t s
     const size_t lds = stack_bytes + (mode == whitted::kAllInLds ? compact_bytes : (mode == whitted::kRecordsInLds ? rec_bytes : 0));
     const unsigned int n_tiles = p.tiles_x * p.tiles_y;
     unsigned int blocks = (n_tiles + (whitted::kRenderBlock / 64) - 1) / (whitted::kRenderBlock / 64);
-    if (blocks > (unsigned int)c->num_cus) blocks = (unsigned int)c->num_cus;
+    // reserve_cus as rtgo_launch takes it: at most half the CUs are left to other streams
+    const unsigned int cus = (unsigned int)c->num_cus - (f->reserve_cus < (uint32_t)c->num_cus / 2 ? f->reserve_cus : (uint32_t)c->num_cus / 2);
+    if (blocks > cus) blocks = cus;
     if (c->w_instanced) {
         const int rc = whitted_enqueue_instanced(c, p, mode_cap, blocks);
         if (rc) return rc;

@@ -56,6 +56,20 @@ struct MatTex {                 // MaterialData::Pbr's three handles, cuda/Mater
     Tex base_color, metallic_roughness, normal;
 };
 
+// The window and row band one launch renders (rtgo_whitted_frame): its k-th owned window row is row k of a compact lw-wide buffer, as on
+// the analytic path.  The full frame is x0 = y0 = 0, lw x lh = width x height, one rank.
+struct Share {
+    unsigned int x0, y0, lw, lh;   // lh: rows this rank owns (rtgo_local_rows)
+    unsigned int band_h, n_ranks, rank;
+};
+
+// local row -> global row under the band interleave (the analytic kernel's, rtgo_device.h)
+__device__ __forceinline__ unsigned int share_row(const Share& s, unsigned int ly)
+{
+    const unsigned int band = ly / s.band_h;
+    return s.y0 + (band * s.n_ranks + s.rank) * s.band_h + (ly - band * s.band_h);
+}
+
 struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74
     const float4* recs;         // the walk's records, 4 float4 each: (left min, left link) (left max, -) (right min, right link) (right max, -);
                                 //   link >= 0: a record; link < 0: a leaf, -1 - (first sorted triangle | (count - 1) << kLeafShift)
@@ -69,7 +83,7 @@ struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74
     int stack_depth;            // per-lane stack entries
     unsigned int* tile_counter; // this launch's tile queue heads (kTileHeads of them, zero at launch) and the set it zeroes for the next launch
     unsigned int* tile_counter_next;
-    unsigned int tiles_x, tiles_y;
+    unsigned int tiles_x, tiles_y;  // 8 x 8 tiles over the compact local image, lw x lh
     unsigned int tile_stride;   // coprime to tiles_x * tiles_y
     const float* positions;     // 3 floats per vertex
     const float* normals;       // 3 floats per vertex, or null (then N = Ng, LocalGeometry.h:113-116)
@@ -80,9 +94,10 @@ struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74
     const Pbr* materials;
     const PointLight* lights;
     int n_triangles, n_lights;
-    float4* accum;
+    float4* accum;              // lw x lh, local row k = the k-th window row this launch owns
     uchar4* image;
-    unsigned int width, height, subframe;
+    unsigned int width, height, subframe;   // the FULL image: seeds and ray directions
+    Share share;
     v3 eye, U, V, W, miss;
     unsigned long long* counters;   // [0] rays_total [1] rays_occlusion
 };
@@ -474,9 +489,10 @@ __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
         wt_n += 1;
 #endif
         const unsigned int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
-        const unsigned int x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
-        if (x < p.width && y < p.height) {
-            const unsigned int idx = y * p.width + x;
+        const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // in the compact local image
+        if (lx < p.share.lw && ly < p.share.lh) {
+            const unsigned int idx = ly * p.share.lw + lx;
+            const unsigned int x = p.share.x0 + lx, y = share_row(p.share, ly);   // in the full image
             // __raygen__pinhole, whitted.cu:183-240
             unsigned int seed = tea4(y * p.width + x, p.subframe);
             float jx = 0.0f, jy = 0.0f;
@@ -612,7 +628,7 @@ __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
 #ifdef RTGO_WHITTED_TIMING
         const unsigned long long wt3 = wall_clock64() + (rays == 0xFFFFFFFFu ? 1 : 0) - wt2;
         wt_tiles += wt3;
-        if (x < p.width && y < p.height) p.accum[y * p.width + x].w = (float)wt3;   // (diagnostic: ticks of the tile)
+        if (lx < p.share.lw && ly < p.share.lh) p.accum[ly * p.share.lw + lx].w = (float)wt3;   // (diagnostic: ticks of the tile)
         wt_max = wt3 > wt_max ? wt3 : wt_max;
 #endif
     }

@@ -63,6 +63,7 @@ struct InstParams {
     float4* accum;
     uchar4* image;
     unsigned int width, height, subframe;
+    Share share;
     v3 eye, U, V, W, miss;
     unsigned long long* counters;
     const int4* clusters;       // clustered meshes: (record base, triangle base, root, 0) per cluster, each mesh's in its mid level's leaf order
@@ -351,9 +352,10 @@ __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstPar
         const unsigned int tile = (unsigned int)(((unsigned long long)(pos * (unsigned int)kTileHeads + head) * p.tile_stride) % n_tiles);
         if (lane == 0u) pending = atomicAdd(p.tile_counter + kTileHeadStride * head, 1u);
         const unsigned int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
-        const unsigned int x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
-        if (x < p.width && y < p.height) {
-            const unsigned int idx = y * p.width + x;
+        const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // render_kernel's share mapping
+        if (lx < p.share.lw && ly < p.share.lh) {
+            const unsigned int idx = ly * p.share.lw + lx;
+            const unsigned int x = p.share.x0 + lx, y = share_row(p.share, ly);
             // __raygen__pinhole, whitted.cu:183-240
             unsigned int seed = tea4(y * p.width + x, p.subframe);
             float jx = 0.0f, jy = 0.0f;
