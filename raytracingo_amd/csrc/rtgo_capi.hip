@@ -485,13 +485,11 @@ int rtgo_create(int device, rtgo_ctx** out)
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildDynLds);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::sah_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(whitted::kMaxTriangles * sizeof(unsigned long long)));
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kAllInL2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kRecordsInLds>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_kernel<whitted::kAllInLds>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::render_inst_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const void* fn : {(const void*)whitted::render_kernel<whitted::kAllInL2>, (const void*)whitted::render_kernel<whitted::kRecordsInLds>,
+                           (const void*)whitted::render_kernel<whitted::kAllInLds>, (const void*)whitted::render_inst_kernel<false>,
+                           (const void*)whitted::render_inst_kernel<true>, (const void*)whitted::render_inst_kernel<false, true>,
+                           (const void*)whitted::render_inst_kernel<true, true>})
+        if (err == hipSuccess) err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whitted::kRenderLds);
     if (err == hipSuccess) err = hipDeviceSynchronize();  // the null-stream memsets above must land before any launch
     if (err != hipSuccess) {
         std::string m = std::string("rtgo_create: ") + hipGetErrorString(err);
@@ -1467,9 +1465,16 @@ static int whitted_tile_heads(rtgo_ctx* c)
 // One structure of the whitted path, built on the device over n triangles (positions, indices: device memory): build_kernel's Morton
 // hierarchy, its records rebuilt top-down with the surface-area heuristic (sah_kernel) when the leaves fit its LDS, and the Morton
 // records again when the surface-area tree comes out deeper than the walk's stack.  nodes: (2n - 1) x 2 float4; scratch: 38 n + 16
-// ints; recs: n x 4 float4; tris: n x 3 float4; qrecs: n x 2 uint4; tidx: n uint2.  m = build_kernel's out_meta.  Synchronous.
+// ints; recs: n x 4 float4; tris: n x 3 float4; qrecs: n x 2 uint4; tidx: n uint2.  Synchronous.
+struct WhittedBuildMeta {   // build_kernel's out_meta as it lays it out (sah_kernel rewrites n_recs and walk_depth)
+    int depth;              // of the Morton hierarchy
+    int n_recs;             // records of the walk; 0: the structure is one leaf
+    int walk_depth;         // stack entries the walk needs
+    v3 grid_lo, grid_step;  // the grid of the compact records
+};
+static_assert(sizeof(WhittedBuildMeta) == 9 * sizeof(int), "build_kernel's out_meta");
 static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int* indices, int n, float4* nodes, int* scratch, float4* recs, float4* tris,
-                         uint4* qrecs, uint2* tidx, int m[9], const char* what)
+                         uint4* qrecs, uint2* tidx, WhittedBuildMeta& m, const char* what)
 {
     int* parent = scratch;   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
     int* visit = parent + (2 * n - 1);
@@ -1490,24 +1495,44 @@ static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int
                            (const int*)first_of, (const int*)count_of, meta + 16, recs, qrecs, meta);
         RTGO_HIP(c, hipGetLastError());
     }
-    for (int k = 0; k < 9; ++k) m[k] = 0;
-    RTGO_HIP(c, hipMemcpyAsync(m, meta, 9 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    std::memset(&m, 0, sizeof m);
+    RTGO_HIP(c, hipMemcpyAsync(&m, meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (m[2] > whitted::kMaxWalkDepth && sah) {
+    if (m.walk_depth > whitted::kMaxWalkDepth && sah) {
         // the surface-area tree came out deeper than the walk's stack (it has no depth bound of its own): back to the Morton records,
         // whose depth is bounded by the code length
         hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, nodes,
                            parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, meta);
         RTGO_HIP(c, hipGetLastError());
-        RTGO_HIP(c, hipMemcpyAsync(m, meta, 9 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipMemcpyAsync(&m, meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
         RTGO_HIP(c, hipStreamSynchronize(c->stream));
     }
-    if (m[0] > 2 * whitted::kStack)
-        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": triangle LBVH depth " + std::to_string(m[0]) + " exceeds what the build handles (" +
+    if (m.depth > 2 * whitted::kStack)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": triangle LBVH depth " + std::to_string(m.depth) + " exceeds what the build handles (" +
                                                std::to_string(2 * whitted::kStack) + ")");
-    if (m[2] > whitted::kMaxWalkDepth)
-        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the walk needs " + std::to_string(m[2]) + " stack entries (limit " +
+    if (m.walk_depth > whitted::kMaxWalkDepth)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the walk needs " + std::to_string(m.walk_depth) + " stack entries (limit " +
                                                std::to_string(whitted::kMaxWalkDepth) + ")");
+    return RTGO_OK;
+}
+
+// The checks every mesh of the whitted path passes (rtgo_whitted_set_mesh, rtgo_whitted_set_scene; `at` names it in the messages): vertex
+// indices inside the vertex array, finite vertex data, material indices inside the table.  Also finds the mesh's largest material index.
+static int whitted_check_mesh(rtgo_ctx* c, const rtgo_whitted_mesh& q, uint32_t n_materials, const std::string& at, uint32_t& max_material)
+{
+    for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
+        if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
+    for (uint32_t i = 0; i < 3 * q.n_vertices; ++i)
+        if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
+    if (q.texcoords)
+        for (uint32_t i = 0; i < 2 * q.n_vertices; ++i)
+            if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + ": non-finite texture coordinate");
+    max_material = 0;
+    if (q.material_of_triangle)
+        for (uint32_t i = 0; i < q.n_triangles; ++i) {
+            if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material index beyond the material array");
+            max_material = std::max(max_material, q.material_of_triangle[i]);
+        }
     return RTGO_OK;
 }
 
@@ -1517,13 +1542,10 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
     if (!c || !positions || !indices || !materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_mesh: NULL argument");
     if (n_triangles == 0 || n_triangles > RTGO_MAX_TRIANGLES || n_vertices == 0 || n_materials == 0)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_mesh: triangle count must be in [1, " + std::to_string(RTGO_MAX_TRIANGLES) + "], vertices and materials non-empty");
-    for (uint32_t i = 0; i < 3 * n_triangles; ++i)
-        if (indices[i] >= n_vertices) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_mesh: index beyond the vertex array");
-    for (uint32_t i = 0; i < 3 * n_vertices; ++i)
-        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_mesh: non-finite vertex data");
-    if (material_of_triangle)
-        for (uint32_t i = 0; i < n_triangles; ++i)
-            if (material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_mesh: material index beyond the material array");
+    const rtgo_whitted_mesh mesh = {positions, normals, nullptr, n_vertices, indices, material_of_triangle, n_triangles};
+    uint32_t max_material;
+    const int rc0 = whitted_check_mesh(c, mesh, n_materials, "rtgo_whitted_set_mesh", max_material);
+    if (rc0) return rc0;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     free_mesh(c);
@@ -1548,15 +1570,15 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
     RTGO_HIP(c, hipMalloc(&c->w_qrecs, (size_t)n_triangles * 2 * sizeof(uint4)));
     RTGO_HIP(c, hipMalloc(&c->w_tidx, (size_t)n_triangles * sizeof(uint2)));
     RTGO_HIP(c, hipMalloc(&c->w_scratch, (size_t)(6 * n_triangles + 16 + 32 * n_triangles) * sizeof(int)));   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
-    int m[9];
+    WhittedBuildMeta m;
     const int rc = whitted_build(c, c->w_positions, c->w_indices, (int)n_triangles, c->w_nodes, c->w_scratch, c->w_recs, c->w_tris, c->w_qrecs, c->w_tidx, m,
                                  "rtgo_whitted_set_mesh");
     if (rc) return rc;
-    c->w_n_recs = m[1];
+    c->w_n_recs = m.n_recs;
     c->w_n_vertices = (int)n_vertices;
-    std::memcpy(&c->w_grid_lo, &m[3], 3 * sizeof(float));
-    std::memcpy(&c->w_grid_step, &m[6], 3 * sizeof(float));
-    c->w_walk_depth = m[2] < 1 ? 1 : m[2];
+    c->w_grid_lo = m.grid_lo;
+    c->w_grid_step = m.grid_step;
+    c->w_walk_depth = m.walk_depth < 1 ? 1 : m.walk_depth;
     const int rc2 = whitted_tile_heads(c);
     if (rc2) return rc2;
     c->w_triangles = (int)n_triangles;
@@ -1637,18 +1659,26 @@ static int whitted_prepare_instances(rtgo_ctx* c, const std::vector<WhittedMeshI
     return RTGO_OK;
 }
 
+// The index array that hands n boxes to whitted_build (box k: "vertices" 2k = lo, 2k + 1 = hi) as the degenerate triangles (lo, hi, lo),
+// whose bounds are the boxes: the top level's and the mid levels' builds
+static std::vector<unsigned int> whitted_box_indices(int n)
+{
+    std::vector<unsigned int> idx((size_t)3 * n);
+    for (int k = 0; k < n; ++k) {
+        idx[3 * k + 0] = 2 * k;
+        idx[3 * k + 1] = 2 * k + 1;
+        idx[3 * k + 2] = 2 * k;
+    }
+    return idx;
+}
+
 // the top level over prepared instances: build_kernel + sah_kernel over the instance boxes, the InstWalk records in leaf order, and the
 // stack both levels need.  Replaces the context's top level only once all of it succeeded.
 static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos, const rtgo_whitted_instance* inst,
                              const char* what)
 {
     const int n = (int)shade.size();
-    std::vector<unsigned int> box_idx((size_t)3 * n);
-    for (int i = 0; i < n; ++i) {
-        box_idx[3 * i + 0] = 2 * i;
-        box_idx[3 * i + 1] = 2 * i + 1;
-        box_idx[3 * i + 2] = 2 * i;
-    }
+    const std::vector<unsigned int> box_idx = whitted_box_indices(n);
     float* d_pos = nullptr;
     unsigned int* d_idx = nullptr;
     float4 *d_nodes = nullptr, *d_recs = nullptr, *d_tris = nullptr;
@@ -1688,14 +1718,14 @@ static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>&
     RTGO_TOP_HIP(hipMalloc(&d_scratch, (size_t)(38 * n + 16) * sizeof(int)));
     RTGO_TOP_HIP(hipMemcpyAsync(d_pos, box_pos.data(), box_pos.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     RTGO_TOP_HIP(hipMemcpyAsync(d_idx, box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
-    int m[9];
+    WhittedBuildMeta m;
     const int rc = whitted_build(c, d_pos, d_idx, n, d_nodes, d_scratch, d_recs, d_tris, d_qrecs, d_tidx, m, what);
     if (rc) return fail_all(rc);
     // leaf order: build_kernel's Morton-ordered "triangles" carry the instance index in .w of their first corner
     std::vector<float4> order((size_t)3 * n);
     RTGO_TOP_HIP(hipMemcpyAsync(order.data(), d_tris, order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_TOP_HIP(hipStreamSynchronize(c->stream));
-    const int top_depth = m[1] > 0 ? m[2] : 0;
+    const int top_depth = m.n_recs > 0 ? m.walk_depth : 0;
     const int depth = top_depth + c->w_mesh_depth;
     if (depth > whitted::kMaxInstWalkDepth)
         return fail_all(fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
@@ -1718,7 +1748,7 @@ static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>&
     c->w_top_recs = d_recs;
     c->w_inst = d_inst;
     c->w_inst_shade = d_shade;
-    c->w_n_top_recs = m[1];
+    c->w_n_top_recs = m.n_recs;
     c->w_n_instances = n;
     c->w_walk_depth = depth < 1 ? 1 : depth;
     return RTGO_OK;
@@ -1784,30 +1814,25 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
     int rec = mi.rec_base + ncl - 1, cdepth = 0;
     for (int k = 0; k < ncl; ++k) {
         const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
-        int m[9];
+        WhittedBuildMeta m;
         const int rc = whitted_build(c, positions, bs.cidx + 3 * (size_t)s, nc, c->w_nodes, c->w_scratch, c->w_recs + 4 * (size_t)rec,
                                      c->w_tris + 3 * ((size_t)mi.tri_base + s), c->w_qrecs + 2 * ((size_t)mi.tri_base + s), c->w_tidx + mi.tri_base + s, m, what);
         if (rc) return rc;
         crec[k] = rec;
-        croot[k] = m[1] > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
-        cdepth = std::max(cdepth, m[1] > 0 ? m[2] : 0);
-        rec += m[1];
+        croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
+        cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
+        rec += m.n_recs;
     }
     hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->w_tris + 3 * (size_t)mi.tri_base, sorted, n, ncl);
     RTGO_HIP(c, hipGetLastError());
-    // the mid level: the clusters' boxes as the degenerate triangles (lo, hi, lo), the top level's recipe
-    std::vector<unsigned int> box_idx((size_t)3 * ncl);
-    for (int k = 0; k < ncl; ++k) {
-        box_idx[3 * k + 0] = 2 * k;
-        box_idx[3 * k + 1] = 2 * k + 1;
-        box_idx[3 * k + 2] = 2 * k;
-    }
+    // the mid level over the clusters' boxes
+    const std::vector<unsigned int> box_idx = whitted_box_indices(ncl);
     RTGO_HIP(c, hipMemcpyAsync(bs.crec, crec.data(), ncl * sizeof(int), hipMemcpyHostToDevice, c->stream));
     RTGO_HIP(c, hipMemcpyAsync(bs.mid_idx, box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)c->w_recs, (const int*)bs.crec, ncl,
                        bs.mid_pos);
     RTGO_HIP(c, hipGetLastError());
-    int m[9];
+    WhittedBuildMeta m;
     const int rc = whitted_build(c, bs.mid_pos, bs.mid_idx, ncl, c->w_nodes, c->w_scratch, c->w_recs + 4 * (size_t)mi.rec_base, bs.mid_tris, bs.mid_qrecs,
                                  bs.mid_tidx, m, what);
     if (rc) return rc;
@@ -1816,7 +1841,7 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
     std::vector<float> boxes((size_t)6 * ncl);
     RTGO_HIP(c, hipMemcpyAsync(order.data(), bs.mid_tris, order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.mid_pos, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (m[1] > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), c->w_recs + 4 * (size_t)mi.rec_base, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (m.n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), c->w_recs + 4 * (size_t)mi.rec_base, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     const int tbase = (int)table.size();
     for (int pos = 0; pos < ncl; ++pos) {
@@ -1833,13 +1858,13 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
             mi.hi[a] = std::fmax(mi.hi[a], h[a]);
         }
     };
-    if (m[1] > 0) {
+    if (m.n_recs > 0) {
         widen(root_rec[0].x, root_rec[0].y, root_rec[0].z, root_rec[1].x, root_rec[1].y, root_rec[1].z);
         widen(root_rec[2].x, root_rec[2].y, root_rec[2].z, root_rec[3].x, root_rec[3].y, root_rec[3].z);
     }
     for (int k = 0; k < ncl; ++k) widen(boxes[6 * k + 0], boxes[6 * k + 1], boxes[6 * k + 2], boxes[6 * k + 3], boxes[6 * k + 4], boxes[6 * k + 5]);
-    mi.root = 1 + ((tbase << 3) | (m[1] > 0 ? kMidHasRecords : ncl - 1));
-    mi.depth = (m[1] > 0 ? m[2] : 0) + cdepth;
+    mi.root = 1 + ((tbase << 3) | (m.n_recs > 0 ? kMidHasRecords : ncl - 1));
+    mi.depth = (m.n_recs > 0 ? m.walk_depth : 0) + cdepth;
     return RTGO_OK;
 }
 
@@ -1861,26 +1886,14 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
             return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESH_TRIANGLES) + "], vertices non-empty");
         if (n_tri + q.n_triangles > RTGO_WHITTED_MAX_SCENE_TRIANGLES)
             return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
+        WhittedMeshInfo& mi = info[k];
+        const int rc0 = whitted_check_mesh(c, q, n_materials, at, mi.max_material);
+        if (rc0) return rc0;
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < 3 * q.n_triangles; ++i) {
-            if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
-        }
-        for (uint32_t i = 0; i < 3 * q.n_vertices; ++i)
-            if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
-        if (q.texcoords)
-            for (uint32_t i = 0; i < 2 * q.n_vertices; ++i)
-                if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + ": non-finite texture coordinate");
         for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
             for (int a = 0; a < 3; ++a) {
                 lo[a] = std::fmin(lo[a], q.positions[3 * q.indices[i] + a]);
                 hi[a] = std::fmax(hi[a], q.positions[3 * q.indices[i] + a]);
-            }
-        WhittedMeshInfo& mi = info[k];
-        mi.max_material = 0;
-        if (q.material_of_triangle)
-            for (uint32_t i = 0; i < q.n_triangles; ++i) {
-                if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material index beyond the material array");
-                mi.max_material = std::max(mi.max_material, q.material_of_triangle[i]);
             }
         // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
         float maxext = 0.0f;
@@ -1977,7 +1990,7 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
             mesh_depth = std::max(mesh_depth, mi.depth);
             continue;
         }
-        int m[9];
+        WhittedBuildMeta m;
         rc = whitted_build(c, c->w_positions + 3 * (size_t)mi.vert_base, c->w_indices + 3 * (size_t)mi.tri_base, nt, c->w_nodes, c->w_scratch,
                            c->w_recs + 4 * (size_t)mi.rec_base, c->w_tris + 3 * (size_t)mi.tri_base, c->w_qrecs + 2 * (size_t)mi.tri_base,
                            c->w_tidx + mi.tri_base, m, "rtgo_whitted_set_scene");
@@ -1985,8 +1998,8 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
             free_mesh(c);
             return rc;
         }
-        mi.root = m[1] > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
-        mi.depth = m[1] > 0 ? m[2] : 0;
+        mi.root = m.n_recs > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
+        mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
         mesh_depth = std::max(mesh_depth, mi.depth);
     }
     if (!table.empty()) {
@@ -2098,13 +2111,47 @@ int rtgo_whitted_set_miss_color(rtgo_ctx* c, const float rgb[3])
     return RTGO_OK;
 }
 
-// the launch of an instanced scene: rtgo_whitted_launch's frame, tile queue and buffers over the two-level structure.  The top level's
-// records and InstWalk array go to LDS beside the stacks when they fit (and RTGO_WHITTED_MODE allows any LDS residency); the meshes'
-// records and triangles are read through L2 (kAllInL2's way).
-static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Params& p, int mode_cap, unsigned int blocks)
+// The launch of one mesh (rtgo_whitted_set_mesh).  Beside the lanes' stacks (stack_bytes), its LDS holds as much of the structure as
+// fits: everything in its compact form (quantised records, vertices, 16-bit vertex indices), or the fp32 records alone, or nothing.
+static int whitted_enqueue_mesh(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
+{
+    whitted::Params p;
+    std::memset(&p, 0, sizeof p);
+    p.frame = fr;
+    p.recs = c->w_recs;
+    p.tris = c->w_tris;
+    p.qrecs = c->w_qrecs;
+    p.tidx = c->w_tidx;
+    p.n_vertices = c->w_n_vertices;
+    p.grid_lo = c->w_grid_lo;
+    p.grid_step = c->w_grid_step;
+    p.n_recs = c->w_n_recs;
+    p.n_triangles = c->w_triangles;
+    p.positions = c->w_positions;
+    p.normals = c->w_normals;
+    p.indices = c->w_indices;
+    p.tri_material = c->w_tri_material;
+    p.texcoords = c->w_texcoords;
+    const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
+    const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
+    const dim3 grid(blocks), block(whitted::kRenderBlock);
+    if (mode_cap >= whitted::kAllInLds && p.n_vertices <= 65535 && compact_bytes + stack_bytes <= whitted::kRenderLds)
+        hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, grid, block, compact_bytes + stack_bytes, c->stream, p);
+    else if (mode_cap >= whitted::kRecordsInLds && rec_bytes + stack_bytes <= whitted::kRenderLds)
+        hipLaunchKernelGGL(whitted::render_kernel<whitted::kRecordsInLds>, grid, block, rec_bytes + stack_bytes, c->stream, p);
+    else
+        hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInL2>, grid, block, stack_bytes, c->stream, p);
+    RTGO_HIP(c, hipGetLastError());
+    return RTGO_OK;
+}
+
+// The launch of an instanced scene.  The top level's records and InstWalk array go to LDS beside the stacks when they fit (and
+// RTGO_WHITTED_MODE allows any LDS residency); the meshes' records and triangles are read through L2 (kAllInL2's way).
+static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
 {
     whitted::InstParams q;
     std::memset(&q, 0, sizeof q);
+    q.frame = fr;
     q.top_recs = c->w_top_recs;
     q.inst = c->w_inst;
     q.shade = c->w_inst_shade;
@@ -2112,47 +2159,23 @@ static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Params& p, int 
     q.n_instances = c->w_n_instances;
     q.recs = c->w_recs;
     q.tris = c->w_tris;
+    q.clusters = c->w_clusters;
     q.positions = c->w_positions;
     q.normals = c->w_normals;
     q.texcoords = c->w_texcoords;
     q.indices = c->w_indices;
     q.tri_material = c->w_tri_material;
-    q.stack_depth = c->w_walk_depth;
-    q.tile_counter = p.tile_counter;
-    q.tile_counter_next = p.tile_counter_next;
-    q.tiles_x = p.tiles_x;
-    q.tiles_y = p.tiles_y;
-    q.tile_stride = p.tile_stride;
-    q.mat_tex = p.mat_tex;
-    q.materials = p.materials;
-    q.lights = p.lights;
-    q.n_lights = p.n_lights;
-    q.accum = p.accum;
-    q.image = p.image;
-    q.width = p.width;
-    q.height = p.height;
-    q.subframe = p.subframe;
-    q.share = p.share;
-    q.eye = p.eye;
-    q.U = p.U;
-    q.V = p.V;
-    q.W = p.W;
-    q.miss = p.miss;
-    q.counters = p.counters;
-    q.clusters = c->w_clusters;
-    const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)q.stack_depth * sizeof(unsigned short);
     const size_t top_bytes = (size_t)q.n_top_recs * 4 * sizeof(float4) + (size_t)q.n_instances * sizeof(whitted::InstWalk);
-    const size_t lds_cap = 160 * 1024;
-    const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= lds_cap;
-    if (c->w_clusters) {   // a clustered mesh in the scene: the three-level walk
-        if (in_lds)
-            hipLaunchKernelGGL((whitted::render_inst_kernel<true, true>), dim3(blocks), dim3(whitted::kRenderBlock), top_bytes + stack_bytes, c->stream, q);
-        else
-            hipLaunchKernelGGL((whitted::render_inst_kernel<false, true>), dim3(blocks), dim3(whitted::kRenderBlock), stack_bytes, c->stream, q);
+    const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= whitted::kRenderLds;
+    const size_t lds = stack_bytes + (in_lds ? top_bytes : 0);
+    const dim3 grid(blocks), block(whitted::kRenderBlock);
+    if (q.clusters) {   // a clustered mesh in the scene: the three-level walk
+        if (in_lds) hipLaunchKernelGGL((whitted::render_inst_kernel<true, true>), grid, block, lds, c->stream, q);
+        else hipLaunchKernelGGL((whitted::render_inst_kernel<false, true>), grid, block, lds, c->stream, q);
     } else if (in_lds)
-        hipLaunchKernelGGL(whitted::render_inst_kernel<true>, dim3(blocks), dim3(whitted::kRenderBlock), top_bytes + stack_bytes, c->stream, q);
+        hipLaunchKernelGGL(whitted::render_inst_kernel<true>, grid, block, lds, c->stream, q);
     else
-        hipLaunchKernelGGL(whitted::render_inst_kernel<false>, dim3(blocks), dim3(whitted::kRenderBlock), stack_bytes, c->stream, q);
+        hipLaunchKernelGGL(whitted::render_inst_kernel<false>, grid, block, lds, c->stream, q);
     RTGO_HIP(c, hipGetLastError());
     return RTGO_OK;
 }
@@ -2193,81 +2216,53 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     if (s.lh == 0) return RTGO_OK;   // a rank that owns no row of the window: nothing to enqueue
     RTGO_HIP(c, hipSetDevice(c->device));
     if (!c->w_lights) RTGO_HIP(c, hipMalloc(&c->w_lights, RTGO_MAX_LIGHTS * sizeof(whitted::PointLight)));
-    whitted::Params p;
-    std::memset(&p, 0, sizeof p);
-    p.recs = c->w_recs;
-    p.tris = c->w_tris;
-    p.n_recs = c->w_n_recs;
-    p.qrecs = c->w_qrecs;
-    p.tidx = c->w_tidx;
-    p.n_vertices = c->w_n_vertices;
-    p.grid_lo = c->w_grid_lo;
-    p.grid_step = c->w_grid_step;
-    p.stack_depth = c->w_walk_depth;
-    p.tile_counter = c->w_tile_counters + (size_t)c->w_launch_parity * whitted::kTileHeads * whitted::kTileHeadStride;
-    p.tile_counter_next = c->w_tile_counters + (size_t)(1 - c->w_launch_parity) * whitted::kTileHeads * whitted::kTileHeadStride;
-    p.tiles_x = (s.lw + 7) / 8;
-    p.tiles_y = (s.lh + 7) / 8;
+    whitted::Frame fr;
+    std::memset(&fr, 0, sizeof fr);
+    fr.tile_counter = c->w_tile_counters + (size_t)c->w_launch_parity * whitted::kTileHeads * whitted::kTileHeadStride;
+    fr.tile_counter_next = c->w_tile_counters + (size_t)(1 - c->w_launch_parity) * whitted::kTileHeads * whitted::kTileHeadStride;
+    fr.tiles_x = (s.lw + 7) / 8;
+    fr.tiles_y = (s.lh + 7) / 8;
     {
-        const uint64_t nt = (uint64_t)p.tiles_x * p.tiles_y;
+        const uint64_t nt = (uint64_t)fr.tiles_x * fr.tiles_y;
         auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
         uint64_t stride = (uint64_t)((double)nt * 0.6180339887498949);
         if (stride < 1) stride = 1;
         while (gcd(stride, nt) != 1) ++stride;   // (terminates: nt - 1 and 1 are coprime to nt)
-        p.tile_stride = (unsigned int)(stride % (nt > 1 ? nt : 2));
-        if (p.tile_stride == 0) p.tile_stride = 1;
+        fr.tile_stride = (unsigned int)(stride % (nt > 1 ? nt : 2));
+        if (fr.tile_stride == 0) fr.tile_stride = 1;
     }
-    p.positions = c->w_positions;
-    p.normals = c->w_normals;
-    p.indices = c->w_indices;
-    p.tri_material = c->w_tri_material;
-    p.texcoords = c->w_texcoords;
-    p.mat_tex = c->w_mat_tex;
-    p.materials = c->w_materials;
-    p.lights = c->w_lights;
-    p.n_triangles = c->w_triangles;
-    p.n_lights = c->w_n_lights;
-    p.accum = c->d_accum;
-    p.image = c->d_image;
-    p.width = width;
-    p.height = height;
-    p.subframe = f->subframe_index;
-    p.share = s;
-    p.eye = c->eye;
-    p.U = c->U;
-    p.V = c->V;
-    p.W = c->W;
-    p.miss = c->w_miss;
-    p.counters = c->d_counters;
+    fr.mat_tex = c->w_mat_tex;
+    fr.materials = c->w_materials;
+    fr.lights = c->w_lights;
+    fr.n_lights = c->w_n_lights;
+    fr.accum = c->d_accum;
+    fr.image = c->d_image;
+    fr.width = width;
+    fr.height = height;
+    fr.subframe = f->subframe_index;
+    fr.share = s;
+    fr.eye = c->eye;
+    fr.U = c->U;
+    fr.V = c->V;
+    fr.W = c->W;
+    fr.miss = c->w_miss;
+    fr.counters = c->d_counters;
     if (c->ev_pending == rtgo_ctx::kEvRing) {
         int rc = harvest_events(c, 1);
         if (rc) return rc;
     }
     const int slot = c->ev_head;
     RTGO_HIP(c, hipEventRecord(c->ev_start[slot], c->stream));
-    // one persistent workgroup per CU.  Its LDS holds, beside the lanes' stacks, as much of the structure as fits: everything in
-    // its compact form (quantised records, vertices, 16-bit vertex indices), or the fp32 records alone, or nothing
-    const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)p.stack_depth * sizeof(unsigned short);
-    const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
-    const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
-    const size_t lds_cap = 160 * 1024;
-    const int mode_cap = env_whitted_mode();
-    int mode = whitted::kAllInL2;
-    if (mode_cap >= whitted::kAllInLds && p.n_vertices <= 65535 && compact_bytes + stack_bytes <= lds_cap) mode = whitted::kAllInLds;
-    else if (mode_cap >= whitted::kRecordsInLds && rec_bytes + stack_bytes <= lds_cap) mode = whitted::kRecordsInLds;
-    const size_t lds = stack_bytes + (mode == whitted::kAllInLds ? compact_bytes : (mode == whitted::kRecordsInLds ? rec_bytes : 0));
-    const unsigned int n_tiles = p.tiles_x * p.tiles_y;
+    // one persistent workgroup per CU; its LDS holds the lanes' stacks and, beside them, as much of the structure as fits
+    const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)c->w_walk_depth * sizeof(unsigned short);
+    const unsigned int n_tiles = fr.tiles_x * fr.tiles_y;
     unsigned int blocks = (n_tiles + (whitted::kRenderBlock / 64) - 1) / (whitted::kRenderBlock / 64);
     // reserve_cus as rtgo_launch takes it: at most half the CUs are left to other streams
     const unsigned int cus = (unsigned int)c->num_cus - (f->reserve_cus < (uint32_t)c->num_cus / 2 ? f->reserve_cus : (uint32_t)c->num_cus / 2);
     if (blocks > cus) blocks = cus;
-    if (c->w_instanced) {
-        const int rc = whitted_enqueue_instanced(c, p, mode_cap, blocks);
-        if (rc) return rc;
-    } else if (mode == whitted::kAllInLds) hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
-    else if (mode == whitted::kRecordsInLds) hipLaunchKernelGGL(whitted::render_kernel<whitted::kRecordsInLds>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
-    else hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInL2>, dim3(blocks), dim3(whitted::kRenderBlock), lds, c->stream, p);
-    RTGO_HIP(c, hipGetLastError());
+    const int rc = c->w_instanced ? whitted_enqueue_instanced(c, fr, stack_bytes, env_whitted_mode(), blocks)
+                                  : whitted_enqueue_mesh(c, fr, stack_bytes, env_whitted_mode(), blocks);
+    if (rc) return rc;
     c->w_launch_parity = 1 - c->w_launch_parity;   // (only once the launch that zeroes the other head is in the stream)
     RTGO_HIP(c, hipEventRecord(c->ev_stop[slot], c->stream));
     c->ev_head = (c->ev_head + 1) % rtgo_ctx::kEvRing;

@@ -23,6 +23,7 @@ constexpr int kLeafShift = 13;        // leaf code = first sorted triangle | (co
 constexpr int kBuildThreads = 1024;
 constexpr int kStack = 32;            // the bottom-up fit runs 2 * kStack + 2 = 66 passes: enough for any Karras hierarchy over 30-bit codes of <= 8192 triangles (depth <= 43)
 constexpr int kRenderBlock = 1024;    // one workgroup per CU shares one LDS copy of the records
+constexpr size_t kRenderLds = 160 * 1024;   // the most LDS a render workgroup takes: its stacks and what of the structure fits beside them
 #ifndef RTGO_LEAF_TRIS
 #define RTGO_LEAF_TRIS 4
 #endif
@@ -70,7 +71,26 @@ __device__ __forceinline__ unsigned int share_row(const Share& s, unsigned int l
     return s.y0 + (band * s.n_ranks + s.rank) * s.band_h + (ly - band * s.band_h);
 }
 
-struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74
+// What a launch renders, whatever structure it walks (rtgo_whitted_launch_frame fills it once; Params and InstParams embed it)
+struct Frame {
+    unsigned int* tile_counter; // this launch's tile queue heads (kTileHeads of them, zero at launch) and the set it zeroes for the next launch
+    unsigned int* tile_counter_next;
+    unsigned int tiles_x, tiles_y;  // 8 x 8 tiles over the compact local image, lw x lh
+    unsigned int tile_stride;   // coprime to tiles_x * tiles_y
+    const MatTex* mat_tex;      // per material, or null when no material has a texture
+    const Pbr* materials;
+    const PointLight* lights;
+    int n_lights;
+    float4* accum;              // lw x lh, local row k = the k-th window row this launch owns
+    uchar4* image;
+    unsigned int width, height, subframe;   // the FULL image: seeds and ray directions
+    Share share;
+    v3 eye, U, V, W, miss;
+    unsigned long long* counters;   // [0] rays_total [1] rays_occlusion
+};
+
+struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74, over one mesh in world space
+    Frame frame;
     const float4* recs;         // the walk's records, 4 float4 each: (left min, left link) (left max, -) (right min, right link) (right max, -);
                                 //   link >= 0: a record; link < 0: a leaf, -1 - (first sorted triangle | (count - 1) << kLeafShift)
     const float4* tris;         // 3 float4 per triangle in Morton order: (P0, original index) (P1, -) (P2, -)
@@ -80,26 +100,12 @@ struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74
     int n_vertices;
     v3 grid_lo, grid_step;      // world = grid_lo + cell * grid_step
     int n_recs;                 // 0: the whole mesh is one leaf (at most kLeafTris triangles)
-    int stack_depth;            // per-lane stack entries
-    unsigned int* tile_counter; // this launch's tile queue heads (kTileHeads of them, zero at launch) and the set it zeroes for the next launch
-    unsigned int* tile_counter_next;
-    unsigned int tiles_x, tiles_y;  // 8 x 8 tiles over the compact local image, lw x lh
-    unsigned int tile_stride;   // coprime to tiles_x * tiles_y
+    int n_triangles;
     const float* positions;     // 3 floats per vertex
     const float* normals;       // 3 floats per vertex, or null (then N = Ng, LocalGeometry.h:113-116)
     const unsigned int* indices;    // 3 per triangle
     const unsigned int* tri_material;
     const float* texcoords;     // 2 floats per vertex, or null (then UV = the barycentrics, LocalGeometry.h:97-102)
-    const MatTex* mat_tex;      // per material, or null when no material has a texture
-    const Pbr* materials;
-    const PointLight* lights;
-    int n_triangles, n_lights;
-    float4* accum;              // lw x lh, local row k = the k-th window row this launch owns
-    uchar4* image;
-    unsigned int width, height, subframe;   // the FULL image: seeds and ray directions
-    Share share;
-    v3 eye, U, V, W, miss;
-    unsigned long long* counters;   // [0] rays_total [1] rays_occlusion
 };
 
 // tea<4>, cuda/random.h:30-45 with N = 4
@@ -194,16 +200,53 @@ __device__ __forceinline__ bool leaf_tris(const float4* __restrict__ tris, int f
     return false;
 }
 
+// the reciprocal direction of the slab tests (exact, with a finite stand-in for division by zero)
+__device__ __forceinline__ v3 safe_inv(v3 d)
+{
+    auto inv = [](float x) { return fabsf(x) < 1e-30f ? copysignf(1e30f, x) : 1.0f / x; };
+    return mk(inv(d.x), inv(d.y), inv(d.z));
+}
+
+// One step of a walk over 64-byte records (every level of every walk but trace_lds): read ONE record -- both children's boxes, 64
+// contiguous bytes -- descend into the nearer child that is hit and park the other one on the lane's stack (2-byte entries: a record
+// index, or 0x8000 | leaf code).  False: neither child is hit.
+__device__ __forceinline__ bool record_step(const float4* __restrict__ recs, int& cur, unsigned short* __restrict__ s_stack, int stride, int& sp, v3 o,
+                                            v3 id, float tmin, float bt)
+{
+    const float4 a0 = recs[4 * cur + 0], a1 = recs[4 * cur + 1], b0 = recs[4 * cur + 2], b1 = recs[4 * cur + 3];
+    float tl, tr;
+    const bool hl = node_hit(a0, a1, o, id, tmin, bt, tl);
+    const bool hr = node_hit(b0, b1, o, id, tmin, bt, tr);
+    const int ll = __float_as_int(a0.w), lr = __float_as_int(b0.w);
+    const bool go_r = hr && (!hl || tr < tl);
+    if (hl && hr) {
+        const int far = go_r ? ll : lr;
+        s_stack[sp * stride] = (unsigned short)(far >= 0 ? far : (0x8000 | (-1 - far)));
+        ++sp;
+    }
+    if (hl || hr) {
+        cur = go_r ? lr : ll;
+        return true;
+    }
+    return false;
+}
+// the next parked entry above sp_floor (a level's own part of the lane stack); false: that part is empty
+__device__ __forceinline__ bool pop_entry(const unsigned short* __restrict__ s_stack, int stride, int& sp, int sp_floor, int& cur)
+{
+    if (sp == sp_floor) return false;
+    --sp;
+    const int e = (int)s_stack[sp * stride];
+    cur = (e & 0x8000) ? -1 - (e & 0x7FFF) : e;
+    return true;
+}
+
 // closest hit (ANY = false: smallest t, lowest triangle index on ties) or any hit (ANY = true: the occlusion ray's
-// OPTIX_RAY_FLAG_TERMINATE_ON_FIRST_HIT, whitted.cu:140-151) over the triangle LBVH.  A step reads ONE record -- both
-// children's boxes, 64 contiguous bytes -- descends into the nearer child that is hit and parks the other one on the lane's
-// stack (2-byte entries: a record index, or 0x8000 | leaf code).
-template <bool ANY, typename Recs>
-__device__ __forceinline__ bool trace(const Params& p, Recs recs, unsigned short* __restrict__ s_stack, int stride, v3 o, v3 d, float tmin, float tmax,
+// OPTIX_RAY_FLAG_TERMINATE_ON_FIRST_HIT, whitted.cu:140-151) over the triangle LBVH, one record_step at a time.
+template <bool ANY>
+__device__ __forceinline__ bool trace(const Params& p, const float4* recs, unsigned short* __restrict__ s_stack, int stride, v3 o, v3 d, float tmin, float tmax,
                                       int& tri_out, int& pos_out, float& t_out, float& u_out, float& v_out)
 {
-    auto safe_inv = [](float x) { return fabsf(x) < 1e-30f ? copysignf(1e30f, x) : 1.0f / x; };
-    const v3 id = mk(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+    const v3 id = safe_inv(d);
     int best = -1, best_pos = 0;
     float bt = tmax, bu = 0.0f, bv = 0.0f;
     if (p.n_recs == 0) {
@@ -214,31 +257,12 @@ __device__ __forceinline__ bool trace(const Params& p, Recs recs, unsigned short
         for (;;) {
             bool pop = true;
             if (cur >= 0) {
-                const float4 a0 = recs[4 * cur + 0], a1 = recs[4 * cur + 1], b0 = recs[4 * cur + 2], b1 = recs[4 * cur + 3];
-                float tl, tr;
-                const bool hl = node_hit(a0, a1, o, id, tmin, bt, tl);
-                const bool hr = node_hit(b0, b1, o, id, tmin, bt, tr);
-                const int ll = __float_as_int(a0.w), lr = __float_as_int(b0.w);
-                const bool go_r = hr && (!hl || tr < tl);
-                if (hl && hr) {
-                    const int far = go_r ? ll : lr;
-                    s_stack[sp * stride] = (unsigned short)(far >= 0 ? far : (0x8000 | (-1 - far)));
-                    ++sp;
-                }
-                if (hl || hr) {
-                    cur = go_r ? lr : ll;
-                    pop = false;
-                }
+                pop = !record_step(recs, cur, s_stack, stride, sp, o, id, tmin, bt);
             } else {
                 const int code = -1 - cur;
                 if (leaf_tris<ANY>(p.tris, code & ((1 << kLeafShift) - 1), (code >> kLeafShift) + 1, o, d, tmin, tmax, best, best_pos, bt, bu, bv)) break;   // (true only when ANY)
             }
-            if (pop) {
-                if (sp == 0) break;
-                --sp;
-                const int e = (int)s_stack[sp * stride];
-                cur = (e & 0x8000) ? -1 - (e & 0x7FFF) : e;
-            }
+            if (pop && !pop_entry(s_stack, stride, sp, 0, cur)) break;
         }
     }
     tri_out = best;
@@ -355,8 +379,7 @@ __device__ __forceinline__ bool trace_lds(const Params& p, const uint4* __restri
                                           unsigned short* __restrict__ s_stack, int stride, v3 o, v3 d, float tmin, float tmax, int& tri_out, int& pos_out,
                                           float& t_out, float& u_out, float& v_out)
 {
-    auto safe_inv = [](float x) { return fabsf(x) < 1e-30f ? copysignf(1e30f, x) : 1.0f / x; };
-    const v3 id = mk(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+    const v3 id = safe_inv(d);
     const v3 sid = mk(p.grid_step.x * id.x, p.grid_step.y * id.y, p.grid_step.z * id.z);
     const v3 snoid = mk((p.grid_lo.x - o.x) * id.x, (p.grid_lo.y - o.y) * id.y, (p.grid_lo.z - o.z) * id.z);
     int best = -1, best_pos = 0;
@@ -407,14 +430,209 @@ __device__ __forceinline__ bool trace_lds(const Params& p, const uint4* __restri
     return best >= 0;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
+// ---- the pixel pipeline every render kernel runs: whitted.cu's programs around the kernel's own walk and hit geometry -------------
+
+// __raygen__pinhole, whitted.cu:183-240: the primary ray's direction through pixel (x, y) of the full image (its origin is the eye)
+__device__ __forceinline__ v3 raygen(const Frame& f, unsigned int x, unsigned int y)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char w_smem[];
+    unsigned int seed = tea4(y * f.width + x, f.subframe);
+    float jx = 0.0f, jy = 0.0f;
+    if (f.subframe != 0) {
+        jx = rnd(seed) - 0.5f;   // x first (source order)
+        jy = rnd(seed) - 0.5f;
+    }
+    const float dx = 2.0f * div_cr((float)x + jx, (float)f.width) - 1.0f;
+    const float dy = 2.0f * div_cr((float)y + jy, (float)f.height) - 1.0f;
+    return vnormalize(vadd(vadd(vscale(f.U, dx), vscale(f.V, dy)), f.W));
+}
+
+struct Rays {   // a lane's share of the counters
+    unsigned int total = 0, occlusion = 0;
+};
+
+// What a kernel's hit step hands to shading: getLocalGeometry (LocalGeometry.h:55-141) up to the shading normal, which is N here
+// before the normal map
+struct HitGeom {
+    v3 P, N;                // world space
+    v3 P0, P1, P2;          // the corners in the space dp/du, dp/dv are taken in (world for one mesh, object for an instance: :118-134)
+    float w0, bu, bv;       // barycentrics
+    unsigned int i0, i1, i2;    // vertex indices (into texcoords)
+    const float* texcoords; // 2 floats per vertex, or null (then UV = the barycentrics, :97-102)
+    unsigned int material;
+};
+
+// __closesthit__radiance, whitted.cu:255-337, from the hit geometry on: material, textures, and the GGX light loop with one occlusion
+// ray per light that faces the surface (occluded(o, d, tmin, tmax): the kernel's any-hit walk).  rd: the WORLD ray direction (:307).
+template <typename Occluded>
+__device__ __forceinline__ v3 shade(const Frame& f, const HitGeom& h, v3 rd, Occluded&& occluded, Rays& rays)
+{
+    v3 N = h.N;
+    const Pbr m = f.materials[h.material];
+    v3 base = mk(m.base_color[0], m.base_color[1], m.base_color[2]);
+    float mr_y = 1.0f, mr_z = 1.0f;   // the (1,1,1,1) of an absent metallic-roughness texture, whitted.cu:271
+    if (f.mat_tex) {
+        const MatTex mt = f.mat_tex[h.material];
+        if (mt.base_color.px || mt.metallic_roughness.px || mt.normal.px) {
+            // getLocalGeometry's UV and dp/du, dp/dv (LocalGeometry.h:88-135); the texcoords are read here only, so that nothing of
+            // them stays live across the light loop
+            const float w0 = h.w0, bu = h.bu, bv = h.bv;
+            float2 UV0 = make_float2(0.0f, 0.0f), UV1 = make_float2(0.0f, 1.0f), UV2 = make_float2(1.0f, 0.0f), UV = make_float2(bu, bv);
+            if (h.texcoords) {
+                const float* tc = h.texcoords;
+                UV0 = make_float2(tc[2 * h.i0], tc[2 * h.i0 + 1]);
+                UV1 = make_float2(tc[2 * h.i1], tc[2 * h.i1 + 1]);
+                UV2 = make_float2(tc[2 * h.i2], tc[2 * h.i2 + 1]);
+                UV = make_float2(w0 * UV0.x + bu * UV1.x + bv * UV2.x, w0 * UV0.y + bu * UV1.y + bv * UV2.y);
+            }
+            if (mt.base_color.px) {
+                // base_color *= linearize( tex2D ), whitted.cu:78-85, 264-267
+                const float4 tc = tex2d(mt.base_color, UV.x, UV.y);
+                base = vmul(base, mk(powf(tc.x, 2.2f), powf(tc.y, 2.2f), powf(tc.z, 2.2f)));
+            }
+            if (mt.metallic_roughness.px) {
+                const float4 tc = tex2d(mt.metallic_roughness, UV.x, UV.y);   // (occlusion, roughness, metallic), :272-276
+                mr_y = tc.y;
+                mr_z = tc.z;
+            }
+            if (mt.normal.px) {
+                // whitted.cu:288-292 over LocalGeometry.h:118-134
+                const float du1 = UV0.x - UV2.x, du2 = UV1.x - UV2.x, dv1 = UV0.y - UV2.y, dv2 = UV1.y - UV2.y;
+                const v3 dp1 = vsub(h.P0, h.P2), dp2 = vsub(h.P1, h.P2);
+                const float det = du1 * dv2 - dv1 * du2;
+                const float invdet = 1.0f / det;
+                const v3 dpdu = vscale(vsub(vscale(dp1, dv2), vscale(dp2, dv1)), invdet);
+                const v3 dpdv = vscale(vadd(vscale(dp1, -du2), vscale(dp2, du1)), invdet);
+                const float4 tc = tex2d(mt.normal, UV.x, UV.y);
+                const float nx = 2.0f * tc.x - 1.0f, ny = 2.0f * tc.y - 1.0f, nz = 2.0f * tc.z - 1.0f;
+                N = vnormalize(vadd(vadd(vscale(vnormalize(dpdu), nx), vscale(vnormalize(dpdv), ny)), vscale(N, nz)));
+            }
+        }
+    }
+    const float metallic = m.metallic * mr_z, roughness = m.roughness * mr_y;   // :269-276
+    const float F0 = 0.04f;
+    const v3 diff_color = vscale(vscale(base, 1.0f - F0), 1.0f - metallic);
+    // lerp(a, b, t) = a + t * (b - a), vec_math.h:496-499
+    const v3 spec_color = vadd(mk(F0, F0, F0), vscale(vsub(base, mk(F0, F0, F0)), metallic));
+    const float alpha = roughness * roughness;
+    v3 result = mk(0.0f, 0.0f, 0.0f);
+    for (int l = 0; l < f.n_lights; ++l) {
+        const PointLight L = f.lights[l];
+        const v3 toL = vsub(mk(L.position[0], L.position[1], L.position[2]), h.P);
+        const float Ldist = vlength(toL);
+        const v3 Lv = vscale(toL, 1.0f / Ldist);   // float3 / float multiplies by the reciprocal (vec_math.h:479-483)
+        const v3 Vv = vneg(vnormalize(rd));
+        const v3 H = vnormalize(vadd(Lv, Vv));
+        const float NdotL = vdot(N, Lv), NdotV = vdot(N, Vv), NdotH = vdot(N, H), VdotH = vdot(Vv, H);
+        if (NdotL > 0.0f && NdotV > 0.0f) {
+            rays.total += 1;
+            rays.occlusion += 1;
+            if (!occluded(h.P, Lv, 0.001f, Ldist - 0.001f)) {
+                const v3 F = schlick(spec_color, VdotH);
+                const float G = vis(NdotL, NdotV, alpha);
+                const float D = ggx_normal(NdotH, alpha);
+                const v3 one_minus_F = vsub(mk(1.0f, 1.0f, 1.0f), F);
+                const v3 dd = vmul(one_minus_F, diff_color);
+                const float ip = 1.0f / kPi;
+                const v3 diff = vscale(dd, ip);   // float3 / float
+                const v3 spec = vscale(vscale(F, G), D);
+                const v3 lc = vscale(mk(L.color[0], L.color[1], L.color[2]), L.intensity);
+                result = vadd(result, vmul(vscale(lc, NdotL), vadd(diff, spec)));
+            }
+        }
+    }
+    return result;
+}
+
+// whitted.cu:226-239: the running mean over subframes, and make_color (:164-173, gamma 2.2) of it
+__device__ __forceinline__ void accumulate(const Frame& f, unsigned int idx, v3 result)
+{
+    v3 acc = result;
+    if (f.subframe > 0) {
+        const float a = 1.0f / (float)(f.subframe + 1);
+        const float4 prev = f.accum[idx];
+        acc = vadd(mk(prev.x, prev.y, prev.z), vscale(vsub(acc, mk(prev.x, prev.y, prev.z)), a));
+    }
+    f.accum[idx] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+    const float g = (float)(1.0 / 2.2f);
+    f.image[idx] = make_uchar4((unsigned char)(powf(clampf(acc.x, 0.0f, 1.0f), g) * 255.0f), (unsigned char)(powf(clampf(acc.y, 0.0f, 1.0f), g) * 255.0f),
+                               (unsigned char)(powf(clampf(acc.z, 0.0f, 1.0f), g) * 255.0f), 255u);
+}
+
+// The body of every render kernel: preload() (the kernel's LDS image of its structure, ending in a barrier), then the wave's tiles
+// from the queue, pixel(x, y, rays) -> radiance for each pixel of the launch's share (x, y: in the full image), accumulated, and the
+// wave's ray counts added to the counters.
+//
+// Tile queue: kTileHeads counters 64 bytes apart, head h serves the tiles h, h + kTileHeads, ...  (one counter hands out ~88 entries per
+// microsecond chip-wide: a 1080p subframe is 32 k tiles).  A wave starts on head blockIdx % kTileHeads; when that is dry it looks at all
+// heads with one load and moves to an open one.  The pull for the next tile is in flight while the current one is rendered.
+template <typename Preload, typename Pixel>
+__device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, Pixel&& pixel)
+{
 #ifdef RTGO_WHITTED_TIMING
     const unsigned long long wt0 = wall_clock64();
     unsigned long long wt_tiles = 0, wt_n = 0, wt_max = 0;
 #endif
+    preload();
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned int)kTileHeads) f.tile_counter_next[kTileHeadStride * threadIdx.x] = 0u;
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int n_tiles = f.tiles_x * f.tiles_y;
+    Rays rays;
+    auto tiles_of = [&](unsigned int h) { return (n_tiles + (unsigned int)kTileHeads - 1u - h) / (unsigned int)kTileHeads; };
+    unsigned int head = blockIdx.x % (unsigned int)kTileHeads;
+    unsigned int pending = 0u;
+    if (lane == 0u) pending = atomicAdd(f.tile_counter + kTileHeadStride * head, 1u);
+    for (;;) {
+        unsigned int pos = (unsigned int)__builtin_amdgcn_readfirstlane((int)pending);
+        if (pos >= tiles_of(head)) {
+            // this head is dry: any other one still open?
+            unsigned int v = 0xFFFFFFFFu;
+            if (lane < (unsigned int)kTileHeads) v = __hip_atomic_load(f.tile_counter + kTileHeadStride * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long open = __builtin_amdgcn_ballot_w64(lane < (unsigned int)kTileHeads && v < tiles_of(lane));
+            if (open == 0ull) break;
+            // the first open head after this one (waves spread over the open heads instead of all falling on the lowest)
+            const unsigned long long above = open & ~((2ull << head) - 1ull);
+            head = (unsigned int)(__ffsll((long long)(above ? above : open)) - 1);
+            if (lane == 0u) pending = atomicAdd(f.tile_counter + kTileHeadStride * head, 1u);
+            continue;
+        }
+        // queue entry -> tile through a fixed permutation (multiplication by a number coprime to the tile count, near the golden
+        // section of it): in row-major order every wave of the chip reaches the dense part of the mesh at the same time and they all
+        // queue at the vector memory pipeline for its triangles; scattered, tiles that wait for triangles overlap tiles that do not
+        const unsigned int tile = (unsigned int)(((unsigned long long)(pos * (unsigned int)kTileHeads + head) * f.tile_stride) % n_tiles);
+        if (lane == 0u) pending = atomicAdd(f.tile_counter + kTileHeadStride * head, 1u);
+#ifdef RTGO_WHITTED_TIMING
+        const unsigned long long wt2 = wall_clock64();
+        wt_n += 1;
+#endif
+        const unsigned int ty = tile / f.tiles_x, tx = tile - ty * f.tiles_x;
+        const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // in the compact local image
+        if (lx < f.share.lw && ly < f.share.lh) accumulate(f, ly * f.share.lw + lx, pixel(f.share.x0 + lx, share_row(f.share, ly), rays));
+#ifdef RTGO_WHITTED_TIMING
+        const unsigned long long wt3 = wall_clock64() + (rays.total == 0xFFFFFFFFu ? 1 : 0) - wt2;
+        wt_tiles += wt3;
+        if (lx < f.share.lw && ly < f.share.lh) f.accum[ly * f.share.lw + lx].w = (float)wt3;   // (diagnostic: ticks of the tile)
+        wt_max = wt3 > wt_max ? wt3 : wt_max;
+#endif
+    }
+    const unsigned int total = wave_sum(rays.total), occlusion = wave_sum(rays.occlusion);
+    if (lane == 0u) {
+        atomicAdd(&f.counters[0], (unsigned long long)total);
+        atomicAdd(&f.counters[1], (unsigned long long)occlusion);
+#ifdef RTGO_WHITTED_TIMING
+        // diagnostic build (tools/whitted_perf.py prints them): 10 ns ticks summed over the waves
+        atomicAdd(&f.counters[2], wall_clock64() - wt0);   // wave lifetime          -> rtgo_stats.node_visits
+        atomicAdd(&f.counters[4], wt_tiles);               // inside tiles           -> hits
+        atomicAdd(&f.counters[5], wt_n);                   // tiles                  -> dbg_fast_boxes
+        atomicMax(&f.counters[6], wt_max);                 // the longest tile       -> dbg_fast_tests
+#endif
+    }
+}
+
+// One mesh in world space.  MODE: where the walk reads its structure from (kAllInL2 / kRecordsInLds / kAllInLds)
+template <int MODE>
+__global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char w_smem[];
     // LDS image.  kRecordsInLds: [fp32 records, 64 B each][stacks];  kAllInLds: [quantised records, 32 B][vertices, 16 B][triangle
     // indices, 8 B][stacks];  kAllInL2: [stacks]
     float4* s_recs = reinterpret_cast<float4*>(w_smem);
@@ -424,227 +642,74 @@ __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
     const int stride = (int)blockDim.x;
     unsigned short* s_stack = (MODE == kAllInLds ? reinterpret_cast<unsigned short*>(s_tidx + p.n_triangles)
                                                  : reinterpret_cast<unsigned short*>(s_recs + (MODE == kRecordsInLds ? 4 * p.n_recs : 0))) + threadIdx.x;   // entry e at [e * stride]
-    if (MODE == kRecordsInLds) {
-        for (int i = (int)threadIdx.x; i < 4 * p.n_recs; i += stride) s_recs[i] = p.recs[i];
-        __syncthreads();
-    }
-    if (MODE == kAllInLds) {
-        for (int i = (int)threadIdx.x; i < 2 * p.n_recs; i += stride) s_q[i] = p.qrecs[i];
-        for (int i = (int)threadIdx.x; i < p.n_vertices; i += stride) s_verts[i] = make_float4(p.positions[3 * i + 0], p.positions[3 * i + 1], p.positions[3 * i + 2], 0.0f);
-        for (int i = (int)threadIdx.x; i < p.n_triangles; i += stride) s_tidx[i] = p.tidx[i];
-        __syncthreads();
-    }
-#ifdef RTGO_WHITTED_TIMING
-    const unsigned long long wt1 = wall_clock64();
-#endif
-    if (blockIdx.x == 0 && threadIdx.x < (unsigned int)kTileHeads) p.tile_counter_next[kTileHeadStride * threadIdx.x] = 0u;
-    auto pick = [&]() {
-        if constexpr (MODE == kRecordsInLds) return static_cast<const float4*>(s_recs);
-        else return p.recs;
+    auto preload = [&]() {
+        if (MODE == kRecordsInLds) {
+            for (int i = (int)threadIdx.x; i < 4 * p.n_recs; i += stride) s_recs[i] = p.recs[i];
+            __syncthreads();
+        }
+        if (MODE == kAllInLds) {
+            for (int i = (int)threadIdx.x; i < 2 * p.n_recs; i += stride) s_q[i] = p.qrecs[i];
+            for (int i = (int)threadIdx.x; i < p.n_vertices; i += stride) s_verts[i] = make_float4(p.positions[3 * i + 0], p.positions[3 * i + 1], p.positions[3 * i + 2], 0.0f);
+            for (int i = (int)threadIdx.x; i < p.n_triangles; i += stride) s_tidx[i] = p.tidx[i];
+            __syncthreads();
+        }
     };
-    const auto recs = pick();
-    // closest hit / any hit through whichever form of the structure this instantiation walks
-    auto closest = [&](v3 o, v3 d, float t0, float t1, int& tri, int& pos, float& t, float& u, float& v) -> bool {
-        if constexpr (MODE == kAllInLds) return trace_lds<false>(p, s_q, s_verts, s_tidx, s_stack, stride, o, d, t0, t1, tri, pos, t, u, v);
-        else return trace<false>(p, recs, s_stack, stride, o, d, t0, t1, tri, pos, t, u, v);
-    };
+    const float4* recs = MODE == kRecordsInLds ? static_cast<const float4*>(s_recs) : p.recs;
     auto occluded = [&](v3 o, v3 d, float t0, float t1) -> bool {
         int tri, pos;
         float t, u, v;
         if constexpr (MODE == kAllInLds) return trace_lds<true>(p, s_q, s_verts, s_tidx, s_stack, stride, o, d, t0, t1, tri, pos, t, u, v);
         else return trace<true>(p, recs, s_stack, stride, o, d, t0, t1, tri, pos, t, u, v);
     };
-    const unsigned int lane = threadIdx.x & 63u;
-    const unsigned int n_tiles = p.tiles_x * p.tiles_y;
-    unsigned int rays = 0, occl = 0;
-    // Tile queue: kTileHeads counters 64 bytes apart, head h serves the tiles h, h + kTileHeads, ...  (one counter hands out ~88
-    // entries per microsecond chip-wide: a 1080p subframe is 32 k tiles).  A wave starts on head blockIdx % kTileHeads; when that is
-    // dry it looks at all heads with one load and moves to an open one.  The pull for the next tile is in flight while the
-    // current one is rendered.
-    auto tiles_of = [&](unsigned int h) { return (n_tiles + (unsigned int)kTileHeads - 1u - h) / (unsigned int)kTileHeads; };
-    unsigned int head = blockIdx.x % (unsigned int)kTileHeads;
-    unsigned int pending = 0u;
-    if (lane == 0u) pending = atomicAdd(p.tile_counter + kTileHeadStride * head, 1u);
-    for (;;) {
-        unsigned int pos = (unsigned int)__builtin_amdgcn_readfirstlane((int)pending);
-        if (pos >= tiles_of(head)) {
-            // this head is dry: any other one still open?
-            unsigned int v = 0xFFFFFFFFu;
-            if (lane < (unsigned int)kTileHeads) v = __hip_atomic_load(p.tile_counter + kTileHeadStride * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long open = __builtin_amdgcn_ballot_w64(lane < (unsigned int)kTileHeads && v < tiles_of(lane));
-            if (open == 0ull) break;
-            // the first open head after this one (waves spread over the open heads instead of all falling on the lowest)
-            const unsigned long long above = open & ~((2ull << head) - 1ull);
-            head = (unsigned int)(__ffsll((long long)(above ? above : open)) - 1);
-            if (lane == 0u) pending = atomicAdd(p.tile_counter + kTileHeadStride * head, 1u);
-            continue;
+    render_tiles(p.frame, preload, [&](unsigned int x, unsigned int y, Rays& rays) -> v3 {
+        const v3 rd = raygen(p.frame, x, y);
+        const v3 miss = p.frame.miss;   // __miss__constant_radiance, :243-246 (read ahead of the walk: after it, kAllInLds spills)
+        int tri, tpos;
+        float t, bu, bv;
+        rays.total += 1;
+        bool hit;
+        if constexpr (MODE == kAllInLds) hit = trace_lds<false>(p, s_q, s_verts, s_tidx, s_stack, stride, p.frame.eye, rd, 0.01f, 1e16f, tri, tpos, t, bu, bv);
+        else hit = trace<false>(p, recs, s_stack, stride, p.frame.eye, rd, 0.01f, 1e16f, tri, tpos, t, bu, bv);
+        if (!hit) return miss;
+        // the hit geometry of a mesh in world space.  (The corners come from the Morton-ordered copy the walk read them from: same
+        // values, no trip through the index array.)
+        float4 c0, c1, c2;
+        HitGeom h;
+        h.i0 = h.i1 = h.i2 = 0;
+        if constexpr (MODE == kAllInLds) {
+            const uint2 ti = s_tidx[tpos];
+            h.i0 = ti.x & 0xFFFFu;
+            h.i1 = ti.x >> 16;
+            h.i2 = ti.y & 0xFFFFu;
+            c0 = s_verts[h.i0];
+            c1 = s_verts[h.i1];
+            c2 = s_verts[h.i2];
+        } else {
+            c0 = p.tris[3 * tpos + 0];
+            c1 = p.tris[3 * tpos + 1];
+            c2 = p.tris[3 * tpos + 2];
+            if (p.normals || p.texcoords) {
+                h.i0 = p.indices[3 * tri + 0];
+                h.i1 = p.indices[3 * tri + 1];
+                h.i2 = p.indices[3 * tri + 2];
+            }
         }
-        // queue entry -> tile through a fixed permutation (multiplication by a number coprime to the tile count, near the golden
-        // section of it): in row-major order every wave of the chip reaches the dense part of the mesh at the same time and they all
-        // queue at the vector memory pipeline for its triangles; scattered, tiles that wait for triangles overlap tiles that do not
-        const unsigned int tile = (unsigned int)(((unsigned long long)(pos * (unsigned int)kTileHeads + head) * p.tile_stride) % n_tiles);
-        if (lane == 0u) pending = atomicAdd(p.tile_counter + kTileHeadStride * head, 1u);
-#ifdef RTGO_WHITTED_TIMING
-        const unsigned long long wt2 = wall_clock64();
-        wt_n += 1;
-#endif
-        const unsigned int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
-        const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // in the compact local image
-        if (lx < p.share.lw && ly < p.share.lh) {
-            const unsigned int idx = ly * p.share.lw + lx;
-            const unsigned int x = p.share.x0 + lx, y = share_row(p.share, ly);   // in the full image
-            // __raygen__pinhole, whitted.cu:183-240
-            unsigned int seed = tea4(y * p.width + x, p.subframe);
-            float jx = 0.0f, jy = 0.0f;
-            if (p.subframe != 0) {
-                jx = rnd(seed) - 0.5f;   // x first (source order)
-                jy = rnd(seed) - 0.5f;
-            }
-            const float dx = 2.0f * div_cr((float)x + jx, (float)p.width) - 1.0f;
-            const float dy = 2.0f * div_cr((float)y + jy, (float)p.height) - 1.0f;
-            const v3 rd = vnormalize(vadd(vadd(vscale(p.U, dx), vscale(p.V, dy)), p.W));
-            const v3 ro = p.eye;
-            v3 result = p.miss;   // __miss__constant_radiance, :243-246
-            int tri, tpos;
-            float t, bu, bv;
-            rays += 1;
-            if (closest(ro, rd, 0.01f, 1e16f, tri, tpos, t, bu, bv)) {
-                // __closesthit__radiance, :255-337, with getLocalGeometry (LocalGeometry.h:55-141) for a mesh in world space.
-                // (the corners come from the Morton-ordered copy the walk read them from: same values, no trip through the index array)
-                float4 c0, c1, c2;
-                unsigned int i0 = 0, i1 = 0, i2 = 0;   // vertex indices (for the normals)
-                if constexpr (MODE == kAllInLds) {
-                    const uint2 ti = s_tidx[tpos];
-                    i0 = ti.x & 0xFFFFu;
-                    i1 = ti.x >> 16;
-                    i2 = ti.y & 0xFFFFu;
-                    c0 = s_verts[i0];
-                    c1 = s_verts[i1];
-                    c2 = s_verts[i2];
-                } else {
-                    c0 = p.tris[3 * tpos + 0];
-                    c1 = p.tris[3 * tpos + 1];
-                    c2 = p.tris[3 * tpos + 2];
-                    if (p.normals || p.texcoords) {
-                        i0 = p.indices[3 * tri + 0];
-                        i1 = p.indices[3 * tri + 1];
-                        i2 = p.indices[3 * tri + 2];
-                    }
-                }
-                const v3 P0 = mk(c0.x, c0.y, c0.z), P1 = mk(c1.x, c1.y, c1.z), P2 = mk(c2.x, c2.y, c2.z);
-                const float w0 = 1.0f - bu - bv;
-                const v3 P = vadd(vadd(vscale(P0, w0), vscale(P1, bu)), vscale(P2, bv));
-                const v3 Ng = vnormalize(vcross(vsub(P1, P0), vsub(P2, P0)));
-                v3 N = Ng;
-                if (p.normals) {
-                    const v3 N0 = ld3(p.normals, i0), N1 = ld3(p.normals, i1), N2 = ld3(p.normals, i2);
-                    N = vnormalize(vadd(vadd(vscale(N0, w0), vscale(N1, bu)), vscale(N2, bv)));
-                }
-                const unsigned int mi = p.tri_material ? p.tri_material[tri] : 0u;
-                const Pbr m = p.materials[mi];
-                v3 base = mk(m.base_color[0], m.base_color[1], m.base_color[2]);
-                float mr_y = 1.0f, mr_z = 1.0f;   // the (1,1,1,1) of an absent metallic-roughness texture, whitted.cu:271
-                if (p.mat_tex) {
-                    const MatTex mt = p.mat_tex[mi];
-                    if (mt.base_color.px || mt.metallic_roughness.px || mt.normal.px) {
-                        // getLocalGeometry's UV and dp/du, dp/dv (LocalGeometry.h:88-135)
-                        float2 UV0 = make_float2(0.0f, 0.0f), UV1 = make_float2(0.0f, 1.0f), UV2 = make_float2(1.0f, 0.0f), UV = make_float2(bu, bv);
-                        if (p.texcoords) {
-                            UV0 = make_float2(p.texcoords[2 * i0], p.texcoords[2 * i0 + 1]);
-                            UV1 = make_float2(p.texcoords[2 * i1], p.texcoords[2 * i1 + 1]);
-                            UV2 = make_float2(p.texcoords[2 * i2], p.texcoords[2 * i2 + 1]);
-                            UV = make_float2(w0 * UV0.x + bu * UV1.x + bv * UV2.x, w0 * UV0.y + bu * UV1.y + bv * UV2.y);
-                        }
-                        if (mt.base_color.px) {
-                            // base_color *= linearize( tex2D ), whitted.cu:78-85, 264-267
-                            const float4 tc = tex2d(mt.base_color, UV.x, UV.y);
-                            base = vmul(base, mk(powf(tc.x, 2.2f), powf(tc.y, 2.2f), powf(tc.z, 2.2f)));
-                        }
-                        if (mt.metallic_roughness.px) {
-                            const float4 tc = tex2d(mt.metallic_roughness, UV.x, UV.y);   // (occlusion, roughness, metallic), :272-276
-                            mr_y = tc.y;
-                            mr_z = tc.z;
-                        }
-                        if (mt.normal.px) {
-                            // whitted.cu:288-292 over LocalGeometry.h:118-134
-                            const float du1 = UV0.x - UV2.x, du2 = UV1.x - UV2.x, dv1 = UV0.y - UV2.y, dv2 = UV1.y - UV2.y;
-                            const v3 dp1 = vsub(P0, P2), dp2 = vsub(P1, P2);
-                            const float det = du1 * dv2 - dv1 * du2;
-                            const float invdet = 1.0f / det;
-                            const v3 dpdu = vscale(vsub(vscale(dp1, dv2), vscale(dp2, dv1)), invdet);
-                            const v3 dpdv = vscale(vadd(vscale(dp1, -du2), vscale(dp2, du1)), invdet);
-                            const float4 tc = tex2d(mt.normal, UV.x, UV.y);
-                            const float nx = 2.0f * tc.x - 1.0f, ny = 2.0f * tc.y - 1.0f, nz = 2.0f * tc.z - 1.0f;
-                            N = vnormalize(vadd(vadd(vscale(vnormalize(dpdu), nx), vscale(vnormalize(dpdv), ny)), vscale(N, nz)));
-                        }
-                    }
-                }
-                const float metallic = m.metallic * mr_z, roughness = m.roughness * mr_y;   // :269-276
-                const float F0 = 0.04f;
-                const v3 diff_color = vscale(vscale(base, 1.0f - F0), 1.0f - metallic);
-                // lerp(a, b, t) = a + t * (b - a), vec_math.h:496-499
-                const v3 spec_color = vadd(mk(F0, F0, F0), vscale(vsub(base, mk(F0, F0, F0)), metallic));
-                const float alpha = roughness * roughness;
-                result = mk(0.0f, 0.0f, 0.0f);
-                for (int l = 0; l < p.n_lights; ++l) {
-                    const PointLight L = p.lights[l];
-                    const v3 toL = vsub(mk(L.position[0], L.position[1], L.position[2]), P);
-                    const float Ldist = vlength(toL);
-                    const v3 Lv = vscale(toL, 1.0f / Ldist);   // float3 / float multiplies by the reciprocal (vec_math.h:479-483)
-                    const v3 Vv = vneg(vnormalize(rd));
-                    const v3 H = vnormalize(vadd(Lv, Vv));
-                    const float NdotL = vdot(N, Lv), NdotV = vdot(N, Vv), NdotH = vdot(N, H), VdotH = vdot(Vv, H);
-                    if (NdotL > 0.0f && NdotV > 0.0f) {
-                        rays += 1;
-                        occl += 1;
-                        if (!occluded(P, Lv, 0.001f, Ldist - 0.001f)) {
-                            const v3 F = schlick(spec_color, VdotH);
-                            const float G = vis(NdotL, NdotV, alpha);
-                            const float D = ggx_normal(NdotH, alpha);
-                            const v3 one_minus_F = vsub(mk(1.0f, 1.0f, 1.0f), F);
-                            const v3 dd = vmul(one_minus_F, diff_color);
-                            const float ip = 1.0f / kPi;
-                            const v3 diff = vscale(dd, ip);   // float3 / float
-                            const v3 spec = vscale(vscale(F, G), D);
-                            const v3 lc = vscale(mk(L.color[0], L.color[1], L.color[2]), L.intensity);
-                            result = vadd(result, vmul(vscale(lc, NdotL), vadd(diff, spec)));
-                        }
-                    }
-                }
-            }
-            // whitted.cu:226-239
-            v3 acc = result;
-            if (p.subframe > 0) {
-                const float a = 1.0f / (float)(p.subframe + 1);
-                const float4 prev = p.accum[idx];
-                acc = vadd(mk(prev.x, prev.y, prev.z), vscale(vsub(acc, mk(prev.x, prev.y, prev.z)), a));
-            }
-            p.accum[idx] = make_float4(acc.x, acc.y, acc.z, 1.0f);
-            // make_color, whitted.cu:164-173: gamma 2.2
-            const float g = (float)(1.0 / 2.2f);
-            p.image[idx] = make_uchar4((unsigned char)(powf(clampf(acc.x, 0.0f, 1.0f), g) * 255.0f), (unsigned char)(powf(clampf(acc.y, 0.0f, 1.0f), g) * 255.0f),
-                                       (unsigned char)(powf(clampf(acc.z, 0.0f, 1.0f), g) * 255.0f), 255u);
+        h.P0 = mk(c0.x, c0.y, c0.z);
+        h.P1 = mk(c1.x, c1.y, c1.z);
+        h.P2 = mk(c2.x, c2.y, c2.z);
+        h.w0 = 1.0f - bu - bv;
+        h.bu = bu;
+        h.bv = bv;
+        h.P = vadd(vadd(vscale(h.P0, h.w0), vscale(h.P1, bu)), vscale(h.P2, bv));
+        h.N = vnormalize(vcross(vsub(h.P1, h.P0), vsub(h.P2, h.P0)));   // Ng
+        if (p.normals) {
+            const v3 N0 = ld3(p.normals, h.i0), N1 = ld3(p.normals, h.i1), N2 = ld3(p.normals, h.i2);
+            h.N = vnormalize(vadd(vadd(vscale(N0, h.w0), vscale(N1, bu)), vscale(N2, bv)));
         }
-#ifdef RTGO_WHITTED_TIMING
-        const unsigned long long wt3 = wall_clock64() + (rays == 0xFFFFFFFFu ? 1 : 0) - wt2;
-        wt_tiles += wt3;
-        if (lx < p.share.lw && ly < p.share.lh) p.accum[ly * p.share.lw + lx].w = (float)wt3;   // (diagnostic: ticks of the tile)
-        wt_max = wt3 > wt_max ? wt3 : wt_max;
-#endif
-    }
-    rays = wave_sum(rays);
-    occl = wave_sum(occl);
-    if (lane == 0u) {
-        atomicAdd(&p.counters[0], (unsigned long long)rays);
-        atomicAdd(&p.counters[1], (unsigned long long)occl);
-#ifdef RTGO_WHITTED_TIMING
-        // diagnostic build (tools/whitted_perf.py prints them): 10 ns ticks summed over the waves
-        atomicAdd(&p.counters[2], wall_clock64() - wt0);   // wave lifetime          -> rtgo_stats.node_visits
-        atomicAdd(&p.counters[4], wt_tiles);               // inside tiles           -> hits
-        atomicAdd(&p.counters[5], wt_n);                   // tiles                  -> dbg_fast_boxes
-        atomicMax(&p.counters[6], wt_max);                 // the longest tile       -> dbg_fast_tests
-#endif
-    }
+        h.texcoords = p.texcoords;
+        h.material = p.tri_material ? p.tri_material[tri] : 0u;
+        return shade(p.frame, h, rd, occluded, rays);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
