@@ -127,6 +127,15 @@ struct rtgo_ctx {
     // queue + counters
     unsigned int* d_queue = nullptr;          // two sets of work-queue heads: a launch counts on one and zeroes the other for the next
     int queue_set = 0;
+    // next frame's pixel seeds (LaunchParams::seeds): two buffers, a launch reads one and writes the other.  seeds_ok: the buffer
+    // seeds_read holds frame seeds_frame's seeds for the strip layout seeds_key (written by the last launch on this context)
+    unsigned int* d_seeds[2] = {nullptr, nullptr};
+    size_t seeds_capacity = 0;                // words of each
+    int seeds_read = 0;
+    bool seeds_ok = false;
+    uint32_t seeds_frame = 0;
+    std::vector<uint32_t> seeds_key;
+    uint32_t seeds_last = 0;                  // rtgo_debug_seeds: 1 = the last launch read pre-hashed seeds, 2 = it wrote the next frame's
     unsigned long long rays_culled = 0;       // since rtgo_reset_stats (host arithmetic: the cold pixels of each launch x N*N)
     uint32_t launches_canonical = 0;          // since rtgo_reset_stats
     uint32_t launches_trial = 0, last_variant = 0;   // (rtgo_stats)
@@ -384,6 +393,15 @@ static Rect box_screen_rect(const float* bounds, const LaunchParams& p)
 
 extern "C" {
 
+// diagnostic (tests, tools; not part of include/rtgo.h): whether the last rtgo_launch read pre-hashed pixel seeds (bit 0) and
+// whether it wrote the next frame's (bit 1)
+extern "C" int rtgo_debug_seeds(rtgo_ctx* c, uint32_t* out)
+{
+    if (!c || !out) return fail(c, RTGO_E_INVALID, "rtgo_debug_seeds: NULL argument");
+    *out = c->seeds_last;
+    return RTGO_OK;
+}
+
 // diagnostic (tests, tools; not part of include/rtgo.h): what rtgo_set_scene's grid build came to -- {has one, nx, ny, nz, list entries, bytes}
 extern "C" int rtgo_debug_grid(rtgo_ctx* c, int32_t out[6])
 {
@@ -501,6 +519,15 @@ int rtgo_create(int device, rtgo_ctx** out)
     return RTGO_OK;
 }
 
+// the pre-hashed pixel seeds (rtgo_set_scene, rtgo_resize, rtgo_destroy)
+static void free_seeds(rtgo_ctx* c)
+{
+    release(c->d_seeds[0]);
+    release(c->d_seeds[1]);
+    c->seeds_capacity = 0;
+    c->seeds_ok = false;
+}
+
 // the scene's device buffers: both fast-walk structures, the grid, the canonical LBVH, boxes and frames (rtgo_set_scene, rtgo_destroy)
 static void free_scene(rtgo_ctx* c)
 {
@@ -519,6 +546,7 @@ static void free_scene(rtgo_ctx* c)
     release(c->d_frames);
     release(c->d_tight);
     c->n_prims = 0;
+    free_seeds(c);
 }
 
 // the output buffers, when the context owns them (rtgo_resize, rtgo_bind_output, rtgo_destroy)
@@ -930,6 +958,7 @@ int rtgo_resize(rtgo_ctx* c, size_t pixels)
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     free_output(c);
+    free_seeds(c);
     RTGO_HIP(c, hipMalloc(&c->d_accum, pixels * sizeof(float4)));
     RTGO_HIP(c, hipMalloc(&c->d_image, pixels * sizeof(uchar4)));
     RTGO_HIP(c, hipMemsetAsync(c->d_accum, 0, pixels * sizeof(float4), c->stream));
@@ -1294,6 +1323,32 @@ static int update_hot_mask(rtgo_ctx* c, uint32_t strip_px, LaunchParams& p, unsi
     return RTGO_OK;
 }
 
+// Pixel seeds of a progressive job (LaunchParams::seeds): a launch of the kernel variant that has the seed pass (the 6-waves lock-step
+// one, kernel_has_seed_pass: launches of >= kUnitsPerWave4For6 units per wave) writes frame + 1's seeds of its hot strips into one
+// buffer; the next launch reads them when it runs that variant for exactly that frame over exactly that strip layout, and otherwise
+// (the first frame, a skipped or repeated frame index, a new window, band share or rectangle, any other variant) hashes them inline.
+// Seeds depend on the image width, the pixel and the frame alone, not on camera or scene: the layout is all the key needs.
+// Stream order makes the writes of launch f visible to launch f + 1.  `key`: what rtgo_launch records once the launch is on the stream.
+static int plan_seeds(rtgo_ctx* c, LaunchParams& p, uint32_t strip_px, bool has_pass, std::vector<uint32_t>& key)
+{
+    p.seeds = nullptr;
+    p.seeds_next = nullptr;
+    key.clear();
+    const uint64_t words = (uint64_t)p.n_hot * strip_px;
+    if (!has_pass || words == 0 || words > (1ull << 27)) return RTGO_OK;
+    key = {p.W, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, p.grab, strip_px, p.hot_x0, p.hot_y0, p.hot_w, p.hot_h};
+    if (words > c->seeds_capacity) {
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));   // (launches in flight may still use the old buffers)
+        free_seeds(c);
+        RTGO_HIP(c, hipMalloc(&c->d_seeds[0], words * sizeof(unsigned int)));
+        RTGO_HIP(c, hipMalloc(&c->d_seeds[1], words * sizeof(unsigned int)));
+        c->seeds_capacity = (size_t)words;
+    }
+    if (c->seeds_ok && c->seeds_frame == p.frame && c->seeds_key == key) p.seeds = c->d_seeds[c->seeds_read];
+    p.seeds_next = c->d_seeds[1 - c->seeds_read];
+    return RTGO_OK;
+}
+
 static constexpr uint64_t kUnitsPerWave4For6 = 8;   // launches with fewer units per wave (counted at 4 waves/SIMD) take at most 5 waves (pick_block)
 
 struct Block {
@@ -1420,7 +1475,18 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     const RenderKernel kernel = find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid);
     if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
     const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels;
-    return enqueue(c, kernel, p, b, pk, canon, culled * nn);
+    std::vector<uint32_t> seeds_key;
+    if (const int rc = plan_seeds(c, p, strip_px, kernel_has_seed_pass(canon, b.wpe, pk.stream), seeds_key)) return rc;
+    c->seeds_ok = false;   // (until this launch is on the stream)
+    if (const int rc = enqueue(c, kernel, p, b, pk, canon, culled * nn)) return rc;
+    c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
+    if (p.seeds_next) {
+        c->seeds_read = 1 - c->seeds_read;
+        c->seeds_frame = p.frame + 1u;
+        c->seeds_key = std::move(seeds_key);
+        c->seeds_ok = true;
+    }
+    return RTGO_OK;
 }
 
 int rtgo_assemble_bands(rtgo_ctx* c, void* hip_stream, const void* d_gathered, void* d_full, uint32_t w, uint32_t h, uint32_t band_h,

@@ -72,6 +72,12 @@ struct LaunchParams {
     uchar4* image;
     unsigned int* queue;            // kQueues work-queue heads, kQueueStride words apart, all zero when the launch starts
     unsigned int* queue_next;       // the other set of heads: zeroed by this launch for the next one (no memset between frames)
+    // Pixel seeds of a progressive job: tea<16>(pixel, frame) for every pixel of the hot strips, grab * 64 / nn_eff words per strip
+    // (word strip * strip_px + i: pixel i of strip `strip`).  `seeds`: this frame's, written by the previous launch on this context
+    // (null: hash them inline).  `seeds_next`: where this launch writes frame + 1's (null: it does not), 64 pixels per chunk, by
+    // the waves whose queue has run dry.
+    const unsigned int* seeds;
+    unsigned int* seeds_next;
     unsigned long long* counters;   // [0] rays_total [1] rays_occlusion [2] node_visits [3] prim_tests [4] hits
     int n_prims, n_nodes, n_lights;
     unsigned int W, H;              // full image
@@ -1195,6 +1201,33 @@ constexpr int kStreamWindow = RTGO_STREAM_WINDOW;   // STREAM: passes a lane may
 // far-field guard, where it is the product path.
 // FRAMES: the scene holds flat primitives only (cornell, checkered): closest-hit takes N and the sampling tangent from the frames
 // build_kernel computed (bit for bit the per-hit values); an instantiation of its own, so that the other scenes' code is untouched.
+// A progressive job's next frame redoes this frame's pixels with frame + 1.  A wave whose queue has run dry hashes their seeds for the
+// next launch (LaunchParams::seeds_next) in chunks of 64 pixels, one per lane, so that every lane of the 16 rounds is used -- against a
+// strip's hash in the ray loop's prologue, of which a 1-unit strip keeps 4 of 64 lanes.  Wave w of the grid takes chunks w, w + waves,
+// ... (1080p: ~1.5 per wave): no shared counter, which 6144 waves would queue at (one counter, ~88 atomics / us: +0.39 ms a frame).
+// The pixel of word i is the one render_kernel hashes for lane i % strip_px of hot strip i / strip_px.
+// Only the 6-waves lock-step variant has the pass (and reads LaunchParams::seeds): the host picks it for launches of >= 8 units per
+// wave (kUnitsPerWave4For6), where the strips' hashes saved outweigh a pass at the end of every wave -- a 1/8 band share of the bench
+// frame has ~3 strips per wave -- and every other variant compiles as it did without it (their register budgets have no room).
+constexpr bool kernel_has_seed_pass(bool stats, int wpe, bool stream) { return !stats && wpe >= 6 && !stream; }
+
+__device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned int lane, unsigned int P, unsigned int wave, unsigned int waves)
+{
+    const unsigned int strip_px = p.grab * P;
+    const unsigned int n_px = p.n_hot * strip_px;
+    for (unsigned int c = wave; c < (n_px + 63u) / 64u; c += waves) {
+        const unsigned int i = c * 64u + lane;
+        if (i < n_px) {
+            const unsigned int strip = i / strip_px, j = i - strip * strip_px;
+            const unsigned int lr = p.hot_y0 + strip / p.hot_w;
+            const unsigned int sx = p.hot_x0 + (strip - (lr - p.hot_y0) * p.hot_w);
+            const unsigned int band = lr / p.band_h;
+            const unsigned int gy = p.y0 + (band * p.n_ranks + p.rank) * p.band_h + (lr - band * p.band_h);
+            p.seeds_next[i] = tea16(p.W * gy + (p.x0 + sx * strip_px + j), p.frame + 1u);
+        }
+    }
+}
+
 template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p, const float4* __restrict__ g_fprims)
 {
@@ -1284,6 +1317,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     // where they are used (opaque_lane, s_cam) instead of being held in VGPRs through every ray loop -- what fits 80 VGPRs without
     // scratch.  The other variants keep the hoisted values, which their budgets afford and which are cheaper.
     constexpr bool LEAN = (WPE >= 6);
+    constexpr bool SEEDS = kernel_has_seed_pass(STATS, WPE, STREAM);
     auto lane_index = [&]() { return LEAN ? opaque_lane() : (unsigned int)lane; };
     auto frame_ratio = [&]() { return LEAN ? s_cam[16] : 1.0f / (float)(p.frame + 1); };
     const unsigned int nn = (unsigned int)(p.sqrt_spp * p.sqrt_spp);
@@ -1388,7 +1422,10 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         const unsigned int gy = p.y0 + wrow;
         const float fy = (float)gy;
         const unsigned int strip_x0 = sx * p.grab * P;
-        const unsigned int strip_seed = tea16(p.W * gy + (p.x0 + strip_x0 + lane_q), p.frame);
+        // (pre-hashed by the previous launch when the host says they are there: one load instead of the 16 rounds)
+        unsigned int strip_seed;
+        if (SEEDS && p.seeds != nullptr) strip_seed = lane_q < p.grab * P ? p.seeds[strip * (p.grab * P) + lane_q] : 0u;
+        else strip_seed = tea16(p.W * gy + (p.x0 + strip_x0 + lane_q), p.frame);
 #ifdef RTGO_TIMELINE
         if (tl_b == 0) tl_b = wall_clock64() + (strip_seed == 0x12345u ? 1 : 0);
 #endif
@@ -1625,6 +1662,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 #endif
         }  // unit
     }
+    // the queue has run dry: next frame's seeds
+    if constexpr (SEEDS)
+        if (p.seeds_next != nullptr) next_frame_seeds(p, lane_index(), P, blockIdx.x * wpb + ((unsigned int)tid >> 6), gridDim.x * wpb);
 
 #ifdef RTGO_TIMELINE
     if (lane == 0) {
