@@ -27,6 +27,7 @@ extern "C" {
 
 #define RTGO_ABI_VERSION 6
 #define RTGO_MAX_PRIMS 512  /* scene staged whole in LDS (largest reference scene: checkered, 390) */
+#define RTGO_MAX_SCENE_PRIMS (1 << 20)  /* rtgo_set_large_scene: scene built and walked in global memory */
 #define RTGO_MAX_LIGHTS 10  /* Params::MAX_LIGHTS, engine/params.h:115 */
 
 enum {
@@ -97,14 +98,14 @@ typedef struct rtgo_stats {
     float last_launch_ms;     /* HIP-event time of the last megakernel launch (valid after rtgo_sync) */
     float total_launch_ms;    /* sum over launches since rtgo_reset_stats */
     uint32_t launches;
-    uint32_t lbvh_depth;      /* depth of the on-device LBVH */
+    uint32_t lbvh_depth;      /* depth of the on-device LBVH (rtgo_set_scene's or rtgo_set_large_scene's) */
     uint64_t dbg_fast_boxes;  /* diagnostic builds (-DRTGO_FAST_COUNTERS) only: boxes tested by the fast walk, else 0 */
     uint64_t dbg_fast_tests;  /* diagnostic builds only: leaf tests of the fast walk incl. the up-front list, else 0 */
     uint64_t rays_culled;     /* primary rays among rays_total that were answered (as misses) by the screen rectangle of the
                                  scene's bounds instead of a traversal; always 0 for collect_stats launches */
-    uint32_t launches_canonical; /* launches since rtgo_reset_stats that walked the canonical LBVH: collect_stats launches, and
-                                    launches beyond the far-field guard (guard_reach / guard_quadric below; several times slower;
-                                    DESIGN.md 3.2) */
+    uint32_t launches_canonical; /* launches since rtgo_reset_stats that walked the canonical LBVH: collect_stats launches, launches
+                                    beyond the far-field guard (guard_reach / guard_quadric below; several times slower),
+                                    and every launch over a scene of rtgo_set_large_scene */
     uint32_t cuboid_groups;   /* scene property: groups of three rectangle pairs the build certified as the faces of one box or room
                                  (tested by the fast walk's cuboid test); the up-front list's counts as one */
     float guard_reach;        /* last launch: max(|scene bounds|, |eye|), world units -- the far-field guard's first quantity */
@@ -113,7 +114,8 @@ typedef struct rtgo_stats {
     uint32_t last_variant;    /* last launch: bit 0 streaming loop, bit 1 the second fast-walk structure, bit 2 canonical walk, bit 3 the
                                  launch was one of the launch-time trial's (the first launches of a job time the candidate
                                  (loop, structure) pairs -- same pixels either way -- and the fastest keeps the job), bit 4 the fast walk
-                                 over the uniform grid instead of a tree */
+                                 over the uniform grid instead of a tree, bit 5 the scene walked from global memory (a scene of
+                                 rtgo_set_large_scene; always with bit 2) */
     uint32_t launches_trial;  /* launches since rtgo_reset_stats that were trial launches */
 } rtgo_stats;
 
@@ -140,6 +142,13 @@ int rtgo_set_stream(rtgo_ctx* ctx, void* hip_stream);
    kernel relies on that and culls with its own tighter per-shape boxes.
    Builds M^-1 per primitive and the canonical LBVH on the device.  Synchronous. */
 int rtgo_set_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n);
+
+/* optixAccelBuild over any number of primitives (the reference has no size limit): rtgo_set_scene's arguments, checks and error codes,
+   for n in [1, RTGO_MAX_SCENE_PRIMS].  Builds the same canonical LBVH as rtgo_set_scene with a multi-workgroup build in global memory and
+   renders every launch with the canonical walk over it, straight from global memory (no fast-walk structures, no launch-time trial).
+   A tree deeper than the walk's stack (64) is refused with RTGO_E_UNSUPPORTED.  Replaces whatever scene the context holds.  Synchronous.
+   A scene within RTGO_MAX_PRIMS renders the same pixels bit for bit through rtgo_set_scene, and faster there. */
+int rtgo_set_large_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n);
 
 /* raygen SBT record: Renderer::CreateRayGen / SyncCameraToSbt (renderer.cpp:321-336, 719-731); device::CameraData */
 int rtgo_set_camera(rtgo_ctx* ctx, const float eye[3], const float U[3], const float V[3], const float W[3]);
@@ -176,7 +185,7 @@ int rtgo_write_accum(rtgo_ctx* ctx, const void* host_float4, size_t bytes);
 int rtgo_get_stats(rtgo_ctx* ctx, rtgo_stats* out);
 int rtgo_reset_stats(rtgo_ctx* ctx);
 
-/* Debug/test access to what rtgo_set_scene built: nodes = 2n-1 records of 32 bytes
+/* Debug/test access to what rtgo_set_scene or rtgo_set_large_scene built: nodes = 2n-1 records of 32 bytes
    {float bmin[3]; int32 left; float bmax[3]; int32 right} ... see DESIGN.md; inverses = n x 12 floats (rows 0..2). */
 int rtgo_read_bvh(rtgo_ctx* ctx, void* host_nodes, size_t node_bytes, void* host_inverses, size_t inv_bytes,
                   void* host_aabbs, size_t aabb_bytes);

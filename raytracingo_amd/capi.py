@@ -13,6 +13,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTGO_HIP_LIB") or os.path.join(PKG_DIR, "librtgo_hip.so")
 
 RTGO_MAX_PRIMS = 512
+RTGO_MAX_SCENE_PRIMS = 1 << 20   # rtgo_set_large_scene: built and walked in global memory
 RTGO_MAX_LIGHTS = 10
 CYLINDER, DISK, RECTANGLE, SPHERE = 0, 1, 2, 3
 
@@ -21,7 +22,7 @@ SYMBOLS = [
     "rtgo_create", "rtgo_destroy", "rtgo_last_error", "rtgo_set_stream", "rtgo_set_scene", "rtgo_set_camera",
     "rtgo_set_background", "rtgo_set_lights", "rtgo_resize", "rtgo_bind_output", "rtgo_launch", "rtgo_sync",
     "rtgo_read_image", "rtgo_read_accum", "rtgo_write_accum", "rtgo_get_stats", "rtgo_reset_stats", "rtgo_read_bvh",
-    "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands",
+    "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands", "rtgo_set_large_scene",
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame",
@@ -39,6 +40,12 @@ class RtgoError(RuntimeError):
 class Prim(C.Structure):
     _fields_ = [("type", C.c_uint32), ("model", C.c_float * 16), ("kd", C.c_float * 3), ("kr", C.c_float * 3),
                 ("specularity", C.c_float), ("Le", C.c_float * 3)]
+
+
+# rtgo_prim as a numpy record (packed, 108 bytes): bulk packing for set_large_scene
+PRIM_DTYPE = np.dtype([("type", "<u4"), ("model", "<f4", (16,)), ("kd", "<f4", (3,)), ("kr", "<f4", (3,)), ("specularity", "<f4"),
+                       ("Le", "<f4", (3,))])
+assert PRIM_DTYPE.itemsize == C.sizeof(Prim)
 
 
 class Aabb(C.Structure):
@@ -112,6 +119,7 @@ def load():
     L.rtgo_destroy.argtypes = [vp]
     L.rtgo_set_stream.argtypes = [vp, vp]
     L.rtgo_set_scene.argtypes = [vp, C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32]
+    L.rtgo_set_large_scene.argtypes = [vp, C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32]
     L.rtgo_set_camera.argtypes = [vp, fp, fp, fp, fp]
     L.rtgo_set_background.argtypes = [vp, fp]
     L.rtgo_set_lights.argtypes = [vp, C.POINTER(Light), C.c_int]
@@ -206,6 +214,26 @@ class Context:
             for i in range(n):
                 (bb[i].minX, bb[i].minY, bb[i].minZ, bb[i].maxX, bb[i].maxY, bb[i].maxZ) = aabbs[i].tolist()
         self._check(self._lib.rtgo_set_scene(self._h, arr, bb, n), "rtgo_set_scene")
+        self.n_prims = n
+
+    def set_large_scene(self, types, models, materials, aabbs=None):
+        """rtgo_set_large_scene: set_scene's arguments, up to RTGO_MAX_SCENE_PRIMS primitives.  The records are packed with numpy
+        (a million primitives upload in seconds)."""
+        types = np.asarray(types)
+        n = len(types)
+        rec = np.zeros(n, dtype=PRIM_DTYPE)
+        rec["type"] = types.astype(np.uint32)
+        rec["model"] = np.asarray(models, dtype=np.float32).reshape(-1, 16)
+        mat = np.asarray(materials, dtype=np.float32).reshape(-1, 10)
+        rec["kd"], rec["kr"], rec["specularity"], rec["Le"] = mat[:, 0:3], mat[:, 3:6], mat[:, 6], mat[:, 7:10]
+        bb = None
+        if aabbs is not None:
+            bb = np.ascontiguousarray(aabbs, dtype=np.float32).reshape(-1, 6)
+            if len(bb) != n:
+                raise ValueError("aabbs: %d boxes for %d primitives" % (len(bb), n))
+        self._check(self._lib.rtgo_set_large_scene(self._h, rec.ctypes.data_as(C.POINTER(Prim)) if n else (Prim * 1)(),
+                                                   bb.ctypes.data_as(C.POINTER(Aabb)) if bb is not None else None, n),
+                    "rtgo_set_large_scene")
         self.n_prims = n
 
     def set_camera(self, eye, U, V, W):

@@ -3,6 +3,7 @@
 // There is no CPU fallback anywhere in this file: every path ends in a HIP launch or an error code.
 #include "../../include/rtgo.h"
 #include "rtgo_device.h"
+#include "rtgo_large.h"
 #include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
 
@@ -21,6 +22,7 @@ static_assert(sizeof(rtgo_prim) == 108, "rtgo_prim is type + HitGroupData (104 B
 static_assert(sizeof(rtgo_light) == sizeof(LightRec) && sizeof(rtgo_light) == 64, "SurfaceLight is 64 B");
 static_assert(sizeof(rtgo_aabb) == 24, "OptixAabb is 24 B");
 static_assert(RTGO_MAX_PRIMS == kMaxPrims && RTGO_MAX_LIGHTS == kMaxLights, "limits");
+static_assert(RTGO_MAX_SCENE_PRIMS <= (1 << 29), "2n-1 nodes of 32 bytes and their int indices stay within int range");
 
 // one mesh of an instanced whitted scene (rtgo_whitted_set_scene), host side
 struct WhittedMeshInfo {
@@ -92,6 +94,7 @@ struct rtgo_ctx {
     float4* d_nodes = nullptr;
     float4* d_prims = nullptr;
     float4* d_frames = nullptr;   // shading frames of the flat primitives (2 float4 per primitive, SBT order)
+    bool large = false;           // the scene came from rtgo_set_large_scene: d_nodes / d_prims / d_aabb only, walked from global memory
     int* d_meta = nullptr;        // build_kernel's meta words (one build at a time)
     int lbvh_depth = 0;
     float bounds[6] = {0, 0, 0, 0, 0, 0};  // tight world bounds of the scene (min xyz, max xyz)
@@ -206,10 +209,12 @@ struct RenderKernelEntry {
     bool count, frames;
     RenderKernel fn;
     bool grid = false;
+    bool global = false;   // the canonical walk over a scene in global memory (rtgo_set_large_scene)
 };
 #define RTGO_K(P, S, W, T) {P, S, T, W, S, false, render_kernel<P, S, W, T>}
 #define RTGO_KF(W, T) {true, false, T, W, false, true, render_kernel<true, false, W, T, false, true>}
 #define RTGO_KG(P, W, T) {P, false, T, W, false, false, render_kernel<P, false, W, T, false, false, true>, true}
+#define RTGO_KL(P, C) {P, true, false, 4, C, false, render_kernel<P, true, 4, false, C, false, false, true>, false, true}
 static const RenderKernelEntry kRenderKernels[] = {
     RTGO_K(true, false, 4, false),  RTGO_K(true, false, 5, false),    // path mode, fast walk
     RTGO_K(false, false, 4, false), RTGO_K(false, false, 5, false),   // distributed mode, fast walk
@@ -222,15 +227,17 @@ static const RenderKernelEntry kRenderKernels[] = {
     RTGO_KF(6, false),                                                                      // ... at 6 waves/SIMD: the only combination that fits 80 VGPRs without scratch
     RTGO_KG(true, 4, false), RTGO_KG(true, 5, false), RTGO_KG(true, 4, true), RTGO_KG(true, 5, true),       // fast walk over the uniform grid instead of the tree (fast_grid)
     RTGO_KG(false, 4, false), RTGO_KG(false, 5, false), RTGO_KG(false, 4, true), RTGO_KG(false, 5, true),
+    RTGO_KL(true, false), RTGO_KL(false, false), RTGO_KL(true, true), RTGO_KL(false, true),   // scenes of rtgo_set_large_scene: timed, collect_stats
 };
 #undef RTGO_K
 #undef RTGO_KF
 #undef RTGO_KG
-static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, bool count, bool frames, bool grid)
+#undef RTGO_KL
+static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, bool count, bool frames, bool grid, bool global = false)
 {
     for (const RenderKernelEntry& e : kRenderKernels)
         if (e.path == path && e.canon == canon && e.wpe == (canon ? 4 : wpe) && e.stream == (canon ? false : stream) && e.count == (canon && count) &&
-            e.frames == (frames && path && !canon) && e.grid == (grid && !canon))
+            e.frames == (frames && path && !canon) && e.grid == (grid && !canon) && e.global == (global && canon))
             return e.fn;
     return nullptr;
 }
@@ -546,6 +553,7 @@ static void free_scene(rtgo_ctx* c)
     release(c->d_frames);
     release(c->d_tight);
     c->n_prims = 0;
+    c->large = false;
     free_seeds(c);
 }
 
@@ -836,14 +844,12 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
     return RTGO_OK;
 }
 
-int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+// the per-primitive checks of rtgo_set_scene and rtgo_set_large_scene (`what`: the entry point, for the message)
+static int check_prims(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n, const std::string& what)
 {
-    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: NULL argument");
-    if (n == 0 || n > RTGO_MAX_PRIMS)
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_PRIMS) + "]");
     for (uint32_t i = 0; i < n; ++i) {
         const rtgo_prim& q = prims[i];
-        if (q.type > RTGO_SPHERE) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: unknown primitive type");
+        if (q.type > RTGO_SPHERE) return fail(c, RTGO_E_INVALID, what + ": unknown primitive type");
         // the intersection programs work in object space through M^-1 (kernel.cu:125-135): M must be finite and invertible
         bool finite = std::isfinite(q.specularity);
         for (int k = 0; k < 16; ++k) finite = finite && std::isfinite(q.model[k]);
@@ -852,13 +858,22 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
                      l = q.model[9], m = q.model[10];
         const double det = a * (g * m - h * l) - b * (e * m - h * k2) + d3 * (e * l - g * k2);
         if (!finite || !std::isfinite(det) || std::fabs(det) < 1e-30)
-            return fail(c, RTGO_E_INVALID, "rtgo_set_scene: primitive " + std::to_string(i) + " has a non-finite or singular model matrix / material");
+            return fail(c, RTGO_E_INVALID, what + ": primitive " + std::to_string(i) + " has a non-finite or singular model matrix / material");
         if (aabbs) {
             const rtgo_aabb& bb = aabbs[i];
             if (!(bb.minX <= bb.maxX && bb.minY <= bb.maxY && bb.minZ <= bb.maxZ) || !std::isfinite(bb.minX + bb.minY + bb.minZ + bb.maxX + bb.maxY + bb.maxZ))
-                return fail(c, RTGO_E_INVALID, "rtgo_set_scene: box " + std::to_string(i) + " is empty or not finite");
+                return fail(c, RTGO_E_INVALID, what + ": box " + std::to_string(i) + " is empty or not finite");
         }
     }
+    return RTGO_OK;
+}
+
+int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+{
+    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: NULL argument");
+    if (n == 0 || n > RTGO_MAX_PRIMS)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_PRIMS) + "]");
+    if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_scene")) return rc;
     const Knobs kn;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
@@ -920,6 +935,103 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
         e.w = (float)(smax / (smin * smin));
         c->quadrics.push_back(e);
     }
+    return RTGO_OK;
+}
+
+// the temporaries of rtgo_set_large_scene's build, freed however the call ends
+struct LargeScratch {
+    unsigned long long *keys = nullptr, *keys_alt = nullptr;
+    unsigned int* hist = nullptr;
+    int *left = nullptr, *right = nullptr, *parent = nullptr, *depth = nullptr;
+    float* small = nullptr;   // scene bounds (6 floats), then the largest leaf depth (int)
+    ~LargeScratch()
+    {
+        release(keys);
+        release(keys_alt);
+        release(hist);
+        release(left);
+        release(right);
+        release(parent);
+        release(depth);
+        release(small);
+    }
+};
+
+int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+{
+    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_large_scene: NULL argument");
+    if (n == 0 || n > RTGO_MAX_SCENE_PRIMS)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_SCENE_PRIMS) + "]");
+    if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_large_scene")) return rc;
+    const Knobs kn;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    free_scene(c);
+    c->mask_key.clear();
+    c->trial = rtgo_ctx::Trial();
+    c->quadrics.clear();
+    c->lbvh_depth = 0;
+    const int ni = (int)n, n_int = ni > 1 ? ni - 1 : 1;
+    const int nb = (ni + whitted::kRadixTile - 1) / whitted::kRadixTile;
+    LargeScratch ls;
+    RTGO_HIP(c, hipMalloc(&c->d_prims_in, (size_t)n * sizeof(PrimIn)));
+    RTGO_HIP(c, hipMalloc(&c->d_aabb, (size_t)n * 6 * sizeof(float)));
+    RTGO_HIP(c, hipMalloc(&c->d_nodes, (2 * (size_t)n - 1) * 2 * sizeof(float4)));
+    RTGO_HIP(c, hipMalloc(&c->d_prims, (size_t)n * 6 * sizeof(float4)));
+    RTGO_HIP(c, hipMalloc(&ls.keys, (size_t)n * sizeof(unsigned long long)));
+    RTGO_HIP(c, hipMalloc(&ls.keys_alt, (size_t)n * sizeof(unsigned long long)));
+    RTGO_HIP(c, hipMalloc(&ls.hist, (size_t)256 * nb * sizeof(unsigned int)));
+    RTGO_HIP(c, hipMalloc(&ls.left, (size_t)n_int * sizeof(int)));
+    RTGO_HIP(c, hipMalloc(&ls.right, (size_t)n_int * sizeof(int)));
+    RTGO_HIP(c, hipMalloc(&ls.parent, (2 * (size_t)n - 1) * sizeof(int)));
+    RTGO_HIP(c, hipMalloc(&ls.depth, (size_t)n_int * sizeof(int)));
+    RTGO_HIP(c, hipMalloc(&ls.small, 8 * sizeof(float)));
+    RTGO_HIP(c, hipMemcpyAsync(c->d_prims_in, prims, (size_t)n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
+    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(c->d_aabb, aabbs, (size_t)n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemsetAsync(ls.small, 0, 8 * sizeof(float), c->stream));
+    const dim3 g_prims((n + 255) / 256), g_nodes((2 * n - 1 + 255) / 256), g_int((n_int + 255) / 256);
+    // records and boxes; bounds; Morton keys in (code, index) order (four stable passes over the code's bytes: back in ls.keys)
+    hipLaunchKernelGGL(large_prep_kernel, g_prims, dim3(256), 0, c->stream, (const PrimIn*)c->d_prims_in, c->d_aabb, aabbs ? 1 : 0, ni, c->d_prims);
+    hipLaunchKernelGGL(whitted::big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)c->d_aabb, ni, ls.small);
+    hipLaunchKernelGGL(large_keys_kernel, g_prims, dim3(256), 0, c->stream, (const float*)c->d_aabb, ni, (const float*)ls.small, ls.keys);
+    unsigned long long *src = ls.keys, *dst = ls.keys_alt;
+    for (int shift = 32; shift < 64; shift += 8) {
+        hipLaunchKernelGGL(whitted::radix_count_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift, ls.hist);
+        hipLaunchKernelGGL(whitted::radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, ls.hist, 256 * nb);
+        hipLaunchKernelGGL(whitted::radix_scatter_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift,
+                           (const unsigned int*)ls.hist, dst);
+        std::swap(src, dst);
+    }
+    // hierarchy, depths and leaves
+    int* d_max_depth = reinterpret_cast<int*>(ls.small + 6);
+    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, ls.left, ls.right, ls.parent);
+    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, (const float*)c->d_aabb,
+                       (const int*)ls.parent, ls.depth, c->d_nodes, d_max_depth);
+    RTGO_HIP(c, hipGetLastError());
+    int depth = 0;
+    RTGO_HIP(c, hipMemcpyAsync(&depth, d_max_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (depth > kLargeMaxDepth) {
+        free_scene(c);
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
+                                               std::to_string(kLargeMaxDepth) + ")");
+    }
+    // boxes, one level per launch from the deepest up (a kernel boundary between a node's children and the node)
+    for (int level = depth - 1; level >= 0; --level)
+        hipLaunchKernelGGL(large_fit_kernel, g_int, dim3(256), 0, c->stream, (const int*)ls.left, (const int*)ls.right, (const int*)ls.depth,
+                           ni - 1, level, c->d_nodes);
+    RTGO_HIP(c, hipGetLastError());
+    float4 root[2];
+    RTGO_HIP(c, hipMemcpyAsync(root, c->d_nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    release(c->d_prims_in);   // (the records hold all the walk and the shading read)
+    const float b[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
+    std::memcpy(c->bounds, b, sizeof c->bounds);
+    c->lbvh_depth = depth;
+    c->n_prims = n;
+    c->large = true;
+    if (kn.debug)
+        std::fprintf(stderr, "rtgo_set_large_scene: %d primitives, canonical LBVH depth %d in global memory\n", ni, depth);
     return RTGO_OK;
 }
 
@@ -1357,15 +1469,17 @@ struct Block {
     unsigned int grid = 0;                       // workgroups
 };
 
-// LDS image of the chosen kernel (see render_kernel): canonical = nodes + 6/prim; fast = fnodes + 4/prim + 3/prim.
+// LDS image of the chosen kernel (see render_kernel): canonical = nodes + 6/prim; fast = fnodes + 4/prim + 3/prim; global (a scene of
+// rtgo_set_large_scene): no scene at all.
 // The scene copy is per workgroup and the stack per lane, so bigger scenes want bigger workgroups: pick the size that
-// puts the most waves on a CU (4, 5 or 6 per SIMD, what the variant's VGPR budget admits), smallest size on ties.
+// puts the most waves on a CU (4, 5 or 6 per SIMD, what the variant's VGPR budget admits), smallest size on ties.  Without a scene copy
+// the stack alone sets the count, and workgroups of one or two waves fit the most of them.
 static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, bool canon, bool stream, bool frames, bool grid,
-                      uint64_t units_hot, const Knobs& kn, Block& b)
+                      uint64_t units_hot, const Knobs& kn, Block& b, bool global = false)
 {
     const bool path = f->path_tracing != 0;
     const int fast_nodes = p.n_fnodes;   // (the tree's nodes, or the grid in their place)
-    const size_t scene_lds = (size_t)(2 * (canon ? p.n_nodes : fast_nodes) + (canon ? 6 : 7) * p.n_prims + (frames ? 2 * p.n_prims : 0) /* shading frames */) * sizeof(float4) +
+    const size_t scene_lds = (global ? 0 : (size_t)(2 * (canon ? p.n_nodes : fast_nodes) + (canon ? 6 : 7) * p.n_prims + (frames ? 2 * p.n_prims : 0) /* shading frames */) * sizeof(float4)) +
                              (size_t)kMaxLights * sizeof(LightRec) + kCamWords * sizeof(float) +   // + the raygen constants (kCamWordsLean at 6 waves: below)
                              (size_t)(nn < (uint32_t)kSampleTab ? nn : (uint32_t)kSampleTab) * sizeof(uint4);   // + the per-sample start table
     int best_waves = 0;
@@ -1377,12 +1491,12 @@ static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, u
     // HBM per launch, profiles/r02d) and was dropped; today's fits because the per-lane values derived from the lane index are
     // derived where they are used (opaque_lane in rtgo_device.h) instead of being held through every ray loop.
     const uint64_t units_per_wave4 = units_hot * (passes_of(nn)) / ((uint64_t)c->num_cus * 16u);
-    const int top_wpe = find_kernel(path, canon, 6, stream, false, frames, grid) ? 6 : 5;   // the 6-waves variant exists for some combinations only
+    const int top_wpe = find_kernel(path, canon, 6, stream, false, frames, grid, global) ? 6 : 5;   // the 6-waves variant exists for some combinations only
     const int max_wpe_work = units_per_wave4 >= kUnitsPerWave4For6 ? 6 : (units_per_wave4 >= 3 ? 5 : 4);
     int max_wpe = canon ? 4 : (kn.max_wpe ? (int)kn.max_wpe : max_wpe_work);   // (RTGO_MAX_WPE: experiment knob, clamped to what exists)
     max_wpe = max_wpe < 4 ? 4 : (max_wpe > top_wpe ? top_wpe : max_wpe);
     for (int w = 4; w <= max_wpe; ++w)
-        for (int bs = 256; bs <= kMaxBlock; bs *= 2) {
+        for (int bs = global ? 64 : 256; bs <= kMaxBlock; bs *= 2) {
             const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + (w >= 5 ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0) + (w >= 6 ? (size_t)(kCamWordsLean - kCamWords) * sizeof(float) : 0);
             int per_cu = (int)((160 * 1024) / l);
             if (per_cu * (bs / 64) > 4 * w) per_cu = (4 * w) / (bs / 64);
@@ -1443,11 +1557,45 @@ static int enqueue(rtgo_ctx* c, RenderKernel kernel, const LaunchParams& p, cons
     return RTGO_OK;
 }
 
+// A launch over a scene of rtgo_set_large_scene: the canonical walk from global memory (render_kernel's GLOBAL instantiations), the
+// stack as deep as the scene's tree.  No launch-time trial, fast structure, far-field guard (the canonical walk is what every other
+// walk is held to) or seed pass; the screen rectangle comes from the root box, without a per-strip mask.
+static int launch_large(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p, const Knobs& kn)
+{
+    const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
+    const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
+    const Rect r = f->collect_stats != 1 ? box_screen_rect(c->bounds, p) : Rect{0, p.w, 0, p.h};
+    c->guard_reach = 0.0f;
+    c->guard_quadric = 0.0f;
+    p.nodes = c->d_nodes;
+    p.prims = c->d_prims;
+    p.stack_depth = c->lbvh_depth > 0 ? c->lbvh_depth : 1;
+    uint32_t strip_px = 0;
+    uint64_t units_hot = 0;
+    if (const int rc = schedule(c, nn, r, p, strip_px, units_hot)) return rc;
+    if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
+    Block b;
+    if (const int rc = pick_block(c, f, p, nn, true, false, false, false, units_hot, kn, b, true)) return rc;
+    if (kn.debug)
+        std::fprintf(stderr, "rtgo_launch: canonical walk from global memory, grid %u x %d threads, %zu B LDS, %d workgroups/CU, %u strips of %u px, stack %d\n",
+                     b.grid, b.block, b.lds, b.blocks_per_cu, p.n_hot, strip_px, p.stack_depth);
+    const RenderKernel kernel = find_kernel(path, true, 4, false, stats, false, false, true);
+    if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
+    const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0);
+    c->seeds_ok = false;
+    Pick pk;
+    if (const int rc = enqueue(c, kernel, p, b, pk, true, culled * nn)) return rc;
+    c->last_variant |= 32u;
+    c->seeds_last = 0;
+    return RTGO_OK;
+}
+
 int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
 {
     const Knobs kn;
     LaunchParams p;
     if (const int rc = frame_params(c, f, p)) return rc;
+    if (c->large) return launch_large(c, f, p, kn);
     const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
     const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
     // collect_stats 1: the instrumented kernel traces every pixel (V, T, h over ALL rays); 2: it culls like the timed

@@ -1228,22 +1228,27 @@ __device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned
     }
 }
 
-template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false>
+// GLOBAL (with STATS, not FRAMES / GRID / STREAM): a scene of rtgo_set_large_scene.  The canonical walk reads nodes and primitive records
+// straight from global memory (p.nodes / p.prims: the same layout and the same arithmetic as the LDS copy), nothing is staged; LDS holds
+// the stack (p.stack_depth entries: the scene's depth), the lights, the raygen constants and the sample table.
+template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false, bool GLOBAL = false>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p, const float4* __restrict__ g_fprims)
 {
+    static_assert(!GLOBAL || (STATS && !FRAMES && !GRID && !STREAM), "the global-memory scene is walked by the canonical walk alone");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // LDS image.  STATS (canonical, instrumented walk): [nodes 2/node][prims 6/prim, SBT order][frames 2/prim][stack][lights]
     //             fast walk (the timed kernel):          [fnodes 2/node][fprims 4/prim, Morton order][materials 3/prim][frames 2/prim][stack, 4 B/entry][lights]
+    //             GLOBAL:                                [stack][lights]
     constexpr int MS = STATS ? 6 : 3;  // float4 stride between two primitives' material rows (kd|spec, kr|type, Le)
     const int n_nodes = STATS ? p.n_nodes : p.n_fnodes;
-    float4* s_nodes = reinterpret_cast<float4*>(smem);
-    float4* s_prims = s_nodes + 2 * n_nodes;
+    float4* s_nodes = GLOBAL ? const_cast<float4*>(p.nodes) : reinterpret_cast<float4*>(smem);
+    float4* s_prims = GLOBAL ? const_cast<float4*>(p.prims) : s_nodes + 2 * n_nodes;
     float4* s_mat_w = STATS ? s_prims + 3 : s_prims + 4 * p.n_prims;
     float4* s_frame_w = STATS ? s_prims + 6 * p.n_prims : s_mat_w + 3 * p.n_prims;   // shading frames of the flat primitives, 2 float4 per primitive, SBT order
-    float4* s_end = s_frame_w + (FRAMES ? 2 * p.n_prims : 0);   // (only the instantiation that uses them pays for them)
+    float4* s_end = GLOBAL ? reinterpret_cast<float4*>(smem) : s_frame_w + (FRAMES ? 2 * p.n_prims : 0);   // (only the instantiation that uses them pays for them)
     const float4* s_frame = s_frame_w;
     float2* s_stack_base = reinterpret_cast<float2*>(s_end);
-    const int stack_depth = STATS ? kStackDepth : p.stack_depth;
+    const int stack_depth = (STATS && !GLOBAL) ? kStackDepth : p.stack_depth;
     const int kBlock = (int)blockDim.x;           // 256, 512 or 1024
     const int bshift = 31 - __clz(kBlock);        // per-lane stack entry e lives at [e << bshift]
     // (entries x workgroup size x 8 bytes for the canonical walk, x 4 for the fast walk's packed words: a multiple of 1 KiB either way)
@@ -1278,8 +1283,10 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     unsigned int tl_units = 0, tl_iters = 0;
 #endif
     if (STATS) {
-        for (int i = tid; i < 2 * p.n_nodes; i += kBlock) s_nodes[i] = p.nodes[i];
-        for (int i = tid; i < 6 * p.n_prims; i += kBlock) s_prims[i] = p.prims[i];
+        if (!GLOBAL) {
+            for (int i = tid; i < 2 * p.n_nodes; i += kBlock) s_nodes[i] = p.nodes[i];
+            for (int i = tid; i < 6 * p.n_prims; i += kBlock) s_prims[i] = p.prims[i];
+        }
     } else {
         for (int i = tid; i < 2 * n_nodes; i += kBlock) s_nodes[i] = p.fnodes[i];
         for (int i = tid; i < 4 * p.n_prims; i += kBlock) s_prims[i] = p.fprims[i];
@@ -1805,6 +1812,54 @@ __device__ __forceinline__ int lbvh_delta(const unsigned long long* keys, int n,
     return __clz(a ^ b);
 }
 
+// One axis of a box centre c on the 10-bit Morton grid of the scene bounds [lo, lo + ext] (build_kernel and the global-memory build)
+__device__ __forceinline__ unsigned int morton_cell(float c, float lo, float ext)
+{
+    const float u = ext > 0.0f ? (c - lo) / ext : 0.0f;
+    return (unsigned int)fminf(fmaxf(u * 1024.0f, 0.0f), 1023.0f);
+}
+__device__ __forceinline__ unsigned int morton3(const unsigned int q[3])
+{
+    return (expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2]);
+}
+
+// Karras 2012: the children and the sorted key range [lo, hi] of internal node i of the tree over the m sorted unique keys (leaves are
+// nodes [m-1, 2m-2]; node 0 is the root)
+__device__ __forceinline__ void karras_node(const unsigned long long* keys, int m, int i, int& left, int& right, int& lo, int& hi)
+{
+    const int leaf0 = m - 1;
+    const int d = (lbvh_delta(keys, m, i, i + 1) - lbvh_delta(keys, m, i, i - 1)) >= 0 ? 1 : -1;
+    const int dmin = lbvh_delta(keys, m, i, i - d);
+    int lmax = 2;
+    while (lbvh_delta(keys, m, i, i + lmax * d) > dmin) lmax *= 2;
+    int l = 0;
+    for (int t = lmax / 2; t >= 1; t /= 2)
+        if (lbvh_delta(keys, m, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = lbvh_delta(keys, m, i, j);
+    int s = 0, t = l;
+    do {
+        t = (t + 1) / 2;
+        if (lbvh_delta(keys, m, i, i + (s + t) * d) > dnode) s += t;
+    } while (t > 1);
+    const int gamma = i + s * d + (d < 0 ? -1 : 0);
+    lo = i < j ? i : j;
+    hi = i < j ? j : i;
+    left = (lo == gamma) ? leaf0 + gamma : gamma;
+    right = (hi == gamma + 1) ? leaf0 + gamma + 1 : gamma + 1;
+}
+
+// The 6-float4 record of a primitive (SBT order, layout above) from its PrimIn and rows 0..2 of M^-1
+__device__ __forceinline__ void store_prim_record(float4* __restrict__ out, const PrimIn& P, const float* inv)
+{
+    out[0] = make_float4(inv[0], inv[1], inv[2], inv[3]);
+    out[1] = make_float4(inv[4], inv[5], inv[6], inv[7]);
+    out[2] = make_float4(inv[8], inv[9], inv[10], inv[11]);
+    out[3] = make_float4(P.kd[0], P.kd[1], P.kd[2], P.spec);
+    out[4] = make_float4(P.kr[0], P.kr[1], P.kr[2], __int_as_float((int)P.type));
+    out[5] = make_float4(P.Le[0], P.Le[1], P.Le[2], 0.0f);
+}
+
 // Outputs.  out_nodes: (2n-1) x 2 float4 canonical LBVH; out_prims: n x 6 float4 (SBT order); aabb_io: n x 6 floats (read when
 // have_aabb, else written); out_fnodes / out_fprims: the fast walk's tree (2*n_small-1 nodes) and Morton-ordered records
 // (small primitives first, then the "big" ones that are tested up front);
@@ -1864,10 +1919,9 @@ __global__ __launch_bounds__(kMaxPrims) void build_kernel(const PrimIn* __restri
             }
             const float c = (lo + hi) * 0.5f;
             const float ext = cubic ? emax : s_red[3 + a][0] - s_red[a][0];
-            const float u = ext > 0.0f ? (c - s_red[a][0]) / ext : 0.0f;
-            q[a] = (unsigned int)fminf(fmaxf(u * 1024.0f, 0.0f), 1023.0f);
+            q[a] = morton_cell(c, s_red[a][0], ext);
         }
-        return (expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2]);
+        return morton3(q);
     };
     // bitonic sort of the kMaxPrims keys in LDS; keys are unique, so the result is THE (code, index) order
     auto sort_keys = [&]() {
@@ -1898,24 +1952,8 @@ __global__ __launch_bounds__(kMaxPrims) void build_kernel(const PrimIn* __restri
         if (i + kMaxPrims < 2 * m - 1) s_parent[i + kMaxPrims] = -1;
         __syncthreads();
         if (i < m - 1) {
-            const int d = (lbvh_delta(s_keys, m, i, i + 1) - lbvh_delta(s_keys, m, i, i - 1)) >= 0 ? 1 : -1;
-            const int dmin = lbvh_delta(s_keys, m, i, i - d);
-            int lmax = 2;
-            while (lbvh_delta(s_keys, m, i, i + lmax * d) > dmin) lmax *= 2;
-            int l = 0;
-            for (int t = lmax / 2; t >= 1; t /= 2)
-                if (lbvh_delta(s_keys, m, i, i + (l + t) * d) > dmin) l += t;
-            const int j = i + l * d;
-            const int dnode = lbvh_delta(s_keys, m, i, j);
-            int s = 0, t = l;
-            do {
-                t = (t + 1) / 2;
-                if (lbvh_delta(s_keys, m, i, i + (s + t) * d) > dnode) s += t;
-            } while (t > 1);
-            const int gamma = i + s * d + (d < 0 ? -1 : 0);
-            const int lo = i < j ? i : j, hi = i < j ? j : i;
-            const int left = (lo == gamma) ? leaf0 + gamma : gamma;
-            const int right = (hi == gamma + 1) ? leaf0 + gamma + 1 : gamma + 1;
+            int left, right, lo, hi;
+            karras_node(s_keys, m, i, left, right, lo, hi);
             s_left[i] = left;
             s_right[i] = right;
             s_lo[i] = (short)lo;
@@ -1954,12 +1992,7 @@ __global__ __launch_bounds__(kMaxPrims) void build_kernel(const PrimIn* __restri
         P = prims[i];
         float inv[12];
         inverse_rows012(P.M, inv);
-        out_prims[6 * i + 0] = make_float4(inv[0], inv[1], inv[2], inv[3]);
-        out_prims[6 * i + 1] = make_float4(inv[4], inv[5], inv[6], inv[7]);
-        out_prims[6 * i + 2] = make_float4(inv[8], inv[9], inv[10], inv[11]);
-        out_prims[6 * i + 3] = make_float4(P.kd[0], P.kd[1], P.kd[2], P.spec);
-        out_prims[6 * i + 4] = make_float4(P.kr[0], P.kr[1], P.kr[2], __int_as_float((int)P.type));
-        out_prims[6 * i + 5] = make_float4(P.Le[0], P.Le[1], P.Le[2], 0.0f);
+        store_prim_record(out_prims + 6 * i, P, inv);
         // Shading frame of a FLAT primitive (rectangle, disk: object-space normal (0,1,0), kernel.cu:345,388): what the closest-hit
         // program computes from it on every hit -- N = normalize(TransformNormal(0,1,0)) (kernel.cu:428) and the tangent of
         // GetRayOnHemisphere for direction N, X = normalize(N.y - N.z, -N.x, N.x) (kernel.cu:105) -- depends on the primitive alone.

@@ -95,7 +95,10 @@ MultiGpuRenderer::MultiGpuRenderer(std::shared_ptr<Scene> scene, RenderMode rend
                 auto check = [&](int r, const char* what) {
                     if (r != RTGO_OK) throw std::runtime_error(std::string(what) + " failed (" + std::to_string(r) + "): " + rtgo_last_error(s->ctx));
                 };
-                check(rtgo_set_scene(s->ctx, records.data(), boxes.data(), static_cast<uint32_t>(records.size())), "rtgo_set_scene");
+                if (records.size() > RTGO_MAX_PRIMS)
+                    check(rtgo_set_large_scene(s->ctx, records.data(), boxes.data(), static_cast<uint32_t>(records.size())), "rtgo_set_large_scene");
+                else
+                    check(rtgo_set_scene(s->ctx, records.data(), boxes.data(), static_cast<uint32_t>(records.size())), "rtgo_set_scene");
                 check(rtgo_set_camera(s->ctx, eye, U, Vv, W), "rtgo_set_camera");
                 check(rtgo_set_background(s->ctx, rgb), "rtgo_set_background");
                 check(rtgo_set_lights(s->ctx, lights.data(), static_cast<int>(lights.size())), "rtgo_set_lights");

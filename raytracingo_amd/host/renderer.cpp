@@ -84,7 +84,11 @@ void Renderer::CreateShapes()
             boxes.push_back(primitive.GetAabb());
         }
     // BuildAccelerationStructure + BuildHitGroupRecords (renderer.cpp:514-611, 636-653)
-    Check(rtgo_set_scene(m_context, records.data(), boxes.data(), static_cast<uint32_t>(records.size())), "rtgo_set_scene");
+    // (beyond RTGO_MAX_PRIMS primitives: the scene is built and walked in global memory; the reference scenes stay within it)
+    if (records.size() > RTGO_MAX_PRIMS)
+        Check(rtgo_set_large_scene(m_context, records.data(), boxes.data(), static_cast<uint32_t>(records.size())), "rtgo_set_large_scene");
+    else
+        Check(rtgo_set_scene(m_context, records.data(), boxes.data(), static_cast<uint32_t>(records.size())), "rtgo_set_scene");
 }
 
 void Renderer::WriteLights()
