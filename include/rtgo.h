@@ -115,7 +115,8 @@ typedef struct rtgo_stats {
                                  launch was one of the launch-time trial's (the first launches of a job time the candidate
                                  (loop, structure) pairs -- same pixels either way -- and the fastest keeps the job), bit 4 the fast walk
                                  over the uniform grid instead of a tree, bit 5 the scene walked from global memory (a scene of
-                                 rtgo_set_large_scene; always with bit 2) */
+                                 rtgo_set_large_scene; always with bit 2), bit 6 path mode under the last-ray certificate (a path's last
+                                 ray tests the emitters and skips the room) */
     uint32_t launches_trial;  /* launches since rtgo_reset_stats that were trial launches */
 } rtgo_stats;
 

@@ -84,6 +84,11 @@ struct rtgo_ctx {
         int tree_spheres = 0;              // every primitive of the tree is a sphere
         int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
         float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
+        // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and
+        // for each (emitter, wall) pair k = 6 e + g the least y_g over the emitter's corners and the coefficients of the margin it
+        // has to exceed, K (emit_a R + emit_b) (last_ray_params)
+        int emit_n = 0;
+        float emit_ymin[6 * kMaxEmitters] = {}, emit_a[6 * kMaxEmitters] = {}, emit_b[6 * kMaxEmitters] = {};
         bool sane(uint32_t n) const { return n_fnodes >= 0 && n_fnodes <= 2 * (int)n - 1 && !(n_small > 0 && n_fnodes < 1); }
     } tree[2];                             // the structures of 36 % and 15 %
     bool have_alt = false;                 // tree[1] is a candidate: false when the two builds came out the same, or RTGO_BIG_PERCENT pins one
@@ -336,6 +341,7 @@ struct Knobs {
     bool debug = std::getenv("RTGO_DEBUG") != nullptr;              // a line per scene and launch on stderr
     bool no_frames = std::getenv("RTGO_NO_FRAMES") != nullptr;      // flat scenes compute N and the sampling tangent per hit
     bool no_cuboid = std::getenv("RTGO_NO_CUBOID") != nullptr;      // the build certifies no cuboids
+    bool no_last_emitter = std::getenv("RTGO_NO_LAST_EMITTER") != nullptr;   // launches go without the last-ray certificate
     bool pin_big = std::getenv("RTGO_BIG_PERCENT") != nullptr;      // one fast-walk structure, of big_percent (else 36 % and 15 %)
     unsigned int big_percent = env_uint("RTGO_BIG_PERCENT", 36);
     unsigned int max_wpe = env_uint("RTGO_MAX_WPE", 0);             // cap of the waves-per-SIMD variant; 0: by the work
@@ -844,6 +850,75 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
     return RTGO_OK;
 }
 
+// The scene half of the last-ray certificate (render_kernel: a path's last ray tests the emitters first and skips the up-front list; DESIGN.md
+// 3.2).  It holds when the up-front list is a certified room followed by nothing but the scene's emitters (material Le.x > 0.01, the
+// kernel's test), all of them rectangles, at most kMaxEmitters.  For each (emitter e, wall g) it records how far inside g's plane
+// e lies -- the least y_g over e's corners, e taken as the exact rectangle its fprims rows describe (their inverse, in double) -- and
+// the margin's coefficients.  Why the margin suffices: a wall is hit only where the ray approaches it (d.y_g < 0) from its inner side
+// (o.y_g > 0); y_g falls along the ray, so if y_g > 0 at the emitter's hit point P = o + t_e d the wall's t_w = -o.y_g / d.y_g is
+// beyond t_e and the wall cannot be the closest hit.  y_g(P) >= ymin - L * err_e, where err_e is how far the reference's test lets P
+// sit outside e (its u, v, and the plane offset o.y_e + t_e d.y_e, in e's object units) and L carries e's object units into y_g's
+// (ymax - ymin over the corners: the in-plane part, + |r1_g . e's y axis|).  The kernel's t_w > t_e then needs y_g(P) to exceed the
+// rounding of o.y_g, d.y_g and the quotient.  Each is a few float operations on terms <= |row|_1 (|o| + t |d|) + |w| <= |row|_1 3 R
+// + |w| (R: the launch's reach, as for cub_mu), <= 12 * 2^-24 of them; K = 64 * 2^-24 leaves five times that.  So the margin is
+// K (A R + B) with A = 3 (L max|row_e|_1 + |r1_g|_1), B = L (max|w_e| + 1) + |w_g| (the 1: u = px + 0.5 is rounded at 1's scale).
+static int emitter_cert(rtgo_ctx* c, const rtgo_prim* prims, uint32_t n, rtgo_ctx::FastTree& t)
+{
+    t.emit_n = 0;
+    if (t.list_cub != 2) return RTGO_OK;
+    std::vector<float4> fp((size_t)n * 4);
+    RTGO_HIP(c, hipMemcpyAsync(fp.data(), t.d_fprims, fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    auto orig_at = [&](int pos) { int o; std::memcpy(&o, &fp[4 * pos + 3].y, 4); return o; };
+    auto type_at = [&](int pos) { int o; std::memcpy(&o, &fp[4 * pos + 3].x, 4); return o; };
+    uint32_t emitters = 0;
+    for (uint32_t i = 0; i < n; ++i) emitters += prims[i].Le[0] > 0.01f ? 1u : 0u;
+    const int first = t.n_small + 6;
+    if (emitters == 0 || emitters > (uint32_t)kMaxEmitters || (int)n - first != (int)emitters) return RTGO_OK;
+    for (int k = 0; k < (int)emitters; ++k) {
+        const int o = orig_at(first + k);
+        if (o < 0 || o >= (int)n || !(prims[o].Le[0] > 0.01f) || type_at(first + k) != (int)RTGO_RECTANGLE) return RTGO_OK;
+    }
+    auto n1 = [](const float4& r) { return std::fabs((double)r.x) + std::fabs((double)r.y) + std::fabs((double)r.z); };
+    for (int e = 0; e < (int)emitters; ++e) {
+        const float4* R = &fp[4 * (first + e)];
+        // M = the inverse of the rows' 3x3 part: world = M (obj - w)
+        const double a[3][3] = {{R[0].x, R[0].y, R[0].z}, {R[1].x, R[1].y, R[1].z}, {R[2].x, R[2].y, R[2].z}};
+        const double w[3] = {R[0].w, R[1].w, R[2].w};
+        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+        if (!(std::fabs(det) > 1e-300) || !std::isfinite(det)) return RTGO_OK;
+        double M[3][3];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const int i1 = (j + 1) % 3, i2 = (j + 2) % 3, j1 = (i + 1) % 3, j2 = (i + 2) % 3;
+                M[i][j] = (a[i1][j1] * a[i2][j2] - a[i1][j2] * a[i2][j1]) / det;
+            }
+        const double n1e = std::max(n1(R[0]), std::max(n1(R[1]), n1(R[2])));
+        const double we = std::max(std::fabs(w[0]), std::max(std::fabs(w[1]), std::fabs(w[2]))) + 1.0;
+        for (int g = 0; g < 6; ++g) {
+            const float4 r1 = fp[4 * (t.n_small + g) + 1];
+            const double rg[3] = {r1.x, r1.y, r1.z};
+            double ymin = INFINITY, ymax = -INFINITY;
+            for (int k = 0; k < 4; ++k) {
+                const double ob[3] = {((k & 1) ? 0.5 : -0.5) - w[0], 0.0 - w[1], ((k & 2) ? 0.5 : -0.5) - w[2]};
+                double y = r1.w;
+                for (int i = 0; i < 3; ++i) y += rg[i] * (M[i][0] * ob[0] + M[i][1] * ob[1] + M[i][2] * ob[2]);
+                ymin = std::min(ymin, y);
+                ymax = std::max(ymax, y);
+            }
+            const double L = (ymax - ymin) + std::fabs(rg[0] * M[0][1] + rg[1] * M[1][1] + rg[2] * M[2][1]);
+            const double A = 3.0 * (L * n1e + n1(r1)), B = L * we + std::fabs((double)r1.w);
+            if (!(std::isfinite(ymin) && A < 1e30 && B < 1e30)) return RTGO_OK;
+            t.emit_ymin[6 * e + g] = (float)ymin;
+            t.emit_a[6 * e + g] = (float)A;
+            t.emit_b[6 * e + g] = (float)B;
+        }
+    }
+    t.emit_n = (int)emitters;
+    return RTGO_OK;
+}
+
 // the per-primitive checks of rtgo_set_scene and rtgo_set_large_scene (`what`: the entry point, for the message)
 static int check_prims(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n, const std::string& what)
 {
@@ -891,6 +966,7 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     if (aabbs) RTGO_HIP(c, hipMemcpyAsync(c->d_aabb, aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
     int meta[15];
     if (const int rc = build_fast_tree(c, n, aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, c->tree[0], meta)) return rc;
+    if (const int rc = emitter_cert(c, prims, n, c->tree[0])) return rc;
     c->tight.assign((size_t)n * 6, 0.0f);
     RTGO_HIP(c, hipMemcpyAsync(c->tight.data(), c->d_tight, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
@@ -903,6 +979,7 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
         // the alternative structure: big_frac 15 % (the canonical outputs, boxes and frames are rewritten with the same values)
         int m2[15];
         if (const int rc = build_fast_tree(c, n, 1, 0.15f, kn, c->tree[1], m2)) return rc;
+        if (const int rc = emitter_cert(c, prims, n, c->tree[1])) return rc;
         const rtgo_ctx::FastTree& t1 = c->tree[1];
         // (the same split of primitives = the same structure: nothing to try)
         c->have_alt = m2[0] == meta[0] && t1.sane(n) &&
@@ -1307,6 +1384,24 @@ static void walk_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool ca
     p.stack_depth = canon ? kStackDepth : ((ft.fast_depth > 0 && !use_grid) ? ft.fast_depth : 1) + 1;   // (+1: fast_tree writes the slot past the top before it knows whether it pushes)
 }
 
+// The launch half of the last-ray certificate (see emitter_cert): path mode, the fast walk over a tree, the room still certified at this
+// launch's reach (walk_params), a background of +0 in all three channels (a miss then pays what a non-emitter hit pays: compared as
+// bits), every emitter inside every wall by more than the margin at this reach, and max_depth >= 1 (the last ray is never a primary
+// ray: the pixel's "every primary ray missed" shortcut does not see it).  RTGO_NO_LAST_EMITTER: off.
+static void last_ray_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool path, bool canon, bool use_grid, const Knobs& kn, LaunchParams& p)
+{
+    p.emit_n = 0;
+    const float bg[3] = {p.bg.x, p.bg.y, p.bg.z};
+    uint32_t bg_bits[3];
+    std::memcpy(bg_bits, bg, sizeof bg_bits);
+    if (!path || canon || use_grid || kn.no_last_emitter || p.list_cub != 2 || p.max_depth < 1 || (bg_bits[0] | bg_bits[1] | bg_bits[2]) != 0u)
+        return;
+    const double K = 64.0 * 5.9604644775390625e-8, R = (double)c->guard_reach;
+    for (int k = 0; k < 6 * ft.emit_n; ++k)
+        if (!((double)ft.emit_ymin[k] > K * ((double)ft.emit_a[k] * R + (double)ft.emit_b[k]))) return;
+    p.emit_n = ft.emit_n;
+}
+
 // Scheduling: units of 64 paths = the N*N samples of `unit_px` neighbouring pixels of one row; the queue hands out STRIPS of
 // `grab` units side by side (<= 64 pixels) from the rectangle that can contain geometry.  Strips are long when there is
 // plenty of work (their pixel seeds are hashed once per strip) and short when units are scarce (small windows, one GPU's
@@ -1553,7 +1648,8 @@ static int enqueue(rtgo_ctx* c, RenderKernel kernel, const LaunchParams& p, cons
     c->ev_pending++;
     c->launches++;
     if (canon) c->launches_canonical++;
-    c->last_variant = (pk.stream ? 1u : 0u) | (pk.structure == 1 ? 2u : 0u) | (canon ? 4u : 0u) | (pk.trial_k >= 0 ? 8u : 0u) | (pk.structure == 2 ? 16u : 0u);
+    c->last_variant = (pk.stream ? 1u : 0u) | (pk.structure == 1 ? 2u : 0u) | (canon ? 4u : 0u) | (pk.trial_k >= 0 ? 8u : 0u) | (pk.structure == 2 ? 16u : 0u) |
+                      (p.emit_n > 0 ? 64u : 0u);
     return RTGO_OK;
 }
 
@@ -1607,6 +1703,7 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     if (const int rc = choose_candidate(c, f, p, nn, kn, canon, pk)) return rc;
     const bool use_alt = pk.structure == 1, use_grid = pk.structure == 2;
     walk_params(c, c->tree[use_alt ? 1 : 0], canon, use_grid, p);
+    last_ray_params(c, c->tree[use_alt ? 1 : 0], path, canon, use_grid, kn, p);
     uint32_t strip_px = 0;
     uint64_t units_hot = 0;
     if (const int rc = schedule(c, nn, r, p, strip_px, units_hot)) return rc;

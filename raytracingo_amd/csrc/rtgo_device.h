@@ -26,6 +26,7 @@ constexpr int kSampleTab = 256;     // samples per pixel whose start (LCG skip, 
 constexpr int kCamWords = 16;        // raygen constants in LDS (render_kernel's s_cam) ...
 constexpr int kCamWordsLean = 20;    // ... + the launch's two reciprocals in the 6-waves variant (a multiple of 4: s_tab follows)
 constexpr int kMaxLevels = 5;        // bounce records kept per path (maxTraceDepth <= 5)
+constexpr int kMaxEmitters = 4;      // emitters of the last-ray certificate (LaunchParams::emit_n); scenes with more go without it
 constexpr float kPi = 3.14159265358979323846f;  // M_PIf, sutil/vec_math.h:43
 
 struct v3 {
@@ -65,7 +66,7 @@ struct LaunchParams {
     int n_big_pairs;                // ... of which the first 2*n_big_pairs records are pairs of opposite rectangles (pair_test)
     int list_cub;                   // 1 / 2: the up-front list starts with three pairs certified as one box / one room (cuboid_range), 0: it does not
     float cub_mu;                   // cuboid_range's margin for this launch (object-space units of a face's y axis)
-    int tree_spheres;               // 1: every primitive of the fast walk's tree is a sphere (balls): leaves go straight to the sphere test
+    int tree_spheres;              // 1: every primitive of the fast walk's tree is a sphere (balls): leaves go straight to the sphere test
     GridParams grid;                // GRID instantiations: fnodes holds the grid instead of a tree
     const LightRec* lights;
     float4* accum;
@@ -113,6 +114,11 @@ struct LaunchParams {
 #endif
     v3 eye, U, V, Wv, bg;
     v3 bg_pixel;                     // ((0 + bg) + bg + ... N*N times) * (1/(N*N)) in float: the value of a pixel whose samples all miss
+    // Last-ray certificate (path mode; rtgo_capi.hip, emitter_cert and last_ray_params): the up-front list is a room followed by the
+    // scene's emitters and nothing else, each emitter inside every wall by more than a margin, and a miss pays the same +0 as a
+    // non-emitter hit.  A path's last ray then skips the room, and only the lanes that hit an emitter walk the tree (closest_hit_fast).
+    // emit_n: the emitters (fprims [n_small + 6, n_prims)); 0: off.
+    int emit_n;
 };
 
 // ---- float3 helpers, same operation order as sutil/vec_math.h ----------------------------------------------------
@@ -724,8 +730,10 @@ __device__ __forceinline__ bool box_fast(const float4 q0, const float4 q1, v3 id
 
 // The fast walk in three parts (closest_hit_fast below runs them back to back; an experiment of round 2 ran the middle one in another
 // lane than the other two: profiles/r02f/README.md).  fast_list: the up-front list, which also gives the ray its first closest-hit bound.
+// LAST, `last`: the lane's ray is the last of its path under the last-ray certificate (closest_hit_fast): it skips the room.
+template <bool LAST = false>
 __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, const float4* __restrict__ g_fprims, int n_small, int n_prims, int n_big_pairs,
-                                          int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best)
+                                          int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, bool last = false)
 {
     // the few "big" primitives (walls, floors; the whole scene when it is tiny) first.  The loop index is wave-uniform and
     // g_fprims is a read-only kernel argument, so the records arrive by scalar loads (s_load_dwordx4) into SGPRs: no LDS
@@ -733,7 +741,9 @@ __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, c
     // It also gives every ray a closest-hit bound before it enters the tree.
     if (list_cub != 0) {
         // the room's six walls (or one big box) as a cuboid, the rest of the list after them
-        cuboid_range<true>(g_fprims, s_fprims, n_small, list_cub == 1 ? cub_mu : INFINITY, list_cub == 1 ? -INFINITY : -cub_mu, o, d, tmin, best);
+        if (!LAST || __ballot(!last) != 0ull) {
+            if (!LAST || !last) cuboid_range<true>(g_fprims, s_fprims, n_small, list_cub == 1 ? cub_mu : INFINITY, list_cub == 1 ? -INFINITY : -cub_mu, o, d, tmin, best);
+        }
         leaf_range<true>(g_fprims, s_fprims, n_small + 6, n_prims - n_small - 6, 0, o, d, tmin, best);
     } else {
         leaf_range<true>(g_fprims, s_fprims, n_small, n_prims - n_small, n_big_pairs, o, d, tmin, best);
@@ -983,12 +993,17 @@ __device__ __forceinline__ bool fast_winner(const float4* __restrict__ s_fprims,
     return true;
 }
 
-template <bool GRID>
+// `last`: this lane traces the last ray of its path under the last-ray certificate (LaunchParams::emit_n).  Only an emitter can make
+// that ray's payload nonzero, and the certificate shows that no wall of the room can be met before an emitter.  So the lane skips the
+// room (fast_list), tests the emitters as the list always does, and, when it hits none, is done: no hit, payload = the background (+0,
+// like the term of a non-emitter hit).  When it hits one, the tree walks from `best` = that hit: the closest hit does not depend on the
+// order in which candidates are met (closer()).  LAST: the instantiation has this path at all (else `last` is ignored).
+template <bool GRID, bool LAST = false>
 __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims,
                                                  const float4* __restrict__ g_fprims, const GridParams grid,
  unsigned int* __restrict__ s_stack, int bshift,
                                                  int n_small, int n_prims, int n_big_pairs, int list_cub, float cub_mu, bool tree_spheres, v3 o, v3 d, float tmin, float tmax, Hit& out,
-                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests
+                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, bool last
 #ifdef RTGO_TIMELINE
                                                  , unsigned long long& tl_big, unsigned long long& tl_tree
 #endif
@@ -1001,16 +1016,17 @@ __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fn
     best.t = tmax;
     best.pos = -1;
     best.orig = -1;
-    fast_list(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best);
+    fast_list<LAST>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
+    const bool walk = !last || best.pos >= 0;
 #if defined(RTGO_FAST_COUNTERS) && RTGO_FAST_COUNTERS != 2
-    dbg_tests += (unsigned int)(n_prims - n_small);
+    dbg_tests += (unsigned int)(n_prims - n_small - (last ? 6 : 0));
 #endif
 #ifdef RTGO_TIMELINE
     const unsigned long long tl_s1 = wall_clock64() + (best.pos == 12345 ? 1 : 0);
     tl_big += tl_s1 - tl_s0;
 #endif
     if constexpr (GRID) fast_grid(s_fnodes, s_fprims, grid, tree_spheres, o, d, tmin, best, dbg_boxes, dbg_tests);
-    else fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
+    else if (!LAST || walk) fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
 #ifdef RTGO_TIMELINE
     tl_tree += wall_clock64() + (best.pos == 12345 ? 1 : 0) - tl_s1;
 #endif
@@ -1324,6 +1340,8 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     // where they are used (opaque_lane, s_cam) instead of being held in VGPRs through every ray loop -- what fits 80 VGPRs without
     // scratch.  The other variants keep the hoisted values, which their budgets afford and which are cheaper.
     constexpr bool LEAN = (WPE >= 6);
+    // path mode, fast walk over a tree: a path's last ray takes the emitters-first walk when the launch has the certificate (p.emit_n)
+    constexpr bool LASTRAY = PATH && !STATS && !GRID;
     constexpr bool SEEDS = kernel_has_seed_pass(STATS, WPE, STREAM);
     auto lane_index = [&]() { return LEAN ? opaque_lane() : (unsigned int)lane; };
     auto frame_ratio = [&]() { return LEAN ? s_cam[16] : 1.0f / (float)(p.frame + 1); };

@@ -5,8 +5,9 @@
                 c_rays += 1;
                 bool hit;
                 if constexpr (STATS) hit = closest_hit<COUNT>(s_nodes, s_prims, s_stack, bshift, ro, rd, tmin, tmax, h, c_nodes, c_tests);
-                else hit = closest_hit_fast<GRID>(s_nodes, s_prims, g_fprims, p.grid,
-                                            s_stack4, bshift, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, h, c_nodes, c_tests
+                else hit = closest_hit_fast<GRID, LASTRAY>(s_nodes, s_prims, g_fprims, p.grid,
+                                            s_stack4, bshift, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, h, c_nodes, c_tests,
+                                            LASTRAY && depth == p.max_depth && p.emit_n != 0
 #ifdef RTGO_TIMELINE
                                             , tl_big, tl_tree
 #endif
@@ -21,8 +22,8 @@
                     // (this lane's canonical stack is idle here: its own 8-byte slots serve as the fast walk's one-word entries)
                     // (RTGO_TREE=2 hands this launch the grid in p.fnodes: p.grid.n_cells > 0 then)
                     const bool hitf = p.grid.n_cells > 0
-                        ? closest_hit_fast<true>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1)
-                        : closest_hit_fast<false>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1);
+                        ? closest_hit_fast<true>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1, false)
+                        : closest_hit_fast<false>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1, false);
                     const bool same = hit == hitf && (!hit || (h.t == hf.t && h.prim == hf.prim && h.n.x == hf.n.x && h.n.y == hf.n.y && h.n.z == hf.n.z));
                     if (!same) {
                         const unsigned int slot = atomicAdd(reinterpret_cast<unsigned int*>(p.cmp), 1u);
