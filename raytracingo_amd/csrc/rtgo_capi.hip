@@ -4,10 +4,12 @@
 #include "../../include/rtgo.h"
 #include "rtgo_device.h"
 #include "rtgo_large.h"
+#include "rtgo_owners.h"
 #include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +37,89 @@ struct WhittedMeshInfo {
     bool clustered;            // beyond kMaxTriangles triangles: a mid level over clusters (rtgo_whitted_big.h)
 };
 
+// The analytic scene (rtgo_set_scene, rtgo_set_large_scene): replaced as a whole, by assigning a fresh one
+struct AnalyticScene {
+    // The third structure of the trial (rtgo_ctx::Trial): a uniform grid over structure 0's small primitives (rtgo::fast_grid), built by
+    // the host from the boxes build_kernel reports.  Scenes of many small primitives spread evenly (balls: 256 spheres in a room) walk it
+    // in a third of the tree's instructions; where it is slower the trial drops it after two launches.
+    struct Grid {
+        DeviceArray<unsigned char> d;      // [table: n_cells words, 0 = empty cell, else 1 + its record][records: 32 B per listing cell, its box
+                                           // and (first item | count << 16)][items: 16-bit positions into d_fprims] (GridParams' offsets)
+        int n_nodes = 0;                   // its size in 32-byte units (what LaunchParams::n_fnodes counts)
+        int entries = 0;                   // list entries (rtgo_debug_grid)
+        rtgo::GridParams gp = {};
+        float reach_max = 0.0f;            // the pad of the binning covers the walk's rounding for rays that start within this reach
+        bool have = false;
+    } grid;
+    struct FastTree {                      // what build_kernel makes for one big_frac
+        DeviceArray<float4> d_fnodes;      // collapsed LBVH of the fast walk
+        DeviceArray<float4> d_fprims;      // Morton-ordered traversal records of the fast walk
+        int fast_depth = 0, n_small = 0, n_fnodes = 0;   // its depth, primitives (the rest are tested up front) and nodes
+        int cuboid_groups = 0;             // certified groups in the scene (leaves + the list's)
+        int tree_spheres = 0;              // every primitive of the tree is a sphere
+        int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
+        float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
+        // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and
+        // for each (emitter, wall) pair k = 6 e + g the least y_g over the emitter's corners and the coefficients of the margin it
+        // has to exceed, K (emit_a R + emit_b) (last_ray_params)
+        int emit_n = 0;
+        float emit_ymin[6 * kMaxEmitters] = {}, emit_a[6 * kMaxEmitters] = {}, emit_b[6 * kMaxEmitters] = {};
+        bool sane(uint32_t n) const { return n_fnodes >= 0 && n_fnodes <= 2 * (int)n - 1 && !(n_small > 0 && n_fnodes < 1); }
+    } tree[2];                             // the structures of 36 % and 15 %
+    bool have_alt = false;                 // tree[1] is a candidate: false when the two builds came out the same, or RTGO_BIG_PERCENT pins one
+    uint32_t n_prims = 0;                  // 0: no scene (set last, once the build succeeded)
+    DeviceArray<PrimIn> d_prims_in;
+    DeviceArray<float> d_aabb;
+    DeviceArray<float4> d_nodes, d_prims;
+    DeviceArray<float4> d_frames;          // shading frames of the flat primitives (2 float4 per primitive, SBT order)
+    bool large = false;                    // the scene came from rtgo_set_large_scene: d_nodes / d_prims / d_aabb only, walked from global memory
+    int lbvh_depth = 0;
+    float bounds[6] = {0, 0, 0, 0, 0, 0};  // tight world bounds of the scene (min xyz, max xyz)
+    // far-field guard (rtgo_launch): per sphere / cylinder its centre and smax / smin^2 of its model matrix' axis scales -- the
+    // reported hit of a quadric seen from distance D lies up to ~2^-25 D^2 smax / smin^2 off its surface (b^2 - 4ac cancels)
+    struct Quadric { float c[3], w; };
+    std::vector<Quadric> quadrics;
+    DeviceArray<float> d_tight;            // the fast walk's box of every primitive (device), and its host copy
+    std::vector<float> tight;
+};
+
+// An instanced scene's top level (rtgo_whitted_set_instances replaces it alone)
+struct WhittedTop {
+    DeviceArray<float4> recs;
+    DeviceArray<whitted::InstWalk> inst;       // in the top level's leaf order
+    DeviceArray<whitted::InstShade> shade;     // in the caller's order
+    int n_recs = 0, n_instances = 0;
+};
+
+// The whitted triangle path's scene (rtgo_whitted.h; rtgo_whitted_set_mesh, rtgo_whitted_set_scene): replaced as a whole
+struct WhittedMesh {
+    DeviceArray<float> positions, normals;
+    DeviceArray<float> texcoords;              // 2 floats per vertex, or empty
+    DeviceArray<unsigned int> indices, tri_material;
+    DeviceArray<whitted::Pbr> materials;
+    // textures: per material its three texel arrays, the table that points into them, and its device copy (empty while no material
+    // has a texture)
+    std::vector<std::array<DeviceArray<uchar4>, 3>> texels;
+    std::vector<whitted::MatTex> mat_tex_host;
+    DeviceArray<whitted::MatTex> mat_tex;
+    DeviceArray<float4> nodes;
+    DeviceArray<float4> recs, tris;            // the walk's records (4 float4 each) and the triangles in Morton order (3 float4 each)
+    DeviceArray<uint4> qrecs;                  // the compact form: quantised records, (vertex indices | triangle index) per triangle
+    DeviceArray<uint2> tidx;
+    DeviceArray<int> scratch;
+    int n_vertices = 0;
+    v3 grid_lo{0, 0, 0}, grid_step{0, 0, 0};
+    int n_recs = 0, walk_depth = 0;
+    int triangles = 0, n_materials = 0;        // triangles = 0: no mesh
+    // an instanced scene (rtgo_whitted_set_scene): the mesh buffers above hold every mesh back to back in object space (nodes,
+    // scratch: the largest mesh's build), plus the top level
+    bool instanced = false;
+    std::vector<WhittedMeshInfo> meshes;
+    int mesh_depth = 0;                        // the deepest mesh walk
+    WhittedTop top;
+    DeviceArray<int4> clusters;                // the clustered meshes' cluster tables (InstParams::clusters), or empty when there are none
+};
+
 struct rtgo_ctx {
     int device = 0;
     int num_cus = 0;
@@ -46,6 +131,33 @@ struct rtgo_ctx {
     hipEvent_t ev_start[kEvRing] = {}, ev_stop[kEvRing] = {};
     int ev_head = 0, ev_pending = 0;
     unsigned char ev_tag[kEvRing] = {};    // a trial launch of candidate k carries k + 1, any other launch 0 (see `trial` below)
+    DeviceArray<unsigned int> d_queue;     // two sets of work-queue heads: a launch counts on one and zeroes the other for the next
+    int queue_set = 0;
+    DeviceArray<unsigned long long> d_counters;   // 8 x u64
+    DeviceArray<LightRec> d_lights;
+    int n_lights = 0;
+    DeviceArray<int> d_meta;               // build_kernel's meta words (one build at a time)
+    int leaf_budget = kDefaultLeafBudget;
+    bool have_camera = false;
+    v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};
+    // stats (rtgo_get_stats)
+    float guard_reach = 0.0f, guard_quadric = 0.0f;   // of the last launch
+    unsigned long long rays_culled = 0;       // since rtgo_reset_stats (host arithmetic: the cold pixels of each launch x N*N)
+    uint32_t launches_canonical = 0;          // since rtgo_reset_stats
+    uint32_t launches_trial = 0, last_variant = 0;
+    float total_ms = 0.0f, last_ms = 0.0f;
+    uint32_t launches = 0;
+    uint32_t seeds_last = 0;                  // rtgo_debug_seeds: 1 = the last launch read pre-hashed seeds, 2 = it wrote the next frame's
+#ifdef RTGO_CMPWALK
+    DeviceArray<float> d_cmp;                 // diagnostic build: disagreements between the two walks
+#endif
+#ifdef RTGO_TIMELINE
+    DeviceArray<unsigned long long> d_timeline;   // diagnostic build: 8 x u64 per wave
+    unsigned int timeline_waves = 0;
+#endif
+
+    AnalyticScene scene;
+    // ---- launch caches of the analytic path
     // Frames of several passes per pixel (> 16 spp) have two kernels with bitwise the same output: lanes streaming through their
     // samples (open scenes, where path lengths differ: plateau 3840x2160 spp 256 18.8 ms against 20.5) or the wave running pass by
     // pass in lock-step (closed scenes, where nearly every path runs to the depth limit and regeneration only costs: cornell spp 64
@@ -64,132 +176,43 @@ struct rtgo_ctx {
         float best[8] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
         int choice = -1;                   // index of the winning candidate, -1 = undecided
     } trial;
-    // The third structure of the trial: a uniform grid over structure 0's small primitives (rtgo::fast_grid), built by the host from
-    // the boxes build_kernel reports.  Scenes of many small primitives spread evenly (balls: 256 spheres in a room) walk it in a third of
-    // the tree's instructions; where it is slower the trial drops it after two launches.
-    struct Grid {
-        void* d = nullptr;                 // [table: n_cells words, 0 = empty cell, else 1 + its record][records: 32 B per listing cell, its box
-                                           // and (first item | count << 16)][items: 16-bit positions into d_fprims] (GridParams' offsets)
-        int n_nodes = 0;                   // its size in 32-byte units (what LaunchParams::n_fnodes counts)
-        int entries = 0;                   // list entries (rtgo_debug_grid)
-        rtgo::GridParams gp = {};
-        float reach_max = 0.0f;            // the pad of the binning covers the walk's rounding for rays that start within this reach
-        bool have = false;
-    } grid;
-    struct FastTree {                      // what build_kernel makes for one big_frac
-        float4* d_fnodes = nullptr;        // collapsed LBVH of the fast walk
-        float4* d_fprims = nullptr;        // Morton-ordered traversal records of the fast walk
-        int fast_depth = 0, n_small = 0, n_fnodes = 0;   // its depth, primitives (the rest are tested up front) and nodes
-        int cuboid_groups = 0;             // certified groups in the scene (leaves + the list's)
-        int tree_spheres = 0;              // every primitive of the tree is a sphere
-        int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
-        float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
-        // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and
-        // for each (emitter, wall) pair k = 6 e + g the least y_g over the emitter's corners and the coefficients of the margin it
-        // has to exceed, K (emit_a R + emit_b) (last_ray_params)
-        int emit_n = 0;
-        float emit_ymin[6 * kMaxEmitters] = {}, emit_a[6 * kMaxEmitters] = {}, emit_b[6 * kMaxEmitters] = {};
-        bool sane(uint32_t n) const { return n_fnodes >= 0 && n_fnodes <= 2 * (int)n - 1 && !(n_small > 0 && n_fnodes < 1); }
-    } tree[2];                             // the structures of 36 % and 15 %
-    bool have_alt = false;                 // tree[1] is a candidate: false when the two builds came out the same, or RTGO_BIG_PERCENT pins one
-    // scene
-    uint32_t n_prims = 0;
-    PrimIn* d_prims_in = nullptr;
-    float* d_aabb = nullptr;
-    float4* d_nodes = nullptr;
-    float4* d_prims = nullptr;
-    float4* d_frames = nullptr;   // shading frames of the flat primitives (2 float4 per primitive, SBT order)
-    bool large = false;           // the scene came from rtgo_set_large_scene: d_nodes / d_prims / d_aabb only, walked from global memory
-    int* d_meta = nullptr;        // build_kernel's meta words (one build at a time)
-    int lbvh_depth = 0;
-    float bounds[6] = {0, 0, 0, 0, 0, 0};  // tight world bounds of the scene (min xyz, max xyz)
-    // far-field guard (rtgo_launch): per sphere / cylinder its centre and smax / smin^2 of its model matrix' axis scales -- the
-    // reported hit of a quadric seen from distance D lies up to ~2^-25 D^2 smax / smin^2 off its surface (b^2 - 4ac cancels)
-    struct Quadric { float c[3], w; };
-    std::vector<Quadric> quadrics;
-    float guard_reach = 0.0f, guard_quadric = 0.0f;   // of the last launch (rtgo_stats)
-    float* d_tight = nullptr;              // the fast walk's box of every primitive (device), and its host copy
-    std::vector<float> tight;
-    // per-strip mask of the scene's screen rectangle (LaunchParams::hot_mask), kept until the launch geometry changes
-    unsigned int* d_mask = nullptr;
-    size_t mask_capacity = 0;              // words
-    // pinned staging for its upload, two slots used in turn with an event each: a camera change (every frame of an interactive
-    // drag) rebuilds the mask, and the upload must not make the host wait for the stream
-    unsigned int* h_mask[2] = {nullptr, nullptr};
-    size_t h_mask_capacity[2] = {0, 0};
-    hipEvent_t mask_copied[2] = {nullptr, nullptr};
-    int mask_slot = 0;
-    std::vector<uint32_t> mask_key;        // what the cached mask was built for
-    bool mask_all_hot = true;
-    unsigned long long mask_cold_pixels = 0;
-    int leaf_budget = kDefaultLeafBudget;
-    LightRec* d_lights = nullptr;
-    int n_lights = 0;
-    bool have_camera = false;
-    v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};
-    // output
-    float4* d_accum = nullptr;
-    uchar4* d_image = nullptr;
-    size_t pixels = 0;
-    bool own_output = false;
-    // queue + counters
-    unsigned int* d_queue = nullptr;          // two sets of work-queue heads: a launch counts on one and zeroes the other for the next
-    int queue_set = 0;
-    // next frame's pixel seeds (LaunchParams::seeds): two buffers, a launch reads one and writes the other.  seeds_ok: the buffer
-    // seeds_read holds frame seeds_frame's seeds for the strip layout seeds_key (written by the last launch on this context)
-    unsigned int* d_seeds[2] = {nullptr, nullptr};
-    size_t seeds_capacity = 0;                // words of each
-    int seeds_read = 0;
-    bool seeds_ok = false;
-    uint32_t seeds_frame = 0;
-    std::vector<uint32_t> seeds_key;
-    uint32_t seeds_last = 0;                  // rtgo_debug_seeds: 1 = the last launch read pre-hashed seeds, 2 = it wrote the next frame's
-    unsigned long long rays_culled = 0;       // since rtgo_reset_stats (host arithmetic: the cold pixels of each launch x N*N)
-    uint32_t launches_canonical = 0;          // since rtgo_reset_stats
-    uint32_t launches_trial = 0, last_variant = 0;   // (rtgo_stats)
-    unsigned long long* d_counters = nullptr;  // 8 x u64
-#ifdef RTGO_CMPWALK
-    float* d_cmp = nullptr;                    // diagnostic build: disagreements between the two walks
-#endif
-#ifdef RTGO_TIMELINE
-    unsigned long long* d_timeline = nullptr;  // diagnostic build: 8 x u64 per wave
-    unsigned int timeline_waves = 0;
-#endif
-    float total_ms = 0.0f, last_ms = 0.0f;
-    uint32_t launches = 0;
-    // the whitted triangle path (rtgo_whitted.h)
-    float* w_positions = nullptr;
-    float* w_normals = nullptr;
-    unsigned int* w_indices = nullptr;
-    unsigned int* w_tri_material = nullptr;
-    whitted::Pbr* w_materials = nullptr;
-    whitted::PointLight* w_lights = nullptr;
-    float* w_texcoords = nullptr;              // 2 floats per vertex, or null
-    whitted::MatTex* w_mat_tex = nullptr;      // device copy of w_mat_tex_host, or null while no material has a texture
-    std::vector<whitted::MatTex> w_mat_tex_host;
-    std::vector<void*> w_texels;               // device texel arrays the table points into (freed with the mesh)
-    float4* w_nodes = nullptr;
-    float4* w_recs = nullptr;              // the walk's records (4 float4 each) and the triangles in Morton order (3 float4 each)
-    float4* w_tris = nullptr;
-    uint4* w_qrecs = nullptr;              // the compact form: quantised records, (vertex indices | triangle index) per triangle
-    uint2* w_tidx = nullptr;
-    int w_n_vertices = 0;
-    v3 w_grid_lo{0, 0, 0}, w_grid_step{0, 0, 0};
-    int* w_scratch = nullptr;
-    unsigned int* w_tile_counters = nullptr;   // two sets of tile-queue heads: a launch counts on one and zeroes the other
-    int w_n_recs = 0, w_walk_depth = 0, w_launch_parity = 0;
-    int w_triangles = 0, w_n_lights = 0, w_n_materials = 0;
+    // per-strip mask of the scene's screen rectangle (LaunchParams::hot_mask), kept until the launch geometry changes; its buffers
+    // outlive a scene
+    struct HotMask {
+        DeviceArray<unsigned int> d;
+        // pinned staging for its upload, two slots used in turn with an event each: a camera change (every frame of an interactive
+        // drag) rebuilds the mask, and the upload must not make the host wait for the stream
+        PinnedArray<unsigned int> h[2];
+        LazyEvent copied[2];
+        int slot = 0;
+        std::vector<uint32_t> key;         // what the cached mask was built for
+        bool all_hot = true;
+        unsigned long long cold_pixels = 0;
+    } mask;
+    // next frame's pixel seeds (LaunchParams::seeds): two buffers, a launch reads one and writes the other.  ok: the buffer `read`
+    // holds frame `frame`'s seeds for the strip layout `key` (written by the last launch on this context)
+    struct Seeds {
+        DeviceArray<unsigned int> d[2];
+        int read = 0;
+        bool ok = false;
+        uint32_t frame = 0;
+        std::vector<uint32_t> key;
+    } seeds;
+    // ---- output: the context's own buffers (rtgo_resize) or the caller's (rtgo_bind_output)
+    struct Output {
+        DeviceArray<float4> own_accum;
+        DeviceArray<uchar4> own_image;
+        float4* accum = nullptr;           // what launches write
+        uchar4* image = nullptr;
+        size_t pixels = 0;
+    } out;
+    // ---- the whitted triangle path: the scene, and what outlives it (lights, tile-queue heads, miss colour)
+    WhittedMesh wm;
+    DeviceArray<whitted::PointLight> w_lights;
+    int w_n_lights = 0;
+    DeviceArray<unsigned int> w_tile_counters;   // two sets of tile-queue heads: a launch counts on one and zeroes the other
+    int w_launch_parity = 0;
     v3 w_miss{0, 0, 0};
-    // an instanced scene (rtgo_whitted_set_scene): the mesh buffers above hold every mesh back to back in object space (w_nodes,
-    // w_scratch: the largest mesh's build), plus the top level
-    bool w_instanced = false;
-    std::vector<WhittedMeshInfo> w_meshes;
-    int w_mesh_depth = 0;                      // the deepest mesh walk
-    float4* w_top_recs = nullptr;
-    whitted::InstWalk* w_inst = nullptr;       // in the top level's leaf order
-    whitted::InstShade* w_inst_shade = nullptr;   // in the caller's order
-    int w_n_top_recs = 0, w_n_instances = 0;
-    int4* w_clusters = nullptr;                // the clustered meshes' cluster tables (InstParams::clusters), or null when there are none
     std::string err;
 };
 
@@ -254,13 +277,6 @@ static int fail(rtgo_ctx* c, int code, const std::string& msg)
     return code;
 }
 
-template <class T>
-static void release(T*& d)
-{
-    (void)hipFree(d);
-    d = nullptr;
-}
-
 #define RTGO_HIP(ctx, call)                                                                                       \
     do {                                                                                                          \
         hipError_t e_ = (call);                                                                                   \
@@ -287,6 +303,23 @@ static int harvest_events(rtgo_ctx* c, int count)
             c->ev_tag[slot] = 0;
         }
     }
+    return RTGO_OK;
+}
+
+// One launch of either path between the two events of the ring's next slot on the context's stream (the oldest pair read back
+// first when the ring is full), counted.  `launch` enqueues the kernel and returns an RTGO code; `slot`: the ring slot it took.
+template <class Launch>
+static int timed_launch(rtgo_ctx* c, int& slot, Launch&& launch)
+{
+    if (c->ev_pending == rtgo_ctx::kEvRing)
+        if (const int rc = harvest_events(c, 1)) return rc;
+    slot = c->ev_head;
+    RTGO_HIP(c, hipEventRecord(c->ev_start[slot], c->stream));
+    if (const int rc = launch()) return rc;
+    RTGO_HIP(c, hipEventRecord(c->ev_stop[slot], c->stream));
+    c->ev_head = (c->ev_head + 1) % rtgo_ctx::kEvRing;
+    c->ev_pending++;
+    c->launches++;
     return RTGO_OK;
 }
 
@@ -419,12 +452,13 @@ extern "C" int rtgo_debug_seeds(rtgo_ctx* c, uint32_t* out)
 extern "C" int rtgo_debug_grid(rtgo_ctx* c, int32_t out[6])
 {
     if (!c || !out) return RTGO_E_INVALID;
-    out[0] = c->grid.have ? 1 : 0;
-    out[1] = c->grid.gp.nx;
-    out[2] = c->grid.gp.ny;
-    out[3] = c->grid.gp.nz;
-    out[4] = c->grid.entries;
-    out[5] = c->grid.n_nodes * 32;
+    const AnalyticScene::Grid& g = c->scene.grid;
+    out[0] = g.have ? 1 : 0;
+    out[1] = g.gp.nx;
+    out[2] = g.gp.ny;
+    out[3] = g.gp.nz;
+    out[4] = g.entries;
+    out[5] = g.n_nodes * 32;
     return RTGO_OK;
 }
 
@@ -432,11 +466,11 @@ extern "C" int rtgo_debug_grid(rtgo_ctx* c, int32_t out[6])
 // diagnostic build only (tools/cmp_walks.py): rays on which the canonical and the fast walk disagreed since the last call
 extern "C" int rtgo_debug_cmpwalk(rtgo_ctx* c, void* host, size_t bytes)
 {
-    if (!c || !c->d_cmp) return -1;
+    if (!c || !c->d_cmp.get()) return -1;
     if (rtgo_sync(c)) return -1;
     const size_t n = 256 * 16 * sizeof(float);
-    if (hipMemcpy(host, c->d_cmp, n < bytes ? n : bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (hipMemset(c->d_cmp, 0, n) != hipSuccess) return -1;
+    if (hipMemcpy(host, c->d_cmp.get(), n < bytes ? n : bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemset(c->d_cmp.get(), 0, n) != hipSuccess) return -1;
     if (hipStreamSynchronize(nullptr) != hipSuccess) return -1;
     return 0;
 }
@@ -446,10 +480,10 @@ extern "C" int rtgo_debug_cmpwalk(rtgo_ctx* c, void* host, size_t bytes)
 // diagnostic build only (tools/timeline.py): per-wave records of the last launch; returns the number of waves
 extern "C" int rtgo_debug_timeline(rtgo_ctx* c, void* host, size_t bytes)
 {
-    if (!c || !c->d_timeline) return -1;
+    if (!c || !c->d_timeline.get()) return -1;
     if (rtgo_sync(c)) return -1;
     const size_t n = (size_t)c->timeline_waves * 128;
-    if (hipMemcpy(host, c->d_timeline, n < bytes ? n : bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(host, c->d_timeline.get(), n < bytes ? n : bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (int)c->timeline_waves;
 }
 #endif
@@ -501,13 +535,13 @@ int rtgo_create(int device, rtgo_ctx** out)
         err = hipEventCreate(&c->ev_start[i]);
         if (err == hipSuccess) err = hipEventCreate(&c->ev_stop[i]);
     }
-    if (err == hipSuccess) err = hipMalloc(&c->d_queue, 2 * kQueues * kQueueStride * sizeof(unsigned int));
-    if (err == hipSuccess) err = hipMemset(c->d_queue, 0, 2 * kQueues * kQueueStride * sizeof(unsigned int));
-    if (err == hipSuccess) err = hipMalloc(&c->d_counters, 8 * sizeof(unsigned long long));
-    if (err == hipSuccess) err = hipMemset(c->d_counters, 0, 8 * sizeof(unsigned long long));
-    if (err == hipSuccess) err = hipMalloc(&c->d_lights, kMaxLights * sizeof(LightRec));
-    if (err == hipSuccess) err = hipMemset(c->d_lights, 0, kMaxLights * sizeof(LightRec));
-    if (err == hipSuccess) err = hipMalloc(&c->d_meta, 16 * sizeof(int));
+    if (err == hipSuccess) err = c->d_queue.alloc(2 * kQueues * kQueueStride);
+    if (err == hipSuccess) err = hipMemset(c->d_queue.get(), 0, 2 * kQueues * kQueueStride * sizeof(unsigned int));
+    if (err == hipSuccess) err = c->d_counters.alloc(8);
+    if (err == hipSuccess) err = hipMemset(c->d_counters.get(), 0, 8 * sizeof(unsigned long long));
+    if (err == hipSuccess) err = c->d_lights.alloc(kMaxLights);
+    if (err == hipSuccess) err = hipMemset(c->d_lights.get(), 0, kMaxLights * sizeof(LightRec));
+    if (err == hipSuccess) err = c->d_meta.alloc(16);
     // the megakernel may use most of the 160 KiB LDS of a CU
     const int max_lds = 160 * 1024;
     for (const RenderKernelEntry& e : kRenderKernels)
@@ -532,107 +566,12 @@ int rtgo_create(int device, rtgo_ctx** out)
     return RTGO_OK;
 }
 
-// the pre-hashed pixel seeds (rtgo_set_scene, rtgo_resize, rtgo_destroy)
-static void free_seeds(rtgo_ctx* c)
-{
-    release(c->d_seeds[0]);
-    release(c->d_seeds[1]);
-    c->seeds_capacity = 0;
-    c->seeds_ok = false;
-}
-
-// the scene's device buffers: both fast-walk structures, the grid, the canonical LBVH, boxes and frames (rtgo_set_scene, rtgo_destroy)
-static void free_scene(rtgo_ctx* c)
-{
-    for (rtgo_ctx::FastTree& t : c->tree) {
-        release(t.d_fnodes);
-        release(t.d_fprims);
-        t = rtgo_ctx::FastTree();
-    }
-    c->have_alt = false;
-    release(c->grid.d);
-    c->grid = rtgo_ctx::Grid();
-    release(c->d_prims_in);
-    release(c->d_aabb);
-    release(c->d_nodes);
-    release(c->d_prims);
-    release(c->d_frames);
-    release(c->d_tight);
-    c->n_prims = 0;
-    c->large = false;
-    free_seeds(c);
-}
-
-// the output buffers, when the context owns them (rtgo_resize, rtgo_bind_output, rtgo_destroy)
-static void free_output(rtgo_ctx* c)
-{
-    if (c->own_output) {
-        release(c->d_accum);
-        release(c->d_image);
-    }
-    c->d_accum = nullptr;
-    c->d_image = nullptr;
-    c->own_output = false;
-    c->pixels = 0;
-}
-
-// an instanced scene's top level (rtgo_whitted_set_instances replaces it alone)
-static void free_top(rtgo_ctx* c)
-{
-    release(c->w_top_recs);
-    release(c->w_inst);
-    release(c->w_inst_shade);
-    c->w_n_top_recs = 0;
-    c->w_n_instances = 0;
-}
-
-// the whitted scene's device buffers (rtgo_whitted_set_mesh, rtgo_whitted_set_scene, rtgo_destroy; the lights and tile-queue heads
-// outlive a scene)
-static void free_mesh(rtgo_ctx* c)
-{
-    release(c->w_positions);
-    release(c->w_normals);
-    release(c->w_indices);
-    release(c->w_tri_material);
-    release(c->w_materials);
-    release(c->w_texcoords);
-    release(c->w_mat_tex);
-    for (void* t : c->w_texels) (void)hipFree(t);
-    c->w_texels.clear();
-    c->w_mat_tex_host.clear();
-    release(c->w_nodes);
-    release(c->w_recs);
-    release(c->w_tris);
-    release(c->w_qrecs);
-    release(c->w_tidx);
-    release(c->w_scratch);
-    free_top(c);
-    release(c->w_clusters);
-    c->w_meshes.clear();
-    c->w_instanced = false;
-    c->w_mesh_depth = 0;
-    c->w_triangles = 0;
-}
-
+// (the context's buffers are released by its owners, when `delete c` runs)
 int rtgo_destroy(rtgo_ctx* c)
 {
     if (!c) return RTGO_OK;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    free_scene(c);
-    (void)hipFree(c->d_meta);
-    (void)hipFree(c->d_lights);
-    free_output(c);
-    (void)hipFree(c->d_queue);
-    (void)hipFree(c->d_counters);
-    (void)hipFree(c->d_mask);
-    for (int k = 0; k < 2; ++k) {
-        if (c->h_mask[k]) (void)hipHostFree(c->h_mask[k]);
-        if (c->mask_copied[k]) (void)hipEventDestroy(c->mask_copied[k]);
-    }
-    free_mesh(c);
-    (void)hipFree(c->w_lights);
-    (void)hipFree(c->w_tile_counters);
     for (int i = 0; i < rtgo_ctx::kEvRing; ++i) {
         if (c->ev_start[i]) (void)hipEventDestroy(c->ev_start[i]);
         if (c->ev_stop[i]) (void)hipEventDestroy(c->ev_stop[i]);
@@ -654,17 +593,18 @@ int rtgo_set_stream(rtgo_ctx* c, void* hip_stream)
 }
 
 // The uniform grid of rtgo::fast_grid over structure 0's small primitives (fprims [0, n_small)), from the boxes the fast walk culls
-// with (c->tight: build_kernel's, SBT order).  Every box is grown by `pad` before it is binned, and fast_grid stops `pad / 2` (in t)
+// with (scene.tight: build_kernel's, SBT order).  Every box is grown by `pad` before it is binned, and fast_grid stops `pad / 2` (in t)
 // late: the walk's own rounding (entry point, 96 accumulated steps: <= ~2e-5 of the rays' reach) stays an order of magnitude inside.
 // Cells: <= 32 per axis; table, cell records and lists within 40 KB of LDS; no grid for fewer than 64 small primitives (RTGO_GRID_MIN) or when
 // every resolution with at least half as many cells as primitives lists more than 3 entries per primitive (RTGO_GRID_MAX_DUP; a few big shapes among small ones: the tree's job).
 static int build_grid(rtgo_ctx* c, uint32_t n, const Knobs& kn)
 {
-    c->grid.have = false;
-    const int ns = c->tree[0].n_small;
+    AnalyticScene& sc = c->scene;
+    sc.grid.have = false;
+    const int ns = sc.tree[0].n_small;
     if (ns < (int)kn.grid_min) return RTGO_OK;
     std::vector<float4> fp((size_t)n * 4);
-    RTGO_HIP(c, hipMemcpyAsync(fp.data(), c->tree[0].d_fprims, fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(fp.data(), sc.tree[0].d_fprims.get(), fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     std::vector<const float*> box((size_t)ns);
     float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f}, scene_reach = 0.0f;
@@ -672,13 +612,13 @@ static int build_grid(rtgo_ctx* c, uint32_t n, const Knobs& kn)
         int orig;
         std::memcpy(&orig, &fp[4 * (size_t)pos + 3].y, sizeof orig);
         if (orig < 0 || orig >= (int)n) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: fast-walk record without a primitive");
-        box[pos] = &c->tight[6 * (size_t)orig];
+        box[pos] = &sc.tight[6 * (size_t)orig];
         for (int a = 0; a < 3; ++a) {
             lo[a] = std::fmin(lo[a], box[pos][a]);
             hi[a] = std::fmax(hi[a], box[pos][3 + a]);
         }
     }
-    for (int a = 0; a < 6; ++a) scene_reach = std::fmax(scene_reach, std::fabs(c->bounds[a]));
+    for (int a = 0; a < 6; ++a) scene_reach = std::fmax(scene_reach, std::fabs(sc.bounds[a]));
     const float reach_max = 4.0f * scene_reach;
     float ext[3], max_ext = 0.0f;
     for (int a = 0; a < 3; ++a) {
@@ -813,14 +753,13 @@ static int build_grid(rtgo_ctx* c, uint32_t n, const Knobs& kn)
         q[7] = 0.0f;
         ++rec;
     }
-    RTGO_HIP(c, hipMalloc(&c->grid.d, bytes));
-    RTGO_HIP(c, hipMemcpyAsync(c->grid.d, img.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, sc.grid.d.upload(img.data(), bytes, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    c->grid.n_nodes = (int)(bytes / 32);
-    c->grid.entries = (int)total;
-    c->grid.gp = g;
-    c->grid.reach_max = reach_max;
-    c->grid.have = true;
+    sc.grid.n_nodes = (int)(bytes / 32);
+    sc.grid.entries = (int)total;
+    sc.grid.gp = g;
+    sc.grid.reach_max = reach_max;
+    sc.grid.have = true;
     if (kn.debug)
         std::fprintf(stderr, "rtgo_set_scene: grid %d x %d x %d over %d primitives, %zu list entries, %zu bytes, pad %g, for rays within %g\n", dim[0], dim[1], dim[2], ns,
                      total, bytes, pad, reach_max);
@@ -829,14 +768,16 @@ static int build_grid(rtgo_ctx* c, uint32_t n, const Knobs& kn)
 
 // build_kernel for one big_frac into a structure of its own (the canonical LBVH, boxes and frames it also writes are the same for every
 // big_frac), and its 15 meta words decoded
-static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_frac, const Knobs& kn, rtgo_ctx::FastTree& t, int meta[15])
+static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_frac, const Knobs& kn, AnalyticScene::FastTree& t, int meta[15])
 {
-    RTGO_HIP(c, hipMalloc(&t.d_fnodes, (2 * n - 1) * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&t.d_fprims, n * 4 * sizeof(float4)));
-    hipLaunchKernelGGL(build_kernel, dim3(1), dim3(kMaxPrims), kBuildDynLds, c->stream, c->d_prims_in, c->d_aabb, have_aabbs, (int)n,
-                       c->d_nodes, c->d_prims, t.d_fnodes, t.d_fprims, c->leaf_budget, big_frac, c->d_meta, c->d_tight, kn.no_cuboid ? 0 : 1, c->d_frames);
+    AnalyticScene& sc = c->scene;
+    RTGO_HIP(c, t.d_fnodes.alloc((2 * n - 1) * 2));
+    RTGO_HIP(c, t.d_fprims.alloc(n * 4));
+    hipLaunchKernelGGL(build_kernel, dim3(1), dim3(kMaxPrims), kBuildDynLds, c->stream, sc.d_prims_in.get(), sc.d_aabb.get(), have_aabbs, (int)n,
+                       sc.d_nodes.get(), sc.d_prims.get(), t.d_fnodes.get(), t.d_fprims.get(), c->leaf_budget, big_frac, c->d_meta.get(), sc.d_tight.get(),
+                       kn.no_cuboid ? 0 : 1, sc.d_frames.get());
     RTGO_HIP(c, hipGetLastError());
-    RTGO_HIP(c, hipMemcpyAsync(meta, c->d_meta, 15 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(meta, c->d_meta.get(), 15 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     t.fast_depth = meta[1];
     t.n_small = meta[2];
@@ -862,12 +803,12 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
 // rounding of o.y_g, d.y_g and the quotient.  Each is a few float operations on terms <= |row|_1 (|o| + t |d|) + |w| <= |row|_1 3 R
 // + |w| (R: the launch's reach, as for cub_mu), <= 12 * 2^-24 of them; K = 64 * 2^-24 leaves five times that.  So the margin is
 // K (A R + B) with A = 3 (L max|row_e|_1 + |r1_g|_1), B = L (max|w_e| + 1) + |w_g| (the 1: u = px + 0.5 is rounded at 1's scale).
-static int emitter_cert(rtgo_ctx* c, const rtgo_prim* prims, uint32_t n, rtgo_ctx::FastTree& t)
+static int emitter_cert(rtgo_ctx* c, const rtgo_prim* prims, uint32_t n, AnalyticScene::FastTree& t)
 {
     t.emit_n = 0;
     if (t.list_cub != 2) return RTGO_OK;
     std::vector<float4> fp((size_t)n * 4);
-    RTGO_HIP(c, hipMemcpyAsync(fp.data(), t.d_fprims, fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(fp.data(), t.d_fprims.get(), fp.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     auto orig_at = [&](int pos) { int o; std::memcpy(&o, &fp[4 * pos + 3].y, 4); return o; };
     auto type_at = [&](int pos) { int o; std::memcpy(&o, &fp[4 * pos + 3].x, 4); return o; };
@@ -943,6 +884,16 @@ static int check_prims(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aab
     return RTGO_OK;
 }
 
+// Drops the analytic scene and what was cached for it (rtgo_set_scene, rtgo_set_large_scene: after their stream sync).  The mask's
+// buffers stay for the next scene.
+static void drop_scene(rtgo_ctx* c)
+{
+    c->scene = AnalyticScene();
+    c->seeds = rtgo_ctx::Seeds();
+    c->mask.key.clear();
+    c->trial = rtgo_ctx::Trial();
+}
+
 int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
 {
     if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: NULL argument");
@@ -952,37 +903,36 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     const Knobs kn;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    free_scene(c);
-    c->mask_key.clear();
-    c->trial = rtgo_ctx::Trial();
-    RTGO_HIP(c, hipMalloc(&c->d_prims_in, n * sizeof(PrimIn)));
-    RTGO_HIP(c, hipMalloc(&c->d_aabb, n * 6 * sizeof(float)));
-    RTGO_HIP(c, hipMalloc(&c->d_nodes, (2 * n - 1) * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_prims, n * 6 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_frames, n * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_tight, n * 6 * sizeof(float)));
+    drop_scene(c);
+    AnalyticScene& sc = c->scene;
+    RTGO_HIP(c, sc.d_prims_in.alloc(n));
+    RTGO_HIP(c, sc.d_aabb.alloc(n * 6));
+    RTGO_HIP(c, sc.d_nodes.alloc((2 * n - 1) * 2));
+    RTGO_HIP(c, sc.d_prims.alloc(n * 6));
+    RTGO_HIP(c, sc.d_frames.alloc(n * 2));
+    RTGO_HIP(c, sc.d_tight.alloc(n * 6));
     if (kn.leaf_budget >= 0) c->leaf_budget = kn.leaf_budget;
-    RTGO_HIP(c, hipMemcpyAsync(c->d_prims_in, prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
-    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(c->d_aabb, aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
+    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
     int meta[15];
-    if (const int rc = build_fast_tree(c, n, aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, c->tree[0], meta)) return rc;
-    if (const int rc = emitter_cert(c, prims, n, c->tree[0])) return rc;
-    c->tight.assign((size_t)n * 6, 0.0f);
-    RTGO_HIP(c, hipMemcpyAsync(c->tight.data(), c->d_tight, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (const int rc = build_fast_tree(c, n, aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, sc.tree[0], meta)) return rc;
+    if (const int rc = emitter_cert(c, prims, n, sc.tree[0])) return rc;
+    sc.tight.assign((size_t)n * 6, 0.0f);
+    RTGO_HIP(c, hipMemcpyAsync(sc.tight.data(), sc.d_tight.get(), (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    const rtgo_ctx::FastTree& t0 = c->tree[0];
+    const AnalyticScene::FastTree& t0 = sc.tree[0];
     const int depth = meta[0];
-    c->lbvh_depth = depth;
+    sc.lbvh_depth = depth;
     if (!t0.sane(n)) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: the fast walk's tree has " + std::to_string(t0.n_fnodes) + " nodes");
-    std::memcpy(c->bounds, &meta[3], sizeof c->bounds);
+    std::memcpy(sc.bounds, &meta[3], sizeof sc.bounds);
     if (!kn.pin_big) {
         // the alternative structure: big_frac 15 % (the canonical outputs, boxes and frames are rewritten with the same values)
         int m2[15];
-        if (const int rc = build_fast_tree(c, n, 1, 0.15f, kn, c->tree[1], m2)) return rc;
-        if (const int rc = emitter_cert(c, prims, n, c->tree[1])) return rc;
-        const rtgo_ctx::FastTree& t1 = c->tree[1];
+        if (const int rc = build_fast_tree(c, n, 1, 0.15f, kn, sc.tree[1], m2)) return rc;
+        if (const int rc = emitter_cert(c, prims, n, sc.tree[1])) return rc;
+        const AnalyticScene::FastTree& t1 = sc.tree[1];
         // (the same split of primitives = the same structure: nothing to try)
-        c->have_alt = m2[0] == meta[0] && t1.sane(n) &&
+        sc.have_alt = m2[0] == meta[0] && t1.sane(n) &&
                       !(t1.n_small == t0.n_small && t1.n_fnodes == t0.n_fnodes && t1.n_big_pairs == t0.n_big_pairs && t1.list_cub == t0.list_cub);
     }
     if (const int rc = build_grid(c, n, kn)) return rc;
@@ -992,8 +942,7 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     if (depth > kStackDepth)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
                                                std::to_string(kStackDepth) + ")");
-    c->n_prims = n;
-    c->quadrics.clear();
+    sc.n_prims = n;
     for (uint32_t i = 0; i < n; ++i) {
         const rtgo_prim& q = prims[i];
         if (q.type != RTGO_SPHERE && q.type != RTGO_CYLINDER) continue;
@@ -1005,33 +954,22 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
             smin = s[1] < smin ? s[1] : smin;
             smax = s[1] > smax ? s[1] : smax;
         }
-        rtgo_ctx::Quadric e;
+        AnalyticScene::Quadric e;
         e.c[0] = q.model[3];
         e.c[1] = q.model[7];
         e.c[2] = q.model[11];
         e.w = (float)(smax / (smin * smin));
-        c->quadrics.push_back(e);
+        sc.quadrics.push_back(e);
     }
     return RTGO_OK;
 }
 
 // the temporaries of rtgo_set_large_scene's build, freed however the call ends
 struct LargeScratch {
-    unsigned long long *keys = nullptr, *keys_alt = nullptr;
-    unsigned int* hist = nullptr;
-    int *left = nullptr, *right = nullptr, *parent = nullptr, *depth = nullptr;
-    float* small = nullptr;   // scene bounds (6 floats), then the largest leaf depth (int)
-    ~LargeScratch()
-    {
-        release(keys);
-        release(keys_alt);
-        release(hist);
-        release(left);
-        release(right);
-        release(parent);
-        release(depth);
-        release(small);
-    }
+    DeviceArray<unsigned long long> keys, keys_alt;
+    DeviceArray<unsigned int> hist;
+    DeviceArray<int> left, right, parent, depth;
+    DeviceArray<float> small;   // scene bounds (6 floats), then the largest leaf depth (int)
 };
 
 int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
@@ -1043,70 +981,67 @@ int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* a
     const Knobs kn;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    free_scene(c);
-    c->mask_key.clear();
-    c->trial = rtgo_ctx::Trial();
-    c->quadrics.clear();
-    c->lbvh_depth = 0;
+    drop_scene(c);
+    AnalyticScene& sc = c->scene;
     const int ni = (int)n, n_int = ni > 1 ? ni - 1 : 1;
     const int nb = (ni + whitted::kRadixTile - 1) / whitted::kRadixTile;
     LargeScratch ls;
-    RTGO_HIP(c, hipMalloc(&c->d_prims_in, (size_t)n * sizeof(PrimIn)));
-    RTGO_HIP(c, hipMalloc(&c->d_aabb, (size_t)n * 6 * sizeof(float)));
-    RTGO_HIP(c, hipMalloc(&c->d_nodes, (2 * (size_t)n - 1) * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_prims, (size_t)n * 6 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&ls.keys, (size_t)n * sizeof(unsigned long long)));
-    RTGO_HIP(c, hipMalloc(&ls.keys_alt, (size_t)n * sizeof(unsigned long long)));
-    RTGO_HIP(c, hipMalloc(&ls.hist, (size_t)256 * nb * sizeof(unsigned int)));
-    RTGO_HIP(c, hipMalloc(&ls.left, (size_t)n_int * sizeof(int)));
-    RTGO_HIP(c, hipMalloc(&ls.right, (size_t)n_int * sizeof(int)));
-    RTGO_HIP(c, hipMalloc(&ls.parent, (2 * (size_t)n - 1) * sizeof(int)));
-    RTGO_HIP(c, hipMalloc(&ls.depth, (size_t)n_int * sizeof(int)));
-    RTGO_HIP(c, hipMalloc(&ls.small, 8 * sizeof(float)));
-    RTGO_HIP(c, hipMemcpyAsync(c->d_prims_in, prims, (size_t)n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
-    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(c->d_aabb, aabbs, (size_t)n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
-    RTGO_HIP(c, hipMemsetAsync(ls.small, 0, 8 * sizeof(float), c->stream));
+    RTGO_HIP(c, sc.d_prims_in.alloc(n));
+    RTGO_HIP(c, sc.d_aabb.alloc((size_t)n * 6));
+    RTGO_HIP(c, sc.d_nodes.alloc((2 * (size_t)n - 1) * 2));
+    RTGO_HIP(c, sc.d_prims.alloc((size_t)n * 6));
+    RTGO_HIP(c, ls.keys.alloc(n));
+    RTGO_HIP(c, ls.keys_alt.alloc(n));
+    RTGO_HIP(c, ls.hist.alloc((size_t)256 * nb));
+    RTGO_HIP(c, ls.left.alloc(n_int));
+    RTGO_HIP(c, ls.right.alloc(n_int));
+    RTGO_HIP(c, ls.parent.alloc(2 * (size_t)n - 1));
+    RTGO_HIP(c, ls.depth.alloc(n_int));
+    RTGO_HIP(c, ls.small.alloc(8));
+    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, (size_t)n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
+    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, (size_t)n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemsetAsync(ls.small.get(), 0, 8 * sizeof(float), c->stream));
     const dim3 g_prims((n + 255) / 256), g_nodes((2 * n - 1 + 255) / 256), g_int((n_int + 255) / 256);
     // records and boxes; bounds; Morton keys in (code, index) order (four stable passes over the code's bytes: back in ls.keys)
-    hipLaunchKernelGGL(large_prep_kernel, g_prims, dim3(256), 0, c->stream, (const PrimIn*)c->d_prims_in, c->d_aabb, aabbs ? 1 : 0, ni, c->d_prims);
-    hipLaunchKernelGGL(whitted::big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)c->d_aabb, ni, ls.small);
-    hipLaunchKernelGGL(large_keys_kernel, g_prims, dim3(256), 0, c->stream, (const float*)c->d_aabb, ni, (const float*)ls.small, ls.keys);
-    unsigned long long *src = ls.keys, *dst = ls.keys_alt;
+    hipLaunchKernelGGL(large_prep_kernel, g_prims, dim3(256), 0, c->stream, (const PrimIn*)sc.d_prims_in.get(), sc.d_aabb.get(), aabbs ? 1 : 0, ni, sc.d_prims.get());
+    hipLaunchKernelGGL(whitted::big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)sc.d_aabb.get(), ni, ls.small.get());
+    hipLaunchKernelGGL(large_keys_kernel, g_prims, dim3(256), 0, c->stream, (const float*)sc.d_aabb.get(), ni, (const float*)ls.small.get(), ls.keys.get());
+    unsigned long long *src = ls.keys.get(), *dst = ls.keys_alt.get();
     for (int shift = 32; shift < 64; shift += 8) {
-        hipLaunchKernelGGL(whitted::radix_count_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift, ls.hist);
-        hipLaunchKernelGGL(whitted::radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, ls.hist, 256 * nb);
+        hipLaunchKernelGGL(whitted::radix_count_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift, ls.hist.get());
+        hipLaunchKernelGGL(whitted::radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, ls.hist.get(), 256 * nb);
         hipLaunchKernelGGL(whitted::radix_scatter_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift,
-                           (const unsigned int*)ls.hist, dst);
+                           (const unsigned int*)ls.hist.get(), dst);
         std::swap(src, dst);
     }
     // hierarchy, depths and leaves
-    int* d_max_depth = reinterpret_cast<int*>(ls.small + 6);
-    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, ls.left, ls.right, ls.parent);
-    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, (const float*)c->d_aabb,
-                       (const int*)ls.parent, ls.depth, c->d_nodes, d_max_depth);
+    int* d_max_depth = reinterpret_cast<int*>(ls.small.get() + 6);
+    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, ls.left.get(), ls.right.get(), ls.parent.get());
+    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, (const float*)sc.d_aabb.get(),
+                       (const int*)ls.parent.get(), ls.depth.get(), sc.d_nodes.get(), d_max_depth);
     RTGO_HIP(c, hipGetLastError());
     int depth = 0;
     RTGO_HIP(c, hipMemcpyAsync(&depth, d_max_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     if (depth > kLargeMaxDepth) {
-        free_scene(c);
+        c->scene = AnalyticScene();
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
                                                std::to_string(kLargeMaxDepth) + ")");
     }
     // boxes, one level per launch from the deepest up (a kernel boundary between a node's children and the node)
     for (int level = depth - 1; level >= 0; --level)
-        hipLaunchKernelGGL(large_fit_kernel, g_int, dim3(256), 0, c->stream, (const int*)ls.left, (const int*)ls.right, (const int*)ls.depth,
-                           ni - 1, level, c->d_nodes);
+        hipLaunchKernelGGL(large_fit_kernel, g_int, dim3(256), 0, c->stream, (const int*)ls.left.get(), (const int*)ls.right.get(), (const int*)ls.depth.get(),
+                           ni - 1, level, sc.d_nodes.get());
     RTGO_HIP(c, hipGetLastError());
     float4 root[2];
-    RTGO_HIP(c, hipMemcpyAsync(root, c->d_nodes, sizeof root, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(root, sc.d_nodes.get(), sizeof root, hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    release(c->d_prims_in);   // (the records hold all the walk and the shading read)
+    sc.d_prims_in.reset();   // (the records hold all the walk and the shading read)
     const float b[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
-    std::memcpy(c->bounds, b, sizeof c->bounds);
-    c->lbvh_depth = depth;
-    c->n_prims = n;
-    c->large = true;
+    std::memcpy(sc.bounds, b, sizeof sc.bounds);
+    sc.lbvh_depth = depth;
+    sc.n_prims = n;
+    sc.large = true;
     if (kn.debug)
         std::fprintf(stderr, "rtgo_set_large_scene: %d primitives, canonical LBVH depth %d in global memory\n", ni, depth);
     return RTGO_OK;
@@ -1135,7 +1070,7 @@ int rtgo_set_lights(rtgo_ctx* c, const rtgo_light* lights, int n)
     if (!c || n < 0 || (n > 0 && !lights)) return fail(c, RTGO_E_INVALID, "rtgo_set_lights: bad argument");
     if (n > RTGO_MAX_LIGHTS) n = RTGO_MAX_LIGHTS;  // Renderer::WriteLights copies at most MAX_LIGHTS (renderer.cpp:661)
     RTGO_HIP(c, hipSetDevice(c->device));
-    if (n > 0) RTGO_HIP(c, hipMemcpyAsync(c->d_lights, lights, n * sizeof(rtgo_light), hipMemcpyHostToDevice, c->stream));
+    if (n > 0) RTGO_HIP(c, hipMemcpyAsync(c->d_lights.get(), lights, n * sizeof(rtgo_light), hipMemcpyHostToDevice, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     c->n_lights = n;
     return RTGO_OK;
@@ -1146,14 +1081,16 @@ int rtgo_resize(rtgo_ctx* c, size_t pixels)
     if (!c || pixels == 0) return fail(c, RTGO_E_INVALID, "rtgo_resize: bad argument");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    free_output(c);
-    free_seeds(c);
-    RTGO_HIP(c, hipMalloc(&c->d_accum, pixels * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->d_image, pixels * sizeof(uchar4)));
-    RTGO_HIP(c, hipMemsetAsync(c->d_accum, 0, pixels * sizeof(float4), c->stream));
-    RTGO_HIP(c, hipMemsetAsync(c->d_image, 0, pixels * sizeof(uchar4), c->stream));
-    c->own_output = true;
-    c->pixels = pixels;
+    c->out = rtgo_ctx::Output();
+    c->seeds = rtgo_ctx::Seeds();
+    rtgo_ctx::Output& o = c->out;
+    RTGO_HIP(c, o.own_accum.alloc(pixels));
+    RTGO_HIP(c, o.own_image.alloc(pixels));
+    RTGO_HIP(c, hipMemsetAsync(o.own_accum.get(), 0, pixels * sizeof(float4), c->stream));
+    RTGO_HIP(c, hipMemsetAsync(o.own_image.get(), 0, pixels * sizeof(uchar4), c->stream));
+    o.accum = o.own_accum.get();
+    o.image = o.own_image.get();
+    o.pixels = pixels;
     return RTGO_OK;
 }
 
@@ -1162,10 +1099,10 @@ int rtgo_bind_output(rtgo_ctx* c, void* d_accum, void* d_image, size_t pixels)
     if (!c || !d_accum || !d_image || pixels == 0) return fail(c, RTGO_E_INVALID, "rtgo_bind_output: bad argument");
     if (((uintptr_t)d_accum & 15u) || ((uintptr_t)d_image & 3u))
         return fail(c, RTGO_E_INVALID, "rtgo_bind_output: accum must be 16-byte aligned, image 4-byte aligned");
-    free_output(c);
-    c->d_accum = (float4*)d_accum;
-    c->d_image = (uchar4*)d_image;
-    c->pixels = pixels;
+    c->out = rtgo_ctx::Output();
+    c->out.accum = (float4*)d_accum;
+    c->out.image = (uchar4*)d_image;
+    c->out.pixels = pixels;
     return RTGO_OK;
 }
 
@@ -1173,9 +1110,9 @@ int rtgo_bind_output(rtgo_ctx* c, void* d_accum, void* d_image, size_t pixels)
 static int frame_params(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p)
 {
     if (!c || !f) return fail(c, RTGO_E_INVALID, "rtgo_launch: NULL argument");
-    if (c->n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_launch: no scene (call rtgo_set_scene)");
+    if (c->scene.n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_launch: no scene (call rtgo_set_scene)");
     if (!c->have_camera) return fail(c, RTGO_E_STATE, "rtgo_launch: no camera (call rtgo_set_camera)");
-    if (!c->d_accum || !c->d_image) return fail(c, RTGO_E_STATE, "rtgo_launch: no output (call rtgo_resize or rtgo_bind_output)");
+    if (!c->out.accum || !c->out.image) return fail(c, RTGO_E_STATE, "rtgo_launch: no output (call rtgo_resize or rtgo_bind_output)");
     if (f->image_width == 0 || f->image_height == 0 || f->sqrt_spp <= 0)
         return fail(c, RTGO_E_INVALID, "rtgo_launch: image size and sqrt_spp must be positive");
     if (f->max_trace_depth < 0 || f->max_trace_depth > kMaxLevels)
@@ -1195,7 +1132,7 @@ static int frame_params(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p)
     p.rank = f->rank;
     if (p.rank >= p.n_ranks) return fail(c, RTGO_E_INVALID, "rtgo_launch: rank >= n_ranks");
     p.local_rows = rtgo_local_rows(p.h, p.band_h, p.n_ranks, p.rank);
-    if ((size_t)p.local_rows * p.w > c->pixels) return fail(c, RTGO_E_INVALID, "rtgo_launch: output buffer too small for this window");
+    if ((size_t)p.local_rows * p.w > c->out.pixels) return fail(c, RTGO_E_INVALID, "rtgo_launch: output buffer too small for this window");
     p.eye = c->eye;
     p.U = c->U;
     p.V = c->V;
@@ -1213,26 +1150,26 @@ static int frame_params(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p)
         const float inv = 1.0f / (float)nn;
         p.bg_pixel = v3{sx * inv, sy * inv, sz * inv};
     }
-    p.lights = c->d_lights;
-    p.accum = c->d_accum;
-    p.image = c->d_image;
-    p.queue = c->d_queue + (size_t)c->queue_set * kQueues * kQueueStride;
-    p.queue_next = c->d_queue + (size_t)(1 - c->queue_set) * kQueues * kQueueStride;
-    p.counters = c->d_counters;
+    p.lights = c->d_lights.get();
+    p.accum = c->out.accum;
+    p.image = c->out.image;
+    p.queue = c->d_queue.get() + (size_t)c->queue_set * kQueues * kQueueStride;
+    p.queue_next = c->d_queue.get() + (size_t)(1 - c->queue_set) * kQueues * kQueueStride;
+    p.counters = c->d_counters.get();
 #ifdef RTGO_CMPWALK
-    if (!c->d_cmp) {
-        RTGO_HIP(c, hipMalloc(&c->d_cmp, 256 * 16 * sizeof(float)));
-        RTGO_HIP(c, hipMemset(c->d_cmp, 0, 256 * 16 * sizeof(float)));
+    if (!c->d_cmp.get()) {
+        RTGO_HIP(c, c->d_cmp.alloc(256 * 16));
+        RTGO_HIP(c, hipMemset(c->d_cmp.get(), 0, 256 * 16 * sizeof(float)));
         RTGO_HIP(c, hipStreamSynchronize(nullptr));   // (null-stream memset: the launch stream does not wait for it)
     }
-    p.cmp = c->d_cmp;
+    p.cmp = c->d_cmp.get();
 #endif
 #ifdef RTGO_TIMELINE
-    if (!c->d_timeline) RTGO_HIP(c, hipMalloc(&c->d_timeline, 16384 * 128));
-    p.timeline = c->d_timeline;
+    if (!c->d_timeline.get()) RTGO_HIP(c, c->d_timeline.alloc(16384 * 128 / sizeof(unsigned long long)));
+    p.timeline = c->d_timeline.get();
 #endif
-    p.n_prims = (int)c->n_prims;
-    p.n_nodes = 2 * (int)c->n_prims - 1;
+    p.n_prims = (int)c->scene.n_prims;
+    p.n_nodes = 2 * (int)c->scene.n_prims - 1;
     p.n_lights = c->n_lights;
     p.sqrt_spp = f->sqrt_spp;
     p.max_depth = f->max_trace_depth;
@@ -1248,8 +1185,9 @@ static int frame_params(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p)
 // Returns whether the launch is beyond the guard; records both quantities for rtgo_get_stats.
 static bool far_field_guard(rtgo_ctx* c, const LaunchParams& p, const Knobs& kn)
 {
+    const AnalyticScene& sc = c->scene;
     float reach = 0.0f;
-    for (int k = 0; k < 6; ++k) reach = std::fabs(c->bounds[k]) > reach ? std::fabs(c->bounds[k]) : reach;
+    for (int k = 0; k < 6; ++k) reach = std::fabs(sc.bounds[k]) > reach ? std::fabs(sc.bounds[k]) : reach;
     const float e[3] = {p.eye.x, p.eye.y, p.eye.z};
     for (int k = 0; k < 3; ++k) reach = std::fabs(e[k]) > reach ? std::fabs(e[k]) : reach;
     // ... and a sphere's or cylinder's reported hit leaves its surface as the ray origin recedes: b^2 - 4ac cancels to the last
@@ -1260,10 +1198,10 @@ static bool far_field_guard(rtgo_ctx* c, const LaunchParams& p, const Knobs& kn)
     // tight bounds (where bounce rays start).  Thresholds: kGuardReach / kGuardQuadric, set from tools/fuzz_farfield.py's table
     // (profiles/r03a) with the safety factors stated at their definition.
     float quad = 0.0f;
-    for (const rtgo_ctx::Quadric& qd : c->quadrics) {
+    for (const AnalyticScene::Quadric& qd : sc.quadrics) {
         float d2 = 0.0f, e2 = 0.0f;
         for (int k = 0; k < 3; ++k) {
-            const float lo = std::fabs(c->bounds[k] - qd.c[k]), hi = std::fabs(c->bounds[3 + k] - qd.c[k]);
+            const float lo = std::fabs(sc.bounds[k] - qd.c[k]), hi = std::fabs(sc.bounds[3 + k] - qd.c[k]);
             const float far_k = lo > hi ? lo : hi;
             d2 += far_k * far_k;
             e2 += (e[k] - qd.c[k]) * (e[k] - qd.c[k]);
@@ -1295,19 +1233,19 @@ static int choose_candidate(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams
     if (canon) {
 #ifdef RTGO_CMPWALK
         // (diagnostic build: the instrumented launch also runs the pinned fast structure on every ray, rtgo_ray_trace.inc)
-        if (kn.tree == 1 && c->have_alt) pk.structure = 1;
-        if (kn.tree == 2 && c->grid.have && c->guard_reach <= c->grid.reach_max) pk.structure = 2;
+        if (kn.tree == 1 && c->scene.have_alt) pk.structure = 1;
+        if (kn.tree == 2 && c->scene.grid.have && c->guard_reach <= c->scene.grid.reach_max) pk.structure = 2;
 #endif
         return RTGO_OK;
     }
     const bool path = f->path_tracing != 0, multi_pass = passes_of(nn) > 1;
     // (the grid: where rtgo_set_scene built one, for rays that start within the reach its pad was sized for, and in the instantiations
     // that exist -- not the flat-primitives one)
-    const bool flat_only = path && c->quadrics.empty() && !kn.no_frames;
-    const bool grid_ok = c->grid.have && c->guard_reach <= c->grid.reach_max && !flat_only;
+    const bool flat_only = path && c->scene.quadrics.empty() && !kn.no_frames;
+    const bool grid_ok = c->scene.grid.have && c->guard_reach <= c->scene.grid.reach_max && !flat_only;
     int structs[3], n_structs = 0;
     structs[n_structs++] = 0;
-    if (c->have_alt) structs[n_structs++] = 1;
+    if (c->scene.have_alt) structs[n_structs++] = 1;
     if (grid_ok) structs[n_structs++] = 2;
     if (kn.tree >= 0) {   // (RTGO_TREE, RTGO_STREAM: experiment and test knobs, no trial over that dimension)
         pk.structure = 0;
@@ -1358,7 +1296,7 @@ static int choose_candidate(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams
 }
 
 // what the walk reads: the canonical LBVH, and the chosen fast structure (`ft`, or the grid over ft's small primitives)
-static void walk_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool canon, bool use_grid, LaunchParams& p)
+static void walk_params(const rtgo_ctx* c, const AnalyticScene::FastTree& ft, bool canon, bool use_grid, LaunchParams& p)
 {
     // cuboid_range's margin, in the object-space y units of a face g: the certificate's tolerance plus the rounding of what is
     // compared -- the reference's (u, v) on a face f, carried into y_g units by L_fg, and y_g(t_f) itself.  Each is a handful of
@@ -1372,13 +1310,14 @@ static void walk_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool ca
         p.list_cub = 0;
         p.cub_mu = -1.0f;        // tree leaves: cuboid_range is not taken either (see render_kernel)
     }
-    p.nodes = c->d_nodes;
-    p.prims = c->d_prims;
-    p.fnodes = use_grid ? (const float4*)c->grid.d : ft.d_fnodes;
-    p.n_fnodes = use_grid ? c->grid.n_nodes : ft.n_fnodes;
-    p.grid = use_grid ? c->grid.gp : rtgo::GridParams();
-    p.fprims = ft.d_fprims;
-    p.frames = c->d_frames;
+    const AnalyticScene& sc = c->scene;
+    p.nodes = sc.d_nodes.get();
+    p.prims = sc.d_prims.get();
+    p.fnodes = use_grid ? (const float4*)sc.grid.d.get() : ft.d_fnodes.get();
+    p.n_fnodes = use_grid ? sc.grid.n_nodes : ft.n_fnodes;
+    p.grid = use_grid ? sc.grid.gp : rtgo::GridParams();
+    p.fprims = ft.d_fprims.get();
+    p.frames = sc.d_frames.get();
     p.n_small = ft.n_small;
     p.n_big_pairs = ft.n_big_pairs;
     p.stack_depth = canon ? kStackDepth : ((ft.fast_depth > 0 && !use_grid) ? ft.fast_depth : 1) + 1;   // (+1: fast_tree writes the slot past the top before it knows whether it pushes)
@@ -1388,7 +1327,7 @@ static void walk_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool ca
 // launch's reach (walk_params), a background of +0 in all three channels (a miss then pays what a non-emitter hit pays: compared as
 // bits), every emitter inside every wall by more than the margin at this reach, and max_depth >= 1 (the last ray is never a primary
 // ray: the pixel's "every primary ray missed" shortcut does not see it).  RTGO_NO_LAST_EMITTER: off.
-static void last_ray_params(const rtgo_ctx* c, const rtgo_ctx::FastTree& ft, bool path, bool canon, bool use_grid, const Knobs& kn, LaunchParams& p)
+static void last_ray_params(const rtgo_ctx* c, const AnalyticScene::FastTree& ft, bool path, bool canon, bool use_grid, const Knobs& kn, LaunchParams& p)
 {
     p.emit_n = 0;
     const float bg[3] = {p.bg.x, p.bg.y, p.bg.z};
@@ -1456,11 +1395,12 @@ static int update_hot_mask(rtgo_ctx* c, uint32_t strip_px, LaunchParams& p, unsi
         key.push_back(bits);
     }
     const size_t words = ((size_t)p.n_hot + 31) / 32;
-    if (key != c->mask_key) {
+    rtgo_ctx::HotMask& hm = c->mask;
+    if (key != hm.key) {
         std::vector<uint32_t> mask(words, 0u);
         bool all_hot = false;
-        for (uint32_t i = 0; i < c->n_prims && !all_hot; ++i) {
-            const Rect q = box_screen_rect(&c->tight[6 * (size_t)i], p);
+        for (uint32_t i = 0; i < c->scene.n_prims && !all_hot; ++i) {
+            const Rect q = box_screen_rect(&c->scene.tight[6 * (size_t)i], p);
             if (q.x0 == 0 && q.x1 == p.w && q.y0 == 0 && q.y1 == p.h) {   // a primitive whose rectangle is the whole window (or unknown)
                 all_hot = true;
                 break;
@@ -1495,37 +1435,26 @@ static int update_hot_mask(rtgo_ctx* c, uint32_t strip_px, LaunchParams& p, unsi
             all_hot = hot_bits == (size_t)p.n_hot;
         }
         if (!all_hot) {
-            if (words > c->mask_capacity) {
-                release(c->d_mask);
-                c->mask_capacity = 0;
-                RTGO_HIP(c, hipMalloc(&c->d_mask, words * sizeof(uint32_t)));
-                c->mask_capacity = words;
-            }
+            if (words > hm.d.size()) RTGO_HIP(c, hm.d.alloc(words));
             // (the previous launch may still be reading the old mask: stream order takes care of it.)  The copy leaves from pinned
             // memory the context keeps, so nothing here waits for the stream; a slot is reused two rebuilds later, by when its copy
             // has long completed (the event wait is a formality)
-            const int slot = c->mask_slot;
-            c->mask_slot = 1 - slot;
-            if (!c->mask_copied[slot]) RTGO_HIP(c, hipEventCreateWithFlags(&c->mask_copied[slot], hipEventDisableTiming));
-            else RTGO_HIP(c, hipEventSynchronize(c->mask_copied[slot]));
-            if (words > c->h_mask_capacity[slot]) {
-                if (c->h_mask[slot]) (void)hipHostFree(c->h_mask[slot]);
-                c->h_mask[slot] = nullptr;
-                c->h_mask_capacity[slot] = 0;
-                RTGO_HIP(c, hipHostMalloc((void**)&c->h_mask[slot], words * sizeof(uint32_t), hipHostMallocDefault));
-                c->h_mask_capacity[slot] = words;
-            }
-            std::memcpy(c->h_mask[slot], mask.data(), words * sizeof(uint32_t));
-            RTGO_HIP(c, hipMemcpyAsync(c->d_mask, c->h_mask[slot], words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            RTGO_HIP(c, hipEventRecord(c->mask_copied[slot], c->stream));
+            const int slot = hm.slot;
+            hm.slot = 1 - slot;
+            if (!hm.copied[slot].get()) RTGO_HIP(c, hm.copied[slot].create(hipEventDisableTiming));
+            else RTGO_HIP(c, hipEventSynchronize(hm.copied[slot].get()));
+            if (words > hm.h[slot].size()) RTGO_HIP(c, hm.h[slot].alloc(words));
+            std::memcpy(hm.h[slot].get(), mask.data(), words * sizeof(uint32_t));
+            RTGO_HIP(c, hipMemcpyAsync(hm.d.get(), hm.h[slot].get(), words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            RTGO_HIP(c, hipEventRecord(hm.copied[slot].get(), c->stream));
         }
-        c->mask_all_hot = all_hot;
-        c->mask_cold_pixels = all_hot ? 0 : cold_px;
-        c->mask_key = key;
+        hm.all_hot = all_hot;
+        hm.cold_pixels = all_hot ? 0 : cold_px;
+        hm.key = key;
     }
-    if (!c->mask_all_hot) {
-        p.hot_mask = c->d_mask;
-        cold_pixels = c->mask_cold_pixels;
+    if (!hm.all_hot) {
+        p.hot_mask = hm.d.get();
+        cold_pixels = hm.cold_pixels;
     }
     return RTGO_OK;
 }
@@ -1544,15 +1473,15 @@ static int plan_seeds(rtgo_ctx* c, LaunchParams& p, uint32_t strip_px, bool has_
     const uint64_t words = (uint64_t)p.n_hot * strip_px;
     if (!has_pass || words == 0 || words > (1ull << 27)) return RTGO_OK;
     key = {p.W, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, p.grab, strip_px, p.hot_x0, p.hot_y0, p.hot_w, p.hot_h};
-    if (words > c->seeds_capacity) {
+    rtgo_ctx::Seeds& sd = c->seeds;
+    if (words > sd.d[1].size()) {   // (d[1] is allocated last)
         RTGO_HIP(c, hipStreamSynchronize(c->stream));   // (launches in flight may still use the old buffers)
-        free_seeds(c);
-        RTGO_HIP(c, hipMalloc(&c->d_seeds[0], words * sizeof(unsigned int)));
-        RTGO_HIP(c, hipMalloc(&c->d_seeds[1], words * sizeof(unsigned int)));
-        c->seeds_capacity = (size_t)words;
+        sd = rtgo_ctx::Seeds();
+        RTGO_HIP(c, sd.d[0].alloc(words));
+        RTGO_HIP(c, sd.d[1].alloc(words));
     }
-    if (c->seeds_ok && c->seeds_frame == p.frame && c->seeds_key == key) p.seeds = c->d_seeds[c->seeds_read];
-    p.seeds_next = c->d_seeds[1 - c->seeds_read];
+    if (sd.ok && sd.frame == p.frame && sd.key == key) p.seeds = sd.d[sd.read].get();
+    p.seeds_next = sd.d[1 - sd.read].get();
     return RTGO_OK;
 }
 
@@ -1612,7 +1541,7 @@ static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, u
     return RTGO_OK;
 }
 
-// The launch between its two events on the context's stream, then its bookkeeping: only now does the trial (rtgo_ctx::Trial) learn of it
+// The timed launch of the analytic path, then its bookkeeping: only now does the trial (rtgo_ctx::Trial) learn of it
 static int enqueue(rtgo_ctx* c, RenderKernel kernel, const LaunchParams& p, const Block& b, Pick& pk, bool canon, uint64_t rays_culled)
 {
 #ifdef RTGO_TIMELINE
@@ -1620,13 +1549,13 @@ static int enqueue(rtgo_ctx* c, RenderKernel kernel, const LaunchParams& p, cons
     if (c->timeline_waves > 16384) return fail(c, RTGO_E_UNSUPPORTED, "timeline buffer too small");
 #endif
     RTGO_HIP(c, hipSetDevice(c->device));
-    if (c->ev_pending == rtgo_ctx::kEvRing)
-        if (const int rc = harvest_events(c, 1)) return rc;
-    const int slot = c->ev_head;
-    RTGO_HIP(c, hipEventRecord(c->ev_start[slot], c->stream));
-    hipLaunchKernelGGL(kernel, dim3(b.grid), dim3(b.block), b.lds, c->stream, p, p.fprims);
-    RTGO_HIP(c, hipGetLastError());
-    RTGO_HIP(c, hipEventRecord(c->ev_stop[slot], c->stream));
+    int slot = 0;
+    const int rc = timed_launch(c, slot, [&]() -> int {
+        hipLaunchKernelGGL(kernel, dim3(b.grid), dim3(b.block), b.lds, c->stream, p, p.fprims);
+        RTGO_HIP(c, hipGetLastError());
+        return RTGO_OK;
+    });
+    if (rc) return rc;
     if (pk.n_cand > 1) {
         rtgo_ctx::Trial& t = c->trial;
         if (!pk.new_key.empty()) {
@@ -1644,9 +1573,6 @@ static int enqueue(rtgo_ctx* c, RenderKernel kernel, const LaunchParams& p, cons
     }
     c->queue_set = 1 - c->queue_set;
     c->rays_culled += rays_culled;
-    c->ev_head = (c->ev_head + 1) % rtgo_ctx::kEvRing;
-    c->ev_pending++;
-    c->launches++;
     if (canon) c->launches_canonical++;
     c->last_variant = (pk.stream ? 1u : 0u) | (pk.structure == 1 ? 2u : 0u) | (canon ? 4u : 0u) | (pk.trial_k >= 0 ? 8u : 0u) | (pk.structure == 2 ? 16u : 0u) |
                       (p.emit_n > 0 ? 64u : 0u);
@@ -1660,12 +1586,12 @@ static int launch_large(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p, const
 {
     const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
     const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
-    const Rect r = f->collect_stats != 1 ? box_screen_rect(c->bounds, p) : Rect{0, p.w, 0, p.h};
+    const Rect r = f->collect_stats != 1 ? box_screen_rect(c->scene.bounds, p) : Rect{0, p.w, 0, p.h};
     c->guard_reach = 0.0f;
     c->guard_quadric = 0.0f;
-    p.nodes = c->d_nodes;
-    p.prims = c->d_prims;
-    p.stack_depth = c->lbvh_depth > 0 ? c->lbvh_depth : 1;
+    p.nodes = c->scene.d_nodes.get();
+    p.prims = c->scene.d_prims.get();
+    p.stack_depth = c->scene.lbvh_depth > 0 ? c->scene.lbvh_depth : 1;
     uint32_t strip_px = 0;
     uint64_t units_hot = 0;
     if (const int rc = schedule(c, nn, r, p, strip_px, units_hot)) return rc;
@@ -1678,7 +1604,7 @@ static int launch_large(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p, const
     const RenderKernel kernel = find_kernel(path, true, 4, false, stats, false, false, true);
     if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
     const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0);
-    c->seeds_ok = false;
+    c->seeds.ok = false;
     Pick pk;
     if (const int rc = enqueue(c, kernel, p, b, pk, true, culled * nn)) return rc;
     c->last_variant |= 32u;
@@ -1691,19 +1617,19 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     const Knobs kn;
     LaunchParams p;
     if (const int rc = frame_params(c, f, p)) return rc;
-    if (c->large) return launch_large(c, f, p, kn);
+    if (c->scene.large) return launch_large(c, f, p, kn);
     const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
     const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
     // collect_stats 1: the instrumented kernel traces every pixel (V, T, h over ALL rays); 2: it culls like the timed
     // kernel, so that the counters describe the traversed rays only
     const bool cull = f->collect_stats != 1;
-    const Rect r = cull ? box_screen_rect(c->bounds, p) : Rect{0, p.w, 0, p.h};
+    const Rect r = cull ? box_screen_rect(c->scene.bounds, p) : Rect{0, p.w, 0, p.h};
     const bool canon = far_field_guard(c, p, kn) || stats;
     Pick pk;
     if (const int rc = choose_candidate(c, f, p, nn, kn, canon, pk)) return rc;
     const bool use_alt = pk.structure == 1, use_grid = pk.structure == 2;
-    walk_params(c, c->tree[use_alt ? 1 : 0], canon, use_grid, p);
-    last_ray_params(c, c->tree[use_alt ? 1 : 0], path, canon, use_grid, kn, p);
+    walk_params(c, c->scene.tree[use_alt ? 1 : 0], canon, use_grid, p);
+    last_ray_params(c, c->scene.tree[use_alt ? 1 : 0], path, canon, use_grid, kn, p);
     uint32_t strip_px = 0;
     uint64_t units_hot = 0;
     if (const int rc = schedule(c, nn, r, p, strip_px, units_hot)) return rc;
@@ -1711,7 +1637,7 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     if (cull && p.n_hot > 0)
         if (const int rc = update_hot_mask(c, strip_px, p, mask_cold_pixels)) return rc;
     if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
-    const bool frames = path && !canon && c->quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
+    const bool frames = path && !canon && c->scene.quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
     Block b;
     if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b)) return rc;
     if (kn.debug)
@@ -1722,14 +1648,14 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels;
     std::vector<uint32_t> seeds_key;
     if (const int rc = plan_seeds(c, p, strip_px, kernel_has_seed_pass(canon, b.wpe, pk.stream), seeds_key)) return rc;
-    c->seeds_ok = false;   // (until this launch is on the stream)
+    c->seeds.ok = false;   // (until this launch is on the stream)
     if (const int rc = enqueue(c, kernel, p, b, pk, canon, culled * nn)) return rc;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
-        c->seeds_read = 1 - c->seeds_read;
-        c->seeds_frame = p.frame + 1u;
-        c->seeds_key = std::move(seeds_key);
-        c->seeds_ok = true;
+        c->seeds.read = 1 - c->seeds.read;
+        c->seeds.frame = p.frame + 1u;
+        c->seeds.key = std::move(seeds_key);
+        c->seeds.ok = true;
     }
     return RTGO_OK;
 }
@@ -1764,10 +1690,10 @@ int rtgo_assemble_bands(rtgo_ctx* c, void* hip_stream, const void* d_gathered, v
 // the two sets of tile-queue heads of the whitted launches (allocated once, zero)
 static int whitted_tile_heads(rtgo_ctx* c)
 {
-    if (!c->w_tile_counters) {
-        const size_t heads_bytes = 2 * (size_t)whitted::kTileHeads * whitted::kTileHeadStride * sizeof(unsigned int);
-        RTGO_HIP(c, hipMalloc(&c->w_tile_counters, heads_bytes));
-        RTGO_HIP(c, hipMemsetAsync(c->w_tile_counters, 0, heads_bytes, c->stream));
+    if (!c->w_tile_counters.get()) {
+        const size_t heads = 2 * (size_t)whitted::kTileHeads * whitted::kTileHeadStride;
+        RTGO_HIP(c, c->w_tile_counters.alloc(heads));
+        RTGO_HIP(c, hipMemsetAsync(c->w_tile_counters.get(), 0, heads * sizeof(unsigned int), c->stream));
         RTGO_HIP(c, hipStreamSynchronize(c->stream));
     }
     return RTGO_OK;
@@ -1859,41 +1785,32 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
     if (rc0) return rc0;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    free_mesh(c);
-    const size_t vb = (size_t)n_vertices * 3 * sizeof(float), ib = (size_t)n_triangles * 3 * sizeof(unsigned int);
-    RTGO_HIP(c, hipMalloc(&c->w_positions, vb));
-    RTGO_HIP(c, hipMemcpyAsync(c->w_positions, positions, vb, hipMemcpyHostToDevice, c->stream));
-    if (normals) {
-        RTGO_HIP(c, hipMalloc(&c->w_normals, vb));
-        RTGO_HIP(c, hipMemcpyAsync(c->w_normals, normals, vb, hipMemcpyHostToDevice, c->stream));
-    }
-    RTGO_HIP(c, hipMalloc(&c->w_indices, ib));
-    RTGO_HIP(c, hipMemcpyAsync(c->w_indices, indices, ib, hipMemcpyHostToDevice, c->stream));
-    if (material_of_triangle) {
-        RTGO_HIP(c, hipMalloc(&c->w_tri_material, (size_t)n_triangles * sizeof(unsigned int)));
-        RTGO_HIP(c, hipMemcpyAsync(c->w_tri_material, material_of_triangle, (size_t)n_triangles * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
-    }
-    RTGO_HIP(c, hipMalloc(&c->w_materials, (size_t)n_materials * sizeof(whitted::Pbr)));
-    RTGO_HIP(c, hipMemcpyAsync(c->w_materials, materials, (size_t)n_materials * sizeof(whitted::Pbr), hipMemcpyHostToDevice, c->stream));
-    RTGO_HIP(c, hipMalloc(&c->w_nodes, (size_t)(2 * n_triangles - 1) * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->w_recs, (size_t)n_triangles * 4 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->w_tris, (size_t)n_triangles * 3 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->w_qrecs, (size_t)n_triangles * 2 * sizeof(uint4)));
-    RTGO_HIP(c, hipMalloc(&c->w_tidx, (size_t)n_triangles * sizeof(uint2)));
-    RTGO_HIP(c, hipMalloc(&c->w_scratch, (size_t)(6 * n_triangles + 16 + 32 * n_triangles) * sizeof(int)));   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
+    c->wm = WhittedMesh();
+    WhittedMesh& wm = c->wm;
+    RTGO_HIP(c, wm.positions.upload(positions, (size_t)n_vertices * 3, c->stream));
+    if (normals) RTGO_HIP(c, wm.normals.upload(normals, (size_t)n_vertices * 3, c->stream));
+    RTGO_HIP(c, wm.indices.upload(indices, (size_t)n_triangles * 3, c->stream));
+    if (material_of_triangle) RTGO_HIP(c, wm.tri_material.upload(material_of_triangle, n_triangles, c->stream));
+    RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
+    RTGO_HIP(c, wm.nodes.alloc((size_t)(2 * n_triangles - 1) * 2));
+    RTGO_HIP(c, wm.recs.alloc((size_t)n_triangles * 4));
+    RTGO_HIP(c, wm.tris.alloc((size_t)n_triangles * 3));
+    RTGO_HIP(c, wm.qrecs.alloc((size_t)n_triangles * 2));
+    RTGO_HIP(c, wm.tidx.alloc(n_triangles));
+    RTGO_HIP(c, wm.scratch.alloc((size_t)(6 * n_triangles + 16 + 32 * n_triangles)));   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
     WhittedBuildMeta m;
-    const int rc = whitted_build(c, c->w_positions, c->w_indices, (int)n_triangles, c->w_nodes, c->w_scratch, c->w_recs, c->w_tris, c->w_qrecs, c->w_tidx, m,
-                                 "rtgo_whitted_set_mesh");
+    const int rc = whitted_build(c, wm.positions.get(), wm.indices.get(), (int)n_triangles, wm.nodes.get(), wm.scratch.get(), wm.recs.get(), wm.tris.get(),
+                                 wm.qrecs.get(), wm.tidx.get(), m, "rtgo_whitted_set_mesh");
     if (rc) return rc;
-    c->w_n_recs = m.n_recs;
-    c->w_n_vertices = (int)n_vertices;
-    c->w_grid_lo = m.grid_lo;
-    c->w_grid_step = m.grid_step;
-    c->w_walk_depth = m.walk_depth < 1 ? 1 : m.walk_depth;
+    wm.n_recs = m.n_recs;
+    wm.n_vertices = (int)n_vertices;
+    wm.grid_lo = m.grid_lo;
+    wm.grid_step = m.grid_step;
+    wm.walk_depth = m.walk_depth < 1 ? 1 : m.walk_depth;
     const int rc2 = whitted_tile_heads(c);
     if (rc2) return rc2;
-    c->w_triangles = (int)n_triangles;
-    c->w_n_materials = (int)n_materials;
+    wm.triangles = (int)n_triangles;
+    wm.n_materials = (int)n_materials;
     return RTGO_OK;
 }
 
@@ -1984,111 +1901,65 @@ static std::vector<unsigned int> whitted_box_indices(int n)
 }
 
 // the top level over prepared instances: build_kernel + sah_kernel over the instance boxes, the InstWalk records in leaf order, and the
-// stack both levels need.  Replaces the context's top level only once all of it succeeded.
+// stack both levels need.  Built aside: replaces the context's top level only once all of it succeeded.
 static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos, const rtgo_whitted_instance* inst,
                              const char* what)
 {
     const int n = (int)shade.size();
     const std::vector<unsigned int> box_idx = whitted_box_indices(n);
-    float* d_pos = nullptr;
-    unsigned int* d_idx = nullptr;
-    float4 *d_nodes = nullptr, *d_recs = nullptr, *d_tris = nullptr;
-    int* d_scratch = nullptr;
-    uint4* d_qrecs = nullptr;
-    uint2* d_tidx = nullptr;
-    whitted::InstWalk* d_inst = nullptr;
-    whitted::InstShade* d_shade = nullptr;
-    auto cleanup = [&]() {
-        release(d_pos);
-        release(d_idx);
-        release(d_nodes);
-        release(d_tris);
-        release(d_scratch);
-        release(d_qrecs);
-        release(d_tidx);
-    };
-    auto fail_all = [&](int rc) {
-        cleanup();
-        release(d_recs);
-        release(d_inst);
-        release(d_shade);
-        return rc;
-    };
-#define RTGO_TOP_HIP(x)                                                                                                    \
-    do {                                                                                                                   \
-        const hipError_t e_ = (x);                                                                                         \
-        if (e_ != hipSuccess) return fail_all(fail(c, RTGO_E_HIP_BASE + (int)e_, std::string(what) + ": " + hipGetErrorString(e_))); \
-    } while (0)
-    RTGO_TOP_HIP(hipMalloc(&d_pos, box_pos.size() * sizeof(float)));
-    RTGO_TOP_HIP(hipMalloc(&d_idx, box_idx.size() * sizeof(unsigned int)));
-    RTGO_TOP_HIP(hipMalloc(&d_nodes, (size_t)(2 * n - 1) * 2 * sizeof(float4)));
-    RTGO_TOP_HIP(hipMalloc(&d_recs, (size_t)n * 4 * sizeof(float4)));
-    RTGO_TOP_HIP(hipMalloc(&d_tris, (size_t)n * 3 * sizeof(float4)));
-    RTGO_TOP_HIP(hipMalloc(&d_qrecs, (size_t)n * 2 * sizeof(uint4)));
-    RTGO_TOP_HIP(hipMalloc(&d_tidx, (size_t)n * sizeof(uint2)));
-    RTGO_TOP_HIP(hipMalloc(&d_scratch, (size_t)(38 * n + 16) * sizeof(int)));
-    RTGO_TOP_HIP(hipMemcpyAsync(d_pos, box_pos.data(), box_pos.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RTGO_TOP_HIP(hipMemcpyAsync(d_idx, box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+    DeviceArray<float> d_pos;
+    DeviceArray<unsigned int> d_idx;
+    DeviceArray<float4> d_nodes, d_tris;
+    DeviceArray<int> d_scratch;
+    DeviceArray<uint4> d_qrecs;
+    DeviceArray<uint2> d_tidx;
+    WhittedTop top;
+    RTGO_HIP(c, d_pos.upload(box_pos.data(), box_pos.size(), c->stream));
+    RTGO_HIP(c, d_idx.upload(box_idx.data(), box_idx.size(), c->stream));
+    RTGO_HIP(c, d_nodes.alloc((size_t)(2 * n - 1) * 2));
+    RTGO_HIP(c, top.recs.alloc((size_t)n * 4));
+    RTGO_HIP(c, d_tris.alloc((size_t)n * 3));
+    RTGO_HIP(c, d_qrecs.alloc((size_t)n * 2));
+    RTGO_HIP(c, d_tidx.alloc(n));
+    RTGO_HIP(c, d_scratch.alloc((size_t)(38 * n + 16)));
     WhittedBuildMeta m;
-    const int rc = whitted_build(c, d_pos, d_idx, n, d_nodes, d_scratch, d_recs, d_tris, d_qrecs, d_tidx, m, what);
-    if (rc) return fail_all(rc);
+    const int rc = whitted_build(c, d_pos.get(), d_idx.get(), n, d_nodes.get(), d_scratch.get(), top.recs.get(), d_tris.get(), d_qrecs.get(), d_tidx.get(), m, what);
+    if (rc) return rc;
     // leaf order: build_kernel's Morton-ordered "triangles" carry the instance index in .w of their first corner
     std::vector<float4> order((size_t)3 * n);
-    RTGO_TOP_HIP(hipMemcpyAsync(order.data(), d_tris, order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTGO_TOP_HIP(hipStreamSynchronize(c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(order.data(), d_tris.get(), order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
     const int top_depth = m.n_recs > 0 ? m.walk_depth : 0;
-    const int depth = top_depth + c->w_mesh_depth;
+    const int depth = top_depth + c->wm.mesh_depth;
     if (depth > whitted::kMaxInstWalkDepth)
-        return fail_all(fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
-                                                        std::to_string(whitted::kMaxInstWalkDepth) + ")"));
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
+                                               std::to_string(whitted::kMaxInstWalkDepth) + ")");
     std::vector<whitted::InstWalk> walk((size_t)n);
     for (int pos = 0; pos < n; ++pos) {
         int i;
         std::memcpy(&i, &order[3 * pos].w, sizeof i);
-        const WhittedMeshInfo& mi = c->w_meshes[inst[i].mesh];
+        const WhittedMeshInfo& mi = c->wm.meshes[inst[i].mesh];
         walk[pos] = whitted::InstWalk{{shade[i].w2o[0], shade[i].w2o[1], shade[i].w2o[2]}, mi.rec_base, mi.tri_base, mi.root, i};
     }
-    RTGO_TOP_HIP(hipMalloc(&d_inst, walk.size() * sizeof(whitted::InstWalk)));
-    RTGO_TOP_HIP(hipMalloc(&d_shade, shade.size() * sizeof(whitted::InstShade)));
-    RTGO_TOP_HIP(hipMemcpyAsync(d_inst, walk.data(), walk.size() * sizeof(whitted::InstWalk), hipMemcpyHostToDevice, c->stream));
-    RTGO_TOP_HIP(hipMemcpyAsync(d_shade, shade.data(), shade.size() * sizeof(whitted::InstShade), hipMemcpyHostToDevice, c->stream));
-    RTGO_TOP_HIP(hipStreamSynchronize(c->stream));
-#undef RTGO_TOP_HIP
-    cleanup();
-    free_top(c);
-    c->w_top_recs = d_recs;
-    c->w_inst = d_inst;
-    c->w_inst_shade = d_shade;
-    c->w_n_top_recs = m.n_recs;
-    c->w_n_instances = n;
-    c->w_walk_depth = depth < 1 ? 1 : depth;
+    RTGO_HIP(c, top.inst.upload(walk.data(), walk.size(), c->stream));
+    RTGO_HIP(c, top.shade.upload(shade.data(), shade.size(), c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    top.n_recs = m.n_recs;
+    top.n_instances = n;
+    c->wm.top = std::move(top);
+    c->wm.walk_depth = depth < 1 ? 1 : depth;
     return RTGO_OK;
 }
 
 // Device scratch of the clustered builds of one rtgo_whitted_set_scene, sized for its largest clustered mesh (freed on every return).
 struct WhittedBigScratch {
-    unsigned long long *keys = nullptr, *keys_alt = nullptr;
-    unsigned int *hist = nullptr, *cidx = nullptr, *mid_idx = nullptr;
-    float *partial = nullptr, *bounds = nullptr, *mid_pos = nullptr;
-    int* crec = nullptr;
-    float4* mid_tris = nullptr;
-    uint4* mid_qrecs = nullptr;
-    uint2* mid_tidx = nullptr;
-    ~WhittedBigScratch()
-    {
-        release(keys);
-        release(keys_alt);
-        release(hist);
-        release(cidx);
-        release(mid_idx);
-        release(partial);
-        release(bounds);
-        release(mid_pos);
-        release(crec);
-        release(mid_tris);
-        release(mid_qrecs);
-        release(mid_tidx);
-    }
+    DeviceArray<unsigned long long> keys, keys_alt;
+    DeviceArray<unsigned int> hist, cidx, mid_idx;
+    DeviceArray<float> partial, bounds, mid_pos;
+    DeviceArray<int> crec;
+    DeviceArray<float4> mid_tris;
+    DeviceArray<uint4> mid_qrecs;
+    DeviceArray<uint2> mid_tidx;
 };
 
 // One clustered mesh (n > kMaxTriangles triangles; rtgo_whitted_big.h), in its slices of the context's arrays: Morton order over the
@@ -2101,24 +1972,25 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
 {
     using namespace whitted;
     const int ncl = (n + kClusterTris - 1) / kClusterTris;
-    const float* positions = c->w_positions + 3 * (size_t)mi.vert_base;
-    const unsigned int* indices = c->w_indices + 3 * (size_t)mi.tri_base;
+    WhittedMesh& wm = c->wm;
+    const float* positions = wm.positions.get() + 3 * (size_t)mi.vert_base;
+    const unsigned int* indices = wm.indices.get() + 3 * (size_t)mi.tri_base;
     // Morton keys over the mesh's bounds, sorted by four stable passes over the code's bytes
     const int nbb = std::min(1024, (n + 1023) / 1024);
-    hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, positions, indices, n, bs.partial);
-    hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)bs.partial, nbb, bs.bounds);
-    hipLaunchKernelGGL(big_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, positions, indices, n, (const float*)bs.bounds, bs.keys);
+    hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, positions, indices, n, bs.partial.get());
+    hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)bs.partial.get(), nbb, bs.bounds.get());
+    hipLaunchKernelGGL(big_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, positions, indices, n, (const float*)bs.bounds.get(), bs.keys.get());
     const int nb = (n + kRadixTile - 1) / kRadixTile;
-    unsigned long long *src = bs.keys, *dst = bs.keys_alt;
+    unsigned long long *src = bs.keys.get(), *dst = bs.keys_alt.get();
     for (int shift = 32; shift < 64; shift += 8) {
-        hipLaunchKernelGGL(radix_count_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift, bs.hist);
-        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bs.hist, 256 * nb);
+        hipLaunchKernelGGL(radix_count_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift, bs.hist.get());
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bs.hist.get(), 256 * nb);
         hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift,
-                           (const unsigned int*)bs.hist, dst);
+                           (const unsigned int*)bs.hist.get(), dst);
         std::swap(src, dst);
     }
     const unsigned long long* sorted = src;   // (four passes: back in bs.keys)
-    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, sorted, n, indices, bs.cidx);
+    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, sorted, n, indices, bs.cidx.get());
     RTGO_HIP(c, hipGetLastError());
     // the clusters
     std::vector<int> crec(ncl), croot(ncl);
@@ -2126,33 +1998,34 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
     for (int k = 0; k < ncl; ++k) {
         const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
         WhittedBuildMeta m;
-        const int rc = whitted_build(c, positions, bs.cidx + 3 * (size_t)s, nc, c->w_nodes, c->w_scratch, c->w_recs + 4 * (size_t)rec,
-                                     c->w_tris + 3 * ((size_t)mi.tri_base + s), c->w_qrecs + 2 * ((size_t)mi.tri_base + s), c->w_tidx + mi.tri_base + s, m, what);
+        const int rc = whitted_build(c, positions, bs.cidx.get() + 3 * (size_t)s, nc, wm.nodes.get(), wm.scratch.get(), wm.recs.get() + 4 * (size_t)rec,
+                                     wm.tris.get() + 3 * ((size_t)mi.tri_base + s), wm.qrecs.get() + 2 * ((size_t)mi.tri_base + s), wm.tidx.get() + mi.tri_base + s, m,
+                                     what);
         if (rc) return rc;
         crec[k] = rec;
         croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
         cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
         rec += m.n_recs;
     }
-    hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->w_tris + 3 * (size_t)mi.tri_base, sorted, n, ncl);
+    hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, wm.tris.get() + 3 * (size_t)mi.tri_base, sorted, n, ncl);
     RTGO_HIP(c, hipGetLastError());
     // the mid level over the clusters' boxes
     const std::vector<unsigned int> box_idx = whitted_box_indices(ncl);
-    RTGO_HIP(c, hipMemcpyAsync(bs.crec, crec.data(), ncl * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    RTGO_HIP(c, hipMemcpyAsync(bs.mid_idx, box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)c->w_recs, (const int*)bs.crec, ncl,
-                       bs.mid_pos);
+    RTGO_HIP(c, hipMemcpyAsync(bs.crec.get(), crec.data(), ncl * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(bs.mid_idx.get(), box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)wm.recs.get(), (const int*)bs.crec.get(), ncl,
+                       bs.mid_pos.get());
     RTGO_HIP(c, hipGetLastError());
     WhittedBuildMeta m;
-    const int rc = whitted_build(c, bs.mid_pos, bs.mid_idx, ncl, c->w_nodes, c->w_scratch, c->w_recs + 4 * (size_t)mi.rec_base, bs.mid_tris, bs.mid_qrecs,
-                                 bs.mid_tidx, m, what);
+    const int rc = whitted_build(c, bs.mid_pos.get(), bs.mid_idx.get(), ncl, wm.nodes.get(), wm.scratch.get(), wm.recs.get() + 4 * (size_t)mi.rec_base,
+                                 bs.mid_tris.get(), bs.mid_qrecs.get(), bs.mid_tidx.get(), m, what);
     if (rc) return rc;
     // leaf order: the mid level's Morton-ordered "triangles" carry the cluster in .w of their first corner
     std::vector<float4> order((size_t)3 * ncl), root_rec(4);
     std::vector<float> boxes((size_t)6 * ncl);
-    RTGO_HIP(c, hipMemcpyAsync(order.data(), bs.mid_tris, order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.mid_pos, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (m.n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), c->w_recs + 4 * (size_t)mi.rec_base, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(order.data(), bs.mid_tris.get(), order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.mid_pos.get(), boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (m.n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), wm.recs.get() + 4 * (size_t)mi.rec_base, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     const int tbase = (int)table.size();
     for (int pos = 0; pos < ncl; ++pos) {
@@ -2250,40 +2123,35 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
     }
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    free_mesh(c);
-    auto upload = [&](auto*& d, const auto& v) -> hipError_t {
-        hipError_t e = hipMalloc(&d, v.size() * sizeof(v[0]));
-        if (e == hipSuccess) e = hipMemcpyAsync(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream);
-        return e;
-    };
-    RTGO_HIP(c, upload(c->w_positions, pos));
-    RTGO_HIP(c, upload(c->w_normals, nrm));
-    RTGO_HIP(c, upload(c->w_texcoords, uv));
-    RTGO_HIP(c, upload(c->w_indices, idx));
-    RTGO_HIP(c, upload(c->w_tri_material, tmat));
-    RTGO_HIP(c, hipMalloc(&c->w_materials, (size_t)n_materials * sizeof(whitted::Pbr)));
-    RTGO_HIP(c, hipMemcpyAsync(c->w_materials, materials, (size_t)n_materials * sizeof(whitted::Pbr), hipMemcpyHostToDevice, c->stream));
-    RTGO_HIP(c, hipMalloc(&c->w_nodes, (size_t)(2 * max_tri - 1) * 2 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->w_scratch, (size_t)(38 * max_tri + 16) * sizeof(int)));
-    RTGO_HIP(c, hipMalloc(&c->w_recs, n_tri * 4 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->w_tris, n_tri * 3 * sizeof(float4)));
-    RTGO_HIP(c, hipMalloc(&c->w_qrecs, n_tri * 2 * sizeof(uint4)));
-    RTGO_HIP(c, hipMalloc(&c->w_tidx, n_tri * sizeof(uint2)));
+    c->wm = WhittedMesh();
+    WhittedMesh& wm = c->wm;
+    RTGO_HIP(c, wm.positions.upload(pos.data(), pos.size(), c->stream));
+    RTGO_HIP(c, wm.normals.upload(nrm.data(), nrm.size(), c->stream));
+    RTGO_HIP(c, wm.texcoords.upload(uv.data(), uv.size(), c->stream));
+    RTGO_HIP(c, wm.indices.upload(idx.data(), idx.size(), c->stream));
+    RTGO_HIP(c, wm.tri_material.upload(tmat.data(), tmat.size(), c->stream));
+    RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
+    RTGO_HIP(c, wm.nodes.alloc((size_t)(2 * max_tri - 1) * 2));
+    RTGO_HIP(c, wm.scratch.alloc((size_t)(38 * max_tri + 16)));
+    RTGO_HIP(c, wm.recs.alloc(n_tri * 4));
+    RTGO_HIP(c, wm.tris.alloc(n_tri * 3));
+    RTGO_HIP(c, wm.qrecs.alloc(n_tri * 2));
+    RTGO_HIP(c, wm.tidx.alloc(n_tri));
     WhittedBigScratch bs;
     if (max_big > 0) {
         const int ncl = (max_big + whitted::kClusterTris - 1) / whitted::kClusterTris, nb = (max_big + whitted::kRadixTile - 1) / whitted::kRadixTile;
-        RTGO_HIP(c, hipMalloc(&bs.keys, (size_t)max_big * sizeof(unsigned long long)));
-        RTGO_HIP(c, hipMalloc(&bs.keys_alt, (size_t)max_big * sizeof(unsigned long long)));
-        RTGO_HIP(c, hipMalloc(&bs.hist, (size_t)256 * nb * sizeof(unsigned int)));
-        RTGO_HIP(c, hipMalloc(&bs.cidx, (size_t)3 * max_big * sizeof(unsigned int)));
-        RTGO_HIP(c, hipMalloc(&bs.partial, (size_t)6 * 1024 * sizeof(float)));
-        RTGO_HIP(c, hipMalloc(&bs.bounds, 6 * sizeof(float)));
-        RTGO_HIP(c, hipMalloc(&bs.crec, (size_t)ncl * sizeof(int)));
-        RTGO_HIP(c, hipMalloc(&bs.mid_pos, (size_t)6 * ncl * sizeof(float)));
-        RTGO_HIP(c, hipMalloc(&bs.mid_idx, (size_t)3 * ncl * sizeof(unsigned int)));
-        RTGO_HIP(c, hipMalloc(&bs.mid_tris, (size_t)3 * ncl * sizeof(float4)));
-        RTGO_HIP(c, hipMalloc(&bs.mid_qrecs, (size_t)2 * ncl * sizeof(uint4)));
-        RTGO_HIP(c, hipMalloc(&bs.mid_tidx, (size_t)ncl * sizeof(uint2)));
+        RTGO_HIP(c, bs.keys.alloc(max_big));
+        RTGO_HIP(c, bs.keys_alt.alloc(max_big));
+        RTGO_HIP(c, bs.hist.alloc((size_t)256 * nb));
+        RTGO_HIP(c, bs.cidx.alloc((size_t)3 * max_big));
+        RTGO_HIP(c, bs.partial.alloc((size_t)6 * 1024));
+        RTGO_HIP(c, bs.bounds.alloc(6));
+        RTGO_HIP(c, bs.crec.alloc(ncl));
+        RTGO_HIP(c, bs.mid_pos.alloc((size_t)6 * ncl));
+        RTGO_HIP(c, bs.mid_idx.alloc((size_t)3 * ncl));
+        RTGO_HIP(c, bs.mid_tris.alloc((size_t)3 * ncl));
+        RTGO_HIP(c, bs.mid_qrecs.alloc((size_t)2 * ncl));
+        RTGO_HIP(c, bs.mid_tidx.alloc(ncl));
     }
     std::vector<int4> table;
     // bottom level: each mesh's own structure, as rtgo_whitted_set_mesh builds it, in its slice of the arrays (a clustered mesh: its
@@ -2295,18 +2163,18 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
         if (mi.clustered) {
             rc = whitted_build_clustered(c, mi, nt, bs, table, "rtgo_whitted_set_scene");
             if (rc) {
-                free_mesh(c);
+                c->wm = WhittedMesh();
                 return rc;
             }
             mesh_depth = std::max(mesh_depth, mi.depth);
             continue;
         }
         WhittedBuildMeta m;
-        rc = whitted_build(c, c->w_positions + 3 * (size_t)mi.vert_base, c->w_indices + 3 * (size_t)mi.tri_base, nt, c->w_nodes, c->w_scratch,
-                           c->w_recs + 4 * (size_t)mi.rec_base, c->w_tris + 3 * (size_t)mi.tri_base, c->w_qrecs + 2 * (size_t)mi.tri_base,
-                           c->w_tidx + mi.tri_base, m, "rtgo_whitted_set_scene");
+        rc = whitted_build(c, wm.positions.get() + 3 * (size_t)mi.vert_base, wm.indices.get() + 3 * (size_t)mi.tri_base, nt, wm.nodes.get(), wm.scratch.get(),
+                           wm.recs.get() + 4 * (size_t)mi.rec_base, wm.tris.get() + 3 * (size_t)mi.tri_base, wm.qrecs.get() + 2 * (size_t)mi.tri_base,
+                           wm.tidx.get() + mi.tri_base, m, "rtgo_whitted_set_scene");
         if (rc) {
-            free_mesh(c);
+            c->wm = WhittedMesh();
             return rc;
         }
         mi.root = m.n_recs > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
@@ -2314,37 +2182,36 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
         mesh_depth = std::max(mesh_depth, mi.depth);
     }
     if (!table.empty()) {
-        RTGO_HIP(c, hipMalloc(&c->w_clusters, table.size() * sizeof(int4)));
-        RTGO_HIP(c, hipMemcpyAsync(c->w_clusters, table.data(), table.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream));
+        RTGO_HIP(c, wm.clusters.upload(table.data(), table.size(), c->stream));
         // the clustered meshes' boxes took in their mid levels' boxes: the instance boxes again from them (the checks passed above)
         rc = whitted_prepare_instances(c, info, n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_scene");
         if (rc) {
-            free_mesh(c);
+            c->wm = WhittedMesh();
             return rc;
         }
     }
-    c->w_meshes = info;
-    c->w_mesh_depth = mesh_depth;
-    c->w_n_materials = (int)n_materials;
+    wm.meshes = info;
+    wm.mesh_depth = mesh_depth;
+    wm.n_materials = (int)n_materials;
     rc = whitted_build_top(c, shade, box_pos, instances, "rtgo_whitted_set_scene");
     if (rc == RTGO_OK) rc = whitted_tile_heads(c);
     if (rc) {
-        free_mesh(c);
+        c->wm = WhittedMesh();
         return rc;
     }
-    c->w_n_vertices = (int)n_vert;
-    c->w_instanced = true;
-    c->w_triangles = (int)std::min(n_tri, (size_t)0x7FFFFFFF);
+    wm.n_vertices = (int)n_vert;
+    wm.instanced = true;
+    wm.triangles = (int)std::min(n_tri, (size_t)0x7FFFFFFF);
     return RTGO_OK;
 }
 
 int rtgo_whitted_set_instances(rtgo_ctx* c, const rtgo_whitted_instance* instances, uint32_t n_instances)
 {
     if (!c) return RTGO_E_INVALID;
-    if (!c->w_instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_instances: no instanced scene (call rtgo_whitted_set_scene first)");
+    if (!c->wm.instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_instances: no instanced scene (call rtgo_whitted_set_scene first)");
     std::vector<whitted::InstShade> shade;
     std::vector<float> box_pos;
-    int rc = whitted_prepare_instances(c, c->w_meshes, (uint32_t)c->w_n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_instances");
+    int rc = whitted_prepare_instances(c, c->wm.meshes, (uint32_t)c->wm.n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_instances");
     if (rc) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
@@ -2354,18 +2221,17 @@ int rtgo_whitted_set_instances(rtgo_ctx* c, const rtgo_whitted_instance* instanc
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
 {
     if (!c) return RTGO_E_INVALID;
-    if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: no mesh (call rtgo_whitted_set_mesh first)");
-    if (c->w_instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: an instanced scene takes its texture coordinates per mesh (rtgo_whitted_set_scene)");
-    if (uv && n_vertices != (uint32_t)c->w_n_vertices) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_texcoords: one (u, v) per vertex of the mesh");
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->w_texcoords);
-    c->w_texcoords = nullptr;
-    if (uv) {
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: no mesh (call rtgo_whitted_set_mesh first)");
+    if (c->wm.instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: an instanced scene takes its texture coordinates per mesh (rtgo_whitted_set_scene)");
+    if (uv && n_vertices != (uint32_t)c->wm.n_vertices) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_texcoords: one (u, v) per vertex of the mesh");
+    if (uv)
         for (size_t k = 0; k < (size_t)n_vertices * 2; ++k)
             if (!std::isfinite(uv[k])) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_texcoords: non-finite coordinate");
-        RTGO_HIP(c, hipMalloc(&c->w_texcoords, (size_t)n_vertices * 2 * sizeof(float)));
-        RTGO_HIP(c, hipMemcpyAsync(c->w_texcoords, uv, (size_t)n_vertices * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    c->wm.texcoords.reset();
+    if (uv) {
+        RTGO_HIP(c, c->wm.texcoords.upload(uv, (size_t)n_vertices * 2, c->stream));
         RTGO_HIP(c, hipStreamSynchronize(c->stream));
     }
     return RTGO_OK;
@@ -2375,29 +2241,30 @@ int rtgo_whitted_set_material_textures(rtgo_ctx* c, uint32_t material, const rtg
                                        const rtgo_texture* normal)
 {
     if (!c) return RTGO_E_INVALID;
-    if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_material_textures: no mesh (call rtgo_whitted_set_mesh first)");
-    if (material >= (uint32_t)c->w_n_materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_material_textures: material index beyond the table");
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_material_textures: no mesh (call rtgo_whitted_set_mesh first)");
+    if (material >= (uint32_t)c->wm.n_materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_material_textures: material index beyond the table");
     const rtgo_texture* in[3] = {base_color, metallic_roughness, normal};
     for (const rtgo_texture* t : in)
         if (t && (!t->rgba8 || t->width == 0 || t->height == 0 || t->width > 16384 || t->height > 16384))
             return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_material_textures: a texture needs texels and a size in [1, 16384]^2");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->w_mat_tex_host.empty()) c->w_mat_tex_host.assign((size_t)c->w_n_materials, whitted::MatTex{{nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}});
-    whitted::Tex out[3];
+    WhittedMesh& wm = c->wm;
+    std::array<DeviceArray<uchar4>, 3> texels;
+    whitted::Tex out[3] = {};
     for (int k = 0; k < 3; ++k) {
-        out[k] = whitted::Tex{nullptr, 0, 0};
         if (!in[k]) continue;
-        const size_t bytes = (size_t)in[k]->width * in[k]->height * 4;
-        void* d = nullptr;
-        RTGO_HIP(c, hipMalloc(&d, bytes));
-        c->w_texels.push_back(d);
-        RTGO_HIP(c, hipMemcpyAsync(d, in[k]->rgba8, bytes, hipMemcpyHostToDevice, c->stream));
-        out[k] = whitted::Tex{(const uchar4*)d, in[k]->width, in[k]->height};
+        RTGO_HIP(c, texels[k].upload((const uchar4*)in[k]->rgba8, (size_t)in[k]->width * in[k]->height, c->stream));
+        out[k] = whitted::Tex{texels[k].get(), in[k]->width, in[k]->height};
     }
-    c->w_mat_tex_host[material] = whitted::MatTex{out[0], out[1], out[2]};   // (texels of a replaced entry stay allocated until the next set_mesh)
-    if (!c->w_mat_tex) RTGO_HIP(c, hipMalloc(&c->w_mat_tex, (size_t)c->w_n_materials * sizeof(whitted::MatTex)));
-    RTGO_HIP(c, hipMemcpyAsync(c->w_mat_tex, c->w_mat_tex_host.data(), (size_t)c->w_n_materials * sizeof(whitted::MatTex), hipMemcpyHostToDevice, c->stream));
+    if (!wm.mat_tex.get()) RTGO_HIP(c, wm.mat_tex.alloc((size_t)wm.n_materials));
+    if (wm.mat_tex_host.empty()) {
+        wm.mat_tex_host.assign((size_t)wm.n_materials, whitted::MatTex{{nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}});
+        wm.texels.resize((size_t)wm.n_materials);
+    }
+    wm.mat_tex_host[material] = whitted::MatTex{out[0], out[1], out[2]};
+    wm.texels[material] = std::move(texels);   // (frees the texel arrays these replace: no launch is in flight)
+    RTGO_HIP(c, hipMemcpyAsync(wm.mat_tex.get(), wm.mat_tex_host.data(), (size_t)wm.n_materials * sizeof(whitted::MatTex), hipMemcpyHostToDevice, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     return RTGO_OK;
 }
@@ -2408,8 +2275,8 @@ int rtgo_whitted_set_lights(rtgo_ctx* c, const rtgo_point_light* lights, uint32_
     if (n > RTGO_MAX_LIGHTS) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_lights: at most " + std::to_string(RTGO_MAX_LIGHTS) + " lights");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (!c->w_lights) RTGO_HIP(c, hipMalloc(&c->w_lights, RTGO_MAX_LIGHTS * sizeof(whitted::PointLight)));
-    if (n > 0) RTGO_HIP(c, hipMemcpyAsync(c->w_lights, lights, n * sizeof(whitted::PointLight), hipMemcpyHostToDevice, c->stream));
+    if (!c->w_lights.get()) RTGO_HIP(c, c->w_lights.alloc(RTGO_MAX_LIGHTS));
+    if (n > 0) RTGO_HIP(c, hipMemcpyAsync(c->w_lights.get(), lights, n * sizeof(whitted::PointLight), hipMemcpyHostToDevice, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     c->w_n_lights = (int)n;
     return RTGO_OK;
@@ -2429,20 +2296,21 @@ static int whitted_enqueue_mesh(rtgo_ctx* c, const whitted::Frame& fr, size_t st
     whitted::Params p;
     std::memset(&p, 0, sizeof p);
     p.frame = fr;
-    p.recs = c->w_recs;
-    p.tris = c->w_tris;
-    p.qrecs = c->w_qrecs;
-    p.tidx = c->w_tidx;
-    p.n_vertices = c->w_n_vertices;
-    p.grid_lo = c->w_grid_lo;
-    p.grid_step = c->w_grid_step;
-    p.n_recs = c->w_n_recs;
-    p.n_triangles = c->w_triangles;
-    p.positions = c->w_positions;
-    p.normals = c->w_normals;
-    p.indices = c->w_indices;
-    p.tri_material = c->w_tri_material;
-    p.texcoords = c->w_texcoords;
+    const WhittedMesh& wm = c->wm;
+    p.recs = wm.recs.get();
+    p.tris = wm.tris.get();
+    p.qrecs = wm.qrecs.get();
+    p.tidx = wm.tidx.get();
+    p.n_vertices = wm.n_vertices;
+    p.grid_lo = wm.grid_lo;
+    p.grid_step = wm.grid_step;
+    p.n_recs = wm.n_recs;
+    p.n_triangles = wm.triangles;
+    p.positions = wm.positions.get();
+    p.normals = wm.normals.get();
+    p.indices = wm.indices.get();
+    p.tri_material = wm.tri_material.get();
+    p.texcoords = wm.texcoords.get();
     const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
     const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
     const dim3 grid(blocks), block(whitted::kRenderBlock);
@@ -2463,19 +2331,20 @@ static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Frame& fr, size
     whitted::InstParams q;
     std::memset(&q, 0, sizeof q);
     q.frame = fr;
-    q.top_recs = c->w_top_recs;
-    q.inst = c->w_inst;
-    q.shade = c->w_inst_shade;
-    q.n_top_recs = c->w_n_top_recs;
-    q.n_instances = c->w_n_instances;
-    q.recs = c->w_recs;
-    q.tris = c->w_tris;
-    q.clusters = c->w_clusters;
-    q.positions = c->w_positions;
-    q.normals = c->w_normals;
-    q.texcoords = c->w_texcoords;
-    q.indices = c->w_indices;
-    q.tri_material = c->w_tri_material;
+    const WhittedMesh& wm = c->wm;
+    q.top_recs = wm.top.recs.get();
+    q.inst = wm.top.inst.get();
+    q.shade = wm.top.shade.get();
+    q.n_top_recs = wm.top.n_recs;
+    q.n_instances = wm.top.n_instances;
+    q.recs = wm.recs.get();
+    q.tris = wm.tris.get();
+    q.clusters = wm.clusters.get();
+    q.positions = wm.positions.get();
+    q.normals = wm.normals.get();
+    q.texcoords = wm.texcoords.get();
+    q.indices = wm.indices.get();
+    q.tri_material = wm.tri_material.get();
     const size_t top_bytes = (size_t)q.n_top_recs * 4 * sizeof(float4) + (size_t)q.n_instances * sizeof(whitted::InstWalk);
     const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= whitted::kRenderLds;
     const size_t lds = stack_bytes + (in_lds ? top_bytes : 0);
@@ -2505,9 +2374,9 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
 {
     if (!c) return RTGO_E_INVALID;
     if (!f) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: NULL frame");
-    if (c->w_triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene)");
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene)");
     if (!c->have_camera) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no camera (call rtgo_set_camera)");
-    if (!c->d_accum || !c->d_image) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no output (call rtgo_resize or rtgo_bind_output)");
+    if (!c->out.accum || !c->out.image) return fail(c, RTGO_E_STATE, "rtgo_whitted_launch: no output (call rtgo_resize or rtgo_bind_output)");
     const uint32_t width = f->image_width, height = f->image_height;
     if (width == 0 || height == 0) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image empty");
     // the window and band of rtgo_launch's frame (rtgo_frame's fields, the same defaults)
@@ -2522,15 +2391,15 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     if (s.rank >= s.n_ranks) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: rank >= n_ranks");
     s.lw = win_w;
     s.lh = rtgo_local_rows(win_h, s.band_h, s.n_ranks, s.rank);
-    if ((uint64_t)s.lh * s.lw > c->pixels) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image larger than the output buffers");
+    if ((uint64_t)s.lh * s.lw > c->out.pixels) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: image larger than the output buffers");
     if (f->reserve_cus >= (uint32_t)c->num_cus) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: reserve_cus leaves no CU");
     if (s.lh == 0) return RTGO_OK;   // a rank that owns no row of the window: nothing to enqueue
     RTGO_HIP(c, hipSetDevice(c->device));
-    if (!c->w_lights) RTGO_HIP(c, hipMalloc(&c->w_lights, RTGO_MAX_LIGHTS * sizeof(whitted::PointLight)));
+    if (!c->w_lights.get()) RTGO_HIP(c, c->w_lights.alloc(RTGO_MAX_LIGHTS));
     whitted::Frame fr;
     std::memset(&fr, 0, sizeof fr);
-    fr.tile_counter = c->w_tile_counters + (size_t)c->w_launch_parity * whitted::kTileHeads * whitted::kTileHeadStride;
-    fr.tile_counter_next = c->w_tile_counters + (size_t)(1 - c->w_launch_parity) * whitted::kTileHeads * whitted::kTileHeadStride;
+    fr.tile_counter = c->w_tile_counters.get() + (size_t)c->w_launch_parity * whitted::kTileHeads * whitted::kTileHeadStride;
+    fr.tile_counter_next = c->w_tile_counters.get() + (size_t)(1 - c->w_launch_parity) * whitted::kTileHeads * whitted::kTileHeadStride;
     fr.tiles_x = (s.lw + 7) / 8;
     fr.tiles_y = (s.lh + 7) / 8;
     {
@@ -2542,12 +2411,12 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
         fr.tile_stride = (unsigned int)(stride % (nt > 1 ? nt : 2));
         if (fr.tile_stride == 0) fr.tile_stride = 1;
     }
-    fr.mat_tex = c->w_mat_tex;
-    fr.materials = c->w_materials;
-    fr.lights = c->w_lights;
+    fr.mat_tex = c->wm.mat_tex.get();
+    fr.materials = c->wm.materials.get();
+    fr.lights = c->w_lights.get();
     fr.n_lights = c->w_n_lights;
-    fr.accum = c->d_accum;
-    fr.image = c->d_image;
+    fr.accum = c->out.accum;
+    fr.image = c->out.image;
     fr.width = width;
     fr.height = height;
     fr.subframe = f->subframe_index;
@@ -2557,29 +2426,21 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     fr.V = c->V;
     fr.W = c->W;
     fr.miss = c->w_miss;
-    fr.counters = c->d_counters;
-    if (c->ev_pending == rtgo_ctx::kEvRing) {
-        int rc = harvest_events(c, 1);
-        if (rc) return rc;
-    }
-    const int slot = c->ev_head;
-    RTGO_HIP(c, hipEventRecord(c->ev_start[slot], c->stream));
+    fr.counters = c->d_counters.get();
     // one persistent workgroup per CU; its LDS holds the lanes' stacks and, beside them, as much of the structure as fits
-    const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)c->w_walk_depth * sizeof(unsigned short);
+    const size_t stack_bytes = (size_t)whitted::kRenderBlock * (size_t)c->wm.walk_depth * sizeof(unsigned short);
     const unsigned int n_tiles = fr.tiles_x * fr.tiles_y;
     unsigned int blocks = (n_tiles + (whitted::kRenderBlock / 64) - 1) / (whitted::kRenderBlock / 64);
     // reserve_cus as rtgo_launch takes it: at most half the CUs are left to other streams
     const unsigned int cus = (unsigned int)c->num_cus - (f->reserve_cus < (uint32_t)c->num_cus / 2 ? f->reserve_cus : (uint32_t)c->num_cus / 2);
     if (blocks > cus) blocks = cus;
-    const int rc = c->w_instanced ? whitted_enqueue_instanced(c, fr, stack_bytes, env_whitted_mode(), blocks)
-                                  : whitted_enqueue_mesh(c, fr, stack_bytes, env_whitted_mode(), blocks);
-    if (rc) return rc;
-    c->w_launch_parity = 1 - c->w_launch_parity;   // (only once the launch that zeroes the other head is in the stream)
-    RTGO_HIP(c, hipEventRecord(c->ev_stop[slot], c->stream));
-    c->ev_head = (c->ev_head + 1) % rtgo_ctx::kEvRing;
-    c->ev_pending++;
-    c->launches++;
-    return RTGO_OK;
+    int slot = 0;
+    return timed_launch(c, slot, [&]() -> int {
+        const int rc = c->wm.instanced ? whitted_enqueue_instanced(c, fr, stack_bytes, env_whitted_mode(), blocks)
+                                       : whitted_enqueue_mesh(c, fr, stack_bytes, env_whitted_mode(), blocks);
+        if (rc == RTGO_OK) c->w_launch_parity = 1 - c->w_launch_parity;   // (only once the launch that zeroes the other head is in the stream)
+        return rc;
+    });
 }
 
 int rtgo_sync(rtgo_ctx* c)
@@ -2594,7 +2455,7 @@ static int copy_out(rtgo_ctx* c, void* host, const void* dev, size_t bytes, size
 {
     if (!c || !host) return fail(c, RTGO_E_INVALID, "rtgo_read: NULL argument");
     if (!dev) return fail(c, RTGO_E_STATE, "rtgo_read: no output buffer");
-    if (bytes > c->pixels * elem) return fail(c, RTGO_E_INVALID, "rtgo_read: more bytes than the output holds");
+    if (bytes > c->out.pixels * elem) return fail(c, RTGO_E_INVALID, "rtgo_read: more bytes than the output holds");
     int rc = rtgo_sync(c);
     if (rc) return rc;
     RTGO_HIP(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2602,17 +2463,17 @@ static int copy_out(rtgo_ctx* c, void* host, const void* dev, size_t bytes, size
     return RTGO_OK;
 }
 
-int rtgo_read_image(rtgo_ctx* c, void* host, size_t bytes) { return copy_out(c, host, c ? c->d_image : nullptr, bytes, sizeof(uchar4)); }
-int rtgo_read_accum(rtgo_ctx* c, void* host, size_t bytes) { return copy_out(c, host, c ? c->d_accum : nullptr, bytes, sizeof(float4)); }
+int rtgo_read_image(rtgo_ctx* c, void* host, size_t bytes) { return copy_out(c, host, c ? c->out.image : nullptr, bytes, sizeof(uchar4)); }
+int rtgo_read_accum(rtgo_ctx* c, void* host, size_t bytes) { return copy_out(c, host, c ? c->out.accum : nullptr, bytes, sizeof(float4)); }
 
 int rtgo_write_accum(rtgo_ctx* c, const void* host, size_t bytes)
 {
     if (!c || !host) return fail(c, RTGO_E_INVALID, "rtgo_write_accum: NULL argument");
-    if (!c->d_accum) return fail(c, RTGO_E_STATE, "rtgo_write_accum: no output buffer");
-    if (bytes > c->pixels * sizeof(float4)) return fail(c, RTGO_E_INVALID, "rtgo_write_accum: too many bytes");
+    if (!c->out.accum) return fail(c, RTGO_E_STATE, "rtgo_write_accum: no output buffer");
+    if (bytes > c->out.pixels * sizeof(float4)) return fail(c, RTGO_E_INVALID, "rtgo_write_accum: too many bytes");
     int rc = rtgo_sync(c);
     if (rc) return rc;
-    RTGO_HIP(c, hipMemcpyAsync(c->d_accum, host, bytes, hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(c->out.accum, host, bytes, hipMemcpyHostToDevice, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     return RTGO_OK;
 }
@@ -2623,7 +2484,7 @@ int rtgo_get_stats(rtgo_ctx* c, rtgo_stats* out)
     int rc = rtgo_sync(c);
     if (rc) return rc;
     unsigned long long h[8];
-    RTGO_HIP(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(h, c->d_counters.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     out->rays_total = h[0];
     out->rays_occlusion = h[1];
@@ -2633,12 +2494,12 @@ int rtgo_get_stats(rtgo_ctx* c, rtgo_stats* out)
     out->last_launch_ms = c->last_ms;
     out->total_launch_ms = c->total_ms;
     out->launches = c->launches;
-    out->lbvh_depth = (uint32_t)c->lbvh_depth;
+    out->lbvh_depth = (uint32_t)c->scene.lbvh_depth;
     out->dbg_fast_boxes = h[5];
     out->dbg_fast_tests = h[6];
     out->rays_culled = c->rays_culled;
     out->launches_canonical = c->launches_canonical;
-    out->cuboid_groups = (uint32_t)c->tree[0].cuboid_groups;
+    out->cuboid_groups = (uint32_t)c->scene.tree[0].cuboid_groups;
     out->guard_reach = c->guard_reach;
     out->guard_quadric = c->guard_quadric;
     out->last_variant = c->last_variant;
@@ -2652,7 +2513,7 @@ int rtgo_reset_stats(rtgo_ctx* c)
     int rc = rtgo_sync(c);
     if (rc) return rc;
     // on the launch stream: a memset on the null stream is not ordered against a non-blocking stream's kernels
-    RTGO_HIP(c, hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
+    RTGO_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, 8 * sizeof(unsigned long long), c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     c->total_ms = 0.0f;
     c->last_ms = 0.0f;
@@ -2666,20 +2527,21 @@ int rtgo_reset_stats(rtgo_ctx* c)
 int rtgo_read_bvh(rtgo_ctx* c, void* host_nodes, size_t node_bytes, void* host_inv, size_t inv_bytes, void* host_aabbs, size_t aabb_bytes)
 {
     if (!c) return RTGO_E_INVALID;
-    if (c->n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_read_bvh: no scene");
-    const size_t n = c->n_prims;
+    const AnalyticScene& sc = c->scene;
+    if (sc.n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_read_bvh: no scene");
+    const size_t n = sc.n_prims;
     if ((host_nodes && node_bytes != (2 * n - 1) * 32) || (host_inv && inv_bytes != n * 48) || (host_aabbs && aabb_bytes != n * 24))
         return fail(c, RTGO_E_INVALID, "rtgo_read_bvh: buffer sizes must be (2n-1)*32, n*48, n*24");
     int rc = rtgo_sync(c);
     if (rc) return rc;
-    if (host_nodes) RTGO_HIP(c, hipMemcpy(host_nodes, c->d_nodes, node_bytes, hipMemcpyDeviceToHost));
+    if (host_nodes) RTGO_HIP(c, hipMemcpy(host_nodes, sc.d_nodes.get(), node_bytes, hipMemcpyDeviceToHost));
     if (host_inv) {
         std::vector<float4> tmp(6 * n);
-        RTGO_HIP(c, hipMemcpy(tmp.data(), c->d_prims, 6 * n * sizeof(float4), hipMemcpyDeviceToHost));
+        RTGO_HIP(c, hipMemcpy(tmp.data(), sc.d_prims.get(), 6 * n * sizeof(float4), hipMemcpyDeviceToHost));
         float* o = (float*)host_inv;
         for (size_t i = 0; i < n; ++i) std::memcpy(o + 12 * i, &tmp[6 * i], 48);
     }
-    if (host_aabbs) RTGO_HIP(c, hipMemcpy(host_aabbs, c->d_aabb, aabb_bytes, hipMemcpyDeviceToHost));
+    if (host_aabbs) RTGO_HIP(c, hipMemcpy(host_aabbs, sc.d_aabb.get(), aabb_bytes, hipMemcpyDeviceToHost));
     return RTGO_OK;
 }
 

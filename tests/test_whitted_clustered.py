@@ -376,3 +376,38 @@ def test_clustered_mesh_among_instances_whose_top_level_stays_in_l2(capi, oracle
     _same(_frames(_scene_ctx(capi, meshes, inst, mats, extra, cam, W, H), W, H, 2), got, "RTGO_WHITTED_MODE=0")
     monkeypatch.delenv("RTGO_WHITTED_MODE", raising=False)
     assert ref[2][1] > 0
+
+
+@pytest.mark.gpu
+def test_replaced_textures_and_closed_contexts_release_their_memory(capi, oracle):
+    """a material's base-colour texture set again 20 times (1024 x 1024 texels, 4 MB each) frees the texels it replaces; ten create /
+    set_scene (a clustered mesh among instances) / launch / close cycles give back what they took"""
+    import whitted_scene
+    from test_large_scenes import hip, mem_free
+    W, H = 32, 32
+    meshes, inst = [WI.ground(3.0, -0.4), BM.displaced_torus(200, 100)], [(EYE, 0, 0), (EYE, 1, 1)]
+    mats, extra = WI.materials(), WI.lights()
+    cam = whitted_scene.camera(oracle, W, H, eye=(0.6, 1.5, 2.2), lookat=(0.0, -0.1, 0.0))
+
+    def rendered():
+        ctx = _scene_ctx(capi, meshes, inst, mats, extra, cam, W, H)
+        ctx.whitted_launch(W, H, 0)
+        ctx.sync()
+        return ctx
+
+    rendered().close()   # (the first launch of the process loads the code objects)
+    Hp = hip()
+    tex = np.random.RandomState(3).randint(0, 256, size=(1024, 1024, 4)).astype(np.uint8)
+    ctx = rendered()
+    ctx.whitted_set_material_textures(1, tex)
+    free0 = mem_free(Hp)
+    for _ in range(20):
+        ctx.whitted_set_material_textures(1, tex)
+    free1 = mem_free(Hp)
+    ctx.close()
+    assert free0 - free1 < 8 << 20, ("textures", free0, free1)
+    free0 = mem_free(Hp)
+    for _ in range(10):
+        rendered().close()
+    free1 = mem_free(Hp)
+    assert free0 - free1 < 8 << 20, ("contexts", free0, free1)
