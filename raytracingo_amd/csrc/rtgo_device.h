@@ -1145,6 +1145,24 @@ __device__ __forceinline__ unsigned int opaque_lane()
     return l;
 }
 
+// The launch parameters at their place in the kernel-argument segment, through an address the compiler cannot hoist out of the
+// scope it is taken in: every field read through it is a scalar load there (SMEM, no vector issue slot).  Read through the kernel
+// argument itself, every field is loaded once at the kernel's start and held in an SGPR to the end; the 6-waves variant holds more of
+// them than the 102 SGPRs a wave has, and the rest went to VGPR lanes (a v_writelane_b32 per save, a v_readlane_b32 per restore).
+// p must be render_kernel's first argument: the only one at the start of the segment, where OPAQUE reads it.
+template <bool OPAQUE>
+__device__ __forceinline__ const LaunchParams& params_here(const LaunchParams& p)
+{
+    if constexpr (!OPAQUE) {
+        return p;
+    } else {
+        typedef const __attribute__((address_space(4))) LaunchParams* KernargParams;
+        unsigned long long a = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(a));
+        return *(const LaunchParams*)(KernargParams)a;
+    }
+}
+
 // running average + 8-bit image of one pixel: kernel.cu:236-246
 // ratio = 1.0f / (float)(p.frame + 1): the 6-waves variant reads it from LDS (s_cam) where it writes, instead of holding the
 // VALU division's result in a VGPR for the whole kernel
@@ -1248,8 +1266,9 @@ __device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned
 // straight from global memory (p.nodes / p.prims: the same layout and the same arithmetic as the LDS copy), nothing is staged; LDS holds
 // the stack (p.stack_depth entries: the scene's depth), the lights, the raygen constants and the sample table.
 template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false, bool GLOBAL = false>
-__global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p, const float4* __restrict__ g_fprims)
+__global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
+    const LaunchParams& p = p_arg;
     static_assert(!GLOBAL || (STATS && !FRAMES && !GRID && !STREAM), "the global-memory scene is walked by the canonical walk alone");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // LDS image.  STATS (canonical, instrumented walk): [nodes 2/node][prims 6/prim, SBT order][frames 2/prim][stack][lights]
@@ -1377,8 +1396,11 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     auto n_static = [&](unsigned int qq) { return ((gridDim.x + (unsigned int)kQueues - 1u - qq) / (unsigned int)kQueues) * wpb; };
     // the pull for the NEXT strip is issued before the current one is processed, so its ~1-2 us round trip hides behind work
     // (the head's offset is added when the value is USED: arithmetic on it here would make the wave wait for the atomic at once)
-    unsigned int pending = (blockIdx.x / (unsigned int)kQueues) * wpb + ((unsigned int)tid >> 6), pending_off = 0u;
+    // (LEAN: the wave's index in its workgroup as a wave-uniform value: an SGPR to the seed pass at the end instead of a VGPR of tid)
+    const unsigned int wave_in_block = LEAN ? __builtin_amdgcn_readfirstlane((unsigned int)tid >> 6) : (unsigned int)tid >> 6;
+    unsigned int pending = (blockIdx.x / (unsigned int)kQueues) * wpb + wave_in_block, pending_off = 0u;
     for (;;) {
+        const LaunchParams& p = params_here<LEAN>(p_arg);
         const unsigned int lane_q = lane_index();
         const unsigned int q_count = (p.n_tiles + (unsigned int)kQueues - 1u - q) / (unsigned int)kQueues;   // units in queue q
 #ifdef RTGO_TIMELINE
@@ -1403,12 +1425,12 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
             // (rare path: consume the result at once, so that no write to its register is pending where the paths join --
             // the compiler would otherwise wait for the common path's prefetch there as well)
             unsigned int stolen = 0;
-            if (lane == 0) stolen = atomicAdd(p.queue + kQueueStride * q, 1u);
+            if (lane_index() == 0u) stolen = atomicAdd(p.queue + kQueueStride * q, 1u);
             pending = __builtin_amdgcn_readfirstlane(stolen);
             pending_off = n_static(q);
             continue;
         }
-        if (lane == 0) pending = atomicAdd(p.queue + kQueueStride * q, 1u);
+        if (lane_index() == 0u) pending = atomicAdd(p.queue + kQueueStride * q, 1u);
         pending_off = n_static(q);
         // one queue entry = one STRIP: p.grab units side by side on a row (at most 64 pixels).  The strip's tea<16> pixel seeds
         // are computed once, one pixel per lane (the hash is 16 dependent rounds: ~160 instructions whether 4 or 64 lanes need
@@ -1456,6 +1478,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 #endif
 #pragma unroll 1
         for (unsigned int ui = 0; ui < p.grab; ++ui) {
+        const LaunchParams& p = params_here<LEAN>(p_arg);
         const unsigned int lx_u = strip_x0 + ui * P + pl0;
         if (strip_x0 + ui * P >= p.w) break;
         const bool in_range_u = pl0 < P && lx_u < p.w;
@@ -1466,6 +1489,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         if constexpr (!STREAM) {
 #pragma unroll 1
         for (unsigned int pass = 0; pass < passes; ++pass) {
+        const LaunchParams& p = params_here<LEAN>(p_arg);
         // the lane's pixel and sample, its first jitter input and its LCG seed: held through the unit (the values above), or
         // derived again per pass (LEAN; the *_u values are then dead)
         const unsigned int lane_p = lane_index();
@@ -1515,6 +1539,8 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 #endif
         }
         // color += payload, in sample order (kernel.cu:232): every lane of a pixel's group walks the group's results
+        {
+        const LaunchParams& p = params_here<LEAN>(p_arg);
         const unsigned int cnt = (nn - pass * nn_eff) < nn_eff ? (nn - pass * nn_eff) : nn_eff;
         if (__ballot(any_hit) == 0ull) {
             // every primary ray of the unit missed: all payloads are the background colour, no lane exchange needed
@@ -1526,6 +1552,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
                 const int src = (int)(group_base + q);
                 color = vadd(color, mk(__shfl(result.x, src, 64), __shfl(result.y, src, 64), __shfl(result.z, src, 64)));
             }
+        }
         }
         }  // pass
         } else {
@@ -1675,6 +1702,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         }
 
         if constexpr (!STREAM) {
+            const LaunchParams& p = params_here<LEAN>(p_arg);
             const unsigned int lane_w = lane_index(), pl = LEAN ? lane_w / nn_eff : pl0, kl = LEAN ? lane_w - pl * nn_eff : kl0;
             const unsigned int lx = LEAN ? strip_x0 + ui * P + pl : lx_u;
             if ((LEAN ? (pl < P && lx < p.w) : in_range_u) && kl == 0) {
@@ -1689,7 +1717,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     }
     // the queue has run dry: next frame's seeds
     if constexpr (SEEDS)
-        if (p.seeds_next != nullptr) next_frame_seeds(p, lane_index(), P, blockIdx.x * wpb + ((unsigned int)tid >> 6), gridDim.x * wpb);
+        if (params_here<LEAN>(p_arg).seeds_next != nullptr) next_frame_seeds(params_here<LEAN>(p_arg), lane_index(), P, blockIdx.x * wpb + wave_in_block, gridDim.x * wpb);
 
 #ifdef RTGO_TIMELINE
     if (lane == 0) {
@@ -1731,6 +1759,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     }
 #endif
     if (lane == 0) {
+        const LaunchParams& p = params_here<LEAN>(p_arg);
         atomicAdd(&p.counters[0], (unsigned long long)c_rays);
         if (!PATH) atomicAdd(&p.counters[1], (unsigned long long)c_occl);
         if (COUNT && p.count_stats) {
