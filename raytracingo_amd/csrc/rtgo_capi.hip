@@ -35,6 +35,11 @@ struct WhittedMeshInfo {
     int depth;                 // stack entries its walk needs (a clustered mesh: its mid level's + its deepest cluster's)
     uint32_t max_material;     // its largest material_of_triangle
     bool clustered;            // beyond kMaxTriangles triangles: a mid level over clusters (rtgo_whitted_big.h)
+    int n_tris;
+    // what each whitted_build of this mesh wrote into the context's arrays (rtgo_debug_build_digest): records [rec0, rec0 + n_recs) and
+    // their quantised forms at qrecs[2 tri0 ..] (tri0 < 0: none kept, a mid level's)
+    struct Built { int rec0, n_recs, tri0; };
+    std::vector<Built> built;
 };
 
 // The analytic scene (rtgo_set_scene, rtgo_set_large_scene): replaced as a whole, by assigning a fresh one
@@ -462,6 +467,104 @@ extern "C" int rtgo_debug_grid(rtgo_ctx* c, int32_t out[6])
     return RTGO_OK;
 }
 
+// FNV-1a (64 bit) over `bytes` of device memory, continuing from h
+static int digest_device(rtgo_ctx* c, const void* d, size_t bytes, uint64_t& h)
+{
+    std::vector<unsigned char> host(d ? bytes : 0);
+    if (!host.empty()) RTGO_HIP(c, hipMemcpy(host.data(), d, host.size(), hipMemcpyDeviceToHost));
+    for (const unsigned char b : host) h = (h ^ b) * 0x100000001B3ull;
+    return RTGO_OK;
+}
+static void digest_host(const void* p, size_t bytes, uint64_t& h)
+{
+    for (size_t k = 0; k < bytes; ++k) h = (h ^ static_cast<const unsigned char*>(p)[k]) * 0x100000001B3ull;
+}
+
+// diagnostic (tools/build_digest.py; not part of include/rtgo.h): one FNV-1a digest per device buffer the build kernels wrote for the
+// context's current scene, over the ranges the build defines (not allocation slack); *n_out = how many (at most `cap` are stored).
+//   analytic (whitted = 0): d_nodes, d_prims, d_frames, d_tight, d_aabb; then for tree[0] and tree[1]: d_fnodes (2 * n_fnodes float4),
+//     d_fprims, the decoded meta fields {canonical depth, bounds[6], fast_depth, n_small, n_fnodes, n_big_pairs, list_cub, cuboid_groups,
+//     tree_spheres, cub_a, cub_b}.  A scene of rtgo_set_large_scene has the first five only (frames and tight boxes empty).
+//   whitted (whitted = 1), one mesh: recs (4 * n_recs float4), qrecs (2 * n_recs), tris, tidx, {grid_lo, grid_step}, {n_recs, walk_depth};
+//     an instanced scene: per mesh recs, qrecs (each over the ranges its builds wrote, in build order), tris, tidx, {root, depth, n_recs
+//     of each build}; then the top level's recs and inst, then clusters.
+extern "C" int rtgo_debug_build_digest(rtgo_ctx* c, int whitted, uint64_t* out, uint32_t cap, uint32_t* n_out)
+{
+    if (!c || !out || !n_out) return fail(c, RTGO_E_INVALID, "rtgo_debug_build_digest: NULL argument");
+    if (const int rc = rtgo_sync(c)) return rc;
+    std::vector<uint64_t> d;
+    const uint64_t kBasis = 0xCBF29CE484222325ull;
+    int rc = RTGO_OK;
+    auto whole = [&](auto* p, size_t count) {
+        uint64_t h = kBasis;
+        if (rc == RTGO_OK) rc = digest_device(c, p, count * sizeof(*p), h);
+        d.push_back(h);
+    };
+    if (!whitted) {
+        const AnalyticScene& sc = c->scene;
+        const size_t n = sc.n_prims;
+        if (n == 0) return fail(c, RTGO_E_STATE, "rtgo_debug_build_digest: no scene");
+        whole(sc.d_nodes.get(), (2 * n - 1) * 2);
+        whole(sc.d_prims.get(), n * 6);
+        whole(sc.d_frames.get(), sc.large ? 0 : n * 2);
+        whole(sc.d_tight.get(), sc.large ? 0 : n * 6);
+        whole(sc.d_aabb.get(), n * 6);
+        for (int k = 0; k < 2 && !sc.large; ++k) {
+            const AnalyticScene::FastTree& t = sc.tree[k];
+            const bool have = t.d_fprims.get() != nullptr;
+            whole(t.d_fnodes.get(), have ? (size_t)2 * t.n_fnodes : 0);
+            whole(t.d_fprims.get(), have ? n * 4 : 0);
+            uint64_t h = kBasis;
+            const int ints[] = {sc.lbvh_depth, t.fast_depth, t.n_small, t.n_fnodes, t.n_big_pairs, t.list_cub, t.cuboid_groups, t.tree_spheres};
+            const float floats[] = {t.cub_a, t.cub_b};
+            digest_host(ints, sizeof ints, h);
+            digest_host(sc.bounds, sizeof sc.bounds, h);
+            digest_host(floats, sizeof floats, h);
+            d.push_back(h);
+        }
+    } else {
+        const WhittedMesh& wm = c->wm;
+        if (wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_debug_build_digest: no mesh");
+        if (!wm.instanced) {
+            whole(wm.recs.get(), (size_t)4 * wm.n_recs);
+            whole(wm.qrecs.get(), (size_t)2 * wm.n_recs);
+            whole(wm.tris.get(), (size_t)3 * wm.triangles);
+            whole(wm.tidx.get(), (size_t)wm.triangles);
+            uint64_t h = kBasis;
+            digest_host(&wm.grid_lo, sizeof wm.grid_lo, h);
+            digest_host(&wm.grid_step, sizeof wm.grid_step, h);
+            d.push_back(h);
+            h = kBasis;
+            const int ints[] = {wm.n_recs, wm.walk_depth};
+            digest_host(ints, sizeof ints, h);
+            d.push_back(h);
+        } else {
+            for (const WhittedMeshInfo& mi : wm.meshes) {
+                uint64_t hr = kBasis, hq = kBasis, hm = kBasis;
+                digest_host(&mi.root, sizeof mi.root, hm);
+                digest_host(&mi.depth, sizeof mi.depth, hm);
+                for (const WhittedMeshInfo::Built& b : mi.built) {
+                    if (rc == RTGO_OK) rc = digest_device(c, wm.recs.get() + 4 * (size_t)b.rec0, (size_t)4 * b.n_recs * sizeof(float4), hr);
+                    if (rc == RTGO_OK && b.tri0 >= 0) rc = digest_device(c, wm.qrecs.get() + 2 * (size_t)b.tri0, (size_t)2 * b.n_recs * sizeof(uint4), hq);
+                    digest_host(&b.n_recs, sizeof b.n_recs, hm);
+                }
+                d.push_back(hr);
+                d.push_back(hq);
+                whole(wm.tris.get() + 3 * (size_t)mi.tri_base, (size_t)3 * mi.n_tris);
+                whole(wm.tidx.get() + mi.tri_base, (size_t)mi.n_tris);
+                d.push_back(hm);
+            }
+            whole(wm.top.recs.get(), (size_t)4 * wm.top.n_recs);
+            whole(wm.top.inst.get(), (size_t)wm.top.n_instances);
+            whole(wm.clusters.get(), wm.clusters.size());
+        }
+    }
+    if (rc) return rc;
+    *n_out = (uint32_t)d.size();
+    for (size_t k = 0; k < d.size() && k < cap; ++k) out[k] = d[k];
+    return RTGO_OK;
+}
+
 #ifdef RTGO_CMPWALK
 // diagnostic build only (tools/cmp_walks.py): rays on which the canonical and the fast walk disagreed since the last call
 extern "C" int rtgo_debug_cmpwalk(rtgo_ctx* c, void* host, size_t bytes)
@@ -767,27 +870,27 @@ static int build_grid(rtgo_ctx* c, uint32_t n, const Knobs& kn)
 }
 
 // build_kernel for one big_frac into a structure of its own (the canonical LBVH, boxes and frames it also writes are the same for every
-// big_frac), and its 15 meta words decoded
-static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_frac, const Knobs& kn, AnalyticScene::FastTree& t, int meta[15])
+// big_frac), and its meta words decoded
+static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_frac, const Knobs& kn, AnalyticScene::FastTree& t, BuildMeta& meta)
 {
     AnalyticScene& sc = c->scene;
     RTGO_HIP(c, t.d_fnodes.alloc((2 * n - 1) * 2));
     RTGO_HIP(c, t.d_fprims.alloc(n * 4));
     hipLaunchKernelGGL(build_kernel, dim3(1), dim3(kMaxPrims), kBuildDynLds, c->stream, sc.d_prims_in.get(), sc.d_aabb.get(), have_aabbs, (int)n,
-                       sc.d_nodes.get(), sc.d_prims.get(), t.d_fnodes.get(), t.d_fprims.get(), c->leaf_budget, big_frac, c->d_meta.get(), sc.d_tight.get(),
+                       sc.d_nodes.get(), sc.d_prims.get(), t.d_fnodes.get(), t.d_fprims.get(), c->leaf_budget, big_frac, reinterpret_cast<BuildMeta*>(c->d_meta.get()), sc.d_tight.get(),
                        kn.no_cuboid ? 0 : 1, sc.d_frames.get());
     RTGO_HIP(c, hipGetLastError());
-    RTGO_HIP(c, hipMemcpyAsync(meta, c->d_meta.get(), 15 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(&meta, c->d_meta.get(), sizeof meta, hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    t.fast_depth = meta[1];
-    t.n_small = meta[2];
-    t.n_big_pairs = meta[9] & 0xFF;
-    t.list_cub = meta[9] >> 8;
-    t.cuboid_groups = meta[13] + (t.list_cub ? 1 : 0);
-    t.tree_spheres = (t.n_small > 0 && meta[14] == (1 << 3)) ? 1 : 0;   // (type 3 = sphere)
-    std::memcpy(&t.cub_a, &meta[11], sizeof(float));
-    std::memcpy(&t.cub_b, &meta[12], sizeof(float));
-    t.n_fnodes = meta[10];
+    t.fast_depth = meta.walk_depth;
+    t.n_small = meta.n_small;
+    t.n_big_pairs = group_pairs(meta.list_group);
+    t.list_cub = group_cert(meta.list_group);
+    t.cuboid_groups = meta.cuboid_leaves + (t.list_cub ? 1 : 0);
+    t.tree_spheres = (t.n_small > 0 && meta.tree_types == (1 << 3)) ? 1 : 0;   // (type 3 = sphere)
+    t.cub_a = meta.cub_a;
+    t.cub_b = meta.cub_b;
+    t.n_fnodes = meta.n_fnodes;
     return RTGO_OK;
 }
 
@@ -914,31 +1017,31 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     if (kn.leaf_budget >= 0) c->leaf_budget = kn.leaf_budget;
     RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
     if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
-    int meta[15];
+    BuildMeta meta;
     if (const int rc = build_fast_tree(c, n, aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, sc.tree[0], meta)) return rc;
     if (const int rc = emitter_cert(c, prims, n, sc.tree[0])) return rc;
     sc.tight.assign((size_t)n * 6, 0.0f);
     RTGO_HIP(c, hipMemcpyAsync(sc.tight.data(), sc.d_tight.get(), (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     const AnalyticScene::FastTree& t0 = sc.tree[0];
-    const int depth = meta[0];
+    const int depth = meta.canonical_depth;
     sc.lbvh_depth = depth;
     if (!t0.sane(n)) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: the fast walk's tree has " + std::to_string(t0.n_fnodes) + " nodes");
-    std::memcpy(sc.bounds, &meta[3], sizeof sc.bounds);
+    std::memcpy(sc.bounds, meta.tight_bounds, sizeof sc.bounds);
     if (!kn.pin_big) {
         // the alternative structure: big_frac 15 % (the canonical outputs, boxes and frames are rewritten with the same values)
-        int m2[15];
+        BuildMeta m2;
         if (const int rc = build_fast_tree(c, n, 1, 0.15f, kn, sc.tree[1], m2)) return rc;
         if (const int rc = emitter_cert(c, prims, n, sc.tree[1])) return rc;
         const AnalyticScene::FastTree& t1 = sc.tree[1];
         // (the same split of primitives = the same structure: nothing to try)
-        sc.have_alt = m2[0] == meta[0] && t1.sane(n) &&
+        sc.have_alt = m2.canonical_depth == meta.canonical_depth && t1.sane(n) &&
                       !(t1.n_small == t0.n_small && t1.n_fnodes == t0.n_fnodes && t1.n_big_pairs == t0.n_big_pairs && t1.list_cub == t0.list_cub);
     }
     if (const int rc = build_grid(c, n, kn)) return rc;
     if (kn.debug)
         std::fprintf(stderr, "rtgo_set_scene: %d primitives, %d in the fast walk's tree (%d nodes, depth %d), %d up front (%d pairs, cuboid certificate %d), %d cuboid leaves, margin coefficients %g %g, canonical LBVH depth %d\n",
-                     (int)n, t0.n_small, t0.n_fnodes, t0.fast_depth, (int)n - t0.n_small, t0.n_big_pairs, t0.list_cub, meta[13], t0.cub_a, t0.cub_b, depth);
+                     (int)n, t0.n_small, t0.n_fnodes, t0.fast_depth, (int)n - t0.n_small, t0.n_big_pairs, t0.list_cub, meta.cuboid_leaves, t0.cub_a, t0.cub_b, depth);
     if (depth > kStackDepth)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
                                                std::to_string(kStackDepth) + ")");
@@ -1703,13 +1806,7 @@ static int whitted_tile_heads(rtgo_ctx* c)
 // hierarchy, its records rebuilt top-down with the surface-area heuristic (sah_kernel) when the leaves fit its LDS, and the Morton
 // records again when the surface-area tree comes out deeper than the walk's stack.  nodes: (2n - 1) x 2 float4; scratch: 38 n + 16
 // ints; recs: n x 4 float4; tris: n x 3 float4; qrecs: n x 2 uint4; tidx: n uint2.  Synchronous.
-struct WhittedBuildMeta {   // build_kernel's out_meta as it lays it out (sah_kernel rewrites n_recs and walk_depth)
-    int depth;              // of the Morton hierarchy
-    int n_recs;             // records of the walk; 0: the structure is one leaf
-    int walk_depth;         // stack entries the walk needs
-    v3 grid_lo, grid_step;  // the grid of the compact records
-};
-static_assert(sizeof(WhittedBuildMeta) == 9 * sizeof(int), "build_kernel's out_meta");
+using whitted::WhittedBuildMeta;
 static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int* indices, int n, float4* nodes, int* scratch, float4* recs, float4* tris,
                          uint4* qrecs, uint2* tidx, WhittedBuildMeta& m, const char* what)
 {
@@ -1718,7 +1815,8 @@ static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int
     int* first_of = visit + n;
     int* count_of = first_of + n;
     int* rec_of = count_of + n;
-    int* meta = rec_of + n;
+    WhittedBuildMeta* meta = reinterpret_cast<WhittedBuildMeta*>(rec_of + n);
+    int* sah_scratch = rec_of + n + 16;
     const size_t keys_lds = (size_t)whitted::kMaxTriangles * sizeof(unsigned long long);
     hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, nodes,
                        parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, meta);
@@ -1729,7 +1827,7 @@ static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int
     const bool sah = !std::getenv("RTGO_WHITTED_NO_SAH") && sah_lds <= 150 * 1024;
     if (sah) {
         hipLaunchKernelGGL(whitted::sah_kernel, dim3(1), dim3(whitted::kBuildThreads), sah_lds, c->stream, n, (const float4*)nodes, (const int*)parent,
-                           (const int*)first_of, (const int*)count_of, meta + 16, recs, qrecs, meta);
+                           (const int*)first_of, (const int*)count_of, sah_scratch, recs, qrecs, meta);
         RTGO_HIP(c, hipGetLastError());
     }
     std::memset(&m, 0, sizeof m);
@@ -2002,6 +2100,7 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
                                      wm.tris.get() + 3 * ((size_t)mi.tri_base + s), wm.qrecs.get() + 2 * ((size_t)mi.tri_base + s), wm.tidx.get() + mi.tri_base + s, m,
                                      what);
         if (rc) return rc;
+        mi.built.push_back({rec, m.n_recs, mi.tri_base + s});
         crec[k] = rec;
         croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
         cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
@@ -2020,6 +2119,7 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
     const int rc = whitted_build(c, bs.mid_pos.get(), bs.mid_idx.get(), ncl, wm.nodes.get(), wm.scratch.get(), wm.recs.get() + 4 * (size_t)mi.rec_base,
                                  bs.mid_tris.get(), bs.mid_qrecs.get(), bs.mid_tidx.get(), m, what);
     if (rc) return rc;
+    mi.built.push_back({mi.rec_base, m.n_recs, -1});
     // leaf order: the mid level's Morton-ordered "triangles" carry the cluster in .w of their first corner
     std::vector<float4> order((size_t)3 * ncl), root_rec(4);
     std::vector<float> boxes((size_t)6 * ncl);
@@ -2094,6 +2194,7 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
         mi.root = 0;
         mi.depth = 0;
         mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
+        mi.n_tris = (int)q.n_triangles;
         n_vert += q.n_vertices;
         n_tri += q.n_triangles;
         if (mi.clustered) {
@@ -2177,6 +2278,7 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
             c->wm = WhittedMesh();
             return rc;
         }
+        mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base});
         mi.root = m.n_recs > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
         mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
         mesh_depth = std::max(mesh_depth, mi.depth);

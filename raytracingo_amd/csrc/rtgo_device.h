@@ -1,6 +1,6 @@
-// rtgo_device.h -- gfx950 device code of the RayTracinGO hot path: the scene-preparation/LBVH-build kernel and the
-// render megakernel that replaces the OptiX pipeline of engine/kernel.cu (raygen + traversal + 4 intersection
-// programs + 2 closest-hit programs + miss + accumulation), all in one launch.
+// rtgo_device.h -- gfx950 device code of the RayTracinGO hot path: the render megakernel that replaces the OptiX pipeline of engine/kernel.cu (raygen + traversal + 4 intersection
+// programs + 2 closest-hit programs + miss + accumulation), all in one launch.  What builds the structures it walks (scene
+// preparation, the LBVH build kernel) is rtgo_build.h, included below.
 //
 // Written for CDNA4 only (wave64, LDS-resident scene, per-lane LDS traversal stack).  No MFMA: there is no dense
 // contraction on this path.  Arithmetic follows the reference's IEEE-float32 statement operation by operation (this
@@ -53,6 +53,18 @@ struct GridParams {
     int rec_off4, items_off4;       // where the cell records and the item lists start, in float4 units from the table's start
     float margin;                   // fast_grid stops once the closest hit lies this far (in t) before the exit of the cell it is in
 };
+
+// ---- the packed fields of the fast walk's structure: build_kernel (rtgo_build.h) encodes, the walk and the host decode
+// A group the walk scans linearly (the up-front list, a multi-record leaf): pairs of opposite rectangles at its start (pair_test) and
+// its cuboid certificate (0: none, 1: a box seen from outside, 2: a room seen from inside; cuboid_range)
+__host__ __device__ constexpr int encode_group(int pairs, int cert) { return pairs | (cert << 8); }
+__host__ __device__ constexpr int group_pairs(int group) { return group & 0xFF; }
+__host__ __device__ constexpr int group_cert(int group) { return group >> 8; }
+// A leaf of the fast walk's tree: left = its first record, right = -(count | group << 12), i.e. -(count | pairs << 12 | cuboid << 20)
+__host__ __device__ constexpr int encode_leaf_link(int count, int group) { return -(count | (group << 12)); }
+__host__ __device__ constexpr int leaf_count(int link) { return (-link) & 0xFFF; }
+__host__ __device__ constexpr int leaf_pairs(int link) { return ((-link) >> 12) & 0xFF; }
+__host__ __device__ constexpr int leaf_cuboid(int link) { return (-link) >> 20; }
 
 struct LaunchParams {
     const float4* nodes;            // canonical LBVH, 2 float4 per node
@@ -843,7 +855,7 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
             }
         }
         if (have) {
-            const int first = left, cnt = (-right) & 0xFFF, npairs = ((-right) >> 12) & 0xFF;   // leaf link = -(count | pairs << 12 | cuboid << 20)
+            const int first = left, cnt = leaf_count(right), npairs = leaf_pairs(right);
 #ifdef RTGO_FAST_COUNTERS
 #if RTGO_FAST_COUNTERS == 2
             dbg_tests += (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) ? 1u : 0u;
@@ -852,7 +864,7 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
 #endif
 #endif
             if (tree_spheres) sphere_leaf(s_fprims, first, cnt, o, d, tmin, best);
-            else if (((-right) >> 20) != 0 && cub_mu > 0.0f) cuboid_range<false>(s_fprims, s_fprims, first, cub_mu, -INFINITY, o, d, tmin, best);
+            else if (leaf_cuboid(right) != 0 && cub_mu > 0.0f) cuboid_range<false>(s_fprims, s_fprims, first, cub_mu, -INFINITY, o, d, tmin, best);
             else leaf_range<false>(s_fprims, s_fprims, first, cnt, npairs, o, d, tmin, best);
             have = pop();
         }
@@ -1770,811 +1782,11 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     }
 }
 
-// =====================================================================================================================
-// Scene preparation + canonical LBVH build, one workgroup (n <= 512): replaces optixAccelBuild (renderer.cpp:514-611) and
-// hoists Matrix4x4::inverse() (Matrix.h:591-635) out of the intersection programs.
-// =====================================================================================================================
-struct PrimIn {  // = rtgo_prim
-    unsigned int type;
-    float M[16];
-    float kd[3], kr[3], spec, Le[3];
-};
+}  // namespace rtgo
 
-__device__ __forceinline__ float det4(const float* m)
-{
-    // Matrix.h:591-608, term order and product association preserved
-    return m[0] * m[5] * m[10] * m[15] - m[0] * m[5] * m[11] * m[14] + m[0] * m[9] * m[14] * m[7] - m[0] * m[9] * m[6] * m[15] +
-           m[0] * m[13] * m[6] * m[11] - m[0] * m[13] * m[10] * m[7] - m[4] * m[1] * m[10] * m[15] + m[4] * m[1] * m[11] * m[14] -
-           m[4] * m[9] * m[14] * m[3] + m[4] * m[9] * m[2] * m[15] - m[4] * m[13] * m[2] * m[11] + m[4] * m[13] * m[10] * m[3] +
-           m[8] * m[1] * m[6] * m[15] - m[8] * m[1] * m[14] * m[7] + m[8] * m[5] * m[14] * m[3] - m[8] * m[5] * m[2] * m[15] +
-           m[8] * m[13] * m[2] * m[7] - m[8] * m[13] * m[6] * m[3] - m[12] * m[1] * m[6] * m[11] + m[12] * m[1] * m[10] * m[7] -
-           m[12] * m[5] * m[10] * m[3] + m[12] * m[5] * m[2] * m[11] - m[12] * m[9] * m[2] * m[7] + m[12] * m[9] * m[6] * m[3];
-}
+#include "rtgo_build.h"   // scene preparation and the builds: PrimIn .. build_kernel (uses the definitions above)
 
-// one cofactor group of Matrix.h:612-635: a*(b*c - d*e)
-#define RTGO_G(a, b, c, d, e) (m[a] * (m[b] * m[c] - m[d] * m[e]))
-
-__device__ __forceinline__ void inverse_rows012(const float* m, float* o)
-{
-    const float d = 1.0f / det4(m);
-    o[0] = d * (RTGO_G(5, 10, 15, 14, 11) + RTGO_G(9, 14, 7, 6, 15) + RTGO_G(13, 6, 11, 10, 7));
-    o[4] = d * (RTGO_G(6, 8, 15, 12, 11) + RTGO_G(10, 12, 7, 4, 15) + RTGO_G(14, 4, 11, 8, 7));
-    o[8] = d * (RTGO_G(7, 8, 13, 12, 9) + RTGO_G(11, 12, 5, 4, 13) + RTGO_G(15, 4, 9, 8, 5));
-    o[1] = d * (RTGO_G(9, 2, 15, 14, 3) + RTGO_G(13, 10, 3, 2, 11) + RTGO_G(1, 14, 11, 10, 15));
-    o[5] = d * (RTGO_G(10, 0, 15, 12, 3) + RTGO_G(14, 8, 3, 0, 11) + RTGO_G(2, 12, 11, 8, 15));
-    o[9] = d * (RTGO_G(11, 0, 13, 12, 1) + RTGO_G(15, 8, 1, 0, 9) + RTGO_G(3, 12, 9, 8, 13));
-    o[2] = d * (RTGO_G(13, 2, 7, 6, 3) + RTGO_G(1, 6, 15, 14, 7) + RTGO_G(5, 14, 3, 2, 15));
-    o[6] = d * (RTGO_G(14, 0, 7, 4, 3) + RTGO_G(2, 4, 15, 12, 7) + RTGO_G(6, 12, 3, 0, 15));
-    o[10] = d * (RTGO_G(15, 0, 5, 4, 1) + RTGO_G(3, 4, 13, 12, 5) + RTGO_G(7, 12, 1, 0, 13));
-    o[3] = d * (RTGO_G(1, 10, 7, 6, 11) + RTGO_G(5, 2, 11, 10, 3) + RTGO_G(9, 6, 3, 2, 7));
-    o[7] = d * (RTGO_G(2, 8, 7, 4, 11) + RTGO_G(6, 0, 11, 8, 3) + RTGO_G(10, 4, 3, 0, 7));
-    o[11] = d * (RTGO_G(3, 8, 5, 4, 9) + RTGO_G(7, 0, 9, 8, 1) + RTGO_G(11, 4, 1, 0, 5));
-}
-#undef RTGO_G
-
-// Primitive::GetAabb / CubeBox::TransformAndAlign (primitive.cpp:35-79, 100-115): the 8 corners of [-1,1]^3 through the
-// 4-term matrix product (sum seeded with 0.0f, Matrix.h:344-360), min/max seeded with +-50, +-1e-3 pad.
-__device__ __forceinline__ void cube_aabb(const float* M, float* bb)
-{
-    float mn[3] = {50.0f, 50.0f, 50.0f}, mx[3] = {-50.0f, -50.0f, -50.0f};
-    // corner order of CubeBox::face0/face1 columns: x = {-1,-1,1,1}, z = {-1,1,-1,1}, y = -1 (face0) / +1 (face1)
-    const float cxs[4] = {-1.f, -1.f, 1.f, 1.f}, czs[4] = {-1.f, 1.f, -1.f, 1.f};
-    for (int i = 0; i < 4; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const float* r = M + 4 * a;
-            float p0 = 0.0f, p1 = 0.0f;
-            p0 += r[0] * cxs[i];
-            p0 += r[1] * -1.f;
-            p0 += r[2] * czs[i];
-            p0 += r[3] * 1.f;
-            p1 += r[0] * cxs[i];
-            p1 += r[1] * 1.f;
-            p1 += r[2] * czs[i];
-            p1 += r[3] * 1.f;
-            float t = (p0 < mn[a]) ? p0 : mn[a];
-            mn[a] = (p1 < t) ? p1 : t;
-            t = (mx[a] < p0) ? p0 : mx[a];
-            mx[a] = (t < p1) ? p1 : t;
-        }
-    for (int a = 0; a < 3; ++a) {
-        bb[a] = mn[a] - 0.001f;
-        bb[3 + a] = mx[a] + 0.001f;
-    }
-}
-
-__device__ __forceinline__ unsigned int expand_bits(unsigned int v)
-{
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-
-__device__ __forceinline__ int lbvh_delta(const unsigned long long* keys, int n, int i, int j)
-{
-    if (j < 0 || j >= n) return -1;
-    const unsigned int a = (unsigned int)(keys[i] >> 32), b = (unsigned int)(keys[j] >> 32);
-    if (a == b) return 32 + __clz((unsigned int)i ^ (unsigned int)j);
-    return __clz(a ^ b);
-}
-
-// One axis of a box centre c on the 10-bit Morton grid of the scene bounds [lo, lo + ext] (build_kernel and the global-memory build)
-__device__ __forceinline__ unsigned int morton_cell(float c, float lo, float ext)
-{
-    const float u = ext > 0.0f ? (c - lo) / ext : 0.0f;
-    return (unsigned int)fminf(fmaxf(u * 1024.0f, 0.0f), 1023.0f);
-}
-__device__ __forceinline__ unsigned int morton3(const unsigned int q[3])
-{
-    return (expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2]);
-}
-
-// Karras 2012: the children and the sorted key range [lo, hi] of internal node i of the tree over the m sorted unique keys (leaves are
-// nodes [m-1, 2m-2]; node 0 is the root)
-__device__ __forceinline__ void karras_node(const unsigned long long* keys, int m, int i, int& left, int& right, int& lo, int& hi)
-{
-    const int leaf0 = m - 1;
-    const int d = (lbvh_delta(keys, m, i, i + 1) - lbvh_delta(keys, m, i, i - 1)) >= 0 ? 1 : -1;
-    const int dmin = lbvh_delta(keys, m, i, i - d);
-    int lmax = 2;
-    while (lbvh_delta(keys, m, i, i + lmax * d) > dmin) lmax *= 2;
-    int l = 0;
-    for (int t = lmax / 2; t >= 1; t /= 2)
-        if (lbvh_delta(keys, m, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = lbvh_delta(keys, m, i, j);
-    int s = 0, t = l;
-    do {
-        t = (t + 1) / 2;
-        if (lbvh_delta(keys, m, i, i + (s + t) * d) > dnode) s += t;
-    } while (t > 1);
-    const int gamma = i + s * d + (d < 0 ? -1 : 0);
-    lo = i < j ? i : j;
-    hi = i < j ? j : i;
-    left = (lo == gamma) ? leaf0 + gamma : gamma;
-    right = (hi == gamma + 1) ? leaf0 + gamma + 1 : gamma + 1;
-}
-
-// The 6-float4 record of a primitive (SBT order, layout above) from its PrimIn and rows 0..2 of M^-1
-__device__ __forceinline__ void store_prim_record(float4* __restrict__ out, const PrimIn& P, const float* inv)
-{
-    out[0] = make_float4(inv[0], inv[1], inv[2], inv[3]);
-    out[1] = make_float4(inv[4], inv[5], inv[6], inv[7]);
-    out[2] = make_float4(inv[8], inv[9], inv[10], inv[11]);
-    out[3] = make_float4(P.kd[0], P.kd[1], P.kd[2], P.spec);
-    out[4] = make_float4(P.kr[0], P.kr[1], P.kr[2], __int_as_float((int)P.type));
-    out[5] = make_float4(P.Le[0], P.Le[1], P.Le[2], 0.0f);
-}
-
-// Outputs.  out_nodes: (2n-1) x 2 float4 canonical LBVH; out_prims: n x 6 float4 (SBT order); aabb_io: n x 6 floats (read when
-// have_aabb, else written); out_fnodes / out_fprims: the fast walk's tree (2*n_small-1 nodes) and Morton-ordered records
-// (small primitives first, then the "big" ones that are tested up front);
-// out_tight: n x 6 floats, the fast walk's box of every primitive (SBT order);
-// out_meta = {canonical depth, fast-walk stack depth, n_small, tight scene bounds (6 floats as bits), pairs in the up-front list
-// | cuboid certificate of the list << 8, nodes of the fast walk's tree, the two coefficients of cuboid_range's margin (float bits)}.
-__global__ __launch_bounds__(kMaxPrims) void build_kernel(const PrimIn* __restrict__ prims, float* __restrict__ aabb_io,
-                                                          int have_aabb, int n, float4* __restrict__ out_nodes,
-                                                          float4* __restrict__ out_prims, float4* __restrict__ out_fnodes,
-                                                          float4* __restrict__ out_fprims, int leaf_budget, float big_frac, int* __restrict__ out_meta,
-                                                          float* __restrict__ out_tight, int cuboids, float4* __restrict__ out_frames)
-{
-    __shared__ float s_box[kMaxPrims][6];               // per primitive: reference AABB, later the tight box
-    __shared__ unsigned long long s_keys[kMaxPrims];
-    __shared__ float s_nbox[2 * kMaxPrims][6];
-    __shared__ int s_left[kMaxPrims], s_right[kMaxPrims];
-    __shared__ int s_parent[2 * kMaxPrims];
-    __shared__ int s_visit[kMaxPrims];
-    __shared__ int s_wt[2 * kMaxPrims];                 // fast walk: cost weight of each subtree
-    __shared__ short s_lo[kMaxPrims], s_hi[kMaxPrims];  // Morton range covered by each internal node
-    __shared__ unsigned char s_flag[kMaxPrims];         // fast walk: 1 = "big" primitive kept out of the tree
-    __shared__ unsigned short s_order[kMaxPrims];       // fast walk: primitive at each record position (pairs side by side)
-    __shared__ unsigned char s_used[kMaxPrims];
-    __shared__ int s_depth, s_count, s_tmask;   // s_tmask: primitive types present in the fast walk's tree (bit = type)
-    // the bounds reductions run while s_nbox is not in use: borrow its storage (keeps static LDS under 64 KiB)
-    float(*s_red)[kMaxPrims] = reinterpret_cast<float(*)[kMaxPrims]>(&s_nbox[0][0]);
-
-    const int i = threadIdx.x;
-
-    // min/max over the boxes of the primitives selected by `take` -> s_red[0..5][0] (exact, order-independent)
-    auto reduce_bounds = [&](bool take) {
-        for (int a = 0; a < 3; ++a) {
-            s_red[a][i] = take ? s_box[i][a] : INFINITY;
-            s_red[3 + a][i] = take ? s_box[i][3 + a] : -INFINITY;
-        }
-        __syncthreads();
-        for (int stride = kMaxPrims / 2; stride > 0; stride >>= 1) {
-            if (i < stride)
-                for (int a = 0; a < 3; ++a) {
-                    s_red[a][i] = fminf(s_red[a][i], s_red[a][i + stride]);
-                    s_red[3 + a][i] = fmaxf(s_red[3 + a][i], s_red[3 + a][i + stride]);
-                }
-            __syncthreads();
-        }
-    };
-    // 30-bit Morton code of primitive i's box centre normalised to the bounds in s_red[..][0]
-    auto morton_of = [&](int first = -1, int count = 1, bool cubic = false) -> unsigned int {   // centre of the union of the boxes [first, first + count)
-        if (first < 0) first = i;
-        unsigned int q[3];
-        // cubic: one scale for the three axes (the longest extent), so that a Morton cell is a cube and not a slab
-        const float emax = fmaxf(fmaxf(s_red[3][0] - s_red[0][0], s_red[4][0] - s_red[1][0]), s_red[5][0] - s_red[2][0]);
-        for (int a = 0; a < 3; ++a) {
-            float lo = s_box[first][a], hi = s_box[first][3 + a];
-            for (int k = 1; k < count; ++k) {
-                lo = fminf(lo, s_box[first + k][a]);
-                hi = fmaxf(hi, s_box[first + k][3 + a]);
-            }
-            const float c = (lo + hi) * 0.5f;
-            const float ext = cubic ? emax : s_red[3 + a][0] - s_red[a][0];
-            q[a] = morton_cell(c, s_red[a][0], ext);
-        }
-        return morton3(q);
-    };
-    // bitonic sort of the kMaxPrims keys in LDS; keys are unique, so the result is THE (code, index) order
-    auto sort_keys = [&]() {
-        __syncthreads();
-        for (int k = 2; k <= kMaxPrims; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = s_keys[i], b = s_keys[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
-                        s_keys[i] = b;
-                        s_keys[ixj] = a;
-                    }
-                }
-                __syncthreads();
-            }
-    };
-    // Karras 2012 over the first m sorted keys + bottom-up fit of boxes (and cost weights).  Leaves are nodes [m-1, 2m-2].
-    auto build_tree = [&](int m, bool with_weights) {
-        const int leaf0 = m - 1;
-        if (i < m) {
-            const int prim = (int)(s_keys[i] & 0xFFFFFFFFu);
-            for (int a = 0; a < 6; ++a) s_nbox[leaf0 + i][a] = s_box[prim][a];
-            s_visit[i] = 0;
-        }
-        if (i < 2 * m - 1) s_parent[i] = -1;
-        if (i + kMaxPrims < 2 * m - 1) s_parent[i + kMaxPrims] = -1;
-        __syncthreads();
-        if (i < m - 1) {
-            int left, right, lo, hi;
-            karras_node(s_keys, m, i, left, right, lo, hi);
-            s_left[i] = left;
-            s_right[i] = right;
-            s_lo[i] = (short)lo;
-            s_hi[i] = (short)hi;
-            s_parent[left] = i;
-            s_parent[right] = i;
-        }
-        __syncthreads();
-        // the second arrival at a node (LDS atomic) owns it
-        if (i < m && m > 1) {
-            int pnode = s_parent[leaf0 + i];
-            while (pnode >= 0) {
-                __threadfence_block();
-                if (atomicAdd(&s_visit[pnode], 1) == 0) break;
-                __threadfence_block();
-                const int L = s_left[pnode], R = s_right[pnode];
-                for (int a = 0; a < 3; ++a) {
-                    s_nbox[pnode][a] = fminf(s_nbox[L][a], s_nbox[R][a]);
-                    s_nbox[pnode][3 + a] = fmaxf(s_nbox[L][3 + a], s_nbox[R][3 + a]);
-                }
-                if (with_weights) s_wt[pnode] = s_wt[L] + s_wt[R];
-                pnode = s_parent[pnode];
-            }
-        }
-        __syncthreads();
-    };
-
-    if (i == 0) {
-        s_depth = 0;
-        s_count = 0;
-        s_tmask = 0;
-    }
-    // ---- per primitive: inverse, record, reference AABB
-    PrimIn P;
-    if (i < n) {
-        P = prims[i];
-        float inv[12];
-        inverse_rows012(P.M, inv);
-        store_prim_record(out_prims + 6 * i, P, inv);
-        // Shading frame of a FLAT primitive (rectangle, disk: object-space normal (0,1,0), kernel.cu:345,388): what the closest-hit
-        // program computes from it on every hit -- N = normalize(TransformNormal(0,1,0)) (kernel.cu:428) and the tangent of
-        // GetRayOnHemisphere for direction N, X = normalize(N.y - N.z, -N.x, N.x) (kernel.cu:105) -- depends on the primitive alone.
-        // Computed here ONCE with the same device functions on the same values, so the bits are those of the per-hit computation;
-        // a flipped normal flips both exactly (the expressions are odd in N, negation is exact), and Z = N x X is unchanged.
-        {
-            const bool flat = P.type == 1u || P.type == 2u;
-            v3 fn = mk(0.0f, 0.0f, 0.0f), fx = mk(0.0f, 0.0f, 0.0f);
-            if (flat) {
-                fn = vnormalize(xf_normal(make_float4(inv[0], inv[1], inv[2], inv[3]), make_float4(inv[4], inv[5], inv[6], inv[7]), make_float4(inv[8], inv[9], inv[10], inv[11]), mk(0.0f, 1.0f, 0.0f)));
-                fx = vnormalize(mk(fn.y - fn.z, -fn.x, fn.x));
-            }
-            out_frames[2 * i + 0] = make_float4(fn.x, fn.y, fn.z, flat ? 1.0f : 0.0f);
-            out_frames[2 * i + 1] = make_float4(fx.x, fx.y, fx.z, 0.0f);
-        }
-        float bb[6];
-        if (have_aabb) {
-            for (int a = 0; a < 6; ++a) bb[a] = aabb_io[6 * i + a];
-        } else {
-            cube_aabb(P.M, bb);
-            for (int a = 0; a < 6; ++a) aabb_io[6 * i + a] = bb[a];
-        }
-        for (int a = 0; a < 6; ++a) s_box[i][a] = bb[a];
-    }
-    __syncthreads();
-
-    // ================= canonical LBVH: every primitive, the reference's AABBs =================
-    reduce_bounds(i < n);
-    s_keys[i] = (i < n) ? (((unsigned long long)morton_of() << 32) | (unsigned int)i) : ~0ull;
-    sort_keys();
-    build_tree(n, false);
-    {
-        const int leaf0 = n - 1;
-        if (i < n) {
-            int dep = 0;
-            int q = s_parent[leaf0 + i];
-            while (q >= 0) {
-                ++dep;
-                q = s_parent[q];
-            }
-            atomicMax(&s_depth, dep);
-        }
-        for (int k = i; k < 2 * n - 1; k += kMaxPrims) {
-            int left, right;
-            if (k >= leaf0) {
-                left = (int)(s_keys[k - leaf0] & 0xFFFFFFFFu);
-                right = -1;
-            } else {
-                left = s_left[k];
-                right = s_right[k];
-            }
-            out_nodes[2 * k + 0] = make_float4(s_nbox[k][0], s_nbox[k][1], s_nbox[k][2], __int_as_float(left));
-            out_nodes[2 * k + 1] = make_float4(s_nbox[k][3], s_nbox[k][4], s_nbox[k][5], __int_as_float(right));
-        }
-    }
-    __syncthreads();
-    if (i == 0) out_meta[0] = s_depth;
-
-    // ================= fast walk's structure =================
-    // Any conservative structure returns the same closest hit, so this one is built for speed:
-    //  * TIGHT per-shape boxes for rectangles and disks (the reference's CubeBox boxes span a whole cube around a flat shape);
-    //  * "big" primitives (box spanning >= 36 % of the scene on two axes: room walls, floors) stay out of the tree and are
-    //    tested first, which also gives every ray an early closest-hit bound for culling the tree;
-    //  * LBVH over the rest, subtrees collapsed into multi-primitive leaves by a cost budget.
-    // Spheres and cylinders keep the box the canonical walk uses (the caller's / the CubeBox one): their quadratic loses its
-    // digits with distance (b*b - 4ac at |o| ~ 2000 radii is good to ~0.1 radius), so from far away the intersection program
-    // reports hits up to tenths of a unit OFF the surface -- inside the reference's loose box, outside a tight one -- and the
-    // closest hit must be the reference's arithmetic, not the geometry (tools/fuzz_cameras.py found it: a camera 1200 units
-    // from the slide scene).  Rectangles and disks divide once (error ~1e-7 of the distance): their tight boxes stand.
-    if (i < n && (P.type == 2 || P.type == 1)) {
-        const float* M = P.M;
-        for (int a = 0; a < 3; ++a) {
-            const float mx = M[4 * a + 0], mz = M[4 * a + 2], c = M[4 * a + 3];
-            float e;  // half extent of the unit shape's image along world axis a
-            if (P.type == 2) e = 0.5f * fabsf(mx) + 0.5f * fabsf(mz);   // rectangle |x|,|z| <= 1/2, y = 0
-            else e = sqrtf(mx * mx + mz * mz);                          // disk, radius 1 in y = 0
-            e = e * 1.00001f + 0.001f;  // rounding headroom + the reference's own pad (AABB_EPSILON)
-            s_box[i][a] = c - e;
-            s_box[i][3 + a] = c + e;
-        }
-    }
-    __syncthreads();
-    if (i < n)   // per primitive: the box the fast walk culls with (the host projects these onto the screen: LaunchParams::hot_mask)
-        for (int a = 0; a < 6; ++a) out_tight[6 * i + a] = s_box[i][a];
-    reduce_bounds(i < n);
-    if (i < 6) out_meta[3 + i] = __float_as_int(s_red[i][0]);  // tight scene bounds: min xyz, max xyz
-    bool big = false;
-    if (i < n) {
-        int wide = 0;
-        for (int a = 0; a < 3; ++a)
-            if (s_box[i][3 + a] - s_box[i][a] >= big_frac * (s_red[3 + a][0] - s_red[a][0])) ++wide;
-        big = wide >= 2;
-        s_flag[i] = big ? 1 : 0;
-        if (!big) {
-            atomicAdd(&s_count, 1);
-            atomicOr(&s_tmask, 1 << (int)(P.type & 3u));
-        }
-    }
-    __syncthreads();
-    const int n_small = s_count;
-    reduce_bounds(i < n && !big);
-    // Boxes: six consecutive small rectangles that pair up by opposite normals (ShapeFactory::CreateCube emits a cube's faces
-    // consecutively, shapefactory.cpp) share ONE Morton code, that of the box centre, so that the Karras hierarchy keeps them
-    // in one subtree and the cost budget (6) turns exactly that subtree into a leaf: whole-box leaves, which pair_test halves.
-    // Left to the face centroids, Morton order cuts across touching boxes (checkered: leaves of every mix of pairs and singles).
-    if (i < n) s_used[i] = 0xFF;   // first primitive of the box this one belongs to, relative: 0..5, or 0xFF
-    __syncthreads();
-    if (i == 0) {
-        int a = 0;
-        while (a + 6 <= n) {
-            bool ok = true;
-            for (int k = 0; k < 6 && ok; ++k) ok = prims[a + k].type == 2u && !s_flag[a + k];
-            if (ok) {
-                unsigned int paired = 0;
-                for (int k = 0; k < 6; ++k) {
-                    if (paired & (1u << k)) continue;
-                    const float4 ra = out_prims[6 * (a + k) + 1];
-                    const float la = sqrtf(ra.x * ra.x + ra.y * ra.y + ra.z * ra.z);
-                    for (int m = k + 1; m < 6; ++m) {
-                        if (paired & (1u << m)) continue;
-                        const float4 rb = out_prims[6 * (a + m) + 1];
-                        const float lb = sqrtf(rb.x * rb.x + rb.y * rb.y + rb.z * rb.z);
-                        if (ra.x * rb.x + ra.y * rb.y + ra.z * rb.z < -0.9999f * la * lb) {
-                            paired |= (1u << k) | (1u << m);
-                            break;
-                        }
-                    }
-                }
-                ok = paired == 0x3Fu;
-            }
-            if (ok) {
-                for (int k = 0; k < 6; ++k) s_used[a + k] = (unsigned char)k;
-                a += 6;
-            } else {
-                a += 1;
-            }
-        }
-    }
-    __syncthreads();
-    // small primitives sort by Morton code; big ones after them, in SBT order
-    {
-        const bool boxed = i < n && s_used[i] != 0xFF;
-        const bool cubic = true;   // (balls -1 %, plateau -1 %, slide -2.5 % against per-axis scaling; nothing lost elsewhere)
-        const unsigned int code = (i < n && !big) ? (boxed ? morton_of(i - (int)s_used[i], 6, cubic) : morton_of(-1, 1, cubic)) : 0u;
-        s_keys[i] = (i < n) ? ((big ? (0xFFFFFFFEull << 32) : ((unsigned long long)code << 32)) | (unsigned int)i) : ~0ull;
-    }
-    sort_keys();
-    if (i < n_small) {
-        const int prim = (int)(s_keys[i] & 0xFFFFFFFFu);
-        const unsigned int type = prims[prim].type;
-        // relative cost of one leaf test vs one box test: rectangles reject on two signs, quadrics need the full transform
-        s_wt[n_small - 1 + i] = (type == 2) ? 1 : (type == 1 ? 4 : 32);
-    }
-    if (i == 0) s_depth = 0;
-    __syncthreads();
-    if (n_small > 0) build_tree(n_small, true);
-    {
-        const int leaf0 = n_small - 1;
-        if (i < n_small) {
-            // only ancestors that stay internal (cost above the budget) can push on the fast walk's stack
-            int fdep = 0;
-            int q = s_parent[leaf0 + i];
-            while (q >= 0) {
-                if (s_wt[q] > leaf_budget) ++fdep;
-                q = s_parent[q];
-            }
-            atomicMax(&s_depth, fdep);
-        }
-        // Record order inside every group the walk scans linearly -- the up-front list and each maximal collapsed leaf:
-        // rectangles with opposite normals side by side (pair_test), pairs first, the rest after them.  One thread per group.
-        // Leaves are only paired when EVERY multi-record leaf of the scene pairs up completely (whole boxes): the lanes of a wave
-        // scan different leaves side by side, and with leaves of both kinds they take turns in the pair loop and the single
-        // loop (checkered, whose Morton leaves cut across its 64 cubes: +9 %).  The up-front list is scanned by all lanes
-        // together and is always paired.
-        if (i < n) {
-            s_order[i] = (unsigned short)(s_keys[i] & 0xFFFFFFFFu);
-            s_used[i] = 0;
-            s_visit[i] = 0;   // (build_tree's arrival counters are no longer needed: pairs per node from here on)
-        }
-        __shared__ int s_cubA, s_cubB, s_cubN;   // cuboid_range's margin coefficients (positive floats as bits: integer max = float max)
-        if (i == 0) {
-            out_meta[9] = 0;
-            s_count = 0;   // leaves that do not pair up completely
-            s_cubA = 0;
-            s_cubB = 0;
-            s_cubN = 0;   // leaves certified as cuboids
-        }
-        __syncthreads();
-        int g_lo = 0, g_hi = -1;
-        {
-            const bool list = (i == kMaxPrims - 1);
-            if (list) {
-                g_lo = n_small;
-                g_hi = n - 1;
-            } else if (i < leaf0 && s_wt[i] <= leaf_budget && (s_parent[i] < 0 || s_wt[s_parent[i]] > leaf_budget)) {
-                g_lo = s_lo[i];
-                g_hi = s_hi[i];
-            }
-            if (g_hi > g_lo) {
-                auto prim_at = [&](int pos) { return (int)(s_keys[pos] & 0xFFFFFFFFu); };
-                auto is_rect = [&](int pos) { return prims[prim_at(pos)].type == 2u; };
-                auto normal_of = [&](int pos) {   // world normal of a rectangle = row 1 of M^-1 (TransformNormal of (0,1,0))
-                    const float4 r = out_prims[6 * prim_at(pos) + 1];
-                    const float l = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
-                    return l > 0.0f ? mk(r.x / l, r.y / l, r.z / l) : mk(0.0f, 0.0f, 0.0f);
-                };
-                int out = g_lo;
-                for (int a = g_lo; a <= g_hi; ++a) {
-                    if (s_used[a] || !is_rect(a)) continue;
-                    const v3 na = normal_of(a);
-                    int bsel = -1;
-                    float bdot = -0.9999f;
-                    for (int b = a + 1; b <= g_hi; ++b) {
-                        if (s_used[b] || !is_rect(b)) continue;
-                        const float dt = vdot(na, normal_of(b));
-                        if (dt < bdot) {
-                            bdot = dt;
-                            bsel = b;
-                        }
-                    }
-                    if (bsel >= 0) {
-                        s_used[a] = 1;
-                        s_used[bsel] = 1;
-                        s_order[out] = (unsigned short)prim_at(a);
-                        s_order[out + 1] = (unsigned short)prim_at(bsel);
-                        out += 2;
-                    }
-                }
-                const int npairs = (out - g_lo) / 2;
-                // Cuboid certificate (cuboid_range): three pairs -- a whole leaf, or the pairs of the up-front list -- are the faces
-                // of one box seen from outside when the four corners of every face f lie at or below the plane of every face g of
-                // the other two pairs (y_g <= tol in g's object space; y_g is affine, so the whole face does), of one room seen from
-                // inside when they lie at or above it.  Checked on the matrices themselves: whatever passes is safe, whatever the
-                // shapes were meant to be.  L = how far y_g varies over face f: it carries the rounding of the reference's (u, v) on
-                // f into y_g units; A, B: margin = tol + K (A R + B) for rays within R of the origin (rtgo_capi.hip).
-                int cert = 0;
-                if (cuboids && npairs == 3 && (list || g_hi - g_lo + 1 == 6)) {
-                    bool outw = true, inw = true;
-                    float A = 0.0f, B = 0.0f;
-                    auto n1 = [](const float4 r) { return fabsf(r.x) + fabsf(r.y) + fabsf(r.z); };
-                    for (int f = 0; f < 6; ++f) {
-                        const int pf = (int)s_order[g_lo + f];
-                        const float* M = prims[pf].M;
-                        const float4 f0 = out_prims[6 * pf + 0], f2 = out_prims[6 * pf + 2];
-                        const float n1f = fmaxf(n1(f0), n1(f2)), wf = fmaxf(fabsf(f0.w), fabsf(f2.w));
-                        for (int g = 0; g < 6; ++g) {
-                            if ((g >> 1) == (f >> 1)) continue;
-                            const float4 r1 = out_prims[6 * (int)s_order[g_lo + g] + 1];
-                            float ymax = -INFINITY, ymin = INFINITY;
-                            for (int c = 0; c < 4; ++c) {
-                                const float sx = (c & 1) ? 0.5f : -0.5f, sz = (c & 2) ? 0.5f : -0.5f;
-                                const float cx = M[0] * sx + M[2] * sz + M[3], cy = M[4] * sx + M[6] * sz + M[7], cz = M[8] * sx + M[10] * sz + M[11];
-                                const float y = r1.x * cx + r1.y * cy + r1.z * cz + r1.w;
-                                ymax = fmaxf(ymax, y);
-                                ymin = fminf(ymin, y);
-                                if (!(y == y)) outw = inw = false;
-                            }
-                            outw = outw && ymax <= kCuboidTol;
-                            inw = inw && ymin >= -kCuboidTol;
-                            const float L = ymax - ymin;
-                            A = fmaxf(A, L * n1f + n1(r1));
-                            B = fmaxf(B, L * wf + fabsf(r1.w));
-                        }
-                    }
-                    cert = outw ? 1 : ((inw && list) ? 2 : 0);   // (rooms are big: only the list can hold one)
-                    if (!(A < 1e30f && B < 1e30f)) cert = 0;
-                    if (cert) {
-                        atomicMax(&s_cubA, __float_as_int(A));
-                        atomicMax(&s_cubB, __float_as_int(B));
-                    }
-                }
-                if (list || 2 * npairs == g_hi - g_lo + 1) {
-                    for (int a = g_lo; a <= g_hi; ++a)
-                        if (!s_used[a]) s_order[out++] = (unsigned short)prim_at(a);
-                    if (list) out_meta[9] = npairs | (cert << 8);
-                    else s_visit[i] = npairs | (cert << 8);
-                } else {
-                    atomicAdd(&s_count, 1);
-                }
-            }
-        }
-        __syncthreads();
-        if (s_count > 0 && i != kMaxPrims - 1 && g_hi > g_lo) {   // mixed scene: leave every leaf as it was
-            for (int a = g_lo; a <= g_hi; ++a) s_order[a] = (unsigned short)(s_keys[a] & 0xFFFFFFFFu);
-            s_visit[i] = 0;
-        }
-        if (i == 0) {
-            out_meta[11] = s_cubA;
-            out_meta[12] = s_cubB;
-        }
-        __syncthreads();
-        if (i < n) {
-            // traversal record (inverse rows were written to out_prims by the primitive's own thread above)
-            const int prim = (int)s_order[i];
-            out_fprims[4 * i + 0] = out_prims[6 * prim + 0];
-            out_fprims[4 * i + 1] = out_prims[6 * prim + 1];
-            out_fprims[4 * i + 2] = out_prims[6 * prim + 2];
-            out_fprims[4 * i + 3] = make_float4(__int_as_float((int)prims[prim].type), __int_as_float(prim), 0.0f, 0.0f);
-        }
-        // ---- the tree the walk uses: a top-down surface-area-heuristic build over the walk's UNITS.  A unit is a maximal collapsed
-        // subtree of the Morton hierarchy above (cost <= budget: one multi-record leaf whose records are contiguous) or a single
-        // primitive; the hierarchy only serves to form them.  Above the units the Morton prefixes are a poor guide for rays (they
-        // know nothing of box areas), and any tree over the same leaves returns the same closest hit, so the topology is rebuilt:
-        // every node is split where A(left) * W(left) + A(right) * W(right) is smallest over the three axes and every position of
-        // the units sorted by centroid (W = leaf-test cost weights).  All 512 threads walk one task queue together: a rank sort per
-        // axis in parallel, the sweep by one thread.  (Rotations of the Morton tree gave balls -4.5 %; this build ... see DESIGN.)
-        short* s_unit = reinterpret_cast<short*>(s_keys);    // (the sort keys are no longer needed) [kMaxPrims] binary node of unit u
-        short* s_perm = s_unit + kMaxPrims;                  // [kMaxPrims] the units in the current task order
-        short* s_tmp = s_perm + kMaxPrims;                   // [kMaxPrims]
-        float* s_sfx = &s_box[0][0];                         // (the primitive boxes are no longer needed) [kMaxPrims][7]: suffix box + weight
-        short* s_tq_node = reinterpret_cast<short*>(s_parent);   // task queue, <= 2 * units - 1 entries: node, lo, hi, depth
-        short* s_tq_lo = s_tq_node + 2 * kMaxPrims;
-        short* s_tq_hi = reinterpret_cast<short*>(s_wt);         // (s_wt is read until the units are formed; see the barrier below)
-        short* s_tq_dep = s_tq_hi + 2 * kMaxPrims;
-        __shared__ int s_qtail, s_best_axis, s_best_pos, s_units;
-        // the tree under construction (dynamic LDS, 2 * kMaxPrims nodes): box, links, parent -- rotated below, then written out
-        extern __shared__ __attribute__((aligned(16))) unsigned char build_dyn[];
-        float (*t_box)[6] = reinterpret_cast<float (*)[6]>(build_dyn);
-        int* t_left = reinterpret_cast<int*>(t_box + 2 * kMaxPrims);
-        int* t_right = t_left + 2 * kMaxPrims;
-        int* t_parent = t_right + 2 * kMaxPrims;
-        auto leafish = [&](int k) { return k >= leaf0 || s_wt[k] <= leaf_budget; };
-        __syncthreads();
-        if (i < n_small) s_left[i] = -1;   // (the binary links are no longer needed) unit that starts at Morton position i
-        __syncthreads();
-        for (int k = i; k < 2 * n_small - 1; k += kMaxPrims)
-            if (leafish(k) && (s_parent[k] < 0 || s_wt[s_parent[k]] > leaf_budget)) s_left[k >= leaf0 ? k - leaf0 : s_lo[k]] = k;
-        __syncthreads();
-        if (i == 0) {
-            int L = 0;
-            for (int pos = 0; pos < n_small; ++pos)
-                if (s_left[pos] >= 0) s_unit[L++] = (short)s_left[pos];
-            s_units = L;
-        }
-        __syncthreads();
-        const int L = s_units;
-        // per unit: weight (kept in s_right, an int array that is free now) -- after this barrier s_wt and s_parent are reused
-        if (i < L) {
-            const int k = s_unit[i];
-            s_right[i] = s_wt[k] < 1 ? 1 : s_wt[k];
-            s_perm[i] = (short)i;
-        }
-        __syncthreads();
-        if (i == 0) {
-            s_tq_node[0] = 0;
-            s_tq_lo[0] = 0;
-            s_tq_hi[0] = (short)L;
-            s_tq_dep[0] = 0;
-            s_qtail = L > 0 ? 1 : 0;
-            s_count = L > 0 ? 1 : 0;   // nodes allocated
-            s_depth = 0;
-            t_parent[0] = -1;
-        }
-        __syncthreads();
-        auto ubox = [&](int u, int c) { return s_nbox[s_unit[u]][c]; };
-        for (int qi = 0; qi < 2 * kMaxPrims; ++qi) {
-            __syncthreads();
-            if (qi >= s_qtail) break;   // (uniform: every thread reads the same word after the barrier)
-            const int lo = s_tq_lo[qi], hi = s_tq_hi[qi], node = s_tq_node[qi], dep = s_tq_dep[qi], m = hi - lo;
-            if (m == 1) {
-                if (i == 0) {
-                    const int k = s_unit[s_perm[lo]];
-                    const int first = k >= leaf0 ? k - leaf0 : (int)s_lo[k];
-                    const int cnt = k >= leaf0 ? 1 : (int)s_hi[k] - (int)s_lo[k] + 1;
-                    const int npairs = k >= leaf0 ? 0 : s_visit[k];
-                    for (int c = 0; c < 6; ++c) t_box[node][c] = s_nbox[k][c];
-                    t_left[node] = first;
-                    t_right[node] = -(cnt | (npairs << 12));
-                }
-                continue;
-            }
-            if (i == 0) {
-                s_best_axis = -1;
-                s_best_pos = m / 2;
-            }
-            float best_cost = INFINITY;   // (thread 0's)
-            for (int pass = 0; pass < 4; ++pass) {
-                // passes 0..2: try axis `pass`; pass 3: put the range back in the order of the best axis
-                __syncthreads();
-                const int axis = pass < 3 ? pass : s_best_axis;
-                if (pass == 3 && (axis < 0 || axis == 2)) break;   // (uniform) no finite cost at all, or already in z order
-                if (i < m) {
-                    const int me = s_perm[lo + i];
-                    const float key = ubox(me, axis) + ubox(me, 3 + axis);
-                    int rank = 0;
-                    for (int j = 0; j < m; ++j) {
-                        const int other = s_perm[lo + j];
-                        const float kj = ubox(other, axis) + ubox(other, 3 + axis);
-                        rank += (kj < key || (kj == key && other < me)) ? 1 : 0;
-                    }
-                    s_tmp[lo + rank] = (short)me;
-                }
-                __syncthreads();
-                if (i < m) s_perm[lo + i] = s_tmp[lo + i];
-                __syncthreads();
-                if (pass < 3 && i == 0) {
-                    // suffix boxes and weights from the right, then the sweep from the left
-                    float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                    int w = 0;
-                    for (int j = m - 1; j >= 1; --j) {
-                        const int u = s_perm[lo + j];
-                        for (int c = 0; c < 3; ++c) {
-                            b[c] = fminf(b[c], ubox(u, c));
-                            b[3 + c] = fmaxf(b[3 + c], ubox(u, 3 + c));
-                        }
-                        w += s_right[u];
-                        const float ex = b[3] - b[0], ey = b[4] - b[1], ez = b[5] - b[2];
-                        s_sfx[2 * j + 0] = ex * ey + ey * ez + ez * ex;
-                        s_sfx[2 * j + 1] = (float)w;
-                    }
-                    float a[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                    int wl = 0;
-                    for (int j = 1; j < m; ++j) {   // left = [0, j), right = [j, m)
-                        const int u = s_perm[lo + j - 1];
-                        for (int c = 0; c < 3; ++c) {
-                            a[c] = fminf(a[c], ubox(u, c));
-                            a[3 + c] = fmaxf(a[3 + c], ubox(u, 3 + c));
-                        }
-                        wl += s_right[u];
-                        const float ex = a[3] - a[0], ey = a[4] - a[1], ez = a[5] - a[2];
-                        const float cost = (ex * ey + ey * ez + ez * ex) * (float)wl + s_sfx[2 * j] * s_sfx[2 * j + 1];
-                        if (cost < best_cost) {
-                            best_cost = cost;
-                            s_best_axis = pass;
-                            s_best_pos = j;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (i == 0) {
-                // this node: box of its range, two children appended to the queue
-                float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                for (int j = lo; j < hi; ++j) {
-                    const int u = s_perm[j];
-                    for (int c = 0; c < 3; ++c) {
-                        b[c] = fminf(b[c], ubox(u, c));
-                        b[3 + c] = fmaxf(b[3 + c], ubox(u, 3 + c));
-                    }
-                }
-                const int cl = s_count, cr = s_count + 1;
-                s_count += 2;
-                for (int c = 0; c < 6; ++c) t_box[node][c] = b[c];
-                t_left[node] = cl;
-                t_right[node] = cr;
-                t_parent[cl] = node;
-                t_parent[cr] = node;
-                const int mid = lo + s_best_pos;
-                const int t = s_qtail;
-                s_tq_node[t] = (short)cl; s_tq_lo[t] = (short)lo;  s_tq_hi[t] = (short)mid; s_tq_dep[t] = (short)(dep + 1);
-                s_tq_node[t + 1] = (short)cr; s_tq_lo[t + 1] = (short)mid; s_tq_hi[t + 1] = (short)hi; s_tq_dep[t + 1] = (short)(dep + 1);
-                s_qtail = t + 2;
-            }
-        }
-        // Tree rotations (Kensler 2008) as a second pass: the top-down build is greedy, and a node may still gain from trading one
-        // child for a grandchild on the other side when that shrinks the grandchild's parent.  One thread; a handful of sweeps.
-        __syncthreads();
-        const int n_nodes = s_count;
-        if (i == 0 && n_nodes > 3) {
-            auto internal = [&](int k) { return t_right[k] >= 0; };
-            auto area2 = [&](int a, int b) {
-                float e[3];
-                for (int ax = 0; ax < 3; ++ax) e[ax] = fmaxf(t_box[a][3 + ax], t_box[b][3 + ax]) - fminf(t_box[a][ax], t_box[b][ax]);
-                return e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
-            };
-            auto refit = [&](int k) {
-                const int A = t_left[k], B = t_right[k];
-                for (int ax = 0; ax < 3; ++ax) {
-                    t_box[k][ax] = fminf(t_box[A][ax], t_box[B][ax]);
-                    t_box[k][3 + ax] = fmaxf(t_box[A][3 + ax], t_box[B][3 + ax]);
-                }
-            };
-            for (int pass = 0; pass < 6; ++pass) {
-                int changed = 0;
-                for (int N = 0; N < n_nodes; ++N) {
-                    if (!internal(N)) continue;
-                    const int A = t_left[N], B = t_right[N];
-                    float best = 0.0f;
-                    int which = 0;   // 1: B <-> left(A), 2: B <-> right(A), 3: A <-> left(B), 4: A <-> right(B)
-                    if (internal(A)) {
-                        const float a0 = area2(A, A);
-                        const float g1 = a0 - area2(B, t_right[A]), g2 = a0 - area2(t_left[A], B);
-                        if (g1 > best) { best = g1; which = 1; }
-                        if (g2 > best) { best = g2; which = 2; }
-                    }
-                    if (internal(B)) {
-                        const float a0 = area2(B, B);
-                        const float g3 = a0 - area2(A, t_right[B]), g4 = a0 - area2(t_left[B], A);
-                        if (g3 > best) { best = g3; which = 3; }
-                        if (g4 > best) { best = g4; which = 4; }
-                    }
-                    if (which == 0 || !(best > 1e-6f * area2(N, N))) continue;
-                    if (which <= 2) {
-                        const int g = which == 1 ? t_left[A] : t_right[A];   // the grandchild that moves up
-                        if (which == 1) t_left[A] = B; else t_right[A] = B;
-                        t_parent[B] = A;
-                        t_right[N] = g;
-                        t_parent[g] = N;
-                        refit(A);
-                    } else {
-                        const int g = which == 3 ? t_left[B] : t_right[B];
-                        if (which == 3) t_left[B] = A; else t_right[B] = A;
-                        t_parent[A] = B;
-                        t_left[N] = g;
-                        t_parent[g] = N;
-                        refit(B);
-                    }
-                    ++changed;
-                }
-                if (!changed) break;
-            }
-            s_depth = 0;
-        }
-        __syncthreads();
-        for (int k = i; k < n_nodes; k += kMaxPrims) {
-            out_fnodes[2 * k + 0] = make_float4(t_box[k][0], t_box[k][1], t_box[k][2], __int_as_float(t_left[k]));
-            out_fnodes[2 * k + 1] = make_float4(t_box[k][3], t_box[k][4], t_box[k][5], __int_as_float(t_right[k]));
-            if (t_right[k] < 0) {   // a leaf: internal nodes above it = stack entries the walk can need on the way
-                if (((-t_right[k]) >> 20) != 0) atomicAdd(&s_cubN, 1);
-                int d = 0;
-                for (int q = t_parent[k]; q >= 0; q = t_parent[q]) ++d;
-                atomicMax(&s_depth, d);
-            }
-        }
-        __syncthreads();
-        if (i == 0) out_meta[13] = s_cubN;
-    }
-    __syncthreads();
-    if (i == 0) {
-        out_meta[1] = s_depth;
-        out_meta[2] = n_small;
-        out_meta[10] = s_count;   // nodes of the walk's tree (2 * units - 1)
-        out_meta[14] = s_tmask;
-    }
-}
+namespace rtgo {
 
 // =====================================================================================================================
 // Presentation step of the multi-GPU driver: the root holds n_ranks compact band buffers back to back (rows_pad rows each) and

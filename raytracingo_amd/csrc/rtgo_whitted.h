@@ -712,18 +712,47 @@ __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
     });
 }
 
+// What the two build kernels report (build_kernel writes all of it, sah_kernel rewrites n_recs and walk_depth)
+struct WhittedBuildMeta {
+    int depth;              // of the Morton hierarchy
+    int n_recs;             // records of the walk; 0: the structure is one leaf
+    int walk_depth;         // stack entries the walk needs
+    v3 grid_lo, grid_step;  // the grid of the compact records
+};
+static_assert(sizeof(WhittedBuildMeta) == 9 * sizeof(int), "nine words");
+
+// One record of the walk, r: BOTH children's boxes (a* / b*: lower and upper corner, .w unused) and links, so that a step of the walk reads
+// 64 contiguous bytes -> recs[4 r ..]; and the same record on the 16-bit grid over the padded scene box (lower planes one cell below
+// their floor, upper planes one above their ceiling) -> qrecs[2 r ..]
+__device__ __forceinline__ void write_walk_record(float4* __restrict__ recs, uint4* __restrict__ qrecs, int r, const float4 a0, const float4 a1, int link_a,
+                                                  const float4 b0, const float4 b1, int link_b, const float glo[3], const float gstep[3])
+{
+    recs[4 * r + 0] = make_float4(a0.x, a0.y, a0.z, __int_as_float(link_a));
+    recs[4 * r + 1] = make_float4(a1.x, a1.y, a1.z, 0.0f);
+    recs[4 * r + 2] = make_float4(b0.x, b0.y, b0.z, __int_as_float(link_b));
+    recs[4 * r + 3] = make_float4(b1.x, b1.y, b1.z, 0.0f);
+    auto cell = [&](float v, int a, bool up) -> unsigned int {
+        const float c = (v - glo[a]) / gstep[a];
+        const float q = up ? ceilf(c) + 1.0f : floorf(c) - 1.0f;
+        return (unsigned int)fminf(fmaxf(q, 0.0f), 65535.0f);
+    };
+    qrecs[2 * r + 0] = make_uint4(cell(a0.x, 0, false) | (cell(a1.x, 0, true) << 16), cell(a0.y, 1, false) | (cell(a1.y, 1, true) << 16),
+                                  cell(a0.z, 2, false) | (cell(a1.z, 2, true) << 16), (unsigned int)link_a);
+    qrecs[2 * r + 1] = make_uint4(cell(b0.x, 0, false) | (cell(b1.x, 0, true) << 16), cell(b0.y, 1, false) | (cell(b1.y, 1, true) << 16),
+                                  cell(b0.z, 2, false) | (cell(b1.z, 2, true) << 16), (unsigned int)link_b);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // LBVH over the triangles, one workgroup: replaces optixAccelBuild over OPTIX_BUILD_INPUT_TYPE_TRIANGLES (sutil/Scene.cpp,
-// buildMeshAccels).  Same recipe as the analytic path's canonical tree: 30-bit Morton code of the centroid normalised to the
-// scene bounds, stable order by (code, triangle index), Karras 2012, one triangle per leaf, bottom-up fit.
+// buildMeshAccels).  Same recipe as the analytic path's canonical tree, with rtgo_build.h's functions: 30-bit Morton code of the
+// centroid normalised to the scene bounds, stable order by (code, triangle index), Karras 2012, one triangle per leaf, bottom-up fit.
 // Boxes are padded by 1e-4 of the scene's extent + 1e-6: the slab test rounds, the triangle test must never be cut off.
-// out_meta = {depth of the hierarchy, records of the walk, stack entries the walk needs, grid origin xyz, grid step xyz (float bits)}.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
                                                               float4* __restrict__ nodes, int* __restrict__ parent, int* __restrict__ visit,
                                                               int* __restrict__ first_of, int* __restrict__ count_of, int* __restrict__ rec_of,
                                                               float4* __restrict__ recs, float4* __restrict__ tris, uint4* __restrict__ qrecs,
-                                                              uint2* __restrict__ tidx, int* __restrict__ out_meta)
+                                                              uint2* __restrict__ tidx, WhittedBuildMeta* __restrict__ out_meta)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char build_keys_dyn[];   // kMaxTriangles x 8 B: the launch passes the size
     unsigned long long* s_keys = reinterpret_cast<unsigned long long*>(build_keys_dyn);
@@ -746,19 +775,7 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
                 hi[a] = fmaxf(hi[a], c);
             }
         }
-    for (int a = 0; a < 3; ++a) {
-        s_red[a][tid] = lo[a];
-        s_red[3 + a][tid] = hi[a];
-    }
-    __syncthreads();
-    for (int stride = kBuildThreads / 2; stride > 0; stride >>= 1) {
-        if (tid < stride)
-            for (int a = 0; a < 3; ++a) {
-                s_red[a][tid] = fminf(s_red[a][tid], s_red[a][tid + stride]);
-                s_red[3 + a][tid] = fmaxf(s_red[3 + a][tid], s_red[3 + a][tid + stride]);
-            }
-        __syncthreads();
-    }
+    reduce_bounds<kBuildThreads>(s_red, tid, lo, hi);
     float blo[3], ext[3], maxext = 0.0f;
     for (int a = 0; a < 3; ++a) {
         blo[a] = s_red[a][0];
@@ -766,43 +783,9 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
         maxext = fmaxf(maxext, ext[a]);
     }
     const float pad = maxext * 1e-4f + 1e-6f;
-    // Morton keys
-    for (int i = tid; i < kMaxTriangles; i += kBuildThreads) {
-        unsigned long long key = ~0ull;
-        if (i < n) {
-            unsigned int q[3];
-            for (int a = 0; a < 3; ++a) {
-                const float c = (positions[3 * indices[3 * i + 0] + a] + positions[3 * indices[3 * i + 1] + a] + positions[3 * indices[3 * i + 2] + a]) * (1.0f / 3.0f);
-                const float u = ext[a] > 0.0f ? (c - blo[a]) / ext[a] : 0.0f;
-                q[a] = (unsigned int)fminf(fmaxf(u * 1024.0f, 0.0f), 1023.0f);
-            }
-            key = ((unsigned long long)((expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2])) << 32) | (unsigned int)i;
-        }
-        s_keys[i] = key;
-    }
-    __syncthreads();
-    // bitonic sort of kMaxTriangles keys (unique: the index is part of the key)
-    for (int k = 2; k <= kMaxTriangles; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < kMaxTriangles; i += kBuildThreads) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = s_keys[i], b = s_keys[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
-                        s_keys[i] = b;
-                        s_keys[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    auto delta = [&](int i, int j) -> int {
-        if (j < 0 || j >= n) return -1;
-        const unsigned int a = (unsigned int)(s_keys[i] >> 32), b = (unsigned int)(s_keys[j] >> 32);
-        if (a == b) return 32 + __clz((unsigned int)i ^ (unsigned int)j);
-        return __clz(a ^ b);
-    };
+    // Morton keys, sorted (unique: the index is part of the key)
+    for (int i = tid; i < kMaxTriangles; i += kBuildThreads) s_keys[i] = i < n ? triangle_key(positions, indices, i, blo, ext) : ~0ull;
+    bitonic_sort<kMaxTriangles, kBuildThreads>(s_keys, tid);
     const int leaf0 = n - 1;
     // leaves
     for (int i = tid; i < n; i += kBuildThreads) {
@@ -821,24 +804,8 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
     __syncthreads();
     // Karras 2012
     for (int i = tid; i < n - 1; i += kBuildThreads) {
-        const int d = (delta(i, i + 1) - delta(i, i - 1)) >= 0 ? 1 : -1;
-        const int dmin = delta(i, i - d);
-        int lmax = 2;
-        while (delta(i, i + lmax * d) > dmin) lmax *= 2;
-        int l = 0;
-        for (int t = lmax / 2; t >= 1; t /= 2)
-            if (delta(i, i + (l + t) * d) > dmin) l += t;
-        const int j = i + l * d;
-        const int dnode = delta(i, j);
-        int s = 0, t = l;
-        do {
-            t = (t + 1) / 2;
-            if (delta(i, i + (s + t) * d) > dnode) s += t;
-        } while (t > 1);
-        const int gamma = i + s * d + (d < 0 ? -1 : 0);
-        const int lo_i = i < j ? i : j, hi_i = i < j ? j : i;
-        const int left = (lo_i == gamma) ? leaf0 + gamma : gamma;
-        const int right = (hi_i == gamma + 1) ? leaf0 + gamma + 1 : gamma + 1;
+        int left, right, lo_i, hi_i;
+        karras_node(s_keys, n, i, left, right, lo_i, hi_i);
         nodes[2 * i + 0].w = __int_as_float(left);
         nodes[2 * i + 1].w = __int_as_float(right);
         parent[left] = i;
@@ -896,21 +863,7 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
         if (r < 0) continue;
         const int L = __float_as_int(nodes[2 * i + 0].w), R = __float_as_int(nodes[2 * i + 1].w);
         const float4 a0 = nodes[2 * L], a1 = nodes[2 * L + 1], b0 = nodes[2 * R], b1 = nodes[2 * R + 1];
-        recs[4 * r + 0] = make_float4(a0.x, a0.y, a0.z, __int_as_float(link_of(L)));
-        recs[4 * r + 1] = make_float4(a1.x, a1.y, a1.z, 0.0f);
-        recs[4 * r + 2] = make_float4(b0.x, b0.y, b0.z, __int_as_float(link_of(R)));
-        recs[4 * r + 3] = make_float4(b1.x, b1.y, b1.z, 0.0f);
-        // the same record on the 16-bit grid over the padded scene box: lower planes one cell below their floor, upper planes one
-        // above their ceiling
-        auto cell = [&](float v, int a, bool up) -> unsigned int {
-            const float c = (v - glo[a]) / gstep[a];
-            const float q = up ? ceilf(c) + 1.0f : floorf(c) - 1.0f;
-            return (unsigned int)fminf(fmaxf(q, 0.0f), 65535.0f);
-        };
-        qrecs[2 * r + 0] = make_uint4(cell(a0.x, 0, false) | (cell(a1.x, 0, true) << 16), cell(a0.y, 1, false) | (cell(a1.y, 1, true) << 16),
-                                      cell(a0.z, 2, false) | (cell(a1.z, 2, true) << 16), (unsigned int)link_of(L));
-        qrecs[2 * r + 1] = make_uint4(cell(b0.x, 0, false) | (cell(b1.x, 0, true) << 16), cell(b0.y, 1, false) | (cell(b1.y, 1, true) << 16),
-                                      cell(b0.z, 2, false) | (cell(b1.z, 2, true) << 16), (unsigned int)link_of(R));
+        write_walk_record(recs, qrecs, r, a0, a1, link_of(L), b0, b1, link_of(R), glo, gstep);
         int dd = 1;   // stack entries a walk can hold below this record: one per record on the way down, its own included
         for (int q = parent[i]; q >= 0; q = parent[q]) ++dd;
         atomicMax(&s_wdepth, dd);
@@ -925,13 +878,11 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
     }
     __syncthreads();
     if (tid == 0) {
-        out_meta[0] = s_depth;
-        out_meta[1] = n > kLeafTris ? s_nrec : 0;   // 0: the mesh is one leaf, no records
-        out_meta[2] = s_wdepth;
-        for (int a = 0; a < 3; ++a) {
-            out_meta[3 + a] = __float_as_int(glo[a]);
-            out_meta[6 + a] = __float_as_int(gstep[a]);
-        }
+        out_meta->depth = s_depth;
+        out_meta->n_recs = n > kLeafTris ? s_nrec : 0;   // 0: the mesh is one leaf, no records
+        out_meta->walk_depth = s_wdepth;
+        out_meta->grid_lo = mk(glo[0], glo[1], glo[2]);
+        out_meta->grid_step = mk(gstep[0], gstep[1], gstep[2]);
     }
 }
 
@@ -939,15 +890,13 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
 // The walk's records rebuilt over the same leaves with the surface-area heuristic (second session of round 2).  build_kernel's
 // Morton hierarchy forms the leaves (subtrees of at most kLeafTris triangles: neighbours in Morton order, contiguous in `tris`);
 // above them bit prefixes know nothing of box areas, and any tree over the same leaves returns the same hits, so the topology is
-// rebuilt top-down like the analytic path's (rtgo_device.h, build_kernel): every node is split where
-// A(left) * T(left) + A(right) * T(right) is smallest over the three axes and every position of its leaves sorted by centroid
-// (T = triangles).  One workgroup: all threads walk one task queue together -- a rank sort per axis in parallel, the sweep by one
-// thread.  What sets the whitted launch is one wave's serial walk over the finely tessellated part: fewer steps there.
-// Overwrites recs / qrecs and out_meta[1] (records), [2] (stack entries); scratch: 32 n ints.
+// rebuilt top-down by the analytic path's sah_build (rtgo_build.h) with T = triangles as the weights, ties to the median.
+// What sets the whitted launch is one wave's serial walk over the finely tessellated part: fewer steps there.
+// Overwrites recs / qrecs and out_meta's n_recs and walk_depth; scratch: 32 n ints.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4* __restrict__ nodes, const int* __restrict__ parent, const int* __restrict__ first_of,
                                                             const int* __restrict__ count_of, int* __restrict__ scratch, float4* __restrict__ recs,
-                                                            uint4* __restrict__ qrecs, int* __restrict__ out_meta)
+                                                            uint4* __restrict__ qrecs, WhittedBuildMeta* __restrict__ out_meta)
 {
     if (n <= kLeafTris) return;   // the mesh is one leaf: no records
     extern __shared__ __attribute__((aligned(16))) unsigned char sah_dyn[];
@@ -956,16 +905,13 @@ __global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4*
     short* perm = reinterpret_cast<short*>(u_link + n);               // [n] leaves in the current task order
     short* tmp = perm + n;                                            // [n]
     unsigned char* u_w = reinterpret_cast<unsigned char*>(tmp + n);   // [n] triangles of the leaf
-    __shared__ int s_U, s_qtail, s_count, s_best_axis, s_best_pos, s_wdepth, s_nrec;
+    __shared__ int s_U, s_wdepth, s_nrec;
+    __shared__ SahShared s_sah;
     // global scratch (one thread group, barriers order it)
-    int* t_left = scratch;               // [2n] first child / the leaf's link
-    int* t_right = t_left + 2 * n;       // [2n] second child, -1: a leaf
-    int* t_parent = t_right + 2 * n;     // [2n]
-    int* tq_node = t_parent + 2 * n;     // [2n] task queue
-    int* tq_lo = tq_node + 2 * n;
-    int* tq_hi = tq_lo + 2 * n;
-    float* t_box = reinterpret_cast<float*>(tq_hi + 2 * n);   // [2n][6]
-    int* start = reinterpret_cast<int*>(t_box + 12 * n);      // [n] node of the leaf that starts at a Morton position, -1: none
+    // tree: left [2n] first child / the leaf's link, right [2n] second child, -1: a leaf, parent [2n]; the task queue [2n] x 3; box [2n][6]
+    const SahTree t = {reinterpret_cast<float*>(scratch + 12 * n), scratch, scratch + 2 * n, scratch + 4 * n};
+    const SahQueue<int> tq = {scratch + 6 * n, scratch + 8 * n, scratch + 10 * n};
+    int* start = reinterpret_cast<int*>(t.box + 12 * n);      // [n] node of the leaf that starts at a Morton position, -1: none
     int* rec_of = start + n;                                  // [2n]
     float* sfx = reinterpret_cast<float*>(rec_of + 2 * n);    // [n][2] suffix area and triangles of the sweep
     const int tid = threadIdx.x, leaf0 = n - 1;
@@ -996,151 +942,36 @@ __global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4*
         u_w[u] = (unsigned char)cnt;
         perm[u] = (short)u;
     }
-    if (tid == 0) {
-        tq_node[0] = 0; tq_lo[0] = 0; tq_hi[0] = U;
-        s_qtail = 1;
-        s_count = 1;
-        t_parent[0] = -1;
-    }
-    __syncthreads();
-    for (int qi = 0; qi < 2 * n; ++qi) {
-        __syncthreads();
-        if (qi >= s_qtail) break;   // (uniform: every thread reads the same word after the barrier)
-        const int lo = tq_lo[qi], hi = tq_hi[qi], node = tq_node[qi], m = hi - lo;
-        if (m == 1) {
-            if (tid == 0) {
-                const int u = perm[lo];
-                for (int c = 0; c < 6; ++c) t_box[6 * node + c] = u_box[u][c];
-                t_left[node] = u_link[u];
-                t_right[node] = -1;
-            }
-            continue;
-        }
-        if (tid == 0) {
-            s_best_axis = -1;
-            s_best_pos = m / 2;
-        }
-        float best_cost = INFINITY;   // (thread 0's)
-        for (int pass = 0; pass < 4; ++pass) {
-            // passes 0..2: try axis `pass`; pass 3: put the range back in the order of the best axis
-            __syncthreads();
-            const int axis = pass < 3 ? pass : s_best_axis;
-            if (pass == 3 && (axis < 0 || axis == 2)) break;   // (uniform) no finite cost at all, or already in z order
-            for (int e = tid; e < m; e += kBuildThreads) {
-                const int me = perm[lo + e];
-                const float key = u_box[me][axis] + u_box[me][3 + axis];
-                int rank = 0;
-                for (int j = 0; j < m; ++j) {
-                    const int other = perm[lo + j];
-                    const float kj = u_box[other][axis] + u_box[other][3 + axis];
-                    rank += (kj < key || (kj == key && other < me)) ? 1 : 0;
-                }
-                tmp[lo + rank] = (short)me;
-            }
-            __syncthreads();
-            for (int e = tid; e < m; e += kBuildThreads) perm[lo + e] = tmp[lo + e];
-            __syncthreads();
-            if (pass < 3 && tid == 0) {
-                float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                int w = 0;
-                for (int j = m - 1; j >= 1; --j) {
-                    const int u = perm[lo + j];
-                    for (int c = 0; c < 3; ++c) {
-                        b[c] = fminf(b[c], u_box[u][c]);
-                        b[3 + c] = fmaxf(b[3 + c], u_box[u][3 + c]);
-                    }
-                    w += u_w[u];
-                    const float ex = b[3] - b[0], ey = b[4] - b[1], ez = b[5] - b[2];
-                    sfx[2 * j + 0] = ex * ey + ey * ez + ez * ex;
-                    sfx[2 * j + 1] = (float)w;
-                }
-                float a[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                int wl = 0;
-                for (int j = 1; j < m; ++j) {   // left = [0, j), right = [j, m)
-                    const int u = perm[lo + j - 1];
-                    for (int c = 0; c < 3; ++c) {
-                        a[c] = fminf(a[c], u_box[u][c]);
-                        a[3 + c] = fmaxf(a[3 + c], u_box[u][3 + c]);
-                    }
-                    wl += u_w[u];
-                    const float ex = a[3] - a[0], ey = a[4] - a[1], ez = a[5] - a[2];
-                    const float cost = (ex * ey + ey * ez + ez * ex) * (float)wl + sfx[2 * j] * sfx[2 * j + 1];
-                    // ties go to the split nearer the median: a range of leaves with one and the same box (coincident or duplicated
-                    // triangles) ties at every position, and "first wins" would peel one leaf per level -- a chain as deep as the range
-                    const int dj = j > m / 2 ? j - m / 2 : m / 2 - j, db = s_best_pos > m / 2 ? s_best_pos - m / 2 : m / 2 - s_best_pos;
-                    if (cost < best_cost || (cost == best_cost && dj < db)) {
-                        best_cost = cost;
-                        s_best_axis = pass;
-                        s_best_pos = j;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            for (int j = lo; j < hi; ++j) {
-                const int u = perm[j];
-                for (int c = 0; c < 3; ++c) {
-                    b[c] = fminf(b[c], u_box[u][c]);
-                    b[3 + c] = fmaxf(b[3 + c], u_box[u][3 + c]);
-                }
-            }
-            const int cl = s_count, cr = s_count + 1;
-            s_count += 2;
-            for (int c = 0; c < 6; ++c) t_box[6 * node + c] = b[c];
-            t_left[node] = cl;
-            t_right[node] = cr;
-            t_parent[cl] = node;
-            t_parent[cr] = node;
-            const int mid = lo + s_best_pos;
-            const int t = s_qtail;
-            tq_node[t] = cl; tq_lo[t] = lo; tq_hi[t] = mid;
-            tq_node[t + 1] = cr; tq_lo[t + 1] = mid; tq_hi[t + 1] = hi;
-            s_qtail = t + 2;
-        }
-    }
-    __syncthreads();
-    const int n_nodes = s_count;
+    const int n_nodes = sah_build<kBuildThreads, true>(
+        tid, U, 2 * n, [&](int u, int c) { return u_box[u][c]; }, [&](int u) { return (int)u_w[u]; }, perm, tmp, sfx, tq, t, s_sah, [&](int node, int u) {
+            t.left[node] = u_link[u];
+            t.right[node] = -1;
+        });
     if (tid == 0) {
         int r = 0;
-        for (int k = 0; k < n_nodes; ++k) rec_of[k] = t_right[k] >= 0 ? r++ : -1;   // (the root is node 0 and record 0)
+        for (int k = 0; k < n_nodes; ++k) rec_of[k] = t.right[k] >= 0 ? r++ : -1;   // (the root is node 0 and record 0)
         s_nrec = r;
     }
     __syncthreads();
-    float glo[3], gstep[3];
-    for (int a = 0; a < 3; ++a) {
-        glo[a] = __int_as_float(out_meta[3 + a]);
-        gstep[a] = __int_as_float(out_meta[6 + a]);
-    }
+    const float glo[3] = {out_meta->grid_lo.x, out_meta->grid_lo.y, out_meta->grid_lo.z};
+    const float gstep[3] = {out_meta->grid_step.x, out_meta->grid_step.y, out_meta->grid_step.z};
     for (int k = tid; k < n_nodes; k += kBuildThreads) {
         const int r = rec_of[k];
         if (r < 0) continue;
-        const int L = t_left[k], R = t_right[k];
-        const int linkL = t_right[L] >= 0 ? rec_of[L] : t_left[L], linkR = t_right[R] >= 0 ? rec_of[R] : t_left[R];
-        const float* a = t_box + 6 * L;
-        const float* b = t_box + 6 * R;
-        recs[4 * r + 0] = make_float4(a[0], a[1], a[2], __int_as_float(linkL));
-        recs[4 * r + 1] = make_float4(a[3], a[4], a[5], 0.0f);
-        recs[4 * r + 2] = make_float4(b[0], b[1], b[2], __int_as_float(linkR));
-        recs[4 * r + 3] = make_float4(b[3], b[4], b[5], 0.0f);
-        auto cell = [&](float v, int ax, bool up) -> unsigned int {
-            const float c = (v - glo[ax]) / gstep[ax];
-            const float q = up ? ceilf(c) + 1.0f : floorf(c) - 1.0f;
-            return (unsigned int)fminf(fmaxf(q, 0.0f), 65535.0f);
-        };
-        qrecs[2 * r + 0] = make_uint4(cell(a[0], 0, false) | (cell(a[3], 0, true) << 16), cell(a[1], 1, false) | (cell(a[4], 1, true) << 16),
-                                      cell(a[2], 2, false) | (cell(a[5], 2, true) << 16), (unsigned int)linkL);
-        qrecs[2 * r + 1] = make_uint4(cell(b[0], 0, false) | (cell(b[3], 0, true) << 16), cell(b[1], 1, false) | (cell(b[4], 1, true) << 16),
-                                      cell(b[2], 2, false) | (cell(b[5], 2, true) << 16), (unsigned int)linkR);
+        const int L = t.left[k], R = t.right[k];
+        const int linkL = t.right[L] >= 0 ? rec_of[L] : t.left[L], linkR = t.right[R] >= 0 ? rec_of[R] : t.left[R];
+        const float* a = t.box + 6 * L;
+        const float* b = t.box + 6 * R;
+        write_walk_record(recs, qrecs, r, make_float4(a[0], a[1], a[2], 0.0f), make_float4(a[3], a[4], a[5], 0.0f), linkL, make_float4(b[0], b[1], b[2], 0.0f),
+                          make_float4(b[3], b[4], b[5], 0.0f), linkR, glo, gstep);
         int dd = 1;   // stack entries a walk can hold below this record: one per record on the way down, its own included
-        for (int q = t_parent[k]; q >= 0; q = t_parent[q]) ++dd;
+        for (int q = t.parent[k]; q >= 0; q = t.parent[q]) ++dd;
         atomicMax(&s_wdepth, dd);
     }
     __syncthreads();
     if (tid == 0) {
-        out_meta[1] = s_nrec;
-        out_meta[2] = s_wdepth;
+        out_meta->n_recs = s_nrec;
+        out_meta->walk_depth = s_wdepth;
     }
 }
 

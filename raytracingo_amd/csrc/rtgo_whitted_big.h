@@ -50,19 +50,7 @@ __global__ __launch_bounds__(1024) void big_bounds_kernel(const float* __restric
                 hi[a] = fmaxf(hi[a], c);
             }
         }
-    for (int a = 0; a < 3; ++a) {
-        s_red[a][tid] = lo[a];
-        s_red[3 + a][tid] = hi[a];
-    }
-    __syncthreads();
-    for (int stride = 512; stride > 0; stride >>= 1) {
-        if (tid < stride)
-            for (int a = 0; a < 3; ++a) {
-                s_red[a][tid] = fminf(s_red[a][tid], s_red[a][tid + stride]);
-                s_red[3 + a][tid] = fmaxf(s_red[3 + a][tid], s_red[3 + a][tid + stride]);
-            }
-        __syncthreads();
-    }
+    reduce_bounds<1024>(s_red, tid, lo, hi);
     if (tid < 6) partial[6 * blockIdx.x + tid] = s_red[tid][0];
 }
 
@@ -77,19 +65,7 @@ __global__ __launch_bounds__(1024) void big_bounds_final_kernel(const float* __r
             lo[a] = fminf(lo[a], partial[6 * i + a]);
             hi[a] = fmaxf(hi[a], partial[6 * i + 3 + a]);
         }
-    for (int a = 0; a < 3; ++a) {
-        s_red[a][tid] = lo[a];
-        s_red[3 + a][tid] = hi[a];
-    }
-    __syncthreads();
-    for (int stride = 512; stride > 0; stride >>= 1) {
-        if (tid < stride)
-            for (int a = 0; a < 3; ++a) {
-                s_red[a][tid] = fminf(s_red[a][tid], s_red[a][tid + stride]);
-                s_red[3 + a][tid] = fmaxf(s_red[3 + a][tid], s_red[3 + a][tid + stride]);
-            }
-        __syncthreads();
-    }
+    reduce_bounds<1024>(s_red, tid, lo, hi);
     if (tid < 6) bounds[tid] = s_red[tid][0];
 }
 
@@ -99,15 +75,8 @@ __global__ __launch_bounds__(256) void big_keys_kernel(const float* __restrict__
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    unsigned int q[3];
-    for (int a = 0; a < 3; ++a) {
-        const float blo = bounds[a], ext = bounds[3 + a] - bounds[a];
-        const float c = (positions[3 * (size_t)indices[3 * (size_t)i + 0] + a] + positions[3 * (size_t)indices[3 * (size_t)i + 1] + a] +
-                         positions[3 * (size_t)indices[3 * (size_t)i + 2] + a]) * (1.0f / 3.0f);
-        const float u = ext > 0.0f ? (c - blo) / ext : 0.0f;
-        q[a] = (unsigned int)fminf(fmaxf(u * 1024.0f, 0.0f), 1023.0f);
-    }
-    keys[i] = ((unsigned long long)((expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2])) << 32) | (unsigned int)i;
+    const float lo[3] = {bounds[0], bounds[1], bounds[2]}, ext[3] = {bounds[3] - bounds[0], bounds[4] - bounds[1], bounds[5] - bounds[2]};
+    keys[i] = triangle_key(positions, indices, i, lo, ext);
 }
 
 // radix pass, step 1: how many keys of workgroup b's tile have digit d at `shift` -> hist[d * n_blocks + b]
