@@ -495,6 +495,15 @@ struct FastHit {
 constexpr int kFlat = 0x10000;
 constexpr float kCuboidTol = 1e-4f;   // cuboid certificate: how far (in a face's object-space y) another face's corner may be on the wrong side of its plane
 
+__device__ __forceinline__ unsigned int wave_sum(unsigned int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+#include "rtgo_probes.h"   // the diagnostic builds' instruments: Timeline, StreamStats, FastCounters, CmpWalk, WhittedTiming
+
 // the acceptance rule of SURVEY a14 (tmin < t < current closest; ties keep the lower SBT index), without branches
 __device__ __forceinline__ bool closer(float t, int orig, float tmin, const FastHit& best)
 {
@@ -831,13 +840,7 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
             const float4 l0 = s_fnodes[2 * left], l1 = s_fnodes[2 * left + 1];
             const float4 h0 = s_fnodes[2 * right], h1 = s_fnodes[2 * right + 1];
             float tl, tr;
-#ifdef RTGO_FAST_COUNTERS
-#if RTGO_FAST_COUNTERS == 2   /* wave-level: one count per executed node step / leaf phase, whatever the number of live lanes */
-            dbg_boxes += (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) ? 1u : 0u;
-#else
-            dbg_boxes += 2;
-#endif
-#endif
+            FastCounters::step(dbg_boxes, 2u);
             const bool hl = box_fast(l0, l1, id, noid, tmin, best.t, tl);
             const bool hr = box_fast(h0, h1, id, noid, tmin, best.t, tr);
             // the step as selects: go to the right child when only it is hit, or when both are and it is nearer; the other one
@@ -856,13 +859,7 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
         }
         if (have) {
             const int first = left, cnt = leaf_count(right), npairs = leaf_pairs(right);
-#ifdef RTGO_FAST_COUNTERS
-#if RTGO_FAST_COUNTERS == 2
-            dbg_tests += (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) ? 1u : 0u;
-#else
-            dbg_tests += (unsigned int)cnt;
-#endif
-#endif
+            FastCounters::step(dbg_tests, (unsigned int)cnt);
             if (tree_spheres) sphere_leaf(s_fprims, first, cnt, o, d, tmin, best);
             else if (leaf_cuboid(right) != 0 && cub_mu > 0.0f) cuboid_range<false>(s_fprims, s_fprims, first, cub_mu, -INFINITY, o, d, tmin, best);
             else leaf_range<false>(s_fprims, s_fprims, first, cnt, npairs, o, d, tmin, best);
@@ -941,13 +938,7 @@ __device__ __forceinline__ void fast_grid(const float4* __restrict__ s_grid, con
     while (live) {
         // to the next cell that lists something in the ray's way: out of the current one through the nearest of its three far planes
         while (live && fc == 0u) {
-#ifdef RTGO_FAST_COUNTERS
-#if RTGO_FAST_COUNTERS == 2   /* wave-level: one count per executed iteration, whatever the number of live lanes */
-            dbg_boxes += (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) ? 1u : 0u;
-#else
-            dbg_boxes += 1;
-#endif
-#endif
+            FastCounters::step(dbg_boxes, 1u);
             const bool ux = (tmx <= tmy) & (tmx <= tmz), uy = !ux & (tmy <= tmz);
             const float te = ux ? tmx : (uy ? tmy : tmz);
             live = te <= tstop;
@@ -961,13 +952,9 @@ __device__ __forceinline__ void fast_grid(const float4* __restrict__ s_grid, con
             const int first = (int)(fc & 0xFFFFu), cnt = (int)(fc >> 16);
             for (int k = 0; k < cnt; ++k) {
                 const int pos = (int)items[first + k];
-#if defined(RTGO_FAST_COUNTERS) && RTGO_FAST_COUNTERS == 2
-                dbg_tests += (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63u)) ? 1u : 0u;
-#endif
+                FastCounters::wave_only(dbg_tests);
                 if (pos != last) {
-#if defined(RTGO_FAST_COUNTERS) && RTGO_FAST_COUNTERS != 2
-                    dbg_tests += 1;
-#endif
+                    FastCounters::lane_only(dbg_tests, 1u);
                     if (spheres) sphere_leaf(s_fprims, pos, 1, o, d, tmin, best);
                     else leaf_test(s_fprims, pos, o, d, tmin, best);
                 }
@@ -1015,33 +1002,20 @@ __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fn
                                                  const float4* __restrict__ g_fprims, const GridParams grid,
  unsigned int* __restrict__ s_stack, int bshift,
                                                  int n_small, int n_prims, int n_big_pairs, int list_cub, float cub_mu, bool tree_spheres, v3 o, v3 d, float tmin, float tmax, Hit& out,
-                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, bool last
-#ifdef RTGO_TIMELINE
-                                                 , unsigned long long& tl_big, unsigned long long& tl_tree
-#endif
-)
+                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, bool last, Timeline& tl)
 {
-#ifdef RTGO_TIMELINE
-    const unsigned long long tl_s0 = wall_clock64();
-#endif
+    tl.walk_begin();
     FastHit best;
     best.t = tmax;
     best.pos = -1;
     best.orig = -1;
     fast_list<LAST>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
     const bool walk = !last || best.pos >= 0;
-#if defined(RTGO_FAST_COUNTERS) && RTGO_FAST_COUNTERS != 2
-    dbg_tests += (unsigned int)(n_prims - n_small - (last ? 6 : 0));
-#endif
-#ifdef RTGO_TIMELINE
-    const unsigned long long tl_s1 = wall_clock64() + (best.pos == 12345 ? 1 : 0);
-    tl_big += tl_s1 - tl_s0;
-#endif
+    FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (last ? 6 : 0)));
+    tl.list_done(best.pos);
     if constexpr (GRID) fast_grid(s_fnodes, s_fprims, grid, tree_spheres, o, d, tmin, best, dbg_boxes, dbg_tests);
     else if (!LAST || walk) fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
-#ifdef RTGO_TIMELINE
-    tl_tree += wall_clock64() + (best.pos == 12345 ? 1 : 0) - tl_s1;
-#endif
+    tl.walk_done(best.pos);
     return fast_winner(s_fprims, o, d, tmax, best, out);
 }
 
@@ -1139,13 +1113,6 @@ __device__ __forceinline__ bool faces_away(v3 N, v3 w)
 }
 
 __device__ __forceinline__ float clampf(float f, float a, float b) { return fmaxf(a, fminf(f, b)); }  // vec_math.h:115-118
-
-__device__ __forceinline__ unsigned int wave_sum(unsigned int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // The lane's index within its wave, as a value the compiler cannot hoist out of the loop it is read in.  What render_kernel derives
 // from the lane (the pixel and sample of a unit, per-lane queue addresses, the tea<16> input) is cheap to derive again; hoisted to
@@ -1321,14 +1288,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid < kQueues) p.queue_next[kQueueStride * (unsigned int)tid] = 0u;
-#ifdef RTGO_TIMELINE
-    const unsigned long long tl_t0 = wall_clock64();
-    unsigned long long tl_t1 = 0, tl_first = 0, tl_lanes = 0, tl_qwait = 0, tl_cold = 0;
-    unsigned int tl_hot = 0;
-    unsigned long long tl_a = 0, tl_b = 0, tl_c = 0, tl_d = 0, tl_big = 0, tl_tree = 0, tl_loop = 0;
-    unsigned long long tls_regen = 0, tls_trace = 0, tls_shade = 0, tls_lanes_trace = 0, tls_lanes_regen = 0, tls_regens = 0;   // streaming loop (tools/timeline_stream.py)
-    unsigned int tl_units = 0, tl_iters = 0;
-#endif
+    Timeline tl;        // (diagnostic builds' probes, rtgo_probes.h: empty types in the product build)
+    StreamStats census;
+    tl.kernel_start();
     if (STATS) {
         if (!GLOBAL) {
             for (int i = tid; i < 2 * p.n_nodes; i += kBlock) s_nodes[i] = p.nodes[i];
@@ -1361,9 +1323,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     }
     __syncthreads();
 
-#ifdef RTGO_TIMELINE
-    tl_t1 = wall_clock64();
-#endif
+    tl.staged();
     float2* s_stack = s_stack_base + tid;                                                 // canonical walk: (distance, node) entries
     unsigned int* s_stack4 = reinterpret_cast<unsigned int*>(s_stack_base) + tid;         // fast walk: one packed word per entry
     const int lane = tid & 63;
@@ -1393,9 +1353,6 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
     const unsigned int group_base0 = (pl0 < P ? pl0 : 0u) * nn_eff;
 
     unsigned int c_rays = 0, c_occl = 0, c_nodes = 0, c_tests = 0, c_hits = 0;
-#ifdef RTGO_STREAM_STATS
-    unsigned long long ss_iter = 0, ss_trace = 0, ss_shade_rounds = 0, ss_shade = 0, ss_stall = 0;   // diagnostic: streaming-loop census
-#endif
 
     // Work queue: kQueues heads, 64 bytes apart; head q serves the entries u with u % kQueues == q.  A wave pulls from the head
     // blockIdx % kQueues and, when that runs dry, from the others.  One head saturates at ~88 dequeues/us chip-wide
@@ -1415,14 +1372,10 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         const LaunchParams& p = params_here<LEAN>(p_arg);
         const unsigned int lane_q = lane_index();
         const unsigned int q_count = (p.n_tiles + (unsigned int)kQueues - 1u - q) / (unsigned int)kQueues;   // units in queue q
-#ifdef RTGO_TIMELINE
-        const unsigned long long tl_q0 = wall_clock64();
-#endif
+        tl.queue_wait_begin();
         const unsigned int first = __builtin_amdgcn_readfirstlane(pending) + pending_off;
-#ifdef RTGO_TIMELINE
-        tl_qwait += wall_clock64() - tl_q0;
-        if (tl_a == 0) tl_a = wall_clock64();
-#endif
+        tl.queue_wait_end();
+        tl.first_pull_known();
         if (first >= q_count) {
             // own head is past its end: look at all heads at once (one load, lanes 0..7) and move to one that still has work.
             // Heads only grow, so "none has work" is final: the wave leaves and the grid drains.
@@ -1485,9 +1438,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         unsigned int strip_seed;
         if (SEEDS && p.seeds != nullptr) strip_seed = lane_q < p.grab * P ? p.seeds[strip * (p.grab * P) + lane_q] : 0u;
         else strip_seed = tea16(p.W * gy + (p.x0 + strip_x0 + lane_q), p.frame);
-#ifdef RTGO_TIMELINE
-        if (tl_b == 0) tl_b = wall_clock64() + (strip_seed == 0x12345u ? 1 : 0);
-#endif
+        tl.seeds_hashed(strip_seed);
 #pragma unroll 1
         for (unsigned int ui = 0; ui < p.grab; ++ui) {
         const LaunchParams& p = params_here<LEAN>(p_arg);
@@ -1528,27 +1479,14 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         int sPrim, sLight;
 #include "rtgo_start_sample.inc"
 
-#ifdef RTGO_TIMELINE
-        if (tl_units++ == 0) tl_first = wall_clock64();
-        if (ui == 0) {
-            if (strip < p.n_hot) tl_hot += 1;
-            else if (tl_cold == 0) tl_cold = wall_clock64();
-        }
-#endif
+        tl.unit_begin(ui, strip < p.n_hot);
         while (__ballot(active) != 0ull) {
-#ifdef RTGO_TIMELINE
-            if (tl_iters == 1 && tl_c == 0) tl_c = wall_clock64();
-            tl_iters += 1;
-            const unsigned long long tl_i0 = wall_clock64();
-            tl_lanes += (unsigned long long)__popcll(__ballot(active));
-#endif
+            tl.iter_begin(active);
             if (active) {
 #include "rtgo_ray_trace.inc"
 #include "rtgo_ray_shade.inc"
             }
-#ifdef RTGO_TIMELINE
-            tl_loop += wall_clock64() + (result.x == 12345.0f ? 1 : 0) - tl_i0;
-#endif
+            tl.iter_end(seed);
         }
         // color += payload, in sample order (kernel.cu:232): every lane of a pixel's group walks the group's results
         {
@@ -1613,14 +1551,8 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
                 lvA[q] = mk(0, 0, 0);
                 lvPrim[q] = 0;
             }
-#ifdef RTGO_TIMELINE
-            unsigned long long ts_regen = 0, ts_trace = 0, ts_shade = 0, ts_fold = 0, ts_lanes_trace = 0, ts_lanes_regen = 0, ts_regens = 0;
-#endif
             while (fold_ptr < n_tasks) {
-#ifdef RTGO_TIMELINE
-                const unsigned long long ts0 = wall_clock64();
-                tl_iters += 1;
-#endif
+                tl.stream_iter_begin();
                 // ---- idle lanes take the next tasks, in lane order
                 const unsigned long long m_idle = __builtin_amdgcn_ballot_w64(!active), m_act = ~m_idle;
                 const unsigned int room = kRing - (t_next - fold_ptr);
@@ -1642,36 +1574,18 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 #include "rtgo_start_sample.inc"
                     }
                     t_next += n_take;
-#ifdef RTGO_TIMELINE
-                    ts_lanes_regen += n_take;
-                    ts_regens += 1;
-#endif
+                    tl.stream_regen(n_take);
                 }
-#ifdef RTGO_TIMELINE
-                const unsigned long long ts1 = wall_clock64() + (seed == 0x12345u ? 1 : 0);
-                ts_regen += ts1 - ts0;
-                unsigned long long ts3 = ts1;
-#endif
+                tl.stream_regen_done(seed);
                 const bool run = active;
                 // ---- one ray for every lane that runs
                 if (__builtin_amdgcn_ballot_w64(run) != 0ull) {
-#ifdef RTGO_TIMELINE
-                    ts_lanes_trace += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(run));
-#endif
-#ifdef RTGO_STREAM_STATS
-                    ss_iter += 1;
-                    ss_trace += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(active));
-                    if (room == 0u && m_idle != 0ull && t_next < n_tasks) ss_stall += 1;
-#endif
+                    tl.stream_trace_begin(run);
+                    census.trace_round(active, room == 0u && m_idle != 0ull && t_next < n_tasks);
                     const bool was = run;
                     if (run) {
 #include "rtgo_ray_trace.inc"
-#ifdef RTGO_STREAM_STATS
-                        if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {
-                            ss_shade_rounds += 1;
-                            ss_shade += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(hit));
-                        }
-#endif
+                        census.shade_round(hit);
 #include "rtgo_ray_shade.inc"
                     }
                     if (was && !active) {
@@ -1679,10 +1593,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
                         s_ring[2u * kRing + my_slot] = result.z;
                         s_ring[my_slot] = result.x;
                     }
-#ifdef RTGO_TIMELINE
-                    ts3 = wall_clock64() + (result.x == 12345.0f ? 1 : 0);
-                    ts_trace += ts3 - ts1;   // (trace + shading + the ring write of this iteration)
-#endif
+                    tl.stream_trace_done(result.x);   // (trace + shading + the ring write of this iteration)
                 }
                 // ---- the completed prefix of the task list goes into the pixels
                 {
@@ -1702,14 +1613,9 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
                         fold_ptr += n_ready;
                     }
                 }
-#ifdef RTGO_TIMELINE
-                ts_shade += wall_clock64() + (color.x == 12345.0f ? 1 : 0) - ts3;   // (the fold of the completed prefix)
-#endif
+                tl.stream_fold_done(color.x);   // (the fold of the completed prefix)
             }
-#ifdef RTGO_TIMELINE
-            tls_regen += ts_regen; tls_trace += ts_trace; tls_shade += ts_shade; tls_lanes_trace += ts_lanes_trace; tls_lanes_regen += ts_lanes_regen; tls_regens += ts_regens;
-            tl_units += 1;
-#endif
+            tl.stream_unit_done();
             if ((unsigned int)lane < npx) write_pixel(p, (size_t)lr * p.w + strip_x0 + ui * P + (unsigned int)lane, vscale(color, inv_nn()), frame_ratio());
         }
 
@@ -1722,26 +1628,14 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
                 write_pixel(p, (size_t)lr * p.w + lx, vscale(color, inv_nn()), frame_ratio());
             }
         }
-#ifdef RTGO_TIMELINE
-        if (tl_d == 0) tl_d = wall_clock64();
-#endif
+        tl.unit_done();
         }  // unit
     }
     // the queue has run dry: next frame's seeds
     if constexpr (SEEDS)
         if (params_here<LEAN>(p_arg).seeds_next != nullptr) next_frame_seeds(params_here<LEAN>(p_arg), lane_index(), P, blockIdx.x * wpb + wave_in_block, gridDim.x * wpb);
 
-#ifdef RTGO_TIMELINE
-    if (lane == 0) {
-        unsigned long long* r = p.timeline + 16ull * (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-        r[8] = tl_a; r[9] = tl_b; r[10] = tl_c; r[11] = tl_d; r[12] = tl_big; r[13] = tl_tree; r[14] = tl_loop;
-        if constexpr (STREAM) {
-            r[8] = tls_regen; r[9] = tls_trace; r[10] = tls_shade; r[11] = tls_lanes_trace; r[14] = tls_regens; r[15] = tls_lanes_regen;
-        }
-        r[0] = tl_t0; r[1] = tl_t1; r[2] = tl_first; r[3] = wall_clock64(); r[4] = tl_units | ((unsigned long long)tl_hot << 32); r[5] = tl_iters; r[6] = tl_lanes;
-        r[7] = tl_qwait | ((tl_cold ? tl_cold - tl_t0 : 0ull) << 32);
-    }
-#endif
+    tl.write<STREAM>(p, lane);
     // one atomic per wave per counter
     c_rays = wave_sum(c_rays);
     c_occl = wave_sum(c_occl);
@@ -1750,26 +1644,8 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
         c_tests = wave_sum(c_tests);
         c_hits = wave_sum(c_hits);
     }
-#ifdef RTGO_FAST_COUNTERS
-    // diagnostic build only: what the FAST walk itself visits (boxes tested, leaf tests incl. the up-front list)
-    if (!STATS) {
-        c_nodes = wave_sum(c_nodes);
-        c_tests = wave_sum(c_tests);
-        if (lane == 0) {
-            atomicAdd(&p.counters[5], (unsigned long long)c_nodes);
-            atomicAdd(&p.counters[6], (unsigned long long)c_tests);
-        }
-    }
-#endif
-#ifdef RTGO_STREAM_STATS
-    if (lane == 0 && !STATS) {
-        atomicAdd(&p.counters[2], ss_iter);          // -> node_visits
-        atomicAdd(&p.counters[3], ss_trace);         // -> prim_tests
-        atomicAdd(&p.counters[4], ss_shade_rounds);  // -> hits
-        atomicAdd(&p.counters[5], ss_shade);         // -> dbg_fast_boxes
-        atomicAdd(&p.counters[6], ss_stall);         // -> dbg_fast_tests
-    }
-#endif
+    FastCounters::flush<STATS>(p, c_nodes, c_tests, lane);
+    census.flush<STATS>(p, lane);
     if (lane == 0) {
         const LaunchParams& p = params_here<LEAN>(p_arg);
         atomicAdd(&p.counters[0], (unsigned long long)c_rays);

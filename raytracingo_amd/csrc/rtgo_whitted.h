@@ -568,10 +568,8 @@ __device__ __forceinline__ void accumulate(const Frame& f, unsigned int idx, v3 
 template <typename Preload, typename Pixel>
 __device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, Pixel&& pixel)
 {
-#ifdef RTGO_WHITTED_TIMING
-    const unsigned long long wt0 = wall_clock64();
-    unsigned long long wt_tiles = 0, wt_n = 0, wt_max = 0;
-#endif
+    WhittedTiming timing;   // (diagnostic build's probe, rtgo_probes.h: an empty type in the product build)
+    timing.wave_start();
     preload();
     if (blockIdx.x == 0 && threadIdx.x < (unsigned int)kTileHeads) f.tile_counter_next[kTileHeadStride * threadIdx.x] = 0u;
     const unsigned int lane = threadIdx.x & 63u;
@@ -600,31 +598,17 @@ __device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, 
         // queue at the vector memory pipeline for its triangles; scattered, tiles that wait for triangles overlap tiles that do not
         const unsigned int tile = (unsigned int)(((unsigned long long)(pos * (unsigned int)kTileHeads + head) * f.tile_stride) % n_tiles);
         if (lane == 0u) pending = atomicAdd(f.tile_counter + kTileHeadStride * head, 1u);
-#ifdef RTGO_WHITTED_TIMING
-        const unsigned long long wt2 = wall_clock64();
-        wt_n += 1;
-#endif
+        timing.tile_begin();
         const unsigned int ty = tile / f.tiles_x, tx = tile - ty * f.tiles_x;
         const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // in the compact local image
         if (lx < f.share.lw && ly < f.share.lh) accumulate(f, ly * f.share.lw + lx, pixel(f.share.x0 + lx, share_row(f.share, ly), rays));
-#ifdef RTGO_WHITTED_TIMING
-        const unsigned long long wt3 = wall_clock64() + (rays.total == 0xFFFFFFFFu ? 1 : 0) - wt2;
-        wt_tiles += wt3;
-        if (lx < f.share.lw && ly < f.share.lh) f.accum[ly * f.share.lw + lx].w = (float)wt3;   // (diagnostic: ticks of the tile)
-        wt_max = wt3 > wt_max ? wt3 : wt_max;
-#endif
+        timing.tile_end(f, lx < f.share.lw && ly < f.share.lh, ly * f.share.lw + lx, rays.total);
     }
     const unsigned int total = wave_sum(rays.total), occlusion = wave_sum(rays.occlusion);
     if (lane == 0u) {
         atomicAdd(&f.counters[0], (unsigned long long)total);
         atomicAdd(&f.counters[1], (unsigned long long)occlusion);
-#ifdef RTGO_WHITTED_TIMING
-        // diagnostic build (tools/whitted_perf.py prints them): 10 ns ticks summed over the waves
-        atomicAdd(&f.counters[2], wall_clock64() - wt0);   // wave lifetime          -> rtgo_stats.node_visits
-        atomicAdd(&f.counters[4], wt_tiles);               // inside tiles           -> hits
-        atomicAdd(&f.counters[5], wt_n);                   // tiles                  -> dbg_fast_boxes
-        atomicMax(&f.counters[6], wt_max);                 // the longest tile       -> dbg_fast_tests
-#endif
+        timing.flush(f);
     }
 }
 

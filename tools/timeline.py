@@ -1,6 +1,8 @@
 """developer tool: per-wave timeline of one launch.  Needs the -DRTGO_TIMELINE build:
    hipcc ... -DRTGO_TIMELINE -o tools/_diag/librtgo_hip_timeline.so raytracingo_amd/csrc/rtgo_capi.hip
-   RTGO_HIP_LIB=tools/_diag/librtgo_hip_timeline.so BANDS=8,0 python tools/timeline.py [scene] [W] [H] [N] [mode]"""
+   RTGO_HIP_LIB=tools/_diag/librtgo_hip_timeline.so BANDS=8,0 python tools/timeline.py [scene] [W] [H] [N] [mode]
+   "ray-loop time" sums the lock-step iterations from their start to the point where the lane's random state is final (Timeline::iter_end):
+   the payload write of a path that ends in the iteration may fall after it."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 os.environ.setdefault("RTGO_HIP_LIB", os.path.join(ROOT, "tools/_diag/librtgo_hip_timeline.so"))
