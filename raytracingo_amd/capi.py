@@ -376,6 +376,38 @@ class Context:
         boxes = nodes[:, [0, 1, 2, 4, 5, 6]].copy()
         return boxes, links, inv, aabb
 
+    # ---- diagnostics outside include/rtgo.h (resolved when first used, not declared in load(): SYMBOLS is the header's list) ----
+    def build_digest(self, whitted):
+        """rtgo_debug_build_digest: one FNV-1a digest per span of what the builds wrote, as a list of ints"""
+        fn = self._lib.rtgo_debug_build_digest
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]
+        out, n = (C.c_uint64 * 4096)(), C.c_uint32(0)
+        self._check(fn(self._h, 1 if whitted else 0, out, 4096, C.byref(n)), "rtgo_debug_build_digest")
+        return [int(out[k]) for k in range(min(n.value, 4096))]
+
+    def read_build(self, whitted):
+        """rtgo_debug_read_build: every span of what the builds wrote for the current scene, as a dict name -> numpy array, in the
+        library's order.  float4 arrays come as float32 [n, 4], box lists as float32 [n, 6], qrecs / tidx / clusters / top.inst as 32-bit
+        words per row, grid.image as bytes, everything else (meta words, infos) as int32 words (view them as float32 where they are)."""
+        fn = self._lib.rtgo_debug_read_build_named
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+        n_spans = len(self.build_digest(whitted))
+        shapes = {"nodes": (np.float32, 4), "prims": (np.float32, 4), "frames": (np.float32, 4), "fnodes": (np.float32, 4), "fprims": (np.float32, 4),
+                  "recs": (np.float32, 4), "tris": (np.float32, 4), "tight": (np.float32, 6), "aabb": (np.float32, 6), "qrecs": (np.uint32, 4),
+                  "tidx": (np.uint32, 2), "clusters": (np.int32, 4), "inst": (np.uint32, 16), "image": (np.uint8, 0)}
+        out = {}
+        for k in range(n_spans):
+            size, name = C.c_size_t(0), C.create_string_buffer(64)
+            self._check(fn(self._h, 1 if whitted else 0, k, None, 0, C.byref(size), name, 64), "rtgo_debug_read_build")
+            raw = np.zeros(size.value, np.uint8)
+            self._check(fn(self._h, 1 if whitted else 0, k, raw.ctypes.data if size.value else None, raw.nbytes, C.byref(size), None, 0), "rtgo_debug_read_build")
+            dt, cols = shapes.get(name.value.decode().split(".")[-1], (np.int32, 0))
+            a = raw.view(dt)
+            out[name.value.decode()] = a.reshape(-1, cols) if cols else a
+        return out
+
 
 def whitted_instances(instances):
     """instances: a list of (transform, mesh, material_offset) -- transform a row-major 3 x 4 (or 4 x 4, last row ignored) object-to-world

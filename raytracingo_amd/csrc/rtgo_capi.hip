@@ -38,7 +38,7 @@ struct WhittedMeshInfo {
     int n_tris;
     // what each whitted_build of this mesh wrote into the context's arrays (rtgo_debug_build_digest): records [rec0, rec0 + n_recs) and
     // their quantised forms at qrecs[2 tri0 ..] (tri0 < 0: none kept, a mid level's)
-    struct Built { int rec0, n_recs, tri0; };
+    struct Built { int rec0, n_recs, tri0; whitted::WhittedBuildMeta meta; };   // (meta: what that build reported)
     std::vector<Built> built;
 };
 
@@ -69,6 +69,7 @@ struct AnalyticScene {
         // has to exceed, K (emit_a R + emit_b) (last_ray_params)
         int emit_n = 0;
         float emit_ymin[6 * kMaxEmitters] = {}, emit_a[6 * kMaxEmitters] = {}, emit_b[6 * kMaxEmitters] = {};
+        BuildMeta meta = {};               // build_kernel's meta words as it wrote them (rtgo_debug_read_build)
         bool sane(uint32_t n) const { return n_fnodes >= 0 && n_fnodes <= 2 * (int)n - 1 && !(n_small > 0 && n_fnodes < 1); }
     } tree[2];                             // the structures of 36 % and 15 %
     bool have_alt = false;                 // tree[1] is a candidate: false when the two builds came out the same, or RTGO_BIG_PERCENT pins one
@@ -94,6 +95,7 @@ struct WhittedTop {
     DeviceArray<whitted::InstWalk> inst;       // in the top level's leaf order
     DeviceArray<whitted::InstShade> shade;     // in the caller's order
     int n_recs = 0, n_instances = 0;
+    whitted::WhittedBuildMeta meta = {};       // what its build reported (rtgo_debug_read_build)
 };
 
 // The whitted triangle path's scene (rtgo_whitted.h; rtgo_whitted_set_mesh, rtgo_whitted_set_scene): replaced as a whole
@@ -115,6 +117,7 @@ struct WhittedMesh {
     int n_vertices = 0;
     v3 grid_lo{0, 0, 0}, grid_step{0, 0, 0};
     int n_recs = 0, walk_depth = 0;
+    whitted::WhittedBuildMeta meta = {};       // what the build reported (one mesh; rtgo_debug_read_build)
     int triangles = 0, n_materials = 0;        // triangles = 0: no mesh
     // an instanced scene (rtgo_whitted_set_scene): the mesh buffers above hold every mesh back to back in object space (nodes,
     // scratch: the largest mesh's build), plus the top level
@@ -480,89 +483,191 @@ static void digest_host(const void* p, size_t bytes, uint64_t& h)
     for (size_t k = 0; k < bytes; ++k) h = (h ^ static_cast<const unsigned char*>(p)[k]) * 0x100000001B3ull;
 }
 
-// diagnostic (tools/build_digest.py; not part of include/rtgo.h): one FNV-1a digest per device buffer the build kernels wrote for the
-// context's current scene, over the ranges the build defines (not allocation slack); *n_out = how many (at most `cap` are stored).
-//   analytic (whitted = 0): d_nodes, d_prims, d_frames, d_tight, d_aabb; then for tree[0] and tree[1]: d_fnodes (2 * n_fnodes float4),
-//     d_fprims, the decoded meta fields {canonical depth, bounds[6], fast_depth, n_small, n_fnodes, n_big_pairs, list_cub, cuboid_groups,
-//     tree_spheres, cub_a, cub_b}.  A scene of rtgo_set_large_scene has the first five only (frames and tight boxes empty).
-//   whitted (whitted = 1), one mesh: recs (4 * n_recs float4), qrecs (2 * n_recs), tris, tidx, {grid_lo, grid_step}, {n_recs, walk_depth};
-//     an instanced scene: per mesh recs, qrecs (each over the ranges its builds wrote, in build order), tris, tidx, {root, depth, n_recs
-//     of each build}; then the top level's recs and inst, then clusters.
-extern "C" int rtgo_debug_build_digest(rtgo_ctx* c, int whitted, uint64_t* out, uint32_t cap, uint32_t* n_out)
+}  // extern "C" (a template follows)
+
+// One thing the builds wrote for the context's current scene, over the range the build defines (not allocation slack): its pieces in
+// order, each a range of device memory (dev; a null pointer counts as empty) or bytes the host holds (dev = nullptr, host).
+struct BuildSpan {
+    std::string name;
+    struct Piece {
+        const void* dev;
+        size_t bytes;
+        std::vector<unsigned char> host;
+    };
+    std::vector<Piece> pieces;
+    template <class T>
+    BuildSpan& device(const T* p, size_t count)
+    {
+        pieces.push_back({p, p ? count * sizeof(T) : 0, {}});
+        return *this;
+    }
+    BuildSpan& host(const void* p, size_t bytes)
+    {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        pieces.push_back({nullptr, bytes, std::vector<unsigned char>(b, b + bytes)});
+        return *this;
+    }
+    size_t bytes() const
+    {
+        size_t n = 0;
+        for (const Piece& q : pieces) n += q.bytes;
+        return n;
+    }
+};
+
+// The ordered list of spans of rtgo_debug_build_digest and rtgo_debug_read_build.
+//   analytic (whitted = 0): nodes, prims, frames, tight, aabb; then for tree[0] and tree[1]: fnodes (2 * n_fnodes float4), fprims, the
+//     decoded meta fields {canonical depth, fast_depth, n_small, n_fnodes, n_big_pairs, list_cub, cuboid_groups, tree_spheres, bounds[6],
+//     cub_a, cub_b}.  A scene of rtgo_set_large_scene has the first five only (frames and tight boxes empty).  Then, in the clear:
+//     scene.info {n_prims, large, have_alt, has a grid}, tree0.meta / tree1.meta (BuildMeta's words), grid.params (GridParams, then
+//     {bytes, list entries}), grid.image.
+//   whitted (whitted = 1), one mesh: recs (4 * n_recs float4), qrecs (2 * n_recs), tris, tidx, grid {grid_lo, grid_step}, counts {n_recs,
+//     walk_depth}; then meta (WhittedBuildMeta's words, then {triangles, vertices}).
+//     An instanced scene: per mesh recs, qrecs (each over the ranges its builds wrote, in build order), tris, tidx, {root, depth, n_recs
+//     of each build}; then the top level's recs and inst, then clusters.  Then, in the clear: per mesh its info {rec_base, tri_base,
+//     vert_base, root, depth, clustered, n_tris, builds, then per build rec0, n_recs, tri0 and WhittedBuildMeta's words}, and top.meta
+//     (WhittedBuildMeta's words of the top level, then {n_recs, n_instances, the scene's walk_depth, mesh_depth}).
+static int build_spans(rtgo_ctx* c, int whitted, std::vector<BuildSpan>& out)
 {
-    if (!c || !out || !n_out) return fail(c, RTGO_E_INVALID, "rtgo_debug_build_digest: NULL argument");
-    if (const int rc = rtgo_sync(c)) return rc;
-    std::vector<uint64_t> d;
-    const uint64_t kBasis = 0xCBF29CE484222325ull;
-    int rc = RTGO_OK;
-    auto whole = [&](auto* p, size_t count) {
-        uint64_t h = kBasis;
-        if (rc == RTGO_OK) rc = digest_device(c, p, count * sizeof(*p), h);
-        d.push_back(h);
+    auto span = [&](const std::string& name) -> BuildSpan& {
+        out.push_back(BuildSpan{name, {}});
+        return out.back();
     };
     if (!whitted) {
         const AnalyticScene& sc = c->scene;
         const size_t n = sc.n_prims;
         if (n == 0) return fail(c, RTGO_E_STATE, "rtgo_debug_build_digest: no scene");
-        whole(sc.d_nodes.get(), (2 * n - 1) * 2);
-        whole(sc.d_prims.get(), n * 6);
-        whole(sc.d_frames.get(), sc.large ? 0 : n * 2);
-        whole(sc.d_tight.get(), sc.large ? 0 : n * 6);
-        whole(sc.d_aabb.get(), n * 6);
+        span("nodes").device(sc.d_nodes.get(), (2 * n - 1) * 2);
+        span("prims").device(sc.d_prims.get(), n * 6);
+        span("frames").device(sc.d_frames.get(), sc.large ? 0 : n * 2);
+        span("tight").device(sc.d_tight.get(), sc.large ? 0 : n * 6);
+        span("aabb").device(sc.d_aabb.get(), n * 6);
         for (int k = 0; k < 2 && !sc.large; ++k) {
             const AnalyticScene::FastTree& t = sc.tree[k];
             const bool have = t.d_fprims.get() != nullptr;
-            whole(t.d_fnodes.get(), have ? (size_t)2 * t.n_fnodes : 0);
-            whole(t.d_fprims.get(), have ? n * 4 : 0);
-            uint64_t h = kBasis;
+            const std::string pre = "tree" + std::to_string(k) + ".";
+            span(pre + "fnodes").device(t.d_fnodes.get(), have ? (size_t)2 * t.n_fnodes : 0);
+            span(pre + "fprims").device(t.d_fprims.get(), have ? n * 4 : 0);
             const int ints[] = {sc.lbvh_depth, t.fast_depth, t.n_small, t.n_fnodes, t.n_big_pairs, t.list_cub, t.cuboid_groups, t.tree_spheres};
             const float floats[] = {t.cub_a, t.cub_b};
-            digest_host(ints, sizeof ints, h);
-            digest_host(sc.bounds, sizeof sc.bounds, h);
-            digest_host(floats, sizeof floats, h);
-            d.push_back(h);
+            span(pre + "decoded").host(ints, sizeof ints).host(sc.bounds, sizeof sc.bounds).host(floats, sizeof floats);
         }
+        const int info[] = {(int)n, sc.large ? 1 : 0, sc.have_alt ? 1 : 0, sc.grid.have ? 1 : 0};
+        span("scene.info").host(info, sizeof info);
+        for (int k = 0; k < 2 && !sc.large; ++k) {
+            const AnalyticScene::FastTree& t = sc.tree[k];
+            span("tree" + std::to_string(k) + ".meta").host(&t.meta, t.d_fprims.get() ? sizeof t.meta : 0);
+        }
+        const AnalyticScene::Grid& g = sc.grid;
+        const int gi[] = {g.have ? g.n_nodes * 32 : 0, g.have ? g.entries : 0};
+        span("grid.params").host(&g.gp, sizeof g.gp).host(gi, sizeof gi);
+        span("grid.image").device(g.have ? g.d.get() : nullptr, (size_t)g.n_nodes * 32);
     } else {
         const WhittedMesh& wm = c->wm;
         if (wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_debug_build_digest: no mesh");
         if (!wm.instanced) {
-            whole(wm.recs.get(), (size_t)4 * wm.n_recs);
-            whole(wm.qrecs.get(), (size_t)2 * wm.n_recs);
-            whole(wm.tris.get(), (size_t)3 * wm.triangles);
-            whole(wm.tidx.get(), (size_t)wm.triangles);
-            uint64_t h = kBasis;
-            digest_host(&wm.grid_lo, sizeof wm.grid_lo, h);
-            digest_host(&wm.grid_step, sizeof wm.grid_step, h);
-            d.push_back(h);
-            h = kBasis;
+            span("recs").device(wm.recs.get(), (size_t)4 * wm.n_recs);
+            span("qrecs").device(wm.qrecs.get(), (size_t)2 * wm.n_recs);
+            span("tris").device(wm.tris.get(), (size_t)3 * wm.triangles);
+            span("tidx").device(wm.tidx.get(), (size_t)wm.triangles);
+            span("grid").host(&wm.grid_lo, sizeof wm.grid_lo).host(&wm.grid_step, sizeof wm.grid_step);
             const int ints[] = {wm.n_recs, wm.walk_depth};
-            digest_host(ints, sizeof ints, h);
-            d.push_back(h);
+            span("counts").host(ints, sizeof ints);
+            const int sizes[] = {wm.triangles, wm.n_vertices};
+            span("meta").host(&wm.meta, sizeof wm.meta).host(sizes, sizeof sizes);
         } else {
-            for (const WhittedMeshInfo& mi : wm.meshes) {
-                uint64_t hr = kBasis, hq = kBasis, hm = kBasis;
-                digest_host(&mi.root, sizeof mi.root, hm);
-                digest_host(&mi.depth, sizeof mi.depth, hm);
+            for (size_t k = 0; k < wm.meshes.size(); ++k) {
+                const WhittedMeshInfo& mi = wm.meshes[k];
+                const std::string pre = "mesh" + std::to_string(k) + ".";
+                BuildSpan recs{pre + "recs", {}}, qrecs{pre + "qrecs", {}}, counts{pre + "counts", {}};
+                counts.host(&mi.root, sizeof mi.root).host(&mi.depth, sizeof mi.depth);
                 for (const WhittedMeshInfo::Built& b : mi.built) {
-                    if (rc == RTGO_OK) rc = digest_device(c, wm.recs.get() + 4 * (size_t)b.rec0, (size_t)4 * b.n_recs * sizeof(float4), hr);
-                    if (rc == RTGO_OK && b.tri0 >= 0) rc = digest_device(c, wm.qrecs.get() + 2 * (size_t)b.tri0, (size_t)2 * b.n_recs * sizeof(uint4), hq);
-                    digest_host(&b.n_recs, sizeof b.n_recs, hm);
+                    recs.device(wm.recs.get() + 4 * (size_t)b.rec0, (size_t)4 * b.n_recs);
+                    if (b.tri0 >= 0) qrecs.device(wm.qrecs.get() + 2 * (size_t)b.tri0, (size_t)2 * b.n_recs);
+                    counts.host(&b.n_recs, sizeof b.n_recs);
                 }
-                d.push_back(hr);
-                d.push_back(hq);
-                whole(wm.tris.get() + 3 * (size_t)mi.tri_base, (size_t)3 * mi.n_tris);
-                whole(wm.tidx.get() + mi.tri_base, (size_t)mi.n_tris);
-                d.push_back(hm);
+                out.push_back(recs);
+                out.push_back(qrecs);
+                span(pre + "tris").device(wm.tris.get() + 3 * (size_t)mi.tri_base, (size_t)3 * mi.n_tris);
+                span(pre + "tidx").device(wm.tidx.get() + mi.tri_base, (size_t)mi.n_tris);
+                out.push_back(counts);
             }
-            whole(wm.top.recs.get(), (size_t)4 * wm.top.n_recs);
-            whole(wm.top.inst.get(), (size_t)wm.top.n_instances);
-            whole(wm.clusters.get(), wm.clusters.size());
+            span("top.recs").device(wm.top.recs.get(), (size_t)4 * wm.top.n_recs);
+            span("top.inst").device(wm.top.inst.get(), (size_t)wm.top.n_instances);
+            span("clusters").device(wm.clusters.get(), wm.clusters.size());
+            for (size_t k = 0; k < wm.meshes.size(); ++k) {
+                const WhittedMeshInfo& mi = wm.meshes[k];
+                const int head[] = {mi.rec_base, mi.tri_base, mi.vert_base, mi.root, mi.depth, mi.clustered ? 1 : 0, mi.n_tris, (int)mi.built.size()};
+                BuildSpan& s = span("mesh" + std::to_string(k) + ".info").host(head, sizeof head);
+                for (const WhittedMeshInfo::Built& b : mi.built) {
+                    const int w[] = {b.rec0, b.n_recs, b.tri0};
+                    s.host(w, sizeof w).host(&b.meta, sizeof b.meta);
+                }
+            }
+            const int top[] = {wm.top.n_recs, wm.top.n_instances, wm.walk_depth, wm.mesh_depth};
+            span("top.meta").host(&wm.top.meta, sizeof wm.top.meta).host(top, sizeof top);
         }
     }
-    if (rc) return rc;
+    return RTGO_OK;
+}
+
+extern "C" {
+
+// diagnostic (tools/build_digest.py; not part of include/rtgo.h): one FNV-1a digest per span of build_spans; *n_out = how many (at most
+// `cap` are stored)
+extern "C" int rtgo_debug_build_digest(rtgo_ctx* c, int whitted, uint64_t* out, uint32_t cap, uint32_t* n_out)
+{
+    if (!c || !out || !n_out) return fail(c, RTGO_E_INVALID, "rtgo_debug_build_digest: NULL argument");
+    if (const int rc = rtgo_sync(c)) return rc;
+    std::vector<BuildSpan> spans;
+    if (const int rc = build_spans(c, whitted, spans)) return rc;
+    std::vector<uint64_t> d;
+    for (const BuildSpan& s : spans) {
+        uint64_t h = 0xCBF29CE484222325ull;
+        for (const BuildSpan::Piece& q : s.pieces) {
+            if (q.dev) {
+                if (const int rc = digest_device(c, q.dev, q.bytes, h)) return rc;
+            } else {
+                digest_host(q.host.data(), q.host.size(), h);
+            }
+        }
+        d.push_back(h);
+    }
     *n_out = (uint32_t)d.size();
     for (size_t k = 0; k < d.size() && k < cap; ++k) out[k] = d[k];
     return RTGO_OK;
+}
+
+// diagnostic (tests/accel_check.py, tools/build_digest.py; not part of include/rtgo.h): span `index` of build_spans read back.  *bytes_out
+// = its size; its bytes are copied to `host` when they fit cap_bytes (host may be NULL to ask for the size), its name to `name` (up to
+// name_cap bytes with the terminator; may be NULL).  An index beyond the list: RTGO_E_INVALID with *bytes_out = 0, which ends an enumeration.
+extern "C" int rtgo_debug_read_build_named(rtgo_ctx* c, int whitted, uint32_t index, void* host, size_t cap_bytes, size_t* bytes_out, char* name,
+                                           size_t name_cap)
+{
+    if (!c || !bytes_out) return fail(c, RTGO_E_INVALID, "rtgo_debug_read_build: NULL argument");
+    *bytes_out = 0;
+    if (const int rc = rtgo_sync(c)) return rc;
+    std::vector<BuildSpan> spans;
+    if (const int rc = build_spans(c, whitted, spans)) return rc;
+    if (index >= spans.size()) return fail(c, RTGO_E_INVALID, "rtgo_debug_read_build: no span " + std::to_string(index));
+    const BuildSpan& s = spans[index];
+    *bytes_out = s.bytes();
+    if (name && name_cap > 0) {
+        std::strncpy(name, s.name.c_str(), name_cap - 1);
+        name[name_cap - 1] = 0;
+    }
+    if (!host || cap_bytes < s.bytes()) return RTGO_OK;
+    unsigned char* at = static_cast<unsigned char*>(host);
+    for (const BuildSpan::Piece& q : s.pieces) {
+        if (q.dev && q.bytes) RTGO_HIP(c, hipMemcpy(at, q.dev, q.bytes, hipMemcpyDeviceToHost));
+        else if (!q.host.empty()) std::memcpy(at, q.host.data(), q.host.size());
+        at += q.bytes;
+    }
+    return RTGO_OK;
+}
+extern "C" int rtgo_debug_read_build(rtgo_ctx* c, int whitted, uint32_t index, void* host, size_t cap_bytes, size_t* bytes_out)
+{
+    return rtgo_debug_read_build_named(c, whitted, index, host, cap_bytes, bytes_out, nullptr, 0);
 }
 
 #ifdef RTGO_CMPWALK
@@ -882,6 +987,7 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
     RTGO_HIP(c, hipGetLastError());
     RTGO_HIP(c, hipMemcpyAsync(&meta, c->d_meta.get(), sizeof meta, hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    t.meta = meta;
     t.fast_depth = meta.walk_depth;
     t.n_small = meta.n_small;
     t.n_big_pairs = group_pairs(meta.list_group);
@@ -1901,6 +2007,7 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
                                  wm.qrecs.get(), wm.tidx.get(), m, "rtgo_whitted_set_mesh");
     if (rc) return rc;
     wm.n_recs = m.n_recs;
+    wm.meta = m;
     wm.n_vertices = (int)n_vertices;
     wm.grid_lo = m.grid_lo;
     wm.grid_step = m.grid_step;
@@ -2043,6 +2150,7 @@ static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>&
     RTGO_HIP(c, top.shade.upload(shade.data(), shade.size(), c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     top.n_recs = m.n_recs;
+    top.meta = m;
     top.n_instances = n;
     c->wm.top = std::move(top);
     c->wm.walk_depth = depth < 1 ? 1 : depth;
@@ -2100,7 +2208,7 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
                                      wm.tris.get() + 3 * ((size_t)mi.tri_base + s), wm.qrecs.get() + 2 * ((size_t)mi.tri_base + s), wm.tidx.get() + mi.tri_base + s, m,
                                      what);
         if (rc) return rc;
-        mi.built.push_back({rec, m.n_recs, mi.tri_base + s});
+        mi.built.push_back({rec, m.n_recs, mi.tri_base + s, m});
         crec[k] = rec;
         croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
         cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
@@ -2119,7 +2227,7 @@ static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, Whit
     const int rc = whitted_build(c, bs.mid_pos.get(), bs.mid_idx.get(), ncl, wm.nodes.get(), wm.scratch.get(), wm.recs.get() + 4 * (size_t)mi.rec_base,
                                  bs.mid_tris.get(), bs.mid_qrecs.get(), bs.mid_tidx.get(), m, what);
     if (rc) return rc;
-    mi.built.push_back({mi.rec_base, m.n_recs, -1});
+    mi.built.push_back({mi.rec_base, m.n_recs, -1, m});
     // leaf order: the mid level's Morton-ordered "triangles" carry the cluster in .w of their first corner
     std::vector<float4> order((size_t)3 * ncl), root_rec(4);
     std::vector<float> boxes((size_t)6 * ncl);
@@ -2278,7 +2386,7 @@ int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_
             c->wm = WhittedMesh();
             return rc;
         }
-        mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base});
+        mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base, m});
         mi.root = m.n_recs > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
         mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
         mesh_depth = std::max(mesh_depth, mi.depth);
