@@ -116,7 +116,8 @@ typedef struct rtgo_stats {
                                  (loop, structure) pairs -- same pixels either way -- and the fastest keeps the job), bit 4 the fast walk
                                  over the uniform grid instead of a tree, bit 5 the scene walked from global memory (a scene of
                                  rtgo_set_large_scene; always with bit 2), bit 6 path mode under the last-ray certificate (a path's last
-                                 ray tests the emitters and skips the room) */
+                                 ray tests the emitters and skips the room), bit 7 the last call rendered more than one
+                                 frame in one kernel launch (rtgo_launch_frames' batched kernels) */
     uint32_t launches_trial;  /* launches since rtgo_reset_stats that were trial launches */
 } rtgo_stats;
 
@@ -172,6 +173,23 @@ int rtgo_bind_output(rtgo_ctx* ctx, void* d_accum, void* d_image, size_t pixels)
    the launch-time trial of a job (same frame geometry, spp and mode) has all its timed launches in flight, the next launch of that
    job waits for them to finish, once, to pick the fastest candidate. */
 int rtgo_launch(rtgo_ctx* ctx, const rtgo_frame* frame);
+
+/* n_frames consecutive progressive frames of the frame's window / band share: frame->frame_count, +1, ..., +n_frames-1, over the
+   scene, camera, lights and output the context holds now (a frame loop that presents every k-th frame only: no reference counterpart,
+   renderer.cpp launches once per frame).  Accumulation buffer and image afterwards are, bit for bit, what n_frames calls of rtgo_launch
+   with those frame_counts in turn leave.  Asynchronous on the context's stream.
+   Every check of rtgo_launch applies, with its codes; n_frames == 0, or frame_count + n_frames passing 2^32: RTGO_E_INVALID, nothing is
+   enqueued.  n_frames == 1 is rtgo_launch(ctx, frame).  A rank that owns no row of the window enqueues nothing and returns RTGO_OK.
+   Lock-step launches (at most 16 spp) that take the fast walk over a tree render all their frames in ONE kernel launch: a pixel's
+   frame f + 1 needs its frame f alone, so the wave that holds a strip of pixels renders the strip's frames back to back, keeps the
+   running averages in registers and writes both outputs once.  Every other launch rtgo_launch accepts (more than 16 spp, the uniform
+   grid, beyond the far-field guard, collect_stats, a scene of rtgo_set_large_scene) is n_frames launches enqueued back to back.
+   A call with n_frames > 1 takes no part in the launch-time trial and never blocks: it times nothing and leaves the trial as it is.
+   When the trial of this very job (rtgo_launch's key) has settled it uses that choice, otherwise the first candidate; pixels do not
+   depend on the choice.  (A caller that must never block can therefore render single frames through rtgo_launch_frames' fallback
+   only by asking for two at a time; n_frames == 1 is rtgo_launch, trial included.)
+   rtgo_stats: the ray counts grow by the sum over the frames, launches by the kernel launches made (1, or n_frames). */
+int rtgo_launch_frames(rtgo_ctx* ctx, const rtgo_frame* frame, uint32_t n_frames);
 
 /* cudaStreamSynchronize + CUDA_SYNC_CHECK (CUDAOutputBuffer.h:247-250, renderer.cpp:773) */
 int rtgo_sync(rtgo_ctx* ctx);

@@ -39,6 +39,11 @@ int rtgo_host_material(const char* name, float* out10);
 int rtgo_host_render(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient,
                      int frames, int device, void* host_image, void* host_accum, rtgo_stats* stats);
 
+/* rtgo_host_render with Renderer::SetFramesPerLaunch(frames_per_launch): the frames go k to a call of rtgo_launch_frames (the last call
+   takes what is left).  Same image and accumulation buffer bit for bit; frames_per_launch = 1 is rtgo_host_render. */
+int rtgo_host_render_batched(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient,
+                             int frames, int frames_per_launch, int device, void* host_image, void* host_accum, rtgo_stats* stats);
+
 /* A scripted interactive session with engine::host::Renderer: what the GLFW callbacks + frame loop of the reference do
    (renderer.cpp:36-145, 679-747, 841-862), without a window.  All return 0 or an RTGO_E_* code. */
 /* Headless engine::host::MultiGpuRenderer run (raytracingo_amd/host/multigpu.h): the frame tiled in 4-row bands over
@@ -49,6 +54,13 @@ int rtgo_host_render(const char* scene_name, const char* mode, uint32_t width, u
 int rtgo_host_render_multi(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
                            const int* devices, int n_devices, int launches_per_device, int present_every, int rccl_for_local_shares,
                            void* host_image, void* host_accum, rtgo_stats* stats, double* ms_per_frame);
+
+/* rtgo_host_render_multi with MultiGpuRenderer::Options::framesPerLaunch: every share renders min(frames_per_launch, frames up to the
+   next presented one, frames left) frames per call of rtgo_launch_frames -- with present_every = frames_per_launch = k, one launch and one
+   gather per presented frame.  Same assembled frame bit for bit; frames_per_launch = 1 is rtgo_host_render_multi. */
+int rtgo_host_render_multi_batched(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
+                                   const int* devices, int n_devices, int launches_per_device, int present_every, int rccl_for_local_shares,
+                                   void* host_image, void* host_accum, rtgo_stats* stats, double* ms_per_frame, int frames_per_launch);
 
 typedef struct rtgo_host_session rtgo_host_session;
 int rtgo_host_session_open(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient,

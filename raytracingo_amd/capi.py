@@ -25,7 +25,7 @@ SYMBOLS = [
     "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands", "rtgo_set_large_scene",
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
-    "rtgo_whitted_launch_frame",
+    "rtgo_whitted_launch_frame", "rtgo_launch_frames",
 ]
 RTGO_WHITTED_MAX_MESHES = 256
 RTGO_WHITTED_MAX_INSTANCES = 8192
@@ -126,6 +126,7 @@ def load():
     L.rtgo_resize.argtypes = [vp, C.c_size_t]
     L.rtgo_bind_output.argtypes = [vp, vp, vp, C.c_size_t]
     L.rtgo_launch.argtypes = [vp, C.POINTER(Frame)]
+    L.rtgo_launch_frames.argtypes = [vp, C.POINTER(Frame), C.c_uint32]
     L.rtgo_sync.argtypes = [vp]
     L.rtgo_read_image.argtypes = [vp, vp, C.c_size_t]
     L.rtgo_read_accum.argtypes = [vp, vp, C.c_size_t]
@@ -266,6 +267,10 @@ class Context:
 
     def launch(self, frame):
         self._check(self._lib.rtgo_launch(self._h, C.byref(frame)), "rtgo_launch")
+
+    def launch_frames(self, frame, n_frames):
+        """n_frames progressive frames from frame.frame_count on (rtgo_launch_frames: one kernel launch where the batched kernels apply)"""
+        self._check(self._lib.rtgo_launch_frames(self._h, C.byref(frame), int(n_frames)), "rtgo_launch_frames")
 
     def sync(self):
         self._check(self._lib.rtgo_sync(self._h), "rtgo_sync")

@@ -246,11 +246,13 @@ struct RenderKernelEntry {
     RenderKernel fn;
     bool grid = false;
     bool global = false;   // the canonical walk over a scene in global memory (rtgo_set_large_scene)
+    bool batch = false;    // render_frames_kernel: the frames of rtgo_launch_frames in one launch
 };
 #define RTGO_K(P, S, W, T) {P, S, T, W, S, false, render_kernel<P, S, W, T>}
 #define RTGO_KF(W, T) {true, false, T, W, false, true, render_kernel<true, false, W, T, false, true>}
 #define RTGO_KG(P, W, T) {P, false, T, W, false, false, render_kernel<P, false, W, T, false, false, true>, true}
 #define RTGO_KL(P, C) {P, true, false, 4, C, false, render_kernel<P, true, 4, false, C, false, false, true>, false, true}
+#define RTGO_KB(P, W, F) {P, false, false, W, false, F, render_frames_kernel<P, W, F>, false, false, true}
 static const RenderKernelEntry kRenderKernels[] = {
     RTGO_K(true, false, 4, false),  RTGO_K(true, false, 5, false),    // path mode, fast walk
     RTGO_K(false, false, 4, false), RTGO_K(false, false, 5, false),   // distributed mode, fast walk
@@ -264,16 +266,19 @@ static const RenderKernelEntry kRenderKernels[] = {
     RTGO_KG(true, 4, false), RTGO_KG(true, 5, false), RTGO_KG(true, 4, true), RTGO_KG(true, 5, true),       // fast walk over the uniform grid instead of the tree (fast_grid)
     RTGO_KG(false, 4, false), RTGO_KG(false, 5, false), RTGO_KG(false, 4, true), RTGO_KG(false, 5, true),
     RTGO_KL(true, false), RTGO_KL(false, false), RTGO_KL(true, true), RTGO_KL(false, true),   // scenes of rtgo_set_large_scene: timed, collect_stats
+    RTGO_KB(true, 4, false), RTGO_KB(true, 5, false), RTGO_KB(true, 4, true), RTGO_KB(true, 5, true),   // several frames per launch (rtgo_launch_frames): lock-step, over a tree
+    RTGO_KB(false, 4, false), RTGO_KB(false, 5, false),
 };
 #undef RTGO_K
 #undef RTGO_KF
 #undef RTGO_KG
 #undef RTGO_KL
-static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, bool count, bool frames, bool grid, bool global = false)
+#undef RTGO_KB
+static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, bool count, bool frames, bool grid, bool global = false, bool batch = false)
 {
     for (const RenderKernelEntry& e : kRenderKernels)
         if (e.path == path && e.canon == canon && e.wpe == (canon ? 4 : wpe) && e.stream == (canon ? false : stream) && e.count == (canon && count) &&
-            e.frames == (frames && path && !canon) && e.grid == (grid && !canon) && e.global == (global && canon))
+            e.frames == (frames && path && !canon) && e.grid == (grid && !canon) && e.global == (global && canon) && e.batch == batch)
             return e.fn;
     return nullptr;
 }
@@ -1437,7 +1442,9 @@ struct Pick {
 // (render_kernel, STREAM) lets a lane start its next sample when its path has ended instead of waiting for the wave's longest path,
 // pass after pass; and where rtgo_set_scene's two builds differ, either structure can be the faster one.  Candidate k = loop (k & 1:
 // 0 = streaming when there is a choice) | structure (k >> 1 when both loops are candidates, else k).
-static int choose_candidate(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, const Knobs& kn, bool canon, Pick& pk)
+// in_trial = false (rtgo_launch_frames): the launch takes no part in the trial -- the settled choice of this very job when there is one,
+// else the first candidate; nothing is timed, waited for or recorded.
+static int choose_candidate(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, const Knobs& kn, bool canon, Pick& pk, bool in_trial = true)
 {
     if (canon) {
 #ifdef RTGO_CMPWALK
@@ -1479,6 +1486,10 @@ static int choose_candidate(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams
     std::vector<uint32_t> key = {p.W, p.H, p.x0, p.y0, p.w, p.h, p.band_h, p.n_ranks, p.rank, nn, (uint32_t)path, (uint32_t)f->max_trace_depth,
                                  (uint32_t)(f->use_ambient != 0), (uint32_t)n_cand, (uint32_t)pk.stream, (uint32_t)pk.structure, (uint32_t)grid_ok};
     const bool fresh = key != t.key;
+    if (!in_trial) {
+        decode(!fresh && t.choice >= 0 ? t.choice : 0);
+        return RTGO_OK;
+    }
     const int issued = fresh ? 0 : t.issued;
     int choice = fresh ? -1 : t.choice;
     pk.n_cand = n_cand;
@@ -1708,7 +1719,7 @@ struct Block {
 // puts the most waves on a CU (4, 5 or 6 per SIMD, what the variant's VGPR budget admits), smallest size on ties.  Without a scene copy
 // the stack alone sets the count, and workgroups of one or two waves fit the most of them.
 static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, bool canon, bool stream, bool frames, bool grid,
-                      uint64_t units_hot, const Knobs& kn, Block& b, bool global = false)
+                      uint64_t units_hot, const Knobs& kn, Block& b, bool global = false, bool batch = false)
 {
     const bool path = f->path_tracing != 0;
     const int fast_nodes = p.n_fnodes;   // (the tree's nodes, or the grid in their place)
@@ -1724,13 +1735,13 @@ static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, u
     // HBM per launch, profiles/r02d) and was dropped; today's fits because the per-lane values derived from the lane index are
     // derived where they are used (opaque_lane in rtgo_device.h) instead of being held through every ray loop.
     const uint64_t units_per_wave4 = units_hot * (passes_of(nn)) / ((uint64_t)c->num_cus * 16u);
-    const int top_wpe = find_kernel(path, canon, 6, stream, false, frames, grid, global) ? 6 : 5;   // the 6-waves variant exists for some combinations only
+    const int top_wpe = find_kernel(path, canon, 6, stream, false, frames, grid, global, batch) ? 6 : 5;   // the 6-waves variant exists for some combinations only
     const int max_wpe_work = units_per_wave4 >= kUnitsPerWave4For6 ? 6 : (units_per_wave4 >= 3 ? 5 : 4);
     int max_wpe = canon ? 4 : (kn.max_wpe ? (int)kn.max_wpe : max_wpe_work);   // (RTGO_MAX_WPE: experiment knob, clamped to what exists)
     max_wpe = max_wpe < 4 ? 4 : (max_wpe > top_wpe ? top_wpe : max_wpe);
     for (int w = 4; w <= max_wpe; ++w)
         for (int bs = global ? 64 : 256; bs <= kMaxBlock; bs *= 2) {
-            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + (w >= 5 ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0) + (w >= 6 ? (size_t)(kCamWordsLean - kCamWords) * sizeof(float) : 0);
+            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + ((w >= 5 || (batch && !path)) ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0) + ((batch && !path && w >= 5) ? (size_t)bs * 9 * sizeof(float) : 0) /* render_frames_kernel, distributed: level records at 4 waves too, the shadow ray's state at 5 */ + ((w >= 6 || (batch && !path && w >= 5)) ? (size_t)(kCamWordsLean - kCamWords) * sizeof(float) : 0);
             int per_cu = (int)((160 * 1024) / l);
             if (per_cu * (bs / 64) > 4 * w) per_cu = (4 * w) / (bs / 64);
             const int waves = per_cu * (bs / 64);
@@ -1821,11 +1832,19 @@ static int launch_large(rtgo_ctx* c, const rtgo_frame* f, LaunchParams& p, const
     return RTGO_OK;
 }
 
-int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
+// One kernel launch: frame f->frame_count (n_frames = 1), or n_frames frames from it on in the batched kernels.  in_trial: see
+// choose_candidate.  A launch of several frames that the batched kernels do not cover enqueues nothing and says so in *unbatched.
+static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, bool in_trial, bool* unbatched)
 {
     const Knobs kn;
     LaunchParams p;
     if (const int rc = frame_params(c, f, p)) return rc;
+    const bool batch = n_frames > 1;
+    p.n_frames = n_frames;
+    if (batch && (c->scene.large || f->collect_stats != 0 || passes_of((uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp) > 1)) {
+        *unbatched = true;
+        return RTGO_OK;
+    }
     if (c->scene.large) return launch_large(c, f, p, kn);
     const uint32_t nn = (uint32_t)f->sqrt_spp * (uint32_t)f->sqrt_spp;
     const bool path = f->path_tracing != 0, stats = f->collect_stats != 0;
@@ -1835,8 +1854,12 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     const Rect r = cull ? box_screen_rect(c->scene.bounds, p) : Rect{0, p.w, 0, p.h};
     const bool canon = far_field_guard(c, p, kn) || stats;
     Pick pk;
-    if (const int rc = choose_candidate(c, f, p, nn, kn, canon, pk)) return rc;
+    if (const int rc = choose_candidate(c, f, p, nn, kn, canon, pk, in_trial)) return rc;
     const bool use_alt = pk.structure == 1, use_grid = pk.structure == 2;
+    if (batch && (canon || use_grid)) {
+        *unbatched = true;
+        return RTGO_OK;
+    }
     walk_params(c, c->scene.tree[use_alt ? 1 : 0], canon, use_grid, p);
     last_ray_params(c, c->scene.tree[use_alt ? 1 : 0], path, canon, use_grid, kn, p);
     uint32_t strip_px = 0;
@@ -1848,23 +1871,45 @@ int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f)
     if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
     const bool frames = path && !canon && c->scene.quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
     Block b;
-    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b)) return rc;
+    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b, false, batch)) return rc;
     if (kn.debug)
-        std::fprintf(stderr, "rtgo_launch: %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g\n",
-                     canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric);
-    const RenderKernel kernel = find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid);
+        std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g\n",
+                     n_frames, canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric);
+    const RenderKernel kernel = find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch);
     if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
     const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels;
     std::vector<uint32_t> seeds_key;
-    if (const int rc = plan_seeds(c, p, strip_px, kernel_has_seed_pass(canon, b.wpe, pk.stream), seeds_key)) return rc;
+    // (the batched kernels have no seed pass: they neither read pre-hashed seeds nor leave any, and the next launch hashes inline)
+    if (const int rc = plan_seeds(c, p, strip_px, !batch && kernel_has_seed_pass(canon, b.wpe, pk.stream), seeds_key)) return rc;
     c->seeds.ok = false;   // (until this launch is on the stream)
-    if (const int rc = enqueue(c, kernel, p, b, pk, canon, culled * nn)) return rc;
+    if (const int rc = enqueue(c, kernel, p, b, pk, canon, culled * nn * n_frames)) return rc;
+    if (batch) c->last_variant |= 128u;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
         c->seeds.read = 1 - c->seeds.read;
         c->seeds.frame = p.frame + 1u;
         c->seeds.key = std::move(seeds_key);
         c->seeds.ok = true;
+    }
+    return RTGO_OK;
+}
+
+int rtgo_launch(rtgo_ctx* c, const rtgo_frame* f) { return launch_frame(c, f, 1, true, nullptr); }
+
+int rtgo_launch_frames(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames)
+{
+    if (!c || !f) return fail(c, RTGO_E_INVALID, "rtgo_launch_frames: NULL argument");
+    if (n_frames == 0 || (uint64_t)f->frame_count + n_frames > (1ull << 32))
+        return fail(c, RTGO_E_INVALID, "rtgo_launch_frames: n_frames must be positive and frame_count + n_frames must not pass 2^32");
+    if (n_frames == 1) return rtgo_launch(c, f);
+    bool unbatched = false;
+    if (const int rc = launch_frame(c, f, n_frames, false, &unbatched)) return rc;
+    if (!unbatched) return RTGO_OK;
+    // what the batched kernels do not cover (more than 16 spp, the grid, the canonical walk, large scenes): a launch per frame
+    rtgo_frame g = *f;
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        g.frame_count = f->frame_count + k;
+        if (const int rc = launch_frame(c, &g, 1, false, nullptr)) return rc;
     }
     return RTGO_OK;
 }

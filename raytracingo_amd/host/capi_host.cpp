@@ -106,11 +106,11 @@ int rtgo_host_scene_build(const char* scene_name, uint32_t width, uint32_t heigh
     return RTGO_OK;
 }
 
-int rtgo_host_render(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
-                     int device, void* host_image, void* host_accum, rtgo_stats* stats)
+int rtgo_host_render_batched(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
+                             int frames_per_launch, int device, void* host_image, void* host_accum, rtgo_stats* stats)
 {
     SceneModel model;
-    if (!scene_name || !mode || !scene_from_name(scene_name, model) || width == 0 || height == 0 || sample < 1 || frames < 1) {
+    if (!scene_name || !mode || !scene_from_name(scene_name, model) || width == 0 || height == 0 || sample < 1 || frames < 1 || frames_per_launch < 1) {
         g_error = "rtgo_host_render: bad argument";
         return RTGO_E_INVALID;
     }
@@ -126,6 +126,7 @@ int rtgo_host_render(const char* scene_name, const char* mode, uint32_t width, u
         Renderer renderer(scene, rm, sample, ambient != 0);
         renderer.SetDevice(device);
         renderer.SetFrames(frames);
+        renderer.SetFramesPerLaunch(frames_per_launch);
         renderer.Display();
         if (host_image) {
             const std::vector<unsigned char> img = renderer.ReadImage();
@@ -143,12 +144,18 @@ int rtgo_host_render(const char* scene_name, const char* mode, uint32_t width, u
     return RTGO_OK;
 }
 
-int rtgo_host_render_multi(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
-                           const int* devices, int n_devices, int launches_per_device, int present_every, int rccl_for_local_shares,
-                           void* host_image, void* host_accum, rtgo_stats* stats, double* ms_per_frame)
+int rtgo_host_render(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
+                     int device, void* host_image, void* host_accum, rtgo_stats* stats)
+{
+    return rtgo_host_render_batched(scene_name, mode, width, height, sample, ambient, frames, 1, device, host_image, host_accum, stats);
+}
+
+int rtgo_host_render_multi_batched(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
+                                   const int* devices, int n_devices, int launches_per_device, int present_every, int rccl_for_local_shares,
+                                   void* host_image, void* host_accum, rtgo_stats* stats, double* ms_per_frame, int frames_per_launch)
 {
     SceneModel model;
-    if (!scene_name || !mode || !scene_from_name(scene_name, model) || width == 0 || height == 0 || sample < 1 || frames < 1 || !devices || n_devices < 1) {
+    if (!scene_name || !mode || !scene_from_name(scene_name, model) || width == 0 || height == 0 || sample < 1 || frames < 1 || !devices || n_devices < 1 || frames_per_launch < 1) {
         g_error = "rtgo_host_render_multi: bad argument";
         return RTGO_E_INVALID;
     }
@@ -164,6 +171,7 @@ int rtgo_host_render_multi(const char* scene_name, const char* mode, uint32_t wi
         opt.launchesPerDevice = launches_per_device > 0 ? launches_per_device : 1;
         opt.presentEvery = present_every > 0 ? present_every : 1;
         opt.rcclForLocalShares = rccl_for_local_shares != 0;
+        opt.framesPerLaunch = frames_per_launch;
         MultiGpuRenderer renderer(scene, m == "path" ? RenderMode::PATH_TRACING : RenderMode::DISTRIBUTED_RAY_TRACING, sample, ambient != 0, opt);
         renderer.SetFrames(frames);
         renderer.Display();
@@ -182,6 +190,14 @@ int rtgo_host_render_multi(const char* scene_name, const char* mode, uint32_t wi
         return RTGO_E_STATE;
     }
     return RTGO_OK;
+}
+
+int rtgo_host_render_multi(const char* scene_name, const char* mode, uint32_t width, uint32_t height, int sample, int ambient, int frames,
+                           const int* devices, int n_devices, int launches_per_device, int present_every, int rccl_for_local_shares,
+                           void* host_image, void* host_accum, rtgo_stats* stats, double* ms_per_frame)
+{
+    return rtgo_host_render_multi_batched(scene_name, mode, width, height, sample, ambient, frames, devices, n_devices, launches_per_device, present_every,
+                                          rccl_for_local_shares, host_image, host_accum, stats, ms_per_frame, 1);
 }
 
 struct rtgo_host_session {

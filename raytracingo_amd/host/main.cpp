@@ -25,6 +25,7 @@ static void printUsageAndExit(const char* argv0)
               << "         --out=<file.ppm>            Write the final 8-bit image (P6)              [headless addition]\n"
               << "         --out-accum=<file.pfm>      Write the float accumulation buffer (PFM)       [headless addition]\n"
               << "         --device=<i>                GPU index; default 0                          [headless addition]\n"
+              << "         --frames-per-launch=<k>     Render k frames per kernel launch (rtgo_launch_frames); default 1 [headless addition]\n"
               << "         --gpus=<n>                  Tile the frame in 4-row bands over GPUs 0..n-1, RCCL gather to GPU 0 [multi-GPU addition]\n"
               << "         --launches-per-gpu=<1|2>    Shares per GPU; default 1                       [multi-GPU addition]\n"
               << "         --present-every=<k>         Gather + assemble every k-th frame; default 1   [multi-GPU addition]\n";
@@ -45,7 +46,7 @@ static void parseDimensions(const char* arg, int& width, int& height)
 
 int main(int argc, char* argv[])
 {
-    int width = 600, height = 600, sample = 1, frames = 1, device = 0, gpus = 0, launchesPerGpu = 0, presentEvery = 1;
+    int width = 600, height = 600, sample = 1, frames = 1, device = 0, gpus = 0, launchesPerGpu = 0, presentEvery = 1, framesPerLaunch = 1;
     bool modeFound = false, sceneFound = false, useAmbient = false;
     RenderMode mode = RenderMode::PATH_TRACING;
     SceneModel scene = SceneModel::CORNELL;
@@ -74,6 +75,7 @@ int main(int argc, char* argv[])
                 if (!ok) { std::cerr << "Unknown option '" << arg << "'\n"; printUsageAndExit(argv[0]); }
             } else if (is("--sample=")) sample = std::atoi(value("--sample=").c_str());
             else if (is("--useAmbient")) useAmbient = true;
+            else if (is("--frames-per-launch=")) framesPerLaunch = std::atoi(value("--frames-per-launch=").c_str());
             else if (is("--frames=")) frames = std::atoi(value("--frames=").c_str());
             else if (is("--out-accum=")) outAccum = value("--out-accum=");
             else if (is("--out=")) out = value("--out=");
@@ -92,6 +94,7 @@ int main(int argc, char* argv[])
             for (int g = 0; g < gpus; ++g) opt.devices.push_back(g);
             opt.launchesPerDevice = launchesPerGpu > 0 ? launchesPerGpu : 1;   // (two half-share launches stopped paying with round 3's kernel: DESIGN.md section 6)
             opt.presentEvery = presentEvery;
+            opt.framesPerLaunch = framesPerLaunch;
             engine::host::MultiGpuRenderer renderer(sc, mode, sample, useAmbient, opt);
             renderer.SetFrames(frames);
             renderer.SetOutputFile(out);
@@ -106,6 +109,7 @@ int main(int argc, char* argv[])
         engine::host::Renderer renderer(sc, mode, sample, useAmbient);
         renderer.SetDevice(device);
         renderer.SetFrames(frames);
+        renderer.SetFramesPerLaunch(framesPerLaunch);
         renderer.SetOutputFile(out);
         renderer.SetAccumFile(outAccum);
         renderer.Display();

@@ -41,6 +41,7 @@ MultiGpuRenderer::MultiGpuRenderer(std::shared_ptr<Scene> scene, RenderMode rend
     if (m_opt.launchesPerDevice < 1 || m_opt.launchesPerDevice > 2) throw std::invalid_argument("MultiGpuRenderer: launchesPerDevice must be 1 or 2");
     if (m_opt.bandHeight == 0) m_opt.bandHeight = 4;
     if (m_opt.presentEvery < 1) m_opt.presentEvery = 1;
+    if (m_opt.framesPerLaunch < 1) m_opt.framesPerLaunch = 1;
     if (std::set<int>(m_opt.devices.begin(), m_opt.devices.end()).size() != m_opt.devices.size())
         throw std::invalid_argument("MultiGpuRenderer: a device is listed twice (use launchesPerDevice for two shares on one GPU)");
     try {
@@ -174,10 +175,12 @@ void MultiGpuRenderer::CleanUp()
     m_gpus.clear();
 }
 
-void MultiGpuRenderer::RenderFrame()
+void MultiGpuRenderer::RenderFrames(int n)
 {
-    // frame counter rule of Renderer::Update (renderer.cpp:682) without camera / resize events
-    m_frameCount = m_first ? 0 : m_frameCount + 1;
+    if (n < 1) throw std::invalid_argument("MultiGpuRenderer::RenderFrames: n must be positive");
+    // frame counter rule of Renderer::Update (renderer.cpp:682) without camera / resize events; the band buffer is the last frame's
+    const unsigned int firstFrame = m_first ? 0 : m_frameCount + 1;
+    m_frameCount = firstFrame + static_cast<unsigned int>(n - 1);
     m_first = false;
     const int b = static_cast<int>(m_frameCount & 1u);
     const uint32_t V = static_cast<uint32_t>(m_shares.size());
@@ -197,14 +200,15 @@ void MultiGpuRenderer::RenderFrame()
         f.image_height = m_height;
         f.sqrt_spp = m_sqrtSpp;
         f.max_trace_depth = 5;   // renderer.cpp:616
-        f.frame_count = m_frameCount;
+        f.frame_count = firstFrame;
         f.path_tracing = m_renderMode == RenderMode::PATH_TRACING ? 1u : 0u;
         f.use_ambient = m_useAmbient ? 1u : 0u;
         f.band_h = m_opt.bandHeight;
         f.n_ranks = V;
         f.rank = v;
         f.reserve_cus = (m_gpus.size() > 1 || m_opt.rcclForLocalShares) ? m_opt.reserveCus : 0u;
-        check(rtgo_launch(s.ctx, &f), "rtgo_launch");
+        if (n == 1) check(rtgo_launch(s.ctx, &f), "rtgo_launch");
+        else check(rtgo_launch_frames(s.ctx, &f, static_cast<uint32_t>(n)), "rtgo_launch_frames");
         gpu::EventRecord(s.rendered[b], s.stream);
     }
     m_lastBuffer = b;
@@ -286,9 +290,14 @@ void MultiGpuRenderer::Display()
 {
     Sync();
     const auto t0 = std::chrono::steady_clock::now();
-    for (int f = 0; f < m_frames; ++f) {
-        RenderFrame();
-        if ((f + 1) % m_opt.presentEvery == 0 || f == m_frames - 1) Present();
+    for (int f = 0; f < m_frames;) {
+        // a launch covers min(frames per launch, frames up to the next presented one, frames left)
+        int n = m_opt.presentEvery - f % m_opt.presentEvery;
+        n = n < m_opt.framesPerLaunch ? n : m_opt.framesPerLaunch;
+        n = n < m_frames - f ? n : m_frames - f;
+        RenderFrames(n);
+        f += n;
+        if (f % m_opt.presentEvery == 0 || f == m_frames) Present();
     }
     Sync();
     m_msPerFrame = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (m_frames > 0 ? m_frames : 1);

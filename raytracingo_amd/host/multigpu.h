@@ -34,6 +34,8 @@ public:
         int presentEvery = 1;            ///< gather + assemble every k-th frame (and always the last one of Display())
         bool rcclForLocalShares = false; ///< move the root GPU's own bands through ncclSend/ncclRecv-to-self too instead of a
                                          ///< device-to-device copy (lets a one-GPU box exercise the RCCL path end to end)
+        int framesPerLaunch = 1;         ///< Display(): frames per call of rtgo_launch_frames on every share -- at most up to the next
+                                         ///< presented frame; 1 = a launch per frame
         unsigned int reserveCus = 8;     ///< workgroup slots left free on every GPU for RCCL's kernels beside the persistent megakernel
     };
 
@@ -49,7 +51,9 @@ public:
     void SetAccumFile(const std::string& path) { m_accumFile = path; }
 
     /// launch the next frame on every share (asynchronous); frameCount advances like Renderer::Update (renderer.cpp:682)
-    void RenderFrame();
+    void RenderFrame() { RenderFrames(1); }
+    /// launch the next n frames on every share, one call of rtgo_launch_frames each (asynchronous)
+    void RenderFrames(int n);
     /// gather the 8-bit bands of the last rendered frame to the root and assemble the full image there (asynchronous)
     void Present();
     /// block until every launch and every gather issued so far has completed

@@ -11,7 +11,7 @@ namespace host {
 Renderer::Renderer(std::shared_ptr<Scene> scene, RenderMode renderMode, int sqrtSamplePerPixel, bool useAmbientCoeff)
     : m_scene(scene), m_renderMode(renderMode), m_useAmbientCoefficient(useAmbientCoeff), m_sqrtSamplePerPixel(sqrtSamplePerPixel),
       m_context(nullptr), m_params(), m_firstLaunch(true), m_cameraChangedFlag(false), m_windowResizeFlag(false), m_frames(1),
-      m_device(0)
+      m_framesPerLaunch(1), m_device(0)
 {
 }
 
@@ -171,10 +171,24 @@ void Renderer::RenderFrame()
     LaunchFrame();
 }
 
+void Renderer::RenderFrames(int n)
+{
+    if (n <= 1) return RenderFrame();
+    if (!m_context) Initialize();
+    Update();   // (the first of the n frames; the others follow it without an event in between)
+    Check(rtgo_launch_frames(m_context, &m_params, static_cast<uint32_t>(n)), "rtgo_launch_frames");
+    Check(rtgo_sync(m_context), "rtgo_sync");
+    m_params.frame_count += static_cast<uint32_t>(n - 1);
+}
+
 void Renderer::Display()
 {
     if (!m_context) Initialize();
-    for (int f = 0; f < m_frames; ++f) RenderFrame();
+    for (int f = 0; f < m_frames;) {
+        const int n = m_framesPerLaunch < m_frames - f ? m_framesPerLaunch : m_frames - f;
+        RenderFrames(n);
+        f += n;
+    }
     if (!m_outputFile.empty()) {
         std::cout << "Saving to file " << m_outputFile << std::endl;
         const std::vector<unsigned char> img = ReadImage();

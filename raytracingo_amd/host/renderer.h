@@ -26,12 +26,17 @@ public:
 
     // ---- headless controls (no reference counterpart: the reference is interactive only) ----
     void SetFrames(int frames) { m_frames = frames; }
+    /// Display() renders its frames k to a call of rtgo_launch_frames (the last call: what is left); 1, the default, is a call of
+    /// rtgo_launch per frame.  The pixels are the same either way.
+    void SetFramesPerLaunch(int k) { m_framesPerLaunch = k < 1 ? 1 : k; }
     void SetOutputFile(const std::string& path) { m_outputFile = path; }
     /// also dump the float accumulation buffer (PFM, RGB float32, bottom row first as PFM specifies = buffer order)
     void SetAccumFile(const std::string& path) { m_accumFile = path; }
     void SetDevice(int device) { m_device = device; }
     /// render exactly one more frame (frameCount advances like Renderer::Update does)
     void RenderFrame();
+    /// render exactly n more frames in one call of rtgo_launch_frames (n = 1: RenderFrame)
+    void RenderFrames(int n);
     /// what the trackball callbacks do to the camera (renderer.cpp:36-145 set cameraChangedFlag): the next frame restarts the
     /// accumulation at frameCount 0 and re-uploads the raygen record (Renderer::UpdateCamera, renderer.cpp:703-717)
     void MoveCamera(const float3& eye, const float3& lookat, const float3& up);
@@ -60,6 +65,7 @@ private:
     bool m_cameraChangedFlag;   // RendererState::cameraChangedFlag
     bool m_windowResizeFlag;    // RendererState::windowResizeFlag
     int m_frames;
+    int m_framesPerLaunch;
     int m_device;
     std::string m_outputFile;
     std::string m_accumFile;
