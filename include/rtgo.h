@@ -343,6 +343,51 @@ int rtgo_whitted_set_scene(rtgo_ctx* ctx, const rtgo_whitted_mesh* meshes, uint3
    scene as it was; textures stay.  Synchronous. */
 int rtgo_whitted_set_instances(rtgo_ctx* ctx, const rtgo_whitted_instance* instances, uint32_t n_instances);
 
+/* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
+   rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */
+
+/* One ray, 32 bytes (2 x float4).  dir is used as given, not normalised; t is in units of dir (optixTrace's semantics).  A ray is INVALID
+   when a component is not finite, dir == 0, tmin < 0, or tmax <= tmin (or NaN): it is answered with RTGO_HIT_INVALID and never walked. */
+typedef struct rtgo_ray {
+    float origin[3];
+    float tmin;
+    float dir[3];
+    float tmax;
+} rtgo_ray;
+
+/* One answer, 32 bytes (2 x float4).  A hit is accepted iff tmin < t < tmax; of two accepted hits at the same t the lowest SBT index wins
+   (analytic path), or the lowest (instance, triangle) (triangle path): the rules of the render kernels' walks, which these calls run.
+     analytic hit   t, prim = SBT index,                        instance = -1,             u = v = 0,        n = world-space normal, not normalised
+     triangle hit   t, prim = the mesh's own triangle index,    instance (0 for a mesh of rtgo_whitted_set_mesh), u, v = barycentrics, n = 0
+     miss           t = the ray's tmax, prim = RTGO_HIT_MISS,    everything else 0
+     invalid ray    prim = RTGO_HIT_INVALID,                     everything else 0 */
+typedef struct rtgo_hit {
+    float t;
+    int32_t prim;
+    int32_t instance;
+    float u, v;
+    float n[3];
+} rtgo_hit;
+
+/* flags.  RTGO_TRACE_ANY_HIT: stop at the first accepted hit (OPTIX_RAY_FLAG_TERMINATE_ON_FIRST_HIT): rely on hit-or-miss only, the
+   other fields describe SOME accepted hit.  (The analytic path answers with its closest walk: the reference's occlusion rays are
+   closest-hit rays too, kernel.cu:539-549.) */
+enum { RTGO_TRACE_CLOSEST = 0, RTGO_TRACE_ANY_HIT = 1 };
+#define RTGO_HIT_MISS    (-1)
+#define RTGO_HIT_INVALID (-2)
+
+/* Trace n rays against the scene of rtgo_set_scene / rtgo_set_large_scene.  d_rays = rtgo_ray[n], d_hits = rtgo_hit[n]: DEVICE memory of
+   the context's device, 16-byte aligned, caller-owned, not overlapping.  Asynchronous on the context's stream; needs no camera, lights
+   or output.  RTGO_E_INVALID: a NULL or misaligned pointer, unknown flag bits, n > 1 << 30; RTGO_E_STATE: no such scene; n == 0:
+   RTGO_OK, nothing is enqueued or written.  rtgo_stats: rays_total grows by n (with RTGO_TRACE_ANY_HIT rays_occlusion too); launches,
+   last_launch_ms, last_variant and the launch-time trial are left alone.  Every ray takes the canonical walk.
+   The primitives are the reference's intersection programs as the renders run them (kernel.cu:250-416): they report only t above a small
+   threshold of their own (1e-4, a cylinder 1e-3; units of dir), a rectangle from its front side only, a sphere at its near root only. */
+int rtgo_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags);
+
+/* The same over the scene of rtgo_whitted_set_mesh / rtgo_whitted_set_scene. */
+int rtgo_whitted_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags);
+
 /* number of window rows a rank owns under the band interleave (pure host arithmetic) */
 uint32_t rtgo_local_rows(uint32_t h, uint32_t band_h, uint32_t n_ranks, uint32_t rank);
 

@@ -69,6 +69,13 @@ int rtgo_host_session_frame(rtgo_host_session* s);                              
 int rtgo_host_session_move_camera(rtgo_host_session* s, const float eye[3], const float lookat[3], const float up[3]);
 int rtgo_host_session_resize(rtgo_host_session* s, uint32_t width, uint32_t height);
 int rtgo_host_session_read(rtgo_host_session* s, void* host_image, void* host_accum, uint32_t* frame_count);
+/* What pixel (x, y) shows (row 0 = bottom row, as in the image): the ray through the pixel's centre from the session's current camera,
+   dir = normalize((2 (x + .5) / width - 1) U + (2 (y + .5) / height - 1) V + W), tmin 1e-3, tmax 1e16, through rtgo_trace_rays.
+   *prim = the SBT index of the closest primitive and *t its distance; a miss returns 0 with *prim == -1.  Synchronous; the frame loop's
+   state (frame count, pending camera change or resize) is left as it is.  A pixel outside the image: an error code. */
+int rtgo_host_session_pick(rtgo_host_session* s, uint32_t x, uint32_t y, int32_t* prim, float* t);
+/* The camera pick uses and the next frame renders with (after move_camera / resize: the new one): eye and the raygen record's UVW */
+int rtgo_host_session_camera(rtgo_host_session* s, float eye[3], float U[3], float V[3], float W[3]);
 int rtgo_host_session_close(rtgo_host_session* s);
 
 const char* rtgo_host_last_error(void);

@@ -25,8 +25,10 @@ SYMBOLS = [
     "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands", "rtgo_set_large_scene",
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
-    "rtgo_whitted_launch_frame", "rtgo_launch_frames",
+    "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays",
 ]
+TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
+HIT_MISS, HIT_INVALID = -1, -2
 RTGO_WHITTED_MAX_MESHES = 256
 RTGO_WHITTED_MAX_INSTANCES = 8192
 RTGO_WHITTED_MAX_MESH_TRIANGLES = 1 << 24     # per mesh of rtgo_whitted_set_scene (beyond RTGO_MAX_TRIANGLES: a clustered mesh)
@@ -98,6 +100,28 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("instance", C.c_int32), ("u", C.c_float), ("v", C.c_float), ("n", C.c_float * 3)]
+
+
+# rtgo_ray / rtgo_hit as numpy records (32 bytes each): what Context.trace_rays takes and returns
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("tmin", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<i4"), ("instance", "<i4"), ("u", "<f4"), ("v", "<f4"), ("n", "<f4", (3,))])
+assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(Hit) == 32
+
+
+def make_rays(origins, dirs, tmin=1e-3, tmax=1e16):
+    """a RAY_DTYPE array from origins [n, 3] and directions [n, 3] (broadcast against each other) and scalar or per-ray tmin / tmax"""
+    o, d = np.broadcast_arrays(np.asarray(origins, dtype=np.float32).reshape(-1, 3), np.asarray(dirs, dtype=np.float32).reshape(-1, 3))
+    r = np.zeros(len(o), dtype=RAY_DTYPE)
+    r["origin"], r["dir"], r["tmin"], r["tmax"] = o, d, tmin, tmax
+    return r
+
+
 _lib = None
 
 
@@ -146,12 +170,33 @@ def load():
     L.rtgo_whitted_set_scene.argtypes = [vp, C.POINTER(WhittedMesh), C.c_uint32, C.POINTER(WhittedInstance), C.c_uint32, vp, C.c_uint32]
     L.rtgo_whitted_set_instances.argtypes = [vp, C.POINTER(WhittedInstance), C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
+    L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
+    L.rtgo_whitted_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtgo_last_error", "rtgo_local_rows", "rtgo_abi_version"):
             fn.restype = C.c_int
     _lib = L
     return L
+
+
+_hip = None
+
+
+def hip_runtime():
+    """the HIP runtime librtgo_hip.so runs on (the copy this process has mapped), for the few device buffers the binding itself needs"""
+    global _hip
+    if _hip is None:
+        load()
+        with open("/proc/self/maps") as f:
+            path = next((line.split()[-1] for line in f if "libamdhip64.so" in line), "libamdhip64.so")
+        H = C.CDLL(path)
+        H.hipSetDevice.argtypes = [C.c_int]
+        H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        H.hipFree.argtypes = [C.c_void_p]
+        H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]   # kind: 1 host to device, 2 device to host
+        _hip = H
+    return _hip
 
 
 def local_rows(h, band_h, n_ranks, rank):
@@ -173,6 +218,7 @@ class Context:
         if rc != 0:
             raise RtgoError("rtgo_create(%d) failed (%d): %s" % (device, rc, self._lib.rtgo_last_error(None).decode()))
         self._h = h
+        self.device = int(device)
         self.pixels = 0
 
     def _check(self, rc, what):
@@ -361,6 +407,55 @@ class Context:
     def whitted_launch_frame(self, frame):
         """one subframe of a window / row band of the image (make_whitted_frame): the output holds the share's compact rows"""
         self._check(self._lib.rtgo_whitted_launch_frame(self._h, C.byref(frame)), "rtgo_whitted_launch_frame")
+
+    # ---- ray queries: the caller's own rays against the context's scene ----
+    def _trace(self, fn, what, rays, flags):
+        H = hip_runtime()
+        if hasattr(rays, "data_ptr"):   # a torch device tensor: traced where it is
+            if not rays.is_cuda or not rays.is_contiguous() or rays.numel() * rays.element_size() % 32:
+                raise ValueError("%s: rays must be a contiguous device tensor of 32-byte rtgo_ray records" % what)
+            n, host = rays.numel() * rays.element_size() // 32, None
+        else:
+            host = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+            n = len(host)
+        hits = np.empty(n, dtype=HIT_DTYPE)
+        if n == 0:
+            return hits
+        if H.hipSetDevice(self.device) != 0:
+            raise RtgoError("%s: hipSetDevice(%d) failed" % (what, self.device))
+        buf = C.c_void_p()
+        if H.hipMalloc(C.byref(buf), 32 * n * (1 if host is None else 2)) != 0:
+            raise RtgoError("%s: hipMalloc of %d bytes failed" % (what, 64 * n))
+        try:
+            d_hits = buf.value
+            if host is None:
+                d_rays = rays.data_ptr()
+                H.hipDeviceSynchronize()   # (whatever stream filled the tensor: the trace runs on the context's)
+            else:
+                d_rays = buf.value + 32 * n
+                if H.hipMemcpy(d_rays, host.ctypes.data, 32 * n, 1) != 0:
+                    raise RtgoError("%s: upload failed" % what)
+            self._check(fn(self._h, C.c_void_p(d_rays), C.c_void_p(d_hits), n, int(flags)), what)
+            self.sync()
+            if H.hipMemcpy(hits.ctypes.data, d_hits, 32 * n, 2) != 0:
+                raise RtgoError("%s: download failed" % what)
+        finally:
+            H.hipFree(buf)
+        return hits
+
+    def trace_rays(self, rays, flags=0):
+        """rtgo_trace_rays over the scene of set_scene / set_large_scene.  rays: a RAY_DTYPE array (uploaded) or a contiguous torch
+        device tensor of rtgo_ray records; returns the hits as a HIT_DTYPE array.  Synchronous."""
+        return self._trace(self._lib.rtgo_trace_rays, "rtgo_trace_rays", rays, flags)
+
+    def whitted_trace_rays(self, rays, flags=0):
+        """rtgo_whitted_trace_rays over the scene of whitted_set_mesh / whitted_set_scene; as trace_rays"""
+        return self._trace(self._lib.rtgo_whitted_trace_rays, "rtgo_whitted_trace_rays", rays, flags)
+
+    def trace_rays_raw(self, d_rays_ptr, d_hits_ptr, n, flags=0, whitted=False):
+        """the bare C call on two device pointers (asynchronous); returns the library's code instead of raising"""
+        fn = self._lib.rtgo_whitted_trace_rays if whitted else self._lib.rtgo_trace_rays
+        return int(fn(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr), int(n), int(flags)))
 
     def stats(self):
         s = Stats()

@@ -5,6 +5,7 @@
 #include "rtgo_device.h"
 #include "rtgo_large.h"
 #include "rtgo_owners.h"
+#include "rtgo_trace.h"
 #include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
 
@@ -156,6 +157,7 @@ struct rtgo_ctx {
     float total_ms = 0.0f, last_ms = 0.0f;
     uint32_t launches = 0;
     uint32_t seeds_last = 0;                  // rtgo_debug_seeds: 1 = the last launch read pre-hashed seeds, 2 = it wrote the next frame's
+    unsigned long long trace_rays = 0, trace_rays_any = 0;   // rays of rtgo_trace_rays / rtgo_whitted_trace_rays since rtgo_reset_stats (host arithmetic)
 #ifdef RTGO_CMPWALK
     DeviceArray<float> d_cmp;                 // diagnostic build: disagreements between the two walks
 #endif
@@ -768,6 +770,14 @@ int rtgo_create(int device, rtgo_ctx** out)
                            (const void*)whitted::render_inst_kernel<true>, (const void*)whitted::render_inst_kernel<false, true>,
                            (const void*)whitted::render_inst_kernel<true, true>})
         if (err == hipSuccess) err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whitted::kRenderLds);
+    for (const void* fn : {(const void*)trace_rays_kernel<false>, (const void*)trace_rays_kernel<true>,
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceMesh, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceMesh, true>,
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceInst, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceInst, true>,
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceInstLds, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceInstLds, true>,
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceClustered, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceClustered, true>,
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceClusteredLds, false>,
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceClusteredLds, true>})
+        if (err == hipSuccess) err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
     if (err == hipSuccess) err = hipDeviceSynchronize();  // the null-stream memsets above must land before any launch
     if (err != hipSuccess) {
         std::string m = std::string("rtgo_create: ") + hipGetErrorString(err);
@@ -2698,6 +2708,158 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     });
 }
 
+// ---- ray queries (rtgo_trace.h) ----
+
+// RTGO_TRACE_MODE (test and experiment knob, RTGO_WHITTED_MODE's way): 0 = scene / top level read from global memory, 1 = staged in LDS
+// (where it fits); unset, empty or anything else: the host's own choice (-1).  No result depends on it.
+static int env_trace_mode()
+{
+    const char* v = std::getenv("RTGO_TRACE_MODE");
+    if (!v || !*v) return -1;
+    return v[0] == '0' ? 0 : (v[0] == '1' ? 1 : -1);
+}
+
+// Fewer rays than this walk the analytic scene from global memory: every workgroup of the LDS form copies the whole scene first (61 KB
+// for checkered).  From the smallest batch measured on, the copy repays itself (the measurement).
+static constexpr uint32_t kTraceLdsMinRays = 64;
+static constexpr uint32_t kTraceMaxRays = 1u << 30;
+static constexpr size_t kTraceLds = 160 * 1024;
+
+// the checks both entry points share; RTGO_OK with n == 0 means "nothing to do"
+static int trace_check(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags, const char* what)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (!d_rays || !d_hits) return fail(c, RTGO_E_INVALID, std::string(what) + ": NULL ray or hit buffer");
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return fail(c, RTGO_E_INVALID, std::string(what) + ": ray and hit buffers must be 16-byte aligned");
+    if (flags & ~(uint32_t)RTGO_TRACE_ANY_HIT) return fail(c, RTGO_E_INVALID, std::string(what) + ": unknown flag bits");
+    if (n > kTraceMaxRays) return fail(c, RTGO_E_INVALID, std::string(what) + ": more than 2^30 rays");
+    return RTGO_OK;
+}
+
+// The grid of a grid-stride launch: enough workgroups for the batch, at most per_cu on every CU, at most RTGO_TRACE_BLOCKS
+static unsigned int trace_grid(const rtgo_ctx* c, uint32_t n, int block, int per_cu)
+{
+    const uint64_t need = ((uint64_t)n + (uint64_t)block - 1) / (uint64_t)block;
+    uint64_t grid = (uint64_t)c->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
+    if (grid > need) grid = need;
+    const unsigned int cap = env_uint("RTGO_TRACE_BLOCKS", 0);
+    if (cap && grid > cap) grid = cap;
+    return (unsigned int)grid;
+}
+
+int rtgo_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags)
+{
+    if (const int rc = trace_check(c, d_rays, d_hits, n, flags, "rtgo_trace_rays")) return rc;
+    const AnalyticScene& sc = c->scene;
+    if (sc.n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_trace_rays: no scene (call rtgo_set_scene or rtgo_set_large_scene)");
+    if (n == 0) return RTGO_OK;
+    TraceParams p;
+    std::memset(&p, 0, sizeof p);
+    p.nodes = sc.d_nodes.get();
+    p.prims = sc.d_prims.get();
+    p.rays = (const float4*)d_rays;
+    p.hits = (float4*)d_hits;
+    p.n = n;
+    p.n_prims = (int)sc.n_prims;
+    p.n_nodes = 2 * (int)sc.n_prims - 1;
+    // the stacks as deep as the canonical instantiations have them: kStackDepth over a scene of rtgo_set_scene (its build checks the
+    // tree against it), the tree's own depth over a scene of rtgo_set_large_scene
+    p.stack_depth = sc.large ? (sc.lbvh_depth > 0 ? sc.lbvh_depth : 1) : kStackDepth;
+    const size_t scene_lds = (size_t)(2 * p.n_nodes + 6 * p.n_prims) * sizeof(float4);
+    // the workgroup that puts the most waves on a CU (pick_block's rule: the scene copy is per workgroup, the stacks per lane), at
+    // most 8 a SIMD, the smallest on ties
+    auto pick = [&](bool in_lds, int& block, int& per_cu, size_t& lds) {
+        int best_waves = 0;
+        for (int bs = 64; bs <= kMaxBlock; bs *= 2) {
+            const size_t l = (in_lds ? scene_lds : 0) + (size_t)p.stack_depth * bs * sizeof(float2);
+            int k = (int)(kTraceLds / l);
+            if (k * (bs / 64) > 32) k = 32 / (bs / 64);
+            if (k * (bs / 64) > best_waves) {
+                best_waves = k * (bs / 64);
+                block = bs;
+                per_cu = k;
+                lds = l;
+            }
+        }
+        return best_waves > 0;
+    };
+    const int mode = env_trace_mode();
+    int block = 0, per_cu = 0;
+    size_t lds = 0;
+    bool in_lds = !sc.large && sc.n_prims <= (uint32_t)kMaxPrims && (mode == 1 || (mode < 0 && n >= kTraceLdsMinRays));
+    if (in_lds && !pick(true, block, per_cu, lds)) in_lds = false;
+    if (!in_lds && !pick(false, block, per_cu, lds)) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_trace_rays: the walk's stacks do not fit in LDS");
+    const unsigned int grid = trace_grid(c, n, block, per_cu);
+    RTGO_HIP(c, hipSetDevice(c->device));
+    if (in_lds) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(grid), dim3(block), lds, c->stream, p);
+    else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(grid), dim3(block), lds, c->stream, p);
+    RTGO_HIP(c, hipGetLastError());
+    c->trace_rays += n;
+    if (flags & RTGO_TRACE_ANY_HIT) c->trace_rays_any += n;   // (the analytic path has no any-hit walk: the closest walk answers)
+    return RTGO_OK;
+}
+
+int rtgo_whitted_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags)
+{
+    if (const int rc = trace_check(c, d_rays, d_hits, n, flags, "rtgo_whitted_trace_rays")) return rc;
+    const WhittedMesh& wm = c->wm;
+    if (wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_trace_rays: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene)");
+    if (n == 0) return RTGO_OK;
+    whitted::TraceRaysParams p;
+    std::memset(&p, 0, sizeof p);
+    p.rays = (const float4*)d_rays;
+    p.hits = (float4*)d_hits;
+    p.n = n;
+    // workgroups of 256 lanes: nothing is shared between the lanes but the top level's copy, and the tail of a batch is shorter
+    const int block = 256;
+    const size_t stack_bytes = (size_t)block * (size_t)(wm.walk_depth > 0 ? wm.walk_depth : 1) * sizeof(unsigned short);
+    const bool any = (flags & RTGO_TRACE_ANY_HIT) != 0;
+    size_t lds = stack_bytes;
+    int kind = whitted::kTraceMesh;
+    if (!wm.instanced) {
+        p.mesh.recs = wm.recs.get();
+        p.mesh.tris = wm.tris.get();
+        p.mesh.n_recs = wm.n_recs;
+        p.mesh.n_triangles = wm.triangles;
+    } else {
+        p.inst.top_recs = wm.top.recs.get();
+        p.inst.inst = wm.top.inst.get();
+        p.inst.n_top_recs = wm.top.n_recs;
+        p.inst.n_instances = wm.top.n_instances;
+        p.inst.recs = wm.recs.get();
+        p.inst.tris = wm.tris.get();
+        p.inst.clusters = wm.clusters.get();
+        // the top level in LDS where four workgroups a CU still fit with it (RTGO_TRACE_MODE: never / wherever one fits)
+        const size_t top_bytes = (size_t)p.inst.n_top_recs * 4 * sizeof(float4) + (size_t)p.inst.n_instances * sizeof(whitted::InstWalk);
+        const int mode = env_trace_mode();
+        const bool in_lds = mode != 0 && top_bytes + stack_bytes <= (mode == 1 ? kTraceLds : kTraceLds / 4);
+        if (in_lds) lds += top_bytes;
+        kind = p.inst.clusters ? (in_lds ? whitted::kTraceClusteredLds : whitted::kTraceClustered) : (in_lds ? whitted::kTraceInstLds : whitted::kTraceInst);
+    }
+    int per_cu = (int)(kTraceLds / lds);
+    if (per_cu > 8) per_cu = 8;
+    const dim3 grid(trace_grid(c, n, block, per_cu)), bdim(block);
+    RTGO_HIP(c, hipSetDevice(c->device));
+    using namespace whitted;
+#define RTGO_WT(K)                                                                                             \
+    case K:                                                                                                    \
+        if (any) hipLaunchKernelGGL((whitted_trace_kernel<K, true>), grid, bdim, lds, c->stream, p);           \
+        else hipLaunchKernelGGL((whitted_trace_kernel<K, false>), grid, bdim, lds, c->stream, p);              \
+        break;
+    switch (kind) {
+        RTGO_WT(kTraceMesh)
+        RTGO_WT(kTraceInst)
+        RTGO_WT(kTraceInstLds)
+        RTGO_WT(kTraceClustered)
+        RTGO_WT(kTraceClusteredLds)
+    }
+#undef RTGO_WT
+    RTGO_HIP(c, hipGetLastError());
+    c->trace_rays += n;
+    if (any) c->trace_rays_any += n;
+    return RTGO_OK;
+}
+
 int rtgo_sync(rtgo_ctx* c)
 {
     if (!c) return RTGO_E_INVALID;
@@ -2741,8 +2903,8 @@ int rtgo_get_stats(rtgo_ctx* c, rtgo_stats* out)
     unsigned long long h[8];
     RTGO_HIP(c, hipMemcpyAsync(h, c->d_counters.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    out->rays_total = h[0];
-    out->rays_occlusion = h[1];
+    out->rays_total = h[0] + c->trace_rays;
+    out->rays_occlusion = h[1] + c->trace_rays_any;
     out->node_visits = h[2];
     out->prim_tests = h[3];
     out->hits = h[4];
@@ -2776,6 +2938,8 @@ int rtgo_reset_stats(rtgo_ctx* c)
     c->launches_canonical = 0;
     c->launches_trial = 0;
     c->rays_culled = 0;
+    c->trace_rays = 0;
+    c->trace_rays_any = 0;
     return RTGO_OK;
 }
 

@@ -256,6 +256,32 @@ int rtgo_host_session_resize(rtgo_host_session* s, uint32_t width, uint32_t heig
     RTGO_SESSION_TRY(s->renderer->Resize(width, height))
 }
 
+int rtgo_host_session_pick(rtgo_host_session* s, uint32_t x, uint32_t y, int32_t* prim, float* t)
+{
+    if (!s || !prim || !t) return RTGO_E_INVALID;
+    RTGO_SESSION_TRY({
+        int p = -1;
+        s->renderer->Pick(x, y, p, *t);
+        *prim = p;
+    })
+}
+
+int rtgo_host_session_camera(rtgo_host_session* s, float eye[3], float U[3], float V[3], float W[3])
+{
+    if (!s || !eye || !U || !V || !W) return RTGO_E_INVALID;
+    RTGO_SESSION_TRY({
+        float3 e;
+        float3 u;
+        float3 v;
+        float3 w;
+        s->renderer->CurrentCamera(e, u, v, w);
+        eye[0] = e.x; eye[1] = e.y; eye[2] = e.z;
+        U[0] = u.x; U[1] = u.y; U[2] = u.z;
+        V[0] = v.x; V[1] = v.y; V[2] = v.z;
+        W[0] = w.x; W[1] = w.y; W[2] = w.z;
+    })
+}
+
 int rtgo_host_session_read(rtgo_host_session* s, void* host_image, void* host_accum, uint32_t* frame_count)
 {
     if (!s) return RTGO_E_INVALID;

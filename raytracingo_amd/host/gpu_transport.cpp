@@ -76,6 +76,7 @@ void CopyDeviceToDeviceAsync(void* dst, const void* src, size_t bytes, void* str
     hipCheck(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)), "hipMemcpyAsync");
 }
 void CopyDeviceToHost(void* dst, const void* src, size_t bytes) { hipCheck(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "hipMemcpy"); }
+void CopyHostToDevice(void* dst, const void* src, size_t bytes) { hipCheck(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy"); }
 
 Comms* CommsCreate(const std::vector<int>& devices)
 {

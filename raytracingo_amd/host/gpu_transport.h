@@ -23,6 +23,7 @@ void* Malloc(size_t bytes);                 // zero-filled
 void Free(void* p);
 void CopyDeviceToDeviceAsync(void* dst, const void* src, size_t bytes, void* stream);
 void CopyDeviceToHost(void* dst, const void* src, size_t bytes);
+void CopyHostToDevice(void* dst, const void* src, size_t bytes);
 
 // RCCL: one process, one rank per listed GPU (ncclCommInitAll); rank i is devices[i]
 struct Comms;

@@ -1,6 +1,8 @@
 // renderer.cpp -- Renderer over the rtgo C ABI.  Each private step names the reference step it stands in for.
 #include "renderer.h"
+#include "gpu_transport.h"
 
+#include <cmath>
 #include <fstream>
 #include <iostream>
 #include <stdexcept>
@@ -10,7 +12,7 @@ namespace host {
 
 Renderer::Renderer(std::shared_ptr<Scene> scene, RenderMode renderMode, int sqrtSamplePerPixel, bool useAmbientCoeff)
     : m_scene(scene), m_renderMode(renderMode), m_useAmbientCoefficient(useAmbientCoeff), m_sqrtSamplePerPixel(sqrtSamplePerPixel),
-      m_context(nullptr), m_params(), m_firstLaunch(true), m_cameraChangedFlag(false), m_windowResizeFlag(false), m_frames(1),
+      m_context(nullptr), m_params(), m_pickBuffer(nullptr), m_firstLaunch(true), m_cameraChangedFlag(false), m_windowResizeFlag(false), m_frames(1),
       m_framesPerLaunch(1), m_device(0)
 {
 }
@@ -157,6 +159,39 @@ void Renderer::Resize(unsigned int width, unsigned int height)
     m_windowResizeFlag = true;
 }
 
+void Renderer::CurrentCamera(float3& eye, float3& u, float3& v, float3& w)
+{
+    if (!m_context) Initialize();
+    const std::shared_ptr<sutil::Camera> camera = m_scene->GetCamera();
+    // (UpdateCamera's aspect ratio, set early; the flag stays up: the next frame still restarts the running average)
+    if (m_cameraChangedFlag) camera->setAspectRatio(static_cast<float>(m_params.image_width) / static_cast<float>(m_params.image_height));
+    camera->UVWFrame(u, v, w);
+    eye = camera->eye();
+}
+
+void Renderer::Pick(unsigned int x, unsigned int y, int& prim, float& t)
+{
+    if (!m_context) Initialize();
+    if (x >= m_params.image_width || y >= m_params.image_height) throw std::invalid_argument("Renderer::Pick: pixel outside the image");
+    float3 e, u, v, w;
+    CurrentCamera(e, u, v, w);
+    const float fx = 2.0f * (static_cast<float>(x) + 0.5f) / static_cast<float>(m_params.image_width) - 1.0f;
+    const float fy = 2.0f * (static_cast<float>(y) + 0.5f) / static_cast<float>(m_params.image_height) - 1.0f;
+    const float dx = fx * u.x + fy * v.x + w.x, dy = fx * u.y + fy * v.y + w.y, dz = fx * u.z + fy * v.z + w.z;
+    const float len = std::sqrt(dx * dx + dy * dy + dz * dz);
+    rtgo_ray ray = {{e.x, e.y, e.z}, 1e-3f, {dx / len, dy / len, dz / len}, 1e16f};
+    rtgo_hit hit;
+    gpu::SetDevice(m_device);
+    if (!m_pickBuffer) m_pickBuffer = gpu::Malloc(sizeof(rtgo_ray) + sizeof(rtgo_hit));
+    void* d_hit = static_cast<unsigned char*>(m_pickBuffer) + sizeof(rtgo_ray);
+    gpu::CopyHostToDevice(m_pickBuffer, &ray, sizeof ray);
+    Check(rtgo_trace_rays(m_context, m_pickBuffer, d_hit, 1, RTGO_TRACE_CLOSEST), "rtgo_trace_rays");
+    Check(rtgo_sync(m_context), "rtgo_sync");
+    gpu::CopyDeviceToHost(&hit, d_hit, sizeof hit);
+    prim = hit.prim;
+    t = hit.t;
+}
+
 void Renderer::LaunchFrame()
 {
     // optixLaunch + stream sync + CUDA_SYNC_CHECK (renderer.cpp:749-774)
@@ -261,6 +296,10 @@ void Renderer::SavePFM(const std::string& path, const float* rgba, unsigned int 
 void Renderer::CleanUp()
 {
     // renderer.cpp:870-885
+    if (m_pickBuffer) {
+        gpu::Free(m_pickBuffer);
+        m_pickBuffer = nullptr;
+    }
     if (m_context) {
         rtgo_destroy(m_context);
         m_context = nullptr;

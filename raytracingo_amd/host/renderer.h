@@ -42,6 +42,13 @@ public:
     void MoveCamera(const float3& eye, const float3& lookat, const float3& up);
     /// what windowSizeCallback does (renderer.cpp:61-78 set windowResizeFlag): new image size, aspect ratio, buffers; restarts at 0
     void Resize(unsigned int width, unsigned int height);
+    /// the camera the next frame renders with: the eye and the UVW frame of the raygen record (after MoveCamera / Resize: the new one,
+    /// with the aspect ratio of the current image size, before any frame has used it)
+    void CurrentCamera(float3& eye, float3& u, float3& v, float3& w);
+    /// What the pixel shows (no reference counterpart: the reference's viewer cannot say): the ray through the centre of pixel (x, y)
+    /// of the current camera, dir = normalize((2 (x + .5) / width - 1) U + (2 (y + .5) / height - 1) V + W), tmin 1e-3, tmax 1e16,
+    /// traced with rtgo_trace_rays.  Synchronous; does not touch the frame loop's state.  A miss gives prim -1 and t = tmax.
+    void Pick(unsigned int x, unsigned int y, int& prim, float& t);
     unsigned int Width() const { return m_params.image_width; }
     unsigned int Height() const { return m_params.image_height; }
     unsigned int FrameCount() const { return m_params.frame_count; }
@@ -61,6 +68,7 @@ private:
     int m_sqrtSamplePerPixel;
     rtgo_ctx* m_context;
     rtgo_frame m_params;   // the launch constants the reference keeps in device::Params
+    void* m_pickBuffer;    // device memory of Pick: one rtgo_ray, then one rtgo_hit (allocated on first use)
     bool m_firstLaunch;
     bool m_cameraChangedFlag;   // RendererState::cameraChangedFlag
     bool m_windowResizeFlag;    // RendererState::windowResizeFlag

@@ -156,6 +156,8 @@ class Session:
         L.rtgo_host_session_resize.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.rtgo_host_session_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.rtgo_host_session_close.argtypes = [C.c_void_p]
+        L.rtgo_host_session_pick.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        L.rtgo_host_session_camera.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 4
         self._L = L
         self._h = C.c_void_p()
         self.width, self.height = width, height
@@ -182,6 +184,18 @@ class Session:
         fc = C.c_uint32(0)
         self._ok(self._L.rtgo_host_session_read(self._h, img.ctypes.data, acc.ctypes.data, C.byref(fc)))
         return acc, img, int(fc.value)
+
+    def pick(self, x, y):
+        """(prim, t) of what pixel (x, y) shows through the session's current camera; prim -1: nothing"""
+        prim, t = C.c_int32(0), C.c_float(0.0)
+        self._ok(self._L.rtgo_host_session_pick(self._h, x, y, C.byref(prim), C.byref(t)))
+        return int(prim.value), np.float32(t.value)
+
+    def camera(self):
+        """eye, U, V, W (float32 [3] each) of the session's current camera"""
+        a = [np.zeros(3, dtype=np.float32) for _ in range(4)]
+        self._ok(self._L.rtgo_host_session_camera(self._h, *[x.ctypes.data_as(C.POINTER(C.c_float)) for x in a]))
+        return a
 
     def close(self):
         if self._h:
