@@ -1,6 +1,7 @@
 """Build the native parts of raytracingo_amd in-tree (the .so files travel to the GPU box with the snapshot).
 
-  librtgo_hip.so   csrc/rtgo_capi.hip + rtgo_device.h   hipcc --offload-arch=gfx950   (the product: C ABI + kernels)
+  librtgo_hip.so   csrc/rtgo_capi.hip + csrc/*.h, *.inc  hipcc --offload-arch=gfx950   (the product: C ABI + kernels; one translation unit:
+                   the kernels' headers, and the host side's rtgo_ctx.h and rtgo_whitted_host.h)
   librtgo_host.so  host/*.cpp                            g++ (+ libamdhip64, librccl)  (Scene/Shape/Renderer mirror, multi-GPU driver)
   rtgo_engine      host/main.cpp                         g++                           (headless CLI of engine/main.cpp)
 """

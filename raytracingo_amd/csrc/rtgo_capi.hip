@@ -1,24 +1,7 @@
 // rtgo_capi.hip -- the C ABI of include/rtgo.h over the gfx950 kernels of rtgo_device.h.
 // Host side of the drop-in boundary: where the reference's Renderer calls the OptiX host API, a port calls these.
 // There is no CPU fallback anywhere in this file: every path ends in a HIP launch or an error code.
-#include "../../include/rtgo.h"
-#include "rtgo_device.h"
-#include "rtgo_large.h"
-#include "rtgo_owners.h"
-#include "rtgo_trace.h"
-#include "rtgo_whitted_big.h"
-#include "rtgo_whitted_inst.h"
-
-#include <algorithm>
-#include <array>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-using namespace rtgo;
+#include "rtgo_ctx.h"
 
 static_assert(sizeof(rtgo_prim) == sizeof(PrimIn), "rtgo_prim layout");
 static_assert(sizeof(rtgo_prim) == 108, "rtgo_prim is type + HitGroupData (104 B, params.h:103-110)");
@@ -26,215 +9,6 @@ static_assert(sizeof(rtgo_light) == sizeof(LightRec) && sizeof(rtgo_light) == 64
 static_assert(sizeof(rtgo_aabb) == 24, "OptixAabb is 24 B");
 static_assert(RTGO_MAX_PRIMS == kMaxPrims && RTGO_MAX_LIGHTS == kMaxLights, "limits");
 static_assert(RTGO_MAX_SCENE_PRIMS <= (1 << 29), "2n-1 nodes of 32 bytes and their int indices stay within int range");
-
-// one mesh of an instanced whitted scene (rtgo_whitted_set_scene), host side
-struct WhittedMeshInfo {
-    float lo[3], hi[3];        // a box around the mesh's root record (the padded triangle bounds, padded once more)
-    int rec_base, tri_base, vert_base;   // where its records / triangles / vertices start in the context's arrays
-    int root;                  // InstWalk::root
-    int flags;                 // whitted::kHasNormals | kHasTexcoords
-    int depth;                 // stack entries its walk needs (a clustered mesh: its mid level's + its deepest cluster's)
-    uint32_t max_material;     // its largest material_of_triangle
-    bool clustered;            // beyond kMaxTriangles triangles: a mid level over clusters (rtgo_whitted_big.h)
-    int n_tris;
-    // what each whitted_build of this mesh wrote into the context's arrays (rtgo_debug_build_digest): records [rec0, rec0 + n_recs) and
-    // their quantised forms at qrecs[2 tri0 ..] (tri0 < 0: none kept, a mid level's)
-    struct Built { int rec0, n_recs, tri0; whitted::WhittedBuildMeta meta; };   // (meta: what that build reported)
-    std::vector<Built> built;
-};
-
-// The analytic scene (rtgo_set_scene, rtgo_set_large_scene): replaced as a whole, by assigning a fresh one
-struct AnalyticScene {
-    // The third structure of the trial (rtgo_ctx::Trial): a uniform grid over structure 0's small primitives (rtgo::fast_grid), built by
-    // the host from the boxes build_kernel reports.  Scenes of many small primitives spread evenly (balls: 256 spheres in a room) walk it
-    // in a third of the tree's instructions; where it is slower the trial drops it after two launches.
-    struct Grid {
-        DeviceArray<unsigned char> d;      // [table: n_cells words, 0 = empty cell, else 1 + its record][records: 32 B per listing cell, its box
-                                           // and (first item | count << 16)][items: 16-bit positions into d_fprims] (GridParams' offsets)
-        int n_nodes = 0;                   // its size in 32-byte units (what LaunchParams::n_fnodes counts)
-        int entries = 0;                   // list entries (rtgo_debug_grid)
-        rtgo::GridParams gp = {};
-        float reach_max = 0.0f;            // the pad of the binning covers the walk's rounding for rays that start within this reach
-        bool have = false;
-    } grid;
-    struct FastTree {                      // what build_kernel makes for one big_frac
-        DeviceArray<float4> d_fnodes;      // collapsed LBVH of the fast walk
-        DeviceArray<float4> d_fprims;      // Morton-ordered traversal records of the fast walk
-        int fast_depth = 0, n_small = 0, n_fnodes = 0;   // its depth, primitives (the rest are tested up front) and nodes
-        int cuboid_groups = 0;             // certified groups in the scene (leaves + the list's)
-        int tree_spheres = 0;              // every primitive of the tree is a sphere
-        int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
-        float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
-        // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and
-        // for each (emitter, wall) pair k = 6 e + g the least y_g over the emitter's corners and the coefficients of the margin it
-        // has to exceed, K (emit_a R + emit_b) (last_ray_params)
-        int emit_n = 0;
-        float emit_ymin[6 * kMaxEmitters] = {}, emit_a[6 * kMaxEmitters] = {}, emit_b[6 * kMaxEmitters] = {};
-        BuildMeta meta = {};               // build_kernel's meta words as it wrote them (rtgo_debug_read_build)
-        bool sane(uint32_t n) const { return n_fnodes >= 0 && n_fnodes <= 2 * (int)n - 1 && !(n_small > 0 && n_fnodes < 1); }
-    } tree[2];                             // the structures of 36 % and 15 %
-    bool have_alt = false;                 // tree[1] is a candidate: false when the two builds came out the same, or RTGO_BIG_PERCENT pins one
-    uint32_t n_prims = 0;                  // 0: no scene (set last, once the build succeeded)
-    DeviceArray<PrimIn> d_prims_in;
-    DeviceArray<float> d_aabb;
-    DeviceArray<float4> d_nodes, d_prims;
-    DeviceArray<float4> d_frames;          // shading frames of the flat primitives (2 float4 per primitive, SBT order)
-    bool large = false;                    // the scene came from rtgo_set_large_scene: d_nodes / d_prims / d_aabb only, walked from global memory
-    int lbvh_depth = 0;
-    float bounds[6] = {0, 0, 0, 0, 0, 0};  // tight world bounds of the scene (min xyz, max xyz)
-    // far-field guard (rtgo_launch): per sphere / cylinder its centre and smax / smin^2 of its model matrix' axis scales -- the
-    // reported hit of a quadric seen from distance D lies up to ~2^-25 D^2 smax / smin^2 off its surface (b^2 - 4ac cancels)
-    struct Quadric { float c[3], w; };
-    std::vector<Quadric> quadrics;
-    DeviceArray<float> d_tight;            // the fast walk's box of every primitive (device), and its host copy
-    std::vector<float> tight;
-};
-
-// An instanced scene's top level (rtgo_whitted_set_instances replaces it alone)
-struct WhittedTop {
-    DeviceArray<float4> recs;
-    DeviceArray<whitted::InstWalk> inst;       // in the top level's leaf order
-    DeviceArray<whitted::InstShade> shade;     // in the caller's order
-    int n_recs = 0, n_instances = 0;
-    whitted::WhittedBuildMeta meta = {};       // what its build reported (rtgo_debug_read_build)
-};
-
-// The whitted triangle path's scene (rtgo_whitted.h; rtgo_whitted_set_mesh, rtgo_whitted_set_scene): replaced as a whole
-struct WhittedMesh {
-    DeviceArray<float> positions, normals;
-    DeviceArray<float> texcoords;              // 2 floats per vertex, or empty
-    DeviceArray<unsigned int> indices, tri_material;
-    DeviceArray<whitted::Pbr> materials;
-    // textures: per material its three texel arrays, the table that points into them, and its device copy (empty while no material
-    // has a texture)
-    std::vector<std::array<DeviceArray<uchar4>, 3>> texels;
-    std::vector<whitted::MatTex> mat_tex_host;
-    DeviceArray<whitted::MatTex> mat_tex;
-    DeviceArray<float4> nodes;
-    DeviceArray<float4> recs, tris;            // the walk's records (4 float4 each) and the triangles in Morton order (3 float4 each)
-    DeviceArray<uint4> qrecs;                  // the compact form: quantised records, (vertex indices | triangle index) per triangle
-    DeviceArray<uint2> tidx;
-    DeviceArray<int> scratch;
-    int n_vertices = 0;
-    v3 grid_lo{0, 0, 0}, grid_step{0, 0, 0};
-    int n_recs = 0, walk_depth = 0;
-    whitted::WhittedBuildMeta meta = {};       // what the build reported (one mesh; rtgo_debug_read_build)
-    int triangles = 0, n_materials = 0;        // triangles = 0: no mesh
-    // an instanced scene (rtgo_whitted_set_scene): the mesh buffers above hold every mesh back to back in object space (nodes,
-    // scratch: the largest mesh's build), plus the top level
-    bool instanced = false;
-    std::vector<WhittedMeshInfo> meshes;
-    int mesh_depth = 0;                        // the deepest mesh walk
-    WhittedTop top;
-    DeviceArray<int4> clusters;                // the clustered meshes' cluster tables (InstParams::clusters), or empty when there are none
-};
-
-struct rtgo_ctx {
-    int device = 0;
-    int num_cus = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    // ring of HIP-event pairs bracketing each megakernel launch on the launch stream (launches are asynchronous, so the
-    // elapsed times are harvested later: at rtgo_sync, or when the ring wraps)
-    static constexpr int kEvRing = 64;
-    hipEvent_t ev_start[kEvRing] = {}, ev_stop[kEvRing] = {};
-    int ev_head = 0, ev_pending = 0;
-    unsigned char ev_tag[kEvRing] = {};    // a trial launch of candidate k carries k + 1, any other launch 0 (see `trial` below)
-    DeviceArray<unsigned int> d_queue;     // two sets of work-queue heads: a launch counts on one and zeroes the other for the next
-    int queue_set = 0;
-    DeviceArray<unsigned long long> d_counters;   // 8 x u64
-    DeviceArray<LightRec> d_lights;
-    int n_lights = 0;
-    DeviceArray<int> d_meta;               // build_kernel's meta words (one build at a time)
-    int leaf_budget = kDefaultLeafBudget;
-    bool have_camera = false;
-    v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};
-    // stats (rtgo_get_stats)
-    float guard_reach = 0.0f, guard_quadric = 0.0f;   // of the last launch
-    unsigned long long rays_culled = 0;       // since rtgo_reset_stats (host arithmetic: the cold pixels of each launch x N*N)
-    uint32_t launches_canonical = 0;          // since rtgo_reset_stats
-    uint32_t launches_trial = 0, last_variant = 0;
-    float total_ms = 0.0f, last_ms = 0.0f;
-    uint32_t launches = 0;
-    uint32_t seeds_last = 0;                  // rtgo_debug_seeds: 1 = the last launch read pre-hashed seeds, 2 = it wrote the next frame's
-    unsigned long long trace_rays = 0, trace_rays_any = 0;   // rays of rtgo_trace_rays / rtgo_whitted_trace_rays since rtgo_reset_stats (host arithmetic)
-#ifdef RTGO_CMPWALK
-    DeviceArray<float> d_cmp;                 // diagnostic build: disagreements between the two walks
-#endif
-#ifdef RTGO_TIMELINE
-    DeviceArray<unsigned long long> d_timeline;   // diagnostic build: 8 x u64 per wave
-    unsigned int timeline_waves = 0;
-#endif
-
-    AnalyticScene scene;
-    // ---- launch caches of the analytic path
-    // Frames of several passes per pixel (> 16 spp) have two kernels with bitwise the same output: lanes streaming through their
-    // samples (open scenes, where path lengths differ: plateau 3840x2160 spp 256 18.8 ms against 20.5) or the wave running pass by
-    // pass in lock-step (closed scenes, where nearly every path runs to the depth limit and regeneration only costs: cornell spp 64
-    // 4.42 ms against 4.9).  Which one is faster is a property of scene and frame that the host cannot see, but the launch times
-    // it takes anyway tell: the first four launches of a (scene, frame geometry, spp, mode) alternate between the two, the faster
-    // minimum keeps the job.
-    // Round 3: the same trial also decides WHICH fast-walk structure a launch walks.  How big a primitive has to be to be tested up
-    // front by every ray instead of sitting in the tree (build_kernel's big_frac) is worth 20 % on plateau (nearly everything up front:
-    // a dozen tests at full lanes beat a walk at a third of them) and costs 20 % on cornell (its two boxes lose their cuboid leaves), and
-    // no rule read off the scene predicts it (profiles/r03n/big_sweep.log); so rtgo_set_scene builds the structure twice -- 36 % and 15 % --
-    // and the candidates of a trial are (loop, structure) pairs: every candidate gets two timed launches, the best minimum keeps the job.
-    // All candidates return the same pixels bit for bit (any tree over the same primitives returns the same closest hit).
-    struct Trial {
-        std::vector<uint32_t> key;
-        int issued = 0, done = 0;
-        float best[8] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-        int choice = -1;                   // index of the winning candidate, -1 = undecided
-    } trial;
-    // per-strip mask of the scene's screen rectangle (LaunchParams::hot_mask), kept until the launch geometry changes; its buffers
-    // outlive a scene
-    struct HotMask {
-        DeviceArray<unsigned int> d;
-        // pinned staging for its upload, two slots used in turn with an event each: a camera change (every frame of an interactive
-        // drag) rebuilds the mask, and the upload must not make the host wait for the stream
-        PinnedArray<unsigned int> h[2];
-        LazyEvent copied[2];
-        int slot = 0;
-        std::vector<uint32_t> key;         // what the cached mask was built for
-        bool all_hot = true;
-        unsigned long long cold_pixels = 0;
-    } mask;
-    // next frame's pixel seeds (LaunchParams::seeds): two buffers, a launch reads one and writes the other.  ok: the buffer `read`
-    // holds frame `frame`'s seeds for the strip layout `key` (written by the last launch on this context)
-    struct Seeds {
-        DeviceArray<unsigned int> d[2];
-        int read = 0;
-        bool ok = false;
-        uint32_t frame = 0;
-        std::vector<uint32_t> key;
-    } seeds;
-    // ---- output: the context's own buffers (rtgo_resize) or the caller's (rtgo_bind_output)
-    struct Output {
-        DeviceArray<float4> own_accum;
-        DeviceArray<uchar4> own_image;
-        float4* accum = nullptr;           // what launches write
-        uchar4* image = nullptr;
-        size_t pixels = 0;
-    } out;
-    // ---- the whitted triangle path: the scene, and what outlives it (lights, tile-queue heads, miss colour)
-    WhittedMesh wm;
-    DeviceArray<whitted::PointLight> w_lights;
-    int w_n_lights = 0;
-    DeviceArray<unsigned int> w_tile_counters;   // two sets of tile-queue heads: a launch counts on one and zeroes the other
-    int w_launch_parity = 0;
-    v3 w_miss{0, 0, 0};
-    std::string err;
-};
-
-static_assert(sizeof(rtgo_pbr) == sizeof(whitted::Pbr) && sizeof(rtgo_point_light) == sizeof(whitted::PointLight) && sizeof(rtgo_point_light) == 32,
-              "whitted records");
-static_assert(RTGO_MAX_TRIANGLES == whitted::kMaxTriangles, "limits");
-static_assert(RTGO_WHITTED_MAX_MESHES == whitted::kMaxMeshes && RTGO_WHITTED_MAX_INSTANCES == whitted::kMaxInstances, "instance limits");
-static_assert(RTGO_WHITTED_MAX_MESH_TRIANGLES == whitted::kBigMaxMeshTriangles && RTGO_WHITTED_MAX_SCENE_TRIANGLES == whitted::kBigMaxSceneTriangles,
-              "clustered mesh limits");
-static_assert(sizeof(rtgo_whitted_instance) == 56 && sizeof(whitted::InstWalk) == 64 && sizeof(whitted::InstShade) == 112, "instance records");
-
-static std::string g_create_error;
 
 // dynamic LDS of build_kernel: the fast walk's tree while it is built and rotated (2 * kMaxPrims nodes x (box 24 B + two links + parent))
 static constexpr size_t kBuildDynLds = (size_t)2 * kMaxPrims * (6 * sizeof(float) + 3 * sizeof(int));
@@ -285,59 +59,6 @@ static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, boo
     return nullptr;
 }
 
-static int fail(rtgo_ctx* c, int code, const std::string& msg)
-{
-    if (c) c->err = msg;
-    else g_create_error = msg;
-    return code;
-}
-
-#define RTGO_HIP(ctx, call)                                                                                       \
-    do {                                                                                                          \
-        hipError_t e_ = (call);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return fail(ctx, RTGO_E_HIP_BASE + (int)e_,                                                           \
-                        std::string(#call) + " failed: " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
-// read back the oldest `count` pending event pairs (blocks until their stop events have completed)
-static int harvest_events(rtgo_ctx* c, int count)
-{
-    while (count-- > 0 && c->ev_pending > 0) {
-        const int slot = (c->ev_head - c->ev_pending + 2 * rtgo_ctx::kEvRing) % rtgo_ctx::kEvRing;
-        RTGO_HIP(c, hipEventSynchronize(c->ev_stop[slot]));
-        float ms = 0.0f;
-        RTGO_HIP(c, hipEventElapsedTime(&ms, c->ev_start[slot], c->ev_stop[slot]));
-        c->last_ms = ms;
-        c->total_ms += ms;
-        c->ev_pending--;
-        if (c->ev_tag[slot] != 0) {
-            float& best = c->trial.best[(c->ev_tag[slot] - 1) & 7];
-            best = ms < best ? ms : best;
-            c->trial.done++;
-            c->ev_tag[slot] = 0;
-        }
-    }
-    return RTGO_OK;
-}
-
-// One launch of either path between the two events of the ring's next slot on the context's stream (the oldest pair read back
-// first when the ring is full), counted.  `launch` enqueues the kernel and returns an RTGO code; `slot`: the ring slot it took.
-template <class Launch>
-static int timed_launch(rtgo_ctx* c, int& slot, Launch&& launch)
-{
-    if (c->ev_pending == rtgo_ctx::kEvRing)
-        if (const int rc = harvest_events(c, 1)) return rc;
-    slot = c->ev_head;
-    RTGO_HIP(c, hipEventRecord(c->ev_start[slot], c->stream));
-    if (const int rc = launch()) return rc;
-    RTGO_HIP(c, hipEventRecord(c->ev_stop[slot], c->stream));
-    c->ev_head = (c->ev_head + 1) % rtgo_ctx::kEvRing;
-    c->ev_pending++;
-    c->launches++;
-    return RTGO_OK;
-}
-
 // window rows below y that this rank owns under the band interleave
 static uint32_t owned_rows_below(uint32_t y, uint32_t band_h, uint32_t n_ranks, uint32_t rank)
 {
@@ -362,29 +83,7 @@ static inline uint32_t passes_of(uint32_t nn) { return (nn + (uint32_t)kSamplesP
 static constexpr float kGuardReach = 500.0f;
 static constexpr float kGuardQuadric = 8000.0f;
 
-// Environment knobs for tests and experiments (no result depends on them; DESIGN.md, "Knobs"): each rtgo_set_scene and rtgo_launch
-// reads them afresh into a Knobs
-static float env_float(const char* name, float dflt)
-{
-    const char* v = std::getenv(name);
-    return v ? (float)std::atof(v) : dflt;
-}
-static unsigned int env_uint(const char* name, unsigned int dflt)
-{
-    const char* v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    const long k = std::strtol(v, nullptr, 10);
-    return k > 0 ? (unsigned int)k : dflt;
-}
-// RTGO_WHITTED_MODE (test and experiment knob): 0 / 1 / 2 = at most that much of the whitted structure in LDS (kAllInL2 / kRecordsInLds /
-// kAllInLds); unset, empty or negative: kAllInLds, above 2: 2.  (env_uint cannot carry it: 0 is a value here.)
-static int env_whitted_mode()
-{
-    const char* v = std::getenv("RTGO_WHITTED_MODE");
-    if (!v || !*v) return whitted::kAllInLds;
-    const long k = std::strtol(v, nullptr, 10);
-    return k < 0 ? whitted::kAllInLds : (int)std::min<long>(k, whitted::kAllInLds);
-}
+// The environment knobs of a scene set-up or a launch (rtgo_ctx.h has the readers): each rtgo_set_scene and rtgo_launch reads them afresh
 struct Knobs {
     bool debug = std::getenv("RTGO_DEBUG") != nullptr;              // a line per scene and launch on stderr
     bool no_frames = std::getenv("RTGO_NO_FRAMES") != nullptr;      // flat scenes compute N and the sampling tangent per hit
@@ -573,12 +272,12 @@ static int build_spans(rtgo_ctx* c, int whitted, std::vector<BuildSpan>& out)
         const WhittedMesh& wm = c->wm;
         if (wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_debug_build_digest: no mesh");
         if (!wm.instanced) {
-            span("recs").device(wm.recs.get(), (size_t)4 * wm.n_recs);
-            span("qrecs").device(wm.qrecs.get(), (size_t)2 * wm.n_recs);
+            span("recs").device(wm.recs.get(), (size_t)4 * wm.meta.n_recs);
+            span("qrecs").device(wm.qrecs.get(), (size_t)2 * wm.meta.n_recs);
             span("tris").device(wm.tris.get(), (size_t)3 * wm.triangles);
             span("tidx").device(wm.tidx.get(), (size_t)wm.triangles);
-            span("grid").host(&wm.grid_lo, sizeof wm.grid_lo).host(&wm.grid_step, sizeof wm.grid_step);
-            const int ints[] = {wm.n_recs, wm.walk_depth};
+            span("grid").host(&wm.meta.grid_lo, sizeof wm.meta.grid_lo).host(&wm.meta.grid_step, sizeof wm.meta.grid_step);
+            const int ints[] = {wm.meta.n_recs, wm.walk_depth};
             span("counts").host(ints, sizeof ints);
             const int sizes[] = {wm.triangles, wm.n_vertices};
             span("meta").host(&wm.meta, sizeof wm.meta).host(sizes, sizeof sizes);
@@ -1050,15 +749,9 @@ static int emitter_cert(rtgo_ctx* c, const rtgo_prim* prims, uint32_t n, Analyti
         // M = the inverse of the rows' 3x3 part: world = M (obj - w)
         const double a[3][3] = {{R[0].x, R[0].y, R[0].z}, {R[1].x, R[1].y, R[1].z}, {R[2].x, R[2].y, R[2].z}};
         const double w[3] = {R[0].w, R[1].w, R[2].w};
-        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
-                           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-        if (!(std::fabs(det) > 1e-300) || !std::isfinite(det)) return RTGO_OK;
         double M[3][3];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const int i1 = (j + 1) % 3, i2 = (j + 2) % 3, j1 = (i + 1) % 3, j2 = (i + 2) % 3;
-                M[i][j] = (a[i1][j1] * a[i2][j2] - a[i1][j2] * a[i2][j1]) / det;
-            }
+        const double det = mat3_det_inverse(a, M);
+        if (!(std::fabs(det) > 1e-300) || !std::isfinite(det)) return RTGO_OK;
         const double n1e = std::max(n1(R[0]), std::max(n1(R[1]), n1(R[2])));
         const double we = std::max(std::fabs(w[0]), std::max(std::fabs(w[1]), std::fabs(w[2]))) + 1.0;
         for (int g = 0; g < 6; ++g) {
@@ -1094,9 +787,8 @@ static int check_prims(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aab
         bool finite = std::isfinite(q.specularity);
         for (int k = 0; k < 16; ++k) finite = finite && std::isfinite(q.model[k]);
         for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(q.kd[k]) && std::isfinite(q.kr[k]) && std::isfinite(q.Le[k]);
-        const double a = q.model[0], b = q.model[1], d3 = q.model[2], e = q.model[4], g = q.model[5], h = q.model[6], k2 = q.model[8],
-                     l = q.model[9], m = q.model[10];
-        const double det = a * (g * m - h * l) - b * (e * m - h * k2) + d3 * (e * l - g * k2);
+        const double a[3][3] = {{q.model[0], q.model[1], q.model[2]}, {q.model[4], q.model[5], q.model[6]}, {q.model[8], q.model[9], q.model[10]}};
+        const double det = mat3_det_inverse(a);
         if (!finite || !std::isfinite(det) || std::fabs(det) < 1e-30)
             return fail(c, RTGO_E_INVALID, what + ": primitive " + std::to_string(i) + " has a non-finite or singular model matrix / material");
         if (aabbs) {
@@ -1208,7 +900,6 @@ int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* a
     drop_scene(c);
     AnalyticScene& sc = c->scene;
     const int ni = (int)n, n_int = ni > 1 ? ni - 1 : 1;
-    const int nb = (ni + whitted::kRadixTile - 1) / whitted::kRadixTile;
     LargeScratch ls;
     RTGO_HIP(c, sc.d_prims_in.alloc(n));
     RTGO_HIP(c, sc.d_aabb.alloc((size_t)n * 6));
@@ -1216,7 +907,7 @@ int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* a
     RTGO_HIP(c, sc.d_prims.alloc((size_t)n * 6));
     RTGO_HIP(c, ls.keys.alloc(n));
     RTGO_HIP(c, ls.keys_alt.alloc(n));
-    RTGO_HIP(c, ls.hist.alloc((size_t)256 * nb));
+    RTGO_HIP(c, ls.hist.alloc((size_t)256 * ((ni + whitted::kRadixTile - 1) / whitted::kRadixTile)));
     RTGO_HIP(c, ls.left.alloc(n_int));
     RTGO_HIP(c, ls.right.alloc(n_int));
     RTGO_HIP(c, ls.parent.alloc(2 * (size_t)n - 1));
@@ -1230,18 +921,11 @@ int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* a
     hipLaunchKernelGGL(large_prep_kernel, g_prims, dim3(256), 0, c->stream, (const PrimIn*)sc.d_prims_in.get(), sc.d_aabb.get(), aabbs ? 1 : 0, ni, sc.d_prims.get());
     hipLaunchKernelGGL(whitted::big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)sc.d_aabb.get(), ni, ls.small.get());
     hipLaunchKernelGGL(large_keys_kernel, g_prims, dim3(256), 0, c->stream, (const float*)sc.d_aabb.get(), ni, (const float*)ls.small.get(), ls.keys.get());
-    unsigned long long *src = ls.keys.get(), *dst = ls.keys_alt.get();
-    for (int shift = 32; shift < 64; shift += 8) {
-        hipLaunchKernelGGL(whitted::radix_count_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift, ls.hist.get());
-        hipLaunchKernelGGL(whitted::radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, ls.hist.get(), 256 * nb);
-        hipLaunchKernelGGL(whitted::radix_scatter_kernel, dim3(nb), dim3(whitted::kRadixThreads), 0, c->stream, (const unsigned long long*)src, ni, shift,
-                           (const unsigned int*)ls.hist.get(), dst);
-        std::swap(src, dst);
-    }
+    const unsigned long long* src = radix_sort_keys(c, ls.keys.get(), ls.keys_alt.get(), ls.hist.get(), ni);
     // hierarchy, depths and leaves
     int* d_max_depth = reinterpret_cast<int*>(ls.small.get() + 6);
-    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, ls.left.get(), ls.right.get(), ls.parent.get());
-    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, (const unsigned long long*)src, ni, (const float*)sc.d_aabb.get(),
+    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, src, ni, ls.left.get(), ls.right.get(), ls.parent.get());
+    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, src, ni, (const float*)sc.d_aabb.get(),
                        (const int*)ls.parent.get(), ls.depth.get(), sc.d_nodes.get(), d_max_depth);
     RTGO_HIP(c, hipGetLastError());
     int depth = 0;
@@ -1951,86 +1635,13 @@ int rtgo_assemble_bands(rtgo_ctx* c, void* hip_stream, const void* d_gathered, v
     return RTGO_OK;
 }
 
-// the two sets of tile-queue heads of the whitted launches (allocated once, zero)
-static int whitted_tile_heads(rtgo_ctx* c)
-{
-    if (!c->w_tile_counters.get()) {
-        const size_t heads = 2 * (size_t)whitted::kTileHeads * whitted::kTileHeadStride;
-        RTGO_HIP(c, c->w_tile_counters.alloc(heads));
-        RTGO_HIP(c, hipMemsetAsync(c->w_tile_counters.get(), 0, heads * sizeof(unsigned int), c->stream));
-        RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    return RTGO_OK;
-}
+}  // extern "C"
 
-// One structure of the whitted path, built on the device over n triangles (positions, indices: device memory): build_kernel's Morton
-// hierarchy, its records rebuilt top-down with the surface-area heuristic (sah_kernel) when the leaves fit its LDS, and the Morton
-// records again when the surface-area tree comes out deeper than the walk's stack.  nodes: (2n - 1) x 2 float4; scratch: 38 n + 16
-// ints; recs: n x 4 float4; tris: n x 3 float4; qrecs: n x 2 uint4; tidx: n uint2.  Synchronous.
-using whitted::WhittedBuildMeta;
-static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int* indices, int n, float4* nodes, int* scratch, float4* recs, float4* tris,
-                         uint4* qrecs, uint2* tidx, WhittedBuildMeta& m, const char* what)
-{
-    int* parent = scratch;   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
-    int* visit = parent + (2 * n - 1);
-    int* first_of = visit + n;
-    int* count_of = first_of + n;
-    int* rec_of = count_of + n;
-    WhittedBuildMeta* meta = reinterpret_cast<WhittedBuildMeta*>(rec_of + n);
-    int* sah_scratch = rec_of + n + 16;
-    const size_t keys_lds = (size_t)whitted::kMaxTriangles * sizeof(unsigned long long);
-    hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, nodes,
-                       parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, meta);
-    RTGO_HIP(c, hipGetLastError());
-    // the records over the same leaves, rebuilt top-down with the surface-area heuristic (leaf boxes, links, order arrays in LDS: 33 B per
-    // triangle, so meshes beyond ~4650 triangles keep the Morton records)
-    const size_t sah_lds = (size_t)n * (6 * sizeof(float) + sizeof(int) + 2 * sizeof(short) + 1) + 16;
-    const bool sah = !std::getenv("RTGO_WHITTED_NO_SAH") && sah_lds <= 150 * 1024;
-    if (sah) {
-        hipLaunchKernelGGL(whitted::sah_kernel, dim3(1), dim3(whitted::kBuildThreads), sah_lds, c->stream, n, (const float4*)nodes, (const int*)parent,
-                           (const int*)first_of, (const int*)count_of, sah_scratch, recs, qrecs, meta);
-        RTGO_HIP(c, hipGetLastError());
-    }
-    std::memset(&m, 0, sizeof m);
-    RTGO_HIP(c, hipMemcpyAsync(&m, meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (m.walk_depth > whitted::kMaxWalkDepth && sah) {
-        // the surface-area tree came out deeper than the walk's stack (it has no depth bound of its own): back to the Morton records,
-        // whose depth is bounded by the code length
-        hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, nodes,
-                           parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, meta);
-        RTGO_HIP(c, hipGetLastError());
-        RTGO_HIP(c, hipMemcpyAsync(&m, meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
-        RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    if (m.depth > 2 * whitted::kStack)
-        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": triangle LBVH depth " + std::to_string(m.depth) + " exceeds what the build handles (" +
-                                               std::to_string(2 * whitted::kStack) + ")");
-    if (m.walk_depth > whitted::kMaxWalkDepth)
-        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the walk needs " + std::to_string(m.walk_depth) + " stack entries (limit " +
-                                               std::to_string(whitted::kMaxWalkDepth) + ")");
-    return RTGO_OK;
-}
+// ---- the whitted triangle path: what its entry points call is in rtgo_whitted_host.h.  (Included here, below rtgo_create: the compiler
+// emits the kernel instantiations in the order the host code first names them, and rtgo_create's lists set that order.)
+#include "rtgo_whitted_host.h"
 
-// The checks every mesh of the whitted path passes (rtgo_whitted_set_mesh, rtgo_whitted_set_scene; `at` names it in the messages): vertex
-// indices inside the vertex array, finite vertex data, material indices inside the table.  Also finds the mesh's largest material index.
-static int whitted_check_mesh(rtgo_ctx* c, const rtgo_whitted_mesh& q, uint32_t n_materials, const std::string& at, uint32_t& max_material)
-{
-    for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
-        if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
-    for (uint32_t i = 0; i < 3 * q.n_vertices; ++i)
-        if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
-    if (q.texcoords)
-        for (uint32_t i = 0; i < 2 * q.n_vertices; ++i)
-            if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + ": non-finite texture coordinate");
-    max_material = 0;
-    if (q.material_of_triangle)
-        for (uint32_t i = 0; i < q.n_triangles; ++i) {
-            if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material index beyond the material array");
-            max_material = std::max(max_material, q.material_of_triangle[i]);
-        }
-    return RTGO_OK;
-}
+extern "C" {
 
 int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* normals, uint32_t n_vertices, const uint32_t* indices,
                           const uint32_t* material_of_triangle, uint32_t n_triangles, const rtgo_pbr* materials, uint32_t n_materials)
@@ -2040,433 +1651,45 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_mesh: triangle count must be in [1, " + std::to_string(RTGO_MAX_TRIANGLES) + "], vertices and materials non-empty");
     const rtgo_whitted_mesh mesh = {positions, normals, nullptr, n_vertices, indices, material_of_triangle, n_triangles};
     uint32_t max_material;
-    const int rc0 = whitted_check_mesh(c, mesh, n_materials, "rtgo_whitted_set_mesh", max_material);
-    if (rc0) return rc0;
+    if (const int rc = whitted_check_mesh(c, mesh, n_materials, "rtgo_whitted_set_mesh", max_material)) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    c->wm = WhittedMesh();
-    WhittedMesh& wm = c->wm;
-    RTGO_HIP(c, wm.positions.upload(positions, (size_t)n_vertices * 3, c->stream));
-    if (normals) RTGO_HIP(c, wm.normals.upload(normals, (size_t)n_vertices * 3, c->stream));
-    RTGO_HIP(c, wm.indices.upload(indices, (size_t)n_triangles * 3, c->stream));
-    if (material_of_triangle) RTGO_HIP(c, wm.tri_material.upload(material_of_triangle, n_triangles, c->stream));
-    RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
-    RTGO_HIP(c, wm.nodes.alloc((size_t)(2 * n_triangles - 1) * 2));
-    RTGO_HIP(c, wm.recs.alloc((size_t)n_triangles * 4));
-    RTGO_HIP(c, wm.tris.alloc((size_t)n_triangles * 3));
-    RTGO_HIP(c, wm.qrecs.alloc((size_t)n_triangles * 2));
-    RTGO_HIP(c, wm.tidx.alloc(n_triangles));
-    RTGO_HIP(c, wm.scratch.alloc((size_t)(6 * n_triangles + 16 + 32 * n_triangles)));   // parent [2n-1], visit, first, count, record [n each], meta, sah_kernel's 32 n
-    WhittedBuildMeta m;
-    const int rc = whitted_build(c, wm.positions.get(), wm.indices.get(), (int)n_triangles, wm.nodes.get(), wm.scratch.get(), wm.recs.get(), wm.tris.get(),
-                                 wm.qrecs.get(), wm.tidx.get(), m, "rtgo_whitted_set_mesh");
-    if (rc) return rc;
-    wm.n_recs = m.n_recs;
-    wm.meta = m;
-    wm.n_vertices = (int)n_vertices;
-    wm.grid_lo = m.grid_lo;
-    wm.grid_step = m.grid_step;
-    wm.walk_depth = m.walk_depth < 1 ? 1 : m.walk_depth;
-    const int rc2 = whitted_tile_heads(c);
-    if (rc2) return rc2;
-    wm.triangles = (int)n_triangles;
-    wm.n_materials = (int)n_materials;
+    c->wm = WhittedMesh();   // (the old scene goes before the new one is allocated; a failure from here on leaves none)
+    WhittedMesh next;
+    if (const int rc = whitted_build_single(c, next, mesh, materials, n_materials, "rtgo_whitted_set_mesh")) return rc;
+    if (const int rc = whitted_tile_heads(c)) return rc;
+    next.triangles = (int)n_triangles;
+    c->wm = std::move(next);
     return RTGO_OK;
 }
 
-// ---- instanced scenes ----------------------------------------------------------------------------------------------------
-// The instances' side, checked and laid out on the host before anything on the device changes: per instance its InstShade record
-// (o2w as given, W2O = its inverse in double, rounded once) and its world box (the 8 corners of its mesh's box through o2w in double,
-// rounded outwards), which the top-level build takes as the degenerate triangle (lo, hi, lo).
-static int whitted_prepare_instances(rtgo_ctx* c, const std::vector<WhittedMeshInfo>& meshes, uint32_t n_materials, const rtgo_whitted_instance* inst,
-                                     uint32_t n, std::vector<whitted::InstShade>& shade, std::vector<float>& box_pos, const char* what)
-{
-    const std::string w(what);
-    if (!inst) return fail(c, RTGO_E_INVALID, w + ": NULL instance array");
-    if (n == 0 || n > RTGO_WHITTED_MAX_INSTANCES)
-        return fail(c, RTGO_E_UNSUPPORTED, w + ": instance count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_INSTANCES) + "]");
-    shade.assign(n, whitted::InstShade{});
-    box_pos.assign((size_t)6 * n, 0.0f);
-    for (uint32_t i = 0; i < n; ++i) {
-        const rtgo_whitted_instance& q = inst[i];
-        const std::string at = w + ": instance " + std::to_string(i);
-        if (q.mesh >= meshes.size()) return fail(c, RTGO_E_INVALID, at + " names a mesh beyond the meshes array");
-        const WhittedMeshInfo& mi = meshes[q.mesh];
-        if ((uint64_t)q.material_offset + mi.max_material >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material offset + material index beyond the material array");
-        bool finite = true;
-        for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(q.transform[k]);
-        // the walk takes rays to object space through the inverse: the transform must be finite and invertible (the analytic path's
-        // test of a model matrix, rtgo_set_scene)
-        double A[3][4];
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 4; ++k) A[r][k] = q.transform[4 * r + k];
-        const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                           A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-        if (!finite || !std::isfinite(det) || std::fabs(det) < 1e-30) return fail(c, RTGO_E_INVALID, at + " has a non-finite or singular transform");
-        double B[3][4];   // the inverse: adj(A) / det, then -A^-1 t
-        B[0][0] = (A[1][1] * A[2][2] - A[1][2] * A[2][1]) / det;
-        B[0][1] = (A[0][2] * A[2][1] - A[0][1] * A[2][2]) / det;
-        B[0][2] = (A[0][1] * A[1][2] - A[0][2] * A[1][1]) / det;
-        B[1][0] = (A[1][2] * A[2][0] - A[1][0] * A[2][2]) / det;
-        B[1][1] = (A[0][0] * A[2][2] - A[0][2] * A[2][0]) / det;
-        B[1][2] = (A[0][2] * A[1][0] - A[0][0] * A[1][2]) / det;
-        B[2][0] = (A[1][0] * A[2][1] - A[1][1] * A[2][0]) / det;
-        B[2][1] = (A[0][1] * A[2][0] - A[0][0] * A[2][1]) / det;
-        B[2][2] = (A[0][0] * A[1][1] - A[0][1] * A[1][0]) / det;
-        for (int r = 0; r < 3; ++r) B[r][3] = -(B[r][0] * A[0][3] + B[r][1] * A[1][3] + B[r][2] * A[2][3]);
-        whitted::InstShade& sh = shade[i];
-        float* o2w = &sh.o2w[0].x;
-        float* w2o = &sh.w2o[0].x;
-        for (int k = 0; k < 12; ++k) {
-            o2w[k] = q.transform[k];
-            w2o[k] = (float)B[k / 4][k % 4];
-            if (!std::isfinite(w2o[k])) return fail(c, RTGO_E_INVALID, at + " has a non-finite or singular transform");
-        }
-        sh.material_offset = (int)q.material_offset;
-        sh.vert_base = mi.vert_base;
-        sh.tri_base = mi.tri_base;
-        sh.flags = mi.flags;
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int corner = 0; corner < 8; ++corner) {
-            const double x = (corner & 1) ? mi.hi[0] : mi.lo[0], y = (corner & 2) ? mi.hi[1] : mi.lo[1], z = (corner & 4) ? mi.hi[2] : mi.lo[2];
-            for (int r = 0; r < 3; ++r) {
-                const double v = A[r][0] * x + A[r][1] * y + A[r][2] * z + A[r][3];
-                lo[r] = std::fmin(lo[r], v);
-                hi[r] = std::fmax(hi[r], v);
-            }
-        }
-        for (int r = 0; r < 3; ++r) {
-            float l = (float)lo[r], h = (float)hi[r];
-            if ((double)l > lo[r]) l = std::nextafter(l, -INFINITY);
-            if ((double)h < hi[r]) h = std::nextafter(h, INFINITY);
-            if (!std::isfinite(l) || !std::isfinite(h)) return fail(c, RTGO_E_INVALID, at + " places its mesh beyond the float range");
-            box_pos[6 * i + r] = l;
-            box_pos[6 * i + 3 + r] = h;
-        }
-    }
-    return RTGO_OK;
-}
-
-// The index array that hands n boxes to whitted_build (box k: "vertices" 2k = lo, 2k + 1 = hi) as the degenerate triangles (lo, hi, lo),
-// whose bounds are the boxes: the top level's and the mid levels' builds
-static std::vector<unsigned int> whitted_box_indices(int n)
-{
-    std::vector<unsigned int> idx((size_t)3 * n);
-    for (int k = 0; k < n; ++k) {
-        idx[3 * k + 0] = 2 * k;
-        idx[3 * k + 1] = 2 * k + 1;
-        idx[3 * k + 2] = 2 * k;
-    }
-    return idx;
-}
-
-// the top level over prepared instances: build_kernel + sah_kernel over the instance boxes, the InstWalk records in leaf order, and the
-// stack both levels need.  Built aside: replaces the context's top level only once all of it succeeded.
-static int whitted_build_top(rtgo_ctx* c, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos, const rtgo_whitted_instance* inst,
-                             const char* what)
-{
-    const int n = (int)shade.size();
-    const std::vector<unsigned int> box_idx = whitted_box_indices(n);
-    DeviceArray<float> d_pos;
-    DeviceArray<unsigned int> d_idx;
-    DeviceArray<float4> d_nodes, d_tris;
-    DeviceArray<int> d_scratch;
-    DeviceArray<uint4> d_qrecs;
-    DeviceArray<uint2> d_tidx;
-    WhittedTop top;
-    RTGO_HIP(c, d_pos.upload(box_pos.data(), box_pos.size(), c->stream));
-    RTGO_HIP(c, d_idx.upload(box_idx.data(), box_idx.size(), c->stream));
-    RTGO_HIP(c, d_nodes.alloc((size_t)(2 * n - 1) * 2));
-    RTGO_HIP(c, top.recs.alloc((size_t)n * 4));
-    RTGO_HIP(c, d_tris.alloc((size_t)n * 3));
-    RTGO_HIP(c, d_qrecs.alloc((size_t)n * 2));
-    RTGO_HIP(c, d_tidx.alloc(n));
-    RTGO_HIP(c, d_scratch.alloc((size_t)(38 * n + 16)));
-    WhittedBuildMeta m;
-    const int rc = whitted_build(c, d_pos.get(), d_idx.get(), n, d_nodes.get(), d_scratch.get(), top.recs.get(), d_tris.get(), d_qrecs.get(), d_tidx.get(), m, what);
-    if (rc) return rc;
-    // leaf order: build_kernel's Morton-ordered "triangles" carry the instance index in .w of their first corner
-    std::vector<float4> order((size_t)3 * n);
-    RTGO_HIP(c, hipMemcpyAsync(order.data(), d_tris.get(), order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    const int top_depth = m.n_recs > 0 ? m.walk_depth : 0;
-    const int depth = top_depth + c->wm.mesh_depth;
-    if (depth > whitted::kMaxInstWalkDepth)
-        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
-                                               std::to_string(whitted::kMaxInstWalkDepth) + ")");
-    std::vector<whitted::InstWalk> walk((size_t)n);
-    for (int pos = 0; pos < n; ++pos) {
-        int i;
-        std::memcpy(&i, &order[3 * pos].w, sizeof i);
-        const WhittedMeshInfo& mi = c->wm.meshes[inst[i].mesh];
-        walk[pos] = whitted::InstWalk{{shade[i].w2o[0], shade[i].w2o[1], shade[i].w2o[2]}, mi.rec_base, mi.tri_base, mi.root, i};
-    }
-    RTGO_HIP(c, top.inst.upload(walk.data(), walk.size(), c->stream));
-    RTGO_HIP(c, top.shade.upload(shade.data(), shade.size(), c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    top.n_recs = m.n_recs;
-    top.meta = m;
-    top.n_instances = n;
-    c->wm.top = std::move(top);
-    c->wm.walk_depth = depth < 1 ? 1 : depth;
-    return RTGO_OK;
-}
-
-// Device scratch of the clustered builds of one rtgo_whitted_set_scene, sized for its largest clustered mesh (freed on every return).
-struct WhittedBigScratch {
-    DeviceArray<unsigned long long> keys, keys_alt;
-    DeviceArray<unsigned int> hist, cidx, mid_idx;
-    DeviceArray<float> partial, bounds, mid_pos;
-    DeviceArray<int> crec;
-    DeviceArray<float4> mid_tris;
-    DeviceArray<uint4> mid_qrecs;
-    DeviceArray<uint2> mid_tidx;
-};
-
-// One clustered mesh (n > kMaxTriangles triangles; rtgo_whitted_big.h), in its slices of the context's arrays: Morton order over the
-// whole mesh on the device, clusters of consecutive sorted triangles each built by whitted_build (tris[].w then remapped to the mesh's
-// own indices), and a mid level over the clusters' boxes whose records take the first ncl - 1 record slots of the mesh (the clusters
-// follow: a mesh of n triangles has at most n slots, and a cluster of m triangles fewer than m records).  Appends the mesh's clusters,
-// in the mid level's leaf order, to `table`; sets mi.root, mi.depth, and widens mi.lo / hi over every box the walk can reach from the
-// mesh's root, so the instance boxes built from it contain them by construction.  Synchronous.
-static int whitted_build_clustered(rtgo_ctx* c, WhittedMeshInfo& mi, int n, WhittedBigScratch& bs, std::vector<int4>& table, const char* what)
-{
-    using namespace whitted;
-    const int ncl = (n + kClusterTris - 1) / kClusterTris;
-    WhittedMesh& wm = c->wm;
-    const float* positions = wm.positions.get() + 3 * (size_t)mi.vert_base;
-    const unsigned int* indices = wm.indices.get() + 3 * (size_t)mi.tri_base;
-    // Morton keys over the mesh's bounds, sorted by four stable passes over the code's bytes
-    const int nbb = std::min(1024, (n + 1023) / 1024);
-    hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, positions, indices, n, bs.partial.get());
-    hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)bs.partial.get(), nbb, bs.bounds.get());
-    hipLaunchKernelGGL(big_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, positions, indices, n, (const float*)bs.bounds.get(), bs.keys.get());
-    const int nb = (n + kRadixTile - 1) / kRadixTile;
-    unsigned long long *src = bs.keys.get(), *dst = bs.keys_alt.get();
-    for (int shift = 32; shift < 64; shift += 8) {
-        hipLaunchKernelGGL(radix_count_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift, bs.hist.get());
-        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, c->stream, bs.hist.get(), 256 * nb);
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(kRadixThreads), 0, c->stream, (const unsigned long long*)src, n, shift,
-                           (const unsigned int*)bs.hist.get(), dst);
-        std::swap(src, dst);
-    }
-    const unsigned long long* sorted = src;   // (four passes: back in bs.keys)
-    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, sorted, n, indices, bs.cidx.get());
-    RTGO_HIP(c, hipGetLastError());
-    // the clusters
-    std::vector<int> crec(ncl), croot(ncl);
-    int rec = mi.rec_base + ncl - 1, cdepth = 0;
-    for (int k = 0; k < ncl; ++k) {
-        const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
-        WhittedBuildMeta m;
-        const int rc = whitted_build(c, positions, bs.cidx.get() + 3 * (size_t)s, nc, wm.nodes.get(), wm.scratch.get(), wm.recs.get() + 4 * (size_t)rec,
-                                     wm.tris.get() + 3 * ((size_t)mi.tri_base + s), wm.qrecs.get() + 2 * ((size_t)mi.tri_base + s), wm.tidx.get() + mi.tri_base + s, m,
-                                     what);
-        if (rc) return rc;
-        mi.built.push_back({rec, m.n_recs, mi.tri_base + s, m});
-        crec[k] = rec;
-        croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
-        cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
-        rec += m.n_recs;
-    }
-    hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, wm.tris.get() + 3 * (size_t)mi.tri_base, sorted, n, ncl);
-    RTGO_HIP(c, hipGetLastError());
-    // the mid level over the clusters' boxes
-    const std::vector<unsigned int> box_idx = whitted_box_indices(ncl);
-    RTGO_HIP(c, hipMemcpyAsync(bs.crec.get(), crec.data(), ncl * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    RTGO_HIP(c, hipMemcpyAsync(bs.mid_idx.get(), box_idx.data(), box_idx.size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)wm.recs.get(), (const int*)bs.crec.get(), ncl,
-                       bs.mid_pos.get());
-    RTGO_HIP(c, hipGetLastError());
-    WhittedBuildMeta m;
-    const int rc = whitted_build(c, bs.mid_pos.get(), bs.mid_idx.get(), ncl, wm.nodes.get(), wm.scratch.get(), wm.recs.get() + 4 * (size_t)mi.rec_base,
-                                 bs.mid_tris.get(), bs.mid_qrecs.get(), bs.mid_tidx.get(), m, what);
-    if (rc) return rc;
-    mi.built.push_back({mi.rec_base, m.n_recs, -1, m});
-    // leaf order: the mid level's Morton-ordered "triangles" carry the cluster in .w of their first corner
-    std::vector<float4> order((size_t)3 * ncl), root_rec(4);
-    std::vector<float> boxes((size_t)6 * ncl);
-    RTGO_HIP(c, hipMemcpyAsync(order.data(), bs.mid_tris.get(), order.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.mid_pos.get(), boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (m.n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), wm.recs.get() + 4 * (size_t)mi.rec_base, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    const int tbase = (int)table.size();
-    for (int pos = 0; pos < ncl; ++pos) {
-        int k;
-        std::memcpy(&k, &order[3 * pos].w, sizeof k);
-        table.push_back(make_int4(crec[k], mi.tri_base + cluster_start(n, ncl, k), croot[k], 0));
-    }
-    // what the walk can reach first below an instance: the mid root's two child boxes, or (a mid level of one leaf) the clusters' root
-    // records, whose boxes are the ones big_cluster_boxes_kernel took
-    auto widen = [&](float l0, float l1, float l2, float h0, float h1, float h2) {
-        const float l[3] = {l0, l1, l2}, h[3] = {h0, h1, h2};
-        for (int a = 0; a < 3; ++a) {
-            mi.lo[a] = std::fmin(mi.lo[a], l[a]);
-            mi.hi[a] = std::fmax(mi.hi[a], h[a]);
-        }
-    };
-    if (m.n_recs > 0) {
-        widen(root_rec[0].x, root_rec[0].y, root_rec[0].z, root_rec[1].x, root_rec[1].y, root_rec[1].z);
-        widen(root_rec[2].x, root_rec[2].y, root_rec[2].z, root_rec[3].x, root_rec[3].y, root_rec[3].z);
-    }
-    for (int k = 0; k < ncl; ++k) widen(boxes[6 * k + 0], boxes[6 * k + 1], boxes[6 * k + 2], boxes[6 * k + 3], boxes[6 * k + 4], boxes[6 * k + 5]);
-    mi.root = 1 + ((tbase << 3) | (m.n_recs > 0 ? kMidHasRecords : ncl - 1));
-    mi.depth = (m.n_recs > 0 ? m.walk_depth : 0) + cdepth;
-    return RTGO_OK;
-}
-
+// (rtgo_whitted_host.h's stages over a scene built aside: a refusal by the host checks leaves the old scene; once that is dropped, a failure leaves none)
 int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances, uint32_t n_instances,
                            const rtgo_pbr* materials, uint32_t n_materials)
 {
+    const char* what = "rtgo_whitted_set_scene";
     if (!c || !meshes || !instances || !materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_scene: NULL argument");
     if (n_meshes == 0 || n_meshes > RTGO_WHITTED_MAX_MESHES || n_materials == 0)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_scene: mesh count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESHES) + "], materials non-empty");
-    // every mesh as rtgo_whitted_set_mesh checks it, and where it will sit in the arrays
-    std::vector<WhittedMeshInfo> info(n_meshes);
-    size_t n_vert = 0, n_tri = 0;
-    int max_tri = 0, max_big = 0;   // the largest single build, the largest clustered mesh
-    for (uint32_t k = 0; k < n_meshes; ++k) {
-        const rtgo_whitted_mesh& q = meshes[k];
-        const std::string at = "rtgo_whitted_set_scene: mesh " + std::to_string(k);
-        if (!q.positions || !q.indices) return fail(c, RTGO_E_INVALID, at + ": NULL positions or indices");
-        if (q.n_triangles == 0 || q.n_triangles > RTGO_WHITTED_MAX_MESH_TRIANGLES || q.n_vertices == 0)
-            return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESH_TRIANGLES) + "], vertices non-empty");
-        if (n_tri + q.n_triangles > RTGO_WHITTED_MAX_SCENE_TRIANGLES)
-            return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
-        WhittedMeshInfo& mi = info[k];
-        const int rc0 = whitted_check_mesh(c, q, n_materials, at, mi.max_material);
-        if (rc0) return rc0;
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::fmin(lo[a], q.positions[3 * q.indices[i] + a]);
-                hi[a] = std::fmax(hi[a], q.positions[3 * q.indices[i] + a]);
-            }
-        // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
-        float maxext = 0.0f;
-        for (int a = 0; a < 3; ++a) maxext = std::fmax(maxext, hi[a] - lo[a]);
-        const float pad = 2.0f * (maxext * 1e-4f + 1e-6f);
-        for (int a = 0; a < 3; ++a) {
-            mi.lo[a] = lo[a] - pad;
-            mi.hi[a] = hi[a] + pad;
-        }
-        mi.rec_base = (int)n_tri;   // (a mesh of n triangles has fewer than n records)
-        mi.tri_base = (int)n_tri;
-        mi.vert_base = (int)n_vert;
-        mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
-        mi.root = 0;
-        mi.depth = 0;
-        mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
-        mi.n_tris = (int)q.n_triangles;
-        n_vert += q.n_vertices;
-        n_tri += q.n_triangles;
-        if (mi.clustered) {
-            // one workgroup's builds: clusters of at most kClusterTris triangles and a mid level of ncl boxes
-            const int ncl = ((int)q.n_triangles + whitted::kClusterTris - 1) / whitted::kClusterTris;
-            max_tri = std::max(max_tri, std::max(whitted::kClusterTris, ncl));
-            max_big = std::max(max_big, (int)q.n_triangles);
-        } else {
-            max_tri = std::max(max_tri, (int)q.n_triangles);
-        }
-    }
+    WhittedLayout lay;
     std::vector<whitted::InstShade> shade;
     std::vector<float> box_pos;
-    int rc = whitted_prepare_instances(c, info, n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_scene");
-    if (rc) return rc;
-    // the meshes back to back (indices stay relative to their mesh's vertices: each build reads its own slice)
-    std::vector<float> pos(3 * n_vert), nrm(3 * n_vert, 0.0f), uv(2 * n_vert, 0.0f);
-    std::vector<unsigned int> idx(3 * n_tri), tmat(n_tri, 0u);
-    for (uint32_t k = 0; k < n_meshes; ++k) {
-        const rtgo_whitted_mesh& q = meshes[k];
-        const WhittedMeshInfo& mi = info[k];
-        std::memcpy(&pos[3 * (size_t)mi.vert_base], q.positions, (size_t)q.n_vertices * 3 * sizeof(float));
-        if (q.normals) std::memcpy(&nrm[3 * (size_t)mi.vert_base], q.normals, (size_t)q.n_vertices * 3 * sizeof(float));
-        if (q.texcoords) std::memcpy(&uv[2 * (size_t)mi.vert_base], q.texcoords, (size_t)q.n_vertices * 2 * sizeof(float));
-        std::memcpy(&idx[3 * (size_t)mi.tri_base], q.indices, (size_t)q.n_triangles * 3 * sizeof(unsigned int));
-        if (q.material_of_triangle) std::memcpy(&tmat[mi.tri_base], q.material_of_triangle, (size_t)q.n_triangles * sizeof(unsigned int));
-    }
+    if (const int rc = whitted_layout_meshes(c, meshes, n_meshes, n_materials, lay)) return rc;
+    if (const int rc = whitted_prepare_instances(c, lay.info, n_materials, instances, n_instances, shade, box_pos, what)) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     c->wm = WhittedMesh();
-    WhittedMesh& wm = c->wm;
-    RTGO_HIP(c, wm.positions.upload(pos.data(), pos.size(), c->stream));
-    RTGO_HIP(c, wm.normals.upload(nrm.data(), nrm.size(), c->stream));
-    RTGO_HIP(c, wm.texcoords.upload(uv.data(), uv.size(), c->stream));
-    RTGO_HIP(c, wm.indices.upload(idx.data(), idx.size(), c->stream));
-    RTGO_HIP(c, wm.tri_material.upload(tmat.data(), tmat.size(), c->stream));
-    RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
-    RTGO_HIP(c, wm.nodes.alloc((size_t)(2 * max_tri - 1) * 2));
-    RTGO_HIP(c, wm.scratch.alloc((size_t)(38 * max_tri + 16)));
-    RTGO_HIP(c, wm.recs.alloc(n_tri * 4));
-    RTGO_HIP(c, wm.tris.alloc(n_tri * 3));
-    RTGO_HIP(c, wm.qrecs.alloc(n_tri * 2));
-    RTGO_HIP(c, wm.tidx.alloc(n_tri));
-    WhittedBigScratch bs;
-    if (max_big > 0) {
-        const int ncl = (max_big + whitted::kClusterTris - 1) / whitted::kClusterTris, nb = (max_big + whitted::kRadixTile - 1) / whitted::kRadixTile;
-        RTGO_HIP(c, bs.keys.alloc(max_big));
-        RTGO_HIP(c, bs.keys_alt.alloc(max_big));
-        RTGO_HIP(c, bs.hist.alloc((size_t)256 * nb));
-        RTGO_HIP(c, bs.cidx.alloc((size_t)3 * max_big));
-        RTGO_HIP(c, bs.partial.alloc((size_t)6 * 1024));
-        RTGO_HIP(c, bs.bounds.alloc(6));
-        RTGO_HIP(c, bs.crec.alloc(ncl));
-        RTGO_HIP(c, bs.mid_pos.alloc((size_t)6 * ncl));
-        RTGO_HIP(c, bs.mid_idx.alloc((size_t)3 * ncl));
-        RTGO_HIP(c, bs.mid_tris.alloc((size_t)3 * ncl));
-        RTGO_HIP(c, bs.mid_qrecs.alloc((size_t)2 * ncl));
-        RTGO_HIP(c, bs.mid_tidx.alloc(ncl));
-    }
-    std::vector<int4> table;
-    // bottom level: each mesh's own structure, as rtgo_whitted_set_mesh builds it, in its slice of the arrays (a clustered mesh: its
-    // clusters and mid level)
-    int mesh_depth = 0;
-    for (uint32_t k = 0; k < n_meshes; ++k) {
-        WhittedMeshInfo& mi = info[k];
-        const int nt = (int)meshes[k].n_triangles;
-        if (mi.clustered) {
-            rc = whitted_build_clustered(c, mi, nt, bs, table, "rtgo_whitted_set_scene");
-            if (rc) {
-                c->wm = WhittedMesh();
-                return rc;
-            }
-            mesh_depth = std::max(mesh_depth, mi.depth);
-            continue;
-        }
-        WhittedBuildMeta m;
-        rc = whitted_build(c, wm.positions.get() + 3 * (size_t)mi.vert_base, wm.indices.get() + 3 * (size_t)mi.tri_base, nt, wm.nodes.get(), wm.scratch.get(),
-                           wm.recs.get() + 4 * (size_t)mi.rec_base, wm.tris.get() + 3 * (size_t)mi.tri_base, wm.qrecs.get() + 2 * (size_t)mi.tri_base,
-                           wm.tidx.get() + mi.tri_base, m, "rtgo_whitted_set_scene");
-        if (rc) {
-            c->wm = WhittedMesh();
-            return rc;
-        }
-        mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base, m});
-        mi.root = m.n_recs > 0 ? 0 : -1 - ((nt - 1) << whitted::kLeafShift);
-        mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
-        mesh_depth = std::max(mesh_depth, mi.depth);
-    }
-    if (!table.empty()) {
-        RTGO_HIP(c, wm.clusters.upload(table.data(), table.size(), c->stream));
-        // the clustered meshes' boxes took in their mid levels' boxes: the instance boxes again from them (the checks passed above)
-        rc = whitted_prepare_instances(c, info, n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_scene");
-        if (rc) {
-            c->wm = WhittedMesh();
-            return rc;
-        }
-    }
-    wm.meshes = info;
-    wm.mesh_depth = mesh_depth;
-    wm.n_materials = (int)n_materials;
-    rc = whitted_build_top(c, shade, box_pos, instances, "rtgo_whitted_set_scene");
-    if (rc == RTGO_OK) rc = whitted_tile_heads(c);
-    if (rc) {
-        c->wm = WhittedMesh();
-        return rc;
-    }
-    wm.n_vertices = (int)n_vert;
-    wm.instanced = true;
-    wm.triangles = (int)std::min(n_tri, (size_t)0x7FFFFFFF);
+    WhittedMesh next;
+    if (const int rc = whitted_upload_meshes(c, next, lay, materials, n_materials)) return rc;
+    if (const int rc = whitted_build_meshes(c, next, lay, what)) return rc;
+    // the clustered meshes' boxes took in their mid levels' boxes: the instance boxes again from them (the checks passed above)
+    if (next.clusters.get())
+        if (const int rc = whitted_prepare_instances(c, next.meshes, n_materials, instances, n_instances, shade, box_pos, what)) return rc;
+    if (const int rc = whitted_build_top(c, next, shade, box_pos, instances, what)) return rc;
+    if (const int rc = whitted_tile_heads(c)) return rc;
+    next.instanced = true;
+    next.triangles = (int)std::min(lay.n_tri, (size_t)0x7FFFFFFF);
+    c->wm = std::move(next);
     return RTGO_OK;
 }
 
@@ -2476,11 +1699,10 @@ int rtgo_whitted_set_instances(rtgo_ctx* c, const rtgo_whitted_instance* instanc
     if (!c->wm.instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_instances: no instanced scene (call rtgo_whitted_set_scene first)");
     std::vector<whitted::InstShade> shade;
     std::vector<float> box_pos;
-    int rc = whitted_prepare_instances(c, c->wm.meshes, (uint32_t)c->wm.n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_instances");
-    if (rc) return rc;
+    if (const int rc = whitted_prepare_instances(c, c->wm.meshes, (uint32_t)c->wm.n_materials, instances, n_instances, shade, box_pos, "rtgo_whitted_set_instances")) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    return whitted_build_top(c, shade, box_pos, instances, "rtgo_whitted_set_instances");
+    return whitted_build_top(c, c->wm, shade, box_pos, instances, "rtgo_whitted_set_instances");
 }
 
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
@@ -2551,77 +1773,6 @@ int rtgo_whitted_set_miss_color(rtgo_ctx* c, const float rgb[3])
 {
     if (!c || !rgb) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_miss_color: NULL argument");
     c->w_miss = v3{rgb[0], rgb[1], rgb[2]};
-    return RTGO_OK;
-}
-
-// The launch of one mesh (rtgo_whitted_set_mesh).  Beside the lanes' stacks (stack_bytes), its LDS holds as much of the structure as
-// fits: everything in its compact form (quantised records, vertices, 16-bit vertex indices), or the fp32 records alone, or nothing.
-static int whitted_enqueue_mesh(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
-{
-    whitted::Params p;
-    std::memset(&p, 0, sizeof p);
-    p.frame = fr;
-    const WhittedMesh& wm = c->wm;
-    p.recs = wm.recs.get();
-    p.tris = wm.tris.get();
-    p.qrecs = wm.qrecs.get();
-    p.tidx = wm.tidx.get();
-    p.n_vertices = wm.n_vertices;
-    p.grid_lo = wm.grid_lo;
-    p.grid_step = wm.grid_step;
-    p.n_recs = wm.n_recs;
-    p.n_triangles = wm.triangles;
-    p.positions = wm.positions.get();
-    p.normals = wm.normals.get();
-    p.indices = wm.indices.get();
-    p.tri_material = wm.tri_material.get();
-    p.texcoords = wm.texcoords.get();
-    const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
-    const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
-    const dim3 grid(blocks), block(whitted::kRenderBlock);
-    if (mode_cap >= whitted::kAllInLds && p.n_vertices <= 65535 && compact_bytes + stack_bytes <= whitted::kRenderLds)
-        hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, grid, block, compact_bytes + stack_bytes, c->stream, p);
-    else if (mode_cap >= whitted::kRecordsInLds && rec_bytes + stack_bytes <= whitted::kRenderLds)
-        hipLaunchKernelGGL(whitted::render_kernel<whitted::kRecordsInLds>, grid, block, rec_bytes + stack_bytes, c->stream, p);
-    else
-        hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInL2>, grid, block, stack_bytes, c->stream, p);
-    RTGO_HIP(c, hipGetLastError());
-    return RTGO_OK;
-}
-
-// The launch of an instanced scene.  The top level's records and InstWalk array go to LDS beside the stacks when they fit (and
-// RTGO_WHITTED_MODE allows any LDS residency); the meshes' records and triangles are read through L2 (kAllInL2's way).
-static int whitted_enqueue_instanced(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
-{
-    whitted::InstParams q;
-    std::memset(&q, 0, sizeof q);
-    q.frame = fr;
-    const WhittedMesh& wm = c->wm;
-    q.top_recs = wm.top.recs.get();
-    q.inst = wm.top.inst.get();
-    q.shade = wm.top.shade.get();
-    q.n_top_recs = wm.top.n_recs;
-    q.n_instances = wm.top.n_instances;
-    q.recs = wm.recs.get();
-    q.tris = wm.tris.get();
-    q.clusters = wm.clusters.get();
-    q.positions = wm.positions.get();
-    q.normals = wm.normals.get();
-    q.texcoords = wm.texcoords.get();
-    q.indices = wm.indices.get();
-    q.tri_material = wm.tri_material.get();
-    const size_t top_bytes = (size_t)q.n_top_recs * 4 * sizeof(float4) + (size_t)q.n_instances * sizeof(whitted::InstWalk);
-    const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= whitted::kRenderLds;
-    const size_t lds = stack_bytes + (in_lds ? top_bytes : 0);
-    const dim3 grid(blocks), block(whitted::kRenderBlock);
-    if (q.clusters) {   // a clustered mesh in the scene: the three-level walk
-        if (in_lds) hipLaunchKernelGGL((whitted::render_inst_kernel<true, true>), grid, block, lds, c->stream, q);
-        else hipLaunchKernelGGL((whitted::render_inst_kernel<false, true>), grid, block, lds, c->stream, q);
-    } else if (in_lds)
-        hipLaunchKernelGGL(whitted::render_inst_kernel<true>, grid, block, lds, c->stream, q);
-    else
-        hipLaunchKernelGGL(whitted::render_inst_kernel<false>, grid, block, lds, c->stream, q);
-    RTGO_HIP(c, hipGetLastError());
     return RTGO_OK;
 }
 
@@ -2701,8 +1852,7 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     if (blocks > cus) blocks = cus;
     int slot = 0;
     return timed_launch(c, slot, [&]() -> int {
-        const int rc = c->wm.instanced ? whitted_enqueue_instanced(c, fr, stack_bytes, env_whitted_mode(), blocks)
-                                       : whitted_enqueue_mesh(c, fr, stack_bytes, env_whitted_mode(), blocks);
+        const int rc = whitted_enqueue(c, fr, stack_bytes, env_whitted_mode(), blocks);
         if (rc == RTGO_OK) c->w_launch_parity = 1 - c->w_launch_parity;   // (only once the launch that zeroes the other head is in the stream)
         return rc;
     });
@@ -2710,14 +1860,6 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
 
 // ---- ray queries (rtgo_trace.h) ----
 
-// RTGO_TRACE_MODE (test and experiment knob, RTGO_WHITTED_MODE's way): 0 = scene / top level read from global memory, 1 = staged in LDS
-// (where it fits); unset, empty or anything else: the host's own choice (-1).  No result depends on it.
-static int env_trace_mode()
-{
-    const char* v = std::getenv("RTGO_TRACE_MODE");
-    if (!v || !*v) return -1;
-    return v[0] == '0' ? 0 : (v[0] == '1' ? 1 : -1);
-}
 
 // Fewer rays than this walk the analytic scene from global memory: every workgroup of the LDS form copies the whole scene first (61 KB
 // for checkered).  From the smallest batch measured on, the copy repays itself (the measurement).
@@ -2817,18 +1959,9 @@ int rtgo_whitted_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint3
     size_t lds = stack_bytes;
     int kind = whitted::kTraceMesh;
     if (!wm.instanced) {
-        p.mesh.recs = wm.recs.get();
-        p.mesh.tris = wm.tris.get();
-        p.mesh.n_recs = wm.n_recs;
-        p.mesh.n_triangles = wm.triangles;
+        p.mesh = mesh_params(wm);
     } else {
-        p.inst.top_recs = wm.top.recs.get();
-        p.inst.inst = wm.top.inst.get();
-        p.inst.n_top_recs = wm.top.n_recs;
-        p.inst.n_instances = wm.top.n_instances;
-        p.inst.recs = wm.recs.get();
-        p.inst.tris = wm.tris.get();
-        p.inst.clusters = wm.clusters.get();
+        p.inst = inst_params(wm);
         // the top level in LDS where four workgroups a CU still fit with it (RTGO_TRACE_MODE: never / wherever one fits)
         const size_t top_bytes = (size_t)p.inst.n_top_recs * 4 * sizeof(float4) + (size_t)p.inst.n_instances * sizeof(whitted::InstWalk);
         const int mode = env_trace_mode();

@@ -732,6 +732,19 @@ __device__ __forceinline__ void write_walk_record(float4* __restrict__ recs, uin
 // centroid normalised to the scene bounds, stable order by (code, triangle index), Karras 2012, one triangle per leaf, bottom-up fit.
 // Boxes are padded by 1e-4 of the scene's extent + 1e-6: the slab test rounds, the triangle test must never be cut off.
 // ---------------------------------------------------------------------------------------------------------------------
+// The work arrays of one build of n triangles (host side: whitted_build), carved out of build_scratch_ints(n) ints: parent [2n - 1], visit,
+// first, count, record [n each], 16 words for the meta, sah_kernel's 32 n
+constexpr size_t build_scratch_ints(size_t n) { return 38 * n + 16; }
+struct BuildScratch {
+    int *parent, *visit, *first_of, *count_of, *rec_of, *sah;
+    WhittedBuildMeta* meta;
+    BuildScratch(int* ints, int n)
+        : parent(ints), visit(parent + (2 * n - 1)), first_of(visit + n), count_of(first_of + n), rec_of(count_of + n), sah(rec_of + n + 16),
+          meta(reinterpret_cast<WhittedBuildMeta*>(rec_of + n))
+    {
+    }
+};
+
 __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
                                                               float4* __restrict__ nodes, int* __restrict__ parent, int* __restrict__ visit,
                                                               int* __restrict__ first_of, int* __restrict__ count_of, int* __restrict__ rec_of,

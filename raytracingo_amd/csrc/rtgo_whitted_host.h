@@ -1,0 +1,527 @@
+// rtgo_whitted_host.h -- host side of the whitted (triangle) path: what the rtgo_whitted_* entry points of rtgo_capi.hip call once they
+// have checked their arguments (no exported symbol lives here).  Scene set-up first, then the launches' parameter blocks.  Every build
+// works on the WhittedMesh it is handed -- a scene built aside, or the context's -- and frees its temporaries on return.
+#pragma once
+
+#include "rtgo_ctx.h"
+
+using whitted::WhittedBuildMeta;
+
+// the two sets of tile-queue heads of the whitted launches (allocated once, zero)
+static int whitted_tile_heads(rtgo_ctx* c)
+{
+    if (!c->w_tile_counters.get()) {
+        const size_t heads = 2 * (size_t)whitted::kTileHeads * whitted::kTileHeadStride;
+        RTGO_HIP(c, c->w_tile_counters.alloc(heads));
+        RTGO_HIP(c, hipMemsetAsync(c->w_tile_counters.get(), 0, heads * sizeof(unsigned int), c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return RTGO_OK;
+}
+
+// What one whitted_build of n triangles writes (recs n x 4 float4, tris n x 3 float4, qrecs n x 2 uint4, tidx n uint2), and the slice of a
+// scene's arrays that starts at record `rec` and (sorted) triangle `tri`
+struct WhittedBuildTarget { float4 *recs, *tris; uint4* qrecs; uint2* tidx; };
+static WhittedBuildTarget whitted_target(const WhittedMesh& wm, size_t rec, size_t tri)
+{
+    return {wm.recs.get() + 4 * rec, wm.tris.get() + 3 * tri, wm.qrecs.get() + 2 * tri, wm.tidx.get() + tri};
+}
+
+// What a whitted_build of up to n triangles needs while it runs: the Morton hierarchy's nodes and the kernels' work arrays
+struct WhittedBuildScratch {
+    DeviceArray<float4> nodes;
+    DeviceArray<int> ints;
+    hipError_t alloc(size_t n)
+    {
+        const hipError_t e = nodes.alloc((2 * n - 1) * 2);
+        return e != hipSuccess ? e : ints.alloc(whitted::build_scratch_ints(n));
+    }
+};
+
+// One structure of the whitted path, built on the device over n triangles (positions, indices: device memory) into `t`: build_kernel's
+// Morton hierarchy, its records rebuilt top-down with the surface-area heuristic (sah_kernel) when the leaves fit its LDS, and the Morton
+// records again when the surface-area tree comes out deeper than the walk's stack.  Synchronous.
+static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int* indices, int n, const WhittedBuildTarget& t, const WhittedBuildScratch& s,
+                         WhittedBuildMeta& m, const char* what)
+{
+    const whitted::BuildScratch w(s.ints.get(), n);
+    const size_t keys_lds = (size_t)whitted::kMaxTriangles * sizeof(unsigned long long);
+    hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, s.nodes.get(),
+                       w.parent, w.visit, w.first_of, w.count_of, w.rec_of, t.recs, t.tris, t.qrecs, t.tidx, w.meta);
+    RTGO_HIP(c, hipGetLastError());
+    // the records over the same leaves, rebuilt top-down with the surface-area heuristic (leaf boxes, links, order arrays in LDS: 33 B per
+    // triangle, so meshes beyond ~4650 triangles keep the Morton records)
+    const size_t sah_lds = (size_t)n * (6 * sizeof(float) + sizeof(int) + 2 * sizeof(short) + 1) + 16;
+    const bool sah = !std::getenv("RTGO_WHITTED_NO_SAH") && sah_lds <= 150 * 1024;
+    if (sah) {
+        hipLaunchKernelGGL(whitted::sah_kernel, dim3(1), dim3(whitted::kBuildThreads), sah_lds, c->stream, n, (const float4*)s.nodes.get(), (const int*)w.parent,
+                           (const int*)w.first_of, (const int*)w.count_of, w.sah, t.recs, t.qrecs, w.meta);
+        RTGO_HIP(c, hipGetLastError());
+    }
+    std::memset(&m, 0, sizeof m);
+    RTGO_HIP(c, hipMemcpyAsync(&m, w.meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (m.walk_depth > whitted::kMaxWalkDepth && sah) {
+        // the surface-area tree came out deeper than the walk's stack (it has no depth bound of its own): back to the Morton records,
+        // whose depth is bounded by the code length
+        hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, s.nodes.get(),
+                           w.parent, w.visit, w.first_of, w.count_of, w.rec_of, t.recs, t.tris, t.qrecs, t.tidx, w.meta);
+        RTGO_HIP(c, hipGetLastError());
+        RTGO_HIP(c, hipMemcpyAsync(&m, w.meta, sizeof m, hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (m.depth > 2 * whitted::kStack)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": triangle LBVH depth " + std::to_string(m.depth) + " exceeds what the build handles (" +
+                                               std::to_string(2 * whitted::kStack) + ")");
+    if (m.walk_depth > whitted::kMaxWalkDepth)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the walk needs " + std::to_string(m.walk_depth) + " stack entries (limit " +
+                                               std::to_string(whitted::kMaxWalkDepth) + ")");
+    return RTGO_OK;
+}
+
+// One structure over n boxes (d_boxes: lo xyz, hi xyz each, device memory): the top level over the instances' boxes, a mid level over the
+// clusters'.  whitted_build takes box k as the degenerate triangle (lo, hi, lo) of "vertices" 2k and 2k + 1, whose bounds are the box; its
+// Morton-ordered "triangles" carry k in .w of their first corner: the leaf order returned.  Records to recs (n x 4 float4).  Synchronous.
+static int whitted_build_boxes(rtgo_ctx* c, const float* d_boxes, int n, float4* recs, std::vector<int>& order, WhittedBuildMeta& m, const char* what)
+{
+    std::vector<unsigned int> idx((size_t)3 * n);
+    for (int k = 0; k < 3 * n; ++k) idx[k] = 2 * (k / 3) + (k % 3 == 1 ? 1 : 0);
+    DeviceArray<unsigned int> d_idx;
+    DeviceArray<float4> d_tris;   // (what the build writes beside the records: only the order is read)
+    DeviceArray<uint4> d_qrecs;
+    DeviceArray<uint2> d_tidx;
+    WhittedBuildScratch scratch;
+    RTGO_HIP(c, d_idx.upload(idx.data(), idx.size(), c->stream));
+    RTGO_HIP(c, d_tris.alloc((size_t)n * 3));
+    RTGO_HIP(c, d_qrecs.alloc((size_t)n * 2));
+    RTGO_HIP(c, d_tidx.alloc(n));
+    RTGO_HIP(c, scratch.alloc(n));
+    if (const int rc = whitted_build(c, d_boxes, d_idx.get(), n, {recs, d_tris.get(), d_qrecs.get(), d_tidx.get()}, scratch, m, what)) return rc;
+    std::vector<float4> tris((size_t)3 * n);
+    RTGO_HIP(c, hipMemcpyAsync(tris.data(), d_tris.get(), tris.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    order.resize(n);
+    for (int pos = 0; pos < n; ++pos) std::memcpy(&order[pos], &tris[3 * pos].w, sizeof(int));
+    return RTGO_OK;
+}
+
+// The checks every mesh of the whitted path passes (rtgo_whitted_set_mesh, rtgo_whitted_set_scene; `at` names it in the messages): vertex
+// indices inside the vertex array, finite vertex data, material indices inside the table.  Also finds the mesh's largest material index.
+static int whitted_check_mesh(rtgo_ctx* c, const rtgo_whitted_mesh& q, uint32_t n_materials, const std::string& at, uint32_t& max_material)
+{
+    for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
+        if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
+    for (uint32_t i = 0; i < 3 * q.n_vertices; ++i)
+        if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
+    if (q.texcoords)
+        for (uint32_t i = 0; i < 2 * q.n_vertices; ++i)
+            if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + ": non-finite texture coordinate");
+    max_material = 0;
+    if (q.material_of_triangle)
+        for (uint32_t i = 0; i < q.n_triangles; ++i) {
+            if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material index beyond the material array");
+            max_material = std::max(max_material, q.material_of_triangle[i]);
+        }
+    return RTGO_OK;
+}
+
+// The one mesh of rtgo_whitted_set_mesh into `wm` (empty): uploads, the build, and what the launches read of its meta
+static int whitted_build_single(rtgo_ctx* c, WhittedMesh& wm, const rtgo_whitted_mesh& q, const rtgo_pbr* materials, uint32_t n_materials, const char* what)
+{
+    const size_t n = q.n_triangles;
+    WhittedBuildScratch scratch;
+    RTGO_HIP(c, wm.positions.upload(q.positions, (size_t)q.n_vertices * 3, c->stream));
+    if (q.normals) RTGO_HIP(c, wm.normals.upload(q.normals, (size_t)q.n_vertices * 3, c->stream));
+    RTGO_HIP(c, wm.indices.upload(q.indices, n * 3, c->stream));
+    if (q.material_of_triangle) RTGO_HIP(c, wm.tri_material.upload(q.material_of_triangle, n, c->stream));
+    RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
+    RTGO_HIP(c, wm.recs.alloc(n * 4));
+    RTGO_HIP(c, wm.tris.alloc(n * 3));
+    RTGO_HIP(c, wm.qrecs.alloc(n * 2));
+    RTGO_HIP(c, wm.tidx.alloc(n));
+    RTGO_HIP(c, scratch.alloc(n));
+    if (const int rc = whitted_build(c, wm.positions.get(), wm.indices.get(), (int)n, whitted_target(wm, 0, 0), scratch, wm.meta, what)) return rc;
+    wm.n_vertices = (int)q.n_vertices;
+    wm.walk_depth = wm.meta.walk_depth < 1 ? 1 : wm.meta.walk_depth;
+    wm.n_materials = (int)n_materials;
+    return RTGO_OK;
+}
+
+// ---- instanced scenes ----------------------------------------------------------------------------------------------------
+// The instances' side, checked and laid out on the host before anything on the device changes: per instance its InstShade record
+// (o2w as given, W2O = its inverse in double, rounded once) and its world box (the 8 corners of its mesh's box through o2w in double,
+// rounded outwards), which the top-level build takes as the degenerate triangle (lo, hi, lo).
+static int whitted_prepare_instances(rtgo_ctx* c, const std::vector<WhittedMeshInfo>& meshes, uint32_t n_materials, const rtgo_whitted_instance* inst,
+                                     uint32_t n, std::vector<whitted::InstShade>& shade, std::vector<float>& box_pos, const char* what)
+{
+    const std::string w(what);
+    if (!inst) return fail(c, RTGO_E_INVALID, w + ": NULL instance array");
+    if (n == 0 || n > RTGO_WHITTED_MAX_INSTANCES)
+        return fail(c, RTGO_E_UNSUPPORTED, w + ": instance count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_INSTANCES) + "]");
+    shade.assign(n, whitted::InstShade{});
+    box_pos.assign((size_t)6 * n, 0.0f);
+    for (uint32_t i = 0; i < n; ++i) {
+        const rtgo_whitted_instance& q = inst[i];
+        const std::string at = w + ": instance " + std::to_string(i);
+        if (q.mesh >= meshes.size()) return fail(c, RTGO_E_INVALID, at + " names a mesh beyond the meshes array");
+        const WhittedMeshInfo& mi = meshes[q.mesh];
+        if ((uint64_t)q.material_offset + mi.max_material >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material offset + material index beyond the material array");
+        bool finite = true;
+        for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(q.transform[k]);
+        // the walk takes rays to object space through the inverse: the transform must be finite and invertible (the analytic path's
+        // test of a model matrix, rtgo_set_scene)
+        double A[3][4], B[3][4];   // B: the inverse, adj(A) / det, then -A^-1 t
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 4; ++k) A[r][k] = q.transform[4 * r + k];
+        const double det = mat3_det_inverse(A, B);
+        if (!finite || !std::isfinite(det) || std::fabs(det) < 1e-30) return fail(c, RTGO_E_INVALID, at + " has a non-finite or singular transform");
+        for (int r = 0; r < 3; ++r) B[r][3] = -(B[r][0] * A[0][3] + B[r][1] * A[1][3] + B[r][2] * A[2][3]);
+        whitted::InstShade& sh = shade[i];
+        float* o2w = &sh.o2w[0].x;
+        float* w2o = &sh.w2o[0].x;
+        for (int k = 0; k < 12; ++k) {
+            o2w[k] = q.transform[k];
+            w2o[k] = (float)B[k / 4][k % 4];
+            if (!std::isfinite(w2o[k])) return fail(c, RTGO_E_INVALID, at + " has a non-finite or singular transform");
+        }
+        sh.material_offset = (int)q.material_offset;
+        sh.vert_base = mi.vert_base;
+        sh.tri_base = mi.tri_base;
+        sh.flags = mi.flags;
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int corner = 0; corner < 8; ++corner) {
+            const double x = (corner & 1) ? mi.hi[0] : mi.lo[0], y = (corner & 2) ? mi.hi[1] : mi.lo[1], z = (corner & 4) ? mi.hi[2] : mi.lo[2];
+            for (int r = 0; r < 3; ++r) {
+                const double v = A[r][0] * x + A[r][1] * y + A[r][2] * z + A[r][3];
+                lo[r] = std::fmin(lo[r], v);
+                hi[r] = std::fmax(hi[r], v);
+            }
+        }
+        for (int r = 0; r < 3; ++r) {
+            float l = (float)lo[r], h = (float)hi[r];
+            if ((double)l > lo[r]) l = std::nextafter(l, -INFINITY);
+            if ((double)h < hi[r]) h = std::nextafter(h, INFINITY);
+            if (!std::isfinite(l) || !std::isfinite(h)) return fail(c, RTGO_E_INVALID, at + " places its mesh beyond the float range");
+            box_pos[6 * i + r] = l;
+            box_pos[6 * i + 3 + r] = h;
+        }
+    }
+    return RTGO_OK;
+}
+
+// The top level of `wm` (its meshes built) over prepared instances: the structure over the instance boxes, the InstWalk records in leaf
+// order, and the stack both levels need.  Built aside: replaces wm's top level only once all of it succeeded.
+static int whitted_build_top(rtgo_ctx* c, WhittedMesh& wm, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos,
+                             const rtgo_whitted_instance* inst, const char* what)
+{
+    const int n = (int)shade.size();
+    DeviceArray<float> d_boxes;
+    WhittedTop top;
+    std::vector<int> order;
+    RTGO_HIP(c, d_boxes.upload(box_pos.data(), box_pos.size(), c->stream));
+    RTGO_HIP(c, top.recs.alloc((size_t)n * 4));
+    if (const int rc = whitted_build_boxes(c, d_boxes.get(), n, top.recs.get(), order, top.meta, what)) return rc;
+    const int depth = (top.meta.n_recs > 0 ? top.meta.walk_depth : 0) + wm.mesh_depth;
+    if (depth > whitted::kMaxInstWalkDepth)
+        return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
+                                               std::to_string(whitted::kMaxInstWalkDepth) + ")");
+    std::vector<whitted::InstWalk> walk((size_t)n);
+    for (int pos = 0; pos < n; ++pos) {
+        const int i = order[pos];
+        const WhittedMeshInfo& mi = wm.meshes[inst[i].mesh];
+        walk[pos] = whitted::InstWalk{{shade[i].w2o[0], shade[i].w2o[1], shade[i].w2o[2]}, mi.rec_base, mi.tri_base, mi.root, i};
+    }
+    RTGO_HIP(c, top.inst.upload(walk.data(), walk.size(), c->stream));
+    RTGO_HIP(c, top.shade.upload(shade.data(), shade.size(), c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    top.n_recs = top.meta.n_recs;
+    top.n_instances = n;
+    wm.top = std::move(top);
+    wm.walk_depth = depth < 1 ? 1 : depth;
+    return RTGO_OK;
+}
+
+// Device scratch of the clustered builds of one rtgo_whitted_set_scene, sized for its largest clustered mesh (whitted_build_meshes)
+struct WhittedBigScratch {
+    DeviceArray<unsigned long long> keys, keys_alt;
+    DeviceArray<unsigned int> hist, cidx;
+    DeviceArray<float> partial, bounds, boxes;
+    DeviceArray<int> crec;
+};
+
+// One clustered mesh (n > kMaxTriangles triangles; rtgo_whitted_big.h), in its slices of wm's arrays: Morton order over the
+// whole mesh on the device, clusters of consecutive sorted triangles each built by whitted_build (tris[].w then remapped to the mesh's
+// own indices), and a mid level over the clusters' boxes whose records take the first ncl - 1 record slots of the mesh (the clusters
+// follow: a mesh of n triangles has at most n slots, and a cluster of m triangles fewer than m records).  Appends the mesh's clusters,
+// in the mid level's leaf order, to `table`; sets mi.root, mi.depth, and widens mi.lo / hi over every box the walk can reach from the
+// mesh's root, so the instance boxes built from it contain them by construction.  Synchronous.
+static int whitted_build_clustered(rtgo_ctx* c, const WhittedMesh& wm, WhittedMeshInfo& mi, int n, WhittedBigScratch& bs, const WhittedBuildScratch& scratch,
+                                   std::vector<int4>& table, const char* what)
+{
+    using namespace whitted;
+    const int ncl = (n + kClusterTris - 1) / kClusterTris;
+    const float* positions = wm.positions.get() + 3 * (size_t)mi.vert_base;
+    const unsigned int* indices = wm.indices.get() + 3 * (size_t)mi.tri_base;
+    const WhittedBuildTarget mesh = whitted_target(wm, mi.rec_base, mi.tri_base);
+    // Morton keys over the mesh's bounds, sorted by four stable passes over the code's bytes
+    const int nbb = std::min(1024, (n + 1023) / 1024);
+    hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, positions, indices, n, bs.partial.get());
+    hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)bs.partial.get(), nbb, bs.bounds.get());
+    hipLaunchKernelGGL(big_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, positions, indices, n, (const float*)bs.bounds.get(), bs.keys.get());
+    const unsigned long long* sorted = radix_sort_keys(c, bs.keys.get(), bs.keys_alt.get(), bs.hist.get(), n);
+    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, sorted, n, indices, bs.cidx.get());
+    RTGO_HIP(c, hipGetLastError());
+    // the clusters
+    std::vector<int> crec(ncl), croot(ncl);
+    int rec = mi.rec_base + ncl - 1, cdepth = 0;
+    for (int k = 0; k < ncl; ++k) {
+        const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
+        WhittedBuildMeta m;
+        if (const int rc = whitted_build(c, positions, bs.cidx.get() + 3 * (size_t)s, nc, whitted_target(wm, rec, mi.tri_base + s), scratch, m, what)) return rc;
+        mi.built.push_back({rec, m.n_recs, mi.tri_base + s, m});
+        crec[k] = rec;
+        croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
+        cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
+        rec += m.n_recs;
+    }
+    hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, mesh.tris, sorted, n, ncl);
+    RTGO_HIP(c, hipGetLastError());
+    // the mid level over the clusters' boxes
+    RTGO_HIP(c, hipMemcpyAsync(bs.crec.get(), crec.data(), ncl * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)wm.recs.get(), (const int*)bs.crec.get(), ncl,
+                       bs.boxes.get());
+    RTGO_HIP(c, hipGetLastError());
+    WhittedBuildMeta m;
+    std::vector<int> order;
+    if (const int rc = whitted_build_boxes(c, bs.boxes.get(), ncl, mesh.recs, order, m, what)) return rc;
+    mi.built.push_back({mi.rec_base, m.n_recs, -1, m});
+    std::vector<float4> root_rec(4);
+    std::vector<float> boxes((size_t)6 * ncl);
+    RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.boxes.get(), boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (m.n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), mesh.recs, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    const int tbase = (int)table.size();
+    for (const int k : order) table.push_back(make_int4(crec[k], mi.tri_base + cluster_start(n, ncl, k), croot[k], 0));
+    // what the walk can reach first below an instance: the mid root's two child boxes, or (a mid level of one leaf) the clusters' root
+    // records, whose boxes are the ones big_cluster_boxes_kernel took
+    auto widen = [&](const float* l, const float* h) {
+        for (int a = 0; a < 3; ++a) {
+            mi.lo[a] = std::fmin(mi.lo[a], l[a]);
+            mi.hi[a] = std::fmax(mi.hi[a], h[a]);
+        }
+    };
+    if (m.n_recs > 0) {
+        widen(&root_rec[0].x, &root_rec[1].x);
+        widen(&root_rec[2].x, &root_rec[3].x);
+    }
+    for (int k = 0; k < ncl; ++k) widen(&boxes[6 * k], &boxes[6 * k + 3]);
+    mi.root = 1 + ((tbase << 3) | (m.n_recs > 0 ? kMidHasRecords : ncl - 1));
+    mi.depth = (m.n_recs > 0 ? m.walk_depth : 0) + cdepth;
+    return RTGO_OK;
+}
+
+// where the meshes of an instanced scene sit in its arrays, and the sizes its builds need
+struct WhittedLayout {
+    std::vector<WhittedMeshInfo> info;
+    size_t n_vert = 0, n_tri = 0;
+    int max_tri = 0, max_big = 0;   // the largest single build, the largest clustered mesh
+    // the meshes back to back (indices stay relative to their mesh's vertices: each build reads its own slice)
+    std::vector<float> pos, nrm, uv;
+    std::vector<unsigned int> idx, tmat;
+};
+
+// The stages of rtgo_whitted_set_scene.  Stage 1 (host only): every mesh as rtgo_whitted_set_mesh checks it, its padded box, where it will sit in the arrays, and packed there
+static int whitted_layout_meshes(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, uint32_t n_materials, WhittedLayout& lay)
+{
+    lay.info.assign(n_meshes, WhittedMeshInfo());
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        const rtgo_whitted_mesh& q = meshes[k];
+        const std::string at = "rtgo_whitted_set_scene: mesh " + std::to_string(k);
+        if (!q.positions || !q.indices) return fail(c, RTGO_E_INVALID, at + ": NULL positions or indices");
+        if (q.n_triangles == 0 || q.n_triangles > RTGO_WHITTED_MAX_MESH_TRIANGLES || q.n_vertices == 0)
+            return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESH_TRIANGLES) + "], vertices non-empty");
+        if (lay.n_tri + q.n_triangles > RTGO_WHITTED_MAX_SCENE_TRIANGLES)
+            return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
+        WhittedMeshInfo& mi = lay.info[k];
+        if (const int rc = whitted_check_mesh(c, q, n_materials, at, mi.max_material)) return rc;
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::fmin(lo[a], q.positions[3 * q.indices[i] + a]);
+                hi[a] = std::fmax(hi[a], q.positions[3 * q.indices[i] + a]);
+            }
+        // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
+        float maxext = 0.0f;
+        for (int a = 0; a < 3; ++a) maxext = std::fmax(maxext, hi[a] - lo[a]);
+        const float pad = 2.0f * (maxext * 1e-4f + 1e-6f);
+        for (int a = 0; a < 3; ++a) {
+            mi.lo[a] = lo[a] - pad;
+            mi.hi[a] = hi[a] + pad;
+        }
+        mi.rec_base = (int)lay.n_tri;   // (a mesh of n triangles has fewer than n records)
+        mi.tri_base = (int)lay.n_tri;
+        mi.vert_base = (int)lay.n_vert;
+        mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
+        mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
+        mi.n_tris = (int)q.n_triangles;
+        lay.n_vert += q.n_vertices;
+        lay.n_tri += q.n_triangles;
+        if (mi.clustered) {
+            // one workgroup's builds: clusters of at most kClusterTris triangles and a mid level of ncl boxes
+            const int ncl = ((int)q.n_triangles + whitted::kClusterTris - 1) / whitted::kClusterTris;
+            lay.max_tri = std::max(lay.max_tri, std::max(whitted::kClusterTris, ncl));
+            lay.max_big = std::max(lay.max_big, (int)q.n_triangles);
+        } else {
+            lay.max_tri = std::max(lay.max_tri, (int)q.n_triangles);
+        }
+    }
+    // the meshes' arrays back to back, zero where a mesh has no normals, texture coordinates or materials
+    lay.pos.assign(3 * lay.n_vert, 0.0f);
+    lay.nrm.assign(3 * lay.n_vert, 0.0f);
+    lay.uv.assign(2 * lay.n_vert, 0.0f);
+    lay.idx.assign(3 * lay.n_tri, 0u);
+    lay.tmat.assign(lay.n_tri, 0u);
+    for (size_t k = 0; k < lay.info.size(); ++k) {
+        const rtgo_whitted_mesh& q = meshes[k];
+        const WhittedMeshInfo& mi = lay.info[k];
+        std::memcpy(&lay.pos[3 * (size_t)mi.vert_base], q.positions, (size_t)q.n_vertices * 3 * sizeof(float));
+        if (q.normals) std::memcpy(&lay.nrm[3 * (size_t)mi.vert_base], q.normals, (size_t)q.n_vertices * 3 * sizeof(float));
+        if (q.texcoords) std::memcpy(&lay.uv[2 * (size_t)mi.vert_base], q.texcoords, (size_t)q.n_vertices * 2 * sizeof(float));
+        std::memcpy(&lay.idx[3 * (size_t)mi.tri_base], q.indices, (size_t)q.n_triangles * 3 * sizeof(unsigned int));
+        if (q.material_of_triangle) std::memcpy(&lay.tmat[mi.tri_base], q.material_of_triangle, (size_t)q.n_triangles * sizeof(unsigned int));
+    }
+    return RTGO_OK;
+}
+
+// Stage 2: the packed meshes and the materials to the device, and the arrays the builds write
+static int whitted_upload_meshes(rtgo_ctx* c, WhittedMesh& wm, const WhittedLayout& lay, const rtgo_pbr* materials, uint32_t n_materials)
+{
+    RTGO_HIP(c, wm.positions.upload(lay.pos.data(), lay.pos.size(), c->stream));
+    RTGO_HIP(c, wm.normals.upload(lay.nrm.data(), lay.nrm.size(), c->stream));
+    RTGO_HIP(c, wm.texcoords.upload(lay.uv.data(), lay.uv.size(), c->stream));
+    RTGO_HIP(c, wm.indices.upload(lay.idx.data(), lay.idx.size(), c->stream));
+    RTGO_HIP(c, wm.tri_material.upload(lay.tmat.data(), lay.tmat.size(), c->stream));
+    RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
+    RTGO_HIP(c, wm.recs.alloc(lay.n_tri * 4));
+    RTGO_HIP(c, wm.tris.alloc(lay.n_tri * 3));
+    RTGO_HIP(c, wm.qrecs.alloc(lay.n_tri * 2));
+    RTGO_HIP(c, wm.tidx.alloc(lay.n_tri));
+    wm.n_vertices = (int)lay.n_vert;
+    wm.n_materials = (int)n_materials;
+    return RTGO_OK;
+}
+
+// Stage 3, the bottom level: each mesh's own structure in its slice of the arrays (a clustered mesh: its clusters and mid level), then the table
+static int whitted_build_meshes(rtgo_ctx* c, WhittedMesh& wm, WhittedLayout& lay, const char* what)
+{
+    WhittedBuildScratch scratch;
+    WhittedBigScratch bs;
+    RTGO_HIP(c, scratch.alloc(lay.max_tri));
+    if (lay.max_big > 0) {
+        const int n = lay.max_big, ncl = (n + whitted::kClusterTris - 1) / whitted::kClusterTris, nb = (n + whitted::kRadixTile - 1) / whitted::kRadixTile;
+        RTGO_HIP(c, bs.keys.alloc(n));
+        RTGO_HIP(c, bs.keys_alt.alloc(n));
+        RTGO_HIP(c, bs.hist.alloc((size_t)256 * nb));
+        RTGO_HIP(c, bs.cidx.alloc((size_t)3 * n));
+        RTGO_HIP(c, bs.partial.alloc((size_t)6 * 1024));
+        RTGO_HIP(c, bs.bounds.alloc(6));
+        RTGO_HIP(c, bs.crec.alloc(ncl));
+        RTGO_HIP(c, bs.boxes.alloc((size_t)6 * ncl));
+    }
+    std::vector<int4> table;
+    for (WhittedMeshInfo& mi : lay.info) {
+        if (mi.clustered) {
+            if (const int rc = whitted_build_clustered(c, wm, mi, mi.n_tris, bs, scratch, table, what)) return rc;
+        } else {
+            WhittedBuildMeta m;
+            if (const int rc = whitted_build(c, wm.positions.get() + 3 * (size_t)mi.vert_base, wm.indices.get() + 3 * (size_t)mi.tri_base, mi.n_tris,
+                                             whitted_target(wm, mi.rec_base, mi.tri_base), scratch, m, what))
+                return rc;
+            mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base, m});
+            mi.root = m.n_recs > 0 ? 0 : -1 - ((mi.n_tris - 1) << whitted::kLeafShift);
+            mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
+        }
+        wm.mesh_depth = std::max(wm.mesh_depth, mi.depth);
+    }
+    if (!table.empty()) RTGO_HIP(c, wm.clusters.upload(table.data(), table.size(), c->stream));
+    wm.meshes = lay.info;
+    return RTGO_OK;
+}
+
+// The launches.  What a launch over one mesh (rtgo_whitted_set_mesh) reads of the scene: everything of Params but the frame
+static whitted::Params mesh_params(const WhittedMesh& wm)
+{
+    whitted::Params p;
+    std::memset(&p, 0, sizeof p);
+    p.recs = wm.recs.get();
+    p.tris = wm.tris.get();
+    p.qrecs = wm.qrecs.get();
+    p.tidx = wm.tidx.get();
+    p.n_vertices = wm.n_vertices;
+    p.grid_lo = wm.meta.grid_lo;
+    p.grid_step = wm.meta.grid_step;
+    p.n_recs = wm.meta.n_recs;
+    p.n_triangles = wm.triangles;
+    p.positions = wm.positions.get();
+    p.normals = wm.normals.get();
+    p.indices = wm.indices.get();
+    p.tri_material = wm.tri_material.get();
+    p.texcoords = wm.texcoords.get();
+    return p;
+}
+
+// ... and over an instanced scene (rtgo_whitted_set_scene): everything of InstParams but the frame
+static whitted::InstParams inst_params(const WhittedMesh& wm)
+{
+    whitted::InstParams q;
+    std::memset(&q, 0, sizeof q);
+    q.top_recs = wm.top.recs.get();
+    q.inst = wm.top.inst.get();
+    q.shade = wm.top.shade.get();
+    q.n_top_recs = wm.top.n_recs;
+    q.n_instances = wm.top.n_instances;
+    q.recs = wm.recs.get();
+    q.tris = wm.tris.get();
+    q.clusters = wm.clusters.get();
+    q.positions = wm.positions.get();
+    q.normals = wm.normals.get();
+    q.texcoords = wm.texcoords.get();
+    q.indices = wm.indices.get();
+    q.tri_material = wm.tri_material.get();
+    return q;
+}
+
+// The launch of the context's scene.  One mesh: beside the lanes' stacks (stack_bytes), its LDS holds as much of the structure as fits --
+// everything in its compact form (quantised records, vertices, 16-bit vertex indices), or the fp32 records alone, or nothing.  An instanced
+// scene: the top level's records and InstWalk array when they fit (and RTGO_WHITTED_MODE allows); the meshes are read through L2.
+static int whitted_enqueue(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
+{
+    const dim3 grid(blocks), block(whitted::kRenderBlock);
+    if (!c->wm.instanced) {
+        whitted::Params p = mesh_params(c->wm);
+        p.frame = fr;
+        const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
+        const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
+        if (mode_cap >= whitted::kAllInLds && p.n_vertices <= 65535 && compact_bytes + stack_bytes <= whitted::kRenderLds)
+            hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, grid, block, compact_bytes + stack_bytes, c->stream, p);
+        else if (mode_cap >= whitted::kRecordsInLds && rec_bytes + stack_bytes <= whitted::kRenderLds)
+            hipLaunchKernelGGL(whitted::render_kernel<whitted::kRecordsInLds>, grid, block, rec_bytes + stack_bytes, c->stream, p);
+        else
+            hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInL2>, grid, block, stack_bytes, c->stream, p);
+    } else {
+        whitted::InstParams q = inst_params(c->wm);
+        q.frame = fr;
+        const size_t top_bytes = (size_t)q.n_top_recs * 4 * sizeof(float4) + (size_t)q.n_instances * sizeof(whitted::InstWalk);
+        const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= whitted::kRenderLds;
+        const size_t lds = stack_bytes + (in_lds ? top_bytes : 0);
+        if (q.clusters) {   // a clustered mesh in the scene: the three-level walk
+            if (in_lds) hipLaunchKernelGGL((whitted::render_inst_kernel<true, true>), grid, block, lds, c->stream, q);
+            else hipLaunchKernelGGL((whitted::render_inst_kernel<false, true>), grid, block, lds, c->stream, q);
+        } else if (in_lds)
+            hipLaunchKernelGGL(whitted::render_inst_kernel<true>, grid, block, lds, c->stream, q);
+        else
+            hipLaunchKernelGGL(whitted::render_inst_kernel<false>, grid, block, lds, c->stream, q);
+    }
+    RTGO_HIP(c, hipGetLastError());
+    return RTGO_OK;
+}

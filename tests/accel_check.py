@@ -7,7 +7,8 @@ Geometry is done in float64 on the exact values of the fp32 words, and containme
 min / max of fp32 numbers and every pad in the builds is added, never subtracted, so a correct build satisfies containment exactly.
 Where a check restates a DECISION the build takes in fp32 (which primitives are big, which rectangles pair up) it says so below.
 
-Layouts (rtgo_device.h, rtgo_build.h, rtgo_whitted.h, rtgo_whitted_inst.h, rtgo_capi.hip's build_grid):
+Layouts (rtgo_device.h, rtgo_build.h, rtgo_whitted.h, rtgo_whitted_inst.h, rtgo_whitted_host.h's WhittedBuildTarget, rtgo_capi.hip's
+build_grid):
   fnodes   2 float4 per node: (lo, left) (hi, right); a leaf: left = first record, right = -(count | pairs << 12 | cuboid << 20)
   fprims   4 float4 per record: rows 0..2 of M^-1, (bits(type), bits(SBT index), 0, 0); [0, n_small) in the tree, the rest up front
   recs     4 float4 per record: (left lo, left link) (left hi, -) (right lo, right link) (right hi, -); link >= 0: a record,

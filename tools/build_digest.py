@@ -2,7 +2,7 @@
 boxes, both fast-walk trees and their meta fields; the whitted records, triangles and grids; then the meta words, the grid image and the
 per-mesh infos that capi.Context.read_build returns in the clear), one line per scene -- two builds of the
 library (RTGO_HIP_LIB) give the same lines iff they build the same structures.   python tools/build_digest.py [analytic|whitted]"""
-import importlib.util, os, sys
+import importlib.util, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
@@ -15,10 +15,10 @@ def digest(ctx, whitted):
     return " ".join("%016x" % h for h in ctx.build_digest(whitted))
 
 
-def analytic(name, types, M, mat, aabb):
+def analytic(name, types, M, mat, aabb, large=False):
     ctx = capi.Context(0)
     try:
-        ctx.set_scene(types, M, mat, aabb)
+        (ctx.set_large_scene if large else ctx.set_scene)(types, M, mat, aabb)
         line = digest(ctx, False)
     except capi.RtgoError as e:   # (a refused scene is a result too: both builds must refuse it alike)
         line = str(e)
@@ -62,13 +62,16 @@ def main(ONLY):
             _, t = tg._box_scene(O, seed, W, H, (1, 6, 40)[seed % 3], bool(seed & 1), bool(seed & 2))
             analytic("boxes %d" % seed, t["type"], t["M"], t["mat"], None if (seed // 3) % 2 else t["aabb"])
         analytic("capacity", *capacity_scene(7, 512), None)
+        analytic("large 8193", *capacity_scene(7, 8193), None, large=True)   # (kRadixTile = 8192: the first size with two radix tiles)
 
     if ONLY != "analytic":
         import whitted_scene, whitted_instances as WI, whitted_big_meshes as BM
 
         def whitted(name, setup):
             ctx = capi.Context(0)
+            t0 = time.perf_counter()
             setup(ctx)
+            print("whitted  %-28s set up in %.1f ms" % (name, 1e3 * (time.perf_counter() - t0)), file=sys.stderr, flush=True)   # (stderr: the lines compare)
             print("whitted  %-28s %s" % (name, digest(ctx, True)), flush=True)
             ctx.close()
 
@@ -81,6 +84,8 @@ def main(ONLY):
         meshes, inst = WI.tori_scene()
         whitted("tori", lambda ctx: ctx.whitted_set_scene(meshes, inst, WI.materials()))
         whitted("clustered", lambda ctx: ctx.whitted_set_scene([BM.displaced_torus(200, 100)], [(WI.transform(np.eye(3), [0, 1, 0]), 0, 0)], WI.materials()))
+        # just over kMaxTriangles: 8320 triangles, three clusters, a mid level of one leaf without records
+        whitted("clustered 8320", lambda ctx: ctx.whitted_set_scene([BM.displaced_torus(65, 64)], [(WI.transform(np.eye(3), [0, 1, 0]), 0, 0)], WI.materials()))
         # test_whitted_coincident_triangles' mesh: every split of the surface-area sweep ties
         base = np.array([[-1.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.5, 0.0]], np.float32)
         extra = np.array([[-2.0, 0.0, -1.0], [2.0, 0.0, -1.0], [0.0, 2.5, -1.0], [-0.5, 0.2, 0.5], [0.5, 0.2, 0.5], [0.0, 0.9, 0.5]], np.float32)
