@@ -145,6 +145,8 @@ def lib():
         L.oracle_whitted_trace_instanced.restype = C.c_int
         L.oracle_whitted_trace_instanced.argtypes = [C.POINTER(WhittedIScene), fp, fp, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                      fp, fp, fp]
+        L.oracle_whitted_shade_point.restype = C.c_int
+        L.oracle_whitted_shade_point.argtypes = [fp, fp, fp, fp, fp, fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, fp]
         L.oracle_tex2d.restype = None
         L.oracle_tex2d.argtypes = [C.POINTER(Tex), C.c_float, C.c_float, fp]
         L.oracle_material.restype = C.c_int
@@ -404,3 +406,19 @@ def whitted_render_instanced(meshes, instances, materials, extra, cam12, width, 
     """the oracle's whitted path over an instanced scene (oracle_whitted_render_instanced), `subframes` accumulated: what
     Context.whitted_set_scene takes, `extra` as InstancedScene.  Returns (accum [h,w,4] f32, image [h,w,4] u8, {rays_total, rays_occlusion})."""
     return InstancedScene(meshes, instances, materials, extra, cam12, cull).render(width, height, subframes, threads)
+
+
+def whitted_shade_point(P, N, corners, corner_uv, UV, rd, material, lights, textures=None, occlusion=False):
+    """oracle_whitted_shade_point: the closest-hit program on a stated hit.  P, N, rd (3,), corners (3, 3), corner_uv (3, 2), UV (2,),
+    material (6,) (base colour rgba, metallic, roughness), lights [nl, 8], textures (base_color, metallic_roughness, normal) each uint8
+    [h, w, 4] or None; occlusion: the triangle of the corners occludes (False: nothing does).  Returns (rgb (3,) f32, gate-passing lights)."""
+    a = [f32(np.asarray(x).reshape(-1)) for x in (P, N, corners, corner_uv, UV, rd)]
+    mat = f32(np.asarray(material).reshape(6))
+    ls = f32(np.asarray(lights).reshape(-1, 8))
+    keep = []
+    mt = _mat_tex({0: textures} if textures is not None and any(t is not None for t in textures) else None, 1, keep)
+    rgb = np.zeros(3, dtype=np.float32)
+    n = lib().oracle_whitted_shade_point(*[fptr(x) for x in a], mat.ctypes.data, C.addressof(mt) if mt is not None else None,
+                                         ls.ctypes.data if len(ls) else None, len(ls), 0 if occlusion else 1, fptr(rgb))
+    assert n >= 0
+    return rgb, n

@@ -184,6 +184,13 @@ typedef struct {
 /* oracle_whitted_render over an instanced scene; -1 on an invalid scene (mesh index, material range, singular transform) */
 int oracle_whitted_render_instanced(const oracle_whitted_iscene* s, uint32_t width, uint32_t height, uint32_t subframe, float* accum,
                                     uint8_t* image, uint64_t* rays, int threads);
+/* __closesthit__radiance alone on a hit the caller states: world P[3] and N[3], corners[9] (the space dp/du, dp/dv are taken in) with
+   corner_uv[6], UV[2], the world ray direction rd[3] (normalised by the shader, not here), one material and its textures (or NULL), the
+   lights.  Occlusion rays meet the triangle of the corners alone; none is ever occluded when no_occlusion is set.  rgb[3] is the
+   radiance; returns the number of occlusion rays (the lights that pass the N.L > 0 && N.V > 0 gate), -1 on a NULL argument. */
+int oracle_whitted_shade_point(const float* P, const float* N, const float* corners, const float* corner_uv, const float* UV, const float* rd,
+                               const oracle_pbr* material, const oracle_mat_tex* textures, const oracle_point_light* lights, uint32_t n_lights,
+                               int no_occlusion, float* rgb);
 /* one closest-hit ray in world space: 1 and (instance, triangle, t, u, v) on a hit, 0 on a miss, -1 on an invalid scene */
 int oracle_whitted_trace_instanced(const oracle_whitted_iscene* s, const float* o, const float* d, float tmin, float tmax, int* instance,
                                    int* triangle, float* t, float* u, float* v);

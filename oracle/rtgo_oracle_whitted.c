@@ -11,7 +11,8 @@
  * ever launches it (engine/ never instantiates sutil::Scene), and the reference holds no fixture for it.  Triangle
  * intersection itself is OptiX's built-in (closed): the Moeller-Trumbore statement below is this project's definition, shared
  * operation for operation with the device code (raytracingo_amd/csrc/rtgo_whitted.h).  Traversal is brute force in triangle
- * order: the closest hit is the smallest t, the lowest triangle index on ties.
+ * order: the closest hit is the smallest t, the lowest triangle index on ties.  What this file computes after the hit is held to a float64
+ * statement written from whitted.cu and the definitions, not from this text (tests/whitted_ref64.py, tests/test_oracle_whitted_float64.py).
  */
 #include "rtgo_oracle.h"
 
@@ -545,4 +546,48 @@ int oracle_whitted_trace_instanced(const oracle_whitted_iscene* s, const float* 
     const int hit = itrace(&p, wld(o, 0), wld(d, 0), tmin, tmax, 0, instance, triangle, t, u, v);
     iprep_free(&p);
     return hit;
+}
+
+/* ---- the closest-hit program alone ----
+   shade() on a hit the caller states: world P and N, the triangle's corners (the space dp/du, dp/dv are taken in) and their texture
+   coordinates, UV, the world ray direction, one material with its optional textures, the lights.  Occlusion rays meet the triangle of
+   the three corners alone, or nothing when no_occlusion is set. */
+static int point_occluded(const void* scene, w3 o, w3 d, float tmin, float tmax)
+{
+    const float* c = (const float*)scene;
+    const float O[3] = { o.x, o.y, o.z }, D[3] = { d.x, d.y, d.z };
+    float t, u, v;
+    return oracle_tri_intersect(c, c + 3, c + 6, O, D, tmin, tmax, &t, &u, &v);
+}
+static int point_unoccluded(const void* scene, w3 o, w3 d, float tmin, float tmax)
+{
+    (void)scene; (void)o; (void)d; (void)tmin; (void)tmax;
+    return 0;
+}
+
+int oracle_whitted_shade_point(const float* P, const float* N, const float* corners, const float* corner_uv, const float* UV, const float* rd,
+                               const oracle_pbr* material, const oracle_mat_tex* textures, const oracle_point_light* lights, uint32_t n_lights,
+                               int no_occlusion, float* rgb)
+{
+    if (!P || !N || !corners || !corner_uv || !UV || !rd || !material || !rgb || (n_lights && !lights)) return -1;
+    hit_geom g;
+    g.P = wld(P, 0);
+    g.N = wld(N, 0);
+    g.P0 = wld(corners, 0);
+    g.P1 = wld(corners, 1);
+    g.P2 = wld(corners, 2);
+    for (int k = 0; k < 2; ++k) {
+        g.UV0[k] = corner_uv[k];
+        g.UV1[k] = corner_uv[2 + k];
+        g.UV2[k] = corner_uv[4 + k];
+        g.UV[k] = UV[k];
+    }
+    g.material = 0u;
+    const pipeline pl = { corners, NULL, no_occlusion ? point_unoccluded : point_occluded, material, textures, lights, n_lights, NULL, NULL, NULL, NULL, NULL };
+    uint64_t n_rays = 0, n_occl = 0;
+    const w3 c = shade(&pl, &g, wld(rd, 0), &n_rays, &n_occl);
+    rgb[0] = c.x;
+    rgb[1] = c.y;
+    rgb[2] = c.z;
+    return (int)n_occl;
 }
