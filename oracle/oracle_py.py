@@ -53,6 +53,18 @@ class Counters(C.Structure):
                 "prim_tests": int(self.prim_tests), "hits": int(self.hits)}
 
 
+class RayRecord(C.Structure):
+    _fields_ = [("parent", C.c_int32), ("kind", C.c_int32), ("depth", C.c_int32), ("seed", C.c_uint32), ("o", C.c_float * 3),
+                ("d", C.c_float * 3), ("tmin", C.c_float), ("tmax", C.c_float), ("hit", C.c_int32), ("prim", C.c_int32), ("t", C.c_float),
+                ("n", C.c_float * 3), ("payload", C.c_float * 3)]
+
+
+RAY_RECORD_DTYPE = np.dtype([("parent", "<i4"), ("kind", "<i4"), ("depth", "<i4"), ("seed", "<u4"), ("o", "<f4", 3), ("d", "<f4", 3),
+                             ("tmin", "<f4"), ("tmax", "<f4"), ("hit", "<i4"), ("prim", "<i4"), ("t", "<f4"), ("n", "<f4", 3),
+                             ("payload", "<f4", 3)])
+assert RAY_RECORD_DTYPE.itemsize == C.sizeof(RayRecord)
+
+
 class Node(C.Structure):
     _fields_ = [("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("left", C.c_int32), ("right", C.c_int32)]
 
@@ -155,6 +167,8 @@ def lib():
         L.oracle_lbvh_build.argtypes = [C.c_void_p, C.c_int, C.POINTER(Node), u32p, C.POINTER(C.c_int32)]
         L.oracle_render.restype = C.c_int
         L.oracle_render.argtypes = [C.POINTER(Scene), C.POINTER(Frame), C.c_void_p, C.c_void_p, C.POINTER(Counters)]
+        L.oracle_log_pixel.restype = C.c_int
+        L.oracle_log_pixel.argtypes = [C.POINTER(Scene), C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.oracle_local_rows.restype = C.c_uint32
         L.oracle_local_rows.argtypes = [C.c_uint32] * 4
         _lib = L
@@ -218,6 +232,27 @@ def render(sc, fr, accum_prev=None):
     ctr = Counters()
     lib().oracle_render(C.byref(sc), C.byref(fr), accum.ctypes.data, image.ctypes.data, C.byref(ctr))
     return accum, image, ctr.as_dict()
+
+
+def log_launch(sc, fr, accum_prev=None):
+    """oracle_log_pixel over every pixel of fr's window, row by row: (records: RAY_RECORD_DTYPE in call order, `parent` indexing this
+    array, -1 for raygen's own calls; pixel [records]: the flat index of each record's pixel in the window; accum [h, w, 4]; image [h, w, 4])"""
+    accum = np.zeros((fr.h, fr.w, 4), dtype=np.float32) if accum_prev is None else np.array(accum_prev, dtype=np.float32)
+    image = np.zeros((fr.h, fr.w, 4), dtype=np.uint8)
+    cap = 4 * fr.sqrt_spp * fr.sqrt_spp * (fr.max_depth + 2)       # a path: one radiance and at most one occlusion call per depth
+    buf = np.zeros(cap, dtype=RAY_RECORD_DTYPE)
+    parts, pixel, base = [], [], 0
+    for y in range(fr.h):
+        for x in range(fr.w):
+            n = lib().oracle_log_pixel(C.byref(sc), C.byref(fr), fr.x0 + x, fr.y0 + y, accum[y, x].ctypes.data, image[y, x].ctypes.data,
+                                       buf.ctypes.data, cap)
+            assert 0 < n <= cap
+            r = buf[:n].copy()
+            r["parent"][r["parent"] >= 0] += base
+            parts.append(r)
+            pixel.append(np.full(n, y * fr.w + x))
+            base += n
+    return np.concatenate(parts), np.concatenate(pixel), accum, image
 
 
 def lbvh(aabb):

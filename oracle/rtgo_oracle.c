@@ -597,6 +597,9 @@ typedef struct {
     const float (*inv)[16];   /* mode 1: hoisted inverses (bit-identical to the per-call inverse()) */
     const oracle_node* nodes; /* mode 1 */
     oracle_counters c;
+    /* the ray log (oracle_log_pixel): NULL otherwise */
+    oracle_ray_record* log;
+    int log_n, log_cap, log_parent;
 } tctx;
 
 typedef struct {
@@ -604,6 +607,45 @@ typedef struct {
     v3 n;
     int prim;
 } hit_t;
+
+/* opens the record of one trace call and makes it the parent of what its closest-hit program traces; returns its index */
+static int log_open(tctx* cx, int kind, v3 o, v3 d, float tmin, float tmax, int depth, uint32_t seed, int* saved_parent)
+{
+    const int k = cx->log_n++;
+    *saved_parent = cx->log_parent;
+    if (k < cx->log_cap) {
+        oracle_ray_record* r = &cx->log[k];
+        memset(r, 0, sizeof *r);
+        r->parent = cx->log_parent;
+        r->kind = kind;
+        r->depth = depth;
+        r->seed = seed;
+        st3(r->o, o);
+        st3(r->d, d);
+        r->tmin = tmin;
+        r->tmax = tmax;
+        r->prim = -1;
+    }
+    cx->log_parent = k;
+    return k;
+}
+
+static void log_hit(tctx* cx, int k, const hit_t* h)
+{
+    if (k < cx->log_cap) {
+        oracle_ray_record* r = &cx->log[k];
+        r->hit = 1;
+        r->prim = h->prim;
+        r->t = h->t;
+        st3(r->n, h->n);
+    }
+}
+
+static void log_close(tctx* cx, int k, v3 payload, int saved_parent)
+{
+    if (k < cx->log_cap) st3(cx->log[k].payload, payload);
+    cx->log_parent = saved_parent;
+}
 
 /* box test shared (bit for bit) with the HIP kernel: slab test with IEEE 1/d, fminf/fmaxf NaN-dropping */
 static inline int box_test(const oracle_node* nd, v3 o, v3 id, float tmin, float tmax, float* tn_out)
@@ -705,18 +747,22 @@ static int closest_hit(tctx* cx, v3 o, v3 d, float tmin, float tmax, hit_t* best
 /* forward */
 static void trace_radiance(tctx* cx, v3 o, v3 d, float tmin, float tmax, v3* prd, int depth, uint32_t seed);
 
-static void trace_occlusion(tctx* cx, v3 o, v3 d, float tmin, float tmax, v3* prd)
+static void trace_occlusion(tctx* cx, v3 o, v3 d, float tmin, float tmax, v3* prd, int depth)
 {
     /* trace(..., RAY_TYPE_OCCLUSION, ...) kernel.cu:46-79 + __closesthit__full_occlusion :539-549.
        miss: missSBTIndex 1 is out of bounds in the reference; de-facto the payload keeps its initial value. */
     hit_t h;
+    int saved = -1;
+    const int rec = cx->log ? log_open(cx, 1, o, d, tmin, tmax, depth, 0u, &saved) : -1;
     cx->c.rays_occlusion++;
     cx->c.rays_total++;
     if (closest_hit(cx, o, d, tmin, tmax, &h)) {
         const oracle_prim* p = &cx->sc->prims[h.prim];
         cx->c.hits++;
+        if (cx->log) log_hit(cx, rec, &h);
         *prd = V3(fminf(p->Le[0], 1.0f), fminf(p->Le[1], 1.0f), fminf(p->Le[2], 1.0f));
     }
+    if (cx->log) log_close(cx, rec, *prd, saved);
 }
 
 static void closesthit_ch(tctx* cx, const hit_t* h, v3 origin, v3 direction, v3* payload, int depth, uint32_t seed)
@@ -763,7 +809,7 @@ static void closesthit_ch(tctx* cx, const hit_t* h, v3 origin, v3 direction, v3*
         const v3 Lm = vnormalize(vsub(samplingPos, x));
         const float lightDistance = vlength(vsub(samplingPos, x));
         v3 illumination = V3(1.0f, 1.0f, 1.0f);
-        trace_occlusion(cx, x, Lm, rayEpsilon, lightDistance - rayEpsilon, &illumination);
+        trace_occlusion(cx, x, Lm, rayEpsilon, lightDistance - rayEpsilon, &illumination, depth);
         const v3 lightColor = vscale(illumination, fabsf(vdot(Lm, lightNormal)));
         const float falloff = 1.0f / (1.0f + L->falloff * lightDistance);
         const v3 compDiffuse =
@@ -797,14 +843,18 @@ static void trace_radiance(tctx* cx, v3 o, v3 d, float tmin, float tmax, v3* prd
 {
     /* trace(..., RAY_TYPE_RADIANCE, ...) kernel.cu:46-79: depth and seed travel by value */
     hit_t h;
+    int saved = -1;
+    const int rec = cx->log ? log_open(cx, 0, o, d, tmin, tmax, depth, seed, &saved) : -1;
     cx->c.rays_radiance[depth < 7 ? depth : 7]++;
     cx->c.rays_total++;
     if (closest_hit(cx, o, d, tmin, tmax, &h)) {
         cx->c.hits++;
+        if (cx->log) log_hit(cx, rec, &h);
         closesthit_ch(cx, &h, o, d, prd, depth, seed);
     } else {
         *prd = ld3(cx->sc->bg); /* __miss__ms, kernel.cu:419-423 */
     }
+    if (cx->log) log_close(cx, rec, *prd, saved);
 }
 
 uint32_t oracle_local_rows(uint32_t h, uint32_t band_h, uint32_t n_ranks, uint32_t rank)
@@ -921,4 +971,36 @@ int oracle_render(const oracle_scene* sc, const oracle_frame* fr, float* accum, 
     free(inv);
     free(nodes);
     return 0;
+}
+
+int oracle_log_pixel(const oracle_scene* sc, const oracle_frame* fr, uint32_t px, uint32_t py, float* accum4, uint8_t* image4,
+                     oracle_ray_record* records, int capacity)
+{
+    /* raygen_pixel for launch index (px, py) with every trace call recorded in call order; the window and bands of fr are not looked at */
+    const int n = sc->n_prims;
+    float(*inv)[16] = NULL;
+    oracle_node* nodes = NULL;
+    if (fr->mode == 1) {
+        inv = (float(*)[16])malloc(sizeof(float[16]) * (size_t)n);
+        nodes = (oracle_node*)malloc(sizeof(oracle_node) * (size_t)(2 * n));
+        uint32_t* code = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)n);
+        int32_t* order = (int32_t*)malloc(sizeof(int32_t) * (size_t)n);
+        for (int i = 0; i < n; ++i) oracle_mat_inverse(sc->prims[i].M, inv[i]);
+        oracle_lbvh_build(sc->aabb, n, nodes, code, order);
+        free(code);
+        free(order);
+    }
+    tctx cx;
+    memset(&cx, 0, sizeof cx);
+    cx.sc = sc;
+    cx.fr = fr;
+    cx.inv = (const float(*)[16])inv;
+    cx.nodes = nodes;
+    cx.log = records;
+    cx.log_cap = records ? capacity : 0;
+    cx.log_parent = -1;
+    raygen_pixel(&cx, px, py, accum4, image4);
+    free(inv);
+    free(nodes);
+    return cx.log_n;
 }

@@ -134,6 +134,22 @@ int oracle_lbvh_build(const float (*aabb)[6], int n, oracle_node* nodes, uint32_
    accum is read when frame_count > 0 (kernel.cu:239-244). counters may be NULL. returns 0. */
 int oracle_render(const oracle_scene* sc, const oracle_frame* fr, float* accum, uint8_t* image, oracle_counters* ctr);
 
+/* --- the ray log: one record per trace call of one pixel, in call order */
+typedef struct {
+    int32_t parent;   /* index of the record whose closest-hit program made this call; -1: raygen */
+    int32_t kind;     /* 0 radiance, 1 occlusion */
+    int32_t depth;    /* as passed */
+    uint32_t seed;    /* as passed (radiance; an occlusion ray's program reads none: 0) */
+    float o[3], d[3], tmin, tmax;
+    int32_t hit, prim; /* prim -1: miss */
+    float t, n[3];     /* the accepted hit: t and the intersector's un-normalised normal */
+    float payload[3];  /* what the call returned */
+} oracle_ray_record;
+/* raygen_pixel for launch index (px, py) of fr (its window and bands are not looked at); accum4 is read when frame_count > 0 and written,
+   image4 written, as oracle_render does for that pixel.  Returns the number of trace calls; records past `capacity` are not stored. */
+int oracle_log_pixel(const oracle_scene* sc, const oracle_frame* fr, uint32_t px, uint32_t py, float* accum4, uint8_t* image4,
+                     oracle_ray_record* records, int capacity);
+
 /* number of local rows a (window h, band_h, n_ranks, rank) owns */
 uint32_t oracle_local_rows(uint32_t h, uint32_t band_h, uint32_t n_ranks, uint32_t rank);
 
