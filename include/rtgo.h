@@ -343,6 +343,20 @@ int rtgo_whitted_set_scene(rtgo_ctx* ctx, const rtgo_whitted_mesh* meshes, uint3
    scene as it was; textures stay.  Synchronous. */
 int rtgo_whitted_set_instances(rtgo_ctx* ctx, const rtgo_whitted_instance* instances, uint32_t n_instances);
 
+/* optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE: new vertex positions (and normals) for mesh `mesh` of the scene the context
+   holds -- 0 for the mesh of rtgo_whitted_set_mesh, an index into the meshes of the last rtgo_whitted_set_scene otherwise.
+   Indices, materials, texture coordinates, textures, instances and lights stay.  The structure keeps its topology and its boxes are
+   refitted to the moved triangles (in an instanced scene the top level is rebuilt over the mesh's new box): no sort, no hierarchy,
+   no surface-area sweep, a fraction of the time of setting the mesh again.  The frame is bit for bit that of a scene set afresh with
+   the same vertices (any tree over the same triangles returns the same closest hit); what a refit cannot keep is the quality of the
+   tree, so after a deformation that moves neighbouring triangles far apart the walk slows down and setting the mesh again pays.
+   positions: n_vertices x 3 floats, copied; normals: the same, or NULL to keep the normals the mesh has.  RTGO_E_STATE: no whitted
+   scene.  RTGO_E_INVALID: `mesh` beyond the scene's meshes, positions NULL, n_vertices not the mesh's own, non-finite data, normals
+   for a mesh that was set without, an instance that now places the mesh beyond the float range.  RTGO_E_UNSUPPORTED: a clustered mesh
+   (beyond RTGO_MAX_TRIANGLES: its cluster and mid levels are not refitted yet -- set the scene again), or a top level deeper than the
+   walk's stack.  A refused call leaves the scene as it was.  Synchronous. */
+int rtgo_whitted_update_mesh(rtgo_ctx* ctx, uint32_t mesh, const float* positions, const float* normals, uint32_t n_vertices);
+
 /* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
    rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */
 

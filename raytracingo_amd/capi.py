@@ -25,7 +25,7 @@ SYMBOLS = [
     "rtgo_local_rows", "rtgo_abi_version", "rtgo_assemble_bands", "rtgo_set_large_scene",
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
-    "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays",
+    "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
 ]
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
@@ -169,6 +169,7 @@ def load():
     L.rtgo_whitted_set_material_textures.argtypes = [vp, C.c_uint32, C.POINTER(Texture), C.POINTER(Texture), C.POINTER(Texture)]
     L.rtgo_whitted_set_scene.argtypes = [vp, C.POINTER(WhittedMesh), C.c_uint32, C.POINTER(WhittedInstance), C.c_uint32, vp, C.c_uint32]
     L.rtgo_whitted_set_instances.argtypes = [vp, C.POINTER(WhittedInstance), C.c_uint32]
+    L.rtgo_whitted_update_mesh.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
@@ -372,6 +373,15 @@ class Context:
     def whitted_set_instances(self, instances):
         inst = whitted_instances(instances)
         self._check(self._lib.rtgo_whitted_set_instances(self._h, inst, len(instances)), "rtgo_whitted_set_instances")
+
+    def whitted_update_mesh(self, mesh, positions, normals=None):
+        """rtgo_whitted_update_mesh: new positions [nv, 3] (and normals, None keeps them) for mesh `mesh` of the scene, refitted in place"""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if nrm is not None and len(nrm) != len(pos):
+            raise ValueError("whitted_update_mesh: one normal per position")
+        self._check(self._lib.rtgo_whitted_update_mesh(self._h, int(mesh), pos.ctypes.data, nrm.ctypes.data if nrm is not None else None, len(pos)),
+                    "rtgo_whitted_update_mesh")
 
     def whitted_set_texcoords(self, uv):
         if uv is None:

@@ -1705,6 +1705,13 @@ int rtgo_whitted_set_instances(rtgo_ctx* c, const rtgo_whitted_instance* instanc
     return whitted_build_top(c, c->wm, shade, box_pos, instances, "rtgo_whitted_set_instances");
 }
 
+int rtgo_whitted_update_mesh(rtgo_ctx* c, uint32_t mesh, const float* positions, const float* normals, uint32_t n_vertices)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_update_mesh: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene first)");
+    return whitted_update_mesh(c, mesh, positions, normals, n_vertices);
+}
+
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
 {
     if (!c) return RTGO_E_INVALID;

@@ -30,7 +30,7 @@ struct WhittedMeshInfo {
     int depth;                 // stack entries its walk needs (a clustered mesh: its mid level's + its deepest cluster's)
     uint32_t max_material;     // its largest material_of_triangle
     bool clustered;            // beyond kMaxTriangles triangles: a mid level over clusters (rtgo_whitted_big.h)
-    int n_tris;
+    int n_tris, n_verts;
     // what each whitted_build of this mesh wrote into the context's arrays (rtgo_debug_build_digest): records [rec0, rec0 + n_recs) and
     // their quantised forms at qrecs[2 tri0 ..] (tri0 < 0: none kept, a mid level's)
     struct Built { int rec0, n_recs, tri0; whitted::WhittedBuildMeta meta; };   // (meta: what that build reported)
@@ -115,6 +115,7 @@ struct WhittedMesh {
     std::vector<WhittedMeshInfo> meshes;
     int mesh_depth = 0;                        // the deepest mesh walk
     WhittedTop top;
+    std::vector<rtgo_whitted_instance> instances;   // the caller's instances as last given (rtgo_whitted_update_mesh lays them out again)
     DeviceArray<int4> clusters;                // the clustered meshes' cluster tables (InstParams::clusters), or empty when there are none
 };
 

@@ -972,5 +972,103 @@ __global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4*
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Refit (optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE): the structure of one build over MOVED vertices, topology kept.  One
+// workgroup, n <= kMaxTriangles.  Keeps the Morton order (tris[3 i].w), tidx and every link; from the new positions it writes what
+// build_kernel + sah_kernel would write over this topology: the bounds and from them the pad and the grid (build_kernel's formulas,
+// word for word), the corners of `tris`, and every record's two boxes -- a leaf link's box from its triangles' corners -/+ pad, a
+// record link's box as the union of that record's two boxes (what both builds' fits compute: fminf / fmaxf are exact, so over unchanged
+// vertices the arrays come out bit for bit as built).  The records are fitted bottom-up in passes like build_kernel's fit: a record is
+// fitted in the pass after the records it links to.  done[r] = the pass that fitted record r (0: not yet); a stamp of the running pass
+// reads as "not yet", so one barrier per pass orders them.  The topology is read from `recs` alone, whichever build left it.
+// Writes out_meta's grid_lo / grid_step only (depth, n_recs and walk_depth stay).  Scratch: done[n_recs].
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBuildThreads) void refit_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n, int n_recs,
+                                                              int walk_depth, float4* recs, float4* tris, uint4* qrecs, int* done,
+                                                              WhittedBuildMeta* __restrict__ out_meta)
+{
+    __shared__ float s_red[6][kBuildThreads];
+    const int tid = threadIdx.x;
+    // scene bounds, pad and grid: build_kernel's
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = tid; i < n; i += kBuildThreads)
+        for (int k = 0; k < 3; ++k) {
+            const unsigned int vi = indices[3 * i + k];
+            for (int a = 0; a < 3; ++a) {
+                const float c = positions[3 * vi + a];
+                lo[a] = fminf(lo[a], c);
+                hi[a] = fmaxf(hi[a], c);
+            }
+        }
+    reduce_bounds<kBuildThreads>(s_red, tid, lo, hi);
+    float blo[3], ext[3], maxext = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        blo[a] = s_red[a][0];
+        ext[a] = s_red[3 + a][0] - s_red[a][0];
+        maxext = fmaxf(maxext, ext[a]);
+    }
+    const float pad = maxext * 1e-4f + 1e-6f;
+    float glo[3], gstep[3];
+    for (int a = 0; a < 3; ++a) {
+        glo[a] = blo[a] - pad;
+        gstep[a] = (ext[a] + 2.0f * pad) * (1.0f / 65533.0f);
+    }
+    if (tid == 0) {
+        out_meta->grid_lo = mk(glo[0], glo[1], glo[2]);
+        out_meta->grid_step = mk(gstep[0], gstep[1], gstep[2]);
+    }
+    // the triangles' corners, in the order they have
+    for (int i = tid; i < n; i += kBuildThreads) {
+        const unsigned int tri = (unsigned int)__float_as_int(tris[3 * i + 0].w);
+        const unsigned int i0 = indices[3 * tri + 0], i1 = indices[3 * tri + 1], i2 = indices[3 * tri + 2];
+        tris[3 * i + 0] = make_float4(positions[3 * i0 + 0], positions[3 * i0 + 1], positions[3 * i0 + 2], __int_as_float((int)tri));
+        tris[3 * i + 1] = make_float4(positions[3 * i1 + 0], positions[3 * i1 + 1], positions[3 * i1 + 2], 0.0f);
+        tris[3 * i + 2] = make_float4(positions[3 * i2 + 0], positions[3 * i2 + 1], positions[3 * i2 + 2], 0.0f);
+    }
+    for (int r = tid; r < n_recs; r += kBuildThreads) done[r] = 0;
+    __syncthreads();
+    // the box behind a link: a leaf's from its triangles, a record's from its two boxes (fitted in an earlier pass)
+    auto link_box = [&](int link, float4& b0, float4& b1) {
+        if (link < 0) {
+            const int code = -1 - link, first = code & ((1 << kLeafShift) - 1), cnt = (code >> kLeafShift) + 1;
+            float l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (int k = 3 * first; k < 3 * (first + cnt); ++k) {
+                const float4 c = tris[k];
+                l[0] = fminf(l[0], c.x); l[1] = fminf(l[1], c.y); l[2] = fminf(l[2], c.z);
+                h[0] = fmaxf(h[0], c.x); h[1] = fmaxf(h[1], c.y); h[2] = fmaxf(h[2], c.z);
+            }
+            b0 = make_float4(l[0] - pad, l[1] - pad, l[2] - pad, 0.0f);
+            b1 = make_float4(h[0] + pad, h[1] + pad, h[2] + pad, 0.0f);
+        } else {
+            const float4 q0 = recs[4 * link + 0], q1 = recs[4 * link + 1], q2 = recs[4 * link + 2], q3 = recs[4 * link + 3];
+            b0 = make_float4(fminf(q0.x, q2.x), fminf(q0.y, q2.y), fminf(q0.z, q2.z), 0.0f);
+            b1 = make_float4(fmaxf(q1.x, q3.x), fmaxf(q1.y, q3.y), fmaxf(q1.z, q3.z), 0.0f);
+        }
+    };
+    // leaves lie within the triangles and records within the records; anything else is never ready, and the passes run out
+    auto ready = [&](int link, int pass) {
+        if (link < 0) return ((-1 - link) & ((1 << kLeafShift) - 1)) + ((-1 - link) >> kLeafShift) < n;
+        const int stamp = link < n_recs ? done[link] : 0;
+        return stamp != 0 && stamp < pass;
+    };
+    if (n_recs == 0) return;   // the mesh is one leaf: the triangles and the grid are all of it
+    for (int pass = 1; pass <= walk_depth; ++pass) {   // (a record's height in the tree is at most walk_depth)
+        for (int r = tid; r < n_recs; r += kBuildThreads) {
+            if (done[r] != 0) continue;
+            const int la = __float_as_int(recs[4 * r + 0].w), lb = __float_as_int(recs[4 * r + 2].w);
+            if (!ready(la, pass) || !ready(lb, pass)) continue;
+            float4 a0, a1, b0, b1;
+            link_box(la, a0, a1);
+            link_box(lb, b0, b1);
+            write_walk_record(recs, qrecs, r, a0, a1, la, b0, b1, lb, glo, gstep);
+            done[r] = pass;
+        }
+        __syncthreads();
+        // the root is done (uniform: a thread already in the next pass can only turn a 0 into pass + 1, and both read as "not done")
+        const int root = done[0];
+        if (root != 0 && root <= pass) break;
+    }
+}
+
 }  // namespace whitted
 }  // namespace rtgo

@@ -209,19 +209,18 @@ static int whitted_prepare_instances(rtgo_ctx* c, const std::vector<WhittedMeshI
     return RTGO_OK;
 }
 
-// The top level of `wm` (its meshes built) over prepared instances: the structure over the instance boxes, the InstWalk records in leaf
-// order, and the stack both levels need.  Built aside: replaces wm's top level only once all of it succeeded.
-static int whitted_build_top(rtgo_ctx* c, WhittedMesh& wm, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos,
-                             const rtgo_whitted_instance* inst, const char* what)
+// The top level of `wm` (its meshes built) over prepared instances, into `top`: the structure over the instance boxes, the InstWalk records
+// in leaf order, and the stack both levels need (depth).  Nothing of wm changes.
+static int whitted_make_top(rtgo_ctx* c, const WhittedMesh& wm, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos,
+                            const rtgo_whitted_instance* inst, const char* what, WhittedTop& top, int& depth)
 {
     const int n = (int)shade.size();
     DeviceArray<float> d_boxes;
-    WhittedTop top;
     std::vector<int> order;
     RTGO_HIP(c, d_boxes.upload(box_pos.data(), box_pos.size(), c->stream));
     RTGO_HIP(c, top.recs.alloc((size_t)n * 4));
     if (const int rc = whitted_build_boxes(c, d_boxes.get(), n, top.recs.get(), order, top.meta, what)) return rc;
-    const int depth = (top.meta.n_recs > 0 ? top.meta.walk_depth : 0) + wm.mesh_depth;
+    depth = (top.meta.n_recs > 0 ? top.meta.walk_depth : 0) + wm.mesh_depth;
     if (depth > whitted::kMaxInstWalkDepth)
         return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
                                                std::to_string(whitted::kMaxInstWalkDepth) + ")");
@@ -236,8 +235,26 @@ static int whitted_build_top(rtgo_ctx* c, WhittedMesh& wm, const std::vector<whi
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     top.n_recs = top.meta.n_recs;
     top.n_instances = n;
+    return RTGO_OK;
+}
+
+// ... and that top level in wm's place
+static void whitted_install_top(WhittedMesh& wm, WhittedTop&& top, int depth)
+{
     wm.top = std::move(top);
     wm.walk_depth = depth < 1 ? 1 : depth;
+}
+
+// Both, for instances the caller hands in: built aside, wm's top level replaced only once all of it succeeded; wm keeps a copy of the
+// instances (rtgo_whitted_update_mesh lays them out again over a mesh's new box)
+static int whitted_build_top(rtgo_ctx* c, WhittedMesh& wm, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos,
+                             const rtgo_whitted_instance* inst, const char* what)
+{
+    WhittedTop top;
+    int depth = 0;
+    if (const int rc = whitted_make_top(c, wm, shade, box_pos, inst, what, top, depth)) return rc;
+    wm.instances.assign(inst, inst + shade.size());
+    whitted_install_top(wm, std::move(top), depth);
     return RTGO_OK;
 }
 
@@ -330,6 +347,25 @@ struct WhittedLayout {
     std::vector<unsigned int> idx, tmat;
 };
 
+// The box an instanced mesh's instances are laid out from (WhittedMeshInfo::lo / hi): the bounds of the vertices its triangles name, padded
+static void whitted_mesh_box(const float* positions, const uint32_t* indices, uint32_t n_triangles, float out_lo[3], float out_hi[3])
+{
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t i = 0; i < 3 * n_triangles; ++i)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::fmin(lo[a], positions[3 * indices[i] + a]);
+            hi[a] = std::fmax(hi[a], positions[3 * indices[i] + a]);
+        }
+    // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
+    float maxext = 0.0f;
+    for (int a = 0; a < 3; ++a) maxext = std::fmax(maxext, hi[a] - lo[a]);
+    const float pad = 2.0f * (maxext * 1e-4f + 1e-6f);
+    for (int a = 0; a < 3; ++a) {
+        out_lo[a] = lo[a] - pad;
+        out_hi[a] = hi[a] + pad;
+    }
+}
+
 // The stages of rtgo_whitted_set_scene.  Stage 1 (host only): every mesh as rtgo_whitted_set_mesh checks it, its padded box, where it will sit in the arrays, and packed there
 static int whitted_layout_meshes(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, uint32_t n_materials, WhittedLayout& lay)
 {
@@ -344,26 +380,14 @@ static int whitted_layout_meshes(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, u
             return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
         WhittedMeshInfo& mi = lay.info[k];
         if (const int rc = whitted_check_mesh(c, q, n_materials, at, mi.max_material)) return rc;
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::fmin(lo[a], q.positions[3 * q.indices[i] + a]);
-                hi[a] = std::fmax(hi[a], q.positions[3 * q.indices[i] + a]);
-            }
-        // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
-        float maxext = 0.0f;
-        for (int a = 0; a < 3; ++a) maxext = std::fmax(maxext, hi[a] - lo[a]);
-        const float pad = 2.0f * (maxext * 1e-4f + 1e-6f);
-        for (int a = 0; a < 3; ++a) {
-            mi.lo[a] = lo[a] - pad;
-            mi.hi[a] = hi[a] + pad;
-        }
+        whitted_mesh_box(q.positions, q.indices, q.n_triangles, mi.lo, mi.hi);
         mi.rec_base = (int)lay.n_tri;   // (a mesh of n triangles has fewer than n records)
         mi.tri_base = (int)lay.n_tri;
         mi.vert_base = (int)lay.n_vert;
         mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
         mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
         mi.n_tris = (int)q.n_triangles;
+        mi.n_verts = (int)q.n_vertices;
         lay.n_vert += q.n_vertices;
         lay.n_tri += q.n_triangles;
         if (mi.clustered) {
@@ -445,6 +469,80 @@ static int whitted_build_meshes(rtgo_ctx* c, WhittedMesh& wm, WhittedLayout& lay
     }
     if (!table.empty()) RTGO_HIP(c, wm.clusters.upload(table.data(), table.size(), c->stream));
     wm.meshes = lay.info;
+    return RTGO_OK;
+}
+
+// ---- refit (rtgo_whitted_update_mesh) -------------------------------------------------------------------------------------------
+// What rtgo_whitted_update_mesh needs to know of the mesh it moves: where it sits in wm's arrays and what its build reported
+struct WhittedRefitMesh { int vert_base, tri_base, rec_base, n_verts, n_tris; bool has_normals; WhittedBuildMeta meta; };
+
+// New vertices into the mesh's slice of wm's arrays and refit_kernel over its structure; `m.meta` gets the new grid.  Synchronous.
+static int whitted_refit(rtgo_ctx* c, WhittedMesh& wm, WhittedRefitMesh& m, const float* positions, const float* normals)
+{
+    float* d_pos = wm.positions.get() + 3 * (size_t)m.vert_base;
+    const size_t bytes = (size_t)m.n_verts * 3 * sizeof(float);
+    DeviceArray<int> done;                          // refit_kernel's flags, one per record
+    DeviceArray<WhittedBuildMeta> d_meta;
+    RTGO_HIP(c, done.alloc((size_t)std::max(m.meta.n_recs, 1)));
+    RTGO_HIP(c, d_meta.alloc(1));
+    RTGO_HIP(c, hipMemcpyAsync(d_pos, positions, bytes, hipMemcpyHostToDevice, c->stream));
+    if (normals) RTGO_HIP(c, hipMemcpyAsync(wm.normals.get() + 3 * (size_t)m.vert_base, normals, bytes, hipMemcpyHostToDevice, c->stream));
+    const WhittedBuildTarget t = whitted_target(wm, m.rec_base, m.tri_base);
+    hipLaunchKernelGGL(whitted::refit_kernel, dim3(1), dim3(whitted::kBuildThreads), 0, c->stream, (const float*)d_pos,
+                       (const unsigned int*)(wm.indices.get() + 3 * (size_t)m.tri_base), m.n_tris, m.meta.n_recs, m.meta.walk_depth, t.recs, t.tris, t.qrecs,
+                       done.get(), d_meta.get());
+    RTGO_HIP(c, hipGetLastError());
+    v3 grid[2];
+    RTGO_HIP(c, hipMemcpyAsync(grid, &d_meta.get()->grid_lo, sizeof grid, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    m.meta.grid_lo = grid[0];
+    m.meta.grid_step = grid[1];
+    return RTGO_OK;
+}
+
+// rtgo_whitted_update_mesh once the scene is known to exist: every check on the host first, and for an instanced scene the new top level
+// built aside (it needs only the mesh's new box) -- a refused call leaves the scene as it was; then the refit, then what the host keeps.
+static int whitted_update_mesh(rtgo_ctx* c, uint32_t mesh, const float* positions, const float* normals, uint32_t n_vertices)
+{
+    const char* what = "rtgo_whitted_update_mesh";
+    const std::string w(what);
+    WhittedMesh& wm = c->wm;
+    if (mesh >= (wm.instanced ? wm.meshes.size() : (size_t)1)) return fail(c, RTGO_E_INVALID, w + ": mesh index beyond the scene's meshes");
+    if (!positions) return fail(c, RTGO_E_INVALID, w + ": NULL positions");
+    WhittedRefitMesh m = {0, 0, 0, wm.n_vertices, wm.triangles, wm.normals.get() != nullptr, wm.meta};
+    if (wm.instanced) {
+        const WhittedMeshInfo& mi = wm.meshes[mesh];
+        if (mi.clustered)
+            return fail(c, RTGO_E_UNSUPPORTED, w + ": a mesh beyond " + std::to_string(RTGO_MAX_TRIANGLES) + " triangles (clustered) takes new vertices through rtgo_whitted_set_scene");
+        m = {mi.vert_base, mi.tri_base, mi.rec_base, mi.n_verts, mi.n_tris, (mi.flags & whitted::kHasNormals) != 0, mi.built[0].meta};
+    }
+    if (n_vertices != (uint32_t)m.n_verts) return fail(c, RTGO_E_INVALID, w + ": the mesh has " + std::to_string(m.n_verts) + " vertices");
+    if (normals && !m.has_normals) return fail(c, RTGO_E_INVALID, w + ": normals for a mesh that was set without");
+    for (size_t i = 0; i < (size_t)3 * n_vertices; ++i)
+        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) return fail(c, RTGO_E_INVALID, w + ": non-finite vertex data");
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (!wm.instanced) {
+        if (const int rc = whitted_refit(c, wm, m, positions, normals)) return rc;
+        wm.meta = m.meta;
+        return RTGO_OK;
+    }
+    // the mesh's new box (its indices are on the device only), every instance laid out again, the top level over them
+    std::vector<uint32_t> idx((size_t)3 * m.n_tris);
+    RTGO_HIP(c, hipMemcpyAsync(idx.data(), wm.indices.get() + 3 * (size_t)m.tri_base, idx.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<WhittedMeshInfo> meshes = wm.meshes;
+    whitted_mesh_box(positions, idx.data(), (uint32_t)m.n_tris, meshes[mesh].lo, meshes[mesh].hi);
+    std::vector<whitted::InstShade> shade;
+    std::vector<float> box_pos;
+    if (const int rc = whitted_prepare_instances(c, meshes, (uint32_t)wm.n_materials, wm.instances.data(), (uint32_t)wm.instances.size(), shade, box_pos, what)) return rc;
+    WhittedTop top;
+    int depth = 0;
+    if (const int rc = whitted_make_top(c, wm, shade, box_pos, wm.instances.data(), what, top, depth)) return rc;
+    if (const int rc = whitted_refit(c, wm, m, positions, normals)) return rc;
+    meshes[mesh].built[0].meta = m.meta;
+    wm.meshes = std::move(meshes);
+    whitted_install_top(wm, std::move(top), depth);
     return RTGO_OK;
 }
 

@@ -20,6 +20,7 @@ def kernels(path):
                 cur = None
                 continue
             line = line.split(";")[0].strip()
+            line = re.sub(r"\.L([A-Za-z]+)\d+_(\d+)", r".L\1_\2", line)   # local labels carry the function's ordinal in the file: a new kernel shifts it
             if line and not line.startswith((".p2align", ".loc", ".file", ".cfi")):
                 cur.append(line)
     return out
