@@ -23,12 +23,14 @@ struct RenderKernelEntry {
     bool grid = false;
     bool global = false;   // the canonical walk over a scene in global memory (rtgo_set_large_scene)
     bool batch = false;    // render_frames_kernel: the frames of rtgo_launch_frames in one launch
+    bool pair = false;     // render_pair_kernel: the straight-line walk of a two-leaf tree (fast_pair)
 };
 #define RTGO_K(P, S, W, T) {P, S, T, W, S, false, render_kernel<P, S, W, T>}
 #define RTGO_KF(W, T) {true, false, T, W, false, true, render_kernel<true, false, W, T, false, true>}
 #define RTGO_KG(P, W, T) {P, false, T, W, false, false, render_kernel<P, false, W, T, false, false, true>, true}
 #define RTGO_KL(P, C) {P, true, false, 4, C, false, render_kernel<P, true, 4, false, C, false, false, true>, false, true}
 #define RTGO_KB(P, W, F) {P, false, false, W, false, F, render_frames_kernel<P, W, F>, false, false, true}
+#define RTGO_KP(W) {true, false, false, W, false, true, render_pair_kernel<W>, false, false, false, true}
 static const RenderKernelEntry kRenderKernels[] = {
     RTGO_K(true, false, 4, false),  RTGO_K(true, false, 5, false),    // path mode, fast walk
     RTGO_K(false, false, 4, false), RTGO_K(false, false, 5, false),   // distributed mode, fast walk
@@ -44,17 +46,19 @@ static const RenderKernelEntry kRenderKernels[] = {
     RTGO_KL(true, false), RTGO_KL(false, false), RTGO_KL(true, true), RTGO_KL(false, true),   // scenes of rtgo_set_large_scene: timed, collect_stats
     RTGO_KB(true, 4, false), RTGO_KB(true, 5, false), RTGO_KB(true, 4, true), RTGO_KB(true, 5, true),   // several frames per launch (rtgo_launch_frames): lock-step, over a tree
     RTGO_KB(false, 4, false), RTGO_KB(false, 5, false),
+    RTGO_KP(6), RTGO_KP(5),   // path mode, flat scene, lock-step, a tree of two cuboid leaves (cornell): the bench launch, and a band share of it
 };
 #undef RTGO_K
 #undef RTGO_KF
 #undef RTGO_KG
 #undef RTGO_KL
 #undef RTGO_KB
-static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, bool count, bool frames, bool grid, bool global = false, bool batch = false)
+#undef RTGO_KP
+static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, bool count, bool frames, bool grid, bool global = false, bool batch = false, bool pair = false)
 {
     for (const RenderKernelEntry& e : kRenderKernels)
         if (e.path == path && e.canon == canon && e.wpe == (canon ? 4 : wpe) && e.stream == (canon ? false : stream) && e.count == (canon && count) &&
-            e.frames == (frames && path && !canon) && e.grid == (grid && !canon) && e.global == (global && canon) && e.batch == batch)
+            e.frames == (frames && path && !canon) && e.grid == (grid && !canon) && e.global == (global && canon) && e.batch == batch && e.pair == pair)
             return e.fn;
     return nullptr;
 }
@@ -89,6 +93,7 @@ struct Knobs {
     bool no_frames = std::getenv("RTGO_NO_FRAMES") != nullptr;      // flat scenes compute N and the sampling tangent per hit
     bool no_cuboid = std::getenv("RTGO_NO_CUBOID") != nullptr;      // the build certifies no cuboids
     bool no_last_emitter = std::getenv("RTGO_NO_LAST_EMITTER") != nullptr;   // launches go without the last-ray certificate
+    bool no_pair = std::getenv("RTGO_NO_PAIR") != nullptr;          // two-leaf trees are walked by fast_tree like every other (render_pair_kernel is not taken)
     bool pin_big = std::getenv("RTGO_BIG_PERCENT") != nullptr;      // one fast-walk structure, of big_percent (else 36 % and 15 %)
     unsigned int big_percent = env_uint("RTGO_BIG_PERCENT", 36);
     unsigned int max_wpe = env_uint("RTGO_MAX_WPE", 0);             // cap of the waves-per-SIMD variant; 0: by the work
@@ -711,6 +716,18 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
     t.cub_a = meta.cub_a;
     t.cub_b = meta.cub_b;
     t.n_fnodes = meta.n_fnodes;
+    // fast_pair's shape: three nodes, the root's links 1 and 2, both of them leaves certified as cuboids, the root's box the union of theirs
+    t.pair = false;
+    if (meta.n_small > 0 && meta.n_fnodes == 3 && meta.cuboid_leaves == 2) {
+        float4 nd[6];
+        RTGO_HIP(c, hipMemcpyAsync(nd, t.d_fnodes.get(), sizeof nd, hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        auto link = [&](int k) { int v; std::memcpy(&v, &nd[k].w, sizeof v); return v; };
+        auto cuboid = [&](int node) { const int r = link(2 * node + 1); return link(2 * node) >= 0 && r < 0 && leaf_cuboid(r) != 0 && leaf_count(r) == 6; };
+        const bool boxed = nd[0].x == std::fmin(nd[2].x, nd[4].x) && nd[0].y == std::fmin(nd[2].y, nd[4].y) && nd[0].z == std::fmin(nd[2].z, nd[4].z) &&
+                           nd[1].x == std::fmax(nd[3].x, nd[5].x) && nd[1].y == std::fmax(nd[3].y, nd[5].y) && nd[1].z == std::fmax(nd[3].z, nd[5].z);
+        t.pair = link(0) == 1 && link(1) == 2 && cuboid(1) && cuboid(2) && boxed;
+    }
     return RTGO_OK;
 }
 
@@ -1566,10 +1583,16 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     const bool frames = path && !canon && c->scene.quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
     Block b;
     if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b, false, batch)) return rc;
+    // The straight-line walk of a two-leaf tree (render_pair_kernel, fast_pair): path mode over a flat scene with frames, the lock-step loop,
+    // one frame per launch, inside the far-field guard, over a tree (not the grid) that is a root over two certified cuboid leaves, the
+    // cuboid margin still positive at this launch's reach -- and a variant at the waves per SIMD pick_block chose (5 and 6).  RTGO_NO_PAIR: off.
+    const bool pair_ok = path && !canon && !pk.stream && frames && !use_grid && !batch && !kn.no_pair && c->scene.tree[use_alt ? 1 : 0].pair && p.cub_mu > 0.0f;
+    const RenderKernel pair_kernel = pair_ok ? find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch, true) : nullptr;
+    const RenderKernel kernel = pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch);
     if (kn.debug)
-        std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g\n",
-                     n_frames, canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric);
-    const RenderKernel kernel = find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch);
+        std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g, kernel %s<%d>\n",
+                     n_frames, canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric,
+                     pair_kernel ? "render_pair_kernel" : (batch ? "render_frames_kernel" : "render_kernel"), b.wpe);
     if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
     const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels;
     std::vector<uint32_t> seeds_key;
@@ -1578,6 +1601,7 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     c->seeds.ok = false;   // (until this launch is on the stream)
     if (const int rc = enqueue(c, kernel, p, b, pk, canon, culled * nn * n_frames)) return rc;
     if (batch) c->last_variant |= 128u;
+    if (pair_kernel) c->last_variant |= 256u;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
         c->seeds.read = 1 - c->seeds.read;

@@ -57,6 +57,7 @@ struct AnalyticScene {
         int fast_depth = 0, n_small = 0, n_fnodes = 0;   // its depth, primitives (the rest are tested up front) and nodes
         int cuboid_groups = 0;             // certified groups in the scene (leaves + the list's)
         int tree_spheres = 0;              // every primitive of the tree is a sphere
+        bool pair = false;                 // the tree is node 0 over the leaves 1 and 2, both certified cuboids: what render_pair_kernel walks
         int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
         float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
         // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and

@@ -870,6 +870,39 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
     }
 }
 
+// fast_pair: fast_tree over a tree that is a root (node 0) over two leaves (nodes 1 and 2), both certified cuboids -- cornell's two boxes;
+// the launch vouches for that shape (rtgo_capi.hip, FastTree::pair) -- as straight-line code.  The same leaf tests on the same values for
+// every lane: both child boxes against the list's closest hit, the nearer hit child's leaf (go_r, as fast_tree steps), then the other
+// one's for the lanes that hit both boxes and whose far entry distance, cut to its upper 16 bits like fast_tree's stack word, is still
+// <= the closest hit.  What is gone is the machinery of a deep tree: the root's own box test (the root box is the union of the two, and
+// fma(q, id, noid) is monotone in q: a lane that passes a child's slab test passes the root's), the while-while loop, the stack word
+// in LDS, the pop loop with its dependent reads of a node's links, and the leaf's dispatch on tree_spheres / leaf_cuboid / cub_mu.
+__device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims, float cub_mu, v3 o, v3 d, float tmin, FastHit& best,
+                                          unsigned int& dbg_boxes, unsigned int& dbg_tests)
+{
+    auto safe_rcp = [](float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(x), -1e30f, 1e30f); };   // (see fast_tree on 1 / 0)
+    const v3 id = mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+    const v3 noid = mk(-(o.x * id.x), -(o.y * id.y), -(o.z * id.z));
+    // (wave-uniform addresses: four reads under one wait; a leaf's first record comes with its box)
+    const float4 l0 = s_fnodes[2], l1 = s_fnodes[3], h0 = s_fnodes[4], h1 = s_fnodes[5];
+    float tl, tr;
+    FastCounters::step(dbg_boxes, 2u);
+    const bool hl = box_fast(l0, l1, id, noid, tmin, best.t, tl);
+    const bool hr = box_fast(h0, h1, id, noid, tmin, best.t, tr);
+    const bool go_r = hr & (!hl | (tr < tl));
+    if (hl | hr) {
+        FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(go_r ? h1.w : l1.w)));
+        cuboid_range<false>(s_fprims, s_fprims, __float_as_int(go_r ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
+    }
+    const bool far = hl & hr & (__uint_as_float(__float_as_uint(go_r ? tl : tr) & 0xFFFF0000u) <= best.t);
+    if (__ballot(far) != 0ull) {
+        if (far) {
+            FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(go_r ? l1.w : h1.w)));
+            cuboid_range<false>(s_fprims, s_fprims, __float_as_int(go_r ? l0.w : h0.w), cub_mu, -INFINITY, o, d, tmin, best);
+        }
+    }
+}
+
 // fast_grid: the same job as fast_tree over a uniform grid (Amanatides & Woo's walk, one lane = one ray).  The host bins every small
 // primitive into the cells its box -- grown by a pad that is far above the rounding of the walk -- overlaps; a lane steps from cell to
 // cell along its ray, tests what the cell lists through the same leaf tests as the tree (so an accepted hit is the tree's and the
@@ -999,7 +1032,8 @@ __device__ __forceinline__ bool fast_winner(const float4* __restrict__ s_fprims,
 // room (fast_list), tests the emitters as the list always does, and, when it hits none, is done: no hit, payload = the background (+0,
 // like the term of a non-emitter hit).  When it hits one, the tree walks from `best` = that hit: the closest hit does not depend on the
 // order in which candidates are met (closer()).  LAST: the instantiation has this path at all (else `last` is ignored).
-template <bool GRID, bool LAST = false>
+// PAIR (render_pair_kernel): the tree is a root over two cuboid leaves, walked by fast_pair.
+template <bool GRID, bool LAST = false, bool PAIR = false>
 __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims,
                                                  const float4* __restrict__ g_fprims, const GridParams grid,
  unsigned int* __restrict__ s_stack, int bshift,
@@ -1016,7 +1050,9 @@ __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fn
     FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (last ? 6 : 0)));
     tl.list_done(best.pos);
     if constexpr (GRID) fast_grid(s_fnodes, s_fprims, grid, tree_spheres, o, d, tmin, best, dbg_boxes, dbg_tests);
-    else if (!LAST || walk) fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
+    else if constexpr (PAIR) {
+        if (!LAST || walk) fast_pair(s_fnodes, s_fprims, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests);
+    } else if (!LAST || walk) fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
     tl.walk_done(best.pos);
     return fast_winner(s_fprims, o, d, tmax, best, out);
 }
@@ -1282,7 +1318,7 @@ __device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned
 template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false, bool GLOBAL = false>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = false;
+    constexpr bool BATCH = false, PAIR = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1290,7 +1326,17 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <bool PATH, int WPE, bool FRAMES>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_frames_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false;
+    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false;
+#include "rtgo_render_body.inc"
+}
+
+// PAIR: path mode over a flat scene whose fast-walk tree is a root over two certified cuboid leaves (cornell: the short and the tall box),
+// lock-step, one frame per launch.  render_kernel<true, false, WPE, false, false, true> with fast_pair in fast_tree's place; at 6 waves it
+// keeps all that kernel has (LEAN, params_here, the seed pass, LASTRAY).  The host takes it where the launch qualifies (rtgo_capi.hip).
+template <int WPE>
+__global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_pair_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
+{
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true;
 #include "rtgo_render_body.inc"
 }
 

@@ -2,7 +2,14 @@
 import collections, csv, glob, json, os, sys
 
 d, tag = sys.argv[1], sys.argv[2]
-KERNEL = "render_kernel<true, false"   # any register-budget variant of the timed path-mode kernel
+KERNEL = "render_kernel<true, false"   # any register-budget variant of the timed path-mode kernel ...
+PAIR = "render_pair_kernel<"           # ... or of the one that walks a two-leaf tree (cornell)
+
+
+def timed(name):
+    return KERNEL in name or PAIR in name
+
+
 head = os.environ.get("RTGO_HEAD")   # the commit the profiled tree is (the GPU box has no .git); a re-run of this script keeps what the first run recorded
 if not head:
     try:
@@ -18,17 +25,18 @@ except Exception as e:
 # both and the faster keeps the job (rtgo_launch).  The profile describes the one that kept it: the instantiation with the most calls.
 dominant = None
 for f in glob.glob(os.path.join(d, "trace", "**", "*kernel_stats.csv"), recursive=True):
-    rows = [r for r in csv.DictReader(open(f)) if KERNEL in r["Name"]]
+    rows = [r for r in csv.DictReader(open(f)) if timed(r["Name"])]
     if rows:
         r = max(rows, key=lambda q: int(q["Calls"]))
         dominant = r["Name"]
+        out["kernel"] = dominant.split("(")[0].replace("void ", "")
         out["kernel_trace"] = {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) / 1e6, "min_ms": float(r["MinNs"]) / 1e6,
                                "max_ms": float(r["MaxNs"]) / 1e6, "pct_of_gpu_time": float(r["Percentage"]), "name": r["Name"][:120],
                                "other_instantiations": [{"name": q["Name"][:120], "calls": int(q["Calls"]), "avg_ms": float(q["AverageNs"]) / 1e6} for q in rows if q is not r]}
     out["kernel_stats_csv"] = os.path.basename(f)
 ctr = collections.defaultdict(list)
 for f in glob.glob(os.path.join(d, "pmc*", "**", "*counter_collection.csv"), recursive=True):
-    rows = [r for r in csv.DictReader(open(f)) if KERNEL in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(f)) if timed(r["Kernel_Name"])]
     names = collections.Counter(r["Kernel_Name"] for r in rows)
     keep = dominant if dominant in names else (names.most_common(1)[0][0] if names else None)
     for r in rows:
@@ -76,7 +84,7 @@ with open(os.path.join(d, "summary.md"), "w") as f:
         f.write("bench: %.1f %s, %.4f ms/step, roofline frac %.3f (kernel %.4f ms by HIP events)\n\n" %
                 (b["value"], b["unit"], b["ms_per_step"], b["roofline"]["frac"], b["roofline"]["kernel_ms"]))
     if "kernel_trace" in out:
-        f.write("rocprofv3 --kernel-trace --stats: %s avg %.4f ms over %d calls\n\n" % (KERNEL, out["kernel_trace"]["avg_ms"], out["kernel_trace"]["calls"]))
+        f.write("rocprofv3 --kernel-trace --stats: %s avg %.4f ms over %d calls\n\n" % (out["kernel_trace"]["name"].split("(")[0], out["kernel_trace"]["avg_ms"], out["kernel_trace"]["calls"]))
     if "hbm_traffic_bytes_per_launch" in out:
         f.write("HBM traffic per launch (PMC): %.1f MB\n\n" % (out["hbm_traffic_bytes_per_launch"] / 1e6))
     for k in sorted(c):
