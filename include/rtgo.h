@@ -400,7 +400,10 @@ enum { RTGO_TRACE_CLOSEST = 0, RTGO_TRACE_ANY_HIT = 1 };
    threshold of their own (1e-4, a cylinder 1e-3; units of dir), a rectangle from its front side only, a sphere at its near root only. */
 int rtgo_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags);
 
-/* The same over the scene of rtgo_whitted_set_mesh / rtgo_whitted_set_scene. */
+/* The same over the scene of rtgo_whitted_set_mesh / rtgo_whitted_set_scene.  The answer is the brute force over the triangle test
+   (closest t, lowest (instance, triangle) on ties) except for that test's phantom hits: where a ray lies within rounding of a triangle's
+   plane, or the triangle is a sliver of aspect ~1e4, the float32 test can accept a hit on a ray that does not meet the triangle's bounds;
+   the walk, which culls by boxes, may then report the next hit instead. */
 int rtgo_whitted_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags);
 
 /* number of window rows a rank owns under the band interleave (pure host arithmetic) */

@@ -727,10 +727,18 @@ __device__ __forceinline__ void write_walk_record(float4* __restrict__ recs, uin
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The pad of every box the builds write: 1e-4 of the scene's extent + 1e-6, and at least two floats at the bounds' largest coordinate
+// (`reach`).  Far from the origin -- vertex data at 1e4, where one float is 1e-3 -- the first alone rounds away, lo - pad == lo, and a
+// box face lies ON the vertices it bounds: a ray in that face plane (a zero direction component, an origin coordinate equal to the
+// plane's) then has a slab interval that ends at -0 or starts at +0 and is cut off from a triangle it meets.  With 2^-22 reach every
+// coordinate c of the scene has c - pad < c and c + pad > c.  Wherever reach is below ~420 extents this is the first term, bit for bit.
+__host__ __device__ inline float box_pad(float maxext, float reach) { return fmaxf(maxext * 1e-4f + 1e-6f, reach * 2.3841858e-7f); }
+
 // LBVH over the triangles, one workgroup: replaces optixAccelBuild over OPTIX_BUILD_INPUT_TYPE_TRIANGLES (sutil/Scene.cpp,
 // buildMeshAccels).  Same recipe as the analytic path's canonical tree, with rtgo_build.h's functions: 30-bit Morton code of the
 // centroid normalised to the scene bounds, stable order by (code, triangle index), Karras 2012, one triangle per leaf, bottom-up fit.
-// Boxes are padded by 1e-4 of the scene's extent + 1e-6: the slab test rounds, the triangle test must never be cut off.
+// Boxes are padded by box_pad (1e-4 of the scene's extent + 1e-6, or two floats at its largest coordinate): the slab test rounds, the
+// triangle test must never be cut off.
 // ---------------------------------------------------------------------------------------------------------------------
 // The work arrays of one build of n triangles (host side: whitted_build), carved out of build_scratch_ints(n) ints: parent [2n - 1], visit,
 // first, count, record [n each], 16 words for the meta, sah_kernel's 32 n
@@ -773,13 +781,14 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
             }
         }
     reduce_bounds<kBuildThreads>(s_red, tid, lo, hi);
-    float blo[3], ext[3], maxext = 0.0f;
+    float blo[3], ext[3], maxext = 0.0f, reach = 0.0f;
     for (int a = 0; a < 3; ++a) {
         blo[a] = s_red[a][0];
         ext[a] = s_red[3 + a][0] - s_red[a][0];
         maxext = fmaxf(maxext, ext[a]);
+        reach = fmaxf(reach, fmaxf(fabsf(s_red[a][0]), fabsf(s_red[3 + a][0])));
     }
-    const float pad = maxext * 1e-4f + 1e-6f;
+    const float pad = box_pad(maxext, reach);
     // Morton keys, sorted (unique: the index is part of the key)
     for (int i = tid; i < kMaxTriangles; i += kBuildThreads) s_keys[i] = i < n ? triangle_key(positions, indices, i, blo, ext) : ~0ull;
     bitonic_sort<kMaxTriangles, kBuildThreads>(s_keys, tid);
@@ -1001,13 +1010,14 @@ __global__ __launch_bounds__(kBuildThreads) void refit_kernel(const float* __res
             }
         }
     reduce_bounds<kBuildThreads>(s_red, tid, lo, hi);
-    float blo[3], ext[3], maxext = 0.0f;
+    float blo[3], ext[3], maxext = 0.0f, reach = 0.0f;
     for (int a = 0; a < 3; ++a) {
         blo[a] = s_red[a][0];
         ext[a] = s_red[3 + a][0] - s_red[a][0];
         maxext = fmaxf(maxext, ext[a]);
+        reach = fmaxf(reach, fmaxf(fabsf(s_red[a][0]), fabsf(s_red[3 + a][0])));
     }
-    const float pad = maxext * 1e-4f + 1e-6f;
+    const float pad = box_pad(maxext, reach);
     float glo[3], gstep[3];
     for (int a = 0; a < 3; ++a) {
         glo[a] = blo[a] - pad;

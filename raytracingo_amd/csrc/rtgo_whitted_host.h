@@ -357,9 +357,12 @@ static void whitted_mesh_box(const float* positions, const uint32_t* indices, ui
             hi[a] = std::fmax(hi[a], positions[3 * indices[i] + a]);
         }
     // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
-    float maxext = 0.0f;
-    for (int a = 0; a < 3; ++a) maxext = std::fmax(maxext, hi[a] - lo[a]);
-    const float pad = 2.0f * (maxext * 1e-4f + 1e-6f);
+    float maxext = 0.0f, reach = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        maxext = std::fmax(maxext, hi[a] - lo[a]);
+        reach = std::fmax(reach, std::fmax(std::fabs(lo[a]), std::fabs(hi[a])));
+    }
+    const float pad = 2.0f * whitted::box_pad(maxext, reach);
     for (int a = 0; a < 3; ++a) {
         out_lo[a] = lo[a] - pad;
         out_hi[a] = hi[a] + pad;
