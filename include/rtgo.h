@@ -118,7 +118,8 @@ typedef struct rtgo_stats {
                                  rtgo_set_large_scene; always with bit 2), bit 6 path mode under the last-ray certificate (a path's last
                                  ray tests the emitters and skips the room), bit 7 the last call rendered more than one
                                  frame in one kernel launch (rtgo_launch_frames' batched kernels),
-                                 bit 8 the straight-line walk of a two-leaf tree (render_pair_kernel) */
+                                 bit 8 the straight-line walk of a two-leaf tree (render_pair_kernel),
+                                 bit 9 that walk's kernel at seven waves per SIMD (render_pair7_kernel; always with bit 8) */
     uint32_t launches_trial;  /* launches since rtgo_reset_stats that were trial launches */
 } rtgo_stats;
 

@@ -47,6 +47,7 @@ static const RenderKernelEntry kRenderKernels[] = {
     RTGO_KB(true, 4, false), RTGO_KB(true, 5, false), RTGO_KB(true, 4, true), RTGO_KB(true, 5, true),   // several frames per launch (rtgo_launch_frames): lock-step, over a tree
     RTGO_KB(false, 4, false), RTGO_KB(false, 5, false),
     RTGO_KP(6), RTGO_KP(5),   // path mode, flat scene, lock-step, a tree of two cuboid leaves (cornell): the bench launch, and a band share of it
+    {true, false, false, 7, false, true, render_pair7_kernel, false, false, false, true},   // ... at 7 waves/SIMD (72 VGPRs): launches of many units per wave
 };
 #undef RTGO_K
 #undef RTGO_KF
@@ -1417,6 +1418,7 @@ static int plan_seeds(rtgo_ctx* c, LaunchParams& p, uint32_t strip_px, bool has_
 }
 
 static constexpr uint64_t kUnitsPerWave4For6 = 8;   // launches with fewer units per wave (counted at 4 waves/SIMD) take at most 5 waves (pick_block)
+static constexpr uint64_t kUnitsPerWave4For7 = 26;  // ... and with fewer than this at most 6: halfway between the tie at 17 and the win at 35 (pick_block)
 
 struct Block {
     int block = 0, blocks_per_cu = 0, wpe = 4;   // threads per workgroup, workgroups per CU, waves per SIMD of the variant
@@ -1427,10 +1429,10 @@ struct Block {
 // LDS image of the chosen kernel (see render_kernel): canonical = nodes + 6/prim; fast = fnodes + 4/prim + 3/prim; global (a scene of
 // rtgo_set_large_scene): no scene at all.
 // The scene copy is per workgroup and the stack per lane, so bigger scenes want bigger workgroups: pick the size that
-// puts the most waves on a CU (4, 5 or 6 per SIMD, what the variant's VGPR budget admits), smallest size on ties.  Without a scene copy
+// puts the most waves on a CU (4, 5, 6 or 7 per SIMD, what the variant's VGPR budget admits), smallest size on ties.  Without a scene copy
 // the stack alone sets the count, and workgroups of one or two waves fit the most of them.
 static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, uint32_t nn, bool canon, bool stream, bool frames, bool grid,
-                      uint64_t units_hot, const Knobs& kn, Block& b, bool global = false, bool batch = false)
+                      uint64_t units_hot, const Knobs& kn, Block& b, bool global = false, bool batch = false, bool pair = false)
 {
     const bool path = f->path_tracing != 0;
     const int fast_nodes = p.n_fnodes;   // (the tree's nodes, or the grid in their place)
@@ -1446,13 +1448,19 @@ static int pick_block(rtgo_ctx* c, const rtgo_frame* f, const LaunchParams& p, u
     // HBM per launch, profiles/r02d) and was dropped; today's fits because the per-lane values derived from the lane index are
     // derived where they are used (opaque_lane in rtgo_device.h) instead of being held through every ray loop.
     const uint64_t units_per_wave4 = units_hot * (passes_of(nn)) / ((uint64_t)c->num_cus * 16u);
-    const int top_wpe = find_kernel(path, canon, 6, stream, false, frames, grid, global, batch) ? 6 : 5;   // the 6-waves variant exists for some combinations only
-    const int max_wpe_work = units_per_wave4 >= kUnitsPerWave4For6 ? 6 : (units_per_wave4 >= 3 ? 5 : 4);
+    // `pair`: the launch qualifies for the pair kernels (launch_frame), which exist at 5, 6 and 7 waves -- 7 (<= 72 VGPRs) for them alone --
+    // and never touch the traversal stack: at those waves the launch reserves none (launch_frame then sets p.stack_depth to 0).  Seven
+    // waves are 7 workgroups of 256 threads per CU; where the LDS image does not fit 7, no block size beats 6 waves' 24 and 6 stays.
+    const auto is_pair = [&](int w) { return pair && find_kernel(path, canon, w, stream, false, frames, grid, global, batch, true) != nullptr; };
+    const int top_wpe = is_pair(7) ? 7 : (find_kernel(path, canon, 6, stream, false, frames, grid, global, batch) ? 6 : 5);   // the 6-waves variant exists for some combinations only
+    // 7 against 6 (profiles/r09a/threshold.log, cornell 1080p and its band shares): the full frame (35 units per wave) 0.6965 -> 0.6854 ms,
+    // ranges apart; the 1/2 share (17) ties; the 1/3, 1/4 and 1/8 shares (11, 8, 4) lose 1.5, 2.6 and 10 % to the longer tail.
+    const int max_wpe_work = units_per_wave4 >= kUnitsPerWave4For7 ? 7 : (units_per_wave4 >= kUnitsPerWave4For6 ? 6 : (units_per_wave4 >= 3 ? 5 : 4));
     int max_wpe = canon ? 4 : (kn.max_wpe ? (int)kn.max_wpe : max_wpe_work);   // (RTGO_MAX_WPE: experiment knob, clamped to what exists)
     max_wpe = max_wpe < 4 ? 4 : (max_wpe > top_wpe ? top_wpe : max_wpe);
     for (int w = 4; w <= max_wpe; ++w)
         for (int bs = global ? 64 : 256; bs <= kMaxBlock; bs *= 2) {
-            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int)) + ((w >= 5 || (batch && !path)) ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0) + ((batch && !path && w >= 5) ? (size_t)bs * 9 * sizeof(float) : 0) /* render_frames_kernel, distributed: level records at 4 waves too, the shadow ray's state at 5 */ + ((w >= 6 || (batch && !path && w >= 5)) ? (size_t)(kCamWordsLean - kCamWords) * sizeof(float) : 0);
+            const size_t l = scene_lds + (stream ? (size_t)(bs / 64) * 192 * kStreamWindow * sizeof(float) : 0) + (is_pair(w) ? 0 : (size_t)p.stack_depth * bs * (canon ? sizeof(float2) : sizeof(unsigned int))) + ((w >= 5 || (batch && !path)) ? (size_t)bs * (path ? 3 : 4) * kMaxLevels * sizeof(float) : 0) + ((batch && !path && w >= 5) ? (size_t)bs * 9 * sizeof(float) : 0) /* render_frames_kernel, distributed: level records at 4 waves too, the shadow ray's state at 5 */ + ((w >= 6 || (batch && !path && w >= 5)) ? (size_t)(kCamWordsLean - kCamWords) * sizeof(float) : 0);
             int per_cu = (int)((160 * 1024) / l);
             if (per_cu * (bs / 64) > 4 * w) per_cu = (4 * w) / (bs / 64);
             const int waves = per_cu * (bs / 64);
@@ -1581,18 +1589,24 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
         if (const int rc = update_hot_mask(c, strip_px, p, mask_cold_pixels)) return rc;
     if (p.n_tiles == 0) return RTGO_OK;  // this rank owns no rows
     const bool frames = path && !canon && c->scene.quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
-    Block b;
-    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b, false, batch)) return rc;
     // The straight-line walk of a two-leaf tree (render_pair_kernel, fast_pair): path mode over a flat scene with frames, the lock-step loop,
     // one frame per launch, inside the far-field guard, over a tree (not the grid) that is a root over two certified cuboid leaves, the
-    // cuboid margin still positive at this launch's reach -- and a variant at the waves per SIMD pick_block chose (5 and 6).  RTGO_NO_PAIR: off.
+    // cuboid margin still positive at this launch's reach -- and a variant at the waves per SIMD pick_block chose (5, 6 and, as
+    // render_pair7_kernel, 7).  RTGO_NO_PAIR: off.
     const bool pair_ok = path && !canon && !pk.stream && frames && !use_grid && !batch && !kn.no_pair && c->scene.tree[use_alt ? 1 : 0].pair && p.cub_mu > 0.0f;
+    Block b;
+    if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b, false, batch, pair_ok)) return rc;
     const RenderKernel pair_kernel = pair_ok ? find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch, true) : nullptr;
     const RenderKernel kernel = pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch);
-    if (kn.debug)
-        std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g, kernel %s<%d>\n",
-                     n_frames, canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric,
-                     pair_kernel ? "render_pair_kernel" : (batch ? "render_frames_kernel" : "render_kernel"), b.wpe);
+    if (pair_kernel) p.stack_depth = 0;   // (fast_pair has no stack: pick_block reserved none, and the lights follow the scene directly)
+    const bool pair7 = pair_kernel && b.wpe == 7;
+    if (kn.debug) {
+        char kname[48];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
+        if (pair7) std::snprintf(kname, sizeof kname, "render_pair7_kernel");
+        else std::snprintf(kname, sizeof kname, "%s<%d>", pair_kernel ? "render_pair_kernel" : (batch ? "render_frames_kernel" : "render_kernel"), b.wpe);
+        std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g, kernel %s\n",
+                     n_frames, canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric, kname);
+    }
     if (!kernel) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_launch: no kernel variant for this configuration");
     const unsigned long long culled = (unsigned long long)p.local_rows * p.w - (unsigned long long)p.hot_h * (p.cold_x1 - p.cold_x0) + mask_cold_pixels;
     std::vector<uint32_t> seeds_key;
@@ -1602,6 +1616,7 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     if (const int rc = enqueue(c, kernel, p, b, pk, canon, culled * nn * n_frames)) return rc;
     if (batch) c->last_variant |= 128u;
     if (pair_kernel) c->last_variant |= 256u;
+    if (pair7) c->last_variant |= 512u;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
         c->seeds.read = 1 - c->seeds.read;

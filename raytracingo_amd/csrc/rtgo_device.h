@@ -1340,9 +1340,19 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 #include "rtgo_render_body.inc"
 }
 
+// ... at 7 waves per SIMD (72 VGPRs): everything render_pair_kernel<6> has -- every WPE >= 6 switch of the body reads 7 as 6 -- under a
+// tighter register budget, for launches with enough units per wave to keep 28 waves of a CU busy (pick_block).  A name of its own: the
+// template above stays at its two instantiations.
+__global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_pair7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
+{
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true;
+    constexpr int WPE = 7;
+#include "rtgo_render_body.inc"
+}
+
 }  // namespace rtgo
 
-#include "rtgo_build.h"   // scene preparation and the builds: PrimIn .. build_kernel (uses the definitions above)
+#include "rtgo_build.h"  // scene preparation and the builds: PrimIn .. build_kernel (uses the definitions above)
 
 namespace rtgo {
 
