@@ -355,9 +355,32 @@ int rtgo_whitted_set_instances(rtgo_ctx* ctx, const rtgo_whitted_instance* insta
    positions: n_vertices x 3 floats, copied; normals: the same, or NULL to keep the normals the mesh has.  RTGO_E_STATE: no whitted
    scene.  RTGO_E_INVALID: `mesh` beyond the scene's meshes, positions NULL, n_vertices not the mesh's own, non-finite data, normals
    for a mesh that was set without, an instance that now places the mesh beyond the float range.  RTGO_E_UNSUPPORTED: a clustered mesh
-   (beyond RTGO_MAX_TRIANGLES: its cluster and mid levels are not refitted yet -- set the scene again), or a top level deeper than the
-   walk's stack.  A refused call leaves the scene as it was.  Synchronous. */
+   (beyond RTGO_MAX_TRIANGLES: rtgo_whitted_update_meshes refits it), or a top level deeper than the walk's stack.  A refused call
+   leaves the scene as it was.  Synchronous. */
 int rtgo_whitted_update_mesh(rtgo_ctx* ctx, uint32_t mesh, const float* positions, const float* normals, uint32_t n_vertices);
+
+/* One entry of rtgo_whitted_update_meshes: rtgo_whitted_update_mesh's arguments. */
+typedef struct rtgo_whitted_mesh_update {
+    uint32_t mesh;            /* as rtgo_whitted_update_mesh's `mesh` */
+    const float* positions;   /* n_vertices x 3, copied */
+    const float* normals;     /* the same, or NULL: keep the normals the mesh has */
+    uint32_t n_vertices;
+} rtgo_whitted_mesh_update;
+
+/* rtgo_whitted_update_mesh for every entry of `updates`, as one transaction: every entry is checked before anything on the device
+   changes, the instances are laid out again once and the top level is built once, over all the new mesh boxes -- a frame that moves k
+   meshes pays for that once, not k times.  Clustered meshes (beyond RTGO_MAX_TRIANGLES) are accepted here: every cluster is refitted
+   by one launch (one workgroup per cluster), then the mid level over the clusters' new boxes; topology, Morton order and cluster cut
+   stay as built, and the frame is bit for bit that of a scene set afresh with the same vertices.  What stays is what stays under
+   rtgo_whitted_update_mesh, and afterwards rtgo_whitted_set_instances, rtgo_whitted_update_mesh and this call work as after a fresh
+   rtgo_whitted_set_scene.  n_updates == 0: RTGO_OK, nothing changes.  A scene of rtgo_whitted_set_mesh takes one entry, mesh 0.
+   RTGO_E_STATE: no whitted scene.  RTGO_E_INVALID: `updates` NULL with n_updates > 0, a mesh index beyond the scene's meshes, a mesh
+   named twice, positions NULL, n_vertices not the mesh's own, non-finite data, normals for a mesh that was set without, an instance
+   that now places a mesh beyond the float range.  RTGO_E_UNSUPPORTED: a top level deeper than the walk's stack.  A refused call leaves
+   the scene as it was, whichever entry it refuses (a clustered mesh's box is known only once it is refitted: its arrays are saved on
+   the device first and put back).  Synchronous.  (rtgo_whitted_update_mesh keeps its own path and its refusal of clustered meshes;
+   forwarding it to this call is left for later.) */
+int rtgo_whitted_update_meshes(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* updates, uint32_t n_updates);
 
 /* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
    rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */

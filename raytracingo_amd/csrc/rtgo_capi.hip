@@ -1751,6 +1751,13 @@ int rtgo_whitted_update_mesh(rtgo_ctx* c, uint32_t mesh, const float* positions,
     return whitted_update_mesh(c, mesh, positions, normals, n_vertices);
 }
 
+int rtgo_whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_update_meshes: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene first)");
+    return whitted_update_meshes(c, updates, n_updates);
+}
+
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
 {
     if (!c) return RTGO_E_INVALID;

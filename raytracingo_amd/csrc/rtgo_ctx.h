@@ -35,6 +35,7 @@ struct WhittedMeshInfo {
     // their quantised forms at qrecs[2 tri0 ..] (tri0 < 0: none kept, a mid level's)
     struct Built { int rec0, n_recs, tri0; whitted::WhittedBuildMeta meta; };   // (meta: what that build reported)
     std::vector<Built> built;
+    std::vector<int> mid_order;   // a clustered mesh: the cluster at each leaf position of its mid level (a refit lays the mid level's input out again)
 };
 
 // The analytic scene (rtgo_set_scene, rtgo_set_large_scene): replaced as a whole, by assigning a fresh one
@@ -224,6 +225,7 @@ static_assert(RTGO_WHITTED_MAX_MESHES == whitted::kMaxMeshes && RTGO_WHITTED_MAX
 static_assert(RTGO_WHITTED_MAX_MESH_TRIANGLES == whitted::kBigMaxMeshTriangles && RTGO_WHITTED_MAX_SCENE_TRIANGLES == whitted::kBigMaxSceneTriangles,
               "clustered mesh limits");
 static_assert(sizeof(rtgo_whitted_instance) == 56 && sizeof(whitted::InstWalk) == 64 && sizeof(whitted::InstShade) == 112, "instance records");
+static_assert(sizeof(rtgo_whitted_mesh_update) == 32, "rtgo_whitted_update_meshes's entry");
 
 static std::string g_create_error;
 

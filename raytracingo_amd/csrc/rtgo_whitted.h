@@ -991,24 +991,50 @@ __global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4*
 // fitted in the pass after the records it links to.  done[r] = the pass that fitted record r (0: not yet); a stamp of the running pass
 // reads as "not yet", so one barrier per pass orders them.  The topology is read from `recs` alone, whichever build left it.
 // Writes out_meta's grid_lo / grid_step only (depth, n_recs and walk_depth stay).  Scratch: done[n_recs].
+// The body is refit_structure, one workgroup over one RefitTarget: refit_kernel runs it over a mesh (and over a clustered mesh's mid
+// level), big_refit_clusters_kernel (rtgo_whitted_big.h) with one workgroup per cluster.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBuildThreads) void refit_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n, int n_recs,
-                                                              int walk_depth, float4* recs, float4* tris, uint4* qrecs, int* done,
-                                                              WhittedBuildMeta* __restrict__ out_meta)
+// What one refit works on: the vertices and index triples its triangles name, the structure of one build (n triangles, n_recs records
+// at recs / qrecs, the sorted triangles at tris), done[n_recs], and where the grid goes
+struct RefitTarget {
+    const float* positions;
+    const unsigned int* indices;
+    int n, n_recs, walk_depth;
+    float4* recs;
+    float4* tris;
+    uint4* qrecs;
+    int* done;
+    WhittedBuildMeta* out_meta;
+};
+
+// One workgroup of kBuildThreads threads, s_red: its 6 x kBuildThreads floats of LDS.  kSubset: the structure's triangles are the n that
+// tris[3 i].w names among the triples of `indices` (a cluster of a clustered mesh: the bounds are taken over them, as the cluster's build
+// took them over its slice of the gathered triples); otherwise they are triples 0 .. n - 1.
+template <bool kSubset>
+__device__ __forceinline__ void refit_structure(const RefitTarget& t, float (*s_red)[kBuildThreads])
 {
-    __shared__ float s_red[6][kBuildThreads];
+    const float* __restrict__ positions = t.positions;
+    const unsigned int* __restrict__ indices = t.indices;
+    const int n = t.n, n_recs = t.n_recs, walk_depth = t.walk_depth;
+    float4* recs = t.recs;
+    float4* tris = t.tris;
+    uint4* qrecs = t.qrecs;
+    int* done = t.done;
+    WhittedBuildMeta* __restrict__ out_meta = t.out_meta;
     const int tid = threadIdx.x;
     // scene bounds, pad and grid: build_kernel's
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = tid; i < n; i += kBuildThreads)
+    for (int i = tid; i < n; i += kBuildThreads) {
+        const int tri = kSubset ? __float_as_int(tris[3 * i + 0].w) : i;
         for (int k = 0; k < 3; ++k) {
-            const unsigned int vi = indices[3 * i + k];
+            const unsigned int vi = indices[3 * tri + k];
             for (int a = 0; a < 3; ++a) {
                 const float c = positions[3 * vi + a];
                 lo[a] = fminf(lo[a], c);
                 hi[a] = fmaxf(hi[a], c);
             }
         }
+    }
     reduce_bounds<kBuildThreads>(s_red, tid, lo, hi);
     float blo[3], ext[3], maxext = 0.0f, reach = 0.0f;
     for (int a = 0; a < 3; ++a) {
@@ -1078,6 +1104,15 @@ __global__ __launch_bounds__(kBuildThreads) void refit_kernel(const float* __res
         const int root = done[0];
         if (root != 0 && root <= pass) break;
     }
+}
+
+
+__global__ __launch_bounds__(kBuildThreads) void refit_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n, int n_recs,
+                                                              int walk_depth, float4* recs, float4* tris, uint4* qrecs, int* done,
+                                                              WhittedBuildMeta* __restrict__ out_meta)
+{
+    __shared__ float s_red[6][kBuildThreads];
+    refit_structure<false>({positions, indices, n, n_recs, walk_depth, recs, tris, qrecs, done, out_meta}, s_red);
 }
 
 }  // namespace whitted

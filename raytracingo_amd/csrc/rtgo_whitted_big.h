@@ -9,6 +9,8 @@
 //   (radix_count_kernel, radix_scan_kernel, radix_scatter_kernel; stable, and the keys start in triangle order, so the order is
 //   (code, triangle): unique keys, one deterministic order) -> big_gather_kernel (each sorted triangle's index triple) -> per cluster
 //   whitted_build -> big_remap_kernel (cluster-local triangle numbers in tris[].w back to the mesh's own).
+// A refit to moved vertices (rtgo_whitted_update_meshes) keeps all of that and runs big_bounds_kernel, big_bounds_final_kernel (the
+// mesh's box), big_refit_clusters_kernel (every cluster, one workgroup each), big_cluster_boxes_kernel and refit_kernel (the mid level).
 #pragma once
 
 #include "rtgo_whitted.h"
@@ -207,6 +209,27 @@ __global__ __launch_bounds__(256) void big_cluster_boxes_kernel(const float4* __
     pos[6 * c + 3] = fmaxf(a1.x, b1.x);
     pos[6 * c + 4] = fmaxf(a1.y, b1.y);
     pos[6 * c + 5] = fmaxf(a1.z, b1.z);
+}
+
+// ---- refit (rtgo_whitted_update_meshes) ---------------------------------------------------------------------------------------------
+// One cluster of a clustered mesh as its build left it: its records start at recs[4 rec0] of the scene, its sorted triangles at
+// position tri0 of the mesh's (tris, qrecs and done are the mesh's own slices), n of them; n_recs and walk_depth as that build reported
+struct ClusterRefit { int rec0, tri0, n, n_recs, walk_depth; };
+
+// refit_kernel's body over every cluster of one mesh, one workgroup per cluster.  positions / indices are the mesh's own: since
+// big_remap_kernel a cluster's tris[].w holds the mesh's triangle index, and that triple is the one the cluster's build read from its
+// slice of the gathered triples; bounds, pad and grid are taken over the cluster's triangles alone, as that build took them.  A
+// workgroup reads and writes its own cluster's records, triangles and flags only, so nothing orders the workgroups: the mid level is
+// refitted by a later launch (big_cluster_boxes_kernel, then refit_kernel over the clusters' boxes).  out_meta[c] gets cluster c's grid.
+__global__ __launch_bounds__(kBuildThreads) void big_refit_clusters_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices,
+                                                                           const ClusterRefit* __restrict__ table, float4* recs, float4* tris, uint4* qrecs,
+                                                                           int* done, WhittedBuildMeta* __restrict__ out_meta)
+{
+    __shared__ float s_red[6][kBuildThreads];
+    const ClusterRefit c = table[blockIdx.x];
+    refit_structure<true>({positions, indices, c.n, c.n_recs, c.walk_depth, recs + 4 * (size_t)c.rec0, tris + 3 * (size_t)c.tri0, qrecs + 2 * (size_t)c.tri0,
+                           done + c.tri0, out_meta + blockIdx.x},
+                          s_red);
 }
 
 }  // namespace whitted

@@ -312,6 +312,7 @@ static int whitted_build_clustered(rtgo_ctx* c, const WhittedMesh& wm, WhittedMe
     std::vector<int> order;
     if (const int rc = whitted_build_boxes(c, bs.boxes.get(), ncl, mesh.recs, order, m, what)) return rc;
     mi.built.push_back({mi.rec_base, m.n_recs, -1, m});
+    mi.mid_order = order;
     std::vector<float4> root_rec(4);
     std::vector<float> boxes((size_t)6 * ncl);
     RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.boxes.get(), boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -347,16 +348,10 @@ struct WhittedLayout {
     std::vector<unsigned int> idx, tmat;
 };
 
-// The box an instanced mesh's instances are laid out from (WhittedMeshInfo::lo / hi): the bounds of the vertices its triangles name, padded
-static void whitted_mesh_box(const float* positions, const uint32_t* indices, uint32_t n_triangles, float out_lo[3], float out_hi[3])
+// The box an instanced mesh's instances are laid out from (WhittedMeshInfo::lo / hi), from the bounds of the vertices its triangles name:
+// the root record's boxes lie within those bounds padded by build_kernel's pad, twice that pad covers them and their rounding
+static void whitted_pad_mesh_box(const float lo[3], const float hi[3], float out_lo[3], float out_hi[3])
 {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t i = 0; i < 3 * n_triangles; ++i)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = std::fmin(lo[a], positions[3 * indices[i] + a]);
-            hi[a] = std::fmax(hi[a], positions[3 * indices[i] + a]);
-        }
-    // the root record's boxes lie within the triangle bounds padded by build_kernel's pad: twice that pad covers them and their rounding
     float maxext = 0.0f, reach = 0.0f;
     for (int a = 0; a < 3; ++a) {
         maxext = std::fmax(maxext, hi[a] - lo[a]);
@@ -367,6 +362,18 @@ static void whitted_mesh_box(const float* positions, const uint32_t* indices, ui
         out_lo[a] = lo[a] - pad;
         out_hi[a] = hi[a] + pad;
     }
+}
+
+// ... with the bounds taken on the host
+static void whitted_mesh_box(const float* positions, const uint32_t* indices, uint32_t n_triangles, float out_lo[3], float out_hi[3])
+{
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t i = 0; i < 3 * n_triangles; ++i)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::fmin(lo[a], positions[3 * indices[i] + a]);
+            hi[a] = std::fmax(hi[a], positions[3 * indices[i] + a]);
+        }
+    whitted_pad_mesh_box(lo, hi, out_lo, out_hi);
 }
 
 // The stages of rtgo_whitted_set_scene.  Stage 1 (host only): every mesh as rtgo_whitted_set_mesh checks it, its padded box, where it will sit in the arrays, and packed there
@@ -544,6 +551,225 @@ static int whitted_update_mesh(rtgo_ctx* c, uint32_t mesh, const float* position
     if (const int rc = whitted_make_top(c, wm, shade, box_pos, wm.instances.data(), what, top, depth)) return rc;
     if (const int rc = whitted_refit(c, wm, m, positions, normals)) return rc;
     meshes[mesh].built[0].meta = m.meta;
+    wm.meshes = std::move(meshes);
+    whitted_install_top(wm, std::move(top), depth);
+    return RTGO_OK;
+}
+
+// ---- refit of a clustered mesh (rtgo_whitted_update_meshes) -------------------------------------------------------------------------
+// One clustered mesh's refit in flight: what it replaces of wm's arrays, kept until the call is known to succeed (the box its instances
+// are laid out from is known only after the refit, so a refusal can follow it: whitted_restore_clustered puts these back), the device
+// scratch of its launches, and what they report.  All of it is proportional to the mesh and freed with this.
+struct WhittedClusteredRefit {
+    int mesh = 0, ncl = 0;
+    const float *positions = nullptr, *normals = nullptr;   // the caller's
+    DeviceArray<float> old_positions, old_normals;
+    DeviceArray<float4> old_recs, old_tris;
+    DeviceArray<uint4> old_qrecs;
+    DeviceArray<int> ints;          // ClusterRefit[ncl], the clusters' record bases [ncl], the mid level's index triples [3 ncl]; then done[n] and the mid level's done[ncl]
+    DeviceArray<float4> mid_tris;   // the mid level's "triangles": .w of each first corner is the cluster at that leaf position
+    DeviceArray<uint4> mid_qrecs;
+    DeviceArray<float> partial;     // big_bounds_kernel's
+    DeviceArray<float> report;      // what comes back: bounds [6], the clusters' boxes [6 ncl], WhittedBuildMeta [ncl + 1] (the mid level's last)
+    std::vector<float> host;        // ... on the host, then the mid root's record [16]
+    std::vector<int> up_ints;       // what `ints` and `mid_tris` are uploaded from: alive until the stream has drained
+    std::vector<float4> up_mid_tris;
+};
+
+// Stage 2 of whitted_update_meshes for a clustered mesh: saves the slices, uploads the vertices and enqueues the refit and its read-back.
+// Three launches refit it whatever its size -- every cluster (one workgroup each), the clusters' boxes, the mid level over them -- and
+// two find its bounds.  Nothing here waits for the device.
+static int whitted_enqueue_clustered_refit(rtgo_ctx* c, WhittedMesh& wm, const WhittedMeshInfo& mi, WhittedClusteredRefit& r)
+{
+    using namespace whitted;
+    const int n = mi.n_tris, ncl = (int)mi.built.size() - 1;
+    const size_t nv3 = (size_t)mi.n_verts * 3;
+    r.ncl = ncl;
+    float* d_pos = wm.positions.get() + 3 * (size_t)mi.vert_base;
+    float* d_nrm = wm.normals.get() + 3 * (size_t)mi.vert_base;
+    const unsigned int* d_idx = wm.indices.get() + 3 * (size_t)mi.tri_base;
+    const WhittedBuildTarget t = whitted_target(wm, mi.rec_base, mi.tri_base);   // (a mesh of n triangles owns n record slots)
+    auto save = [&](auto& keep, const auto* src, size_t count) -> hipError_t {
+        const hipError_t e = keep.alloc(count);
+        return e != hipSuccess ? e : hipMemcpyAsync(keep.get(), src, count * sizeof *src, hipMemcpyDeviceToDevice, c->stream);
+    };
+    RTGO_HIP(c, save(r.old_positions, d_pos, nv3));
+    if (r.normals) RTGO_HIP(c, save(r.old_normals, d_nrm, nv3));
+    RTGO_HIP(c, save(r.old_recs, t.recs, (size_t)4 * n));
+    RTGO_HIP(c, save(r.old_tris, t.tris, (size_t)3 * n));
+    RTGO_HIP(c, save(r.old_qrecs, t.qrecs, (size_t)2 * n));
+    RTGO_HIP(c, hipMemcpyAsync(d_pos, r.positions, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (r.normals) RTGO_HIP(c, hipMemcpyAsync(d_nrm, r.normals, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    // the launches' tables, one upload
+    static_assert(sizeof(ClusterRefit) == 5 * sizeof(int), "five words");
+    const size_t o_crec = (size_t)5 * ncl, o_idx = o_crec + ncl, o_done = o_idx + (size_t)3 * ncl, o_mid_done = o_done + n;
+    std::vector<int>& ints = r.up_ints;
+    std::vector<float4>& mid_tris = r.up_mid_tris;
+    ints.assign(o_done, 0);
+    mid_tris.assign((size_t)3 * ncl, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (int k = 0; k < ncl; ++k) {
+        const WhittedMeshInfo::Built& b = mi.built[k];
+        const ClusterRefit cr = {b.rec0, b.tri0 - mi.tri_base, cluster_start(n, ncl, k + 1) - cluster_start(n, ncl, k), b.n_recs, b.meta.walk_depth};
+        std::memcpy(&ints[(size_t)5 * k], &cr, sizeof cr);
+        ints[o_crec + k] = b.rec0;
+        for (int j = 0; j < 3; ++j) ints[o_idx + 3 * (size_t)k + j] = 2 * k + (j == 1 ? 1 : 0);   // whitted_build_boxes's degenerate triangle (lo, hi, lo)
+        std::memcpy(&mid_tris[3 * (size_t)k].w, &mi.mid_order[k], sizeof(int));
+    }
+    RTGO_HIP(c, r.ints.alloc(o_mid_done + ncl));
+    RTGO_HIP(c, hipMemcpyAsync(r.ints.get(), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, r.mid_tris.upload(mid_tris.data(), mid_tris.size(), c->stream));
+    RTGO_HIP(c, r.mid_qrecs.alloc((size_t)2 * ncl));
+    RTGO_HIP(c, r.partial.alloc((size_t)6 * 1024));
+    const size_t o_boxes = 6, o_meta = o_boxes + (size_t)6 * ncl, n_report = o_meta + (size_t)9 * (ncl + 1);
+    RTGO_HIP(c, r.report.alloc(n_report));
+    float* d_bounds = r.report.get();
+    float* d_boxes = r.report.get() + o_boxes;
+    WhittedBuildMeta* d_meta = reinterpret_cast<WhittedBuildMeta*>(r.report.get() + o_meta);
+    const WhittedBuildMeta& mid = mi.built[ncl].meta;
+    // the triangle bounds (exact min / max: whitted_mesh_box's, without the indices leaving the device)
+    const int nbb = std::min(1024, (n + 1023) / 1024);
+    hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, (const float*)d_pos, d_idx, n, r.partial.get());
+    hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)r.partial.get(), nbb, d_bounds);
+    // clusters -> their boxes -> the mid level (kernel boundaries order them)
+    hipLaunchKernelGGL(big_refit_clusters_kernel, dim3(ncl), dim3(kBuildThreads), 0, c->stream, (const float*)d_pos, d_idx, (const ClusterRefit*)r.ints.get(),
+                       wm.recs.get(), t.tris, t.qrecs, r.ints.get() + o_done, d_meta);
+    hipLaunchKernelGGL(big_cluster_boxes_kernel, dim3((ncl + 255) / 256), dim3(256), 0, c->stream, (const float4*)wm.recs.get(), (const int*)(r.ints.get() + o_crec),
+                       ncl, d_boxes);
+    hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(kBuildThreads), 0, c->stream, (const float*)d_boxes, (const unsigned int*)(r.ints.get() + o_idx), ncl,
+                       mi.built[ncl].n_recs, mid.walk_depth, t.recs, r.mid_tris.get(), r.mid_qrecs.get(), r.ints.get() + o_mid_done, d_meta + ncl);
+    RTGO_HIP(c, hipGetLastError());
+    r.host.assign(n_report + 16, 0.0f);
+    RTGO_HIP(c, hipMemcpyAsync(r.host.data(), r.report.get(), n_report * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (mi.built[ncl].n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(&r.host[n_report], t.recs, 16 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return RTGO_OK;
+}
+
+// ... and once the stream has drained: the mesh's box as whitted_build_clustered takes it, and the grids its builds now report
+static void whitted_finish_clustered_refit(WhittedMeshInfo& mi, const WhittedClusteredRefit& r)
+{
+    const int ncl = r.ncl;
+    const float* bounds = r.host.data();
+    const float* boxes = bounds + 6;
+    const float* meta = boxes + (size_t)6 * ncl;
+    const float* root = meta + (size_t)9 * (ncl + 1);
+    whitted_pad_mesh_box(bounds, bounds + 3, mi.lo, mi.hi);
+    auto widen = [&](const float* l, const float* h) {
+        for (int a = 0; a < 3; ++a) {
+            mi.lo[a] = std::fmin(mi.lo[a], l[a]);
+            mi.hi[a] = std::fmax(mi.hi[a], h[a]);
+        }
+    };
+    if (mi.built[ncl].n_recs > 0) {
+        widen(root, root + 4);
+        widen(root + 8, root + 12);
+    }
+    for (int k = 0; k < ncl; ++k) widen(boxes + 6 * (size_t)k, boxes + 6 * (size_t)k + 3);
+    for (int k = 0; k <= ncl; ++k) {
+        WhittedBuildMeta m;
+        std::memcpy(&m, meta + (size_t)9 * k, sizeof m);
+        mi.built[k].meta.grid_lo = m.grid_lo;
+        mi.built[k].meta.grid_step = m.grid_step;
+    }
+}
+
+// A refused call: the mesh's slices as they were.  Enqueued; the caller waits.
+static int whitted_restore_clustered(rtgo_ctx* c, WhittedMesh& wm, const WhittedMeshInfo& mi, const WhittedClusteredRefit& r)
+{
+    const WhittedBuildTarget t = whitted_target(wm, mi.rec_base, mi.tri_base);
+    auto back = [&](auto* dst, const auto& keep) { return hipMemcpyAsync(dst, keep.get(), keep.size() * sizeof *dst, hipMemcpyDeviceToDevice, c->stream); };
+    RTGO_HIP(c, back(wm.positions.get() + 3 * (size_t)mi.vert_base, r.old_positions));
+    if (r.normals) RTGO_HIP(c, back(wm.normals.get() + 3 * (size_t)mi.vert_base, r.old_normals));
+    RTGO_HIP(c, back(t.recs, r.old_recs));
+    RTGO_HIP(c, back(t.tris, r.old_tris));
+    RTGO_HIP(c, back(t.qrecs, r.old_qrecs));
+    return RTGO_OK;
+}
+
+// rtgo_whitted_update_meshes once the scene is known to exist: rtgo_whitted_update_mesh for every entry as one transaction.  Stages:
+// 1 every check the host can make; 2 every mesh's new box (a small mesh: from its indices read back, all in one wait; a clustered mesh:
+// refitted in place with its slices saved, its box from what the device reports); 3 the instances laid out and the top level built, once,
+// aside; 4 the small meshes' refits; 5 what the host keeps.  A refusal in stage 3 puts the clustered meshes' slices back: nothing else
+// has changed by then.
+static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    const char* what = "rtgo_whitted_update_meshes";
+    const std::string w(what);
+    WhittedMesh& wm = c->wm;
+    if (n_updates == 0) return RTGO_OK;
+    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
+    const size_t n_meshes = wm.instanced ? wm.meshes.size() : (size_t)1;
+    // stage 1
+    std::vector<char> named(n_meshes, 0);
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        const rtgo_whitted_mesh_update& u = updates[k];
+        const std::string at = w + ": update " + std::to_string(k);
+        if (u.mesh >= n_meshes) return fail(c, RTGO_E_INVALID, at + ": mesh index beyond the scene's meshes");
+        if (named[u.mesh]) return fail(c, RTGO_E_INVALID, at + ": mesh " + std::to_string(u.mesh) + " is named twice");
+        named[u.mesh] = 1;
+        if (!u.positions) return fail(c, RTGO_E_INVALID, at + ": NULL positions");
+        const int n_verts = wm.instanced ? wm.meshes[u.mesh].n_verts : wm.n_vertices;
+        const bool has_normals = wm.instanced ? (wm.meshes[u.mesh].flags & whitted::kHasNormals) != 0 : wm.normals.get() != nullptr;
+        if (u.n_vertices != (uint32_t)n_verts) return fail(c, RTGO_E_INVALID, at + ": the mesh has " + std::to_string(n_verts) + " vertices");
+        if (u.normals && !has_normals) return fail(c, RTGO_E_INVALID, at + ": normals for a mesh that was set without");
+        for (size_t i = 0; i < (size_t)3 * u.n_vertices; ++i)
+            if (!std::isfinite(u.positions[i]) || (u.normals && !std::isfinite(u.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
+    }
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (!wm.instanced) {
+        WhittedRefitMesh m = {0, 0, 0, wm.n_vertices, wm.triangles, wm.normals.get() != nullptr, wm.meta};
+        if (const int rc = whitted_refit(c, wm, m, updates[0].positions, updates[0].normals)) return rc;
+        wm.meta = m.meta;
+        return RTGO_OK;
+    }
+    // stage 2
+    std::vector<WhittedMeshInfo> meshes = wm.meshes;
+    std::vector<std::vector<uint32_t>> idx(n_updates);
+    std::vector<WhittedClusteredRefit> big;
+    big.reserve(n_updates);
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        const rtgo_whitted_mesh_update& u = updates[k];
+        const WhittedMeshInfo& mi = meshes[u.mesh];
+        if (mi.clustered) {
+            big.emplace_back();
+            big.back().mesh = (int)u.mesh;
+            big.back().positions = u.positions;
+            big.back().normals = u.normals;
+            if (const int rc = whitted_enqueue_clustered_refit(c, wm, mi, big.back())) return rc;
+        } else {
+            idx[k].resize((size_t)3 * mi.n_tris);
+            RTGO_HIP(c, hipMemcpyAsync(idx[k].data(), wm.indices.get() + 3 * (size_t)mi.tri_base, idx[k].size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        WhittedMeshInfo& mi = meshes[updates[k].mesh];
+        if (!mi.clustered) whitted_mesh_box(updates[k].positions, idx[k].data(), (uint32_t)mi.n_tris, mi.lo, mi.hi);
+    }
+    for (const WhittedClusteredRefit& r : big) whitted_finish_clustered_refit(meshes[r.mesh], r);
+    // stage 3
+    std::vector<whitted::InstShade> shade;
+    std::vector<float> box_pos;
+    WhittedTop top;
+    int depth = 0;
+    int rc = whitted_prepare_instances(c, meshes, (uint32_t)wm.n_materials, wm.instances.data(), (uint32_t)wm.instances.size(), shade, box_pos, what);
+    if (!rc) rc = whitted_make_top(c, wm, shade, box_pos, wm.instances.data(), what, top, depth);
+    if (rc) {
+        for (const WhittedClusteredRefit& r : big)
+            if (const int rc2 = whitted_restore_clustered(c, wm, wm.meshes[r.mesh], r)) return rc2;
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        return rc;
+    }
+    // stage 4
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        const rtgo_whitted_mesh_update& u = updates[k];
+        WhittedMeshInfo& mi = meshes[u.mesh];
+        if (mi.clustered) continue;
+        WhittedRefitMesh m = {mi.vert_base, mi.tri_base, mi.rec_base, mi.n_verts, mi.n_tris, (mi.flags & whitted::kHasNormals) != 0, mi.built[0].meta};
+        if (const int rc4 = whitted_refit(c, wm, m, u.positions, u.normals)) return rc4;
+        mi.built[0].meta = m.meta;
+    }
+    // stage 5
     wm.meshes = std::move(meshes);
     whitted_install_top(wm, std::move(top), depth);
     return RTGO_OK;

@@ -1,5 +1,9 @@
-"""developer tool: what a refit (rtgo_whitted_update_mesh) costs and what it does to the walk, against setting the mesh again
-   python tools/whitted_refit_perf.py [W] [H]
+"""developer tool: what a refit (rtgo_whitted_update_mesh, rtgo_whitted_update_meshes) costs and what it does to the walk, against setting the mesh again
+   python tools/whitted_refit_perf.py [W] [H]        single meshes up to 8192 triangles, rtgo_whitted_update_mesh against rtgo_whitted_set_mesh
+   python tools/whitted_refit_perf.py big [W] [H]    tools/whitted_inst_perf.py big's 1 000 000-triangle displaced torus (a clustered mesh) on a ground:
+                                                     rtgo_whitted_update_meshes against rtgo_whitted_set_scene over the same vertices, subframe time of the
+                                                     refitted scene against the fresh one (smooth, twist); and a batch of k meshes against k calls of
+                                                     rtgo_whitted_update_mesh on a field of 1024 tori drawn from k meshes
 Per mesh and deformation, medians of repeated calls after a warm-up:
    update    ms of rtgo_whitted_update_mesh (synchronous: wall time of the call)
    set_mesh  ms of rtgo_whitted_set_mesh over the same new vertices
@@ -17,8 +21,10 @@ import whitted_instances as WI
 import whitted_big_meshes as BM
 from raytracingo_amd import capi
 
-W = int(sys.argv[1]) if len(sys.argv) > 1 else 1920
-H = int(sys.argv[2]) if len(sys.argv) > 2 else 1080
+BIG = len(sys.argv) > 1 and sys.argv[1] == "big"
+ARGS = sys.argv[2:] if BIG else sys.argv[1:]
+W = int(ARGS[0]) if len(ARGS) > 0 else 1920
+H = int(ARGS[1]) if len(ARGS) > 1 else 1080
 WARM, REPS = 3, 15
 
 
@@ -75,31 +81,83 @@ def deformations(mesh):
     return [("smooth", smooth.astype(np.float32)), ("twist", twist.astype(np.float32)), ("shuffle", shuffle.astype(np.float32))]
 
 
-torus = BM.displaced_torus(64, 64, texcoords=False)
-torus.update(materials=WI.materials(), **WI.lights())
-MESHES = [("scene 342", whitted_scene.build()), ("scene 3758", whitted_scene.build(n_lat=40, n_lon=48)), ("waterbottle", whitted_scene.waterbottle()),
-          ("torus 8192", torus)]
-
-print("whitted refit, %d x %d, medians of %d after %d warm-up calls" % (W, H, REPS, WARM))
-for name, mesh in MESHES:
-    p = mesh["positions"]
-    lo, hi = p.min(0), p.max(0)
-    c, ext = 0.5 * (lo + hi), float((hi - lo).max())
-    cam = frame(c + ext * np.array([0.08, 0.45, 1.1]), c)
-    ctx = capi.Context(0)
-    set_mesh(ctx, mesh, p)
-    ctx.whitted_set_lights(mesh["lights"])
-    ctx.whitted_set_miss_color(mesh["miss"])
+def view(ctx, lights, miss, cam):
+    ctx.whitted_set_lights(lights)
+    ctx.whitted_set_miss_color(miss)
     ctx.set_camera(*cam)
     ctx.resize(W * H)
-    built = subframe_ms(ctx)
-    print("%-12s %5d triangles  %5d vertices  as built %.3f ms/subframe" % (name, len(mesh["indices"]), len(p), built))
-    for what, q in deformations(mesh):
-        set_mesh(ctx, mesh, p)
-        t_update = median_ms(lambda: ctx.whitted_update_mesh(0, q))
+
+
+def big_mode():
+    eye34 = np.eye(3, 4, dtype=np.float32)
+    big = BM.displaced_torus(1000, 500, R=1.0, r=0.35, amp=0.04, freq=(23, 11), texcoords=False)   # 1 000 000 triangles
+    meshes, inst, mats, lt = [WI.ground(4.0, -0.5, normals=True), big], [(eye34, 0, 0), (eye34, 1, 1)], WI.materials(), WI.lights()
+    cam = frame([0.4, 1.6, 2.6], [0.0, -0.1, 0.0])
+    p = big["positions"]
+    print("whitted refit of a clustered mesh, %d x %d, medians of %d after %d warm-up calls" % (W, H, REPS, WARM))
+    ctx = capi.Context(0)
+    ctx.whitted_set_scene(meshes, inst, mats)
+    view(ctx, lt["lights"], lt["miss"], cam)
+    print("%d triangles  %d vertices  as built %.3f ms/subframe" % (len(big["indices"]), len(p), subframe_ms(ctx)))
+    for k, (what, q) in enumerate(deformations(big)[:2]):
+        ctx.whitted_update_meshes([(1, p, None)])
+        t_update = median_ms(lambda: ctx.whitted_update_meshes([(1, q, None)]))
         refit = subframe_ms(ctx)
-        t_set = median_ms(lambda: set_mesh(ctx, mesh, q))
+        moved = [meshes[0], dict(big, positions=q)]
+        if k == 0:
+            t_set = median_ms(lambda: ctx.whitted_set_scene(moved, inst, mats))
+        else:
+            ctx.whitted_set_scene(moved, inst, mats)
         fresh = subframe_ms(ctx)
-        print("    %-8s update %7.3f ms   set_mesh %7.3f ms   set_mesh/update %5.1fx   subframe refit %.3f ms  fresh %.3f ms  refit/fresh %.3f" %
+        print("    %-8s update_meshes %8.3f ms   set_scene %9.3f ms   set_scene/update_meshes %6.1fx   subframe refit %.3f ms  fresh %.3f ms  refit/fresh %.3f" %
               (what, t_update, t_set, t_set / t_update, refit, fresh, refit / fresh))
+        ctx.whitted_set_scene(meshes, inst, mats)
     ctx.close()
+    # a field of 1024 tori drawn from K meshes: all K moved by one call against one call each
+    K = 16
+    tor = WI.torus(n_u=40, n_v=14, R=0.35, r=0.12)
+    meshes = [WI.ground(20.0, normals=True)] + [dict(tor) for _ in range(K)]
+    rng = np.random.RandomState(5)
+    inst = [(eye34, 0, 0)] + [(WI.transform(WI.rotation(rng), [-16.0 + 1.0 * (k % 32), 0.5, -16.0 + 1.0 * (k // 32)]), 1 + k % K, 1) for k in range(1024)]
+    ctx = capi.Context(0)
+    ctx.whitted_set_scene(meshes, inst, mats)
+    grown = [(1 + k, tor["positions"] * np.float32(1.0 + 0.02 * k), None) for k in range(K)]
+    t_batch = median_ms(lambda: ctx.whitted_update_meshes(grown))
+    t_single = median_ms(lambda: [ctx.whitted_update_mesh(m, q) for m, q, _ in grown])
+    t_set = median_ms(lambda: ctx.whitted_set_scene(meshes, inst, mats))
+    print("1024 tori of %d triangles drawn from %d meshes: update_meshes over all %d %.3f ms   %d calls of update_mesh %.3f ms   single/batch %.1fx   set_scene %.3f ms" %
+          (len(tor["indices"]), K, K, t_batch, K, t_single, t_single / t_batch, t_set))
+    ctx.close()
+
+
+if BIG:
+    big_mode()
+else:
+    torus = BM.displaced_torus(64, 64, texcoords=False)
+    torus.update(materials=WI.materials(), **WI.lights())
+    MESHES = [("scene 342", whitted_scene.build()), ("scene 3758", whitted_scene.build(n_lat=40, n_lon=48)), ("waterbottle", whitted_scene.waterbottle()),
+              ("torus 8192", torus)]
+
+    print("whitted refit, %d x %d, medians of %d after %d warm-up calls" % (W, H, REPS, WARM))
+    for name, mesh in MESHES:
+        p = mesh["positions"]
+        lo, hi = p.min(0), p.max(0)
+        c, ext = 0.5 * (lo + hi), float((hi - lo).max())
+        cam = frame(c + ext * np.array([0.08, 0.45, 1.1]), c)
+        ctx = capi.Context(0)
+        set_mesh(ctx, mesh, p)
+        ctx.whitted_set_lights(mesh["lights"])
+        ctx.whitted_set_miss_color(mesh["miss"])
+        ctx.set_camera(*cam)
+        ctx.resize(W * H)
+        built = subframe_ms(ctx)
+        print("%-12s %5d triangles  %5d vertices  as built %.3f ms/subframe" % (name, len(mesh["indices"]), len(p), built))
+        for what, q in deformations(mesh):
+            set_mesh(ctx, mesh, p)
+            t_update = median_ms(lambda: ctx.whitted_update_mesh(0, q))
+            refit = subframe_ms(ctx)
+            t_set = median_ms(lambda: set_mesh(ctx, mesh, q))
+            fresh = subframe_ms(ctx)
+            print("    %-8s update %7.3f ms   set_mesh %7.3f ms   set_mesh/update %5.1fx   subframe refit %.3f ms  fresh %.3f ms  refit/fresh %.3f" %
+                  (what, t_update, t_set, t_set / t_update, refit, fresh, refit / fresh))
+        ctx.close()
