@@ -299,6 +299,22 @@ typedef struct rtgo_whitted_frame {
    CUs (nothing is enqueued).  A rank that owns no row of the window enqueues nothing and returns RTGO_OK.  Asynchronous. */
 int rtgo_whitted_launch_frame(rtgo_ctx* ctx, const rtgo_whitted_frame* frame);
 
+/* n_subframes consecutive subframes of the frame's window / band share: frame->subframe_index, +1, ..., +n_subframes-1, over the scene,
+   camera, lights, miss colour and output the context holds now (an offline render of a still view, or a viewer that presents every
+   k-th subframe once the camera rests: no reference counterpart, the reference launches once per subframe).  Accumulation buffer and
+   image afterwards are, bit for bit, what n_subframes calls of rtgo_whitted_launch_frame with those indices in turn leave; a first index
+   above 0 continues from the accumulation buffer as it is, index 0 does not read it.  Asynchronous on the context's stream.
+   Every check of rtgo_whitted_launch_frame applies, with its codes; n_subframes == 0, or subframe_index + n_subframes passing 2^32:
+   RTGO_E_INVALID, nothing is enqueued.  n_subframes == 1 is rtgo_whitted_launch_frame(ctx, frame).  A rank that owns no row of the
+   window enqueues nothing and returns RTGO_OK.
+   ONE kernel launch, whatever scene the context holds (one mesh or instances, clustered meshes among them): a pixel's subframe f + 1
+   needs its own subframe f alone (whitted.cu:226-239: the running mean reads and writes accum_buffer[image_index] of the launch index
+   only; the seed, :196-198, and the jitter, :200-206, depend on the pixel and the subframe index), so a wave gives each pixel of its tile
+   several lanes, one subframe to a lane, and one of them folds the radiances into the mean in subframe order.  The 8-bit image is
+   written once, from the last mean.
+   rtgo_stats: the ray counts grow by the sum over the subframes, launches by 1; last_launch_ms is that launch. */
+int rtgo_whitted_launch_frames(rtgo_ctx* ctx, const rtgo_whitted_frame* frame, uint32_t n_subframes);
+
 /* ---- instanced meshes: sutil::Scene's two levels (one GAS per MeshGroup, buildMeshAccels; one OptixInstance per group in an IAS,
    buildInstanceAccel, sutil/Scene.cpp:985-1010) ---- */
 #define RTGO_WHITTED_MAX_MESHES 256

@@ -26,7 +26,7 @@ SYMBOLS = [
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
-    "rtgo_whitted_update_meshes",
+    "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames",
 ]
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
@@ -177,6 +177,7 @@ def load():
     L.rtgo_whitted_update_mesh.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32]
     L.rtgo_whitted_update_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
+    L.rtgo_whitted_launch_frames.argtypes = [vp, C.POINTER(WhittedFrame), C.c_uint32]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     for name in SYMBOLS:
@@ -436,6 +437,10 @@ class Context:
     def whitted_launch_frame(self, frame):
         """one subframe of a window / row band of the image (make_whitted_frame): the output holds the share's compact rows"""
         self._check(self._lib.rtgo_whitted_launch_frame(self._h, C.byref(frame)), "rtgo_whitted_launch_frame")
+
+    def whitted_launch_frames(self, frame, n):
+        """n subframes of the frame's share from frame.subframe_index on, in one kernel launch (rtgo_whitted_launch_frames)"""
+        self._check(self._lib.rtgo_whitted_launch_frames(self._h, C.byref(frame), int(n)), "rtgo_whitted_launch_frames")
 
     # ---- ray queries: the caller's own rays against the context's scene ----
     def _trace(self, fn, what, rays, flags):

@@ -473,7 +473,12 @@ int rtgo_create(int device, rtgo_ctx** out)
     for (const void* fn : {(const void*)whitted::render_kernel<whitted::kAllInL2>, (const void*)whitted::render_kernel<whitted::kRecordsInLds>,
                            (const void*)whitted::render_kernel<whitted::kAllInLds>, (const void*)whitted::render_inst_kernel<false>,
                            (const void*)whitted::render_inst_kernel<true>, (const void*)whitted::render_inst_kernel<false, true>,
-                           (const void*)whitted::render_inst_kernel<true, true>})
+                           (const void*)whitted::render_inst_kernel<true, true>,
+                           // ... and their FRAMES forms (rtgo_whitted_launch_frames)
+                           (const void*)whitted::render_kernel<whitted::kAllInL2, true>, (const void*)whitted::render_kernel<whitted::kRecordsInLds, true>,
+                           (const void*)whitted::render_kernel<whitted::kAllInLds, true>, (const void*)whitted::render_inst_kernel<false, false, true>,
+                           (const void*)whitted::render_inst_kernel<true, false, true>, (const void*)whitted::render_inst_kernel<false, true, true>,
+                           (const void*)whitted::render_inst_kernel<true, true, true>})
         if (err == hipSuccess) err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)whitted::kRenderLds);
     for (const void* fn : {(const void*)trace_rays_kernel<false>, (const void*)trace_rays_kernel<true>,
                            (const void*)whitted::whitted_trace_kernel<whitted::kTraceMesh, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceMesh, true>,
@@ -1839,7 +1844,23 @@ int rtgo_whitted_launch(rtgo_ctx* c, uint32_t width, uint32_t height, uint32_t s
     return rtgo_whitted_launch_frame(c, &f);
 }
 
-int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
+// Lanes per pixel of a launch of n subframes (log2; whitted::render_tile_subframes): of 8, 4 and 2 the one that leaves the fewest lanes
+// idle in the last chunk, the larger on a tie (2 -> 2, 3 -> 4, 5 -> 2, 7 -> 8, 11 -> 4, 16 -> 8).  RTGO_WHITTED_SUBFRAME_LANES (experiment
+// knob; no result depends on it): 1, 2, 4 or 8 instead -- 1 is one lane looping over its pixel's subframes.
+static unsigned int whitted_lanes_log2(uint32_t n)
+{
+    const unsigned int forced = env_uint("RTGO_WHITTED_SUBFRAME_LANES", 0);
+    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return forced == 1 ? 0u : (forced == 2 ? 1u : (forced == 4 ? 2u : 3u));
+    unsigned int best = 3;
+    for (unsigned int ls = 3; ls >= 1; --ls) {
+        auto slots = [&](unsigned int l) { return (((uint64_t)n + (1u << l) - 1) >> l) << l; };
+        if (slots(ls) < slots(best)) best = ls;
+    }
+    return best;
+}
+
+// rtgo_whitted_launch_frame (n_subframes 1: the single-subframe kernels) and rtgo_whitted_launch_frames (n_subframes > 1: their FRAMES forms)
+static int whitted_launch(rtgo_ctx* c, const rtgo_whitted_frame* f, uint32_t n_subframes)
 {
     if (!c) return RTGO_E_INVALID;
     if (!f) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch: NULL frame");
@@ -1869,8 +1890,13 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     std::memset(&fr, 0, sizeof fr);
     fr.tile_counter = c->w_tile_counters.get() + (size_t)c->w_launch_parity * whitted::kTileHeads * whitted::kTileHeadStride;
     fr.tile_counter_next = c->w_tile_counters.get() + (size_t)(1 - c->w_launch_parity) * whitted::kTileHeads * whitted::kTileHeadStride;
-    fr.tiles_x = (s.lw + 7) / 8;
-    fr.tiles_y = (s.lh + 7) / 8;
+    // the wave's tile: 8 x 8 pixels, or with 1 << lanes_log2 lanes per pixel 8 x 4, 4 x 4, 4 x 2
+    const bool frames = n_subframes > 1;
+    fr.n_subframes = n_subframes;
+    fr.lanes_log2 = frames ? whitted_lanes_log2(n_subframes) : 0u;
+    const unsigned int tile_w = 8u >> (fr.lanes_log2 >> 1), tile_h = 8u >> ((fr.lanes_log2 + 1u) >> 1);
+    fr.tiles_x = (s.lw + tile_w - 1) / tile_w;
+    fr.tiles_y = (s.lh + tile_h - 1) / tile_h;
     {
         const uint64_t nt = (uint64_t)fr.tiles_x * fr.tiles_y;
         auto gcd = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; };
@@ -1905,10 +1931,21 @@ int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f)
     if (blocks > cus) blocks = cus;
     int slot = 0;
     return timed_launch(c, slot, [&]() -> int {
-        const int rc = whitted_enqueue(c, fr, stack_bytes, env_whitted_mode(), blocks);
+        const int rc = whitted_enqueue(c, fr, stack_bytes, env_whitted_mode(), blocks, frames);
         if (rc == RTGO_OK) c->w_launch_parity = 1 - c->w_launch_parity;   // (only once the launch that zeroes the other head is in the stream)
         return rc;
     });
+}
+
+int rtgo_whitted_launch_frame(rtgo_ctx* c, const rtgo_whitted_frame* f) { return whitted_launch(c, f, 1); }
+
+int rtgo_whitted_launch_frames(rtgo_ctx* c, const rtgo_whitted_frame* f, uint32_t n_subframes)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (!f) return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch_frames: NULL frame");
+    if (n_subframes == 0 || (uint64_t)f->subframe_index + n_subframes > (1ull << 32))
+        return fail(c, RTGO_E_INVALID, "rtgo_whitted_launch_frames: n_subframes must be positive and subframe_index + n_subframes must not pass 2^32");
+    return whitted_launch(c, f, n_subframes);
 }
 
 // ---- ray queries (rtgo_trace.h) ----

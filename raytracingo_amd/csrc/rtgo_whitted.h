@@ -8,7 +8,8 @@
 // BOTH children's boxes).  The render kernel is persistent like the analytic path's: one workgroup of 1024 threads per CU keeps
 // the records in LDS (when they fit: always below ~2000 triangles, usually up to the limit), its waves pull 8 x 8-pixel tiles
 // from a counter; one lane = one pixel, one launch per subframe: a primary ray plus one shadow ray per point light, no
-// recursion (whitted.cu traces none either).
+// recursion (whitted.cu traces none either).  rtgo_whitted_launch_frames renders n subframes in one launch: the FRAMES instantiations,
+// S lanes per pixel (render_tiles).
 //
 // Compiled with -ffp-contract=off like the rest of the library: one IEEE rounding per operation.
 #pragma once
@@ -77,10 +78,14 @@ struct Frame {
     unsigned int* tile_counter_next;
     unsigned int tiles_x, tiles_y;  // 8 x 8 tiles over the compact local image, lw x lh
     unsigned int tile_stride;   // coprime to tiles_x * tiles_y
+    unsigned int lanes_log2;    // the FRAMES kernels alone (rtgo_whitted_launch_frames): 1 << lanes_log2 lanes per pixel, so tiles of
+                                //   64 >> lanes_log2 pixels (tiles_x, tiles_y and tile_stride count those); n_subframes goes with it.
+                                //   (The two sit in the words the pointers' alignment left empty: the layout is the single launch's.)
     const MatTex* mat_tex;      // per material, or null when no material has a texture
     const Pbr* materials;
     const PointLight* lights;
     int n_lights;
+    unsigned int n_subframes;   // FRAMES: the launch renders subframes subframe .. subframe + n_subframes - 1
     float4* accum;              // lw x lh, local row k = the k-th window row this launch owns
     uchar4* image;
     unsigned int width, height, subframe;   // the FULL image: seeds and ray directions
@@ -88,6 +93,7 @@ struct Frame {
     v3 eye, U, V, W, miss;
     unsigned long long* counters;   // [0] rays_total [1] rays_occlusion
 };
+static_assert(sizeof(Frame) == 192 && alignof(Frame) == 8, "Frame: lanes_log2 and n_subframes fill the two padding words");
 
 struct Params {       // whitted::LaunchParams, cuda/whitted.h:59-74, over one mesh in world space
     Frame frame;
@@ -433,11 +439,11 @@ __device__ __forceinline__ bool trace_lds(const Params& p, const uint4* __restri
 // ---- the pixel pipeline every render kernel runs: whitted.cu's programs around the kernel's own walk and hit geometry -------------
 
 // __raygen__pinhole, whitted.cu:183-240: the primary ray's direction through pixel (x, y) of the full image (its origin is the eye)
-__device__ __forceinline__ v3 raygen(const Frame& f, unsigned int x, unsigned int y)
+__device__ __forceinline__ v3 raygen(const Frame& f, unsigned int x, unsigned int y, unsigned int subframe)
 {
-    unsigned int seed = tea4(y * f.width + x, f.subframe);
+    unsigned int seed = tea4(y * f.width + x, subframe);
     float jx = 0.0f, jy = 0.0f;
-    if (f.subframe != 0) {
+    if (subframe != 0) {
         jx = rnd(seed) - 0.5f;   // x first (source order)
         jy = rnd(seed) - 0.5f;
     }
@@ -543,29 +549,93 @@ __device__ __forceinline__ v3 shade(const Frame& f, const HitGeom& h, v3 rd, Occ
     return result;
 }
 
-// whitted.cu:226-239: the running mean over subframes, and make_color (:164-173, gamma 2.2) of it
+// whitted.cu:226-239: the running mean over subframes (one step of it: subframe > 0 folds `result` into the mean of the subframes
+// before it), and make_color (:164-173, gamma 2.2) of it.  Both launch forms fold through running_mean, one subframe at a time in
+// subframe order, so they round alike.
+__device__ __forceinline__ v3 running_mean(v3 prev, v3 result, unsigned int subframe)
+{
+    const float a = 1.0f / (float)(subframe + 1);
+    return vadd(prev, vscale(vsub(result, prev), a));
+}
+__device__ __forceinline__ uchar4 make_color(v3 acc)
+{
+    const float g = (float)(1.0 / 2.2f);
+    return make_uchar4((unsigned char)(powf(clampf(acc.x, 0.0f, 1.0f), g) * 255.0f), (unsigned char)(powf(clampf(acc.y, 0.0f, 1.0f), g) * 255.0f),
+                       (unsigned char)(powf(clampf(acc.z, 0.0f, 1.0f), g) * 255.0f), 255u);
+}
 __device__ __forceinline__ void accumulate(const Frame& f, unsigned int idx, v3 result)
 {
     v3 acc = result;
     if (f.subframe > 0) {
-        const float a = 1.0f / (float)(f.subframe + 1);
         const float4 prev = f.accum[idx];
-        acc = vadd(mk(prev.x, prev.y, prev.z), vscale(vsub(acc, mk(prev.x, prev.y, prev.z)), a));
+        acc = running_mean(mk(prev.x, prev.y, prev.z), acc, f.subframe);
     }
     f.accum[idx] = make_float4(acc.x, acc.y, acc.z, 1.0f);
-    const float g = (float)(1.0 / 2.2f);
-    f.image[idx] = make_uchar4((unsigned char)(powf(clampf(acc.x, 0.0f, 1.0f), g) * 255.0f), (unsigned char)(powf(clampf(acc.y, 0.0f, 1.0f), g) * 255.0f),
-                               (unsigned char)(powf(clampf(acc.z, 0.0f, 1.0f), g) * 255.0f), 255u);
+    f.image[idx] = make_color(acc);
+}
+
+// One tile of a FRAMES launch (rtgo_whitted_launch_frames): S = 1 << lanes_log2 lanes per pixel, so the wave's tile is 64 / S pixels
+// (8 x 8, 8 x 4, 4 x 4, 4 x 2 for S = 1, 2, 4, 8).  Lane p S + j renders subframe first + j of pixel p with the pixel() body of the single
+// launch; lane p S then reads the S radiances from its neighbours and folds them in subframe order through running_mean: the operations
+// of S launches on that pixel, in their order.  More subframes than S are further chunks of the tile; between chunks the mean rests in the
+// accumulation buffer, which the folding lane alone writes and reads back (nothing of it is held across pixel(): the walks leave no
+// register for that).  Lanes of subframes past the last one trace nothing and count no ray.  The 8-bit image is written once.
+template <typename Pixel>
+__device__ __forceinline__ void render_tile_subframes(const Frame& f, unsigned int tile, Pixel&& pixel, Rays& rays)
+{
+    const unsigned int ls = f.lanes_log2, S = 1u << ls;
+    // the lane's pixel in the compact local image.  Derived again from the tile and the lane on either side of pixel() (opaque_lane,
+    // rtgo_device.h): held across it, these would be the registers the walks do not have
+    auto place = [&](unsigned int lane, unsigned int& lx, unsigned int& ly) -> bool {
+        unsigned int t = tile;
+        asm volatile("" : "+s"(t));
+        const unsigned int tw = 3u - (ls >> 1), th = 3u - ((ls + 1u) >> 1);   // log2 of the tile's width and height
+        const unsigned int ty = t / f.tiles_x, tx = t - ty * f.tiles_x;
+        const unsigned int pix = lane >> ls;
+        lx = (tx << tw) + (pix & ((1u << tw) - 1u));
+        ly = (ty << th) + (pix >> tw);
+        return lx < f.share.lw && ly < f.share.lh;
+    };
+    for (unsigned int c = 0;; c += S) {
+        const unsigned int left = f.n_subframes - c;   // subframes from this chunk on (>= 1)
+        v3 r = mk(0.0f, 0.0f, 0.0f);
+        {
+            const unsigned int lane = opaque_lane(), j = lane & (S - 1u);
+            unsigned int lx, ly;
+            if (place(lane, lx, ly) && j < left) r = pixel(f.share.x0 + lx, share_row(f.share, ly), f.subframe + c + j, rays);
+        }
+        const unsigned int lane = opaque_lane();
+        unsigned int lx, ly;
+        const bool fold = place(lane, lx, ly) && (lane & (S - 1u)) == 0u;
+        const unsigned int idx = ly * f.share.lw + lx;
+        const unsigned int first = f.subframe + c;   // the chunk's first subframe
+        v3 acc = mk(0.0f, 0.0f, 0.0f);
+        if (fold && first > 0u) {
+            const float4 prev = f.accum[idx];
+            acc = mk(prev.x, prev.y, prev.z);
+        }
+        for (unsigned int q = 0; q < S; ++q) {   // (every lane takes part in the cross-lane reads)
+            const int src = (int)((lane & ~(S - 1u)) + q);
+            const v3 rq = mk(__shfl(r.x, src), __shfl(r.y, src), __shfl(r.z, src));
+            if (q < left) acc = first + q == 0u ? rq : running_mean(acc, rq, first + q);
+        }
+        if (fold) {
+            f.accum[idx] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+            if (left <= S) f.image[idx] = make_color(acc);
+        }
+        if (left <= S) break;
+    }
 }
 
 // The body of every render kernel: preload() (the kernel's LDS image of its structure, ending in a barrier), then the wave's tiles
-// from the queue, pixel(x, y, rays) -> radiance for each pixel of the launch's share (x, y: in the full image), accumulated, and the
-// wave's ray counts added to the counters.
+// from the queue, pixel(x, y, subframe, rays) -> radiance for each pixel of the launch's share (x, y: in the full image), accumulated,
+// and the wave's ray counts added to the counters.  FRAMES: the launch renders Frame::n_subframes subframes of every pixel
+// (render_tile_subframes); queue, stacks and counters are the single launch's.
 //
 // Tile queue: kTileHeads counters 64 bytes apart, head h serves the tiles h, h + kTileHeads, ...  (one counter hands out ~88 entries per
 // microsecond chip-wide: a 1080p subframe is 32 k tiles).  A wave starts on head blockIdx % kTileHeads; when that is dry it looks at all
 // heads with one load and moves to an open one.  The pull for the next tile is in flight while the current one is rendered.
-template <typename Preload, typename Pixel>
+template <bool FRAMES, typename Preload, typename Pixel>
 __device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, Pixel&& pixel)
 {
     WhittedTiming timing;   // (diagnostic build's probe, rtgo_probes.h: an empty type in the product build)
@@ -598,11 +668,15 @@ __device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, 
         // queue at the vector memory pipeline for its triangles; scattered, tiles that wait for triangles overlap tiles that do not
         const unsigned int tile = (unsigned int)(((unsigned long long)(pos * (unsigned int)kTileHeads + head) * f.tile_stride) % n_tiles);
         if (lane == 0u) pending = atomicAdd(f.tile_counter + kTileHeadStride * head, 1u);
-        timing.tile_begin();
-        const unsigned int ty = tile / f.tiles_x, tx = tile - ty * f.tiles_x;
-        const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // in the compact local image
-        if (lx < f.share.lw && ly < f.share.lh) accumulate(f, ly * f.share.lw + lx, pixel(f.share.x0 + lx, share_row(f.share, ly), rays));
-        timing.tile_end(f, lx < f.share.lw && ly < f.share.lh, ly * f.share.lw + lx, rays.total);
+        if constexpr (FRAMES) {
+            render_tile_subframes(f, tile, pixel, rays);   // (the timing probe stays on the single launch)
+        } else {
+            timing.tile_begin();
+            const unsigned int ty = tile / f.tiles_x, tx = tile - ty * f.tiles_x;
+            const unsigned int lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);   // in the compact local image
+            if (lx < f.share.lw && ly < f.share.lh) accumulate(f, ly * f.share.lw + lx, pixel(f.share.x0 + lx, share_row(f.share, ly), f.subframe, rays));
+            timing.tile_end(f, lx < f.share.lw && ly < f.share.lh, ly * f.share.lw + lx, rays.total);
+        }
     }
     const unsigned int total = wave_sum(rays.total), occlusion = wave_sum(rays.occlusion);
     if (lane == 0u) {
@@ -612,8 +686,8 @@ __device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, 
     }
 }
 
-// One mesh in world space.  MODE: where the walk reads its structure from (kAllInL2 / kRecordsInLds / kAllInLds)
-template <int MODE>
+// One mesh in world space.  MODE: where the walk reads its structure from (kAllInL2 / kRecordsInLds / kAllInLds);  FRAMES: render_tiles'
+template <int MODE, bool FRAMES = false>
 __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char w_smem[];
@@ -645,8 +719,8 @@ __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
         if constexpr (MODE == kAllInLds) return trace_lds<true>(p, s_q, s_verts, s_tidx, s_stack, stride, o, d, t0, t1, tri, pos, t, u, v);
         else return trace<true>(p, recs, s_stack, stride, o, d, t0, t1, tri, pos, t, u, v);
     };
-    render_tiles(p.frame, preload, [&](unsigned int x, unsigned int y, Rays& rays) -> v3 {
-        const v3 rd = raygen(p.frame, x, y);
+    render_tiles<FRAMES>(p.frame, preload, [&](unsigned int x, unsigned int y, unsigned int subframe, Rays& rays) -> v3 {
+        const v3 rd = raygen(p.frame, x, y, subframe);
         const v3 miss = p.frame.miss;   // __miss__constant_radiance, :243-246 (read ahead of the walk: after it, kAllInLds spills)
         int tri, tpos;
         float t, bu, bv;

@@ -821,7 +821,8 @@ static whitted::InstParams inst_params(const WhittedMesh& wm)
 // The launch of the context's scene.  One mesh: beside the lanes' stacks (stack_bytes), its LDS holds as much of the structure as fits --
 // everything in its compact form (quantised records, vertices, 16-bit vertex indices), or the fp32 records alone, or nothing.  An instanced
 // scene: the top level's records and InstWalk array when they fit (and RTGO_WHITTED_MODE allows); the meshes are read through L2.
-static int whitted_enqueue(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
+template <bool FRAMES>
+static void whitted_enqueue_kernels(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks)
 {
     const dim3 grid(blocks), block(whitted::kRenderBlock);
     if (!c->wm.instanced) {
@@ -830,11 +831,11 @@ static int whitted_enqueue(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_b
         const size_t rec_bytes = (size_t)p.n_recs * 4 * sizeof(float4);
         const size_t compact_bytes = (size_t)p.n_recs * 2 * sizeof(uint4) + (size_t)p.n_vertices * sizeof(float4) + (size_t)p.n_triangles * sizeof(uint2);
         if (mode_cap >= whitted::kAllInLds && p.n_vertices <= 65535 && compact_bytes + stack_bytes <= whitted::kRenderLds)
-            hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInLds>, grid, block, compact_bytes + stack_bytes, c->stream, p);
+            hipLaunchKernelGGL((whitted::render_kernel<whitted::kAllInLds, FRAMES>), grid, block, compact_bytes + stack_bytes, c->stream, p);
         else if (mode_cap >= whitted::kRecordsInLds && rec_bytes + stack_bytes <= whitted::kRenderLds)
-            hipLaunchKernelGGL(whitted::render_kernel<whitted::kRecordsInLds>, grid, block, rec_bytes + stack_bytes, c->stream, p);
+            hipLaunchKernelGGL((whitted::render_kernel<whitted::kRecordsInLds, FRAMES>), grid, block, rec_bytes + stack_bytes, c->stream, p);
         else
-            hipLaunchKernelGGL(whitted::render_kernel<whitted::kAllInL2>, grid, block, stack_bytes, c->stream, p);
+            hipLaunchKernelGGL((whitted::render_kernel<whitted::kAllInL2, FRAMES>), grid, block, stack_bytes, c->stream, p);
     } else {
         whitted::InstParams q = inst_params(c->wm);
         q.frame = fr;
@@ -842,13 +843,20 @@ static int whitted_enqueue(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_b
         const bool in_lds = mode_cap >= whitted::kRecordsInLds && top_bytes + stack_bytes <= whitted::kRenderLds;
         const size_t lds = stack_bytes + (in_lds ? top_bytes : 0);
         if (q.clusters) {   // a clustered mesh in the scene: the three-level walk
-            if (in_lds) hipLaunchKernelGGL((whitted::render_inst_kernel<true, true>), grid, block, lds, c->stream, q);
-            else hipLaunchKernelGGL((whitted::render_inst_kernel<false, true>), grid, block, lds, c->stream, q);
+            if (in_lds) hipLaunchKernelGGL((whitted::render_inst_kernel<true, true, FRAMES>), grid, block, lds, c->stream, q);
+            else hipLaunchKernelGGL((whitted::render_inst_kernel<false, true, FRAMES>), grid, block, lds, c->stream, q);
         } else if (in_lds)
-            hipLaunchKernelGGL(whitted::render_inst_kernel<true>, grid, block, lds, c->stream, q);
+            hipLaunchKernelGGL((whitted::render_inst_kernel<true, false, FRAMES>), grid, block, lds, c->stream, q);
         else
-            hipLaunchKernelGGL(whitted::render_inst_kernel<false>, grid, block, lds, c->stream, q);
+            hipLaunchKernelGGL((whitted::render_inst_kernel<false, false, FRAMES>), grid, block, lds, c->stream, q);
     }
+}
+
+// frames: the launch of rtgo_whitted_launch_frames (fr.n_subframes subframes, the FRAMES instantiation of the same kernel)
+static int whitted_enqueue(rtgo_ctx* c, const whitted::Frame& fr, size_t stack_bytes, int mode_cap, unsigned int blocks, bool frames)
+{
+    if (frames) whitted_enqueue_kernels<true>(c, fr, stack_bytes, mode_cap, blocks);
+    else whitted_enqueue_kernels<false>(c, fr, stack_bytes, mode_cap, blocks);
     RTGO_HIP(c, hipGetLastError());
     return RTGO_OK;
 }

@@ -223,7 +223,8 @@ __device__ __forceinline__ bool trace_inst(const InstParams& p, const float4* to
 // Instanced meshes: render_tiles' pipeline over the two-level walk.
 // TOP_IN_LDS: the top level's records and the InstWalk array are copied into LDS ahead of the lanes' stacks; otherwise they are read
 // through L2 like the meshes' records.  CLUSTERED: the scene holds a clustered mesh (trace_inst's mid level and 64-bit hit key).
-template <bool TOP_IN_LDS, bool CLUSTERED = false>
+// FRAMES: render_tiles'.
+template <bool TOP_IN_LDS, bool CLUSTERED = false, bool FRAMES = false>
 __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char wi_smem[];
@@ -247,8 +248,8 @@ __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstPar
         float t, u, v;
         return trace_inst<true, CLUSTERED>(p, top, inst, s_stack, stride, o, d, t0, t1, key, pos, t, u, v);
     };
-    render_tiles(p.frame, preload, [&](unsigned int x, unsigned int y, Rays& rays) -> v3 {
-        const v3 rd = raygen(p.frame, x, y);
+    render_tiles<FRAMES>(p.frame, preload, [&](unsigned int x, unsigned int y, unsigned int subframe, Rays& rays) -> v3 {
+        const v3 rd = raygen(p.frame, x, y, subframe);
         const v3 miss = p.frame.miss;   // (read ahead of the walk, as render_kernel does)
         InstKey<CLUSTERED> key;
         int tpos;

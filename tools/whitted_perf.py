@@ -1,5 +1,7 @@
 """developer tool: time the whitted triangle path (rtgo_whitted_launch) on the procedural scene of tests/whitted_scene.py:
-   python tools/whitted_perf.py [W] [H] [n_lat] [n_lon]"""
+   python tools/whitted_perf.py [W] [H] [n_lat] [n_lon]
+then the same subframes n to a launch (rtgo_whitted_launch_frames, n = 2, 4, 8, 16; RTGO_WHITTED_SUBFRAME_LANES=1|2|4|8 overrides the
+lanes per pixel, 1 being one lane looping over its pixel's subframes)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -52,3 +54,17 @@ if st["node_visits"]:
     print("  map of tile durations (rows top to bottom; . < 25 us, - < 50, + < 100, * < 200, # more):")
     for yy in range(th - 1, -1, -max(1, th // 34)):
         print("    " + "".join(".-+*#"[int(np.searchsorted([25, 50, 100, 200], ticks[yy, xx:xx + max(1, tw // 80)].max()))] for xx in range(0, tw, max(1, tw // 80))))
+# the same scene, subframes 3 .. : n to a launch (the count rounded up to whole launches: 20, 20, 24, 32 subframes)
+for n in (2, 4, 8, 16):
+    calls = (K + n - 1) // n
+    ctx.whitted_launch_frames(capi.make_whitted_frame(W, H, 0), 3)
+    ctx.sync()
+    ctx.reset_stats()
+    for k in range(calls):
+        ctx.whitted_launch_frames(capi.make_whitted_frame(W, H, 3 + k * n), n)
+    ctx.sync()
+    sb = ctx.stats()
+    assert sb["launches"] == calls
+    msb = sb["total_launch_ms"] / (calls * n)
+    print("  %2d subframes per launch (rtgo_whitted_launch_frames): %.3f ms/subframe, %.1f Mray/s, %.2fx the single launches" %
+          (n, msb, sb["rays_total"] / (calls * n) / msb / 1e3, ms / msb))

@@ -3,7 +3,8 @@
    python tools/whitted_share_perf.py big [W] [H]     whitted_inst_perf.py big's scene: a 1 M-triangle clustered torus on a ground
 Rank 0's share at 1/2, 1/4 and 1/8 of a 4-, 8-, 16- and 32-row interleave: ms per launch (HIP events), and the kernel-only projection
 full / share at 2, 4 and 8 GPUs; then the same counts of contiguous row blocks (the slowest block).  The floor line is one 8 x 8
-window: one tile's latency and the fixed cost of a launch.  DESIGN.md section 6 has the numbers."""
+window: one tile's latency and the fixed cost of a launch.  Last, the 1/8 share of the 4-row interleave with n = 2, 4, 8, 16 subframes to
+a launch (rtgo_whitted_launch_frames).  DESIGN.md section 6 has the numbers."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -44,6 +45,20 @@ def time_share(ctx, window=None, bands=(4, 1, 0)):
     return st["total_launch_ms"] / K, st["rays_total"] / K
 
 
+def time_share_frames(ctx, n, bands):
+    """ms per SUBFRAME of the share with n subframes to a launch, over subframes 3 .. (K rounded up to whole launches)"""
+    calls = (K + n - 1) // n
+    ctx.resize(max(W * capi.local_rows(H, *bands), 1))
+    ctx.whitted_launch_frames(capi.make_whitted_frame(W, H, 0, bands=bands), 3)
+    ctx.sync()
+    ctx.reset_stats()
+    for k in range(calls):
+        ctx.whitted_launch_frames(capi.make_whitted_frame(W, H, 3 + k * n, bands=bands), n)
+    ctx.sync()
+    st = ctx.stats()
+    return st["total_launch_ms"] / (calls * n), st["rays_total"] / (calls * n)
+
+
 ctx = capi.Context(0)
 if what == "small":
     mesh = whitted_scene.build(n_lat=40, n_lon=48)
@@ -76,4 +91,10 @@ for G in (2, 4, 8):
     slow = max(range(G), key=lambda g: per[g][0])
     print("  %d contiguous blocks: slowest (block %d) %.4f ms, %.1f %% of the rays, fastest %.4f ms; kernel-only projection at %d GPUs: %.2fx" %
           (G, slow, per[slow][0], 100.0 * per[slow][1] / full_rays, min(p[0] for p in per), G, full_ms / per[slow][0]))
+# n subframes of one 1/8 share to a launch
+one_ms, _ = time_share(ctx, bands=(4, 8, 0))
+for n in (2, 4, 8, 16):
+    ms, rays = time_share_frames(ctx, n, (4, 8, 0))
+    print("  band_h 4 share 1/8, %2d subframes per launch (rtgo_whitted_launch_frames): %.4f ms/subframe, %.2f Gray/s, %.2fx the single launches (%.4f ms)" %
+          (n, ms, rays / ms / 1e6, one_ms / ms, one_ms))
 ctx.close()
