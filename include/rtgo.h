@@ -446,6 +446,28 @@ int rtgo_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uint32_t n,
    the walk, which culls by boxes, may then report the next hit instead. */
 int rtgo_whitted_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags);
 
+/* Shade n rays of the caller's own against the scene of rtgo_whitted_set_mesh / rtgo_whitted_set_scene: __closesthit__radiance and
+   __miss__constant_radiance (whitted.cu:243-337) behind a raygen program that is the caller's -- an orthographic or panoramic camera, a
+   stereo pair, a reflection or light probe, a baked lightmap.  d_rays = rtgo_ray[n], d_accum = float4[n], d_image = uchar4[n] or NULL:
+   DEVICE memory of the context's device, caller-owned, rays and accum 16-byte aligned, the image 4-byte aligned.  Asynchronous on the
+   context's stream.  Needs a whitted scene only: no camera, no output buffer; lights never set are zero lights; the miss colour is the
+   context's (rtgo_whitted_set_miss_color).  Per ray i:
+     invalid ray (rtgo_ray's rule)   sample_index == 0: accum[i] = (0,0,0,0) and image[i] = (0,0,0,0); sample_index > 0: both are left
+                                     untouched.  It is never walked.
+     valid ray                       result = the miss colour when no hit lies in tmin < t < tmax (the closest walk of the render kernels,
+                                     ties broken as there), else the radiance shaded at that hit with the ray's dir, as given, for the
+                                     viewing direction.  The occlusion rays are the shader's own: unit direction, 0.001 .. Ldist - 0.001.
+                                     acc = result when sample_index == 0, else prev + (result - prev) * (1 / (sample_index + 1)) with prev =
+                                     accum[i].xyz (whitted.cu:226-239: the fold of the launches, in float32, operation for operation).
+                                     accum[i] = (acc, 1); image[i] = make_color(acc) (:164-173) when d_image is given.
+   So the pinhole rays of subframe s (origin the eye, tmin 0.01, tmax 1e16) with sample_index = s leave rtgo_whitted_launch's two buffers,
+   bit for bit.  t and the hit's identity are not returned: they come from rtgo_whitted_trace_rays, which runs the same walk.
+   RTGO_E_INVALID: NULL ctx, d_rays or d_accum, a misaligned pointer, n > 1 << 30; RTGO_E_STATE: no whitted scene (an analytic scene alone
+   does not count); n == 0: RTGO_OK.  In all of these nothing is enqueued or written.  rtgo_stats: rays_total grows by n plus the occlusion
+   rays the shader sent, rays_occlusion by those occlusion rays; launches, last_launch_ms and last_variant are left alone, and so are the
+   render launches' tile queue and its parity: launches and these calls may alternate freely. */
+int rtgo_whitted_shade_rays(rtgo_ctx* ctx, const void* d_rays, void* d_accum, void* d_image, uint32_t n, uint32_t sample_index);
+
 /* number of window rows a rank owns under the band interleave (pure host arithmetic) */
 uint32_t rtgo_local_rows(uint32_t h, uint32_t band_h, uint32_t n_ranks, uint32_t rank);
 

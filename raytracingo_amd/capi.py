@@ -26,7 +26,7 @@ SYMBOLS = [
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
-    "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames",
+    "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays",
 ]
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
@@ -180,6 +180,7 @@ def load():
     L.rtgo_whitted_launch_frames.argtypes = [vp, C.POINTER(WhittedFrame), C.c_uint32]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
+    L.rtgo_whitted_shade_rays.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtgo_last_error", "rtgo_local_rows", "rtgo_abi_version"):
@@ -490,6 +491,56 @@ class Context:
         """the bare C call on two device pointers (asynchronous); returns the library's code instead of raising"""
         fn = self._lib.rtgo_whitted_trace_rays if whitted else self._lib.rtgo_trace_rays
         return int(fn(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr), int(n), int(flags)))
+
+    def whitted_shade_rays(self, rays, sample_index=0, accum=None, image=True):
+        """rtgo_whitted_shade_rays over the scene of whitted_set_mesh / whitted_set_scene.  rays: as trace_rays takes them.  accum: the mean
+        of the samples before this one, [n, 4] float32, uploaded when sample_index > 0 (None: zeros).  Returns (accum [n, 4] float32,
+        image [n, 4] uint8, or None with image=False).  Synchronous."""
+        what = "rtgo_whitted_shade_rays"
+        H = hip_runtime()
+        if hasattr(rays, "data_ptr"):   # a torch device tensor: shaded where it is
+            if not rays.is_cuda or not rays.is_contiguous() or rays.numel() * rays.element_size() % 32:
+                raise ValueError("%s: rays must be a contiguous device tensor of 32-byte rtgo_ray records" % what)
+            n, host = rays.numel() * rays.element_size() // 32, None
+        else:
+            host = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+            n = len(host)
+        out = np.zeros((n, 4), dtype=np.float32)
+        if sample_index > 0 and accum is not None:
+            out[:] = np.asarray(accum, dtype=np.float32).reshape(n, 4)
+        img = np.zeros((n, 4), dtype=np.uint8) if image else None
+        if n == 0:
+            return out, img
+        if H.hipSetDevice(self.device) != 0:
+            raise RtgoError("%s: hipSetDevice(%d) failed" % (what, self.device))
+        buf = C.c_void_p()   # [accum 16 n][rays 32 n, when uploaded][image 4 n]
+        ray_bytes = 0 if host is None else 32 * n
+        if H.hipMalloc(C.byref(buf), 16 * n + ray_bytes + 4 * n) != 0:
+            raise RtgoError("%s: hipMalloc of %d bytes failed" % (what, 20 * n + ray_bytes))
+        try:
+            d_accum, d_image = buf.value, buf.value + 16 * n + ray_bytes
+            if host is None:
+                d_rays = rays.data_ptr()
+                H.hipDeviceSynchronize()   # (whatever stream filled the tensor: the call runs on the context's)
+            else:
+                d_rays = buf.value + 16 * n
+                if H.hipMemcpy(d_rays, host.ctypes.data, 32 * n, 1) != 0:
+                    raise RtgoError("%s: upload failed" % what)
+            if sample_index > 0 and H.hipMemcpy(d_accum, out.ctypes.data, 16 * n, 1) != 0:
+                raise RtgoError("%s: upload failed" % what)
+            self._check(self._lib.rtgo_whitted_shade_rays(self._h, C.c_void_p(d_rays), C.c_void_p(d_accum), C.c_void_p(d_image if image else 0), n,
+                                                          int(sample_index)), what)
+            self.sync()
+            if H.hipMemcpy(out.ctypes.data, d_accum, 16 * n, 2) != 0 or (image and H.hipMemcpy(img.ctypes.data, d_image, 4 * n, 2) != 0):
+                raise RtgoError("%s: download failed" % what)
+        finally:
+            H.hipFree(buf)
+        return out, img
+
+    def whitted_shade_rays_raw(self, d_rays_ptr, d_accum_ptr, d_image_ptr, n, sample_index=0):
+        """the bare C call on three device pointers (asynchronous); returns the library's code instead of raising"""
+        return int(self._lib.rtgo_whitted_shade_rays(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_accum_ptr), C.c_void_p(d_image_ptr or 0), int(n),
+                                                     int(sample_index)))
 
     def stats(self):
         s = Stats()

@@ -486,7 +486,11 @@ int rtgo_create(int device, rtgo_ctx** out)
                            (const void*)whitted::whitted_trace_kernel<whitted::kTraceInstLds, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceInstLds, true>,
                            (const void*)whitted::whitted_trace_kernel<whitted::kTraceClustered, false>, (const void*)whitted::whitted_trace_kernel<whitted::kTraceClustered, true>,
                            (const void*)whitted::whitted_trace_kernel<whitted::kTraceClusteredLds, false>,
-                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceClusteredLds, true>})
+                           (const void*)whitted::whitted_trace_kernel<whitted::kTraceClusteredLds, true>,
+                           // ... and the kernels of rtgo_whitted_shade_rays
+                           (const void*)whitted::whitted_shade_kernel<whitted::kTraceMesh>, (const void*)whitted::whitted_shade_kernel<whitted::kTraceInst>,
+                           (const void*)whitted::whitted_shade_kernel<whitted::kTraceInstLds>, (const void*)whitted::whitted_shade_kernel<whitted::kTraceClustered>,
+                           (const void*)whitted::whitted_shade_kernel<whitted::kTraceClusteredLds>})
         if (err == hipSuccess) err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
     if (err == hipSuccess) err = hipDeviceSynchronize();  // the null-stream memsets above must land before any launch
     if (err != hipSuccess) {
@@ -2031,6 +2035,36 @@ int rtgo_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, u
     return RTGO_OK;
 }
 
+// What the two ray-batch calls of the triangle path share (rtgo_whitted_trace_rays, rtgo_whitted_shade_rays): the walk's kind, the scene
+// half of its parameters, LDS and grid.  Workgroups of 256 lanes: nothing is shared between the lanes but the top level's copy, and the
+// tail of a batch is shorter.  max_per_cu: workgroups a CU can hold of the kernel (its registers).
+static constexpr int kWhittedRaysBlock = 256;
+struct WhittedRaysPlan {
+    int kind;
+    size_t lds;
+    unsigned int grid;
+};
+static WhittedRaysPlan whitted_rays_plan(const rtgo_ctx* c, const WhittedMesh& wm, uint32_t n, whitted::Params& mesh, whitted::InstParams& inst, int max_per_cu)
+{
+    const size_t stack_bytes = (size_t)kWhittedRaysBlock * (size_t)(wm.walk_depth > 0 ? wm.walk_depth : 1) * sizeof(unsigned short);
+    WhittedRaysPlan plan{whitted::kTraceMesh, stack_bytes, 0};
+    if (!wm.instanced) {
+        mesh = mesh_params(wm);
+    } else {
+        inst = inst_params(wm);
+        // the top level in LDS where four workgroups a CU still fit with it (RTGO_TRACE_MODE: never / wherever one fits)
+        const size_t top_bytes = (size_t)inst.n_top_recs * 4 * sizeof(float4) + (size_t)inst.n_instances * sizeof(whitted::InstWalk);
+        const int mode = env_trace_mode();
+        const bool in_lds = mode != 0 && top_bytes + stack_bytes <= (mode == 1 ? kTraceLds : kTraceLds / 4);
+        if (in_lds) plan.lds += top_bytes;
+        plan.kind = inst.clusters ? (in_lds ? whitted::kTraceClusteredLds : whitted::kTraceClustered) : (in_lds ? whitted::kTraceInstLds : whitted::kTraceInst);
+    }
+    int per_cu = (int)(kTraceLds / plan.lds);
+    if (per_cu > max_per_cu) per_cu = max_per_cu;
+    plan.grid = trace_grid(c, n, kWhittedRaysBlock, per_cu);
+    return plan;
+}
+
 int rtgo_whitted_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags)
 {
     if (const int rc = trace_check(c, d_rays, d_hits, n, flags, "rtgo_whitted_trace_rays")) return rc;
@@ -2042,26 +2076,11 @@ int rtgo_whitted_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint3
     p.rays = (const float4*)d_rays;
     p.hits = (float4*)d_hits;
     p.n = n;
-    // workgroups of 256 lanes: nothing is shared between the lanes but the top level's copy, and the tail of a batch is shorter
-    const int block = 256;
-    const size_t stack_bytes = (size_t)block * (size_t)(wm.walk_depth > 0 ? wm.walk_depth : 1) * sizeof(unsigned short);
     const bool any = (flags & RTGO_TRACE_ANY_HIT) != 0;
-    size_t lds = stack_bytes;
-    int kind = whitted::kTraceMesh;
-    if (!wm.instanced) {
-        p.mesh = mesh_params(wm);
-    } else {
-        p.inst = inst_params(wm);
-        // the top level in LDS where four workgroups a CU still fit with it (RTGO_TRACE_MODE: never / wherever one fits)
-        const size_t top_bytes = (size_t)p.inst.n_top_recs * 4 * sizeof(float4) + (size_t)p.inst.n_instances * sizeof(whitted::InstWalk);
-        const int mode = env_trace_mode();
-        const bool in_lds = mode != 0 && top_bytes + stack_bytes <= (mode == 1 ? kTraceLds : kTraceLds / 4);
-        if (in_lds) lds += top_bytes;
-        kind = p.inst.clusters ? (in_lds ? whitted::kTraceClusteredLds : whitted::kTraceClustered) : (in_lds ? whitted::kTraceInstLds : whitted::kTraceInst);
-    }
-    int per_cu = (int)(kTraceLds / lds);
-    if (per_cu > 8) per_cu = 8;
-    const dim3 grid(trace_grid(c, n, block, per_cu)), bdim(block);
+    const WhittedRaysPlan plan = whitted_rays_plan(c, wm, n, p.mesh, p.inst, 8);
+    const int kind = plan.kind;
+    const size_t lds = plan.lds;
+    const dim3 grid(plan.grid), bdim(kWhittedRaysBlock);
     RTGO_HIP(c, hipSetDevice(c->device));
     using namespace whitted;
 #define RTGO_WT(K)                                                                                             \
@@ -2080,6 +2099,54 @@ int rtgo_whitted_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint3
     RTGO_HIP(c, hipGetLastError());
     c->trace_rays += n;
     if (any) c->trace_rays_any += n;
+    return RTGO_OK;
+}
+
+// Lights never set: none (the launches allocate the array on first use; this call reads none of it then).  The render launches' tile
+// counters and parity are not touched: the kernel has no tile queue.
+int rtgo_whitted_shade_rays(rtgo_ctx* c, const void* d_rays, void* d_accum, void* d_image, uint32_t n, uint32_t sample_index)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (!d_rays || !d_accum) return fail(c, RTGO_E_INVALID, "rtgo_whitted_shade_rays: NULL ray or accumulation buffer");
+    if ((((uintptr_t)d_rays | (uintptr_t)d_accum) & 15u) || ((uintptr_t)d_image & 3u))
+        return fail(c, RTGO_E_INVALID, "rtgo_whitted_shade_rays: ray and accumulation buffers must be 16-byte aligned, the image 4-byte aligned");
+    if (n > kTraceMaxRays) return fail(c, RTGO_E_INVALID, "rtgo_whitted_shade_rays: more than 2^30 rays");
+    const WhittedMesh& wm = c->wm;
+    if (wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_shade_rays: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene)");
+    if (n == 0) return RTGO_OK;
+    whitted::ShadeRaysParams p;
+    std::memset(&p, 0, sizeof p);
+    p.rays = (const float4*)d_rays;
+    p.accum = (float4*)d_accum;
+    p.image = (uchar4*)d_image;
+    p.n = n;
+    p.sample_index = sample_index;
+    // at 128 VGPRs a CU holds four of the kernel's 256-lane workgroups
+    const WhittedRaysPlan plan = whitted_rays_plan(c, wm, n, p.mesh, p.inst, 4);
+    whitted::Frame& fr = wm.instanced ? p.inst.frame : p.mesh.frame;   // what shade() reads of a frame
+    fr.mat_tex = wm.mat_tex.get();
+    fr.materials = wm.materials.get();
+    fr.lights = c->w_lights.get();
+    fr.n_lights = c->w_lights.get() ? c->w_n_lights : 0;
+    fr.miss = c->w_miss;
+    fr.counters = c->d_counters.get();
+    const dim3 grid(plan.grid), bdim(kWhittedRaysBlock);
+    RTGO_HIP(c, hipSetDevice(c->device));
+    using namespace whitted;
+#define RTGO_WS(K)                                                                                 \
+    case K:                                                                                        \
+        hipLaunchKernelGGL((whitted_shade_kernel<K>), grid, bdim, plan.lds, c->stream, p);         \
+        break;
+    switch (plan.kind) {
+        RTGO_WS(kTraceMesh)
+        RTGO_WS(kTraceInst)
+        RTGO_WS(kTraceInstLds)
+        RTGO_WS(kTraceClustered)
+        RTGO_WS(kTraceClusteredLds)
+    }
+#undef RTGO_WS
+    RTGO_HIP(c, hipGetLastError());
+    c->trace_rays += n;   // the batch; the occlusion rays are counted by the kernel, in both counters
     return RTGO_OK;
 }
 

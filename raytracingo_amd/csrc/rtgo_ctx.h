@@ -9,6 +9,7 @@
 #include "rtgo_trace.h"
 #include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
+#include "rtgo_whitted_shade.h"
 
 #include <algorithm>
 #include <array>
@@ -149,7 +150,7 @@ struct rtgo_ctx {
     float total_ms = 0.0f, last_ms = 0.0f;
     uint32_t launches = 0;
     uint32_t seeds_last = 0;                  // rtgo_debug_seeds: 1 = the last launch read pre-hashed seeds, 2 = it wrote the next frame's
-    unsigned long long trace_rays = 0, trace_rays_any = 0;   // rays of rtgo_trace_rays / rtgo_whitted_trace_rays since rtgo_reset_stats (host arithmetic)
+    unsigned long long trace_rays = 0, trace_rays_any = 0;   // rays of rtgo_trace_rays / rtgo_whitted_trace_rays / rtgo_whitted_shade_rays (its batch; its occlusion rays are the kernel's count) since rtgo_reset_stats (host arithmetic)
 #ifdef RTGO_CMPWALK
     DeviceArray<float> d_cmp;                 // diagnostic build: disagreements between the two walks
 #endif

@@ -686,6 +686,54 @@ __device__ __forceinline__ void render_tiles(const Frame& f, Preload&& preload, 
     }
 }
 
+// __closesthit__radiance at a hit of a mesh in world space, from the walk's answer: triangle `tri` at position tpos of the Morton order,
+// barycentrics (bu, bv) -- the hit geometry, then shade().  MODE: where the render kernel keeps the structure (kAllInLds: corners and indices
+// from its LDS image, s_verts / s_tidx; otherwise through L2, and the LDS pointers are not read).  render_kernel and whitted_shade_kernel
+// (rtgo_whitted_shade.h) both call it, so the arithmetic cannot drift.  (Geometry and shading are ONE function on purpose: with the
+// geometry alone behind a call the compiler forms the normal loads' offsets right after the index load and waits for it there.)
+template <int MODE, typename Occluded>
+__device__ __forceinline__ v3 mesh_shade_hit(const Params& p, const float4* s_verts, const uint2* s_tidx, int tri, int tpos, float bu, float bv, v3 rd,
+                                             Occluded&& occluded, Rays& rays)
+{
+    // (The corners come from the Morton-ordered copy the walk read them from: same values, no trip through the index array.)
+    float4 c0, c1, c2;
+    HitGeom h;
+    h.i0 = h.i1 = h.i2 = 0;
+    if constexpr (MODE == kAllInLds) {
+        const uint2 ti = s_tidx[tpos];
+        h.i0 = ti.x & 0xFFFFu;
+        h.i1 = ti.x >> 16;
+        h.i2 = ti.y & 0xFFFFu;
+        c0 = s_verts[h.i0];
+        c1 = s_verts[h.i1];
+        c2 = s_verts[h.i2];
+    } else {
+        c0 = p.tris[3 * tpos + 0];
+        c1 = p.tris[3 * tpos + 1];
+        c2 = p.tris[3 * tpos + 2];
+        if (p.normals || p.texcoords) {
+            h.i0 = p.indices[3 * tri + 0];
+            h.i1 = p.indices[3 * tri + 1];
+            h.i2 = p.indices[3 * tri + 2];
+        }
+    }
+    h.P0 = mk(c0.x, c0.y, c0.z);
+    h.P1 = mk(c1.x, c1.y, c1.z);
+    h.P2 = mk(c2.x, c2.y, c2.z);
+    h.w0 = 1.0f - bu - bv;
+    h.bu = bu;
+    h.bv = bv;
+    h.P = vadd(vadd(vscale(h.P0, h.w0), vscale(h.P1, bu)), vscale(h.P2, bv));
+    h.N = vnormalize(vcross(vsub(h.P1, h.P0), vsub(h.P2, h.P0)));   // Ng
+    if (p.normals) {
+        const v3 N0 = ld3(p.normals, h.i0), N1 = ld3(p.normals, h.i1), N2 = ld3(p.normals, h.i2);
+        h.N = vnormalize(vadd(vadd(vscale(N0, h.w0), vscale(N1, bu)), vscale(N2, bv)));
+    }
+    h.texcoords = p.texcoords;
+    h.material = p.tri_material ? p.tri_material[tri] : 0u;
+    return shade(p.frame, h, rd, occluded, rays);
+}
+
 // One mesh in world space.  MODE: where the walk reads its structure from (kAllInL2 / kRecordsInLds / kAllInLds);  FRAMES: render_tiles'
 template <int MODE, bool FRAMES = false>
 __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
@@ -729,44 +777,7 @@ __global__ __launch_bounds__(kRenderBlock) void render_kernel(const Params p)
         if constexpr (MODE == kAllInLds) hit = trace_lds<false>(p, s_q, s_verts, s_tidx, s_stack, stride, p.frame.eye, rd, 0.01f, 1e16f, tri, tpos, t, bu, bv);
         else hit = trace<false>(p, recs, s_stack, stride, p.frame.eye, rd, 0.01f, 1e16f, tri, tpos, t, bu, bv);
         if (!hit) return miss;
-        // the hit geometry of a mesh in world space.  (The corners come from the Morton-ordered copy the walk read them from: same
-        // values, no trip through the index array.)
-        float4 c0, c1, c2;
-        HitGeom h;
-        h.i0 = h.i1 = h.i2 = 0;
-        if constexpr (MODE == kAllInLds) {
-            const uint2 ti = s_tidx[tpos];
-            h.i0 = ti.x & 0xFFFFu;
-            h.i1 = ti.x >> 16;
-            h.i2 = ti.y & 0xFFFFu;
-            c0 = s_verts[h.i0];
-            c1 = s_verts[h.i1];
-            c2 = s_verts[h.i2];
-        } else {
-            c0 = p.tris[3 * tpos + 0];
-            c1 = p.tris[3 * tpos + 1];
-            c2 = p.tris[3 * tpos + 2];
-            if (p.normals || p.texcoords) {
-                h.i0 = p.indices[3 * tri + 0];
-                h.i1 = p.indices[3 * tri + 1];
-                h.i2 = p.indices[3 * tri + 2];
-            }
-        }
-        h.P0 = mk(c0.x, c0.y, c0.z);
-        h.P1 = mk(c1.x, c1.y, c1.z);
-        h.P2 = mk(c2.x, c2.y, c2.z);
-        h.w0 = 1.0f - bu - bv;
-        h.bu = bu;
-        h.bv = bv;
-        h.P = vadd(vadd(vscale(h.P0, h.w0), vscale(h.P1, bu)), vscale(h.P2, bv));
-        h.N = vnormalize(vcross(vsub(h.P1, h.P0), vsub(h.P2, h.P0)));   // Ng
-        if (p.normals) {
-            const v3 N0 = ld3(p.normals, h.i0), N1 = ld3(p.normals, h.i1), N2 = ld3(p.normals, h.i2);
-            h.N = vnormalize(vadd(vadd(vscale(N0, h.w0), vscale(N1, bu)), vscale(N2, bv)));
-        }
-        h.texcoords = p.texcoords;
-        h.material = p.tri_material ? p.tri_material[tri] : 0u;
-        return shade(p.frame, h, rd, occluded, rays);
+        return mesh_shade_hit<MODE>(p, s_verts, s_tidx, tri, tpos, bu, bv, rd, occluded, rays);
     });
 }
 

@@ -220,6 +220,41 @@ __device__ __forceinline__ bool trace_inst(const InstParams& p, const float4* to
     return best >= 0;
 }
 
+// __closesthit__radiance at a hit of an instanced mesh, from the walk's answer: the hit key (trace_inst's), the triangle's position tpos in
+// InstParams::tris, barycentrics (bu, bv) -- the hit geometry, then shade().  render_inst_kernel and whitted_shade_kernel
+// (rtgo_whitted_shade.h) both call it.
+template <bool CLUSTERED, typename Occluded>
+__device__ __forceinline__ v3 inst_shade_hit(const InstParams& p, InstKey<CLUSTERED> key, int tpos, float bu, float bv, v3 rd, Occluded&& occluded, Rays& rays)
+{
+    // the corners in object space, o2w for P (LocalGeometry.h:84), W2O^T for the normals (:103, :112)
+    const int ii = CLUSTERED ? (int)(key >> 32) : (int)(key >> kInstShift), tri = CLUSTERED ? (int)(key & 0xFFFFFFFF) : (int)(key & ((1 << kInstShift) - 1));
+    const InstShade sh = p.shade[ii];
+    const float4 c0 = p.tris[3 * tpos + 0], c1 = p.tris[3 * tpos + 1], c2 = p.tris[3 * tpos + 2];
+    HitGeom h;
+    h.i0 = h.i1 = h.i2 = 0;
+    if (sh.flags) {
+        h.i0 = (unsigned int)sh.vert_base + p.indices[3 * (sh.tri_base + tri) + 0];
+        h.i1 = (unsigned int)sh.vert_base + p.indices[3 * (sh.tri_base + tri) + 1];
+        h.i2 = (unsigned int)sh.vert_base + p.indices[3 * (sh.tri_base + tri) + 2];
+    }
+    h.P0 = mk(c0.x, c0.y, c0.z);
+    h.P1 = mk(c1.x, c1.y, c1.z);
+    h.P2 = mk(c2.x, c2.y, c2.z);
+    h.w0 = 1.0f - bu - bv;
+    h.bu = bu;
+    h.bv = bv;
+    h.P = xform_point(sh.o2w[0], sh.o2w[1], sh.o2w[2], vadd(vadd(vscale(h.P0, h.w0), vscale(h.P1, bu)), vscale(h.P2, bv)));
+    const float4 m0 = sh.w2o[0], m1 = sh.w2o[1], m2 = sh.w2o[2];
+    h.N = xform_normal(m0, m1, m2, vnormalize(vcross(vsub(h.P1, h.P0), vsub(h.P2, h.P0))));   // Ng: not unit length under a transform that is not rigid (:103, 116)
+    if (sh.flags & kHasNormals) {
+        const v3 N0 = ld3(p.normals, h.i0), N1 = ld3(p.normals, h.i1), N2 = ld3(p.normals, h.i2);
+        h.N = vnormalize(xform_normal(m0, m1, m2, vadd(vadd(vscale(N0, h.w0), vscale(N1, bu)), vscale(N2, bv))));
+    }
+    h.texcoords = (sh.flags & kHasTexcoords) ? p.texcoords : nullptr;
+    h.material = (unsigned int)sh.material_offset + p.tri_material[sh.tri_base + tri];
+    return shade(p.frame, h, rd, occluded, rays);
+}
+
 // Instanced meshes: render_tiles' pipeline over the two-level walk.
 // TOP_IN_LDS: the top level's records and the InstWalk array are copied into LDS ahead of the lanes' stacks; otherwise they are read
 // through L2 like the meshes' records.  CLUSTERED: the scene holds a clustered mesh (trace_inst's mid level and 64-bit hit key).
@@ -256,34 +291,7 @@ __global__ __launch_bounds__(kRenderBlock) void render_inst_kernel(const InstPar
         float t, bu, bv;
         rays.total += 1;
         if (!trace_inst<false, CLUSTERED>(p, top, inst, s_stack, stride, p.frame.eye, rd, 0.01f, 1e16f, key, tpos, t, bu, bv)) return miss;
-        // the hit geometry of an instanced mesh: the corners in object space, o2w for P (LocalGeometry.h:84), W2O^T for the normals
-        // (:103, :112)
-        const int ii = CLUSTERED ? (int)(key >> 32) : (int)(key >> kInstShift), tri = CLUSTERED ? (int)(key & 0xFFFFFFFF) : (int)(key & ((1 << kInstShift) - 1));
-        const InstShade sh = p.shade[ii];
-        const float4 c0 = p.tris[3 * tpos + 0], c1 = p.tris[3 * tpos + 1], c2 = p.tris[3 * tpos + 2];
-        HitGeom h;
-        h.i0 = h.i1 = h.i2 = 0;
-        if (sh.flags) {
-            h.i0 = (unsigned int)sh.vert_base + p.indices[3 * (sh.tri_base + tri) + 0];
-            h.i1 = (unsigned int)sh.vert_base + p.indices[3 * (sh.tri_base + tri) + 1];
-            h.i2 = (unsigned int)sh.vert_base + p.indices[3 * (sh.tri_base + tri) + 2];
-        }
-        h.P0 = mk(c0.x, c0.y, c0.z);
-        h.P1 = mk(c1.x, c1.y, c1.z);
-        h.P2 = mk(c2.x, c2.y, c2.z);
-        h.w0 = 1.0f - bu - bv;
-        h.bu = bu;
-        h.bv = bv;
-        h.P = xform_point(sh.o2w[0], sh.o2w[1], sh.o2w[2], vadd(vadd(vscale(h.P0, h.w0), vscale(h.P1, bu)), vscale(h.P2, bv)));
-        const float4 m0 = sh.w2o[0], m1 = sh.w2o[1], m2 = sh.w2o[2];
-        h.N = xform_normal(m0, m1, m2, vnormalize(vcross(vsub(h.P1, h.P0), vsub(h.P2, h.P0))));   // Ng: not unit length under a transform that is not rigid (:103, 116)
-        if (sh.flags & kHasNormals) {
-            const v3 N0 = ld3(p.normals, h.i0), N1 = ld3(p.normals, h.i1), N2 = ld3(p.normals, h.i2);
-            h.N = vnormalize(xform_normal(m0, m1, m2, vadd(vadd(vscale(N0, h.w0), vscale(N1, bu)), vscale(N2, bv))));
-        }
-        h.texcoords = (sh.flags & kHasTexcoords) ? p.texcoords : nullptr;
-        h.material = (unsigned int)sh.material_offset + p.tri_material[sh.tri_base + tri];
-        return shade(p.frame, h, rd, occluded, rays);
+        return inst_shade_hit<CLUSTERED>(p, key, tpos, bu, bv, rd, occluded, rays);
     });
 }
 
