@@ -350,9 +350,10 @@ typedef struct rtgo_whitted_instance {
    together, or a structure deeper than the walk's stack (top level + mid level + deepest cluster of a clustered mesh):
    RTGO_E_UNSUPPORTED.  Builds both levels on the device; replaces the scene of rtgo_whitted_set_mesh (and that call replaces this
    one); clears every texture.  The closest hit is the smallest t, then the lowest (instance, triangle): an instanced scene renders
-   like the concatenation of its instances.  Synchronous; a clustered mesh (beyond RTGO_MAX_TRIANGLES) is built cluster by cluster, so the
-   call takes time in proportion to its triangles (about 6 s per million on an MI355X: some 100 s for one mesh at
-   RTGO_WHITTED_MAX_MESH_TRIANGLES). */
+   like the concatenation of its instances.  Synchronous; every structure of the call -- the clusters of its clustered meshes (beyond
+   RTGO_MAX_TRIANGLES) and its small meshes -- is built by one batched sequence of launches, one workgroup per structure, so the call
+   takes time in proportion to its triangles (measured on an MI355X: 42 ms for a mesh of 1 000 000 triangles, of which 27 ms are the
+   surface-area pass over its 245 clusters). */
 int rtgo_whitted_set_scene(rtgo_ctx* ctx, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances,
                            uint32_t n_instances, const rtgo_pbr* materials, uint32_t n_materials);
 
@@ -367,7 +368,8 @@ int rtgo_whitted_set_instances(rtgo_ctx* ctx, const rtgo_whitted_instance* insta
    refitted to the moved triangles (in an instanced scene the top level is rebuilt over the mesh's new box): no sort, no hierarchy,
    no surface-area sweep, a fraction of the time of setting the mesh again.  The frame is bit for bit that of a scene set afresh with
    the same vertices (any tree over the same triangles returns the same closest hit); what a refit cannot keep is the quality of the
-   tree, so after a deformation that moves neighbouring triangles far apart the walk slows down and setting the mesh again pays.
+   tree, so after a deformation that moves neighbouring triangles far apart the walk slows down and building the mesh again
+   (rtgo_whitted_rebuild_meshes) pays.
    positions: n_vertices x 3 floats, copied; normals: the same, or NULL to keep the normals the mesh has.  RTGO_E_STATE: no whitted
    scene.  RTGO_E_INVALID: `mesh` beyond the scene's meshes, positions NULL, n_vertices not the mesh's own, non-finite data, normals
    for a mesh that was set without, an instance that now places the mesh beyond the float range.  RTGO_E_UNSUPPORTED: a clustered mesh
@@ -397,6 +399,22 @@ typedef struct rtgo_whitted_mesh_update {
    the device first and put back).  Synchronous.  (rtgo_whitted_update_mesh keeps its own path and its refusal of clustered meshes;
    forwarding it to this call is left for later.) */
 int rtgo_whitted_update_meshes(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* updates, uint32_t n_updates);
+
+/* optixAccelBuild with OPTIX_BUILD_OPERATION_BUILD for some meshes of the scene the context holds: every entry's mesh is built again
+   over its new vertices -- a fresh Morton order, hierarchy and surface-area records, for a clustered mesh a fresh cluster cut and mid
+   level -- in place, and the top level once over all the new boxes.  Afterwards the context holds what a fresh rtgo_whitted_set_scene
+   (rtgo_whitted_set_mesh for a one-mesh scene) with the new vertices would hold, array for array; unlike that call it keeps the
+   meshes not named, indices, triangle materials, texture coordinates, instances, lights, the miss colour and the textures.  Every
+   structure of the call (all clusters of all named clustered meshes, the named small meshes) is built by one batched sequence of
+   launches.  Arguments, entry struct and refusals are rtgo_whitted_update_meshes's: n_updates == 0: RTGO_OK, nothing changes; a scene
+   of rtgo_whitted_set_mesh takes one entry, mesh 0.  RTGO_E_STATE: no whitted scene.  RTGO_E_INVALID: `updates` NULL with
+   n_updates > 0, a mesh index beyond the scene's meshes, a mesh named twice, positions NULL, n_vertices not the mesh's own, non-finite
+   data, normals for a mesh that was set without, an instance that now places a mesh beyond the float range.  RTGO_E_UNSUPPORTED: a
+   structure deeper than the walk's stack (top level + mid level + deepest cluster).  A refused call leaves the scene as it was,
+   whichever entry it refuses (depth and box are known only after the build: what it writes for a named mesh is saved on the device
+   first and put back).  Afterwards rtgo_whitted_set_instances, rtgo_whitted_update_mesh, rtgo_whitted_update_meshes and this call
+   work as after a fresh rtgo_whitted_set_scene.  Synchronous. */
+int rtgo_whitted_rebuild_meshes(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* updates, uint32_t n_updates);
 
 /* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
    rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */

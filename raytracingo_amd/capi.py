@@ -26,7 +26,7 @@ SYMBOLS = [
     "rtgo_whitted_set_mesh", "rtgo_whitted_set_lights", "rtgo_whitted_set_miss_color", "rtgo_whitted_launch",
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
-    "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays",
+    "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
 ]
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
@@ -176,6 +176,7 @@ def load():
     L.rtgo_whitted_set_instances.argtypes = [vp, C.POINTER(WhittedInstance), C.c_uint32]
     L.rtgo_whitted_update_mesh.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32]
     L.rtgo_whitted_update_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
+    L.rtgo_whitted_rebuild_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
     L.rtgo_whitted_launch_frames.argtypes = [vp, C.POINTER(WhittedFrame), C.c_uint32]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
@@ -391,18 +392,28 @@ class Context:
         self._check(self._lib.rtgo_whitted_update_mesh(self._h, int(mesh), pos.ctypes.data, nrm.ctypes.data if nrm is not None else None, len(pos)),
                     "rtgo_whitted_update_mesh")
 
-    def whitted_update_meshes(self, updates):
-        """rtgo_whitted_update_meshes: [(mesh, positions [nv, 3], normals or None), ...] refitted as one transaction (clustered meshes too)"""
+    def _mesh_updates(self, updates, who):
         arr = (WhittedMeshUpdate * max(len(updates), 1))()
-        keep = []
+        keep = []   # the arrays the entries point into, alive until the call returns
         for k, (mesh, positions, normals) in enumerate(updates):
             pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
             nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
             if nrm is not None and len(nrm) != len(pos):
-                raise ValueError("whitted_update_meshes: one normal per position")
+                raise ValueError(who + ": one normal per position")
             keep += [pos, nrm]
             arr[k] = WhittedMeshUpdate(int(mesh), pos.ctypes.data, nrm.ctypes.data if nrm is not None else None, len(pos))
+        return arr, keep
+
+    def whitted_update_meshes(self, updates):
+        """rtgo_whitted_update_meshes: [(mesh, positions [nv, 3], normals or None), ...] refitted as one transaction (clustered meshes too)"""
+        arr, keep = self._mesh_updates(updates, "whitted_update_meshes")
         self._check(self._lib.rtgo_whitted_update_meshes(self._h, arr, len(updates)), "rtgo_whitted_update_meshes")
+
+    def whitted_rebuild_meshes(self, updates):
+        """rtgo_whitted_rebuild_meshes: [(mesh, positions [nv, 3], normals or None), ...] built again in place as one transaction; the
+        rest of the scene (other meshes, instances, materials, textures) stays"""
+        arr, keep = self._mesh_updates(updates, "whitted_rebuild_meshes")
+        self._check(self._lib.rtgo_whitted_rebuild_meshes(self._h, arr, len(updates)), "rtgo_whitted_rebuild_meshes")
 
     def whitted_set_texcoords(self, uv):
         if uv is None:

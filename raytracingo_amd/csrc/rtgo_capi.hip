@@ -470,6 +470,9 @@ int rtgo_create(int device, rtgo_ctx** out)
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildDynLds);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::sah_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(whitted::kMaxTriangles * sizeof(unsigned long long)));
+    // (the batched builds of rtgo_whitted_big.h: each keeps the LDS of the kernel whose body it runs)
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::big_sah_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)whitted::big_build_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(whitted::kMaxTriangles * sizeof(unsigned long long)));
     for (const void* fn : {(const void*)whitted::render_kernel<whitted::kAllInL2>, (const void*)whitted::render_kernel<whitted::kRecordsInLds>,
                            (const void*)whitted::render_kernel<whitted::kAllInLds>, (const void*)whitted::render_inst_kernel<false>,
                            (const void*)whitted::render_inst_kernel<true>, (const void*)whitted::render_inst_kernel<false, true>,
@@ -1765,6 +1768,13 @@ int rtgo_whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* upda
     if (!c) return RTGO_E_INVALID;
     if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_update_meshes: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene first)");
     return whitted_update_meshes(c, updates, n_updates);
+}
+
+int rtgo_whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_rebuild_meshes: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene first)");
+    return whitted_rebuild_meshes(c, updates, n_updates);
 }
 
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)

@@ -831,27 +831,42 @@ constexpr size_t build_scratch_ints(size_t n) { return 38 * n + 16; }
 struct BuildScratch {
     int *parent, *visit, *first_of, *count_of, *rec_of, *sah;
     WhittedBuildMeta* meta;
-    BuildScratch(int* ints, int n)
+    __host__ __device__ BuildScratch(int* ints, int n)
         : parent(ints), visit(parent + (2 * n - 1)), first_of(visit + n), count_of(first_of + n), rec_of(count_of + n), sah(rec_of + n + 16),
           meta(reinterpret_cast<WhittedBuildMeta*>(rec_of + n))
     {
     }
 };
 
-__global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
-                                                              float4* __restrict__ nodes, int* __restrict__ parent, int* __restrict__ visit,
-                                                              int* __restrict__ first_of, int* __restrict__ count_of, int* __restrict__ rec_of,
-                                                              float4* __restrict__ recs, float4* __restrict__ tris, uint4* __restrict__ qrecs,
-                                                              uint2* __restrict__ tidx, WhittedBuildMeta* __restrict__ out_meta)
+// What one build works on: the vertices and the n index triples of its triangles, its work arrays (BuildScratch's, and the Morton
+// hierarchy's nodes [(2n - 1) x 2]), and where its structure goes.  The body is build_structure, one workgroup over one BuildJob:
+// build_kernel runs it over one structure, big_build_batch_kernel (rtgo_whitted_big.h) with one workgroup per structure of a table.
+struct BuildJob {
+    const float* positions;
+    const unsigned int* indices;
+    int n;
+    float4* nodes;
+    int *parent, *visit, *first_of, *count_of, *rec_of;
+    float4 *recs, *tris;
+    uint4* qrecs;
+    uint2* tidx;
+    WhittedBuildMeta* out_meta;
+};
+
+// One workgroup of kBuildThreads threads; s_keys: its kMaxTriangles x 8 B of (dynamic) LDS.  (The job's arrays do not overlap: the body
+// takes them as __restrict__ parameters, as build_kernel always declared them.)
+__device__ __forceinline__ void build_structure_body(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
+                                                     float4* __restrict__ nodes, int* __restrict__ parent, int* __restrict__ visit, int* __restrict__ first_of,
+                                                     int* __restrict__ count_of, int* __restrict__ rec_of, float4* __restrict__ recs, float4* __restrict__ tris,
+                                                     uint4* __restrict__ qrecs, uint2* __restrict__ tidx, WhittedBuildMeta* __restrict__ out_meta,
+                                                     unsigned long long* s_keys)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char build_keys_dyn[];   // kMaxTriangles x 8 B: the launch passes the size
-    unsigned long long* s_keys = reinterpret_cast<unsigned long long*>(build_keys_dyn);
     __shared__ float s_red[6][kBuildThreads];
     __shared__ int s_depth, s_nrec, s_wdepth;
     const int tid = threadIdx.x;
     if (tid == 0) {
         s_depth = 0;
-        s_nrec = 1;     // record 0 is the root's
+        s_nrec = 0;
         s_wdepth = 0;
     }
     // scene bounds
@@ -936,7 +951,32 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
     // ---- the structure the render kernel walks --------------------------------------------------------------------
     // Subtrees of at most kLeafTris triangles become leaves (their triangles are neighbours in Morton order); every node above
     // them gets one record with BOTH children's boxes, so that a step of the walk reads 64 contiguous bytes.
-    for (int i = tid; i < n - 1; i += kBuildThreads) rec_of[i] = count_of[i] > kLeafTris ? (i == 0 ? 0 : atomicAdd(&s_nrec, 1)) : -1;
+    // Records are numbered in node order, by a prefix sum over the nodes that get one (the root's is record 0): the same numbers whichever
+    // kernel runs this body and however its waves are scheduled -- a counter handed out by atomicAdd numbers them in arrival order, and
+    // then two builds of the same mesh need not write the same arrays.
+    {
+        constexpr int kPer = kMaxTriangles / kBuildThreads;    // a thread numbers kPer consecutive nodes
+        int* s_cnt = reinterpret_cast<int*>(&s_red[0][0]);     // [kBuildThreads] (the bounds were read out of s_red long ago)
+        int mine = 0;
+        for (int k = 0; k < kPer; ++k) {
+            const int i = tid * kPer + k;
+            if (i < n - 1 && count_of[i] > kLeafTris) ++mine;
+        }
+        s_cnt[tid] = mine;
+        __syncthreads();
+        for (int d = 1; d < kBuildThreads; d <<= 1) {
+            const int below = tid >= d ? s_cnt[tid - d] : 0;
+            __syncthreads();
+            s_cnt[tid] += below;
+            __syncthreads();
+        }
+        int r = s_cnt[tid] - mine;
+        for (int k = 0; k < kPer; ++k) {
+            const int i = tid * kPer + k;
+            if (i < n - 1) rec_of[i] = count_of[i] > kLeafTris ? r++ : -1;
+        }
+        if (tid == kBuildThreads - 1) s_nrec = s_cnt[tid];
+    }
     __syncthreads();
     // grid of the compact form: cells 1 .. 65534 span the padded scene box
     float glo[3], gstep[3];
@@ -977,6 +1017,22 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
     }
 }
 
+__device__ __forceinline__ void build_structure(const BuildJob& j, unsigned long long* s_keys)
+{
+    build_structure_body(j.positions, j.indices, j.n, j.nodes, j.parent, j.visit, j.first_of, j.count_of, j.rec_of, j.recs, j.tris, j.qrecs, j.tidx, j.out_meta, s_keys);
+}
+
+__global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices, int n,
+                                                              float4* __restrict__ nodes, int* __restrict__ parent, int* __restrict__ visit,
+                                                              int* __restrict__ first_of, int* __restrict__ count_of, int* __restrict__ rec_of,
+                                                              float4* __restrict__ recs, float4* __restrict__ tris, uint4* __restrict__ qrecs,
+                                                              uint2* __restrict__ tidx, WhittedBuildMeta* __restrict__ out_meta)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char build_keys_dyn[];   // kMaxTriangles x 8 B: the launch passes the size
+    build_structure({positions, indices, n, nodes, parent, visit, first_of, count_of, rec_of, recs, tris, qrecs, tidx, out_meta},
+                    reinterpret_cast<unsigned long long*>(build_keys_dyn));
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The walk's records rebuilt over the same leaves with the surface-area heuristic (second session of round 2).  build_kernel's
 // Morton hierarchy forms the leaves (subtrees of at most kLeafTris triangles: neighbours in Morton order, contiguous in `tris`);
@@ -985,12 +1041,25 @@ __global__ __launch_bounds__(kBuildThreads) void build_kernel(const float* __res
 // What sets the whitted launch is one wave's serial walk over the finely tessellated part: fewer steps there.
 // Overwrites recs / qrecs and out_meta's n_recs and walk_depth; scratch: 32 n ints.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4* __restrict__ nodes, const int* __restrict__ parent, const int* __restrict__ first_of,
-                                                            const int* __restrict__ count_of, int* __restrict__ scratch, float4* __restrict__ recs,
-                                                            uint4* __restrict__ qrecs, WhittedBuildMeta* __restrict__ out_meta)
+// What one surface-area pass works on: build_structure's hierarchy over n triangles (read), its 32 n ints of scratch, and the records and
+// meta it rewrites.  The body is sah_structure, one workgroup over one SahJob: sah_kernel runs it over one structure,
+// big_sah_batch_kernel (rtgo_whitted_big.h) with one workgroup per structure of a table.
+struct SahJob {
+    int n;
+    const float4* nodes;
+    const int *parent, *first_of, *count_of;
+    int* scratch;
+    float4* recs;
+    uint4* qrecs;
+    WhittedBuildMeta* out_meta;
+};
+
+// One workgroup of kBuildThreads threads; sah_dyn: its 33 n + 16 bytes of (dynamic) LDS
+__device__ __forceinline__ void sah_structure_body(int n, const float4* __restrict__ nodes, const int* __restrict__ parent, const int* __restrict__ first_of,
+                                                   const int* __restrict__ count_of, int* __restrict__ scratch, float4* __restrict__ recs,
+                                                   uint4* __restrict__ qrecs, WhittedBuildMeta* __restrict__ out_meta, unsigned char* sah_dyn)
 {
     if (n <= kLeafTris) return;   // the mesh is one leaf: no records
-    extern __shared__ __attribute__((aligned(16))) unsigned char sah_dyn[];
     float (*u_box)[6] = reinterpret_cast<float (*)[6]>(sah_dyn);      // [n] leaf boxes
     int* u_link = reinterpret_cast<int*>(u_box + n);                  // [n] the leaf's link in the walk's records
     short* perm = reinterpret_cast<short*>(u_link + n);               // [n] leaves in the current task order
@@ -1064,6 +1133,19 @@ __global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4*
         out_meta->n_recs = s_nrec;
         out_meta->walk_depth = s_wdepth;
     }
+}
+
+__device__ __forceinline__ void sah_structure(const SahJob& j, unsigned char* sah_dyn)
+{
+    sah_structure_body(j.n, j.nodes, j.parent, j.first_of, j.count_of, j.scratch, j.recs, j.qrecs, j.out_meta, sah_dyn);
+}
+
+__global__ __launch_bounds__(kBuildThreads) void sah_kernel(int n, const float4* __restrict__ nodes, const int* __restrict__ parent, const int* __restrict__ first_of,
+                                                            const int* __restrict__ count_of, int* __restrict__ scratch, float4* __restrict__ recs,
+                                                            uint4* __restrict__ qrecs, WhittedBuildMeta* __restrict__ out_meta)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char sah_dyn[];
+    sah_structure({n, nodes, parent, first_of, count_of, scratch, recs, qrecs, out_meta}, sah_dyn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

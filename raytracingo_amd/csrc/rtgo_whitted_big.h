@@ -7,8 +7,10 @@
 //   big_bounds_kernel (grid-stride partial boxes) -> big_bounds_final_kernel (one workgroup) -> big_keys_kernel (Morton code of the
 //   centroid on build_kernel's 10-bit grid, key = code << 32 | triangle) -> four LSD radix passes over the code's bytes
 //   (radix_count_kernel, radix_scan_kernel, radix_scatter_kernel; stable, and the keys start in triangle order, so the order is
-//   (code, triangle): unique keys, one deterministic order) -> big_gather_kernel (each sorted triangle's index triple) -> per cluster
-//   whitted_build -> big_remap_kernel (cluster-local triangle numbers in tris[].w back to the mesh's own).
+//   (code, triangle): unique keys, one deterministic order) -> big_gather_kernel (each sorted triangle's index triple) -> the batched
+//   builds, whitted_build over every structure of the call with one workgroup each (big_build_batch_kernel, big_sah_batch_kernel,
+//   big_build_batch_kernel for the surface-area trees that came out too deep, big_batch_offsets_kernel, big_pack_records_kernel: below)
+//   -> big_remap_kernel (cluster-local triangle numbers in tris[].w back to the mesh's own).
 // A refit to moved vertices (rtgo_whitted_update_meshes) keeps all of that and runs big_bounds_kernel, big_bounds_final_kernel (the
 // mesh's box), big_refit_clusters_kernel (every cluster, one workgroup each), big_cluster_boxes_kernel and refit_kernel (the mid level).
 #pragma once
@@ -230,6 +232,97 @@ __global__ __launch_bounds__(kBuildThreads) void big_refit_clusters_kernel(const
     refit_structure<true>({positions, indices, c.n, c.n_recs, c.walk_depth, recs + 4 * (size_t)c.rec0, tris + 3 * (size_t)c.tri0, qrecs + 2 * (size_t)c.tri0,
                            done + c.tri0, out_meta + blockIdx.x},
                           s_red);
+}
+
+// ---- batched builds (rtgo_whitted_set_scene, rtgo_whitted_rebuild_meshes) -----------------------------------------------------------
+// One structure of a call's build table: a cluster of a clustered mesh (indices: its slice of the gathered triples) or a whole small
+// mesh, n <= kMaxTriangles triangles.  tris, qrecs and tidx are its final slices (addressed by triangle slot); its records go to the
+// staging of its workgroup's slot first, since where they start in the scene's arrays is known only once the structures before it
+// have reported how many they have.  rec_start >= 0: the first structure of its mesh, whose records start there; the others' follow.
+struct BuildEntry {
+    const float* positions;
+    const unsigned int* indices;
+    float4* tris;
+    uint4* qrecs;
+    uint2* tidx;
+    int n, sah, rec_start, pad;   // sah: the surface-area pass applies (its LDS need fits, RTGO_WHITTED_NO_SAH unset)
+};
+static_assert(sizeof(BuildEntry) == 56, "five pointers, four words");
+
+// The scratch of a round of at most kBatchRound structures, each of at most max_n triangles: slot b (workgroup b of the round's
+// launches) has nodes [2 (2 max_n - 1)] float4, BuildScratch's ints [build_scratch_ints(max_n)] and record staging [4 max_n] float4
+constexpr int kBatchRound = 256;   // of the order of the CU count: one build workgroup fills a CU's LDS
+struct BatchSlots {
+    float4* nodes;
+    int* ints;
+    float4* stage;
+    int max_n;
+    __host__ __device__ float4* nodes_of(int b) const { return nodes + (size_t)b * 2 * (2 * (size_t)max_n - 1); }
+    __host__ __device__ int* ints_of(int b) const { return ints + (size_t)b * build_scratch_ints((size_t)max_n); }
+    __host__ __device__ float4* stage_of(int b) const { return stage + (size_t)b * 4 * (size_t)max_n; }
+};
+
+// build_kernel's body over entries first .. first + gridDim.x - 1 of the table, one workgroup per entry; metas[e] gets entry e's meta.
+// redo = 0: every entry.  redo = 1, launched after big_sah_batch_kernel: only the entries whose surface-area tree came out deeper than
+// the walk's stack get their Morton records back (whitted_build's fallback); the other workgroups leave at once.  A workgroup touches
+// its own entry's slices and its own slot only.
+__global__ __launch_bounds__(kBuildThreads) void big_build_batch_kernel(const BuildEntry* __restrict__ table, int first, BatchSlots slots,
+                                                                        WhittedBuildMeta* metas, int redo)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char build_batch_keys_dyn[];   // kMaxTriangles x 8 B
+    const int e = first + blockIdx.x;
+    const BuildEntry en = table[e];
+    if (redo && !(en.sah && metas[e].walk_depth > kMaxWalkDepth)) return;   // (uniform over the workgroup)
+    const BuildScratch w(slots.ints_of(blockIdx.x), en.n);
+    build_structure({en.positions, en.indices, en.n, slots.nodes_of(blockIdx.x), w.parent, w.visit, w.first_of, w.count_of, w.rec_of,
+                     slots.stage_of(blockIdx.x), en.tris, en.qrecs, en.tidx, metas + e},
+                    reinterpret_cast<unsigned long long*>(build_batch_keys_dyn));
+}
+
+// sah_kernel's body over the same entries and slots (the entries without the pass leave at once)
+__global__ __launch_bounds__(kBuildThreads) void big_sah_batch_kernel(const BuildEntry* __restrict__ table, int first, BatchSlots slots, WhittedBuildMeta* metas)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char sah_batch_dyn[];   // 33 B per triangle of the round's largest entry
+    const int e = first + blockIdx.x;
+    const BuildEntry en = table[e];
+    if (!en.sah) return;
+    const BuildScratch w(slots.ints_of(blockIdx.x), en.n);
+    sah_structure({en.n, slots.nodes_of(blockIdx.x), w.parent, w.first_of, w.count_of, w.sah, slots.stage_of(blockIdx.x), en.qrecs, metas + e}, sah_batch_dyn);
+}
+
+// One workgroup: where the records of entries first .. first + count - 1 (count <= kBatchRound) start in the scene's arrays -> rec0[e]:
+// rec_start for the first structure of a mesh, else where the structure before it ends.  *carry holds that end across rounds.
+__global__ __launch_bounds__(kBatchRound) void big_batch_offsets_kernel(const BuildEntry* __restrict__ table, int first, int count,
+                                                                        const WhittedBuildMeta* __restrict__ metas, int* __restrict__ rec0, int* carry)
+{
+    __shared__ int s_n[kBatchRound], s_start[kBatchRound];
+    const int tid = threadIdx.x;
+    if (tid < count) {
+        s_n[tid] = metas[first + tid].n_recs;
+        s_start[tid] = table[first + tid].rec_start;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int run = *carry;
+        for (int k = 0; k < count; ++k) {
+            if (s_start[k] >= 0) run = s_start[k];
+            rec0[first + k] = run;
+            run += s_n[k];
+        }
+        *carry = run;
+    }
+}
+
+// The staged records of entry first + blockIdx.x to their place, recs[4 rec0 ..] of the scene (links inside a structure are relative to
+// its first record: a plain copy)
+__global__ __launch_bounds__(256) void big_pack_records_kernel(int first, BatchSlots slots, const WhittedBuildMeta* __restrict__ metas,
+                                                               const int* __restrict__ rec0, float4* __restrict__ recs)
+{
+    const int e = first + blockIdx.x;
+    const int n4 = 4 * metas[e].n_recs;
+    const float4* __restrict__ src = slots.stage_of(blockIdx.x);
+    float4* __restrict__ dst = recs + 4 * (size_t)rec0[e];
+    for (int k = threadIdx.x; k < n4; k += 256) dst[k] = src[k];
 }
 
 }  // namespace whitted

@@ -38,6 +38,14 @@ struct WhittedBuildScratch {
     }
 };
 
+// The records over a build's leaves are rebuilt top-down with the surface-area heuristic when sah_kernel's LDS holds them (leaf boxes,
+// links, order arrays: 33 B per triangle, so structures beyond ~4650 triangles keep the Morton records) and RTGO_WHITTED_NO_SAH is unset.
+// RTGO_WHITTED_SEQ_BUILD (set): rtgo_whitted_set_scene builds its structures one after another (whitted_build) instead of by the batched
+// launches (whitted_run_batch) -- the same arrays; for A/B timing and tests/test_whitted_rebuild_meshes.py.
+static size_t whitted_sah_lds(int n) { return (size_t)n * (6 * sizeof(float) + sizeof(int) + 2 * sizeof(short) + 1) + 16; }
+static bool whitted_sah_applies(int n) { return !std::getenv("RTGO_WHITTED_NO_SAH") && whitted_sah_lds(n) <= 150 * 1024; }
+static bool whitted_sequential_builds() { return std::getenv("RTGO_WHITTED_SEQ_BUILD") != nullptr; }
+
 // One structure of the whitted path, built on the device over n triangles (positions, indices: device memory) into `t`: build_kernel's
 // Morton hierarchy, its records rebuilt top-down with the surface-area heuristic (sah_kernel) when the leaves fit its LDS, and the Morton
 // records again when the surface-area tree comes out deeper than the walk's stack.  Synchronous.
@@ -49,10 +57,8 @@ static int whitted_build(rtgo_ctx* c, const float* positions, const unsigned int
     hipLaunchKernelGGL(whitted::build_kernel, dim3(1), dim3(whitted::kBuildThreads), keys_lds, c->stream, positions, indices, n, s.nodes.get(),
                        w.parent, w.visit, w.first_of, w.count_of, w.rec_of, t.recs, t.tris, t.qrecs, t.tidx, w.meta);
     RTGO_HIP(c, hipGetLastError());
-    // the records over the same leaves, rebuilt top-down with the surface-area heuristic (leaf boxes, links, order arrays in LDS: 33 B per
-    // triangle, so meshes beyond ~4650 triangles keep the Morton records)
-    const size_t sah_lds = (size_t)n * (6 * sizeof(float) + sizeof(int) + 2 * sizeof(short) + 1) + 16;
-    const bool sah = !std::getenv("RTGO_WHITTED_NO_SAH") && sah_lds <= 150 * 1024;
+    const size_t sah_lds = whitted_sah_lds(n);
+    const bool sah = whitted_sah_applies(n);
     if (sah) {
         hipLaunchKernelGGL(whitted::sah_kernel, dim3(1), dim3(whitted::kBuildThreads), sah_lds, c->stream, n, (const float4*)s.nodes.get(), (const int*)w.parent,
                            (const int*)w.first_of, (const int*)w.count_of, w.sah, t.recs, t.qrecs, w.meta);
@@ -210,9 +216,10 @@ static int whitted_prepare_instances(rtgo_ctx* c, const std::vector<WhittedMeshI
 }
 
 // The top level of `wm` (its meshes built) over prepared instances, into `top`: the structure over the instance boxes, the InstWalk records
-// in leaf order, and the stack both levels need (depth).  Nothing of wm changes.
-static int whitted_make_top(rtgo_ctx* c, const WhittedMesh& wm, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos,
-                            const rtgo_whitted_instance* inst, const char* what, WhittedTop& top, int& depth)
+// in leaf order, and the stack both levels need (depth).  Nothing of wm changes.  whitted_make_top_over: the same over meshes that are not
+// wm's yet (rtgo_whitted_rebuild_meshes: a rebuilt mesh's root link and depth can differ).
+static int whitted_make_top_over(rtgo_ctx* c, const std::vector<WhittedMeshInfo>& meshes, int mesh_depth, const std::vector<whitted::InstShade>& shade,
+                                 const std::vector<float>& box_pos, const rtgo_whitted_instance* inst, const char* what, WhittedTop& top, int& depth)
 {
     const int n = (int)shade.size();
     DeviceArray<float> d_boxes;
@@ -220,14 +227,14 @@ static int whitted_make_top(rtgo_ctx* c, const WhittedMesh& wm, const std::vecto
     RTGO_HIP(c, d_boxes.upload(box_pos.data(), box_pos.size(), c->stream));
     RTGO_HIP(c, top.recs.alloc((size_t)n * 4));
     if (const int rc = whitted_build_boxes(c, d_boxes.get(), n, top.recs.get(), order, top.meta, what)) return rc;
-    depth = (top.meta.n_recs > 0 ? top.meta.walk_depth : 0) + wm.mesh_depth;
+    depth = (top.meta.n_recs > 0 ? top.meta.walk_depth : 0) + mesh_depth;
     if (depth > whitted::kMaxInstWalkDepth)
         return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " +
                                                std::to_string(whitted::kMaxInstWalkDepth) + ")");
     std::vector<whitted::InstWalk> walk((size_t)n);
     for (int pos = 0; pos < n; ++pos) {
         const int i = order[pos];
-        const WhittedMeshInfo& mi = wm.meshes[inst[i].mesh];
+        const WhittedMeshInfo& mi = meshes[inst[i].mesh];
         walk[pos] = whitted::InstWalk{{shade[i].w2o[0], shade[i].w2o[1], shade[i].w2o[2]}, mi.rec_base, mi.tri_base, mi.root, i};
     }
     RTGO_HIP(c, top.inst.upload(walk.data(), walk.size(), c->stream));
@@ -236,6 +243,12 @@ static int whitted_make_top(rtgo_ctx* c, const WhittedMesh& wm, const std::vecto
     top.n_recs = top.meta.n_recs;
     top.n_instances = n;
     return RTGO_OK;
+}
+
+static int whitted_make_top(rtgo_ctx* c, const WhittedMesh& wm, const std::vector<whitted::InstShade>& shade, const std::vector<float>& box_pos,
+                            const rtgo_whitted_instance* inst, const char* what, WhittedTop& top, int& depth)
+{
+    return whitted_make_top_over(c, wm.meshes, wm.mesh_depth, shade, box_pos, inst, what, top, depth);
 }
 
 // ... and that top level in wm's place
@@ -258,49 +271,191 @@ static int whitted_build_top(rtgo_ctx* c, WhittedMesh& wm, const std::vector<whi
     return RTGO_OK;
 }
 
-// Device scratch of the clustered builds of one rtgo_whitted_set_scene, sized for its largest clustered mesh (whitted_build_meshes)
+// Device scratch of one clustered mesh's build, alive from its sort to its mid level (28 B per triangle: the sorted keys and the
+// gathered index triples are what its clusters' builds and big_remap_kernel read)
 struct WhittedBigScratch {
     DeviceArray<unsigned long long> keys, keys_alt;
     DeviceArray<unsigned int> hist, cidx;
     DeviceArray<float> partial, bounds, boxes;
     DeviceArray<int> crec;
+    const unsigned long long* sorted = nullptr;   // keys or keys_alt, whichever the last radix pass wrote
 };
+
+// What the builds of a clustered mesh's clusters reported: where each cluster's records start, its root link, the deepest cluster walk
+struct WhittedClusterBuilds {
+    std::vector<int> crec, croot;
+    int cdepth = 0;
+    void add(int rec, int nc, const WhittedBuildMeta& m)
+    {
+        crec.push_back(rec);
+        croot.push_back(m.n_recs > 0 ? 0 : -1 - ((nc - 1) << whitted::kLeafShift));   // (nc >= kClusterTris / 2: always records)
+        cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
+    }
+};
+
+// ---- batched builds -------------------------------------------------------------------------------------------------------------------
+// The structures of one call (rtgo_whitted_set_scene: every mesh; rtgo_whitted_rebuild_meshes: the named ones) as one table: all
+// clusters of its clustered meshes and its small meshes, built by whitted_run_batch; then what each build reported, entry for entry
+struct WhittedBatch {
+    std::vector<whitted::BuildEntry> entries;
+    std::vector<WhittedBuildMeta> metas;
+    std::vector<int> rec0;   // where each entry's records start in the scene's arrays
+    int max_n = 0;
+    // rec_start >= 0: the first structure of its mesh, its records start there; < 0: they follow the entry before
+    void add(const float* positions, const unsigned int* indices, int n, const WhittedBuildTarget& t, int rec_start)
+    {
+        entries.push_back({positions, indices, t.tris, t.qrecs, t.tidx, n, whitted_sah_applies(n) ? 1 : 0, rec_start, 0});
+        max_n = std::max(max_n, n);
+    }
+};
+
+// whitted_build over every entry of the table, in rounds of at most kBatchRound structures (one workgroup each): the Morton builds, the
+// surface-area passes, the Morton builds again where that tree came out too deep, the records' places, the records packed into
+// `recs` (the scene's) -- five launches a round, whatever the table holds, and one wait at the end.  Scratch: 280 B per triangle of a
+// round (nodes, work arrays, record staging) = min(entries, kBatchRound) x the largest entry, at most 587 MB (256 x 8192 triangles).
+static int whitted_run_batch(rtgo_ctx* c, WhittedBatch& b, float4* recs, const char* what)
+{
+    using namespace whitted;
+    const int ne = (int)b.entries.size();
+    if (ne == 0) return RTGO_OK;
+    const int round = std::min(ne, kBatchRound);
+    const size_t max_n = (size_t)b.max_n;
+    DeviceArray<BuildEntry> d_table;
+    DeviceArray<WhittedBuildMeta> d_metas;
+    DeviceArray<int> d_rec0;   // [ne], then big_batch_offsets_kernel's carry
+    DeviceArray<float4> d_nodes, d_stage;
+    DeviceArray<int> d_ints;
+    RTGO_HIP(c, d_table.upload(b.entries.data(), b.entries.size(), c->stream));
+    RTGO_HIP(c, d_metas.alloc(ne));
+    RTGO_HIP(c, d_rec0.alloc((size_t)ne + 1));
+    RTGO_HIP(c, d_nodes.alloc((size_t)round * 2 * (2 * max_n - 1)));
+    RTGO_HIP(c, d_ints.alloc((size_t)round * build_scratch_ints(max_n)));
+    RTGO_HIP(c, d_stage.alloc((size_t)round * 4 * max_n));
+    RTGO_HIP(c, hipMemsetAsync(d_rec0.get() + ne, 0, sizeof(int), c->stream));
+    const BatchSlots slots = {d_nodes.get(), d_ints.get(), d_stage.get(), b.max_n};
+    const size_t keys_lds = (size_t)kMaxTriangles * sizeof(unsigned long long);
+    for (int first = 0; first < ne; first += round) {
+        const int count = std::min(round, ne - first);
+        size_t sah_lds = 0;   // of the round's largest entry that takes the pass
+        for (int k = first; k < first + count; ++k)
+            if (b.entries[k].sah) sah_lds = std::max(sah_lds, whitted_sah_lds(b.entries[k].n));
+        hipLaunchKernelGGL(big_build_batch_kernel, dim3(count), dim3(kBuildThreads), keys_lds, c->stream, (const BuildEntry*)d_table.get(), first, slots,
+                           d_metas.get(), 0);
+        if (sah_lds > 0) {
+            hipLaunchKernelGGL(big_sah_batch_kernel, dim3(count), dim3(kBuildThreads), sah_lds, c->stream, (const BuildEntry*)d_table.get(), first, slots,
+                               d_metas.get());
+            hipLaunchKernelGGL(big_build_batch_kernel, dim3(count), dim3(kBuildThreads), keys_lds, c->stream, (const BuildEntry*)d_table.get(), first, slots,
+                               d_metas.get(), 1);
+        }
+        hipLaunchKernelGGL(big_batch_offsets_kernel, dim3(1), dim3(kBatchRound), 0, c->stream, (const BuildEntry*)d_table.get(), first, count,
+                           (const WhittedBuildMeta*)d_metas.get(), d_rec0.get(), d_rec0.get() + ne);
+        hipLaunchKernelGGL(big_pack_records_kernel, dim3(count), dim3(256), 0, c->stream, first, slots, (const WhittedBuildMeta*)d_metas.get(),
+                           (const int*)d_rec0.get(), recs);
+        RTGO_HIP(c, hipGetLastError());
+    }
+    b.metas.assign(ne, WhittedBuildMeta{});
+    b.rec0.assign(ne, 0);
+    RTGO_HIP(c, hipMemcpyAsync(b.metas.data(), d_metas.get(), ne * sizeof(WhittedBuildMeta), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(b.rec0.data(), d_rec0.get(), ne * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    for (const WhittedBuildMeta& m : b.metas) {   // (whitted_build's refusals)
+        if (m.depth > 2 * kStack)
+            return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": triangle LBVH depth " + std::to_string(m.depth) + " exceeds what the build handles (" +
+                                                   std::to_string(2 * kStack) + ")");
+        if (m.walk_depth > kMaxWalkDepth)
+            return fail(c, RTGO_E_UNSUPPORTED, std::string(what) + ": the walk needs " + std::to_string(m.walk_depth) + " stack entries (limit " +
+                                                   std::to_string(kMaxWalkDepth) + ")");
+    }
+    return RTGO_OK;
+}
 
 // One clustered mesh (n > kMaxTriangles triangles; rtgo_whitted_big.h), in its slices of wm's arrays: Morton order over the
 // whole mesh on the device, clusters of consecutive sorted triangles each built by whitted_build (tris[].w then remapped to the mesh's
 // own indices), and a mid level over the clusters' boxes whose records take the first ncl - 1 record slots of the mesh (the clusters
 // follow: a mesh of n triangles has at most n slots, and a cluster of m triangles fewer than m records).  Appends the mesh's clusters,
 // in the mid level's leaf order, to `table`; sets mi.root, mi.depth, and widens mi.lo / hi over every box the walk can reach from the
-// mesh's root, so the instance boxes built from it contain them by construction.  Synchronous.
-static int whitted_build_clustered(rtgo_ctx* c, const WhittedMesh& wm, WhittedMeshInfo& mi, int n, WhittedBigScratch& bs, const WhittedBuildScratch& scratch,
-                                   std::vector<int4>& table, const char* what)
+// mesh's root, so the instance boxes built from it contain them by construction.  Three steps: the sort (whitted_sort_clustered,
+// enqueued), the clusters' builds (whitted_add_clusters + whitted_run_batch with the call's other structures, or
+// whitted_build_clusters_sequential), the rest (whitted_finish_clustered, synchronous).
+static int whitted_sort_clustered(rtgo_ctx* c, const WhittedMesh& wm, const WhittedMeshInfo& mi, WhittedBigScratch& bs)
 {
     using namespace whitted;
-    const int ncl = (n + kClusterTris - 1) / kClusterTris;
+    const int n = mi.n_tris, ncl = (n + kClusterTris - 1) / kClusterTris, nb = (n + kRadixTile - 1) / kRadixTile;
     const float* positions = wm.positions.get() + 3 * (size_t)mi.vert_base;
     const unsigned int* indices = wm.indices.get() + 3 * (size_t)mi.tri_base;
-    const WhittedBuildTarget mesh = whitted_target(wm, mi.rec_base, mi.tri_base);
+    RTGO_HIP(c, bs.keys.alloc(n));
+    RTGO_HIP(c, bs.keys_alt.alloc(n));
+    RTGO_HIP(c, bs.hist.alloc((size_t)256 * nb));
+    RTGO_HIP(c, bs.cidx.alloc((size_t)3 * n));
+    RTGO_HIP(c, bs.partial.alloc((size_t)6 * 1024));
+    RTGO_HIP(c, bs.bounds.alloc(6));
+    RTGO_HIP(c, bs.crec.alloc(ncl));
+    RTGO_HIP(c, bs.boxes.alloc((size_t)6 * ncl));
     // Morton keys over the mesh's bounds, sorted by four stable passes over the code's bytes
     const int nbb = std::min(1024, (n + 1023) / 1024);
     hipLaunchKernelGGL(big_bounds_kernel, dim3(nbb), dim3(1024), 0, c->stream, positions, indices, n, bs.partial.get());
     hipLaunchKernelGGL(big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)bs.partial.get(), nbb, bs.bounds.get());
     hipLaunchKernelGGL(big_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, positions, indices, n, (const float*)bs.bounds.get(), bs.keys.get());
-    const unsigned long long* sorted = radix_sort_keys(c, bs.keys.get(), bs.keys_alt.get(), bs.hist.get(), n);
-    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, sorted, n, indices, bs.cidx.get());
+    bs.sorted = radix_sort_keys(c, bs.keys.get(), bs.keys_alt.get(), bs.hist.get(), n);
+    hipLaunchKernelGGL(big_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, bs.sorted, n, indices, bs.cidx.get());
     RTGO_HIP(c, hipGetLastError());
-    // the clusters
-    std::vector<int> crec(ncl), croot(ncl);
-    int rec = mi.rec_base + ncl - 1, cdepth = 0;
+    return RTGO_OK;
+}
+
+// the clusters of a sorted mesh as entries of a call's table ...
+static void whitted_add_clusters(const WhittedMesh& wm, const WhittedMeshInfo& mi, const WhittedBigScratch& bs, WhittedBatch& batch)
+{
+    using namespace whitted;
+    const int n = mi.n_tris, ncl = (n + kClusterTris - 1) / kClusterTris;
+    for (int k = 0; k < ncl; ++k) {
+        const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
+        batch.add(wm.positions.get() + 3 * (size_t)mi.vert_base, bs.cidx.get() + 3 * (size_t)s, nc, whitted_target(wm, 0, mi.tri_base + s),
+                  k == 0 ? mi.rec_base + ncl - 1 : -1);
+    }
+}
+
+// ... and what the table's entries first .. first + ncl - 1 report of them
+static void whitted_take_clusters(WhittedMeshInfo& mi, const WhittedBatch& batch, int first, WhittedClusterBuilds& cb)
+{
+    using namespace whitted;
+    const int n = mi.n_tris, ncl = (n + kClusterTris - 1) / kClusterTris;
+    for (int k = 0; k < ncl; ++k) {
+        const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
+        const WhittedBuildMeta& m = batch.metas[first + k];
+        mi.built.push_back({batch.rec0[first + k], m.n_recs, mi.tri_base + s, m});
+        cb.add(batch.rec0[first + k], nc, m);
+    }
+}
+
+// The clusters one after another, a host wait after each (RTGO_WHITTED_SEQ_BUILD)
+static int whitted_build_clusters_sequential(rtgo_ctx* c, const WhittedMesh& wm, WhittedMeshInfo& mi, const WhittedBigScratch& bs, const WhittedBuildScratch& scratch,
+                                             WhittedClusterBuilds& cb, const char* what)
+{
+    using namespace whitted;
+    const int n = mi.n_tris, ncl = (n + kClusterTris - 1) / kClusterTris;
+    const float* positions = wm.positions.get() + 3 * (size_t)mi.vert_base;
+    int rec = mi.rec_base + ncl - 1;
     for (int k = 0; k < ncl; ++k) {
         const int s = cluster_start(n, ncl, k), nc = cluster_start(n, ncl, k + 1) - s;
         WhittedBuildMeta m;
         if (const int rc = whitted_build(c, positions, bs.cidx.get() + 3 * (size_t)s, nc, whitted_target(wm, rec, mi.tri_base + s), scratch, m, what)) return rc;
         mi.built.push_back({rec, m.n_recs, mi.tri_base + s, m});
-        crec[k] = rec;
-        croot[k] = m.n_recs > 0 ? 0 : -1 - ((nc - 1) << kLeafShift);   // (nc >= kClusterTris / 2: always records)
-        cdepth = std::max(cdepth, m.n_recs > 0 ? m.walk_depth : 0);
+        cb.add(rec, nc, m);
         rec += m.n_recs;
     }
+    return RTGO_OK;
+}
+
+// The clusters built: the mesh's own triangle numbers, the mid level, the mesh's clusters at table[tbase ..], root, depth and box
+static int whitted_finish_clustered(rtgo_ctx* c, const WhittedMesh& wm, WhittedMeshInfo& mi, WhittedBigScratch& bs, const WhittedClusterBuilds& cb,
+                                    std::vector<int4>& table, int tbase, const char* what)
+{
+    using namespace whitted;
+    const int n = mi.n_tris, ncl = (n + kClusterTris - 1) / kClusterTris;
+    const WhittedBuildTarget mesh = whitted_target(wm, mi.rec_base, mi.tri_base);
+    const unsigned long long* sorted = bs.sorted;
+    const std::vector<int>&crec = cb.crec, &croot = cb.croot;
+    const int cdepth = cb.cdepth;
     hipLaunchKernelGGL(big_remap_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, mesh.tris, sorted, n, ncl);
     RTGO_HIP(c, hipGetLastError());
     // the mid level over the clusters' boxes
@@ -318,8 +473,11 @@ static int whitted_build_clustered(rtgo_ctx* c, const WhittedMesh& wm, WhittedMe
     RTGO_HIP(c, hipMemcpyAsync(boxes.data(), bs.boxes.get(), boxes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (m.n_recs > 0) RTGO_HIP(c, hipMemcpyAsync(root_rec.data(), mesh.recs, 4 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    const int tbase = (int)table.size();
-    for (const int k : order) table.push_back(make_int4(crec[k], mi.tri_base + cluster_start(n, ncl, k), croot[k], 0));
+    if (table.size() < (size_t)tbase + ncl) table.resize((size_t)tbase + ncl);
+    for (int pos = 0; pos < ncl; ++pos) {
+        const int k = order[pos];
+        table[(size_t)tbase + pos] = make_int4(crec[k], mi.tri_base + cluster_start(n, ncl, k), croot[k], 0);
+    }
     // what the walk can reach first below an instance: the mid root's two child boxes, or (a mid level of one leaf) the clusters' root
     // records, whose boxes are the ones big_cluster_boxes_kernel took
     auto widen = [&](const float* l, const float* h) {
@@ -445,38 +603,85 @@ static int whitted_upload_meshes(rtgo_ctx* c, WhittedMesh& wm, const WhittedLayo
     return RTGO_OK;
 }
 
+// The structures of the meshes `which` of info (laid out in wm's arrays, their vertices and indices on the device), each in its slice: a
+// small mesh's one build, a clustered mesh's clusters and mid level.  Every build of the call goes through one table (whitted_run_batch),
+// or with RTGO_WHITTED_SEQ_BUILD one after another -- the same arrays either way.  A mesh that was built before (built not empty: a
+// rebuild) keeps its place in `table`, a new one is appended; built, mid_order, root and depth are set, a clustered mesh's box is widened
+// (box_from_device: first taken from the triangle bounds its sort found, for a caller that has no indices on the host).  Synchronous.
+static int whitted_build_structures(rtgo_ctx* c, const WhittedMesh& wm, std::vector<WhittedMeshInfo>& info, const std::vector<int>& which,
+                                    std::vector<int4>& table, bool box_from_device, const char* what)
+{
+    using namespace whitted;
+    const bool sequential = whitted_sequential_builds();
+    const size_t nw = which.size();
+    std::vector<WhittedBigScratch> big(nw);
+    std::vector<float> bounds(6 * nw, 0.0f);
+    std::vector<int> tbase(nw, -1), first(nw, 0);
+    WhittedBatch batch;
+    int next_tbase = (int)table.size(), max_tri = 1;
+    for (size_t i = 0; i < nw; ++i) {
+        WhittedMeshInfo& mi = info[which[i]];
+        const int ncl = (mi.n_tris + kClusterTris - 1) / kClusterTris;
+        if (mi.clustered) {
+            tbase[i] = mi.built.empty() ? next_tbase : (mi.root - 1) >> 3;
+            if (mi.built.empty()) next_tbase += ncl;
+        }
+        mi.built.clear();
+        mi.mid_order.clear();
+        first[i] = (int)batch.entries.size();
+        max_tri = std::max(max_tri, mi.clustered ? std::max(kClusterTris, ncl) : mi.n_tris);
+        if (mi.clustered) {
+            if (const int rc = whitted_sort_clustered(c, wm, mi, big[i])) return rc;
+            if (box_from_device) RTGO_HIP(c, hipMemcpyAsync(&bounds[6 * i], big[i].bounds.get(), 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            if (!sequential) whitted_add_clusters(wm, mi, big[i], batch);
+        } else if (!sequential) {
+            batch.add(wm.positions.get() + 3 * (size_t)mi.vert_base, wm.indices.get() + 3 * (size_t)mi.tri_base, mi.n_tris, whitted_target(wm, 0, mi.tri_base),
+                      mi.rec_base);
+        }
+    }
+    WhittedBuildScratch scratch;
+    if (sequential) {
+        RTGO_HIP(c, scratch.alloc(max_tri));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    } else if (const int rc = whitted_run_batch(c, batch, wm.recs.get(), what)) {
+        return rc;
+    }
+    for (size_t i = 0; i < nw; ++i) {
+        WhittedMeshInfo& mi = info[which[i]];
+        if (mi.clustered) {
+            WhittedClusterBuilds cb;
+            if (sequential) {
+                if (const int rc = whitted_build_clusters_sequential(c, wm, mi, big[i], scratch, cb, what)) return rc;
+            } else {
+                whitted_take_clusters(mi, batch, first[i], cb);
+            }
+            if (box_from_device) whitted_pad_mesh_box(&bounds[6 * i], &bounds[6 * i + 3], mi.lo, mi.hi);
+            if (const int rc = whitted_finish_clustered(c, wm, mi, big[i], cb, table, tbase[i], what)) return rc;
+        } else {
+            WhittedBuildMeta m;
+            if (sequential) {
+                if (const int rc = whitted_build(c, wm.positions.get() + 3 * (size_t)mi.vert_base, wm.indices.get() + 3 * (size_t)mi.tri_base, mi.n_tris,
+                                                 whitted_target(wm, mi.rec_base, mi.tri_base), scratch, m, what))
+                    return rc;
+            } else {
+                m = batch.metas[first[i]];
+            }
+            mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base, m});
+            mi.root = m.n_recs > 0 ? 0 : -1 - ((mi.n_tris - 1) << kLeafShift);
+            mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
+        }
+    }
+    return RTGO_OK;
+}
+
 // Stage 3, the bottom level: each mesh's own structure in its slice of the arrays (a clustered mesh: its clusters and mid level), then the table
 static int whitted_build_meshes(rtgo_ctx* c, WhittedMesh& wm, WhittedLayout& lay, const char* what)
 {
-    WhittedBuildScratch scratch;
-    WhittedBigScratch bs;
-    RTGO_HIP(c, scratch.alloc(lay.max_tri));
-    if (lay.max_big > 0) {
-        const int n = lay.max_big, ncl = (n + whitted::kClusterTris - 1) / whitted::kClusterTris, nb = (n + whitted::kRadixTile - 1) / whitted::kRadixTile;
-        RTGO_HIP(c, bs.keys.alloc(n));
-        RTGO_HIP(c, bs.keys_alt.alloc(n));
-        RTGO_HIP(c, bs.hist.alloc((size_t)256 * nb));
-        RTGO_HIP(c, bs.cidx.alloc((size_t)3 * n));
-        RTGO_HIP(c, bs.partial.alloc((size_t)6 * 1024));
-        RTGO_HIP(c, bs.bounds.alloc(6));
-        RTGO_HIP(c, bs.crec.alloc(ncl));
-        RTGO_HIP(c, bs.boxes.alloc((size_t)6 * ncl));
-    }
+    std::vector<int> all(lay.info.size());
+    for (size_t k = 0; k < all.size(); ++k) all[k] = (int)k;
     std::vector<int4> table;
-    for (WhittedMeshInfo& mi : lay.info) {
-        if (mi.clustered) {
-            if (const int rc = whitted_build_clustered(c, wm, mi, mi.n_tris, bs, scratch, table, what)) return rc;
-        } else {
-            WhittedBuildMeta m;
-            if (const int rc = whitted_build(c, wm.positions.get() + 3 * (size_t)mi.vert_base, wm.indices.get() + 3 * (size_t)mi.tri_base, mi.n_tris,
-                                             whitted_target(wm, mi.rec_base, mi.tri_base), scratch, m, what))
-                return rc;
-            mi.built.push_back({mi.rec_base, m.n_recs, mi.tri_base, m});
-            mi.root = m.n_recs > 0 ? 0 : -1 - ((mi.n_tris - 1) << whitted::kLeafShift);
-            mi.depth = m.n_recs > 0 ? m.walk_depth : 0;
-        }
-        wm.mesh_depth = std::max(wm.mesh_depth, mi.depth);
-    }
+    if (const int rc = whitted_build_structures(c, wm, lay.info, all, table, false, what)) return rc;
+    for (const WhittedMeshInfo& mi : lay.info) wm.mesh_depth = std::max(wm.mesh_depth, mi.depth);
     if (!table.empty()) RTGO_HIP(c, wm.clusters.upload(table.data(), table.size(), c->stream));
     wm.meshes = lay.info;
     return RTGO_OK;
@@ -644,7 +849,7 @@ static int whitted_enqueue_clustered_refit(rtgo_ctx* c, WhittedMesh& wm, const W
     return RTGO_OK;
 }
 
-// ... and once the stream has drained: the mesh's box as whitted_build_clustered takes it, and the grids its builds now report
+// ... and once the stream has drained: the mesh's box as whitted_finish_clustered takes it, and the grids its builds now report
 static void whitted_finish_clustered_refit(WhittedMeshInfo& mi, const WhittedClusteredRefit& r)
 {
     const int ncl = r.ncl;
@@ -685,20 +890,10 @@ static int whitted_restore_clustered(rtgo_ctx* c, WhittedMesh& wm, const Whitted
     return RTGO_OK;
 }
 
-// rtgo_whitted_update_meshes once the scene is known to exist: rtgo_whitted_update_mesh for every entry as one transaction.  Stages:
-// 1 every check the host can make; 2 every mesh's new box (a small mesh: from its indices read back, all in one wait; a clustered mesh:
-// refitted in place with its slices saved, its box from what the device reports); 3 the instances laid out and the top level built, once,
-// aside; 4 the small meshes' refits; 5 what the host keeps.  A refusal in stage 3 puts the clustered meshes' slices back: nothing else
-// has changed by then.
-static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+// The checks rtgo_whitted_update_meshes and rtgo_whitted_rebuild_meshes make of their entries on the host (w: the call, for the messages)
+static int whitted_check_updates(rtgo_ctx* c, const WhittedMesh& wm, const std::string& w, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
 {
-    const char* what = "rtgo_whitted_update_meshes";
-    const std::string w(what);
-    WhittedMesh& wm = c->wm;
-    if (n_updates == 0) return RTGO_OK;
-    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
     const size_t n_meshes = wm.instanced ? wm.meshes.size() : (size_t)1;
-    // stage 1
     std::vector<char> named(n_meshes, 0);
     for (uint32_t k = 0; k < n_updates; ++k) {
         const rtgo_whitted_mesh_update& u = updates[k];
@@ -714,6 +909,23 @@ static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* up
         for (size_t i = 0; i < (size_t)3 * u.n_vertices; ++i)
             if (!std::isfinite(u.positions[i]) || (u.normals && !std::isfinite(u.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
     }
+    return RTGO_OK;
+}
+
+// rtgo_whitted_update_meshes once the scene is known to exist: rtgo_whitted_update_mesh for every entry as one transaction.  Stages:
+// 1 every check the host can make; 2 every mesh's new box (a small mesh: from its indices read back, all in one wait; a clustered mesh:
+// refitted in place with its slices saved, its box from what the device reports); 3 the instances laid out and the top level built, once,
+// aside; 4 the small meshes' refits; 5 what the host keeps.  A refusal in stage 3 puts the clustered meshes' slices back: nothing else
+// has changed by then.
+static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    const char* what = "rtgo_whitted_update_meshes";
+    const std::string w(what);
+    WhittedMesh& wm = c->wm;
+    if (n_updates == 0) return RTGO_OK;
+    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
+    // stage 1
+    if (const int rc = whitted_check_updates(c, wm, w, updates, n_updates)) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     if (!wm.instanced) {
@@ -771,6 +983,120 @@ static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* up
     }
     // stage 5
     wm.meshes = std::move(meshes);
+    whitted_install_top(wm, std::move(top), depth);
+    return RTGO_OK;
+}
+
+// ---- rebuild (rtgo_whitted_rebuild_meshes) --------------------------------------------------------------------------------------------
+// What a rebuild replaces of one named mesh in wm's arrays, kept on the device until the call is known to succeed: the mesh's depth and
+// box are known only after its build, so a refusal can follow it.  (WhittedClusteredRefit's scheme plus tidx: a build writes it too.)
+struct WhittedRebuildSave {
+    DeviceArray<float> positions, normals;
+    DeviceArray<float4> recs, tris;
+    DeviceArray<uint4> qrecs;
+    DeviceArray<uint2> tidx;
+};
+
+// rtgo_whitted_rebuild_meshes once the scene is known to exist: the named meshes built again over new vertices, as rtgo_whitted_set_scene
+// (rtgo_whitted_set_mesh) builds them, in place; everything else of the scene stays.  Stages: 1 every check the host can make; 2 the
+// named meshes' slices saved, the new vertices up; 3 their structures, all through one table (whitted_build_structures), the cluster
+// table aside; 4 the instances laid out over the new boxes and the top level built, aside; 5 what the host keeps.  A refusal in stage 3
+// or 4 puts the slices back: nothing else has changed by then.
+static int whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    const char* what = "rtgo_whitted_rebuild_meshes";
+    const std::string w(what);
+    WhittedMesh& wm = c->wm;
+    if (n_updates == 0) return RTGO_OK;
+    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
+    // stage 1
+    if (const int rc = whitted_check_updates(c, wm, w, updates, n_updates)) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<WhittedMeshInfo> meshes = wm.meshes;
+    if (!wm.instanced) {   // a scene of rtgo_whitted_set_mesh: its one mesh, at the start of every array
+        WhittedMeshInfo mi = WhittedMeshInfo();
+        mi.n_tris = wm.triangles;
+        mi.n_verts = wm.n_vertices;
+        mi.flags = wm.normals.get() ? whitted::kHasNormals : 0;
+        meshes.assign(1, mi);
+    }
+    // stage 2
+    std::vector<WhittedRebuildSave> saved(n_updates);
+    std::vector<std::vector<uint32_t>> idx(n_updates);
+    std::vector<int> which;
+    std::vector<int4> table(wm.clusters.size());
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        const rtgo_whitted_mesh_update& u = updates[k];
+        const WhittedMeshInfo& mi = meshes[u.mesh];
+        const size_t n = (size_t)mi.n_tris, nv3 = (size_t)mi.n_verts * 3;
+        float* d_pos = wm.positions.get() + 3 * (size_t)mi.vert_base;
+        float* d_nrm = wm.normals.get() + 3 * (size_t)mi.vert_base;
+        const WhittedBuildTarget t = whitted_target(wm, mi.rec_base, mi.tri_base);   // (a mesh of n triangles owns n record slots)
+        WhittedRebuildSave& s = saved[k];
+        auto save = [&](auto& keep, const auto* src, size_t count) -> hipError_t {
+            const hipError_t e = keep.alloc(count);
+            return e != hipSuccess ? e : hipMemcpyAsync(keep.get(), src, count * sizeof *src, hipMemcpyDeviceToDevice, c->stream);
+        };
+        RTGO_HIP(c, save(s.positions, d_pos, nv3));
+        if (u.normals) RTGO_HIP(c, save(s.normals, d_nrm, nv3));
+        RTGO_HIP(c, save(s.recs, t.recs, 4 * n));
+        RTGO_HIP(c, save(s.tris, t.tris, 3 * n));
+        RTGO_HIP(c, save(s.qrecs, t.qrecs, 2 * n));
+        RTGO_HIP(c, save(s.tidx, t.tidx, n));
+        RTGO_HIP(c, hipMemcpyAsync(d_pos, u.positions, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (u.normals) RTGO_HIP(c, hipMemcpyAsync(d_nrm, u.normals, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (wm.instanced && !mi.clustered) {   // its new box needs its indices, which are on the device only
+            idx[k].resize(3 * n);
+            RTGO_HIP(c, hipMemcpyAsync(idx[k].data(), wm.indices.get() + 3 * (size_t)mi.tri_base, idx[k].size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+        which.push_back((int)u.mesh);
+    }
+    if (!table.empty()) RTGO_HIP(c, hipMemcpyAsync(table.data(), wm.clusters.get(), table.size() * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        WhittedMeshInfo& mi = meshes[updates[k].mesh];
+        if (wm.instanced && !mi.clustered) whitted_mesh_box(updates[k].positions, idx[k].data(), (uint32_t)mi.n_tris, mi.lo, mi.hi);
+    }
+    auto refused = [&](int rc) -> int {   // the named meshes' slices as they were
+        for (uint32_t k = 0; k < n_updates; ++k) {
+            const WhittedMeshInfo& mi = wm.instanced ? wm.meshes[updates[k].mesh] : meshes[0];
+            const WhittedBuildTarget t = whitted_target(wm, mi.rec_base, mi.tri_base);
+            const WhittedRebuildSave& s = saved[k];
+            auto back = [&](auto* dst, const auto& keep) { return hipMemcpyAsync(dst, keep.get(), keep.size() * sizeof *dst, hipMemcpyDeviceToDevice, c->stream); };
+            RTGO_HIP(c, back(wm.positions.get() + 3 * (size_t)mi.vert_base, s.positions));
+            if (s.normals.get()) RTGO_HIP(c, back(wm.normals.get() + 3 * (size_t)mi.vert_base, s.normals));
+            RTGO_HIP(c, back(t.recs, s.recs));
+            RTGO_HIP(c, back(t.tris, s.tris));
+            RTGO_HIP(c, back(t.qrecs, s.qrecs));
+            RTGO_HIP(c, back(t.tidx, s.tidx));
+        }
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        return rc;
+    };
+    // stage 3
+    if (const int rc = whitted_build_structures(c, wm, meshes, which, table, true, what)) return refused(rc);
+    if (!wm.instanced) {
+        wm.meta = meshes[0].built[0].meta;
+        wm.walk_depth = wm.meta.walk_depth < 1 ? 1 : wm.meta.walk_depth;
+        return RTGO_OK;
+    }
+    DeviceArray<int4> clusters;
+    if (!table.empty()) RTGO_HIP(c, clusters.upload(table.data(), table.size(), c->stream));
+    // stage 4
+    int mesh_depth = 0;
+    for (const WhittedMeshInfo& mi : meshes) mesh_depth = std::max(mesh_depth, mi.depth);
+    std::vector<whitted::InstShade> shade;
+    std::vector<float> box_pos;
+    WhittedTop top;
+    int depth = 0;
+    int rc = whitted_prepare_instances(c, meshes, (uint32_t)wm.n_materials, wm.instances.data(), (uint32_t)wm.instances.size(), shade, box_pos, what);
+    if (!rc) rc = whitted_make_top_over(c, meshes, mesh_depth, shade, box_pos, wm.instances.data(), what, top, depth);
+    if (rc) return refused(rc);
+    // stage 5
+    wm.meshes = std::move(meshes);
+    wm.mesh_depth = mesh_depth;
+    if (!table.empty()) wm.clusters = std::move(clusters);
     whitted_install_top(wm, std::move(top), depth);
     return RTGO_OK;
 }
