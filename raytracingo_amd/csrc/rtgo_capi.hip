@@ -731,7 +731,8 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
     t.n_fnodes = meta.n_fnodes;
     // fast_pair's shape: three nodes, the root's links 1 and 2, both of them leaves certified as cuboids, the root's box the union of theirs
     t.pair = false;
-    if (meta.n_small > 0 && meta.n_fnodes == 3 && meta.cuboid_leaves == 2) {
+    // (the pair kernels take the two counts as compile-time values: kPairNodes, kPairSmall)
+    if (meta.n_small == kPairSmall && meta.n_fnodes == kPairNodes && meta.cuboid_leaves == 2) {
         float4 nd[6];
         RTGO_HIP(c, hipMemcpyAsync(nd, t.d_fnodes.get(), sizeof nd, hipMemcpyDeviceToHost, c->stream));
         RTGO_HIP(c, hipStreamSynchronize(c->stream));
@@ -1285,6 +1286,16 @@ static void last_ray_params(const rtgo_ctx* c, const AnalyticScene::FastTree& ft
     p.emit_n = ft.emit_n;
 }
 
+// A launch that takes a pair kernel: the three words a ray of those kernels reads before its walk (PairWords), from the fields walk_params
+// and last_ray_params have set.  They lie in the grid's space (a pair launch walks no grid), so this is the last write to that space:
+// call it once the kernel is chosen, and write p.grid no more after it.
+static void pair_words(LaunchParams& p)
+{
+    p.pair.cub_mu = p.cub_mu;
+    p.pair.n_prims = p.n_prims;
+    p.pair.last_depth = p.emit_n != 0 ? p.max_depth : -1;
+}
+
 // Scheduling: units of 64 paths = the N*N samples of `unit_px` neighbouring pixels of one row; the queue hands out STRIPS of
 // `grab` units side by side (<= 64 pixels) from the rectangle that can contain geometry.  Strips are long when there is
 // plenty of work (their pixel seeds are hashed once per strip) and short when units are scarce (small windows, one GPU's
@@ -1603,14 +1614,17 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     const bool frames = path && !canon && c->scene.quadrics.empty() && !kn.no_frames;   // scenes of flat primitives only: N and the sampling tangent from LDS
     // The straight-line walk of a two-leaf tree (render_pair_kernel, fast_pair): path mode over a flat scene with frames, the lock-step loop,
     // one frame per launch, inside the far-field guard, over a tree (not the grid) that is a root over two certified cuboid leaves, the
-    // cuboid margin still positive at this launch's reach -- and a variant at the waves per SIMD pick_block chose (5, 6 and, as
+    // cuboid margin still positive at this launch's reach, an up-front list that starts with a certified room (the kind of cuboid the pair
+    // kernels' list test is compiled for: fast_list's KIND) -- and a variant at the waves per SIMD pick_block chose (5, 6 and, as
     // render_pair7_kernel, 7).  RTGO_NO_PAIR: off.
-    const bool pair_ok = path && !canon && !pk.stream && frames && !use_grid && !batch && !kn.no_pair && c->scene.tree[use_alt ? 1 : 0].pair && p.cub_mu > 0.0f;
+    const bool pair_ok = path && !canon && !pk.stream && frames && !use_grid && !batch && !kn.no_pair && c->scene.tree[use_alt ? 1 : 0].pair && p.cub_mu > 0.0f &&
+                         p.list_cub == 2;
     Block b;
     if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b, false, batch, pair_ok)) return rc;
     const RenderKernel pair_kernel = pair_ok ? find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch, true) : nullptr;
     const RenderKernel kernel = pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch);
     if (pair_kernel) p.stack_depth = 0;   // (fast_pair has no stack: pick_block reserved none, and the lights follow the scene directly)
+    if (pair_kernel) pair_words(p);
     const bool pair7 = pair_kernel && b.wpe == 7;
     if (kn.debug) {
         char kname[48];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)

@@ -27,6 +27,10 @@ constexpr int kCamWords = 16;        // raygen constants in LDS (render_kernel's
 constexpr int kCamWordsLean = 20;    // ... + the launch's two reciprocals in the 6-waves variant (a multiple of 4: s_tab follows)
 constexpr int kMaxLevels = 5;        // bounce records kept per path (maxTraceDepth <= 5)
 constexpr int kMaxEmitters = 4;      // emitters of the last-ray certificate (LaunchParams::emit_n); scenes with more go without it
+// the pair kernels' scene (fast_pair: a root over two cuboid leaves of six records each), which their launches vouch for: the tree's
+// nodes and its records.  Compile-time values there, so that the up-front list -- the records from kPairSmall on, in LDS and in global
+// memory -- sits at constant offsets instead of at offsets every ray derives from LaunchParams::n_fnodes and n_small
+constexpr int kPairNodes = 3, kPairSmall = 12;
 constexpr float kPi = 3.14159265358979323846f;  // M_PIf, sutil/vec_math.h:43
 
 struct v3 {
@@ -66,6 +70,18 @@ __host__ __device__ constexpr int leaf_count(int link) { return (-link) & 0xFFF;
 __host__ __device__ constexpr int leaf_pairs(int link) { return ((-link) >> 12) & 0xFF; }
 __host__ __device__ constexpr int leaf_cuboid(int link) { return (-link) >> 20; }
 
+// The pair kernels' launches (render_pair_kernel, render_pair7_kernel): the three words each of their rays reads before its walk, side by
+// side, so that they arrive as a two-word and a one-word scalar load under one wait.  cub_mu and n_prims are LaunchParams' fields of
+// those names.  last_depth is the last-ray certificate as the one value the ray loop compares: the depth at which a ray is its path's
+// last (max_depth) when the launch has the certificate (emit_n != 0), -1 (no depth) when it has not -- the host decides once what every
+// ray would otherwise decide from two fields.  The other kernels read LaunchParams' own fields, as they did; the words lie where a GRID
+// launch has its grid, so that no field of LaunchParams moves and every other kernel compiles to the instructions it had.
+struct PairWords {
+    float cub_mu;
+    int last_depth;
+    int n_prims;
+};
+
 struct LaunchParams {
     const float4* nodes;            // canonical LBVH, 2 float4 per node
     const float4* prims;            // 6 float4 per primitive, SBT order
@@ -79,7 +95,10 @@ struct LaunchParams {
     int list_cub;                   // 1 / 2: the up-front list starts with three pairs certified as one box / one room (cuboid_range), 0: it does not
     float cub_mu;                   // cuboid_range's margin for this launch (object-space units of a face's y axis)
     int tree_spheres;              // 1: every primitive of the fast walk's tree is a sphere (balls): leaves go straight to the sphere test
-    GridParams grid;                // GRID instantiations: fnodes holds the grid instead of a tree
+    union {
+        GridParams grid;            // GRID instantiations: fnodes holds the grid instead of a tree
+        PairWords pair;             // the pair kernels' launches (they walk no grid): see PairWords
+    };
     const LightRec* lights;
     float4* accum;
     uchar4* image;
@@ -134,6 +153,10 @@ struct LaunchParams {
     // render_frames_kernel: this launch renders frames frame .. frame + n_frames - 1 (the other kernels render `frame` and do not read it)
     unsigned int n_frames;
 };
+// (PairWords lies inside the grid's space: no field after it moves, so every kernel but the pair kernels compiles as it did without it)
+static_assert(sizeof(PairWords) <= sizeof(GridParams) && alignof(PairWords) <= alignof(GridParams), "PairWords must fit the space of LaunchParams::grid");
+static_assert(offsetof(LaunchParams, pair) == offsetof(LaunchParams, grid) && offsetof(LaunchParams, lights) == offsetof(LaunchParams, grid) + sizeof(GridParams),
+              "LaunchParams: the pair words overlay the grid and the fields after it stay where they are");
 
 // ---- float3 helpers, same operation order as sutil/vec_math.h ----------------------------------------------------
 __device__ __forceinline__ v3 mk(float x, float y, float z) { return v3{x, y, z}; }
@@ -671,7 +694,12 @@ __device__ __forceinline__ void leaf_range(Ptr fp, const float4* __restrict__ ld
 // mu covers the certificate's tolerance and the rounding of the reference's u, v and of y_g (rtgo_capi.hip, cub_mu): a face the
 // reference accepts is never dropped, and a face that is not dropped gets the reference's whole test, so the closest hit is the same.
 // mu_out / mu_in: drop when y > mu_out or y < mu_in (box: (mu, -inf); room: (+inf, -mu)).
-template <bool LIST, typename Ptr>
+// KIND: what the certificate says the cuboid is, where the kernel knows it when it is compiled -- kCubBox (every leaf) compares against
+// mu_out alone, kCubRoom (the list of the pair kernels, whose launches vouch for a room) against mu_in alone: one comparison per pair of
+// faces, and the margins need not be built per ray.  kCubEither: the list of a kernel that serves both kinds of launch; the kind is in
+// the margins, one of which is infinite and never fires -- the same faces dropped, at two comparisons each.
+enum CubKind { kCubEither = 0, kCubBox = 1, kCubRoom = 2 };   // (= LaunchParams::list_cub's values)
+template <bool LIST, CubKind KIND, typename Ptr>
 __device__ __forceinline__ void cuboid_range(Ptr fp, const float4* __restrict__ lds, int first, float mu_out, float mu_in, v3 wo, v3 wd, float tmin, FastHit& best)
 {
     float t[3], dy[3];
@@ -706,7 +734,9 @@ __device__ __forceinline__ void cuboid_range(Ptr fp, const float4* __restrict__ 
         // y_g at the point where the ray meets f's plane: o.y_g + t_f d.y_g = d.y_g (t_f - t_g) up to 2^-24 of o.y_g (t_g = -o.y_g / d.y_g
         // correctly rounded), which the margin covers -- and three registers fewer than keeping the o.y
         const float y = dy[g] * (t[f] - t[g]);
-        return front[g] & ((y > mu_out) | (y < mu_in));
+        if constexpr (KIND == kCubBox) return front[g] & (y > mu_out);
+        else if constexpr (KIND == kCubRoom) return front[g] & (y < mu_in);
+        else return front[g] & ((y > mu_out) | (y < mu_in));
     };
     bool s0 = ok[0] & !both & !beyond(0, 1) & !beyond(0, 2);
     bool s1 = ok[1] & !both & !beyond(1, 0) & !beyond(1, 2);
@@ -754,7 +784,8 @@ __device__ __forceinline__ bool box_fast(const float4 q0, const float4 q1, v3 id
 // The fast walk in three parts (closest_hit_fast below runs them back to back; an experiment of round 2 ran the middle one in another
 // lane than the other two: profiles/r02f/README.md).  fast_list: the up-front list, which also gives the ray its first closest-hit bound.
 // LAST, `last`: the lane's ray is the last of its path under the last-ray certificate (closest_hit_fast): it skips the room.
-template <bool LAST = false>
+// KIND: kCubRoom when the launch vouches for a list that starts with a certified room (the pair kernels), else kCubEither (list_cub says).
+template <bool LAST = false, CubKind KIND = kCubEither>
 __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, const float4* __restrict__ g_fprims, int n_small, int n_prims, int n_big_pairs,
                                           int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, bool last = false)
 {
@@ -762,10 +793,11 @@ __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, c
     // g_fprims is a read-only kernel argument, so the records arrive by scalar loads (s_load_dwordx4) into SGPRs: no LDS
     // traffic, no VGPRs for the matrices, and the loads of the next primitives overlap the tests of the current ones.
     // It also gives every ray a closest-hit bound before it enters the tree.
-    if (list_cub != 0) {
+    if (KIND != kCubEither || list_cub != 0) {
         // the room's six walls (or one big box) as a cuboid, the rest of the list after them
         if (!LAST || __ballot(!last) != 0ull) {
-            if (!LAST || !last) cuboid_range<true>(g_fprims, s_fprims, n_small, list_cub == 1 ? cub_mu : INFINITY, list_cub == 1 ? -INFINITY : -cub_mu, o, d, tmin, best);
+            const bool box = KIND == kCubEither && list_cub == 1;
+            if (!LAST || !last) cuboid_range<true, KIND>(g_fprims, s_fprims, n_small, box ? cub_mu : INFINITY, box ? -INFINITY : -cub_mu, o, d, tmin, best);
         }
         leaf_range<true>(g_fprims, s_fprims, n_small + 6, n_prims - n_small - 6, 0, o, d, tmin, best);
     } else {
@@ -863,7 +895,7 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
             const int first = left, cnt = leaf_count(right), npairs = leaf_pairs(right);
             FastCounters::step(dbg_tests, (unsigned int)cnt);
             if (tree_spheres) sphere_leaf(s_fprims, first, cnt, o, d, tmin, best);
-            else if (leaf_cuboid(right) != 0 && cub_mu > 0.0f) cuboid_range<false>(s_fprims, s_fprims, first, cub_mu, -INFINITY, o, d, tmin, best);
+            else if (leaf_cuboid(right) != 0 && cub_mu > 0.0f) cuboid_range<false, kCubBox>(s_fprims, s_fprims, first, cub_mu, -INFINITY, o, d, tmin, best);
             else leaf_range<false>(s_fprims, s_fprims, first, cnt, npairs, o, d, tmin, best);
             have = pop();
         }
@@ -892,13 +924,13 @@ __device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, c
     const bool go_r = hr & (!hl | (tr < tl));
     if (hl | hr) {
         FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(go_r ? h1.w : l1.w)));
-        cuboid_range<false>(s_fprims, s_fprims, __float_as_int(go_r ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
+        cuboid_range<false, kCubBox>(s_fprims, s_fprims, __float_as_int(go_r ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
     }
     const bool far = hl & hr & (__uint_as_float(__float_as_uint(go_r ? tl : tr) & 0xFFFF0000u) <= best.t);
     if (__ballot(far) != 0ull) {
         if (far) {
             FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(go_r ? l1.w : h1.w)));
-            cuboid_range<false>(s_fprims, s_fprims, __float_as_int(go_r ? l0.w : h0.w), cub_mu, -INFINITY, o, d, tmin, best);
+            cuboid_range<false, kCubBox>(s_fprims, s_fprims, __float_as_int(go_r ? l0.w : h0.w), cub_mu, -INFINITY, o, d, tmin, best);
         }
     }
 }
@@ -1045,7 +1077,7 @@ __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fn
     best.t = tmax;
     best.pos = -1;
     best.orig = -1;
-    fast_list<LAST>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
+    fast_list<LAST, PAIR ? kCubRoom : kCubEither>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
     const bool walk = !last || best.pos >= 0;
     FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (last ? 6 : 0)));
     tl.list_done(best.pos);

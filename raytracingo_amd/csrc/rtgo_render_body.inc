@@ -9,7 +9,7 @@
     //             fast walk (the timed kernel):          [fnodes 2/node][fprims 4/prim, Morton order][materials 3/prim][frames 2/prim][stack, 4 B/entry][lights]
     //             GLOBAL:                                [stack][lights]
     constexpr int MS = STATS ? 6 : 3;  // float4 stride between two primitives' material rows (kd|spec, kr|type, Le)
-    const int n_nodes = STATS ? p.n_nodes : p.n_fnodes;
+    const int n_nodes = STATS ? p.n_nodes : (PAIR ? kPairNodes : p.n_fnodes);
     float4* s_nodes = GLOBAL ? const_cast<float4*>(p.nodes) : reinterpret_cast<float4*>(smem);
     float4* s_prims = GLOBAL ? const_cast<float4*>(p.prims) : s_nodes + 2 * n_nodes;
     float4* s_mat_w = STATS ? s_prims + 3 : s_prims + 4 * p.n_prims;
