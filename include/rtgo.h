@@ -486,6 +486,46 @@ int rtgo_whitted_trace_rays(rtgo_ctx* ctx, const void* d_rays, void* d_hits, uin
    render launches' tile queue and its parity: launches and these calls may alternate freely. */
 int rtgo_whitted_shade_rays(rtgo_ctx* ctx, const void* d_rays, void* d_accum, void* d_image, uint32_t n, uint32_t sample_index);
 
+/* What a launch's rtgo_frame says about shading, for rays of the caller's own (rtgo_shade_rays).  16 bytes. */
+typedef struct rtgo_shade_options {
+    int32_t  max_trace_depth;  /* Params::maxTraceDepth for these rays, [0, 5] */
+    uint32_t path_tracing;     /* Params::enablePathTracing, 0 or 1 */
+    uint32_t use_ambient;      /* Params::useAmbientLight,  0 or 1 */
+    uint32_t sample_index;     /* Params::frameCount of the fold (kernel.cu:239-246) */
+} rtgo_shade_options;
+
+/* Shade n rays of the caller's own against the scene of rtgo_set_scene / rtgo_set_large_scene: __closesthit__ch,
+   __closesthit__full_occlusion and __miss__ms (kernel.cu:419-549) behind a raygen program that is the caller's -- a panoramic or
+   orthographic camera, a light probe, a stereo pair, a baked lightmap.  One ray is one sample of the reference: a trace(...) call of
+   __raygen__rg at depth 0.  d_rays = rtgo_ray[n], d_seeds = uint32[n] or NULL, d_accum = float4[n], d_image = uchar4[n] or NULL: DEVICE
+   memory of the context's device, caller-owned, rays and accum 16-byte aligned, seeds and image 4-byte aligned.  Asynchronous on the
+   context's stream.  Needs an analytic scene, and in distributed mode (path_tracing == 0) the context's surface lights; no camera, no
+   output buffer; the miss colour is the context's (rtgo_set_background).
+     seed of ray i                   d_seeds[i], handed to the path as trace hands over `seed`: by value, after whatever the caller's
+                                     raygen drew.  d_seeds == NULL: tea<16>(i, sample_index), the raygen's own rule with the ray's index
+                                     for the pixel's and no jitter draws.
+     invalid ray                     rtgo_ray's rule, and in addition dir must be a unit vector, |dot(dir, dir) - 1| <= 1e-5 (the shader
+                                     places a hit at o + t d in path mode and at o + t normalize(d) in distributed mode: one point only
+                                     for unit directions).  sample_index == 0: accum[i] = (0,0,0,0) and image[i] = (0,0,0,0);
+                                     sample_index > 0: both are left untouched.  It is never walked.
+     valid ray                       result = the payload of the path that starts with this ray over tmin < t < tmax: the render kernels'
+                                     closest walk and ties, the three shading modes, their occlusion rays, bounces while depth <
+                                     max_trace_depth; children run over [rayEpsilon, 1e6].  cur = (0 + result) * (1 / 1), the launch's
+                                     arithmetic for one sample; acc = cur when sample_index == 0, else prev + (cur - prev) *
+                                     (1 / (sample_index + 1)) in float32 with prev = accum[i].xyz (kernel.cu:239-246, operation for
+                                     operation).  accum[i] = (acc, 1); image[i] = make_color(acc) (:90-98) when d_image is given.
+   So the rays __raygen__rg makes for sqrt_spp 1 and frame f (origin the eye, tmin 0.05, tmax 1e16), with the seeds as they stand after
+   the two jitter draws and sample_index = f, leave rtgo_launch's two buffers, bit for bit, in all three modes.  More than one sample
+   per result is not offered (the in-order sum of sqrt_spp > 1): a caller folds samples through sample_index.
+   RTGO_E_INVALID: NULL ctx, d_rays, d_accum or opt, a misaligned pointer, n > 1 << 30, path_tracing or use_ambient above 1;
+   RTGO_E_UNSUPPORTED: max_trace_depth outside [0, 5]; RTGO_E_STATE: no analytic scene (a whitted scene alone does not count),
+   distributed mode without a surface light; n == 0 after the checks: RTGO_OK.  In all of these nothing is enqueued or written and no
+   counter moves.  rtgo_stats: rays_total grows by n plus the bounce and occlusion rays the paths sent, rays_occlusion by those occlusion
+   rays; launches, last_launch_ms, last_variant, launches_trial, the launch-time trial and the render launches' queues are left alone:
+   launches and these calls may alternate freely.  Every ray takes the canonical walk. */
+int rtgo_shade_rays(rtgo_ctx* ctx, const void* d_rays, const void* d_seeds, void* d_accum, void* d_image, uint32_t n,
+                    const rtgo_shade_options* opt);
+
 /* number of window rows a rank owns under the band interleave (pure host arithmetic) */
 uint32_t rtgo_local_rows(uint32_t h, uint32_t band_h, uint32_t n_ranks, uint32_t rank);
 

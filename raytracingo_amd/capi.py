@@ -27,6 +27,7 @@ SYMBOLS = [
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
     "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
+    "rtgo_shade_rays",
 ]
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
@@ -109,6 +110,10 @@ class Ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
 
 
+class ShadeOptions(C.Structure):
+    _fields_ = [("max_trace_depth", C.c_int32), ("path_tracing", C.c_uint32), ("use_ambient", C.c_uint32), ("sample_index", C.c_uint32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("instance", C.c_int32), ("u", C.c_float), ("v", C.c_float), ("n", C.c_float * 3)]
 
@@ -182,6 +187,7 @@ def load():
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_shade_rays.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32]
+    L.rtgo_shade_rays.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(ShadeOptions)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtgo_last_error", "rtgo_local_rows", "rtgo_abi_version"):
@@ -552,6 +558,76 @@ class Context:
         """the bare C call on three device pointers (asynchronous); returns the library's code instead of raising"""
         return int(self._lib.rtgo_whitted_shade_rays(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_accum_ptr), C.c_void_p(d_image_ptr or 0), int(n),
                                                      int(sample_index)))
+
+    def shade_rays(self, rays, seeds=None, path=True, ambient=False, max_depth=5, sample_index=0, accum=None, image=True):
+        """rtgo_shade_rays over the scene of set_scene / set_large_scene.  rays: as trace_rays takes them.  seeds: one uint32 per ray (a
+        numpy array, uploaded, or a contiguous torch device tensor), or None: tea<16>(i, sample_index).  accum: the mean of the samples
+        before this one, [n, 4] float32, uploaded when sample_index > 0 (None: zeros).  Returns (accum [n, 4] float32, image [n, 4]
+        uint8, or None with image=False).  Synchronous."""
+        what = "rtgo_shade_rays"
+        H = hip_runtime()
+        if hasattr(rays, "data_ptr"):   # a torch device tensor: shaded where it is
+            if not rays.is_cuda or not rays.is_contiguous() or rays.numel() * rays.element_size() % 32:
+                raise ValueError("%s: rays must be a contiguous device tensor of 32-byte rtgo_ray records" % what)
+            n, host = rays.numel() * rays.element_size() // 32, None
+        else:
+            host = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+            n = len(host)
+        host_seeds = None
+        if seeds is not None:
+            if hasattr(seeds, "data_ptr"):
+                if not seeds.is_cuda or not seeds.is_contiguous() or seeds.numel() * seeds.element_size() != 4 * n:
+                    raise ValueError("%s: seeds must be a contiguous device tensor of one 32-bit word per ray" % what)
+            else:
+                host_seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+                if len(host_seeds) != n:
+                    raise ValueError("%s: %d seeds for %d rays" % (what, len(host_seeds), n))
+        out = np.zeros((n, 4), dtype=np.float32)
+        if sample_index > 0 and accum is not None:
+            out[:] = np.asarray(accum, dtype=np.float32).reshape(n, 4)
+        img = np.zeros((n, 4), dtype=np.uint8) if image else None
+        if n == 0:
+            return out, img
+        if H.hipSetDevice(self.device) != 0:
+            raise RtgoError("%s: hipSetDevice(%d) failed" % (what, self.device))
+        buf = C.c_void_p()   # [accum 16 n][rays 32 n, when uploaded][image 4 n][seeds 4 n, when uploaded]
+        ray_bytes = 0 if host is None else 32 * n
+        total = 16 * n + ray_bytes + 4 * n + (0 if host_seeds is None else 4 * n)
+        if H.hipMalloc(C.byref(buf), total) != 0:
+            raise RtgoError("%s: hipMalloc of %d bytes failed" % (what, total))
+        try:
+            d_accum, d_image = buf.value, buf.value + 16 * n + ray_bytes
+            if host is None:
+                d_rays = rays.data_ptr()
+            else:
+                d_rays = buf.value + 16 * n
+                if H.hipMemcpy(d_rays, host.ctypes.data, 32 * n, 1) != 0:
+                    raise RtgoError("%s: upload failed" % what)
+            d_seeds = 0
+            if host_seeds is not None:
+                d_seeds = d_image + 4 * n
+                if H.hipMemcpy(d_seeds, host_seeds.ctypes.data, 4 * n, 1) != 0:
+                    raise RtgoError("%s: upload failed" % what)
+            elif seeds is not None:
+                d_seeds = seeds.data_ptr()
+            if host is None or (seeds is not None and host_seeds is None):
+                H.hipDeviceSynchronize()   # (whatever stream filled the tensors: the call runs on the context's)
+            if sample_index > 0 and H.hipMemcpy(d_accum, out.ctypes.data, 16 * n, 1) != 0:
+                raise RtgoError("%s: upload failed" % what)
+            opt = ShadeOptions(int(max_depth), 1 if path else 0, 1 if ambient else 0, int(sample_index))
+            self._check(self._lib.rtgo_shade_rays(self._h, C.c_void_p(d_rays), C.c_void_p(d_seeds), C.c_void_p(d_accum),
+                                                  C.c_void_p(d_image if image else 0), n, C.byref(opt)), what)
+            self.sync()
+            if H.hipMemcpy(out.ctypes.data, d_accum, 16 * n, 2) != 0 or (image and H.hipMemcpy(img.ctypes.data, d_image, 4 * n, 2) != 0):
+                raise RtgoError("%s: download failed" % what)
+        finally:
+            H.hipFree(buf)
+        return out, img
+
+    def shade_rays_raw(self, d_rays_ptr, d_seeds_ptr, d_accum_ptr, d_image_ptr, n, opt):
+        """the bare C call on four device pointers and a ShadeOptions (or None) (asynchronous); returns the library's code instead of raising"""
+        return int(self._lib.rtgo_shade_rays(self._h, C.c_void_p(d_rays_ptr or 0), C.c_void_p(d_seeds_ptr or 0), C.c_void_p(d_accum_ptr or 0),
+                                             C.c_void_p(d_image_ptr or 0), int(n), C.byref(opt) if opt is not None else None))
 
     def stats(self):
         s = Stats()

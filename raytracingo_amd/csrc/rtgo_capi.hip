@@ -493,7 +493,10 @@ int rtgo_create(int device, rtgo_ctx** out)
                            // ... and the kernels of rtgo_whitted_shade_rays
                            (const void*)whitted::whitted_shade_kernel<whitted::kTraceMesh>, (const void*)whitted::whitted_shade_kernel<whitted::kTraceInst>,
                            (const void*)whitted::whitted_shade_kernel<whitted::kTraceInstLds>, (const void*)whitted::whitted_shade_kernel<whitted::kTraceClustered>,
-                           (const void*)whitted::whitted_shade_kernel<whitted::kTraceClusteredLds>})
+                           (const void*)whitted::whitted_shade_kernel<whitted::kTraceClusteredLds>,
+                           // ... and of rtgo_shade_rays
+                           (const void*)shade_rays_kernel<true, false>, (const void*)shade_rays_kernel<true, true>,
+                           (const void*)shade_rays_kernel<false, false>, (const void*)shade_rays_kernel<false, true>})
         if (err == hipSuccess) err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
     if (err == hipSuccess) err = hipDeviceSynchronize();  // the null-stream memsets above must land before any launch
     if (err != hipSuccess) {
@@ -2007,6 +2010,46 @@ static unsigned int trace_grid(const rtgo_ctx* c, uint32_t n, int block, int per
     return (unsigned int)grid;
 }
 
+// What the two ray-batch calls of the analytic path share (rtgo_trace_rays, rtgo_shade_rays): whether the workgroups stage the scene in
+// LDS, the stacks' depth, the workgroup and its LDS.  A workgroup's LDS is the scene copy (when staged), `group_bytes` of its own, and a
+// stack per lane.  max_waves: waves a CU can hold of the kernel (its registers).
+struct AnalyticRaysPlan {
+    bool in_lds;
+    int stack_depth, block, per_cu;
+    size_t lds;
+};
+static bool analytic_rays_plan(const AnalyticScene& sc, uint32_t n, size_t group_bytes, int max_waves, AnalyticRaysPlan& plan)
+{
+    const int n_prims = (int)sc.n_prims, n_nodes = 2 * n_prims - 1;
+    // the stacks as deep as the canonical instantiations have them: kStackDepth over a scene of rtgo_set_scene (its build checks the
+    // tree against it), the tree's own depth over a scene of rtgo_set_large_scene
+    plan.stack_depth = sc.large ? (sc.lbvh_depth > 0 ? sc.lbvh_depth : 1) : kStackDepth;
+    const size_t scene_lds = (size_t)(2 * n_nodes + 6 * n_prims) * sizeof(float4);
+    // the workgroup that puts the most waves on a CU (pick_block's rule: the scene copy is per workgroup, the stacks per lane), at
+    // most max_waves, the smallest on ties
+    auto pick = [&](bool in_lds, int& block, int& per_cu, size_t& lds) {
+        int best_waves = 0;
+        for (int bs = 64; bs <= kMaxBlock; bs *= 2) {
+            const size_t l = (in_lds ? scene_lds : 0) + group_bytes + (size_t)plan.stack_depth * bs * sizeof(float2);
+            int k = (int)(kTraceLds / l);
+            if (k * (bs / 64) > max_waves) k = max_waves / (bs / 64);
+            if (k * (bs / 64) > best_waves) {
+                best_waves = k * (bs / 64);
+                block = bs;
+                per_cu = k;
+                lds = l;
+            }
+        }
+        return best_waves > 0;
+    };
+    const int mode = env_trace_mode();
+    plan.block = plan.per_cu = 0;
+    plan.lds = 0;
+    plan.in_lds = !sc.large && sc.n_prims <= (uint32_t)kMaxPrims && (mode == 1 || (mode < 0 && n >= kTraceLdsMinRays));
+    if (plan.in_lds && !pick(true, plan.block, plan.per_cu, plan.lds)) plan.in_lds = false;
+    return plan.in_lds || pick(false, plan.block, plan.per_cu, plan.lds);
+}
+
 int rtgo_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, uint32_t flags)
 {
     if (const int rc = trace_check(c, d_rays, d_hits, n, flags, "rtgo_trace_rays")) return rc;
@@ -2022,40 +2065,70 @@ int rtgo_trace_rays(rtgo_ctx* c, const void* d_rays, void* d_hits, uint32_t n, u
     p.n = n;
     p.n_prims = (int)sc.n_prims;
     p.n_nodes = 2 * (int)sc.n_prims - 1;
-    // the stacks as deep as the canonical instantiations have them: kStackDepth over a scene of rtgo_set_scene (its build checks the
-    // tree against it), the tree's own depth over a scene of rtgo_set_large_scene
-    p.stack_depth = sc.large ? (sc.lbvh_depth > 0 ? sc.lbvh_depth : 1) : kStackDepth;
-    const size_t scene_lds = (size_t)(2 * p.n_nodes + 6 * p.n_prims) * sizeof(float4);
-    // the workgroup that puts the most waves on a CU (pick_block's rule: the scene copy is per workgroup, the stacks per lane), at
-    // most 8 a SIMD, the smallest on ties
-    auto pick = [&](bool in_lds, int& block, int& per_cu, size_t& lds) {
-        int best_waves = 0;
-        for (int bs = 64; bs <= kMaxBlock; bs *= 2) {
-            const size_t l = (in_lds ? scene_lds : 0) + (size_t)p.stack_depth * bs * sizeof(float2);
-            int k = (int)(kTraceLds / l);
-            if (k * (bs / 64) > 32) k = 32 / (bs / 64);
-            if (k * (bs / 64) > best_waves) {
-                best_waves = k * (bs / 64);
-                block = bs;
-                per_cu = k;
-                lds = l;
-            }
-        }
-        return best_waves > 0;
-    };
-    const int mode = env_trace_mode();
-    int block = 0, per_cu = 0;
-    size_t lds = 0;
-    bool in_lds = !sc.large && sc.n_prims <= (uint32_t)kMaxPrims && (mode == 1 || (mode < 0 && n >= kTraceLdsMinRays));
-    if (in_lds && !pick(true, block, per_cu, lds)) in_lds = false;
-    if (!in_lds && !pick(false, block, per_cu, lds)) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_trace_rays: the walk's stacks do not fit in LDS");
-    const unsigned int grid = trace_grid(c, n, block, per_cu);
+    AnalyticRaysPlan plan;
+    if (!analytic_rays_plan(sc, n, 0, 32, plan)) return fail(c, RTGO_E_UNSUPPORTED, "rtgo_trace_rays: the walk's stacks do not fit in LDS");
+    p.stack_depth = plan.stack_depth;
+    const unsigned int grid = trace_grid(c, n, plan.block, plan.per_cu);
     RTGO_HIP(c, hipSetDevice(c->device));
-    if (in_lds) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(grid), dim3(block), lds, c->stream, p);
-    else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(grid), dim3(block), lds, c->stream, p);
+    if (plan.in_lds) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(grid), dim3(plan.block), plan.lds, c->stream, p);
+    else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(grid), dim3(plan.block), plan.lds, c->stream, p);
     RTGO_HIP(c, hipGetLastError());
     c->trace_rays += n;
     if (flags & RTGO_TRACE_ANY_HIT) c->trace_rays_any += n;   // (the analytic path has no any-hit walk: the closest walk answers)
+    return RTGO_OK;
+}
+
+// The render launches' queues, trial and counters of launches are not touched: the kernel has no work queue.
+int rtgo_shade_rays(rtgo_ctx* c, const void* d_rays, const void* d_seeds, void* d_accum, void* d_image, uint32_t n, const rtgo_shade_options* opt)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (!d_rays || !d_accum || !opt) return fail(c, RTGO_E_INVALID, "rtgo_shade_rays: NULL ray buffer, accumulation buffer or options");
+    if ((((uintptr_t)d_rays | (uintptr_t)d_accum) & 15u) || (((uintptr_t)d_seeds | (uintptr_t)d_image) & 3u))
+        return fail(c, RTGO_E_INVALID, "rtgo_shade_rays: ray and accumulation buffers must be 16-byte aligned, seeds and image 4-byte aligned");
+    if (n > kTraceMaxRays) return fail(c, RTGO_E_INVALID, "rtgo_shade_rays: more than 2^30 rays");
+    if (opt->path_tracing > 1u || opt->use_ambient > 1u) return fail(c, RTGO_E_INVALID, "rtgo_shade_rays: path_tracing and use_ambient must be 0 or 1");
+    if (opt->max_trace_depth < 0 || opt->max_trace_depth > kMaxLevels)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_shade_rays: max_trace_depth must be in [0, 5] (reference uses 5, renderer.cpp:616)");
+    const AnalyticScene& sc = c->scene;
+    if (sc.n_prims == 0) return fail(c, RTGO_E_STATE, "rtgo_shade_rays: no scene (call rtgo_set_scene or rtgo_set_large_scene)");
+    if (!opt->path_tracing && c->n_lights < 1) return fail(c, RTGO_E_STATE, "rtgo_shade_rays: distributed mode needs at least one surface light");
+    if (n == 0) return RTGO_OK;
+    const bool path = opt->path_tracing != 0;
+    ShadeParams p;
+    std::memset(&p, 0, sizeof p);
+    p.nodes = sc.d_nodes.get();
+    p.prims = sc.d_prims.get();
+    p.lights = c->d_lights.get();
+    p.rays = (const float4*)d_rays;
+    p.seeds = (const unsigned int*)d_seeds;
+    p.accum = (float4*)d_accum;
+    p.image = (uchar4*)d_image;
+    p.counters = c->d_counters.get();
+    p.n = n;
+    p.sample_index = opt->sample_index;
+    p.n_prims = (int)sc.n_prims;
+    p.n_nodes = 2 * (int)sc.n_prims - 1;
+    p.n_lights = c->n_lights;
+    p.max_depth = opt->max_trace_depth;
+    p.ambient = (int)opt->use_ambient;
+    p.bg = c->bg;
+    // behind the stacks: the light records.  The kernels' registers allow five waves a SIMD in path mode (86 / 93 VGPRs) and four in
+    // distributed mode (108 / 111): 20 and 16 a CU
+    AnalyticRaysPlan plan;
+    if (!analytic_rays_plan(sc, n, kMaxLights * sizeof(LightRec), path ? 20 : 16, plan))
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_shade_rays: the walk's stacks do not fit in LDS");
+    p.stack_depth = plan.stack_depth;
+    const dim3 grid(trace_grid(c, n, plan.block, plan.per_cu)), bdim(plan.block);
+    RTGO_HIP(c, hipSetDevice(c->device));
+    if (path) {
+        if (plan.in_lds) hipLaunchKernelGGL((shade_rays_kernel<true, true>), grid, bdim, plan.lds, c->stream, p);
+        else hipLaunchKernelGGL((shade_rays_kernel<true, false>), grid, bdim, plan.lds, c->stream, p);
+    } else {
+        if (plan.in_lds) hipLaunchKernelGGL((shade_rays_kernel<false, true>), grid, bdim, plan.lds, c->stream, p);
+        else hipLaunchKernelGGL((shade_rays_kernel<false, false>), grid, bdim, plan.lds, c->stream, p);
+    }
+    RTGO_HIP(c, hipGetLastError());
+    c->trace_rays += n;   // the batch; the bounce and occlusion rays are counted by the kernel
     return RTGO_OK;
 }
 

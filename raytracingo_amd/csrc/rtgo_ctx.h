@@ -6,6 +6,7 @@
 #include "rtgo_device.h"
 #include "rtgo_large.h"
 #include "rtgo_owners.h"
+#include "rtgo_shade.h"
 #include "rtgo_trace.h"
 #include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
