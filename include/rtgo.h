@@ -154,6 +154,30 @@ int rtgo_set_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs
    A scene within RTGO_MAX_PRIMS renders the same pixels bit for bit through rtgo_set_scene, and faster there. */
 int rtgo_set_large_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n);
 
+/* flags of rtgo_update_prims */
+enum { RTGO_UPDATE_REFIT = 0, RTGO_UPDATE_REBUILD = 1 };
+
+/* optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE (RTGO_UPDATE_REFIT) or _BUILD (RTGO_UPDATE_REBUILD) over the custom-primitive AABBs,
+   plus a rewrite of n_updates hit-group SBT records (no reference counterpart: its Renderer builds once, renderer.cpp:514-611, 636-653).
+   Primitive indices[j] (an SBT index) of the analytic scene the context holds becomes prims[j] -- type, model matrix and material -- and
+   aabbs[j] its box; aabbs is NULL exactly when the scene was set without boxes (the box is then the CubeBox rule's, as at set time).
+   The primitive count, every primitive not named, camera, lights, background, output and stream stay.  Synchronous.
+   Afterwards every launch, rtgo_trace_rays and rtgo_shade_rays leaves, bit for bit, what it leaves on a fresh context given the edited
+   array through the same set call, the ray counters of rtgo_stats included (any tree over the same primitives returns the same closest
+   hit, ties to the lowest SBT index).
+   A scene of rtgo_set_scene: both flags run the set call's build again from the inputs already on the device; the context then holds what
+   a fresh rtgo_set_scene holds.  A scene of rtgo_set_large_scene: REFIT rewrites the records, the leaves and the boxes of their
+   ancestors (one launch per tree level; none when no box changed) -- topology and lbvh_depth stay, so the tree is as good as the edit
+   left it; REBUILD sorts and builds again over the boxes on the device, to the nodes of a fresh rtgo_set_large_scene.
+   The screen-rectangle mask, the pre-hashed seeds and the launch-time trial are dropped, as by a set call.
+   Everything is checked before anything on the device changes, and a refused call leaves the scene as it was.  RTGO_E_STATE: no
+   analytic scene (a whitted scene alone does not count).  RTGO_E_INVALID: NULL ctx; unknown flag bits; with n_updates > 0: NULL indices
+   or prims, aabbs given or NULL against the scene, an index >= the scene's count, an index named twice, anything the set call refuses of
+   a primitive or a box.  RTGO_E_UNSUPPORTED: a structure the set call would refuse (a rebuilt tree deeper than the walk's stack).
+   n_updates == 0 with a scene and known flags: RTGO_OK, nothing changes. */
+int rtgo_update_prims(rtgo_ctx* ctx, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n_updates,
+                      uint32_t flags);
+
 /* raygen SBT record: Renderer::CreateRayGen / SyncCameraToSbt (renderer.cpp:321-336, 719-731); device::CameraData */
 int rtgo_set_camera(rtgo_ctx* ctx, const float eye[3], const float U[3], const float V[3], const float W[3]);
 

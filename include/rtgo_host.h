@@ -74,6 +74,11 @@ int rtgo_host_session_read(rtgo_host_session* s, void* host_image, void* host_ac
    *prim = the SBT index of the closest primitive and *t its distance; a miss returns 0 with *prim == -1.  Synchronous; the frame loop's
    state (frame count, pending camera change or resize) is left as it is.  A pixel outside the image: an error code. */
 int rtgo_host_session_pick(rtgo_host_session* s, uint32_t x, uint32_t y, int32_t* prim, float* t);
+/* "Pick, then drag": primitive indices[j] (an SBT index, as rtgo_host_session_pick returns it) becomes prims[j] -- type, model matrix and
+   material -- through Renderer::UpdatePrimitives = rtgo_update_prims (a refit), its box by Primitive::GetAabb's rule.  The next frame
+   restarts the progressive accumulation at frame count 0, as after move_camera; a pick answers over the edited scene at once.
+   Whatever rtgo_update_prims refuses (an index beyond the scene or named twice, a singular matrix): an error code, the scene as it was. */
+int rtgo_host_session_update_prims(rtgo_host_session* s, const uint32_t* indices, const rtgo_prim* prims, uint32_t n);
 /* The camera pick uses and the next frame renders with (after move_camera / resize: the new one): eye and the raygen record's UVW */
 int rtgo_host_session_camera(rtgo_host_session* s, float eye[3], float U[3], float V[3], float W[3]);
 int rtgo_host_session_close(rtgo_host_session* s);

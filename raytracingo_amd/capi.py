@@ -27,8 +27,9 @@ SYMBOLS = [
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
     "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
-    "rtgo_shade_rays",
+    "rtgo_shade_rays", "rtgo_update_prims",
 ]
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
 RTGO_WHITTED_MAX_MESHES = 256
@@ -154,6 +155,7 @@ def load():
     L.rtgo_set_stream.argtypes = [vp, vp]
     L.rtgo_set_scene.argtypes = [vp, C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32]
     L.rtgo_set_large_scene.argtypes = [vp, C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32]
+    L.rtgo_update_prims.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32, C.c_uint32]
     L.rtgo_set_camera.argtypes = [vp, fp, fp, fp, fp]
     L.rtgo_set_background.argtypes = [vp, fp]
     L.rtgo_set_lights.argtypes = [vp, C.POINTER(Light), C.c_int]
@@ -298,6 +300,26 @@ class Context:
                                                    bb.ctypes.data_as(C.POINTER(Aabb)) if bb is not None else None, n),
                     "rtgo_set_large_scene")
         self.n_prims = n
+
+    def update_prims(self, indices, types, models, materials, aabbs=None, rebuild=False):
+        """rtgo_update_prims: primitive indices[j] becomes (types[j], models[j], materials[j]) with the box aabbs[j]; the arguments as
+        set_scene takes them.  aabbs: given exactly when the scene was set with boxes.  rebuild: RTGO_UPDATE_REBUILD, else a refit."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        k = len(idx)
+        rec = np.zeros(k, dtype=PRIM_DTYPE)
+        rec["type"] = np.asarray(types).astype(np.uint32).reshape(-1)
+        rec["model"] = np.asarray(models, dtype=np.float32).reshape(-1, 16)
+        mat = np.asarray(materials, dtype=np.float32).reshape(-1, 10)
+        rec["kd"], rec["kr"], rec["specularity"], rec["Le"] = mat[:, 0:3], mat[:, 3:6], mat[:, 6], mat[:, 7:10]
+        bb = None
+        if aabbs is not None:
+            bb = np.ascontiguousarray(aabbs, dtype=np.float32).reshape(-1, 6)
+            if len(bb) != k:
+                raise ValueError("aabbs: %d boxes for %d updates" % (len(bb), k))
+        self._check(self._lib.rtgo_update_prims(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), rec.ctypes.data_as(C.POINTER(Prim)),
+                                                bb.ctypes.data_as(C.POINTER(Aabb)) if bb is not None else None, k,
+                                                UPDATE_REBUILD if rebuild else UPDATE_REFIT),
+                    "rtgo_update_prims")
 
     def set_camera(self, eye, U, V, W):
         a = [_f3(x) for x in (eye, U, V, W)]

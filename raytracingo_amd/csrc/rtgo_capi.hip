@@ -844,16 +844,9 @@ static void drop_scene(rtgo_ctx* c)
     c->trial = rtgo_ctx::Trial();
 }
 
-int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+// The buffers of a scene of rtgo_set_scene for n primitives, in c->scene
+static int alloc_resident(rtgo_ctx* c, uint32_t n)
 {
-    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: NULL argument");
-    if (n == 0 || n > RTGO_MAX_PRIMS)
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_PRIMS) + "]");
-    if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_scene")) return rc;
-    const Knobs kn;
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    drop_scene(c);
     AnalyticScene& sc = c->scene;
     RTGO_HIP(c, sc.d_prims_in.alloc(n));
     RTGO_HIP(c, sc.d_aabb.alloc(n * 6));
@@ -861,11 +854,20 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     RTGO_HIP(c, sc.d_prims.alloc(n * 6));
     RTGO_HIP(c, sc.d_frames.alloc(n * 2));
     RTGO_HIP(c, sc.d_tight.alloc(n * 6));
+    return RTGO_OK;
+}
+
+// The build half of rtgo_set_scene, from what is on the device (rtgo_set_scene after its upload, rtgo_update_prims after its patch): both
+// fast-walk structures, the emitter certificates, the tight boxes, the grid, the bounds and the quadric list of c->scene, whose
+// d_prims_in, d_aabb (with have_aabbs), host_prims and have_aabbs are in place.  Sets n_prims last, once the build succeeded.
+static int build_resident(rtgo_ctx* c, uint32_t n)
+{
+    const Knobs kn;
+    AnalyticScene& sc = c->scene;
+    const rtgo_prim* prims = sc.host_prims.data();
     if (kn.leaf_budget >= 0) c->leaf_budget = kn.leaf_budget;
-    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
-    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
     BuildMeta meta;
-    if (const int rc = build_fast_tree(c, n, aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, sc.tree[0], meta)) return rc;
+    if (const int rc = build_fast_tree(c, n, sc.have_aabbs ? 1 : 0, (float)kn.big_percent * 0.01f, kn, sc.tree[0], meta)) return rc;
     if (const int rc = emitter_cert(c, prims, n, sc.tree[0])) return rc;
     sc.tight.assign((size_t)n * 6, 0.0f);
     RTGO_HIP(c, hipMemcpyAsync(sc.tight.data(), sc.d_tight.get(), (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -914,13 +916,98 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     return RTGO_OK;
 }
 
-// the temporaries of rtgo_set_large_scene's build, freed however the call ends
+int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+{
+    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: NULL argument");
+    if (n == 0 || n > RTGO_MAX_PRIMS)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_PRIMS) + "]");
+    if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_scene")) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    drop_scene(c);
+    AnalyticScene& sc = c->scene;
+    if (const int rc = alloc_resident(c, n)) return rc;
+    sc.host_prims.assign(prims, prims + n);
+    sc.have_aabbs = aabbs != nullptr;
+    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
+    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
+    return build_resident(c, n);
+}
+
+// the temporaries of large_build_tree, freed however it ends
 struct LargeScratch {
     DeviceArray<unsigned long long> keys, keys_alt;
     DeviceArray<unsigned int> hist;
-    DeviceArray<int> left, right, parent, depth;
+    DeviceArray<int> left, right;
     DeviceArray<float> small;   // scene bounds (6 floats), then the largest leaf depth (int)
 };
+
+// What the build of rtgo_set_large_scene makes over n boxes: the nodes, what AnalyticScene::LargeKeep holds, depth and bounds
+struct LargeTree {
+    DeviceArray<float4> nodes;
+    AnalyticScene::LargeKeep keep;
+    int lbvh_depth = 0;
+    float bounds[6] = {0, 0, 0, 0, 0, 0};
+};
+
+// The canonical LBVH over the n boxes at d_aabb (device), into arrays of its own (rtgo_set_large_scene; rtgo_update_prims' rebuild, which
+// swaps them in on success).  A tree deeper than the walk's stack: RTGO_E_UNSUPPORTED.  The stream is idle when it returns.
+static int large_build_tree(rtgo_ctx* c, const float* d_aabb, uint32_t n, const std::string& what, LargeTree& t)
+{
+    const int ni = (int)n, n_int = ni > 1 ? ni - 1 : 1;
+    LargeScratch ls;
+    RTGO_HIP(c, t.nodes.alloc((2 * (size_t)n - 1) * 2));
+    RTGO_HIP(c, t.keep.parent.alloc(2 * (size_t)n - 1));
+    RTGO_HIP(c, t.keep.depth.alloc(n_int));
+    RTGO_HIP(c, t.keep.leaf_of.alloc(n));
+    RTGO_HIP(c, t.keep.mark.alloc(n_int));
+    RTGO_HIP(c, ls.keys.alloc(n));
+    RTGO_HIP(c, ls.keys_alt.alloc(n));
+    RTGO_HIP(c, ls.hist.alloc((size_t)256 * ((ni + whitted::kRadixTile - 1) / whitted::kRadixTile)));
+    RTGO_HIP(c, ls.left.alloc(n_int));
+    RTGO_HIP(c, ls.right.alloc(n_int));
+    RTGO_HIP(c, ls.small.alloc(8));
+    RTGO_HIP(c, hipMemsetAsync(ls.small.get(), 0, 8 * sizeof(float), c->stream));
+    RTGO_HIP(c, hipMemsetAsync(t.keep.mark.get(), 0, (size_t)n_int * sizeof(unsigned int), c->stream));
+    const dim3 g_prims((n + 255) / 256), g_nodes((2 * n - 1 + 255) / 256), g_int((n_int + 255) / 256);
+    // bounds; Morton keys in (code, index) order (four stable passes over the code's bytes: back in ls.keys)
+    hipLaunchKernelGGL(whitted::big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, d_aabb, ni, ls.small.get());
+    hipLaunchKernelGGL(large_keys_kernel, g_prims, dim3(256), 0, c->stream, d_aabb, ni, (const float*)ls.small.get(), ls.keys.get());
+    const unsigned long long* src = radix_sort_keys(c, ls.keys.get(), ls.keys_alt.get(), ls.hist.get(), ni);
+    // hierarchy, depths and leaves
+    int* d_max_depth = reinterpret_cast<int*>(ls.small.get() + 6);
+    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, src, ni, ls.left.get(), ls.right.get(), t.keep.parent.get());
+    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, src, ni, d_aabb, (const int*)t.keep.parent.get(), t.keep.depth.get(),
+                       t.nodes.get(), d_max_depth, t.keep.leaf_of.get());
+    RTGO_HIP(c, hipGetLastError());
+    int depth = 0;
+    RTGO_HIP(c, hipMemcpyAsync(&depth, d_max_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (depth > kLargeMaxDepth)
+        return fail(c, RTGO_E_UNSUPPORTED, what + ": LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
+                                               std::to_string(kLargeMaxDepth) + ")");
+    // boxes, one level per launch from the deepest up (a kernel boundary between a node's children and the node)
+    for (int level = depth - 1; level >= 0; --level)
+        hipLaunchKernelGGL(large_fit_kernel, g_int, dim3(256), 0, c->stream, (const int*)ls.left.get(), (const int*)ls.right.get(), (const int*)t.keep.depth.get(),
+                           ni - 1, level, t.nodes.get());
+    RTGO_HIP(c, hipGetLastError());
+    float4 root[2];
+    RTGO_HIP(c, hipMemcpyAsync(root, t.nodes.get(), sizeof root, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    const float b[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
+    std::memcpy(t.bounds, b, sizeof t.bounds);
+    t.lbvh_depth = depth;
+    return RTGO_OK;
+}
+
+// a tree large_build_tree made becomes the scene's (its nodes, shape, depth and bounds)
+static void adopt_large_tree(AnalyticScene& sc, LargeTree& t)
+{
+    sc.d_nodes = std::move(t.nodes);
+    sc.keep = std::move(t.keep);
+    std::memcpy(sc.bounds, t.bounds, sizeof sc.bounds);
+    sc.lbvh_depth = t.lbvh_depth;
+}
 
 int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
 {
@@ -933,59 +1020,165 @@ int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* a
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     drop_scene(c);
     AnalyticScene& sc = c->scene;
-    const int ni = (int)n, n_int = ni > 1 ? ni - 1 : 1;
-    LargeScratch ls;
     RTGO_HIP(c, sc.d_prims_in.alloc(n));
     RTGO_HIP(c, sc.d_aabb.alloc((size_t)n * 6));
-    RTGO_HIP(c, sc.d_nodes.alloc((2 * (size_t)n - 1) * 2));
     RTGO_HIP(c, sc.d_prims.alloc((size_t)n * 6));
-    RTGO_HIP(c, ls.keys.alloc(n));
-    RTGO_HIP(c, ls.keys_alt.alloc(n));
-    RTGO_HIP(c, ls.hist.alloc((size_t)256 * ((ni + whitted::kRadixTile - 1) / whitted::kRadixTile)));
-    RTGO_HIP(c, ls.left.alloc(n_int));
-    RTGO_HIP(c, ls.right.alloc(n_int));
-    RTGO_HIP(c, ls.parent.alloc(2 * (size_t)n - 1));
-    RTGO_HIP(c, ls.depth.alloc(n_int));
-    RTGO_HIP(c, ls.small.alloc(8));
     RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, (size_t)n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
     if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, (size_t)n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
-    RTGO_HIP(c, hipMemsetAsync(ls.small.get(), 0, 8 * sizeof(float), c->stream));
-    const dim3 g_prims((n + 255) / 256), g_nodes((2 * n - 1 + 255) / 256), g_int((n_int + 255) / 256);
-    // records and boxes; bounds; Morton keys in (code, index) order (four stable passes over the code's bytes: back in ls.keys)
-    hipLaunchKernelGGL(large_prep_kernel, g_prims, dim3(256), 0, c->stream, (const PrimIn*)sc.d_prims_in.get(), sc.d_aabb.get(), aabbs ? 1 : 0, ni, sc.d_prims.get());
-    hipLaunchKernelGGL(whitted::big_bounds_final_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)sc.d_aabb.get(), ni, ls.small.get());
-    hipLaunchKernelGGL(large_keys_kernel, g_prims, dim3(256), 0, c->stream, (const float*)sc.d_aabb.get(), ni, (const float*)ls.small.get(), ls.keys.get());
-    const unsigned long long* src = radix_sort_keys(c, ls.keys.get(), ls.keys_alt.get(), ls.hist.get(), ni);
-    // hierarchy, depths and leaves
-    int* d_max_depth = reinterpret_cast<int*>(ls.small.get() + 6);
-    hipLaunchKernelGGL(large_karras_kernel, g_int, dim3(256), 0, c->stream, src, ni, ls.left.get(), ls.right.get(), ls.parent.get());
-    hipLaunchKernelGGL(large_depth_kernel, g_nodes, dim3(256), 0, c->stream, src, ni, (const float*)sc.d_aabb.get(),
-                       (const int*)ls.parent.get(), ls.depth.get(), sc.d_nodes.get(), d_max_depth);
-    RTGO_HIP(c, hipGetLastError());
-    int depth = 0;
-    RTGO_HIP(c, hipMemcpyAsync(&depth, d_max_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (depth > kLargeMaxDepth) {
-        c->scene = AnalyticScene();
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
-                                               std::to_string(kLargeMaxDepth) + ")");
+    // records and boxes, then the tree over the boxes
+    hipLaunchKernelGGL(large_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const PrimIn*)sc.d_prims_in.get(), sc.d_aabb.get(), aabbs ? 1 : 0, (int)n,
+                       sc.d_prims.get());
+    LargeTree t;
+    if (const int rc = large_build_tree(c, sc.d_aabb.get(), n, "rtgo_set_large_scene", t)) {
+        if (rc == RTGO_E_UNSUPPORTED) c->scene = AnalyticScene();
+        return rc;
     }
-    // boxes, one level per launch from the deepest up (a kernel boundary between a node's children and the node)
-    for (int level = depth - 1; level >= 0; --level)
-        hipLaunchKernelGGL(large_fit_kernel, g_int, dim3(256), 0, c->stream, (const int*)ls.left.get(), (const int*)ls.right.get(), (const int*)ls.depth.get(),
-                           ni - 1, level, sc.d_nodes.get());
-    RTGO_HIP(c, hipGetLastError());
-    float4 root[2];
-    RTGO_HIP(c, hipMemcpyAsync(root, sc.d_nodes.get(), sizeof root, hipMemcpyDeviceToHost, c->stream));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
     sc.d_prims_in.reset();   // (the records hold all the walk and the shading read)
-    const float b[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
-    std::memcpy(sc.bounds, b, sizeof sc.bounds);
-    sc.lbvh_depth = depth;
+    adopt_large_tree(sc, t);
+    sc.have_aabbs = aabbs != nullptr;
     sc.n_prims = n;
     sc.large = true;
     if (kn.debug)
-        std::fprintf(stderr, "rtgo_set_large_scene: %d primitives, canonical LBVH depth %d in global memory\n", ni, depth);
+        std::fprintf(stderr, "rtgo_set_large_scene: %d primitives, canonical LBVH depth %d in global memory\n", (int)n, sc.lbvh_depth);
+    return RTGO_OK;
+}
+
+// ---- rtgo_update_prims ----
+
+// the updates on the device: indices, primitives and (with boxes) boxes, n_updates of each
+struct UpdateStaging {
+    DeviceArray<unsigned int> idx;
+    DeviceArray<PrimIn> prims;
+    DeviceArray<float> aabbs;
+};
+static int stage_updates(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t k, UpdateStaging& st)
+{
+    static_assert(sizeof(PrimIn) == sizeof(rtgo_prim) && sizeof(rtgo_aabb) == 6 * sizeof(float), "update records");
+    RTGO_HIP(c, st.idx.upload(indices, k, c->stream));
+    RTGO_HIP(c, st.prims.upload(reinterpret_cast<const PrimIn*>(prims), k, c->stream));
+    if (aabbs) RTGO_HIP(c, st.aabbs.upload(reinterpret_cast<const float*>(aabbs), (size_t)k * 6, c->stream));
+    return RTGO_OK;
+}
+
+// A scene of rtgo_set_scene: a new scene from the old one's device-resident inputs with the updates patched in, built by build_resident
+// into c->scene (the caller has set the old one aside and puts it back when this fails)
+static int update_resident(rtgo_ctx* c, const AnalyticScene& old, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t k)
+{
+    const uint32_t n = old.n_prims;
+    AnalyticScene& sc = c->scene;
+    if (const int rc = alloc_resident(c, n)) return rc;
+    sc.host_prims = old.host_prims;
+    for (uint32_t j = 0; j < k; ++j) sc.host_prims[indices[j]] = prims[j];
+    sc.have_aabbs = old.have_aabbs;
+    UpdateStaging st;
+    if (const int rc = stage_updates(c, indices, prims, aabbs, k, st)) return rc;
+    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), old.d_prims_in.get(), n * sizeof(PrimIn), hipMemcpyDeviceToDevice, c->stream));
+    if (sc.have_aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), old.d_aabb.get(), (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    hipLaunchKernelGGL(prims_patch_kernel, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const PrimIn*)st.prims.get(),
+                       (const float*)st.aabbs.get(), (int)k, sc.d_prims_in.get(), sc.d_aabb.get());
+    RTGO_HIP(c, hipGetLastError());
+    const int rc = build_resident(c, n);
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));   // (the staging buffers are freed on return)
+    return rc;
+}
+
+// A scene of rtgo_set_large_scene, refitted or rebuilt in place
+static int update_large(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t k, bool rebuild)
+{
+    AnalyticScene& sc = c->scene;
+    const uint32_t n = sc.n_prims;
+    const int n_internal = (int)n - 1;
+    const dim3 g_upd((k + 255) / 256), g_int((std::max(n_internal, 1) + 255) / 256);
+    UpdateStaging st;
+    if (const int rc = stage_updates(c, indices, prims, aabbs, k, st)) return rc;
+    DeviceArray<int> d_changed;
+    RTGO_HIP(c, d_changed.alloc(1));
+    RTGO_HIP(c, hipMemsetAsync(d_changed.get(), 0, sizeof(int), c->stream));
+    if (!rebuild) {
+        if (++sc.keep.epoch == 0) {   // (the counter wrapped: start over with clean marks)
+            RTGO_HIP(c, hipMemsetAsync(sc.keep.mark.get(), 0, sc.keep.mark.size() * sizeof(unsigned int), c->stream));
+            sc.keep.epoch = 1;
+        }
+        const unsigned int epoch = sc.keep.epoch;
+        hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const PrimIn*)st.prims.get(),
+                           (const float*)st.aabbs.get(), (int)k, (const int*)sc.keep.leaf_of.get(), (const int*)sc.keep.parent.get(), epoch, sc.keep.mark.get(),
+                           sc.d_prims.get(), sc.d_aabb.get(), sc.d_nodes.get(), (float4*)nullptr, (float*)nullptr, d_changed.get());
+        RTGO_HIP(c, hipGetLastError());
+        int changed = 0;
+        RTGO_HIP(c, hipMemcpyAsync(&changed, d_changed.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        if (changed) {
+            // the marked ancestors, one level per launch from the deepest up (large_fit_kernel's rule: a kernel boundary between a node's
+            // children and the node); then the bounds from the new root
+            for (int level = sc.lbvh_depth - 1; level >= 0; --level)
+                hipLaunchKernelGGL(large_refit_kernel, g_int, dim3(256), 0, c->stream, (const int*)sc.keep.depth.get(), (const unsigned int*)sc.keep.mark.get(), epoch,
+                                   n_internal, level, sc.d_nodes.get());
+            RTGO_HIP(c, hipGetLastError());
+            float4 root[2];
+            RTGO_HIP(c, hipMemcpyAsync(root, sc.d_nodes.get(), sizeof root, hipMemcpyDeviceToHost, c->stream));
+            RTGO_HIP(c, hipStreamSynchronize(c->stream));
+            const float b[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
+            std::memcpy(sc.bounds, b, sizeof sc.bounds);
+        }
+        return RTGO_OK;
+    }
+    // rebuild: records and boxes patched (the old ones kept), then the set call's pipeline over the boxes into new arrays
+    DeviceArray<float4> old_prims;
+    DeviceArray<float> old_aabb;
+    RTGO_HIP(c, old_prims.alloc((size_t)k * 6));
+    RTGO_HIP(c, old_aabb.alloc((size_t)k * 6));
+    hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const PrimIn*)st.prims.get(),
+                       (const float*)st.aabbs.get(), (int)k, (const int*)nullptr, (const int*)nullptr, 0u, (unsigned int*)nullptr, sc.d_prims.get(), sc.d_aabb.get(),
+                       (float4*)nullptr, old_prims.get(), old_aabb.get(), d_changed.get());
+    RTGO_HIP(c, hipGetLastError());
+    LargeTree t;
+    if (const int rc = large_build_tree(c, sc.d_aabb.get(), n, "rtgo_update_prims", t)) {
+        const std::string msg = c->err;
+        hipLaunchKernelGGL(large_restore_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const float4*)old_prims.get(),
+                           (const float*)old_aabb.get(), (int)k, sc.d_prims.get(), sc.d_aabb.get());
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        c->err = msg;
+        return rc;
+    }
+    adopt_large_tree(sc, t);
+    return RTGO_OK;
+}
+
+int rtgo_update_prims(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n_updates, uint32_t flags)
+{
+    if (!c) return fail(c, RTGO_E_INVALID, "rtgo_update_prims: NULL context");
+    if (flags & ~(uint32_t)RTGO_UPDATE_REBUILD) return fail(c, RTGO_E_INVALID, "rtgo_update_prims: unknown flag bits");
+    const uint32_t n = c->scene.n_prims;
+    if (n == 0) return fail(c, RTGO_E_STATE, "rtgo_update_prims: no analytic scene (rtgo_set_scene or rtgo_set_large_scene first)");
+    if (n_updates == 0) return RTGO_OK;
+    if (!indices || !prims) return fail(c, RTGO_E_INVALID, "rtgo_update_prims: NULL argument");
+    if ((aabbs != nullptr) != c->scene.have_aabbs)
+        return fail(c, RTGO_E_INVALID, c->scene.have_aabbs ? "rtgo_update_prims: the scene was set with boxes, the updates need theirs"
+                                                           : "rtgo_update_prims: the scene was set without boxes, the updates cannot bring any");
+    std::vector<uint32_t> sorted(indices, indices + n_updates);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.back() >= n) return fail(c, RTGO_E_INVALID, "rtgo_update_prims: index " + std::to_string(sorted.back()) + " in a scene of " + std::to_string(n) + " primitives");
+    const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+    if (twice != sorted.end()) return fail(c, RTGO_E_INVALID, "rtgo_update_prims: index " + std::to_string(*twice) + " named twice");
+    if (const int rc = check_prims(c, prims, aabbs, n_updates, "rtgo_update_prims")) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->scene.large) {
+        if (const int rc = update_large(c, indices, prims, aabbs, n_updates, (flags & RTGO_UPDATE_REBUILD) != 0)) return rc;
+    } else {
+        // both flags: the set call's build again, into a scene of its own; the old one comes back when the build is refused
+        AnalyticScene old = std::move(c->scene);
+        c->scene = AnalyticScene();
+        if (const int rc = update_resident(c, old, indices, prims, aabbs, n_updates)) {
+            (void)hipStreamSynchronize(c->stream);
+            c->scene = std::move(old);
+            return rc;
+        }
+    }
+    // what was cached for the scene as it was (drop_scene's list): a primitive moved outside the old screen rectangle must not be culled
+    c->seeds = rtgo_ctx::Seeds();
+    c->mask.key.clear();
+    c->trial = rtgo_ctx::Trial();
     return RTGO_OK;
 }
 

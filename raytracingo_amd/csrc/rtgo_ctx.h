@@ -86,6 +86,17 @@ struct AnalyticScene {
     std::vector<Quadric> quadrics;
     DeviceArray<float> d_tight;            // the fast walk's box of every primitive (device), and its host copy
     std::vector<float> tight;
+    // ---- what rtgo_update_prims needs of the set call
+    bool have_aabbs = false;               // the caller gave boxes (else d_aabb holds the CubeBox rule's)
+    std::vector<rtgo_prim> host_prims;     // a scene of rtgo_set_scene: the primitives as last given (emitter_cert and the quadric list read them)
+    // a scene of rtgo_set_large_scene: the tree's shape, 20 bytes per primitive (the links are in the nodes themselves)
+    struct LargeKeep {
+        DeviceArray<int> parent;           // of each of the 2n-1 nodes; -1: the root
+        DeviceArray<int> depth;            // of each internal node
+        DeviceArray<int> leaf_of;          // each primitive's leaf node
+        DeviceArray<unsigned int> mark;    // per internal node: the refit that last changed a box below it (`epoch` then; 0: none)
+        unsigned int epoch = 0;
+    } keep;
 };
 
 // An instanced scene's top level (rtgo_whitted_set_instances replaces it alone)

@@ -10,6 +10,14 @@
 //   large_fit_kernel      one launch per tree level, deepest first: node box = fminf / fmaxf of its two children's, in build_kernel's
 //                         operand order.  The kernel boundary between two levels is what makes a child box written by another
 //                         workgroup (on another XCD's L2) visible to its parent's: no inter-workgroup hand-off inside a launch.
+// and the edit of such a scene in place (rtgo_update_prims), over what the build keeps on the device -- every node's
+// parent, the internal nodes' depths, each primitive's leaf node and a mark word per internal node:
+//   large_update_kernel   per update: the new record and box, with the functions large_prep_kernel calls; for a refit also the leaf node,
+//                         and a mark on every ancestor of a leaf whose box changed
+//   large_refit_kernel    large_fit_kernel over the marked nodes of one level (the links are read from the node itself): one launch
+//                         per level again, for the same reason
+//   large_restore_kernel  puts back the records and boxes large_update_kernel saved (a rebuild that is refused)
+//   prims_patch_kernel    a scene of rtgo_set_scene: the updates scattered into build_kernel's inputs
 #pragma once
 
 #include "rtgo_device.h"
@@ -63,11 +71,11 @@ __global__ __launch_bounds__(256) void large_karras_kernel(const unsigned long l
     parent[r] = i;
 }
 
-// node k of the 2n-1: its depth (internal nodes -> depth[k]); a leaf also writes its node record and raises *max_depth.  A chain longer
+// node k of the 2n-1: its depth (internal nodes -> depth[k]); a leaf also writes its node record, its primitive's leaf_of and raises *max_depth.  A chain longer
 // than kLargeMaxDepth stops counting there (the host refuses such a tree; the walk up cannot run away either).
 __global__ __launch_bounds__(256) void large_depth_kernel(const unsigned long long* __restrict__ keys, int n, const float* __restrict__ aabb,
                                                           const int* __restrict__ parent, int* __restrict__ depth, float4* __restrict__ nodes,
-                                                          int* __restrict__ max_depth)
+                                                          int* __restrict__ max_depth, int* __restrict__ leaf_of)
 {
     __shared__ int s_max;
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -83,6 +91,7 @@ __global__ __launch_bounds__(256) void large_depth_kernel(const unsigned long lo
             const float* b = aabb + 6 * (size_t)prim;
             nodes[2 * (size_t)k + 0] = make_float4(b[0], b[1], b[2], __int_as_float(prim));
             nodes[2 * (size_t)k + 1] = make_float4(b[3], b[4], b[5], __int_as_float(-1));
+            leaf_of[prim] = k;
             atomicMax(&s_max, d);
         }
     }
@@ -100,6 +109,86 @@ __global__ __launch_bounds__(256) void large_fit_kernel(const int* __restrict__ 
     const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
     nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
     nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+}
+
+// Update j: primitive idx[j] becomes upd[j], its box upd_aabb[j] (or, upd_aabb == nullptr, the CubeBox rule's).  The record and the box are
+// large_prep_kernel's bit for bit.  old_prims / old_aabb (nullable): what they replace, kept at j.  nodes (nullable: a rebuild writes its
+// leaves itself): the primitive's leaf is rewritten, and where the box changed bitwise *changed is set and every ancestor of the leaf is
+// marked with `epoch`.  A thread that finds an ancestor marked stops: whoever marked it first goes on to the root.  The indices are
+// distinct and below n (the host checked): no two threads write the same record.
+__global__ __launch_bounds__(256) void large_update_kernel(const unsigned int* __restrict__ idx, const PrimIn* __restrict__ upd,
+                                                           const float* __restrict__ upd_aabb, int k, const int* __restrict__ leaf_of,
+                                                           const int* __restrict__ parent, unsigned int epoch, unsigned int* __restrict__ mark,
+                                                           float4* __restrict__ out_prims, float* __restrict__ aabb, float4* __restrict__ nodes,
+                                                           float4* __restrict__ old_prims, float* __restrict__ old_aabb, int* __restrict__ changed)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= k) return;
+    const size_t i = idx[j];
+    const PrimIn P = upd[j];
+    if (old_prims) {
+        for (int q = 0; q < 6; ++q) old_prims[6 * (size_t)j + q] = out_prims[6 * i + q];
+        for (int a = 0; a < 6; ++a) old_aabb[6 * (size_t)j + a] = aabb[6 * i + a];
+    }
+    float inv[12];
+    inverse_rows012(P.M, inv);
+    store_prim_record(out_prims + 6 * i, P, inv);
+    float bb[6];
+    if (upd_aabb) {
+        for (int a = 0; a < 6; ++a) bb[a] = upd_aabb[6 * (size_t)j + a];
+    } else {
+        cube_aabb(P.M, bb);
+    }
+    bool moved = false;
+    for (int a = 0; a < 6; ++a) {
+        moved = moved || __float_as_uint(bb[a]) != __float_as_uint(aabb[6 * i + a]);
+        aabb[6 * i + a] = bb[a];
+    }
+    if (!nodes) return;
+    const int leaf = leaf_of[i];
+    nodes[2 * (size_t)leaf + 0] = make_float4(bb[0], bb[1], bb[2], __int_as_float((int)i));
+    nodes[2 * (size_t)leaf + 1] = make_float4(bb[3], bb[4], bb[5], __int_as_float(-1));
+    if (!moved) return;
+    *changed = 1;
+    int q = parent[leaf];
+    for (int d = 0; q >= 0 && d <= kLargeMaxDepth; ++d) {   // (a chain is at most kLargeMaxDepth long: the build refused deeper trees)
+        if (atomicExch(&mark[q], epoch) == epoch) break;
+        q = parent[q];
+    }
+}
+
+// the marked internal nodes at depth `level`: large_fit_kernel's box, from children an earlier launch (or large_update_kernel) wrote
+__global__ __launch_bounds__(256) void large_refit_kernel(const int* __restrict__ depth, const unsigned int* __restrict__ mark, unsigned int epoch,
+                                                          int n_internal, int level, float4* __restrict__ nodes)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_internal || mark[i] != epoch || depth[i] != level) return;
+    const int L = __float_as_int(nodes[2 * (size_t)i].w), R = __float_as_int(nodes[2 * (size_t)i + 1].w);
+    const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
+    nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
+    nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+}
+
+__global__ __launch_bounds__(256) void large_restore_kernel(const unsigned int* __restrict__ idx, const float4* __restrict__ old_prims,
+                                                            const float* __restrict__ old_aabb, int k, float4* __restrict__ out_prims,
+                                                            float* __restrict__ aabb)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= k) return;
+    const size_t i = idx[j];
+    for (int q = 0; q < 6; ++q) out_prims[6 * i + q] = old_prims[6 * (size_t)j + q];
+    for (int a = 0; a < 6; ++a) aabb[6 * i + a] = old_aabb[6 * (size_t)j + a];
+}
+
+// a scene of rtgo_set_scene: update j goes into build_kernel's inputs at idx[j] (upd_aabb == nullptr: the build derives the boxes)
+__global__ __launch_bounds__(256) void prims_patch_kernel(const unsigned int* __restrict__ idx, const PrimIn* __restrict__ upd,
+                                                          const float* __restrict__ upd_aabb, int k, PrimIn* __restrict__ prims, float* __restrict__ aabb)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= k) return;
+    const size_t i = idx[j];
+    prims[i] = upd[j];
+    for (int a = 0; upd_aabb && a < 6; ++a) aabb[6 * i + a] = upd_aabb[6 * (size_t)j + a];
 }
 
 }  // namespace rtgo

@@ -266,6 +266,12 @@ int rtgo_host_session_pick(rtgo_host_session* s, uint32_t x, uint32_t y, int32_t
     })
 }
 
+int rtgo_host_session_update_prims(rtgo_host_session* s, const uint32_t* indices, const rtgo_prim* prims, uint32_t n)
+{
+    if (!s || (n > 0 && (!indices || !prims))) return RTGO_E_INVALID;
+    RTGO_SESSION_TRY(s->renderer->UpdatePrimitives(indices, prims, n))
+}
+
 int rtgo_host_session_camera(rtgo_host_session* s, float eye[3], float U[3], float V[3], float W[3])
 {
     if (!s || !eye || !U || !V || !W) return RTGO_E_INVALID;

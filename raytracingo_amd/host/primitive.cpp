@@ -17,7 +17,9 @@ Primitive::Primitive(PRIMITIVE_TYPE type, const sutil::Matrix4x4& modelMatrix, c
 
 void Primitive::Transform(const sutil::Matrix4x4& transform) { m_modelMatrix = transform * m_modelMatrix; }
 
-rtgo_aabb Primitive::GetAabb() const
+rtgo_aabb Primitive::GetAabb() const { return AabbOf(m_modelMatrix.getData()); }
+
+rtgo_aabb Primitive::AabbOf(const float model[16])
 {
     // The reference pushes the corners of the unit cube through two 4x4 products (one per y face) and scans the
     // columns; corner i of a face is (sx[i], y, sz[i]).  Each coordinate is the 4-term sum seeded with 0.0f.
@@ -26,7 +28,7 @@ rtgo_aabb Primitive::GetAabb() const
     float hi[3] = {-kSceneMaxBound, -kSceneMaxBound, -kSceneMaxBound};
     for (int i = 0; i < 4; ++i)
         for (int axis = 0; axis < 3; ++axis) {
-            const float* row = m_modelMatrix.getData() + 4 * axis;
+            const float* row = model + 4 * axis;
             float below = 0.0f, above = 0.0f;  // y = -1 face, y = +1 face
             const float c[2][4] = {{sx[i], -1.f, sz[i], 1.f}, {sx[i], 1.f, sz[i], 1.f}};
             for (int k = 0; k < 4; ++k) {

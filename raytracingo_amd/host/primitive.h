@@ -22,6 +22,8 @@ public:
     void Transform(const sutil::Matrix4x4& transform);
     /// World-space box of the transformed [-1,1]^3 cube, clipped-seeded at +-50 and padded by 1e-3
     rtgo_aabb GetAabb() const;
+    /// GetAabb of a primitive under this row-major model matrix (what Renderer::UpdatePrimitives gives an edited record)
+    static rtgo_aabb AabbOf(const float model[16]);
     /// Name of the OptiX intersection program the reference binds; kept for source compatibility
     const char* GetIntersectionProgram() const { return m_intersectionProgram.c_str(); }
     sutil::Matrix4x4 GetModelMatrix() const { return m_modelMatrix; }

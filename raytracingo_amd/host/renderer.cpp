@@ -12,7 +12,7 @@ namespace host {
 
 Renderer::Renderer(std::shared_ptr<Scene> scene, RenderMode renderMode, int sqrtSamplePerPixel, bool useAmbientCoeff)
     : m_scene(scene), m_renderMode(renderMode), m_useAmbientCoefficient(useAmbientCoeff), m_sqrtSamplePerPixel(sqrtSamplePerPixel),
-      m_context(nullptr), m_params(), m_pickBuffer(nullptr), m_firstLaunch(true), m_cameraChangedFlag(false), m_windowResizeFlag(false), m_frames(1),
+      m_context(nullptr), m_params(), m_pickBuffer(nullptr), m_firstLaunch(true), m_cameraChangedFlag(false), m_windowResizeFlag(false), m_sceneChangedFlag(false), m_frames(1),
       m_framesPerLaunch(1), m_device(0)
 {
 }
@@ -114,9 +114,10 @@ void Renderer::WriteLights()
 
 void Renderer::Update()
 {
-    // frame counter rule of renderer.cpp:682: any camera change or resize restarts the running average
-    m_params.frame_count = (m_cameraChangedFlag || m_windowResizeFlag || m_firstLaunch) ? 0 : m_params.frame_count + 1;
+    // frame counter rule of renderer.cpp:682: any camera change or resize restarts the running average (and so does an edited scene)
+    m_params.frame_count = (m_cameraChangedFlag || m_windowResizeFlag || m_sceneChangedFlag || m_firstLaunch) ? 0 : m_params.frame_count + 1;
     m_firstLaunch = false;
+    m_sceneChangedFlag = false;
     UpdateCamera();
     ResizeBuffers();
 }
@@ -190,6 +191,17 @@ void Renderer::Pick(unsigned int x, unsigned int y, int& prim, float& t)
     gpu::CopyDeviceToHost(&hit, d_hit, sizeof hit);
     prim = hit.prim;
     t = hit.t;
+}
+
+void Renderer::UpdatePrimitives(const uint32_t* indices, const rtgo_prim* prims, uint32_t n, bool rebuild)
+{
+    if (!m_context) Initialize();
+    if (n > 0 && (!indices || !prims)) throw std::invalid_argument("Renderer::UpdatePrimitives: NULL argument");
+    // (CreateShapes gave the scene boxes: the updates bring theirs, by the same rule)
+    std::vector<rtgo_aabb> boxes(n);
+    for (uint32_t j = 0; j < n; ++j) boxes[j] = Primitive::AabbOf(prims[j].model);
+    Check(rtgo_update_prims(m_context, indices, prims, boxes.data(), n, rebuild ? RTGO_UPDATE_REBUILD : RTGO_UPDATE_REFIT), "rtgo_update_prims");
+    if (n > 0) m_sceneChangedFlag = true;
 }
 
 void Renderer::LaunchFrame()

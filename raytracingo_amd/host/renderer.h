@@ -49,6 +49,10 @@ public:
     /// of the current camera, dir = normalize((2 (x + .5) / width - 1) U + (2 (y + .5) / height - 1) V + W), tmin 1e-3, tmax 1e16,
     /// traced with rtgo_trace_rays.  Synchronous; does not touch the frame loop's state.  A miss gives prim -1 and t = tmax.
     void Pick(unsigned int x, unsigned int y, int& prim, float& t);
+    /// Primitive indices[j] (an SBT index) becomes prims[j], its box Primitive::AabbOf of its model matrix, through rtgo_update_prims
+    /// (a refit; rebuild: RTGO_UPDATE_REBUILD).  No reference counterpart: the reference builds once.  The next frame restarts the
+    /// accumulation at frameCount 0, as after MoveCamera; Pick answers over the edited scene at once.
+    void UpdatePrimitives(const uint32_t* indices, const rtgo_prim* prims, uint32_t n, bool rebuild = false);
     unsigned int Width() const { return m_params.image_width; }
     unsigned int Height() const { return m_params.image_height; }
     unsigned int FrameCount() const { return m_params.frame_count; }
@@ -72,6 +76,7 @@ private:
     bool m_firstLaunch;
     bool m_cameraChangedFlag;   // RendererState::cameraChangedFlag
     bool m_windowResizeFlag;    // RendererState::windowResizeFlag
+    bool m_sceneChangedFlag;    // UpdatePrimitives edited the scene since the last frame (no reference counterpart)
     int m_frames;
     int m_framesPerLaunch;
     int m_device;

@@ -158,6 +158,7 @@ class Session:
         L.rtgo_host_session_close.argtypes = [C.c_void_p]
         L.rtgo_host_session_pick.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
         L.rtgo_host_session_camera.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 4
+        L.rtgo_host_session_update_prims.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(capi.Prim), C.c_uint32]
         self._L = L
         self._h = C.c_void_p()
         self.width, self.height = width, height
@@ -190,6 +191,16 @@ class Session:
         prim, t = C.c_int32(0), C.c_float(0.0)
         self._ok(self._L.rtgo_host_session_pick(self._h, x, y, C.byref(prim), C.byref(t)))
         return int(prim.value), np.float32(t.value)
+
+    def update_prims(self, indices, types, models, materials):
+        """primitive indices[j] becomes (types[j], models[j], materials[j]), as Context.update_prims takes them; the host computes the boxes"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        rec = np.zeros(len(idx), dtype=capi.PRIM_DTYPE)
+        rec["type"] = np.asarray(types).astype(np.uint32).reshape(-1)
+        rec["model"] = np.asarray(models, dtype=np.float32).reshape(-1, 16)
+        mat = np.asarray(materials, dtype=np.float32).reshape(-1, 10)
+        rec["kd"], rec["kr"], rec["specularity"], rec["Le"] = mat[:, 0:3], mat[:, 3:6], mat[:, 6], mat[:, 7:10]
+        self._ok(self._L.rtgo_host_session_update_prims(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), rec.ctypes.data_as(C.POINTER(capi.Prim)), len(idx)))
 
     def camera(self):
         """eye, U, V, W (float32 [3] each) of the session's current camera"""

@@ -1,0 +1,133 @@
+"""developer tool: what rtgo_update_prims costs and what a refit does to the walk, against setting the scene again
+   python tools/update_prims_perf.py [W] [H]
+Sphere fields of tools/large_scene_perf.py (one sphere of radius <= 0.3 per unit cube) of n = 1K, 256K and 2^20 primitives, boxes by the
+CubeBox rule on the device.
+1. Per n and k = 1, 1 % of n, n: k spheres (evenly spaced indices) nudged by up to a radius, back and forth between two positions.
+      set      ms of rtgo_set_large_scene over the edited array (the yardstick: the only way to edit before rtgo_update_prims)
+      refit    ms of rtgo_update_prims(RTGO_UPDATE_REFIT) over the k records
+      rebuild  ms of rtgo_update_prims(RTGO_UPDATE_REBUILD) over the k records
+   All three are WALL-CLOCK times of the synchronous C call on records packed beforehand (no Python packing inside), medians of REPS calls
+   after WARM.
+2. Per n: a fraction of the spheres scattered to random places of the field by a refit, then the same scene rebuilt: ms per frame at W x H,
+   path mode, 1 spp -- HIP-EVENT times (rtgo_stats' total_launch_ms over K launches).  The fractions grow tenfold and stop once a refitted
+   frame takes over 30 ms: a refit keeps the topology chosen for the old places, every ancestor of a scattered leaf spans the way it went,
+   and the walk pays for it.  refit/rebuilt is that price."""
+import ctypes as C
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+from raytracingo_amd import capi, scene as hscene
+
+W = int(sys.argv[1]) if len(sys.argv) > 1 else 1280
+H = int(sys.argv[2]) if len(sys.argv) > 2 else 720
+WARM, REPS, K = 2, 9, 8
+
+
+def field(n):
+    rng = np.random.default_rng(n)
+    side = 2.0 * round(n ** (1.0 / 3.0)) / 2.0
+    rec = np.zeros(n, dtype=capi.PRIM_DTYPE)
+    rec["type"] = capi.SPHERE
+    M = rec["model"]
+    r = rng.uniform(0.05, 0.3, size=n)
+    M[:, 0] = M[:, 5] = M[:, 10] = r
+    M[:, 3] = rng.uniform(-side / 2, side / 2, size=n)
+    M[:, 7] = rng.uniform(-side / 2, side / 2, size=n)
+    M[:, 11] = rng.uniform(-side, 0.0, size=n) - 2.0
+    M[:, 15] = 1.0
+    mat = rng.uniform(0.0, 1.0, size=(n, 10)).astype(np.float32)
+    mat[:, 7:10] *= (rng.uniform(size=(n, 1)) < 0.02) * 4.0
+    rec["kd"], rec["kr"], rec["specularity"], rec["Le"] = mat[:, 0:3], mat[:, 3:6], mat[:, 6], mat[:, 7:10]
+    return rec, side
+
+
+def median_ms(call):
+    for _ in range(WARM):
+        call(0)
+    ts = []
+    for k in range(REPS):
+        t0 = time.perf_counter()
+        call(k + 1)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def c_set(L, ctx, rec):
+    rc = L.rtgo_set_large_scene(ctx._h, rec.ctypes.data_as(C.POINTER(capi.Prim)), None, len(rec))
+    assert rc == 0, L.rtgo_last_error(ctx._h)
+    ctx.n_prims = len(rec)
+
+
+def c_update(L, ctx, idx, rec, flags):
+    rc = L.rtgo_update_prims(ctx._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), rec.ctypes.data_as(C.POINTER(capi.Prim)), None, len(idx), flags)
+    assert rc == 0, L.rtgo_last_error(ctx._h)
+
+
+def frame_ms(ctx):
+    for f in range(2):
+        ctx.launch(capi.make_frame(W, H, 1, f, True))
+        ctx.sync()
+    ctx.reset_stats()
+    for f in range(K):
+        ctx.launch(capi.make_frame(W, H, 1, 2 + f, True))
+    ctx.sync()
+    return ctx.stats()["total_launch_ms"] / K
+
+
+L = capi.load()
+t = hscene.tables("cornell", W, H)
+print("rtgo_update_prims, sphere fields, medians of %d calls after %d (wall clock of the synchronous C call); frames %d x %d path 1 spp, HIP events over %d launches" %
+      (REPS, WARM, W, H, K), flush=True)
+for n in (1 << 10, 1 << 18, 1 << 20):
+    rec, side = field(n)
+    ctx = capi.Context(0)
+    c_set(L, ctx, rec)
+    ctx.set_camera(t["cam"][0:3], t["cam"][3:6], t["cam"][6:9], t["cam"][9:12])
+    ctx.set_background(t["bg"])
+    ctx.set_lights(t["lights"])
+    ctx.resize(W * H)
+    depth = ctx.stats()["lbvh_depth"]
+    print("n = %d  LBVH depth %d  as built %.3f ms/frame" % (n, depth, frame_ms(ctx)), flush=True)
+    for k in sorted({1, max(n // 100, 1), n}):
+        idx = np.ascontiguousarray(np.linspace(0, n - 1, k).astype(np.uint32))
+        there = rec[idx].copy()
+        there["model"][:, 3] += there["model"][:, 0]
+        edits = [there, rec[idx].copy()]     # the calls alternate between the two: every one moves k boxes
+        whole = [rec.copy(), rec]
+        whole[0][idx] = there
+        c_set(L, ctx, rec)
+        t_refit = median_ms(lambda j: c_update(L, ctx, idx, edits[j % 2], capi.UPDATE_REFIT))
+        c_set(L, ctx, rec)
+        t_rebuild = median_ms(lambda j: c_update(L, ctx, idx, edits[j % 2], capi.UPDATE_REBUILD))
+        t_set = median_ms(lambda j: c_set(L, ctx, whole[j % 2]))
+        print("    k = %-8d set %8.3f ms   refit %8.3f ms   rebuild %8.3f ms   set/refit %6.1fx   set/rebuild %5.2fx" %
+              (k, t_set, t_refit, t_rebuild, t_set / t_refit, t_set / t_rebuild), flush=True)
+    frac, last_k = 1e-4, 0
+    while frac <= 0.011:
+        k = max(int(n * frac), 1)
+        if k == last_k:
+            frac *= 10.0
+            continue
+        last_k = k
+        rng = np.random.default_rng(k)
+        idx = np.ascontiguousarray(rng.choice(n, size=k, replace=False).astype(np.uint32))
+        far = rec[idx].copy()
+        far["model"][:, 3] = rng.uniform(-side / 2, side / 2, size=k)
+        far["model"][:, 7] = rng.uniform(-side / 2, side / 2, size=k)
+        far["model"][:, 11] = rng.uniform(-side, 0.0, size=k) - 2.0
+        c_set(L, ctx, rec)
+        c_update(L, ctx, idx, far, capi.UPDATE_REFIT)
+        refit = frame_ms(ctx)
+        c_update(L, ctx, idx, far, capi.UPDATE_REBUILD)
+        rebuilt = frame_ms(ctx)
+        print("    %7d scattered (%.2f %%): refitted %9.3f ms/frame   rebuilt %8.3f ms/frame   refit/rebuilt %6.2f   depth %d / %d" %
+              (k, 100.0 * k / n, refit, rebuilt, refit / rebuilt, depth, ctx.stats()["lbvh_depth"]), flush=True)
+        if refit > 30.0:
+            print("    (a refitted frame took over 30 ms: larger fractions not run)", flush=True)
+            break
+        frac *= 10.0
+    ctx.close()
