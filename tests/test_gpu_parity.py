@@ -883,11 +883,12 @@ def test_rays_with_an_exactly_zero_direction_component(capi, oracle, name):
     ctx.close()
 
 
-def _cuboid_scene(oracle, W, H, variant):
+def _cuboid_scene(oracle, W, H, variant, turns=(0.4, -0.3)):
     """a closed room of six inward-facing walls (three pairs: the up-front list) holding two boxes of six rectangles each.
     variant "good": both are cuboids; "wide_face": one face of the second box is 1.5 x too wide (it sticks out past its neighbours:
     the point where a ray meets its plane can be beyond another face's plane and still inside the face); "sheared": the second box is
-    a parallelepiped (still the image of the unit cube); "inside_out": its six faces look into it"""
+    a parallelepiped (still the image of the unit cube); "inside_out": its six faces look into it.  turns: the two boxes' angles about
+    the vertical (0, 0: axis-aligned boxes)"""
     L = oracle.lib()
     f = oracle.fptr
 
@@ -923,8 +924,8 @@ def _cuboid_scene(oracle, W, H, variant):
     add(mul(mat("translate", 0, 0, 6), mat("rotate", -hp, 1, 0, 0), mat("scale", 12, 1, 8)))
     light = mul(mat("translate", 0, 3.9, 0), mat("rotate", np.pi, 1, 0, 0), mat("scale", 3, 1, 3))
     add(light, kd=(0, 0, 0), kr=0, Le=6.0)
-    box_a = mul(mat("translate", -2.2, -2.5, 0.5), mat("rotate", 0.4, 0, 1, 0), mat("scale", 2.5, 3.0, 2.5))
-    box_b = mul(mat("translate", 2.0, -3.0, -1.0), mat("rotate", -0.3, 0, 1, 0), mat("scale", 2.0, 2.0, 2.0))
+    box_a = mul(mat("translate", -2.2, -2.5, 0.5), mat("rotate", turns[0], 0, 1, 0), mat("scale", 2.5, 3.0, 2.5))
+    box_b = mul(mat("translate", 2.0, -3.0, -1.0), mat("rotate", turns[1], 0, 1, 0), mat("scale", 2.0, 2.0, 2.0))
     if variant == "sheared":
         shear = np.eye(4, dtype=np.float32)
         shear[0, 1] = 0.35
