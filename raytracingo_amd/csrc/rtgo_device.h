@@ -26,6 +26,8 @@ constexpr int kSampleTab = 256;     // samples per pixel whose start (LCG skip, 
 constexpr int kCamWords = 16;        // raygen constants in LDS (render_kernel's s_cam) ...
 constexpr int kCamWordsLean = 20;    // ... + the launch's two reciprocals in the 6-waves variant (a multiple of 4: s_tab follows)
 constexpr int kMaxLevels = 5;        // bounce records kept per path (maxTraceDepth <= 5)
+// path mode, the deferred fold (FOLDLATE, rtgo_render_body.inc): what an ended path's payload is, where it is no emitter's primitive index
+constexpr int kEndsInBackground = -1, kEndsInZero = -2;
 constexpr int kMaxEmitters = 4;      // emitters of the last-ray certificate (LaunchParams::emit_n); scenes with more go without it
 // the pair kernels' scene (fast_pair: a root over two cuboid leaves of six records each), which their launches vouch for: the tree's
 // nodes and its records.  Compile-time values there, so that the up-front list -- the records from kPairSmall on, in LDS and in global

@@ -19,6 +19,7 @@ struct Timeline {
     unsigned long long a = 0, b = 0, c = 0, d = 0, big = 0, tree = 0, loop = 0;
     unsigned long long s_regen = 0, s_trace = 0, s_shade = 0, s_lanes_trace = 0, s_lanes_regen = 0, s_regens = 0;   // streaming loop
     unsigned int units = 0, iters = 0;
+    unsigned int fold_turns = 0, fold_entries = 0, fold_lane_turns = 0;   // the level-record fold of paths that end before their pass's last iteration
     unsigned long long m0 = 0, m1 = 0, m3 = 0, mw = 0;   // the marks an interval is measured from (mw: inside closest_hit_fast)
 
     __device__ __forceinline__ void kernel_start() { t0 = wall_clock64(); }
@@ -46,6 +47,19 @@ struct Timeline {
     // (pinned behind the lane's LCG state, which shading advances, so the interval may end before the iteration's last payload write:
     // a read of the payload there changes the product kernel's instruction order)
     __device__ __forceinline__ void iter_end(unsigned int seed) { loop += clock_after(seed) - m0; }
+    // (lock-step loop, after an iteration; `ended`: the lane's path ended in it, after `depth` bounces.)  What a fold inside the loop costs
+    // a wave in an iteration that leaves lanes running: a divergent loop of as many turns as the deepest ended path has level records,
+    // entered once.  Counted from the paths, so the census reads the same whether the kernel folds there or after the loop.
+    __device__ __forceinline__ void iter_ended(bool ended, bool active, int depth)
+    {
+        if (__ballot(active) == 0ull) return;   // the pass's last iteration: every remaining lane folds
+        if (__ballot(ended && depth > 0) != 0ull) fold_entries += 1;
+        for (int k = 1; k <= kMaxLevels; ++k) {
+            const unsigned long long m = __ballot(ended && depth >= k);
+            if (m != 0ull) fold_turns += 1;
+            fold_lane_turns += (unsigned int)__popcll(m);
+        }
+    }
     // closest_hit_fast: the up-front list, then the tree or grid walk
     __device__ __forceinline__ void walk_begin() { mw = wall_clock64(); }
     __device__ __forceinline__ void list_done(int best_pos)
@@ -92,6 +106,7 @@ struct Timeline {
         }
         r[0] = t0; r[1] = t1; r[2] = first; r[3] = wall_clock64(); r[4] = units | ((unsigned long long)hot << 32); r[5] = iters; r[6] = lanes;
         r[7] = qwait | ((cold ? cold - t0 : 0ull) << 32);
+        if constexpr (!STREAM) r[15] = (unsigned long long)(fold_turns & 0xFFFFu) | ((unsigned long long)(fold_entries & 0xFFFFu) << 16) | ((unsigned long long)fold_lane_turns << 32);
     }
 };
 #else
@@ -105,6 +120,7 @@ struct Timeline {
     __device__ __forceinline__ void unit_begin(unsigned int, bool) {}
     __device__ __forceinline__ void iter_begin(bool) {}
     __device__ __forceinline__ void iter_end(unsigned int) {}
+    __device__ __forceinline__ void iter_ended(bool, bool, int) {}
     __device__ __forceinline__ void walk_begin() {}
     __device__ __forceinline__ void list_done(int) {}
     __device__ __forceinline__ void walk_done(int) {}

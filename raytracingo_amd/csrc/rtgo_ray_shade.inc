@@ -1,15 +1,17 @@
 // rtgo_ray_shade.inc -- the shading half of one ray of one lane's path: the state machine that replaces the recursion of
 // __closesthit__ch / __miss__ms / __closesthit__full_occlusion (kernel.cu:419-549), from the `hit` and `h` rtgo_ray_trace.inc left
 // (the streaming loop may run it later than the trace, for several lanes at once).  A textual fragment, not a function: it works on the
-// per-sample state of the enclosing scope -- active, depth, phase, seed, ro, rd, tmin, tmax, result, any_hit, lvA / lvPrim (or the LDS
-// records s_lv), sN, sRr, sDist, sPrim, sLight -- which has to stay in registers (a lambda capturing the level arrays by reference put
-// them in scratch).
+// per-sample state of the enclosing scope -- active, depth, phase, seed, ro, rd, tmin, tmax, result (FOLDLATE: ended_in), any_hit, lvA /
+// lvPrim (or the LDS records s_lv), sN, sRr, sDist, sPrim, sLight -- which has to stay in registers (a lambda capturing the level arrays
+// by reference put them in scratch).
                 bool done = false;       // path ended: `term` is the payload of the ray at level `depth`
                 v3 term = mk(0, 0, 0);
+                int ends_in = kEndsInZero;   // FOLDLATE: which payload that is
 
                 if (PATH) {
                     if (!hit) {
                         term = p.bg;  // __miss__ms, kernel.cu:419-423
+                        ends_in = kEndsInBackground;
                         done = true;
                     } else {
                         // __closesthit__ch, path branch: kernel.cu:426-475
@@ -39,6 +41,7 @@
                         }
                         if (m5.x > 0.01f) {
                             term = mk(m5.x, m5.y, m5.z);
+                            ends_in = h.prim;
                             done = true;
                         } else if (depth < p.max_depth) {
                             const v3 Ra = hemisphere<true>(N, N, 0.0f, seed, FRAMES, Xf);
@@ -161,7 +164,10 @@
 
                 if (done) {
                     // fold the level records innermost-first: kernel.cu:471-472 (path), :504,519,531 (distributed)
-                    if constexpr (LVLDS) {
+                    if constexpr (FOLDLATE) {
+                        // (the pair kernels' lock-step loop looks the payload up and folds after the loop, all lanes together: rtgo_render_body.inc)
+                        ended_in = ends_in;
+                    } else if constexpr (LVLDS) {
                         for (int k = depth - 1; k >= 0; --k) {
                             const v3 a = mk(s_lv[(k * LVW + 0) << bshift], s_lv[(k * LVW + 1) << bshift], s_lv[(k * LVW + 2) << bshift]);
                             if (PATH) {
@@ -187,6 +193,6 @@
                             }
                         }
                     }
-                    result = term;
+                    if constexpr (!FOLDLATE) result = term;
                     active = false;
                 }

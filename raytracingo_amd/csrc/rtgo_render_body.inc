@@ -31,6 +31,13 @@
     constexpr bool LVLDS = (WPE >= 5) || (BATCH && !PATH);
     constexpr bool SHLDS = BATCH && !PATH && WPE >= 5;
     constexpr int LVW = PATH ? 3 : 4;   // words per level record: the weight (path) / the term and the primitive (distributed)
+    // the pair kernels' lock-step loop folds a path's level records once, after the ray loop, for all 64 lanes together -- in the loop
+    // the fold is a divergent loop that runs for the lane or two whose path has just ended (a ray that reaches the emitter), at a whole
+    // issue slot per instruction.  Until then an ended lane keeps one word, `ended_in`, in place of the payload: in path mode a finished
+    // path's payload is the background colour, the Le row of the emitter it hit, or zero (the depth limit), and nothing touches the lane's
+    // depth and LDS records while it is inactive.  The same multiplications in the same order: the same bits.
+    constexpr bool FOLDLATE = PAIR;
+    static_assert(!FOLDLATE || (PATH && LVLDS && !STREAM && !BATCH), "the deferred fold is the path-mode fold over LDS records, in the lock-step loop");
     // raygen constants (eye, U, V, W, image size, sample step): read from LDS where a sample starts, instead of sitting in
     // registers through the ray loop
     float* s_cam = reinterpret_cast<float*>(s_lights + kMaxLights);
@@ -245,6 +252,7 @@
         // per-level records, folded innermost-first when the path ends (SURVEY Appendix B)
         v3 lvA[kMaxLevels];            // PATH: w_k = dot(N,Ra)*kd ; distributed: a_k = falloff*diffuse
         int lvPrim[kMaxLevels];        // distributed: primitive of level k (kr, kd re-read at fold time)
+        int ended_in = kEndsInZero;    // FOLDLATE: the payload of an ended path, as one word (kEndsIn*, or the emitter's primitive)
         // distributed: state kept across the shadow ray
         v3 sN_r, sRr_r;
         float sDist_r;
@@ -257,11 +265,26 @@
         tl.unit_begin(ui, strip < p.n_hot);
         while (__ballot(active) != 0ull) {
             tl.iter_begin(active);
+            const bool was_active = active;
             if (active) {
 #include "rtgo_ray_trace.inc"
 #include "rtgo_ray_shade.inc"
             }
             tl.iter_end(seed);
+            tl.iter_ended(was_active && !active, active, depth);
+        }
+        if constexpr (FOLDLATE) {
+            // the fold the ray loop left out (rtgo_ray_shade.inc): a lane that never started has depth 0 and kEndsInZero, its payload stays 0
+            v3 term = mk(0.0f, 0.0f, 0.0f);
+            if (ended_in == kEndsInBackground) {
+                term = params_here<LEAN>(p_arg).bg;
+            } else if (ended_in >= 0) {
+                const float4 m5 = s_mat[MS * ended_in + 2];
+                term = mk(m5.x, m5.y, m5.z);
+            }
+            for (int k = depth - 1; k >= 0; --k)
+                term = vmul(mk(s_lv[(k * LVW + 0) << bshift], s_lv[(k * LVW + 1) << bshift], s_lv[(k * LVW + 2) << bshift]), term);
+            result = term;
         }
         // color += payload, in sample order (kernel.cu:232): every lane of a pixel's group walks the group's results
         {
@@ -309,6 +332,7 @@
         // per-level records, folded innermost-first when the path ends (SURVEY Appendix B)
         v3 lvA[kMaxLevels];            // PATH: w_k = dot(N,Ra)*kd ; distributed: a_k = falloff*diffuse
         int lvPrim[kMaxLevels];        // distributed: primitive of level k (kr, kd re-read at fold time)
+        int ended_in = kEndsInZero;    // FOLDLATE: the payload of an ended path, as one word (kEndsIn*, or the emitter's primitive)
         // distributed: state kept across the shadow ray
         v3 sN, sRr;
         float sDist;

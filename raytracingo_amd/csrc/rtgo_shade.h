@@ -50,6 +50,7 @@ __global__ __launch_bounds__(kMaxBlock) void shade_rays_kernel(const ShadeParams
     constexpr int MS = 6;
     constexpr bool FRAMES = false;      // (the per-hit frame: the same bits as the precomputed one, and no frame table to stage)
     constexpr bool LVLDS = false;
+    constexpr bool FOLDLATE = false;    // (a path folds its level records where it ends)
     constexpr int LVW = PATH ? 3 : 4;
     const int tid = (int)threadIdx.x, block = (int)blockDim.x;
     float4* s_scene = reinterpret_cast<float4*>(sh_smem);
@@ -94,6 +95,7 @@ __global__ __launch_bounds__(kMaxBlock) void shade_rays_kernel(const ShadeParams
         v3 result = mk(0.0f, 0.0f, 0.0f);
         v3 lvA[kMaxLevels];
         int lvPrim[kMaxLevels];
+        int ended_in = kEndsInZero;    // (FOLDLATE alone reads it)
 #pragma unroll
         for (int q = 0; q < kMaxLevels; ++q) {
             lvA[q] = mk(0, 0, 0);

@@ -53,6 +53,10 @@ print("queue wait / wave [us]  " + pc(qwait))
 print("ray iterations per wave " + pc(iters))
 print("waves with no unit: %d; total units %d; iterations/unit %.2f; live lanes/iteration %.1f of 64" %
       ((units == 0).sum(), units.sum(), iters.sum() / max(units.sum(), 1), lanes.sum() / max(iters.sum(), 1)))
+# the level-record fold of paths that end before their pass's last iteration (Timeline::iter_ended; lock-step launches)
+f_turns, f_entries, f_lanes = (r[:, 15] & 0xFFFF).sum(), ((r[:, 15] >> 16) & 0xFFFF).sum(), (r[:, 15] >> 32).sum()
+print("early folds (a path ends, others run on): %.2f loop entries and %.2f turns per unit; %.2f lanes live per turn" %
+      (f_entries / max(units.sum(), 1), f_turns / max(units.sum(), 1), f_lanes / max(f_turns, 1)))
 big, tree, loop = r[:, 12].sum(), r[:, 13].sum(), r[:, 14].sum()
 if loop > 0:
     print("ray-loop time: up-front list %.1f %%, tree walk %.1f %%, shading + bookkeeping %.1f %%; per iteration %.2f us" % (100.0 * big / loop, 100.0 * tree / loop, 100.0 * (loop - big - tree) / loop, us(loop) / max(iters.sum(), 1)))
