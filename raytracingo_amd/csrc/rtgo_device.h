@@ -529,12 +529,75 @@ __device__ __forceinline__ unsigned int wave_sum(unsigned int v)
     return v;
 }
 
+// A predicate of the fast walk's leaf tests, in one of two carriers (Pred<MASK>::T).  Pred<false>: a lane's bool; votes go through
+// __ballot, which is what every kernel had.  Pred<true>: the whole wave's lane mask, 64 bits in an SGPR pair.  A compare builtin makes it
+// (the v_cmp's own result: the bits of the lanes live at that point, zero elsewhere), it is combined on the scalar unit, a vote is
+// `!= 0`, and inverse_ballot hands it back to selects and branches as the per-lane condition.  hipcc lowers __ballot of a COMBINATION of
+// compares by turning the mask into a 0/1 vector register and comparing that back (v_cndmask, v_cmp_ne, s_cmp, s_cselect, s_and ahead of
+// the branch), and keeps bools that live across a loop as 0/1 integers in VGPRs; the mask form compiles to s_and / s_cmp / branch alone.
+// The pair kernels' ray loop takes it (MASKS, rtgo_render_body.inc); everything else keeps the bool.
+// Both carriers combine with the language's own `&`, `|` and `^`; what differs is a static function here.  The compares keep their IEEE
+// meaning: lt / gt / le / eq are the ordered ones (false on NaN), not_lt is the complement of ordered-less (true on NaN).  A mask has no
+// bits outside the lanes live where it was made, so `a & b`, `a | b`, `a ^ b` and andnot(a, b) of such masks have none either; inv(a)
+// is the complement WITHIN the lanes live where it is taken (~a alone would set the bits of the lanes that are off, which a vote would
+// count).  A mask made in a region is used in that region or in one nested in it, where `&` with a mask made there, or lane(), cuts it
+// down to the region's lanes.  (Plain types and static functions, no objects: a struct around the bool went through scratch.)
+enum : int {   // the compare builtins' condition codes (LLVM's CmpInst::Predicate)
+    kCmpFOeq = 1, kCmpFOgt = 2, kCmpFOlt = 4, kCmpFOle = 5, kCmpFUge = 11, kCmpIEq = 32, kCmpIUlt = 36, kCmpISge = 39, kCmpISlt = 40
+};
+template <bool MASK>
+struct Pred;
+template <>
+struct Pred<false> {
+    typedef bool T;
+    static __device__ __forceinline__ T off() { return false; }
+    static __device__ __forceinline__ T lt(float a, float b) { return a < b; }
+    static __device__ __forceinline__ T gt(float a, float b) { return a > b; }
+    static __device__ __forceinline__ T le(float a, float b) { return a <= b; }
+    static __device__ __forceinline__ T eq(float a, float b) { return a == b; }
+    static __device__ __forceinline__ T not_lt(float a, float b) { return !(a < b); }
+    static __device__ __forceinline__ T ieq(int a, int b) { return a == b; }
+    static __device__ __forceinline__ T ige(int a, int b) { return a >= b; }
+    static __device__ __forceinline__ T ilt(int a, int b) { return a < b; }
+    static __device__ __forceinline__ T ult(unsigned int a, unsigned int b) { return a < b; }
+    static __device__ __forceinline__ T of(bool b) { return b; }
+    static __device__ __forceinline__ T inv(T a) { return !a; }
+    static __device__ __forceinline__ T either(T a, T b) { return a || b; }
+    static __device__ __forceinline__ T differ(T a, T b) { return a != b; }
+    static __device__ __forceinline__ bool lane(T a) { return a; }
+    static __device__ __forceinline__ bool any(T a) { return __ballot(a) != 0ull; }
+    static __device__ __forceinline__ bool none(T a) { return __ballot(a) == 0ull; }
+};
+template <>
+struct Pred<true> {
+    typedef unsigned long long T;
+    static __device__ __forceinline__ T off() { return 0ull; }
+    static __device__ __forceinline__ T lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kCmpFOlt); }
+    static __device__ __forceinline__ T gt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kCmpFOgt); }
+    static __device__ __forceinline__ T le(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kCmpFOle); }
+    static __device__ __forceinline__ T eq(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kCmpFOeq); }
+    static __device__ __forceinline__ T not_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kCmpFUge); }
+    static __device__ __forceinline__ T ieq(int a, int b) { return __builtin_amdgcn_sicmp(a, b, kCmpIEq); }
+    static __device__ __forceinline__ T ige(int a, int b) { return __builtin_amdgcn_sicmp(a, b, kCmpISge); }
+    static __device__ __forceinline__ T ilt(int a, int b) { return __builtin_amdgcn_sicmp(a, b, kCmpISlt); }
+    static __device__ __forceinline__ T ult(unsigned int a, unsigned int b) { return __builtin_amdgcn_uicmp(a, b, kCmpIUlt); }
+    static __device__ __forceinline__ T of(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+    static __device__ __forceinline__ T inv(T a) { return ~a & __builtin_amdgcn_ballot_w64(true); }
+    static __device__ __forceinline__ T andnot(T a, T b) { return a & ~b; }
+    static __device__ __forceinline__ T either(T a, T b) { return a | b; }
+    static __device__ __forceinline__ T differ(T a, T b) { return a ^ b; }
+    static __device__ __forceinline__ bool lane(T a) { return __builtin_amdgcn_inverse_ballot_w64(a); }
+    static __device__ __forceinline__ bool any(T a) { return a != 0ull; }
+    static __device__ __forceinline__ bool none(T a) { return a == 0ull; }
+};
 #include "rtgo_probes.h"   // the diagnostic builds' instruments: Timeline, StreamStats, FastCounters, CmpWalk, WhittedTiming
 
 // the acceptance rule of SURVEY a14 (tmin < t < current closest; ties keep the lower SBT index), without branches
-__device__ __forceinline__ bool closer(float t, int orig, float tmin, const FastHit& best)
+template <bool MASK = false>
+__device__ __forceinline__ typename Pred<MASK>::T closer(float t, int orig, float tmin, const FastHit& best)
 {
-    return (t > tmin) & ((t < best.t) | ((t == best.t) & (best.orig >= 0) & (orig < best.orig)));
+    typedef Pred<MASK> P;
+    return P::gt(t, tmin) & (P::lt(t, best.t) | (P::eq(t, best.t) & P::ige(best.orig, 0) & P::ilt(orig, best.orig)));
 }
 
 // __intersection__rectangle (kernel.cu:372-416) on M^-1 rows, as straight-line code: every lane evaluates the whole test and the
@@ -543,32 +606,36 @@ __device__ __forceinline__ bool closer(float t, int orig, float tmin, const Fast
 // object space, evaluated by the caller) and the other conditions of the reference enter as predicates.
 // second half of the rectangle test for the lanes in `c` (everything up to t > 0.0001 and the closest-hit rule has passed): the hit
 // point against the unit square, and the commit through selects
-template <typename Ptr>
-__device__ __forceinline__ void rect_finish(Ptr rec, float t, bool c, int pos, int orig, v3 wo, v3 wd, FastHit& best)
+template <bool MASK = false, typename Ptr>
+__device__ __forceinline__ void rect_finish(Ptr rec, float t, typename Pred<MASK>::T c, int pos, int orig, v3 wo, v3 wd, FastHit& best)
 {
-    if (__ballot(c) == 0ull) return;   // (coherent waves -- primary rays -- often leave here together)
+    typedef Pred<MASK> P;
+    if (P::none(c)) return;   // (coherent waves -- primary rays -- often leave here together)
     const float4 r0 = rec[0], r2 = rec[2];
     const float dx = r0.x * wd.x + r0.y * wd.y + r0.z * wd.z, dz = r2.x * wd.x + r2.y * wd.y + r2.z * wd.z;
     const float ox = r0.x * wo.x + r0.y * wo.y + r0.z * wo.z + r0.w, oz = r2.x * wo.x + r2.y * wo.y + r2.z * wo.z + r2.w;
     const float px = ox + t * dx, pz = oz + t * dz;
     const float u = px + 0.5f, v = -(pz - 0.5f);
-    c = c & (0.0f < u) & (u < 1.0f) & (0.0f < v) & (v < 1.0f);
-    best.t = c ? t : best.t;
-    best.pos = c ? (pos | kFlat) : best.pos;
-    best.orig = c ? orig : best.orig;
+    c = c & P::lt(0.0f, u) & P::lt(u, 1.0f) & P::lt(0.0f, v) & P::lt(v, 1.0f);
+    const bool cl = P::lane(c);
+    best.t = cl ? t : best.t;
+    best.pos = cl ? (pos | kFlat) : best.pos;
+    best.orig = cl ? orig : best.orig;
 }
 
-template <typename Ptr>
-__device__ __forceinline__ void rect_commit(Ptr rec, const float4 r1, float dy, bool facing, int pos, int orig, v3 wo, v3 wd, float tmin, FastHit& best)
+template <bool MASK = false, typename Ptr>
+__device__ __forceinline__ void rect_commit(Ptr rec, const float4 r1, float dy, typename Pred<MASK>::T facing, int pos, int orig, v3 wo, v3 wd, float tmin, FastHit& best)
 {
+    typedef Pred<MASK> P;
     const float oy = r1.x * wo.x + r1.y * wo.y + r1.z * wo.z + r1.w;
     // oy > 0 with d.y < 0 is the only way to t > 0 (so d.y != 0 and t > 1e-4 can hold); lanes that fail carry garbage in t
     const float t = div_cr(0.0f - oy, dy);
-    const bool c = facing & (oy > 0.0f) & (t > 0.0001f) & closer(t, orig, tmin, best);
-    rect_finish(rec, t, c, pos, orig, wo, wd, best);
+    const typename P::T c = facing & P::gt(oy, 0.0f) & P::gt(t, 0.0001f) & closer<MASK>(t, orig, tmin, best);
+    rect_finish<MASK>(rec, t, c, pos, orig, wo, wd, best);
 }
 
-template <typename Ptr>
+// MASK: the carrier of the rectangle branch's predicates (Pred); the quadrics' branches are per-lane code either way
+template <bool MASK = false, typename Ptr>
 __device__ __forceinline__ void leaf_test(Ptr s_fprims, int pos, v3 wo, v3 wd, float tmin, FastHit& best)
 {
     const float4 r1 = s_fprims[4 * pos + 1];
@@ -576,7 +643,7 @@ __device__ __forceinline__ void leaf_test(Ptr s_fprims, int pos, v3 wo, v3 wd, f
     const int type = __float_as_int(meta.x), orig = __float_as_int(meta.y);
     if (type == 2) {  // rectangle
         const float dy = r1.x * wd.x + r1.y * wd.y + r1.z * wd.z;
-        rect_commit(s_fprims + 4 * pos, r1, dy, dy < 0.0f, pos, orig, wo, wd, tmin, best);
+        rect_commit<MASK>(s_fprims + 4 * pos, r1, dy, Pred<MASK>::lt(dy, 0.0f), pos, orig, wo, wd, tmin, best);
         return;
     }
     const float4 r0 = s_fprims[4 * pos + 0], r2 = s_fprims[4 * pos + 2];
@@ -671,16 +738,16 @@ __device__ __forceinline__ void pair_test(Ptr fp, const float4* __restrict__ lds
 }
 
 // the records [first, first + cnt) of one leaf (or of the up-front list): npairs pairs first, then single primitives
-template <bool LIST, typename Ptr>
+template <bool LIST, bool MASK = false, typename Ptr>
 __device__ __forceinline__ void leaf_range(Ptr fp, const float4* __restrict__ lds, int first, int cnt, int npairs, v3 wo, v3 wd, float tmin, FastHit& best)
 {
 #pragma unroll 1
     for (int k = 0; k < npairs; ++k) pair_test<LIST>(fp, lds, first + 2 * k, wo, wd, tmin, best);
     if (LIST) {
 #pragma unroll 2
-        for (int k = 2 * npairs; k < cnt; ++k) leaf_test(fp, first + k, wo, wd, tmin, best);
+        for (int k = 2 * npairs; k < cnt; ++k) leaf_test<MASK>(fp, first + k, wo, wd, tmin, best);
     } else {
-        for (int k = 2 * npairs; k < cnt; ++k) leaf_test(fp, first + k, wo, wd, tmin, best);
+        for (int k = 2 * npairs; k < cnt; ++k) leaf_test<MASK>(fp, first + k, wo, wd, tmin, best);
     }
 }
 
@@ -701,65 +768,81 @@ __device__ __forceinline__ void leaf_range(Ptr fp, const float4* __restrict__ ld
 // faces, and the margins need not be built per ray.  kCubEither: the list of a kernel that serves both kinds of launch; the kind is in
 // the margins, one of which is infinite and never fires -- the same faces dropped, at two comparisons each.
 enum CubKind { kCubEither = 0, kCubBox = 1, kCubRoom = 2 };   // (= LaunchParams::list_cub's values)
-template <bool LIST, CubKind KIND, typename Ptr>
+// MASK: the carrier of the predicates (Pred): a lane's bool, or the wave's lane mask (the pair kernels' ray loop).
+template <bool LIST, CubKind KIND, bool MASK = false, typename Ptr>
 __device__ __forceinline__ void cuboid_range(Ptr fp, const float4* __restrict__ lds, int first, float mu_out, float mu_in, v3 wo, v3 wd, float tmin, FastHit& best)
 {
+    typedef Pred<MASK> P;
     float t[3], dy[3];
-    bool front[3], ok[3], second[3];   // second: the pair's front-facing face is its second record
-    bool both = false;
+    typedef typename P::T B;
+    B front[3], ok[3], second[3];   // second: the pair's front-facing face is its second record
+    int face[3];                    // MASK: ... as the record's position, a lane's word in place of three masks held through the finish loop
+    B both = P::off();
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int pos = first + 2 * k;
         const float4 r1a = fp[4 * pos + 1], r1b = fp[4 * pos + 5];
         const float dya = r1a.x * wd.x + r1a.y * wd.y + r1a.z * wd.z;
         const float dyb = r1b.x * wd.x + r1b.y * wd.y + r1b.z * wd.z;
-        const bool fa = dya < 0.0f, fb = dyb < 0.0f;
+        const B fa = P::lt(dya, 0.0f), fb = P::lt(dyb, 0.0f);
         both = both | (fa & fb);
-        second[k] = !fa;
-        const float4 r1 = lds[4 * (fa ? pos : pos + 1) + 1];   // (a per-lane read of the one row: cheaper than holding both for selects)
-        dy[k] = fa ? dya : dyb;
+        const int pos_f = P::lane(fa) ? pos : pos + 1;
+        if constexpr (MASK) face[k] = pos_f;
+        else second[k] = P::inv(fa);
+        const float4 r1 = lds[4 * pos_f + 1];   // (a per-lane read of the one row: cheaper than holding both for selects)
+        dy[k] = P::lane(fa) ? dya : dyb;
         const float oyk = r1.x * wo.x + r1.y * wo.y + r1.z * wo.z + r1.w;
         t[k] = div_cr(0.0f - oyk, dy[k]);
-        front[k] = fa != fb;
-        ok[k] = front[k] & (oyk > 0.0f);
-        both = both | (front[k] & !(fabsf(t[k]) < 1e30f));   // (t overflowed: y_g below needs it finite; never seen, handled like `both`)
+        front[k] = P::differ(fa, fb);
+        ok[k] = front[k] & P::gt(oyk, 0.0f);
+        both = both | (front[k] & P::not_lt(fabsf(t[k]), 1e30f));   // (t overflowed: y_g below needs it finite; never seen, handled like `both`)
     }
     // rounding can let both faces of a pair through the sign test (the ray all but parallel to them): those lanes take the six
     // single tests and nothing else
-    if (__ballot(both) != 0ull) {
-        if (both) {
+    if (P::any(both)) {
+        if (P::lane(both)) {
 #pragma unroll 1
-            for (int k = 0; k < 6; ++k) leaf_test(lds, first + k, wo, wd, tmin, best);
+            for (int k = 0; k < 6; ++k) leaf_test<MASK>(lds, first + k, wo, wd, tmin, best);
         }
     }
     auto beyond = [&](int f, int g) {
         // y_g at the point where the ray meets f's plane: o.y_g + t_f d.y_g = d.y_g (t_f - t_g) up to 2^-24 of o.y_g (t_g = -o.y_g / d.y_g
         // correctly rounded), which the margin covers -- and three registers fewer than keeping the o.y
         const float y = dy[g] * (t[f] - t[g]);
-        if constexpr (KIND == kCubBox) return front[g] & (y > mu_out);
-        else if constexpr (KIND == kCubRoom) return front[g] & (y < mu_in);
-        else return front[g] & ((y > mu_out) | (y < mu_in));
+        if constexpr (KIND == kCubBox) return front[g] & P::gt(y, mu_out);
+        else if constexpr (KIND == kCubRoom) return front[g] & P::lt(y, mu_in);
+        else return front[g] & (P::gt(y, mu_out) | P::lt(y, mu_in));
     };
-    bool s0 = ok[0] & !both & !beyond(0, 1) & !beyond(0, 2);
-    bool s1 = ok[1] & !both & !beyond(1, 0) & !beyond(1, 2);
-    bool s2 = ok[2] & !both & !beyond(2, 0) & !beyond(2, 1);
+    B s0, s1, s2;
+    if constexpr (MASK) {   // (`!` is the bool's complement; the mask's is andnot)
+        s0 = P::andnot(P::andnot(P::andnot(ok[0], both), beyond(0, 1)), beyond(0, 2));
+        s1 = P::andnot(P::andnot(P::andnot(ok[1], both), beyond(1, 0)), beyond(1, 2));
+        s2 = P::andnot(P::andnot(P::andnot(ok[2], both), beyond(2, 0)), beyond(2, 1));
+    } else {
+        s0 = ok[0] & !both & !beyond(0, 1) & !beyond(0, 2);
+        s1 = ok[1] & !both & !beyond(1, 0) & !beyond(1, 2);
+        s2 = ok[2] & !both & !beyond(2, 0) & !beyond(2, 1);
+    }
 #pragma unroll 1
     for (;;) {
-        const bool any = s0 | s1 | s2;
-        if (__ballot(any) == 0ull) break;
-        const float tt = s0 ? t[0] : (s1 ? t[1] : t[2]);
-        const int ps = first + (s0 ? (second[0] ? 1 : 0) : (s1 ? (second[1] ? 3 : 2) : (second[2] ? 5 : 4)));
+        const B any = s0 | s1 | s2;
+        if (P::none(any)) break;
+        const float tt = P::lane(s0) ? t[0] : (P::lane(s1) ? t[1] : t[2]);
+        int ps;
+        if constexpr (MASK) ps = P::lane(s0) ? face[0] : (P::lane(s1) ? face[1] : face[2]);
+        else ps = first + (P::lane(s0) ? (P::lane(second[0]) ? 1 : 0) : (P::lane(s1) ? (P::lane(second[1]) ? 3 : 2) : (P::lane(second[2]) ? 5 : 4)));
         s2 = s2 & (s0 | s1);
         s1 = s1 & s0;
-        s0 = false;
+        s0 = P::off();
         const int orig = __float_as_int(lds[4 * ps + 3].y);
-        const bool c = any & (tt > 0.0001f) & closer(tt, orig, tmin, best);
-        rect_finish(lds + 4 * ps, tt, c, ps, orig, wo, wd, best);
+        const B c = any & P::gt(tt, 0.0001f) & closer<MASK>(tt, orig, tmin, best);
+        rect_finish<MASK>(lds + 4 * ps, tt, c, ps, orig, wo, wd, best);
     }
 }
 
 // conservative slab test: t = fma(b, 1/d, -o/d) with the hardware reciprocal
-__device__ __forceinline__ bool box_fast(const float4 q0, const float4 q1, v3 id, v3 noid, float tmin, float tmax, float& tn_out)
+template <bool MASK = false>
+__device__ __forceinline__ typename Pred<MASK>::T box_fast(const float4 q0, const float4 q1, v3 id, v3 noid, float tmin, float tmax, float& tn_out)
 {
     float t0 = fmaf(q0.x, id.x, noid.x), t1 = fmaf(q1.x, id.x, noid.x);
     float tn = fminf(t0, t1), tf = fmaxf(t0, t1);
@@ -775,10 +858,10 @@ __device__ __forceinline__ bool box_fast(const float4 q0, const float4 q1, v3 id
     tf = fminf(tf, tmax);
     tn_out = tn;
 #ifdef RTGO_NO_WIDEN
-    return tn <= tf;
+    return Pred<MASK>::le(tn, tf);
 #else
     // widen by a few ulps so that the reciprocal's rounding can never drop a box the exact test keeps
-    return tn <= tf * 1.000002f + 1e-7f;
+    return Pred<MASK>::le(tn, tf * 1.000002f + 1e-7f);
 #endif
 }
 
@@ -787,9 +870,9 @@ __device__ __forceinline__ bool box_fast(const float4 q0, const float4 q1, v3 id
 // lane than the other two: profiles/r02f/README.md).  fast_list: the up-front list, which also gives the ray its first closest-hit bound.
 // LAST, `last`: the lane's ray is the last of its path under the last-ray certificate (closest_hit_fast): it skips the room.
 // KIND: kCubRoom when the launch vouches for a list that starts with a certified room (the pair kernels), else kCubEither (list_cub says).
-template <bool LAST = false, CubKind KIND = kCubEither>
+template <bool LAST = false, CubKind KIND = kCubEither, bool MASK = false>
 __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, const float4* __restrict__ g_fprims, int n_small, int n_prims, int n_big_pairs,
-                                          int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, bool last = false)
+                                          int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, typename Pred<MASK>::T last = Pred<MASK>::off())
 {
     // the few "big" primitives (walls, floors; the whole scene when it is tiny) first.  The loop index is wave-uniform and
     // g_fprims is a read-only kernel argument, so the records arrive by scalar loads (s_load_dwordx4) into SGPRs: no LDS
@@ -797,11 +880,11 @@ __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, c
     // It also gives every ray a closest-hit bound before it enters the tree.
     if (KIND != kCubEither || list_cub != 0) {
         // the room's six walls (or one big box) as a cuboid, the rest of the list after them
-        if (!LAST || __ballot(!last) != 0ull) {
+        if (!LAST || Pred<MASK>::any(Pred<MASK>::inv(last))) {
             const bool box = KIND == kCubEither && list_cub == 1;
-            if (!LAST || !last) cuboid_range<true, KIND>(g_fprims, s_fprims, n_small, box ? cub_mu : INFINITY, box ? -INFINITY : -cub_mu, o, d, tmin, best);
+            if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) cuboid_range<true, KIND, MASK>(g_fprims, s_fprims, n_small, box ? cub_mu : INFINITY, box ? -INFINITY : -cub_mu, o, d, tmin, best);
         }
-        leaf_range<true>(g_fprims, s_fprims, n_small + 6, n_prims - n_small - 6, 0, o, d, tmin, best);
+        leaf_range<true, MASK>(g_fprims, s_fprims, n_small + 6, n_prims - n_small - 6, 0, o, d, tmin, best);
     } else {
         leaf_range<true>(g_fprims, s_fprims, n_small, n_prims - n_small, n_big_pairs, o, d, tmin, best);
     }
@@ -911,9 +994,11 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
 // <= the closest hit.  What is gone is the machinery of a deep tree: the root's own box test (the root box is the union of the two, and
 // fma(q, id, noid) is monotone in q: a lane that passes a child's slab test passes the root's), the while-while loop, the stack word
 // in LDS, the pop loop with its dependent reads of a node's links, and the leaf's dispatch on tree_spheres / leaf_cuboid / cub_mu.
+template <bool MASK>
 __device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims, float cub_mu, v3 o, v3 d, float tmin, FastHit& best,
                                           unsigned int& dbg_boxes, unsigned int& dbg_tests)
 {
+    typedef Pred<MASK> P;
     auto safe_rcp = [](float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(x), -1e30f, 1e30f); };   // (see fast_tree on 1 / 0)
     const v3 id = mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
     const v3 noid = mk(-(o.x * id.x), -(o.y * id.y), -(o.z * id.z));
@@ -921,18 +1006,26 @@ __device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, c
     const float4 l0 = s_fnodes[2], l1 = s_fnodes[3], h0 = s_fnodes[4], h1 = s_fnodes[5];
     float tl, tr;
     FastCounters::step(dbg_boxes, 2u);
-    const bool hl = box_fast(l0, l1, id, noid, tmin, best.t, tl);
-    const bool hr = box_fast(h0, h1, id, noid, tmin, best.t, tr);
-    const bool go_r = hr & (!hl | (tr < tl));
-    if (hl | hr) {
-        FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(go_r ? h1.w : l1.w)));
-        cuboid_range<false, kCubBox>(s_fprims, s_fprims, __float_as_int(go_r ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
+    typedef typename P::T B;
+    const B hl = box_fast<MASK>(l0, l1, id, noid, tmin, best.t, tl);
+    const B hr = box_fast<MASK>(h0, h1, id, noid, tmin, best.t, tr);
+    const B go_r = hr & (P::inv(hl) | P::lt(tr, tl));
+    // (what the far leaf needs is picked per lane before the near leaf runs: two words and one mask live across it, not three masks and the boxes)
+    const bool right = P::lane(go_r);
+    const B two = hl & hr;
+    const float t_far = __uint_as_float(__float_as_uint(right ? tl : tr) & 0xFFFF0000u);
+    const int first_far = __float_as_int(right ? l0.w : h0.w);
+    const unsigned int count_far = (unsigned int)leaf_count(__float_as_int(right ? l1.w : h1.w));
+    if (P::lane(hl | hr)) {
+        FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(right ? h1.w : l1.w)));
+        // (the near leaf keeps the bool carrier: as masks its predicates cost render_pair7_kernel ten more SGPR spills than its budget has)
+        cuboid_range<false, kCubBox, false>(s_fprims, s_fprims, __float_as_int(right ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
     }
-    const bool far = hl & hr & (__uint_as_float(__float_as_uint(go_r ? tl : tr) & 0xFFFF0000u) <= best.t);
-    if (__ballot(far) != 0ull) {
-        if (far) {
-            FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(go_r ? l1.w : h1.w)));
-            cuboid_range<false, kCubBox>(s_fprims, s_fprims, __float_as_int(go_r ? l0.w : h0.w), cub_mu, -INFINITY, o, d, tmin, best);
+    const B far = two & P::le(t_far, best.t);
+    if (P::any(far)) {
+        if (P::lane(far)) {
+            FastCounters::step(dbg_tests, count_far);
+            cuboid_range<false, kCubBox, MASK>(s_fprims, s_fprims, first_far, cub_mu, -INFINITY, o, d, tmin, best);
         }
     }
 }
@@ -1067,25 +1160,27 @@ __device__ __forceinline__ bool fast_winner(const float4* __restrict__ s_fprims,
 // like the term of a non-emitter hit).  When it hits one, the tree walks from `best` = that hit: the closest hit does not depend on the
 // order in which candidates are met (closer()).  LAST: the instantiation has this path at all (else `last` is ignored).
 // PAIR (render_pair_kernel): the tree is a root over two cuboid leaves, walked by fast_pair.
-template <bool GRID, bool LAST = false, bool PAIR = false>
+// MASK: the carrier of `last` and of the walk's predicates from here down (Pred); the pair kernels' ray loop alone sets it.
+template <bool GRID, bool LAST = false, bool PAIR = false, bool MASK = false>
 __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims,
                                                  const float4* __restrict__ g_fprims, const GridParams grid,
  unsigned int* __restrict__ s_stack, int bshift,
                                                  int n_small, int n_prims, int n_big_pairs, int list_cub, float cub_mu, bool tree_spheres, v3 o, v3 d, float tmin, float tmax, Hit& out,
-                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, bool last, Timeline& tl)
+                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, typename Pred<MASK>::T last, Timeline& tl)
 {
+    static_assert(!MASK || PAIR, "the lane-mask predicates are the pair kernels'");
     tl.walk_begin();
     FastHit best;
     best.t = tmax;
     best.pos = -1;
     best.orig = -1;
-    fast_list<LAST, PAIR ? kCubRoom : kCubEither>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
-    const bool walk = !last || best.pos >= 0;
-    FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (last ? 6 : 0)));
+    fast_list<LAST, PAIR ? kCubRoom : kCubEither, MASK>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
+    const bool walk = Pred<MASK>::lane(Pred<MASK>::either(Pred<MASK>::inv(last), Pred<MASK>::ige(best.pos, 0)));
+    FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (Pred<MASK>::lane(last) ? 6 : 0)));
     tl.list_done(best.pos);
     if constexpr (GRID) fast_grid(s_fnodes, s_fprims, grid, tree_spheres, o, d, tmin, best, dbg_boxes, dbg_tests);
     else if constexpr (PAIR) {
-        if (!LAST || walk) fast_pair(s_fnodes, s_fprims, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests);
+        if (!LAST || walk) fast_pair<MASK>(s_fnodes, s_fprims, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests);
     } else if (!LAST || walk) fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
     tl.walk_done(best.pos);
     return fast_winner(s_fprims, o, d, tmax, best, out);

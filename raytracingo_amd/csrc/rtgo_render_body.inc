@@ -38,6 +38,9 @@
     // depth and LDS records while it is inactive.  The same multiplications in the same order: the same bits.
     constexpr bool FOLDLATE = PAIR;
     static_assert(!FOLDLATE || (PATH && LVLDS && !STREAM && !BATCH), "the deferred fold is the path-mode fold over LDS records, in the lock-step loop");
+    // the pair kernels' ray loop carries the walk's predicates as the wave's lane masks (Pred<true>, rtgo_device.h): a vote is a scalar
+    // compare, with none of the vector instructions hipcc puts around __ballot of a combination of compares
+    constexpr bool MASKS = PAIR;
     // raygen constants (eye, U, V, W, image size, sample step): read from LDS where a sample starts, instead of sitting in
     // registers through the ray loop
     float* s_cam = reinterpret_cast<float*>(s_lights + kMaxLights);
