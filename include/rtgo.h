@@ -154,7 +154,7 @@ int rtgo_set_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs
    A scene within RTGO_MAX_PRIMS renders the same pixels bit for bit through rtgo_set_scene, and faster there. */
 int rtgo_set_large_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n);
 
-/* flags of rtgo_update_prims */
+/* flags of rtgo_update_prims and rtgo_whitted_update_meshes_device */
 enum { RTGO_UPDATE_REFIT = 0, RTGO_UPDATE_REBUILD = 1 };
 
 /* optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE (RTGO_UPDATE_REFIT) or _BUILD (RTGO_UPDATE_REBUILD) over the custom-primitive AABBs,
@@ -439,6 +439,30 @@ int rtgo_whitted_update_meshes(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* up
    first and put back).  Afterwards rtgo_whitted_set_instances, rtgo_whitted_update_mesh, rtgo_whitted_update_meshes and this call
    work as after a fresh rtgo_whitted_set_scene.  Synchronous. */
 int rtgo_whitted_rebuild_meshes(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* updates, uint32_t n_updates);
+
+/* rtgo_whitted_update_meshes (flags = RTGO_UPDATE_REFIT) or rtgo_whitted_rebuild_meshes (RTGO_UPDATE_REBUILD) for vertices that are
+   already on the device (under OptiX the vertex buffers of a build input are device pointers): a skinning kernel's output, a
+   PyTorch-ROCm tensor.  `updates` is a host array; the positions / normals of its entries are DEVICE memory of the context's device,
+   n_vertices x 3 floats each (normals NULL: keep the normals the mesh has), caller-owned, 4-byte aligned, overlapping nothing of the
+   context; the call reads them and never writes to them.  The caller's writes to them must be complete, or ordered on the context's
+   stream (rtgo_set_stream), before the call.  Beyond NULL and alignment the call cannot tell whether a pointer is good: that the
+   buffers are device memory of the sizes given is the caller's to vouch for, as in the ray-query calls.
+   Afterwards the context holds, array for array, what the host-pointer twin holds after the same vertices, so frames,
+   rtgo_whitted_trace_rays and rtgo_whitted_shade_rays are equal bit for bit; what the twin keeps stays (meshes not named, indices,
+   triangle materials, texture coordinates, textures, instances, lights, miss colour), and every other update call works afterwards as
+   after a fresh rtgo_whitted_set_scene.  A scene of rtgo_whitted_set_mesh takes one entry, mesh 0.
+   No copy in proportion to a mesh crosses the host in either direction: the data is checked where it lies (every float of every
+   entry, named by a triangle or not), the boxes of the small meshes are taken there through the context's indices (both by one pair of
+   launches over all entries, 32 bytes per entry read back, one wait), the vertices move device to device, and all named small meshes
+   are refitted by one launch (one workgroup per mesh).  What still crosses is what the twins read back per cluster or structure.
+   Refusals are the twins'.  RTGO_E_STATE: no whitted scene.  RTGO_E_INVALID: NULL ctx, unknown flag bits, `updates` NULL with
+   n_updates > 0, a mesh index beyond the scene's meshes, a mesh named twice, positions NULL, a pointer that is not 4-byte aligned,
+   n_vertices not the mesh's own, normals for a mesh that was set without, non-finite data, an instance that now places a mesh beyond
+   the float range.  RTGO_E_UNSUPPORTED: a structure deeper than the walk's stack.  n_updates == 0 with a scene and known flags:
+   RTGO_OK, nothing changes.  A refused call leaves the scene as it was, whichever entry it refuses: every check of the entries and of
+   their data runs before anything of the context is written, and a refusal known only after a clustered refit or a build puts the
+   saved arrays back, as in the twins.  Synchronous. */
+int rtgo_whitted_update_meshes_device(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, uint32_t flags);
 
 /* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
    rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */

@@ -27,7 +27,7 @@ SYMBOLS = [
     "rtgo_whitted_set_texcoords", "rtgo_whitted_set_material_textures", "rtgo_whitted_set_scene", "rtgo_whitted_set_instances",
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
     "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
-    "rtgo_shade_rays", "rtgo_update_prims",
+    "rtgo_shade_rays", "rtgo_update_prims", "rtgo_whitted_update_meshes_device",
 ]
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
@@ -184,6 +184,7 @@ def load():
     L.rtgo_whitted_update_mesh.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32]
     L.rtgo_whitted_update_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_rebuild_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
+    L.rtgo_whitted_update_meshes_device.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32, C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
     L.rtgo_whitted_launch_frames.argtypes = [vp, C.POINTER(WhittedFrame), C.c_uint32]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
@@ -442,6 +443,27 @@ class Context:
         rest of the scene (other meshes, instances, materials, textures) stays"""
         arr, keep = self._mesh_updates(updates, "whitted_rebuild_meshes")
         self._check(self._lib.rtgo_whitted_rebuild_meshes(self._h, arr, len(updates)), "rtgo_whitted_rebuild_meshes")
+
+    def whitted_update_meshes_device(self, updates, rebuild=False):
+        """rtgo_whitted_update_meshes_device: [(mesh, positions, normals or None), ...] with positions / normals contiguous float32
+        torch tensors [nv, 3] on the context's device, refitted (rebuild=False: whitted_update_meshes) or built again (rebuild=True:
+        whitted_rebuild_meshes) from where they lie.  The tensors' writes must be complete (torch.cuda.synchronize()) or ordered on the
+        context's stream.  Synchronous."""
+        who = "whitted_update_meshes_device"
+        arr = (WhittedMeshUpdate * max(len(updates), 1))()
+        keep = []   # the tensors the entries point into, alive until the call returns
+        for k, (mesh, positions, normals) in enumerate(updates):
+            for t in (positions,) if normals is None else (positions, normals):
+                if not hasattr(t, "data_ptr") or not t.is_cuda or t.device.index != self.device:
+                    raise ValueError("%s: positions and normals must be torch tensors on device %d" % (who, self.device))
+                if str(t.dtype) != "torch.float32" or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+                    raise ValueError(who + ": positions and normals must be contiguous float32 tensors of shape [nv, 3]")
+            if normals is not None and normals.shape[0] != positions.shape[0]:
+                raise ValueError(who + ": one normal per position")
+            keep += [positions, normals]
+            arr[k] = WhittedMeshUpdate(int(mesh), positions.data_ptr(), normals.data_ptr() if normals is not None else None, positions.shape[0])
+        self._check(self._lib.rtgo_whitted_update_meshes_device(self._h, arr, len(updates), UPDATE_REBUILD if rebuild else UPDATE_REFIT),
+                    "rtgo_whitted_update_meshes_device")
 
     def whitted_set_texcoords(self, uv):
         if uv is None:

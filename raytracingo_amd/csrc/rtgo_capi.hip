@@ -1987,6 +1987,14 @@ int rtgo_whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* upd
     return whitted_rebuild_meshes(c, updates, n_updates);
 }
 
+int rtgo_whitted_update_meshes_device(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, uint32_t flags)
+{
+    if (!c) return RTGO_E_INVALID;
+    if (flags & ~(uint32_t)RTGO_UPDATE_REBUILD) return fail(c, RTGO_E_INVALID, "rtgo_whitted_update_meshes_device: unknown flag bits");
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_update_meshes_device: no mesh (call rtgo_whitted_set_mesh or rtgo_whitted_set_scene first)");
+    return whitted_update_meshes_device(c, updates, n_updates, (flags & RTGO_UPDATE_REBUILD) != 0);
+}
+
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
 {
     if (!c) return RTGO_E_INVALID;

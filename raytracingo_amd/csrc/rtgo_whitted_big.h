@@ -13,6 +13,9 @@
 //   -> big_remap_kernel (cluster-local triangle numbers in tris[].w back to the mesh's own).
 // A refit to moved vertices (rtgo_whitted_update_meshes) keeps all of that and runs big_bounds_kernel, big_bounds_final_kernel (the
 // mesh's box), big_refit_clusters_kernel (every cluster, one workgroup each), big_cluster_boxes_kernel and refit_kernel (the mid level).
+// The small meshes a call names are refitted by one launch, big_refit_meshes_kernel (one workgroup each).  Vertices that are on the
+// device already (rtgo_whitted_update_meshes_device) are checked and bounded where they lie by big_update_check_kernel and
+// big_update_check_final_kernel, one pair of launches over a table of the call's entries.
 #pragma once
 
 #include "rtgo_whitted.h"
@@ -232,6 +235,109 @@ __global__ __launch_bounds__(kBuildThreads) void big_refit_clusters_kernel(const
     refit_structure<true>({positions, indices, c.n, c.n_recs, c.walk_depth, recs + 4 * (size_t)c.rec0, tris + 3 * (size_t)c.tri0, qrecs + 2 * (size_t)c.tri0,
                            done + c.tri0, out_meta + blockIdx.x},
                           s_red);
+}
+
+// One small mesh of a call's refits as its build left it, by absolute offsets into the scene's arrays: its vertices start at vertex
+// vert0, its index triples and sorted triangles at triangle tri0, its records at rec0; its flags at done0 of the call's scratch
+struct MeshRefit { int vert0, tri0, rec0, n, n_recs, walk_depth, done0, pad; };
+static_assert(sizeof(MeshRefit) == 8 * sizeof(int), "eight words");
+
+// refit_kernel's body over every small mesh a call names, one workgroup per mesh: the records are refit_kernel's bit for bit.  A
+// workgroup reads and writes its own mesh's slices only.  out_meta[m] gets mesh m's grid.
+__global__ __launch_bounds__(kBuildThreads) void big_refit_meshes_kernel(const float* __restrict__ positions, const unsigned int* __restrict__ indices,
+                                                                         const MeshRefit* __restrict__ table, float4* recs, float4* tris, uint4* qrecs, int* done,
+                                                                         WhittedBuildMeta* __restrict__ out_meta)
+{
+    __shared__ float s_red[6][kBuildThreads];
+    const MeshRefit m = table[blockIdx.x];
+    refit_structure<false>({positions + 3 * (size_t)m.vert0, indices + 3 * (size_t)m.tri0, m.n, m.n_recs, m.walk_depth, recs + 4 * (size_t)m.rec0,
+                            tris + 3 * (size_t)m.tri0, qrecs + 2 * (size_t)m.tri0, done + m.done0, out_meta + blockIdx.x},
+                           s_red);
+}
+
+// ---- vertices that are on the device already (rtgo_whitted_update_meshes_device) ------------------------------------------------------
+// One entry of the call as its checks see it.  positions / normals: the caller's buffers, 3 n_verts floats each (normals NULL: the mesh
+// keeps its own).  indices: the mesh's n_tris index triples in the scene's arrays when the call needs the bounds of the vertices they
+// name (a small mesh of an instanced scene), else NULL.  Workgroups first_block .. first_block + n_blocks - 1 of big_update_check_kernel
+// are the entry's.
+struct UpdateCheck {
+    const float* positions;
+    const float* normals;
+    const unsigned int* indices;
+    unsigned int n_verts;
+    int n_tris, first_block, n_blocks;
+};
+static_assert(sizeof(UpdateCheck) == 40, "three pointers, four words");
+
+// ... and what comes back of it: the exact min / max over the vertices its triangles name (indices given), and whether any float of its
+// buffers, named by a triangle or not, is an infinity or a NaN
+struct UpdateReport { float lo[3], hi[3]; unsigned int bad, pad; };
+
+__device__ __forceinline__ unsigned int non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
+
+// whitted_check_updates' loop over the floats and big_bounds_kernel, for every entry of a table in one launch: each workgroup takes a
+// grid-stride share of its entry's floats and triangles -> its partial box at partial[6 b ..] and its flag at part_bad[b] (fminf / fmaxf
+// drop NaNs and the box sees named vertices only, so the flag is taken over the floats themselves).  Reads the caller's buffers, writes
+// nothing of the scene.
+__global__ __launch_bounds__(1024) void big_update_check_kernel(const UpdateCheck* __restrict__ table, int n_entries, float* __restrict__ partial,
+                                                                unsigned int* __restrict__ part_bad)
+{
+    __shared__ float s_red[6][1024];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    int e = 0, last = n_entries - 1;   // the entry whose run of workgroups holds b (uniform)
+    while (e < last) {
+        const int mid = (e + last + 1) / 2;
+        if (table[mid].first_block <= b) e = mid;
+        else last = mid - 1;
+    }
+    const UpdateCheck u = table[e];
+    const size_t first = (size_t)(b - u.first_block) * 1024 + tid, stride = (size_t)u.n_blocks * 1024, n_floats = 3 * (size_t)u.n_verts;
+    unsigned int bad = 0;
+    for (size_t i = first; i < n_floats; i += stride) {
+        bad |= non_finite(u.positions[i]);
+        if (u.normals) bad |= non_finite(u.normals[i]);
+    }
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (u.indices)
+        for (size_t i = first; i < (size_t)u.n_tris; i += stride)
+            for (int k = 0; k < 3; ++k) {
+                const unsigned int vi = u.indices[3 * i + k];
+                for (int a = 0; a < 3; ++a) {
+                    const float c = u.positions[3 * (size_t)vi + a];
+                    lo[a] = fminf(lo[a], c);
+                    hi[a] = fmaxf(hi[a], c);
+                }
+            }
+    reduce_bounds<1024>(s_red, tid, lo, hi);
+    if (tid < 6) partial[6 * (size_t)b + tid] = s_red[tid][0];
+    const int any = __syncthreads_or((int)bad);
+    if (tid == 0) part_bad[b] = any ? 1u : 0u;
+}
+
+// one workgroup per entry: its workgroups' partial boxes and flags -> report[entry]
+__global__ __launch_bounds__(1024) void big_update_check_final_kernel(const UpdateCheck* __restrict__ table, const float* __restrict__ partial,
+                                                                      const unsigned int* __restrict__ part_bad, UpdateReport* __restrict__ report)
+{
+    __shared__ float s_red[6][1024];
+    const int tid = threadIdx.x;
+    const UpdateCheck u = table[blockIdx.x];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    unsigned int bad = 0;
+    for (int i = tid; i < u.n_blocks; i += 1024) {
+        const size_t p = (size_t)u.first_block + i;
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], partial[6 * p + a]);
+            hi[a] = fmaxf(hi[a], partial[6 * p + 3 + a]);
+        }
+        bad |= part_bad[p];
+    }
+    reduce_bounds<1024>(s_red, tid, lo, hi);
+    const int any = __syncthreads_or((int)bad);
+    UpdateReport& r = report[blockIdx.x];
+    if (tid < 3) r.lo[tid] = s_red[tid][0];
+    else if (tid < 6) r.hi[tid - 3] = s_red[tid][0];
+    else if (tid == 6) r.bad = any ? 1u : 0u;
+    else if (tid == 7) r.pad = 0u;
 }
 
 // ---- batched builds (rtgo_whitted_set_scene, rtgo_whitted_rebuild_meshes) -----------------------------------------------------------

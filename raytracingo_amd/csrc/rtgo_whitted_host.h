@@ -767,7 +767,8 @@ static int whitted_update_mesh(rtgo_ctx* c, uint32_t mesh, const float* position
 // scratch of its launches, and what they report.  All of it is proportional to the mesh and freed with this.
 struct WhittedClusteredRefit {
     int mesh = 0, ncl = 0;
-    const float *positions = nullptr, *normals = nullptr;   // the caller's
+    const float *positions = nullptr, *normals = nullptr;   // the caller's, and where they lie
+    hipMemcpyKind kind = hipMemcpyHostToDevice;
     DeviceArray<float> old_positions, old_normals;
     DeviceArray<float4> old_recs, old_tris;
     DeviceArray<uint4> old_qrecs;
@@ -781,7 +782,7 @@ struct WhittedClusteredRefit {
     std::vector<float4> up_mid_tris;
 };
 
-// Stage 2 of whitted_update_meshes for a clustered mesh: saves the slices, uploads the vertices and enqueues the refit and its read-back.
+// Stage 2 of whitted_refit_named for a clustered mesh: saves the slices, copies the vertices in and enqueues the refit and its read-back.
 // Three launches refit it whatever its size -- every cluster (one workgroup each), the clusters' boxes, the mid level over them -- and
 // two find its bounds.  Nothing here waits for the device.
 static int whitted_enqueue_clustered_refit(rtgo_ctx* c, WhittedMesh& wm, const WhittedMeshInfo& mi, WhittedClusteredRefit& r)
@@ -803,8 +804,8 @@ static int whitted_enqueue_clustered_refit(rtgo_ctx* c, WhittedMesh& wm, const W
     RTGO_HIP(c, save(r.old_recs, t.recs, (size_t)4 * n));
     RTGO_HIP(c, save(r.old_tris, t.tris, (size_t)3 * n));
     RTGO_HIP(c, save(r.old_qrecs, t.qrecs, (size_t)2 * n));
-    RTGO_HIP(c, hipMemcpyAsync(d_pos, r.positions, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (r.normals) RTGO_HIP(c, hipMemcpyAsync(d_nrm, r.normals, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(d_pos, r.positions, nv3 * sizeof(float), r.kind, c->stream));
+    if (r.normals) RTGO_HIP(c, hipMemcpyAsync(d_nrm, r.normals, nv3 * sizeof(float), r.kind, c->stream));
     // the launches' tables, one upload
     static_assert(sizeof(ClusterRefit) == 5 * sizeof(int), "five words");
     const size_t o_crec = (size_t)5 * ncl, o_idx = o_crec + ncl, o_done = o_idx + (size_t)3 * ncl, o_mid_done = o_done + n;
@@ -890,8 +891,19 @@ static int whitted_restore_clustered(rtgo_ctx* c, WhittedMesh& wm, const Whitted
     return RTGO_OK;
 }
 
-// The checks rtgo_whitted_update_meshes and rtgo_whitted_rebuild_meshes make of their entries on the host (w: the call, for the messages)
-static int whitted_check_updates(rtgo_ctx* c, const WhittedMesh& wm, const std::string& w, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+// Where the vertices of a call's entries lie: host memory (rtgo_whitted_update_meshes, rtgo_whitted_rebuild_meshes), or the device
+// (rtgo_whitted_update_meshes_device), then with what whitted_check_on_device reported of each entry
+struct WhittedUpdateSource {
+    hipMemcpyKind kind;
+    const whitted::UpdateReport* report;   // NULL: host memory
+    bool on_device() const { return report != nullptr; }
+};
+
+// The checks rtgo_whitted_update_meshes and rtgo_whitted_rebuild_meshes make of their entries on the host (w: the call, for the
+// messages).  on_device: the entries point to device memory (rtgo_whitted_update_meshes_device) -- the pointers' alignment is checked
+// here, NULL and misaligned ones never reach a launch, and the data itself is left to whitted_check_on_device.
+static int whitted_check_updates(rtgo_ctx* c, const WhittedMesh& wm, const std::string& w, const rtgo_whitted_mesh_update* updates, uint32_t n_updates,
+                                 bool on_device = false)
 {
     const size_t n_meshes = wm.instanced ? wm.meshes.size() : (size_t)1;
     std::vector<char> named(n_meshes, 0);
@@ -906,32 +918,117 @@ static int whitted_check_updates(rtgo_ctx* c, const WhittedMesh& wm, const std::
         const bool has_normals = wm.instanced ? (wm.meshes[u.mesh].flags & whitted::kHasNormals) != 0 : wm.normals.get() != nullptr;
         if (u.n_vertices != (uint32_t)n_verts) return fail(c, RTGO_E_INVALID, at + ": the mesh has " + std::to_string(n_verts) + " vertices");
         if (u.normals && !has_normals) return fail(c, RTGO_E_INVALID, at + ": normals for a mesh that was set without");
+        if (on_device) {
+            if ((uintptr_t)u.positions % alignof(float) || (uintptr_t)u.normals % alignof(float))
+                return fail(c, RTGO_E_INVALID, at + ": positions and normals must be 4-byte aligned");
+            continue;
+        }
         for (size_t i = 0; i < (size_t)3 * u.n_vertices; ++i)
             if (!std::isfinite(u.positions[i]) || (u.normals && !std::isfinite(u.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
     }
     return RTGO_OK;
 }
 
-// rtgo_whitted_update_meshes once the scene is known to exist: rtgo_whitted_update_mesh for every entry as one transaction.  Stages:
-// 1 every check the host can make; 2 every mesh's new box (a small mesh: from its indices read back, all in one wait; a clustered mesh:
-// refitted in place with its slices saved, its box from what the device reports); 3 the instances laid out and the top level built, once,
-// aside; 4 the small meshes' refits; 5 what the host keeps.  A refusal in stage 3 puts the clustered meshes' slices back: nothing else
-// has changed by then.
-static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+// The rest of those checks for entries in device memory, and the boxes of the call's small meshes, by one pair of launches over a table of
+// the entries (big_update_check_kernel, big_update_check_final_kernel): report[k] says whether entry k holds a non-finite float and, for
+// a small mesh of an instanced scene, has the bounds of the vertices its triangles name, read from the caller's buffer through the
+// scene's indices (whitted_pad_mesh_box then gives whitted_mesh_box's box).  One copy back, 32 B per entry, and one wait; nothing of the
+// scene is written.
+static int whitted_check_on_device(rtgo_ctx* c, const WhittedMesh& wm, const std::string& w, const rtgo_whitted_mesh_update* updates, uint32_t n_updates,
+                                   std::vector<whitted::UpdateReport>& report)
 {
-    const char* what = "rtgo_whitted_update_meshes";
-    const std::string w(what);
-    WhittedMesh& wm = c->wm;
-    if (n_updates == 0) return RTGO_OK;
-    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
-    // stage 1
-    if (const int rc = whitted_check_updates(c, wm, w, updates, n_updates)) return rc;
-    RTGO_HIP(c, hipSetDevice(c->device));
+    using namespace whitted;
+    std::vector<UpdateCheck> table(n_updates);
+    int n_blocks = 0;
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        const rtgo_whitted_mesh_update& u = updates[k];
+        const bool box = wm.instanced && !wm.meshes[u.mesh].clustered;   // (a clustered mesh's comes from its refit or build)
+        const int n_tris = box ? wm.meshes[u.mesh].n_tris : 0;
+        const size_t work = std::max((size_t)3 * u.n_vertices, (size_t)n_tris);
+        const int nb = (int)std::min<size_t>(1024, (work + 1023) / 1024);
+        table[k] = {u.positions, u.normals, box ? wm.indices.get() + 3 * (size_t)wm.meshes[u.mesh].tri_base : nullptr, u.n_vertices, n_tris, n_blocks, nb};
+        n_blocks += nb;
+    }
+    DeviceArray<UpdateCheck> d_table;
+    DeviceArray<float> partial;
+    DeviceArray<unsigned int> part_bad;
+    DeviceArray<UpdateReport> d_report;
+    RTGO_HIP(c, d_table.upload(table.data(), table.size(), c->stream));
+    RTGO_HIP(c, partial.alloc((size_t)6 * n_blocks));
+    RTGO_HIP(c, part_bad.alloc(n_blocks));
+    RTGO_HIP(c, d_report.alloc(n_updates));
+    hipLaunchKernelGGL(big_update_check_kernel, dim3(n_blocks), dim3(1024), 0, c->stream, (const UpdateCheck*)d_table.get(), (int)n_updates, partial.get(),
+                       part_bad.get());
+    hipLaunchKernelGGL(big_update_check_final_kernel, dim3(n_updates), dim3(1024), 0, c->stream, (const UpdateCheck*)d_table.get(), (const float*)partial.get(),
+                       (const unsigned int*)part_bad.get(), d_report.get());
+    RTGO_HIP(c, hipGetLastError());
+    report.assign(n_updates, UpdateReport{});
+    RTGO_HIP(c, hipMemcpyAsync(report.data(), d_report.get(), n_updates * sizeof(UpdateReport), hipMemcpyDeviceToHost, c->stream));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_updates; ++k)
+        if (report[k].bad) return fail(c, RTGO_E_INVALID, w + ": update " + std::to_string(k) + ": non-finite vertex data");
+    return RTGO_OK;
+}
+
+// An entry's vertices into its mesh's slice of wm's arrays (enqueued)
+static int whitted_put_vertices(rtgo_ctx* c, WhittedMesh& wm, int vert_base, int n_verts, const rtgo_whitted_mesh_update& u, hipMemcpyKind kind)
+{
+    const size_t bytes = (size_t)n_verts * 3 * sizeof(float);
+    RTGO_HIP(c, hipMemcpyAsync(wm.positions.get() + 3 * (size_t)vert_base, u.positions, bytes, kind, c->stream));
+    if (u.normals) RTGO_HIP(c, hipMemcpyAsync(wm.normals.get() + 3 * (size_t)vert_base, u.normals, bytes, kind, c->stream));
+    return RTGO_OK;
+}
+
+// whitted_refit's launch for every mesh of `ms` at once (their new vertices are in wm's arrays, or enqueued before this): one workgroup
+// per mesh (big_refit_meshes_kernel), one scratch allocation -- the table, the grids that come back, refit_kernel's flags -- and one
+// wait, however many meshes; every m.meta gets its new grid.  Synchronous.
+static int whitted_refit_small(rtgo_ctx* c, WhittedMesh& wm, std::vector<WhittedRefitMesh>& ms)
+{
+    using namespace whitted;
+    const size_t k = ms.size();
+    if (k == 0) return RTGO_OK;
+    static_assert(sizeof(MeshRefit) == 8 * sizeof(int) && sizeof(WhittedBuildMeta) == 9 * sizeof(int), "the scratch is laid out in words");
+    const size_t o_meta = 8 * k, o_done = o_meta + 9 * k;
+    std::vector<MeshRefit> table(k);
+    size_t n_done = 0;
+    for (size_t i = 0; i < k; ++i) {
+        const WhittedRefitMesh& m = ms[i];
+        table[i] = {m.vert_base, m.tri_base, m.rec_base, m.n_tris, m.meta.n_recs, m.meta.walk_depth, (int)n_done, 0};
+        n_done += (size_t)std::max(m.meta.n_recs, 1);
+    }
+    DeviceArray<int> scratch;
+    RTGO_HIP(c, scratch.alloc(o_done + n_done));
+    RTGO_HIP(c, hipMemcpyAsync(scratch.get(), table.data(), k * sizeof(MeshRefit), hipMemcpyHostToDevice, c->stream));
+    WhittedBuildMeta* d_meta = reinterpret_cast<WhittedBuildMeta*>(scratch.get() + o_meta);
+    hipLaunchKernelGGL(big_refit_meshes_kernel, dim3((unsigned int)k), dim3(kBuildThreads), 0, c->stream, (const float*)wm.positions.get(),
+                       (const unsigned int*)wm.indices.get(), reinterpret_cast<const MeshRefit*>(scratch.get()), wm.recs.get(), wm.tris.get(), wm.qrecs.get(),
+                       scratch.get() + o_done, d_meta);
+    RTGO_HIP(c, hipGetLastError());
+    std::vector<WhittedBuildMeta> metas(k);
+    RTGO_HIP(c, hipMemcpyAsync(metas.data(), d_meta, k * sizeof(WhittedBuildMeta), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < k; ++i) {   // (the kernel writes the grid alone)
+        ms[i].meta.grid_lo = metas[i].grid_lo;
+        ms[i].meta.grid_step = metas[i].grid_step;
+    }
+    return RTGO_OK;
+}
+
+// The refits of rtgo_whitted_update_meshes and rtgo_whitted_update_meshes_device (`what`: the call, for the messages) once every entry
+// has passed its checks and the stream has drained: rtgo_whitted_update_mesh for every entry as one transaction.  Stages: 2 every mesh's
+// new box (a small mesh: from its indices read back, all in one wait -- or, vertices on the device, from what whitted_check_on_device
+// reported, and nothing is read back; a clustered mesh: refitted in place with its slices saved, its box from what the device reports);
+// 3 the instances laid out and the top level built, once, aside; 4 the small meshes' vertices in and their refits, one launch
+// (whitted_refit_small); 5 what the host keeps.  A refusal in stage 3 puts the clustered meshes' slices back: nothing else has changed
+// by then.
+static int whitted_refit_named(rtgo_ctx* c, const char* what, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, const WhittedUpdateSource& src)
+{
+    WhittedMesh& wm = c->wm;
     if (!wm.instanced) {
-        WhittedRefitMesh m = {0, 0, 0, wm.n_vertices, wm.triangles, wm.normals.get() != nullptr, wm.meta};
-        if (const int rc = whitted_refit(c, wm, m, updates[0].positions, updates[0].normals)) return rc;
-        wm.meta = m.meta;
+        std::vector<WhittedRefitMesh> one = {{0, 0, 0, wm.n_vertices, wm.triangles, wm.normals.get() != nullptr, wm.meta}};
+        if (const int rc = whitted_put_vertices(c, wm, 0, wm.n_vertices, updates[0], src.kind)) return rc;
+        if (const int rc = whitted_refit_small(c, wm, one)) return rc;
+        wm.meta = one[0].meta;
         return RTGO_OK;
     }
     // stage 2
@@ -947,16 +1044,19 @@ static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* up
             big.back().mesh = (int)u.mesh;
             big.back().positions = u.positions;
             big.back().normals = u.normals;
+            big.back().kind = src.kind;
             if (const int rc = whitted_enqueue_clustered_refit(c, wm, mi, big.back())) return rc;
-        } else {
+        } else if (!src.on_device()) {
             idx[k].resize((size_t)3 * mi.n_tris);
             RTGO_HIP(c, hipMemcpyAsync(idx[k].data(), wm.indices.get() + 3 * (size_t)mi.tri_base, idx[k].size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         }
     }
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (!big.empty() || !src.on_device()) RTGO_HIP(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = 0; k < n_updates; ++k) {
         WhittedMeshInfo& mi = meshes[updates[k].mesh];
-        if (!mi.clustered) whitted_mesh_box(updates[k].positions, idx[k].data(), (uint32_t)mi.n_tris, mi.lo, mi.hi);
+        if (mi.clustered) continue;
+        if (src.on_device()) whitted_pad_mesh_box(src.report[k].lo, src.report[k].hi, mi.lo, mi.hi);
+        else whitted_mesh_box(updates[k].positions, idx[k].data(), (uint32_t)mi.n_tris, mi.lo, mi.hi);
     }
     for (const WhittedClusteredRefit& r : big) whitted_finish_clustered_refit(meshes[r.mesh], r);
     // stage 3
@@ -973,18 +1073,35 @@ static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* up
         return rc;
     }
     // stage 4
+    std::vector<WhittedRefitMesh> small;
+    std::vector<uint32_t> small_mesh;
     for (uint32_t k = 0; k < n_updates; ++k) {
         const rtgo_whitted_mesh_update& u = updates[k];
-        WhittedMeshInfo& mi = meshes[u.mesh];
+        const WhittedMeshInfo& mi = meshes[u.mesh];
         if (mi.clustered) continue;
-        WhittedRefitMesh m = {mi.vert_base, mi.tri_base, mi.rec_base, mi.n_verts, mi.n_tris, (mi.flags & whitted::kHasNormals) != 0, mi.built[0].meta};
-        if (const int rc4 = whitted_refit(c, wm, m, u.positions, u.normals)) return rc4;
-        mi.built[0].meta = m.meta;
+        if (const int rc4 = whitted_put_vertices(c, wm, mi.vert_base, mi.n_verts, u, src.kind)) return rc4;
+        small.push_back({mi.vert_base, mi.tri_base, mi.rec_base, mi.n_verts, mi.n_tris, (mi.flags & whitted::kHasNormals) != 0, mi.built[0].meta});
+        small_mesh.push_back(u.mesh);
     }
+    if (const int rc4 = whitted_refit_small(c, wm, small)) return rc4;
+    for (size_t i = 0; i < small.size(); ++i) meshes[small_mesh[i]].built[0].meta = small[i].meta;
     // stage 5
     wm.meshes = std::move(meshes);
     whitted_install_top(wm, std::move(top), depth);
     return RTGO_OK;
+}
+
+// rtgo_whitted_update_meshes once the scene is known to exist: every check the host can make (stage 1), then the refits
+static int whitted_update_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    const char* what = "rtgo_whitted_update_meshes";
+    const std::string w(what);
+    if (n_updates == 0) return RTGO_OK;
+    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
+    if (const int rc = whitted_check_updates(c, c->wm, w, updates, n_updates)) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    return whitted_refit_named(c, what, updates, n_updates, {hipMemcpyHostToDevice, nullptr});
 }
 
 // ---- rebuild (rtgo_whitted_rebuild_meshes) --------------------------------------------------------------------------------------------
@@ -997,22 +1114,16 @@ struct WhittedRebuildSave {
     DeviceArray<uint2> tidx;
 };
 
-// rtgo_whitted_rebuild_meshes once the scene is known to exist: the named meshes built again over new vertices, as rtgo_whitted_set_scene
-// (rtgo_whitted_set_mesh) builds them, in place; everything else of the scene stays.  Stages: 1 every check the host can make; 2 the
-// named meshes' slices saved, the new vertices up; 3 their structures, all through one table (whitted_build_structures), the cluster
-// table aside; 4 the instances laid out over the new boxes and the top level built, aside; 5 what the host keeps.  A refusal in stage 3
-// or 4 puts the slices back: nothing else has changed by then.
-static int whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+// The builds of rtgo_whitted_rebuild_meshes and rtgo_whitted_update_meshes_device (`what`: the call, for the messages) once every entry
+// has passed its checks (stage 1) and the stream has drained: the named meshes built again over new vertices, as rtgo_whitted_set_scene
+// (rtgo_whitted_set_mesh) builds them, in place; everything else of the scene stays.  Stages: 2 the named meshes' slices saved, the new
+// vertices in (a small mesh's box: from its indices read back, or, vertices on the device, from what whitted_check_on_device reported);
+// 3 their structures, all through one table (whitted_build_structures), the cluster table aside; 4 the instances laid out over the new
+// boxes and the top level built, aside; 5 what the host keeps.  A refusal in stage 3 or 4 puts the slices back: nothing else has changed
+// by then.
+static int whitted_rebuild_named(rtgo_ctx* c, const char* what, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, const WhittedUpdateSource& src)
 {
-    const char* what = "rtgo_whitted_rebuild_meshes";
-    const std::string w(what);
     WhittedMesh& wm = c->wm;
-    if (n_updates == 0) return RTGO_OK;
-    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
-    // stage 1
-    if (const int rc = whitted_check_updates(c, wm, w, updates, n_updates)) return rc;
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
     std::vector<WhittedMeshInfo> meshes = wm.meshes;
     if (!wm.instanced) {   // a scene of rtgo_whitted_set_mesh: its one mesh, at the start of every array
         WhittedMeshInfo mi = WhittedMeshInfo();
@@ -1044,9 +1155,8 @@ static int whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* u
         RTGO_HIP(c, save(s.tris, t.tris, 3 * n));
         RTGO_HIP(c, save(s.qrecs, t.qrecs, 2 * n));
         RTGO_HIP(c, save(s.tidx, t.tidx, n));
-        RTGO_HIP(c, hipMemcpyAsync(d_pos, u.positions, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (u.normals) RTGO_HIP(c, hipMemcpyAsync(d_nrm, u.normals, nv3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (wm.instanced && !mi.clustered) {   // its new box needs its indices, which are on the device only
+        if (const int rc = whitted_put_vertices(c, wm, mi.vert_base, mi.n_verts, u, src.kind)) return rc;
+        if (wm.instanced && !mi.clustered && !src.on_device()) {   // its new box needs its indices, which are on the device only
             idx[k].resize(3 * n);
             RTGO_HIP(c, hipMemcpyAsync(idx[k].data(), wm.indices.get() + 3 * (size_t)mi.tri_base, idx[k].size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         }
@@ -1056,7 +1166,9 @@ static int whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* u
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = 0; k < n_updates; ++k) {
         WhittedMeshInfo& mi = meshes[updates[k].mesh];
-        if (wm.instanced && !mi.clustered) whitted_mesh_box(updates[k].positions, idx[k].data(), (uint32_t)mi.n_tris, mi.lo, mi.hi);
+        if (!wm.instanced || mi.clustered) continue;
+        if (src.on_device()) whitted_pad_mesh_box(src.report[k].lo, src.report[k].hi, mi.lo, mi.hi);
+        else whitted_mesh_box(updates[k].positions, idx[k].data(), (uint32_t)mi.n_tris, mi.lo, mi.hi);
     }
     auto refused = [&](int rc) -> int {   // the named meshes' slices as they were
         for (uint32_t k = 0; k < n_updates; ++k) {
@@ -1099,6 +1211,40 @@ static int whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* u
     if (!table.empty()) wm.clusters = std::move(clusters);
     whitted_install_top(wm, std::move(top), depth);
     return RTGO_OK;
+}
+
+// rtgo_whitted_rebuild_meshes once the scene is known to exist: every check the host can make (stage 1), then the builds
+static int whitted_rebuild_meshes(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates)
+{
+    const char* what = "rtgo_whitted_rebuild_meshes";
+    const std::string w(what);
+    if (n_updates == 0) return RTGO_OK;
+    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
+    if (const int rc = whitted_check_updates(c, c->wm, w, updates, n_updates)) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    return whitted_rebuild_named(c, what, updates, n_updates, {hipMemcpyHostToDevice, nullptr});
+}
+
+// ---- vertices on the device (rtgo_whitted_update_meshes_device) -----------------------------------------------------------------------
+// Either of the two above for entries whose positions / normals are device memory, once the scene is known to exist and the flags are
+// known.  Stage 1 in two halves: what the host can decide without the data (whitted_check_updates: a NULL or misaligned pointer never
+// reaches a launch), then the data where it lies (whitted_check_on_device, which also brings the small meshes' boxes: one copy of 32 B
+// per entry, one wait) -- both before anything of the scene is written.  The stages after it are the twins', with the vertices copied
+// device to device: nothing in proportion to a mesh's vertices or triangles crosses the host, in either direction.
+static int whitted_update_meshes_device(rtgo_ctx* c, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, bool rebuild)
+{
+    const char* what = "rtgo_whitted_update_meshes_device";
+    const std::string w(what);
+    if (n_updates == 0) return RTGO_OK;
+    if (!updates) return fail(c, RTGO_E_INVALID, w + ": NULL updates");
+    if (const int rc = whitted_check_updates(c, c->wm, w, updates, n_updates, true)) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<whitted::UpdateReport> report;
+    if (const int rc = whitted_check_on_device(c, c->wm, w, updates, n_updates, report)) return rc;
+    const WhittedUpdateSource src = {hipMemcpyDeviceToDevice, report.data()};
+    return rebuild ? whitted_rebuild_named(c, what, updates, n_updates, src) : whitted_refit_named(c, what, updates, n_updates, src);
 }
 
 // The launches.  What a launch over one mesh (rtgo_whitted_set_mesh) reads of the scene: everything of Params but the frame

@@ -3,7 +3,9 @@
    python tools/whitted_refit_perf.py big [W] [H]    tools/whitted_inst_perf.py big's 1 000 000-triangle displaced torus (a clustered mesh) on a ground:
                                                      rtgo_whitted_update_meshes against rtgo_whitted_set_scene over the same vertices, subframe time of the
                                                      refitted scene against the fresh one (smooth, twist); and a batch of k meshes against k calls of
-                                                     rtgo_whitted_update_mesh on a field of 1024 tori drawn from k meshes
+                                                     rtgo_whitted_update_mesh on a field of 1024 tori drawn from k meshes; and
+                                                     rtgo_whitted_update_meshes_device (the same vertices as torch device tensors) beside its host
+                                                     twins, refit and rebuild, on both scenes, in the same process
 Per mesh and deformation, medians of repeated calls after a warm-up:
    update    ms of rtgo_whitted_update_mesh (synchronous: wall time of the call)
    set_mesh  ms of rtgo_whitted_set_mesh over the same new vertices
@@ -88,7 +90,21 @@ def view(ctx, lights, miss, cam):
     ctx.resize(W * H)
 
 
+def device_against_host(ctx, what, updates):
+    """the synchronous calls over the same vertices: from host arrays (update_meshes, rebuild_meshes) and from device tensors"""
+    import torch
+    on_device = [(m, torch.from_numpy(q).cuda(), None if n is None else torch.from_numpy(n).cuda()) for m, q, n in updates]
+    torch.cuda.synchronize()
+    for rebuild, host in ((False, ctx.whitted_update_meshes), (True, ctx.whitted_rebuild_meshes)):
+        t_host = median_ms(lambda: host(updates))
+        t_dev = median_ms(lambda: ctx.whitted_update_meshes_device(on_device, rebuild=rebuild))
+        print("%s, %s: %-22s %8.3f ms   update_meshes_device %8.3f ms   host/device %5.2fx" %
+              (what, "rebuild" if rebuild else "refit", host.__name__[len("whitted_"):], t_host, t_dev, t_host / t_dev))
+
+
 def big_mode():
+    import torch
+    torch.cuda.init()   # torch's HIP runtime up before the first context: device_against_host hands the library torch tensors
     eye34 = np.eye(3, 4, dtype=np.float32)
     big = BM.displaced_torus(1000, 500, R=1.0, r=0.35, amp=0.04, freq=(23, 11), texcoords=False)   # 1 000 000 triangles
     meshes, inst, mats, lt = [WI.ground(4.0, -0.5, normals=True), big], [(eye34, 0, 0), (eye34, 1, 1)], WI.materials(), WI.lights()
@@ -112,6 +128,7 @@ def big_mode():
         print("    %-8s update_meshes %8.3f ms   set_scene %9.3f ms   set_scene/update_meshes %6.1fx   subframe refit %.3f ms  fresh %.3f ms  refit/fresh %.3f" %
               (what, t_update, t_set, t_set / t_update, refit, fresh, refit / fresh))
         ctx.whitted_set_scene(meshes, inst, mats)
+    device_against_host(ctx, "%d triangles, one clustered mesh" % len(big["indices"]), [(1, deformations(big)[0][1], None)])
     ctx.close()
     # a field of 1024 tori drawn from K meshes: all K moved by one call against one call each
     K = 16
@@ -127,6 +144,7 @@ def big_mode():
     t_set = median_ms(lambda: ctx.whitted_set_scene(meshes, inst, mats))
     print("1024 tori of %d triangles drawn from %d meshes: update_meshes over all %d %.3f ms   %d calls of update_mesh %.3f ms   single/batch %.1fx   set_scene %.3f ms" %
           (len(tor["indices"]), K, K, t_batch, K, t_single, t_single / t_batch, t_set))
+    device_against_host(ctx, "%d meshes of %d triangles in one call" % (K, len(tor["indices"])), grown)
     ctx.close()
 
 
