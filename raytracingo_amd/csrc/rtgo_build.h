@@ -671,15 +671,113 @@ __device__ __forceinline__ void morton_units(BuildLds& s, int i, int n, int n_sm
     }
 }
 
+// The slab certificate of one certified cuboid (cuboid_slab, rtgo_device.h), made by the group's thread in pair_and_certify and written
+// into the group's records by write_slab.  The frame is the object frame of the group's FIRST face F (rows 0..2 of its record: F is the
+// unit square of the plane y = 0 there), not the three pairs' own r1 rows: the walk then transforms the ray with rows it has to read for
+// no other reason than this, but they are three rows of ONE record (one address per lane in a leaf).  The frame is affine, not
+// orthonormal: a box sheared as a whole (every face's matrix under one affine map) is an axis-aligned box in it and is certified; a
+// parallelepiped whose faces carry their own true normals as y axes is not (its first face's rows 0 and 2 are not the other pairs' normals).
+struct SlabCert {
+    bool ok = false;
+    int first = 0;             // the group's first record
+    float lo[3], hi[3];        // the box in the frame
+    int map = 0;               // three bits per plane: the face's offset in the group; plane = 2 * axis + (0: low, 1: high)
+    float rho = 1.0f;          // the largest unit of a face's object-space y, in units of its frame axis: carries cub_mu into the frame
+    float thr = 0.0f;          // |d_a| at or below this: the ray counts as parallel to the faces of axis a (2e-5 of the longest axis row, L1)
+};
+constexpr int kSlabBit = 4;    // in a group's certificate code, beside 1 (box) / 2 (room): the group holds the slab certificate
+
+// Holds iff: the 24 corners of the six faces are corners of one axis-aligned box [lo, hi] in the frame, to kCuboidTol; faces and planes
+// are a bijection (each face's centre sits on exactly one plane, mid-box on the other two axes); every face's normal is parallel to its
+// axis to 2e-6 (what float products of a rotation leave); everything is finite; and the cuboid's own margin at reach zero, in frame
+// units, stays below 2 % of the thinnest slab (a small cuboid far from the origin: its margin is no longer positive for any launch).
+// faces: the six primitives in record order; B: the group's own margin coefficient (pair_and_certify).
+__device__ __forceinline__ void slab_certify(const int* faces, const PrimIn* __restrict__ prims, const float4* __restrict__ out_prims, float B, SlabCert& sc)
+{
+    const float4 R[3] = {out_prims[6 * faces[0] + 0], out_prims[6 * faces[0] + 1], out_prims[6 * faces[0] + 2]};
+    auto to_frame = [&](float cx, float cy, float cz, float* q) {
+        for (int k = 0; k < 3; ++k) q[k] = R[k].x * cx + R[k].y * cy + R[k].z * cz + R[k].w;
+    };
+    auto corner = [&](const float* M, int c, float* q) {
+        const float sx = (c & 1) ? 0.5f : -0.5f, sz = (c & 2) ? 0.5f : -0.5f;
+        to_frame(M[0] * sx + M[2] * sz + M[3], M[4] * sx + M[6] * sz + M[7], M[8] * sx + M[10] * sz + M[11], q);
+    };
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool ok = true;
+    for (int f = 0; f < 6; ++f)
+        for (int c = 0; c < 4; ++c) {
+            float q[3];
+            corner(prims[faces[f]].M, c, q);
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = fminf(lo[k], q[k]);
+                hi[k] = fmaxf(hi[k], q[k]);
+                if (!(fabsf(q[k]) < 1e30f)) ok = false;
+            }
+        }
+    float dev = 0.0f, rho = 1.0f, ext = INFINITY;
+    for (int k = 0; k < 3; ++k) ext = fminf(ext, hi[k] - lo[k]);
+    int map = 0, filled = 0;
+    for (int f = 0; f < 6 && ok; ++f) {
+        const float* M = prims[faces[f]].M;
+        for (int c = 0; c < 4; ++c) {
+            float q[3];
+            corner(M, c, q);
+            for (int k = 0; k < 3; ++k) dev = fmaxf(dev, fminf(fabsf(q[k] - lo[k]), fabsf(hi[k] - q[k])));
+        }
+        // the face's plane: the axis along which its centre sits on a plane of the box, the other two coordinates mid-box
+        float qc[3];
+        to_frame(M[3], M[7], M[11], qc);
+        int axis = -1, side = 0;
+        for (int k = 0; k < 3; ++k) {
+            const float e = hi[k] - lo[k];
+            const float dl = fabsf(qc[k] - lo[k]), dh = fabsf(hi[k] - qc[k]);
+            if (fminf(dl, dh) <= 1e-3f * e) {
+                if (axis >= 0) ok = false;   // on two planes at once: not a face of this box
+                axis = k;
+                side = dl <= dh ? 0 : 1;
+            } else if (!(fabsf(qc[k] - 0.5f * (lo[k] + hi[k])) <= 1e-3f * e)) {
+                ok = false;
+            }
+        }
+        if (axis < 0) ok = false;
+        if (!ok) break;
+        const int slot = 2 * axis + side;
+        if ((filled >> slot) & 1) ok = false;
+        filled |= 1 << slot;
+        map |= f << (3 * slot);
+        // the face's normal (row 1 of ITS inverse, as a world direction) against the frame axis (row `axis` of F's)
+        const float4 nf = out_prims[6 * faces[f] + 1];
+        const float4 ax = R[axis];
+        const float cxp = nf.y * ax.z - nf.z * ax.y, cyp = nf.z * ax.x - nf.x * ax.z, czp = nf.x * ax.y - nf.y * ax.x;
+        const float ln = sqrtf(nf.x * nf.x + nf.y * nf.y + nf.z * nf.z), la = sqrtf(ax.x * ax.x + ax.y * ax.y + ax.z * ax.z);
+        if (!(sqrtf(cxp * cxp + cyp * cyp + czp * czp) <= 2e-6f * ln * la)) ok = false;
+        // one unit of the face's object-space y, in units of its frame axis: |R_axis . (column 1 of M_f)|
+        rho = fmaxf(rho, fabsf(ax.x * M[1] + ax.y * M[5] + ax.z * M[9]));
+    }
+    float n1max = 0.0f;
+    for (int k = 0; k < 3; ++k) n1max = fmaxf(n1max, fabsf(R[k].x) + fabsf(R[k].y) + fabsf(R[k].z));
+    const float mu0 = (kCuboidTol + 64.0f * 5.9604645e-8f * B) * rho;   // (rtgo_capi.hip, cub_mu, at reach zero)
+    if (ok && filled == 63 && dev <= kCuboidTol && rho < 1e6f && n1max > 0.0f && n1max < 1e30f && ext > 0.0f && mu0 < 0.02f * ext) {
+        sc.ok = true;
+        for (int k = 0; k < 3; ++k) {
+            sc.lo[k] = lo[k];
+            sc.hi[k] = hi[k];
+        }
+        sc.map = map;
+        sc.rho = rho;
+        sc.thr = 2e-5f * n1max;
+    }
+}
+
 // ---- stage: record order inside every group the walk scans linearly -- the up-front list and each maximal collapsed leaf (->
-// s.order, s.leaf_group, meta.list_group, the margin coefficients); ends in a barrier.
+// s.order, s.leaf_group, meta.list_group, the margin coefficients, the group's slab certificate); ends in a barrier.
 // Rectangles with opposite normals side by side (pair_test), pairs first, the rest after them.  One thread per group.
 // Leaves are only paired when EVERY multi-record leaf of the scene pairs up completely (whole boxes): the lanes of a wave
 // scan different leaves side by side, and with leaves of both kinds they take turns in the pair loop and the single
 // loop (checkered, whose Morton leaves cut across its 64 cubes: +9 %).  The up-front list is scanned by all lanes
 // together and is always paired.
 __device__ __forceinline__ void pair_and_certify(BuildLds& s, int i, int n, int n_small, const PrimIn* __restrict__ prims, const float4* __restrict__ out_prims,
-                                                 int leaf_budget, int cuboids, BuildMeta* __restrict__ out_meta)
+                                                 int leaf_budget, int cuboids, BuildMeta* __restrict__ out_meta, SlabCert& slab)
 {
     const int leaf0 = n_small - 1;
     if (i < n) {
@@ -775,6 +873,11 @@ __device__ __forceinline__ void pair_and_certify(BuildLds& s, int i, int n, int 
             if (cert) {
                 atomicMax(&s.cub_a, __float_as_int(A));
                 atomicMax(&s.cub_b, __float_as_int(B));
+                int faces[6];
+                for (int f = 0; f < 6; ++f) faces[f] = (int)s.order[g_lo + f];
+                slab_certify(faces, prims, out_prims, B, slab);
+                slab.first = g_lo;
+                if (slab.ok) cert |= kSlabBit;
             }
         }
         if (list || 2 * npairs == g_hi - g_lo + 1) {
@@ -790,6 +893,7 @@ __device__ __forceinline__ void pair_and_certify(BuildLds& s, int i, int n, int 
     if (s.n_unpaired_leaves > 0 && i != kMaxPrims - 1 && g_hi > g_lo) {   // mixed scene: leave every leaf as it was
         for (int a = g_lo; a <= g_hi; ++a) s.order[a] = (unsigned short)(s.keys[a] & 0xFFFFFFFFu);
         s.leaf_group[i] = 0;
+        slab.ok = false;
     }
     if (i == 0) {
         out_meta->cub_a = __int_as_float(s.cub_a);
@@ -808,6 +912,23 @@ __device__ __forceinline__ void write_fprims(const BuildLds& s, int i, int n, co
         out_fprims[4 * i + 1] = out_prims[6 * prim + 1];
         out_fprims[4 * i + 2] = out_prims[6 * prim + 2];
         out_fprims[4 * i + 3] = make_float4(__int_as_float((int)prims[prim].type), __int_as_float(prim), 0.0f, 0.0f);
+    }
+}
+
+// ---- stage: the slab certificates' numbers into the spare words (z, w of row 3) of their groups' records, which write_fprims has just
+// written as zeros: record a (a = 0, 1, 2) the bounds of frame axis a, record 3 (map, rho), record 4 (thr, 0); see cuboid_slab
+__device__ __forceinline__ void write_slab(int i, const SlabCert& slab, float4* __restrict__ out_fprims)
+{
+    __syncthreads();   // (write_fprims' rows are another thread's)
+    if (slab.ok) {
+        const float z[5] = {slab.lo[0], slab.lo[1], slab.lo[2], __int_as_float(slab.map), slab.thr};
+        const float w[5] = {slab.hi[0], slab.hi[1], slab.hi[2], slab.rho, 0.0f};
+        for (int k = 0; k < 5; ++k) {
+            float4 m = out_fprims[4 * (slab.first + k) + 3];
+            m.z = z[k];
+            m.w = w[k];
+            out_fprims[4 * (slab.first + k) + 3] = m;
+        }
     }
 }
 
@@ -980,8 +1101,10 @@ __global__ __launch_bounds__(kMaxPrims) void build_kernel(const PrimIn* __restri
     const bool big = tight_boxes_and_big(s, i, n, P, big_frac, out_tight, out_meta, n_small);
     group_cube_faces(s, i, n, prims, out_prims);
     morton_units(s, i, n, n_small, big, prims, leaf_budget);
-    pair_and_certify(s, i, n, n_small, prims, out_prims, leaf_budget, cuboids, out_meta);
+    SlabCert slab;
+    pair_and_certify(s, i, n, n_small, prims, out_prims, leaf_budget, cuboids, out_meta, slab);
     write_fprims(s, i, n, prims, out_prims, out_fprims);
+    write_slab(i, slab, out_fprims);
     const int n_units = form_units(s, i, n_small, leaf_budget);
     const int n_nodes = sah_tree(s, i, n_small, n_units, tree);
     rotate_tree(s, i, n_nodes, tree);

@@ -64,6 +64,10 @@ static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, boo
     return nullptr;
 }
 
+// the pair kernel of `wpe` waves with the slab test in place of cuboid_range (cuboid_slab), where one exists: seven waves only -- six- and
+// five-waves forms were not built (profiles/r22a)
+static RenderKernel find_slab_kernel(int wpe) { return wpe == 7 ? render_slab7_kernel : nullptr; }
+
 // window rows below y that this rank owns under the band interleave
 static uint32_t owned_rows_below(uint32_t y, uint32_t band_h, uint32_t n_ranks, uint32_t rank)
 {
@@ -95,6 +99,7 @@ struct Knobs {
     bool no_cuboid = std::getenv("RTGO_NO_CUBOID") != nullptr;      // the build certifies no cuboids
     bool no_last_emitter = std::getenv("RTGO_NO_LAST_EMITTER") != nullptr;   // launches go without the last-ray certificate
     bool no_pair = std::getenv("RTGO_NO_PAIR") != nullptr;          // two-leaf trees are walked by fast_tree like every other (render_pair_kernel is not taken)
+    bool no_slab = std::getenv("RTGO_NO_SLAB") != nullptr;          // the pair kernels keep cuboid_range (render_slab7_kernel is not taken)
     bool pin_big = std::getenv("RTGO_BIG_PERCENT") != nullptr;      // one fast-walk structure, of big_percent (else 36 % and 15 %)
     unsigned int big_percent = env_uint("RTGO_BIG_PERCENT", 36);
     unsigned int max_wpe = env_uint("RTGO_MAX_WPE", 0);             // cap of the waves-per-SIMD variant; 0: by the work
@@ -230,7 +235,7 @@ struct BuildSpan {
 // The ordered list of spans of rtgo_debug_build_digest and rtgo_debug_read_build.
 //   analytic (whitted = 0): nodes, prims, frames, tight, aabb; then for tree[0] and tree[1]: fnodes (2 * n_fnodes float4), fprims, the
 //     decoded meta fields {canonical depth, fast_depth, n_small, n_fnodes, n_big_pairs, list_cub, cuboid_groups, tree_spheres, bounds[6],
-//     cub_a, cub_b}.  A scene of rtgo_set_large_scene has the first five only (frames and tight boxes empty).  Then, in the clear:
+//     cub_a, cub_b, slab_list, slab_leaves}.  A scene of rtgo_set_large_scene has the first five only (frames and tight boxes empty).  Then, in the clear:
 //     scene.info {n_prims, large, have_alt, has a grid}, tree0.meta / tree1.meta (BuildMeta's words), grid.params (GridParams, then
 //     {bytes, list entries}), grid.image.
 //   whitted (whitted = 1), one mesh: recs (4 * n_recs float4), qrecs (2 * n_recs), tris, tidx, grid {grid_lo, grid_step}, counts {n_recs,
@@ -262,7 +267,8 @@ static int build_spans(rtgo_ctx* c, int whitted, std::vector<BuildSpan>& out)
             span(pre + "fprims").device(t.d_fprims.get(), have ? n * 4 : 0);
             const int ints[] = {sc.lbvh_depth, t.fast_depth, t.n_small, t.n_fnodes, t.n_big_pairs, t.list_cub, t.cuboid_groups, t.tree_spheres};
             const float floats[] = {t.cub_a, t.cub_b};
-            span(pre + "decoded").host(ints, sizeof ints).host(sc.bounds, sizeof sc.bounds).host(floats, sizeof floats);
+            const int slab[] = {t.slab_list ? 1 : 0, t.slab_leaves};
+            span(pre + "decoded").host(ints, sizeof ints).host(sc.bounds, sizeof sc.bounds).host(floats, sizeof floats).host(slab, sizeof slab);
         }
         const int info[] = {(int)n, sc.large ? 1 : 0, sc.have_alt ? 1 : 0, sc.grid.have ? 1 : 0};
         span("scene.info").host(info, sizeof info);
@@ -726,7 +732,9 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
     t.fast_depth = meta.walk_depth;
     t.n_small = meta.n_small;
     t.n_big_pairs = group_pairs(meta.list_group);
-    t.list_cub = group_cert(meta.list_group);
+    t.list_cub = group_cert(meta.list_group) & 3;
+    t.slab_list = (group_cert(meta.list_group) & kSlabBit) != 0;
+    t.slab_leaves = 0;
     t.cuboid_groups = meta.cuboid_leaves + (t.list_cub ? 1 : 0);
     t.tree_spheres = (t.n_small > 0 && meta.tree_types == (1 << 3)) ? 1 : 0;   // (type 3 = sphere)
     t.cub_a = meta.cub_a;
@@ -744,6 +752,8 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
         const bool boxed = nd[0].x == std::fmin(nd[2].x, nd[4].x) && nd[0].y == std::fmin(nd[2].y, nd[4].y) && nd[0].z == std::fmin(nd[2].z, nd[4].z) &&
                            nd[1].x == std::fmax(nd[3].x, nd[5].x) && nd[1].y == std::fmax(nd[3].y, nd[5].y) && nd[1].z == std::fmax(nd[3].z, nd[5].z);
         t.pair = link(0) == 1 && link(1) == 2 && cuboid(1) && cuboid(2) && boxed;
+        // (which of the pair kernels' two leaves also hold the slab certificate: bit 0 node 1, bit 1 node 2)
+        if (t.pair) t.slab_leaves = ((leaf_cuboid(link(3)) & kSlabBit) ? 1 : 0) | ((leaf_cuboid(link(5)) & kSlabBit) ? 2 : 0);
     }
     return RTGO_OK;
 }
@@ -889,8 +899,9 @@ static int build_resident(rtgo_ctx* c, uint32_t n)
     }
     if (const int rc = build_grid(c, n, kn)) return rc;
     if (kn.debug)
-        std::fprintf(stderr, "rtgo_set_scene: %d primitives, %d in the fast walk's tree (%d nodes, depth %d), %d up front (%d pairs, cuboid certificate %d), %d cuboid leaves, margin coefficients %g %g, canonical LBVH depth %d\n",
-                     (int)n, t0.n_small, t0.n_fnodes, t0.fast_depth, (int)n - t0.n_small, t0.n_big_pairs, t0.list_cub, meta.cuboid_leaves, t0.cub_a, t0.cub_b, depth);
+        std::fprintf(stderr, "rtgo_set_scene: %d primitives, %d in the fast walk's tree (%d nodes, depth %d), %d up front (%d pairs, cuboid certificate %d, slab certificate %d), %d cuboid leaves (slab certificates of a two-leaf tree: %d %d), margin coefficients %g %g, canonical LBVH depth %d\n",
+                     (int)n, t0.n_small, t0.n_fnodes, t0.fast_depth, (int)n - t0.n_small, t0.n_big_pairs, t0.list_cub, t0.slab_list ? 1 : 0, meta.cuboid_leaves, t0.slab_leaves & 1, (t0.slab_leaves >> 1) & 1,
+                     t0.cub_a, t0.cub_b, depth);
     if (depth > kStackDepth)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene: LBVH depth " + std::to_string(depth) + " exceeds the per-lane LDS stack (" +
                                                std::to_string(kStackDepth) + ")");
@@ -1818,13 +1829,19 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     Block b;
     if (const int rc = pick_block(c, f, p, nn, canon, pk.stream, frames, use_grid, units_hot, kn, b, false, batch, pair_ok)) return rc;
     const RenderKernel pair_kernel = pair_ok ? find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch, true) : nullptr;
-    const RenderKernel kernel = pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch);
+    // ... and with cuboid_slab where the room and both leaves also hold the slab certificate and the waves have such a kernel.  RTGO_NO_SLAB: off.
+    const AnalyticScene::FastTree& walked = c->scene.tree[use_alt ? 1 : 0];
+    const RenderKernel slab_kernel = (pair_kernel && !kn.no_slab && walked.slab_list && walked.slab_leaves == 3) ? find_slab_kernel(b.wpe) : nullptr;
+    const RenderKernel kernel = slab_kernel ? slab_kernel : (pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch));
     if (pair_kernel) p.stack_depth = 0;   // (fast_pair has no stack: pick_block reserved none, and the lights follow the scene directly)
     if (pair_kernel) pair_words(p);
     const bool pair7 = pair_kernel && b.wpe == 7;
     if (kn.debug) {
-        char kname[48];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
-        if (pair7) std::snprintf(kname, sizeof kname, "render_pair7_kernel");
+        char kname[96];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
+        // (the slab kernel is named with the pair kernel whose body it is and which RTGO_NO_SLAB=1 would run: readers of this line that
+        // ask which walk a launch took -- the pair walk at these waves -- find it where they found it)
+        if (slab_kernel) std::snprintf(kname, sizeof kname, "render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
+        else if (pair7) std::snprintf(kname, sizeof kname, "render_pair7_kernel");
         else std::snprintf(kname, sizeof kname, "%s<%d>", pair_kernel ? "render_pair_kernel" : (batch ? "render_frames_kernel" : "render_kernel"), b.wpe);
         std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g, kernel %s\n",
                      n_frames, canon ? "canonical" : "fast", (canon && !stats) ? " (beyond the far-field guard)" : "", b.grid, b.block, b.lds, b.wpe, b.blocks_per_cu, p.n_hot, strip_px, p.hot_w, p.hot_h, p.hot_x0, p.hot_y0, p.n_cold_segs, p.cold_cs, p.stack_depth, p.cub_mu, c->guard_reach, c->guard_quadric, kname);
@@ -1839,6 +1856,7 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     if (batch) c->last_variant |= 128u;
     if (pair_kernel) c->last_variant |= 256u;
     if (pair7) c->last_variant |= 512u;
+    if (slab_kernel) c->last_variant |= 1024u;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
         c->seeds.read = 1 - c->seeds.read;

@@ -62,6 +62,8 @@ struct AnalyticScene {
         int tree_spheres = 0;              // every primitive of the tree is a sphere
         bool pair = false;                 // the tree is node 0 over the leaves 1 and 2, both certified cuboids: what render_pair_kernel walks
         int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
+        bool slab_list = false;            // the list's cuboid also holds the slab certificate (cuboid_slab)
+        int slab_leaves = 0;               // ... and so do the pair kernels' leaves: bit 0 node 1, bit 1 node 2 (0 when `pair` is false)
         float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
         // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and
         // for each (emitter, wall) pair k = 6 e + g the least y_g over the emitter's corners and the coefficients of the margin it

@@ -562,6 +562,7 @@ struct Pred<false> {
     static __device__ __forceinline__ T ult(unsigned int a, unsigned int b) { return a < b; }
     static __device__ __forceinline__ T of(bool b) { return b; }
     static __device__ __forceinline__ T inv(T a) { return !a; }
+    static __device__ __forceinline__ T andnot(T a, T b) { return a & !b; }
     static __device__ __forceinline__ T either(T a, T b) { return a || b; }
     static __device__ __forceinline__ T differ(T a, T b) { return a != b; }
     static __device__ __forceinline__ bool lane(T a) { return a; }
@@ -840,6 +841,92 @@ __device__ __forceinline__ void cuboid_range(Ptr fp, const float4* __restrict__ 
     }
 }
 
+// cuboid_range's successor for a cuboid that also holds the SLAB certificate (rtgo_build.h, slab_certify): in the object frame of the
+// group's first face -- rows 0..2 of its record -- the six faces are the planes of one axis-aligned box [lo, hi].  One transform of the
+// ray into that frame and a slab test say which face the ray can meet at all -- a box seen from outside: the face of the axis entered
+// LAST, on the side the ray comes from; a room seen from inside: the face of the axis left FIRST, on the side the ray goes to -- and
+// only that face gets the reference's test (kernel.cu:372-416, through rect_commit: the same operations on the same values as a single
+// test, so an accepted hit is bit for bit the reference's).  The frame arithmetic only steers (fused multiply-adds, the hardware
+// reciprocal): what it must never do is leave out a face the reference accepts, and the margins see to that.  With mu = the launch's
+// cuboid margin (rtgo_capi.hip, cub_mu: the certificate's tolerance plus the rounding of coordinates within the launch's reach) carried
+// into frame units by the certificate's rho: the slabs are widened by mu; the plane of axis a is met somewhere in [m - w, m + w], m the
+// plane's parameter as computed and w = mu |1 / d_a|; the face is a candidate iff that interval meets the other two widened slabs'
+// [entry, exit].  A grazing ray (|1 / d_a| large) makes more candidates, never fewer, and so does a NaN (the compares are the
+// complements of "certainly not"); two candidates (near an edge) are tested one after the other.  A ray all but parallel to a pair of
+// faces (|d_a| <= the certificate's threshold, 2e-5 of the longest axis row: below that a face's own d.y, from its own matrix, could
+// have the other sign) takes the six single tests instead, like cuboid_range's `both` lanes.
+// The certificate's numbers ride in the words z, w of row 3 of the group's records: record a (a = 0, 1, 2) the bounds (lo, hi) of frame
+// axis a, record 3 (map, rho), record 4 (the parallel threshold, 0).  map: three bits per plane, the face's offset in the group, low
+// plane of axis 0 first.
+// KIND: kCubBox or kCubRoom (the kernel knows which when it is compiled).  MASK: the predicates' carrier (Pred).
+template <bool LIST, CubKind KIND, bool MASK = false, typename Ptr>
+__device__ __forceinline__ void cuboid_slab(Ptr fp, const float4* __restrict__ lds, int first, float mu_launch, v3 wo, v3 wd, float tmin, FastHit& best)
+{
+    static_assert(KIND != kCubEither, "the slab test is compiled for a box or for a room");
+    constexpr bool ROOM = KIND == kCubRoom;
+    typedef Pred<MASK> P;
+    typedef typename P::T B;
+    // (the certificate's words: the upper half of a record's row 3)
+    auto cert = [&](int rec) { return reinterpret_cast<const float2*>(fp + 4 * rec + 3)[1]; };
+    const float2 m3 = cert(first + 3);
+    const int map = __float_as_int(m3.x);
+    const float mu = mu_launch * m3.y, thr = cert(first + 4).x;
+    // per axis two numbers stay: the plane's parameter as computed (box: the entry, room: the exit) and w with the sign of d_a; E, X: the
+    // latest entry and the earliest exit over the three widened slabs.  An axis's own entry is never past its own interval and its own
+    // exit never before it, so "meets the OTHER slabs" is a compare against E and X themselves.
+    float tp[3], ws[3], E = -INFINITY, X = INFINITY;
+    B flat = P::off();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float4 r = fp[4 * first + a];
+        const float2 m = cert(first + a);
+        const float da = fmaf(r.x, wd.x, fmaf(r.y, wd.y, r.z * wd.z));
+        const float oa = fmaf(r.x, wo.x, fmaf(r.y, wo.y, fmaf(r.z, wo.z, r.w)));
+        flat = flat | P::le(fabsf(da), thr);
+        const float ia = __builtin_amdgcn_rcpf(da);
+        const float noia = -(oa * ia);
+        const float tl = fmaf(m.x, ia, noia), th = fmaf(m.y, ia, noia);
+        ws[a] = mu * ia;
+        const float tn = fminf(tl, th), tf = fmaxf(tl, th);
+        E = fmaxf(E, tn - fabsf(ws[a]));
+        X = fminf(X, tf + fabsf(ws[a]));
+        tp[a] = ROOM ? tf : tn;
+    }
+    B s0, s1, s2;
+    s0 = P::andnot(P::not_lt(tp[0] + fabsf(ws[0]), E) & P::not_lt(X, tp[0] - fabsf(ws[0])), flat);
+    s1 = P::andnot(P::not_lt(tp[1] + fabsf(ws[1]), E) & P::not_lt(X, tp[1] - fabsf(ws[1])), flat);
+    s2 = P::andnot(P::not_lt(tp[2] + fabsf(ws[2]), E) & P::not_lt(X, tp[2] - fabsf(ws[2])), flat);
+#pragma unroll 1
+    for (;;) {
+        const B any = s0 | s1 | s2;
+        if (P::none(any)) break;
+        // the lowest candidate axis, and its plane on the side the ray's sign gives: a box is entered through the side the ray comes from
+        // (d_a > 0: the low plane), a room is left through the side it goes to (d_a > 0: the high plane)
+        const int sg = __float_as_int(P::lane(s0) ? ws[0] : (P::lane(s1) ? ws[1] : ws[2])) >> 31;   // (-1: d_a < 0)
+        const int sh = (P::lane(s0) ? 0 : (P::lane(s1) ? 6 : 12)) + ((ROOM ? ~sg : sg) & 3);
+        const int ps = first + ((map >> sh) & 7);
+        s2 = s2 & (s0 | s1);
+        s1 = s1 & s0;
+        s0 = P::off();
+        const float4 r1 = lds[4 * ps + 1];
+        const int orig = __float_as_int(lds[4 * ps + 3].y);
+        const float dy = r1.x * wd.x + r1.y * wd.y + r1.z * wd.z;
+        rect_commit<MASK>(lds + 4 * ps, r1, dy, any & P::lt(dy, 0.0f), ps, orig, wo, wd, tmin, best);
+    }
+    // (last, so that nothing but the mask lives across it: the closest hit does not depend on the order of the tests, closer())
+    // (the six records are rectangles, or the group held no cuboid certificate: leaf_test's rectangle branch on each)
+    if (P::any(flat)) {
+#pragma unroll 1
+        for (int k = 0; k < 6; ++k) {
+            const int ps = first + k;
+            const float4 r1 = lds[4 * ps + 1];
+            const int orig = __float_as_int(lds[4 * ps + 3].y);
+            const float dy = r1.x * wd.x + r1.y * wd.y + r1.z * wd.z;
+            rect_commit<MASK>(lds + 4 * ps, r1, dy, flat & P::lt(dy, 0.0f), ps, orig, wo, wd, tmin, best);
+        }
+    }
+}
+
 // conservative slab test: t = fma(b, 1/d, -o/d) with the hardware reciprocal
 template <bool MASK = false>
 __device__ __forceinline__ typename Pred<MASK>::T box_fast(const float4 q0, const float4 q1, v3 id, v3 noid, float tmin, float tmax, float& tn_out)
@@ -870,7 +957,7 @@ __device__ __forceinline__ typename Pred<MASK>::T box_fast(const float4 q0, cons
 // lane than the other two: profiles/r02f/README.md).  fast_list: the up-front list, which also gives the ray its first closest-hit bound.
 // LAST, `last`: the lane's ray is the last of its path under the last-ray certificate (closest_hit_fast): it skips the room.
 // KIND: kCubRoom when the launch vouches for a list that starts with a certified room (the pair kernels), else kCubEither (list_cub says).
-template <bool LAST = false, CubKind KIND = kCubEither, bool MASK = false>
+template <bool LAST = false, CubKind KIND = kCubEither, bool MASK = false, bool SLAB = false>
 __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, const float4* __restrict__ g_fprims, int n_small, int n_prims, int n_big_pairs,
                                           int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, typename Pred<MASK>::T last = Pred<MASK>::off())
 {
@@ -882,7 +969,9 @@ __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, c
         // the room's six walls (or one big box) as a cuboid, the rest of the list after them
         if (!LAST || Pred<MASK>::any(Pred<MASK>::inv(last))) {
             const bool box = KIND == kCubEither && list_cub == 1;
-            if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) cuboid_range<true, KIND, MASK>(g_fprims, s_fprims, n_small, box ? cub_mu : INFINITY, box ? -INFINITY : -cub_mu, o, d, tmin, best);
+            if constexpr (SLAB) {
+                if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) cuboid_slab<true, KIND, MASK>(g_fprims, s_fprims, n_small, cub_mu, o, d, tmin, best);
+            } else if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) cuboid_range<true, KIND, MASK>(g_fprims, s_fprims, n_small, box ? cub_mu : INFINITY, box ? -INFINITY : -cub_mu, o, d, tmin, best);
         }
         leaf_range<true, MASK>(g_fprims, s_fprims, n_small + 6, n_prims - n_small - 6, 0, o, d, tmin, best);
     } else {
@@ -994,7 +1083,7 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
 // <= the closest hit.  What is gone is the machinery of a deep tree: the root's own box test (the root box is the union of the two, and
 // fma(q, id, noid) is monotone in q: a lane that passes a child's slab test passes the root's), the while-while loop, the stack word
 // in LDS, the pop loop with its dependent reads of a node's links, and the leaf's dispatch on tree_spheres / leaf_cuboid / cub_mu.
-template <bool MASK>
+template <bool MASK, bool SLAB = false>
 __device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims, float cub_mu, v3 o, v3 d, float tmin, FastHit& best,
                                           unsigned int& dbg_boxes, unsigned int& dbg_tests)
 {
@@ -1019,13 +1108,16 @@ __device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, c
     if (P::lane(hl | hr)) {
         FastCounters::step(dbg_tests, (unsigned int)leaf_count(__float_as_int(right ? h1.w : l1.w)));
         // (the near leaf keeps the bool carrier: as masks its predicates cost render_pair7_kernel ten more SGPR spills than its budget has)
-        cuboid_range<false, kCubBox, false>(s_fprims, s_fprims, __float_as_int(right ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
+        // (cuboid_slab's predicates fit the seven-waves budget as masks here too: 3 SGPR spills in render_slab7_kernel, none in the ray loop)
+        if constexpr (SLAB) cuboid_slab<false, kCubBox, MASK>(s_fprims, s_fprims, __float_as_int(right ? h0.w : l0.w), cub_mu, o, d, tmin, best);
+        else cuboid_range<false, kCubBox, false>(s_fprims, s_fprims, __float_as_int(right ? h0.w : l0.w), cub_mu, -INFINITY, o, d, tmin, best);
     }
     const B far = two & P::le(t_far, best.t);
     if (P::any(far)) {
         if (P::lane(far)) {
             FastCounters::step(dbg_tests, count_far);
-            cuboid_range<false, kCubBox, MASK>(s_fprims, s_fprims, first_far, cub_mu, -INFINITY, o, d, tmin, best);
+            if constexpr (SLAB) cuboid_slab<false, kCubBox, MASK>(s_fprims, s_fprims, first_far, cub_mu, o, d, tmin, best);
+            else cuboid_range<false, kCubBox, MASK>(s_fprims, s_fprims, first_far, cub_mu, -INFINITY, o, d, tmin, best);
         }
     }
 }
@@ -1161,7 +1253,7 @@ __device__ __forceinline__ bool fast_winner(const float4* __restrict__ s_fprims,
 // order in which candidates are met (closer()).  LAST: the instantiation has this path at all (else `last` is ignored).
 // PAIR (render_pair_kernel): the tree is a root over two cuboid leaves, walked by fast_pair.
 // MASK: the carrier of `last` and of the walk's predicates from here down (Pred); the pair kernels' ray loop alone sets it.
-template <bool GRID, bool LAST = false, bool PAIR = false, bool MASK = false>
+template <bool GRID, bool LAST = false, bool PAIR = false, bool MASK = false, bool SLAB = false>
 __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims,
                                                  const float4* __restrict__ g_fprims, const GridParams grid,
  unsigned int* __restrict__ s_stack, int bshift,
@@ -1169,18 +1261,19 @@ __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fn
                                                  unsigned int& dbg_boxes, unsigned int& dbg_tests, typename Pred<MASK>::T last, Timeline& tl)
 {
     static_assert(!MASK || PAIR, "the lane-mask predicates are the pair kernels'");
+    static_assert(!SLAB || PAIR, "the slab test serves the pair kernels' launches");
     tl.walk_begin();
     FastHit best;
     best.t = tmax;
     best.pos = -1;
     best.orig = -1;
-    fast_list<LAST, PAIR ? kCubRoom : kCubEither, MASK>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
+    fast_list<LAST, PAIR ? kCubRoom : kCubEither, MASK, SLAB>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
     const bool walk = Pred<MASK>::lane(Pred<MASK>::either(Pred<MASK>::inv(last), Pred<MASK>::ige(best.pos, 0)));
     FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (Pred<MASK>::lane(last) ? 6 : 0)));
     tl.list_done(best.pos);
     if constexpr (GRID) fast_grid(s_fnodes, s_fprims, grid, tree_spheres, o, d, tmin, best, dbg_boxes, dbg_tests);
     else if constexpr (PAIR) {
-        if (!LAST || walk) fast_pair<MASK>(s_fnodes, s_fprims, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests);
+        if (!LAST || walk) fast_pair<MASK, SLAB>(s_fnodes, s_fprims, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests);
     } else if (!LAST || walk) fast_tree(s_fnodes, s_fprims, s_stack, bshift, n_small, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, tree_spheres);
     tl.walk_done(best.pos);
     return fast_winner(s_fprims, o, d, tmax, best, out);
@@ -1447,7 +1540,7 @@ __device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned
 template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false, bool GLOBAL = false>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = false, PAIR = false;
+    constexpr bool BATCH = false, PAIR = false, SLAB = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1455,7 +1548,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <bool PATH, int WPE, bool FRAMES>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_frames_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false;
+    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false, SLAB = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1465,7 +1558,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <int WPE>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_pair_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1474,7 +1567,16 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 // template above stays at its two instantiations.
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_pair7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false;
+    constexpr int WPE = 7;
+#include "rtgo_render_body.inc"
+}
+
+// render_pair7_kernel with the slab test (cuboid_slab) in cuboid_range's place, for the room and for both leaves: launches whose room and
+// leaves hold the slab certificate (rtgo_build.h).  The one form of the cuboid test in the kernel is the slab's.
+__global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_slab7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
+{
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true;
     constexpr int WPE = 7;
 #include "rtgo_render_body.inc"
 }

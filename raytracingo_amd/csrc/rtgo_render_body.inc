@@ -1,6 +1,7 @@
 // rtgo_render_body.inc -- the body of the render megakernel (rtgo_device.h has the account of it), a textual fragment like the three it
-// includes: render_kernel, render_frames_kernel and render_pair_kernel are this text under their own template parameters.  Expects p_arg, g_fprims and the
-// constants PATH, STATS, WPE, STREAM, COUNT, FRAMES, GRID, GLOBAL, BATCH, PAIR in scope.
+// includes: render_kernel, render_frames_kernel, render_pair_kernel and render_slab7_kernel are this text under their own template parameters.  Expects
+// p_arg, g_fprims and the constants PATH, STATS, WPE, STREAM, COUNT, FRAMES, GRID, GLOBAL, BATCH, PAIR, SLAB in scope (SLAB: the pair kernels' cuboid
+// tests are cuboid_slab's; render_slab7_kernel alone sets it).
     const LaunchParams& p = p_arg;
     static_assert(!BATCH || (!STATS && !STREAM && !GRID && WPE <= 5), "frames are batched by the lock-step kernels over a tree, at 4 and 5 waves");
     static_assert(!GLOBAL || (STATS && !FRAMES && !GRID && !STREAM), "the global-memory scene is walked by the canonical walk alone");

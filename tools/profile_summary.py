@@ -4,11 +4,12 @@ import collections, csv, glob, json, os, sys
 d, tag = sys.argv[1], sys.argv[2]
 KERNEL = "render_kernel<true, false"   # any register-budget variant of the timed path-mode kernel ...
 PAIR = "render_pair_kernel<"           # ... or of the one that walks a two-leaf tree (cornell)
-PAIR7 = "render_pair7_kernel"          # ... at seven waves per SIMD (the bench launch)
+PAIR7 = "render_pair7_kernel"          # ... at seven waves per SIMD
+SLAB = "render_slab"                   # ... with the slab test of a certified cuboid (the bench launch)
 
 
 def timed(name):
-    return KERNEL in name or PAIR in name or PAIR7 in name
+    return KERNEL in name or PAIR in name or PAIR7 in name or SLAB in name
 
 
 head = os.environ.get("RTGO_HEAD")   # the commit the profiled tree is (the GPU box has no .git); a re-run of this script keeps what the first run recorded
