@@ -179,6 +179,37 @@ enum { RTGO_UPDATE_REFIT = 0, RTGO_UPDATE_REBUILD = 1 };
 int rtgo_update_prims(rtgo_ctx* ctx, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n_updates,
                       uint32_t flags);
 
+/* rtgo_set_scene, rtgo_set_large_scene and rtgo_update_prims for records that are already on the device (under OptiX the AABB buffer of a
+   build input and the SBT are device pointers): a particle system's or a rigid-body step's output, a PyTorch-ROCm tensor.  d_prims =
+   rtgo_prim[n] (108 bytes each, the host struct's layout), d_aabbs = rtgo_aabb[n] or NULL under the twin's rule, d_indices =
+   uint32[n_updates]: DEVICE memory of the context's device, caller-owned, 4-byte aligned, overlapping nothing of the context; the calls read
+   them and never write to them.  The caller's writes to them must be complete, or ordered on the context's stream (rtgo_set_stream),
+   before the call.  Beyond NULL and alignment the call cannot tell whether a pointer is good: that the buffers are device memory of the
+   sizes given is the caller's to vouch for, as in the ray-query calls.
+   Afterwards the context holds, array for array, what the host-pointer twin holds after the same data, so frames, rtgo_trace_rays,
+   rtgo_shade_rays and the ray counters of rtgo_stats are equal bit for bit; what the twin keeps or drops (camera, lights, background,
+   output and stream kept; the screen-rectangle mask, the pre-hashed seeds and the launch-time trial dropped) is kept or dropped alike.
+   No copy in proportion to n or n_updates crosses the host in either direction for a scene of rtgo_set_large_scene: the data is checked
+   where it lies by one launch (each workgroup stages its 256 records in LDS with coalesced loads), whose verdict -- 32
+   bytes: per kind of fault the lowest offending entry -- is read back with one wait; then the twin's own kernels build, refit or rebuild
+   from the caller's pointers.  What else crosses is what the twin reads back (the tree's depth, the root box, a refit's `changed` word).
+   A scene of rtgo_set_scene (n <= RTGO_MAX_PRIMS) keeps a host copy of its records for its certificates: there, and only there, the
+   context's n records are read back once.  The index check of rtgo_update_prims_device keeps one word per primitive on the device,
+   allocated by a scene's first such call.
+   Refusals are the twins', with the twins' codes.  Decided on the host, before any launch -- RTGO_E_INVALID: NULL ctx, d_prims or
+   d_indices, a pointer that is not 4-byte aligned, unknown flag bits, d_aabbs given or NULL against the scene, n_updates above the
+   scene's count (an index then repeats or lies beyond it); RTGO_E_UNSUPPORTED: n outside the twin's range; RTGO_E_STATE: no analytic
+   scene; n_updates == 0 with a scene and known flags: RTGO_OK, nothing changes.  Found on the device, all RTGO_E_INVALID: an unknown
+   type, a value among a record's 26 floats that is not finite, a model matrix the twin calls singular (the same determinant, in double,
+   against the same bound), a box that is empty or not finite, an index >= the scene's count, an index named twice.  rtgo_last_error
+   names the kind of fault and the number of the lowest offending entry (of an index named twice: of one of the entries that name it).
+   A refused call leaves the scene as it was: every check of every entry runs, and its verdict is read, before anything of the scene is
+   written -- for the set calls too, which keep the old scene when they refuse an array, as their twins do.  The one refusal known only
+   after a build (RTGO_E_UNSUPPORTED, a tree deeper than the walk's stack) behaves as in the twin.  Synchronous. */
+int rtgo_set_scene_device(rtgo_ctx* ctx, const void* d_prims, const void* d_aabbs, uint32_t n);
+int rtgo_set_large_scene_device(rtgo_ctx* ctx, const void* d_prims, const void* d_aabbs, uint32_t n);
+int rtgo_update_prims_device(rtgo_ctx* ctx, const void* d_indices, const void* d_prims, const void* d_aabbs, uint32_t n_updates, uint32_t flags);
+
 /* raygen SBT record: Renderer::CreateRayGen / SyncCameraToSbt (renderer.cpp:321-336, 719-731); device::CameraData */
 int rtgo_set_camera(rtgo_ctx* ctx, const float eye[3], const float U[3], const float V[3], const float W[3]);
 

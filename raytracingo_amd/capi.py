@@ -28,6 +28,7 @@ SYMBOLS = [
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
     "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
     "rtgo_shade_rays", "rtgo_update_prims", "rtgo_whitted_update_meshes_device",
+    "rtgo_set_scene_device", "rtgo_set_large_scene_device", "rtgo_update_prims_device",
 ]
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
@@ -156,6 +157,9 @@ def load():
     L.rtgo_set_scene.argtypes = [vp, C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32]
     L.rtgo_set_large_scene.argtypes = [vp, C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32]
     L.rtgo_update_prims.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(Prim), C.POINTER(Aabb), C.c_uint32, C.c_uint32]
+    L.rtgo_set_scene_device.argtypes = [vp, vp, vp, C.c_uint32]
+    L.rtgo_set_large_scene_device.argtypes = [vp, vp, vp, C.c_uint32]
+    L.rtgo_update_prims_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_set_camera.argtypes = [vp, fp, fp, fp, fp]
     L.rtgo_set_background.argtypes = [vp, fp]
     L.rtgo_set_lights.argtypes = [vp, C.POINTER(Light), C.c_int]
@@ -321,6 +325,32 @@ class Context:
                                                 bb.ctypes.data_as(C.POINTER(Aabb)) if bb is not None else None, k,
                                                 UPDATE_REBUILD if rebuild else UPDATE_REFIT),
                     "rtgo_update_prims")
+
+    # ---- the same three calls for records a device already holds (torch tensors; see device_prims_args and prims_tensor) ----
+    def _device_args(self, who, indices, prims, aabbs):
+        k, ptrs = device_prims_args(who, self.device, indices, prims, aabbs)
+        hip_runtime().hipDeviceSynchronize()   # (whatever stream filled the tensors: the calls run on the context's)
+        return k, [C.c_void_p(p) for p in ptrs]
+
+    def set_scene_device(self, prims, aabbs=None):
+        """rtgo_set_scene_device: prims a tensor of n rtgo_prim records (prims_tensor's layout), aabbs float32 [n, 6] or None, both on the
+        context's device.  Synchronous."""
+        n, (_, p, b) = self._device_args("set_scene_device", None, prims, aabbs)
+        self._check(self._lib.rtgo_set_scene_device(self._h, p, b, n), "rtgo_set_scene_device")
+        self.n_prims = n
+
+    def set_large_scene_device(self, prims, aabbs=None):
+        """rtgo_set_large_scene_device: set_scene_device's arguments, up to RTGO_MAX_SCENE_PRIMS records, read where they lie."""
+        n, (_, p, b) = self._device_args("set_large_scene_device", None, prims, aabbs)
+        self._check(self._lib.rtgo_set_large_scene_device(self._h, p, b, n), "rtgo_set_large_scene_device")
+        self.n_prims = n
+
+    def update_prims_device(self, indices, prims, aabbs=None, rebuild=False):
+        """rtgo_update_prims_device: primitive indices[j] becomes record prims[j] with the box aabbs[j].  indices: a contiguous int32
+        tensor [k] (its bits are read as uint32); prims, aabbs: as set_scene_device takes them, k of each; all on the context's device.
+        aabbs: given exactly when the scene was set with boxes.  rebuild: RTGO_UPDATE_REBUILD, else a refit.  Synchronous."""
+        k, (i, p, b) = self._device_args("update_prims_device", indices, prims, aabbs)
+        self._check(self._lib.rtgo_update_prims_device(self._h, i, p, b, k, UPDATE_REBUILD if rebuild else UPDATE_REFIT), "rtgo_update_prims_device")
 
     def set_camera(self, eye, U, V, W):
         a = [_f3(x) for x in (eye, U, V, W)]
@@ -736,6 +766,53 @@ def whitted_instances(instances):
         arr[i].mesh = int(mesh)
         arr[i].material_offset = int(off)
     return arr
+
+
+def device_prims_args(who, device, indices, prims, aabbs):
+    """The checks of Context.set_scene_device / set_large_scene_device / update_prims_device on their tensors (needs no context).
+    prims: contiguous, k * 108 bytes, uint8 [k, 108] or int32 / float32 [k, 27]; aabbs: contiguous float32 [k, 6] or None; indices:
+    contiguous int32 [k] or None (the set calls); all on device `device`.  Returns (k, [indices pointer or None, prims pointer, aabbs
+    pointer or None]); ValueError for a tensor that is not on that device, is not contiguous, or has another dtype, shape or byte count."""
+    given = [(name, t) for name, t in (("indices", indices), ("prims", prims), ("aabbs", aabbs)) if t is not None or name == "prims"]
+    for name, t in given:   # layout first, then where it lies: a tensor of the wrong shape is named as that on any device
+        if not hasattr(t, "data_ptr"):
+            raise ValueError("%s: %s must be a torch tensor" % (who, name))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+    rows = {"torch.uint8": 108, "torch.int32": 27, "torch.float32": 27}.get(str(prims.dtype))
+    nbytes = prims.numel() * prims.element_size()
+    if rows is None or prims.dim() != 2 or prims.shape[1] != rows:
+        raise ValueError("%s: prims must be uint8 [k, 108] or int32 / float32 [k, 27] (108 bytes per record), not %s %s (%d bytes)"
+                         % (who, prims.dtype, tuple(prims.shape), nbytes))
+    k = nbytes // 108
+    if indices is not None:
+        if str(indices.dtype) != "torch.int32" or indices.dim() != 1:
+            raise ValueError("%s: indices must be an int32 tensor [k]" % who)
+        if indices.numel() != k:
+            raise ValueError("%s: %d records (%d bytes) for %d indices" % (who, k, nbytes, indices.numel()))
+    if aabbs is not None:
+        if str(aabbs.dtype) != "torch.float32" or aabbs.dim() != 2 or aabbs.shape[1] != 6:
+            raise ValueError("%s: aabbs must be a float32 tensor [k, 6]" % who)
+        if aabbs.shape[0] != k:
+            raise ValueError("%s: %d boxes (%d bytes) for %d records" % (who, aabbs.shape[0], 24 * aabbs.shape[0], k))
+    for name, t in given:
+        if not t.is_cuda or t.device.index != device:
+            raise ValueError("%s: %s must lie on device %d, not on %s" % (who, name, device, t.device))
+    return k, [None if indices is None else indices.data_ptr(), prims.data_ptr(), None if aabbs is None else aabbs.data_ptr()]
+
+
+def prims_tensor(types, models, materials):
+    """rtgo_prim records packed with torch ops on whatever device the inputs live on: types [k] (integers), models [k, 16] (row-major),
+    materials [k, 10] = kd(3) kr(3) specularity Le(3).  Returns float32 [k, 27] whose column 0 holds the type's bits: byte for byte the
+    PRIM_DTYPE records of Context.set_large_scene, and what the *_device calls take."""
+    import torch
+    models = models.reshape(-1, 16).to(torch.float32)
+    k = models.shape[0]
+    out = torch.empty((k, 27), dtype=torch.float32, device=models.device)
+    out.view(torch.int32)[:, 0] = types.reshape(k).to(device=models.device, dtype=torch.int32)
+    out[:, 1:17] = models
+    out[:, 17:27] = materials.reshape(k, 10).to(device=models.device, dtype=torch.float32)
+    return out
 
 
 def make_frame(width, height, sqrt_spp=1, frame_count=0, path=True, ambient=False, window=None, bands=(4, 1, 0),

@@ -927,6 +927,28 @@ static int build_resident(rtgo_ctx* c, uint32_t n)
     return RTGO_OK;
 }
 
+// rtgo_set_scene and rtgo_set_scene_device from drop_scene on: n checked records (and boxes, nullable) in host memory, or (`device`) in
+// device memory -- then the host copy that emitter_cert and the quadric list read is taken from the context's own copy of them
+static int set_resident(rtgo_ctx* c, const void* prims, const void* aabbs, uint32_t n, bool device)
+{
+    const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    drop_scene(c);
+    AnalyticScene& sc = c->scene;
+    if (const int rc = alloc_resident(c, n)) return rc;
+    sc.have_aabbs = aabbs != nullptr;
+    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, n * sizeof(PrimIn), kind, c->stream));
+    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, n * sizeof(rtgo_aabb), kind, c->stream));
+    if (device) {
+        sc.host_prims.resize(n);
+        RTGO_HIP(c, hipMemcpyAsync(sc.host_prims.data(), sc.d_prims_in.get(), n * sizeof(PrimIn), hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    } else {
+        const rtgo_prim* p = static_cast<const rtgo_prim*>(prims);
+        sc.host_prims.assign(p, p + n);
+    }
+    return build_resident(c, n);
+}
+
 int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
 {
     if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene: NULL argument");
@@ -935,14 +957,7 @@ int rtgo_set_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, 
     if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_scene")) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    drop_scene(c);
-    AnalyticScene& sc = c->scene;
-    if (const int rc = alloc_resident(c, n)) return rc;
-    sc.host_prims.assign(prims, prims + n);
-    sc.have_aabbs = aabbs != nullptr;
-    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
-    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
-    return build_resident(c, n);
+    return set_resident(c, prims, aabbs, n, false);
 }
 
 // the temporaries of large_build_tree, freed however it ends
@@ -1020,27 +1035,27 @@ static void adopt_large_tree(AnalyticScene& sc, LargeTree& t)
     sc.lbvh_depth = t.lbvh_depth;
 }
 
-int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+// rtgo_set_large_scene and rtgo_set_large_scene_device from drop_scene on: n checked records (and boxes, nullable) in host memory, or
+// (`device`) in device memory -- large_prep_kernel then reads the caller's records where they lie, and no copy of them is made
+static int set_large(rtgo_ctx* c, const void* prims, const void* aabbs, uint32_t n, bool device, const std::string& what)
 {
-    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_large_scene: NULL argument");
-    if (n == 0 || n > RTGO_MAX_SCENE_PRIMS)
-        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_SCENE_PRIMS) + "]");
-    if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_large_scene")) return rc;
     const Knobs kn;
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
     drop_scene(c);
     AnalyticScene& sc = c->scene;
-    RTGO_HIP(c, sc.d_prims_in.alloc(n));
+    const PrimIn* d_in = static_cast<const PrimIn*>(prims);
+    if (!device) {
+        RTGO_HIP(c, sc.d_prims_in.alloc(n));
+        d_in = sc.d_prims_in.get();
+    }
     RTGO_HIP(c, sc.d_aabb.alloc((size_t)n * 6));
     RTGO_HIP(c, sc.d_prims.alloc((size_t)n * 6));
-    RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, (size_t)n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
-    if (aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, (size_t)n * sizeof(rtgo_aabb), hipMemcpyHostToDevice, c->stream));
+    if (!device) RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), prims, (size_t)n * sizeof(PrimIn), hipMemcpyHostToDevice, c->stream));
+    if (aabbs)
+        RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), aabbs, (size_t)n * sizeof(rtgo_aabb), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     // records and boxes, then the tree over the boxes
-    hipLaunchKernelGGL(large_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const PrimIn*)sc.d_prims_in.get(), sc.d_aabb.get(), aabbs ? 1 : 0, (int)n,
-                       sc.d_prims.get());
+    hipLaunchKernelGGL(large_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_in, sc.d_aabb.get(), aabbs ? 1 : 0, (int)n, sc.d_prims.get());
     LargeTree t;
-    if (const int rc = large_build_tree(c, sc.d_aabb.get(), n, "rtgo_set_large_scene", t)) {
+    if (const int rc = large_build_tree(c, sc.d_aabb.get(), n, what, t)) {
         if (rc == RTGO_E_UNSUPPORTED) c->scene = AnalyticScene();
         return rc;
     }
@@ -1050,8 +1065,19 @@ int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* a
     sc.n_prims = n;
     sc.large = true;
     if (kn.debug)
-        std::fprintf(stderr, "rtgo_set_large_scene: %d primitives, canonical LBVH depth %d in global memory\n", (int)n, sc.lbvh_depth);
+        std::fprintf(stderr, "%s: %d primitives, canonical LBVH depth %d in global memory\n", what.c_str(), (int)n, sc.lbvh_depth);
     return RTGO_OK;
+}
+
+int rtgo_set_large_scene(rtgo_ctx* c, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n)
+{
+    if (!c || !prims) return fail(c, RTGO_E_INVALID, "rtgo_set_large_scene: NULL argument");
+    if (n == 0 || n > RTGO_MAX_SCENE_PRIMS)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene: primitive count must be in [1, " + std::to_string(RTGO_MAX_SCENE_PRIMS) + "]");
+    if (const int rc = check_prims(c, prims, aabbs, n, "rtgo_set_large_scene")) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    return set_large(c, prims, aabbs, n, false, "rtgo_set_large_scene");
 }
 
 // ---- rtgo_update_prims ----
@@ -1071,37 +1097,49 @@ static int stage_updates(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* 
     return RTGO_OK;
 }
 
+// k checked updates where the apply kernels read them: rtgo_update_prims' staging buffers, or the arrays of rtgo_update_prims_device's
+// caller.  host_idx / host_prims: the host's copy of the first two (rtgo_update_prims), or nullptr.
+struct UpdateRefs {
+    const unsigned int* idx;
+    const PrimIn* prims;
+    const float* aabbs;   // nullptr: the scene was set without boxes
+    uint32_t k;
+    const uint32_t* host_idx;
+    const rtgo_prim* host_prims;
+};
+
 // A scene of rtgo_set_scene: a new scene from the old one's device-resident inputs with the updates patched in, built by build_resident
 // into c->scene (the caller has set the old one aside and puts it back when this fails)
-static int update_resident(rtgo_ctx* c, const AnalyticScene& old, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t k)
+static int update_resident(rtgo_ctx* c, const AnalyticScene& old, const UpdateRefs& u)
 {
-    const uint32_t n = old.n_prims;
+    const uint32_t n = old.n_prims, k = u.k;
     AnalyticScene& sc = c->scene;
     if (const int rc = alloc_resident(c, n)) return rc;
-    sc.host_prims = old.host_prims;
-    for (uint32_t j = 0; j < k; ++j) sc.host_prims[indices[j]] = prims[j];
     sc.have_aabbs = old.have_aabbs;
-    UpdateStaging st;
-    if (const int rc = stage_updates(c, indices, prims, aabbs, k, st)) return rc;
     RTGO_HIP(c, hipMemcpyAsync(sc.d_prims_in.get(), old.d_prims_in.get(), n * sizeof(PrimIn), hipMemcpyDeviceToDevice, c->stream));
     if (sc.have_aabbs) RTGO_HIP(c, hipMemcpyAsync(sc.d_aabb.get(), old.d_aabb.get(), (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    hipLaunchKernelGGL(prims_patch_kernel, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const PrimIn*)st.prims.get(),
-                       (const float*)st.aabbs.get(), (int)k, sc.d_prims_in.get(), sc.d_aabb.get());
+    hipLaunchKernelGGL(prims_patch_kernel, dim3((k + 255) / 256), dim3(256), 0, c->stream, u.idx, u.prims, u.aabbs, (int)k, sc.d_prims_in.get(), sc.d_aabb.get());
     RTGO_HIP(c, hipGetLastError());
+    if (u.host_idx) {
+        sc.host_prims = old.host_prims;
+        for (uint32_t j = 0; j < k; ++j) sc.host_prims[u.host_idx[j]] = u.host_prims[j];
+    } else {   // the updates never were on the host: the patched records, at most RTGO_MAX_PRIMS of them, are read back
+        sc.host_prims.resize(n);
+        RTGO_HIP(c, hipMemcpyAsync(sc.host_prims.data(), sc.d_prims_in.get(), n * sizeof(PrimIn), hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    }
     const int rc = build_resident(c, n);
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));   // (the staging buffers are freed on return)
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));   // (the caller frees its staging buffers on return)
     return rc;
 }
 
-// A scene of rtgo_set_large_scene, refitted or rebuilt in place
-static int update_large(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t k, bool rebuild)
+// A scene of rtgo_set_large_scene, refitted or rebuilt in place (`what`: the entry point, for the message)
+static int update_large(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const std::string& what)
 {
     AnalyticScene& sc = c->scene;
-    const uint32_t n = sc.n_prims;
+    const uint32_t n = sc.n_prims, k = u.k;
     const int n_internal = (int)n - 1;
     const dim3 g_upd((k + 255) / 256), g_int((std::max(n_internal, 1) + 255) / 256);
-    UpdateStaging st;
-    if (const int rc = stage_updates(c, indices, prims, aabbs, k, st)) return rc;
     DeviceArray<int> d_changed;
     RTGO_HIP(c, d_changed.alloc(1));
     RTGO_HIP(c, hipMemsetAsync(d_changed.get(), 0, sizeof(int), c->stream));
@@ -1111,9 +1149,9 @@ static int update_large(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* p
             sc.keep.epoch = 1;
         }
         const unsigned int epoch = sc.keep.epoch;
-        hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const PrimIn*)st.prims.get(),
-                           (const float*)st.aabbs.get(), (int)k, (const int*)sc.keep.leaf_of.get(), (const int*)sc.keep.parent.get(), epoch, sc.keep.mark.get(),
-                           sc.d_prims.get(), sc.d_aabb.get(), sc.d_nodes.get(), (float4*)nullptr, (float*)nullptr, d_changed.get());
+        hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, u.idx, u.prims, u.aabbs, (int)k, (const int*)sc.keep.leaf_of.get(),
+                           (const int*)sc.keep.parent.get(), epoch, sc.keep.mark.get(), sc.d_prims.get(), sc.d_aabb.get(), sc.d_nodes.get(), (float4*)nullptr,
+                           (float*)nullptr, d_changed.get());
         RTGO_HIP(c, hipGetLastError());
         int changed = 0;
         RTGO_HIP(c, hipMemcpyAsync(&changed, d_changed.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1138,20 +1176,44 @@ static int update_large(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* p
     DeviceArray<float> old_aabb;
     RTGO_HIP(c, old_prims.alloc((size_t)k * 6));
     RTGO_HIP(c, old_aabb.alloc((size_t)k * 6));
-    hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const PrimIn*)st.prims.get(),
-                       (const float*)st.aabbs.get(), (int)k, (const int*)nullptr, (const int*)nullptr, 0u, (unsigned int*)nullptr, sc.d_prims.get(), sc.d_aabb.get(),
-                       (float4*)nullptr, old_prims.get(), old_aabb.get(), d_changed.get());
+    hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, u.idx, u.prims, u.aabbs, (int)k, (const int*)nullptr, (const int*)nullptr, 0u,
+                       (unsigned int*)nullptr, sc.d_prims.get(), sc.d_aabb.get(), (float4*)nullptr, old_prims.get(), old_aabb.get(), d_changed.get());
     RTGO_HIP(c, hipGetLastError());
     LargeTree t;
-    if (const int rc = large_build_tree(c, sc.d_aabb.get(), n, "rtgo_update_prims", t)) {
+    if (const int rc = large_build_tree(c, sc.d_aabb.get(), n, what, t)) {
         const std::string msg = c->err;
-        hipLaunchKernelGGL(large_restore_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)st.idx.get(), (const float4*)old_prims.get(),
+        hipLaunchKernelGGL(large_restore_kernel, g_upd, dim3(256), 0, c->stream, u.idx, (const float4*)old_prims.get(),
                            (const float*)old_aabb.get(), (int)k, sc.d_prims.get(), sc.d_aabb.get());
         RTGO_HIP(c, hipStreamSynchronize(c->stream));
         c->err = msg;
         return rc;
     }
     adopt_large_tree(sc, t);
+    return RTGO_OK;
+}
+
+// The tail of rtgo_update_prims and rtgo_update_prims_device, for updates that passed every check (the stream idle): the large / resident
+// split, the old scene set aside and put back when the build is refused, and what was cached for the scene as it was dropped
+static int apply_updates(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const std::string& what)
+{
+    if (c->scene.large) {
+        if (const int rc = update_large(c, u, rebuild, what)) return rc;
+    } else {
+        // both flags: the set call's build again, into a scene of its own; the old one comes back when the build is refused
+        AnalyticScene old = std::move(c->scene);
+        c->scene = AnalyticScene();
+        c->scene.claim = std::move(old.claim);
+        if (const int rc = update_resident(c, old, u)) {
+            (void)hipStreamSynchronize(c->stream);
+            old.claim = std::move(c->scene.claim);
+            c->scene = std::move(old);
+            return rc;
+        }
+    }
+    // what was cached for the scene as it was (drop_scene's list): a primitive moved outside the old screen rectangle must not be culled
+    c->seeds = rtgo_ctx::Seeds();
+    c->mask.key.clear();
+    c->trial = rtgo_ctx::Trial();
     return RTGO_OK;
 }
 
@@ -1174,23 +1236,96 @@ int rtgo_update_prims(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* pri
     if (const int rc = check_prims(c, prims, aabbs, n_updates, "rtgo_update_prims")) return rc;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->scene.large) {
-        if (const int rc = update_large(c, indices, prims, aabbs, n_updates, (flags & RTGO_UPDATE_REBUILD) != 0)) return rc;
-    } else {
-        // both flags: the set call's build again, into a scene of its own; the old one comes back when the build is refused
-        AnalyticScene old = std::move(c->scene);
-        c->scene = AnalyticScene();
-        if (const int rc = update_resident(c, old, indices, prims, aabbs, n_updates)) {
-            (void)hipStreamSynchronize(c->stream);
-            c->scene = std::move(old);
-            return rc;
+    UpdateStaging st;
+    if (const int rc = stage_updates(c, indices, prims, aabbs, n_updates, st)) return rc;
+    const UpdateRefs u = {st.idx.get(), st.prims.get(), st.aabbs.get(), n_updates, indices, prims};
+    return apply_updates(c, u, (flags & RTGO_UPDATE_REBUILD) != 0, "rtgo_update_prims");
+}
+
+// ---- the device-pointer twins of the three calls above ----
+
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// check_prims, and with d_idx rtgo_update_prims' index rules over a scene of n primitives, for k entries in device memory: one launch of
+// prims_check_kernel, its verdict read back with one wait.  Nothing of the scene is written; the stream is idle when it returns.
+static int check_prims_device(rtgo_ctx* c, const void* d_idx, const void* d_prims, const void* d_aabbs, uint32_t k, uint32_t n, const std::string& what)
+{
+    if (!c->d_verdict.get()) RTGO_HIP(c, c->d_verdict.alloc(kVerdictWords));
+    unsigned int epoch = 0;
+    if (d_idx) {
+        AnalyticScene::Claim& cl = c->scene.claim;
+        if (cl.d.size() != n) {
+            RTGO_HIP(c, cl.d.alloc(n));
+            cl.epoch = 0;
         }
+        if (cl.epoch == 0 || ++cl.epoch == 0) {   // (a fresh array, or the counter wrapped: start over with clean words)
+            RTGO_HIP(c, hipMemsetAsync(cl.d.get(), 0, (size_t)n * sizeof(unsigned int), c->stream));
+            cl.epoch = 1;
+        }
+        epoch = cl.epoch;
     }
-    // what was cached for the scene as it was (drop_scene's list): a primitive moved outside the old screen rectangle must not be culled
-    c->seeds = rtgo_ctx::Seeds();
-    c->mask.key.clear();
-    c->trial = rtgo_ctx::Trial();
-    return RTGO_OK;
+    RTGO_HIP(c, hipMemsetAsync(c->d_verdict.get(), 0xFF, kVerdictWords * sizeof(unsigned int), c->stream));
+    hipLaunchKernelGGL(prims_check_kernel, dim3((k + 255) / 256), dim3(256), 0, c->stream, static_cast<const unsigned int*>(d_prims),
+                       static_cast<const float*>(d_aabbs), static_cast<const unsigned int*>(d_idx), k, n, epoch, c->scene.claim.d.get(), c->d_verdict.get());
+    RTGO_HIP(c, hipGetLastError());
+    unsigned int v[kVerdictWords];
+    RTGO_HIP(c, hipMemcpyAsync(v, c->d_verdict.get(), sizeof v, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    static const char* const kFault[kVerdictKinds] = {"has an unknown primitive type", "holds a value that is not finite", "has a singular model matrix",
+                                                      "has a box that is empty or not finite", "names an index beyond the scene's primitives",
+                                                      "names an index another entry names too"};
+    int kind = -1;
+    for (int q = 0; q < kVerdictKinds; ++q)
+        if (v[q] != kNoFault && (kind < 0 || v[q] < v[kind])) kind = q;
+    if (kind < 0) return RTGO_OK;
+    return fail(c, RTGO_E_INVALID, what + ": entry " + std::to_string(v[kind]) + " " + kFault[kind]);
+}
+
+int rtgo_set_scene_device(rtgo_ctx* c, const void* d_prims, const void* d_aabbs, uint32_t n)
+{
+    if (!c || !d_prims) return fail(c, RTGO_E_INVALID, "rtgo_set_scene_device: NULL argument");
+    if (!aligned4(d_prims) || !aligned4(d_aabbs)) return fail(c, RTGO_E_INVALID, "rtgo_set_scene_device: a pointer is not 4-byte aligned");
+    if (n == 0 || n > RTGO_MAX_PRIMS)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_scene_device: primitive count must be in [1, " + std::to_string(RTGO_MAX_PRIMS) + "]");
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = check_prims_device(c, nullptr, d_prims, d_aabbs, n, 0, "rtgo_set_scene_device")) return rc;
+    return set_resident(c, d_prims, d_aabbs, n, true);
+}
+
+int rtgo_set_large_scene_device(rtgo_ctx* c, const void* d_prims, const void* d_aabbs, uint32_t n)
+{
+    if (!c || !d_prims) return fail(c, RTGO_E_INVALID, "rtgo_set_large_scene_device: NULL argument");
+    if (!aligned4(d_prims) || !aligned4(d_aabbs)) return fail(c, RTGO_E_INVALID, "rtgo_set_large_scene_device: a pointer is not 4-byte aligned");
+    if (n == 0 || n > RTGO_MAX_SCENE_PRIMS)
+        return fail(c, RTGO_E_UNSUPPORTED, "rtgo_set_large_scene_device: primitive count must be in [1, " + std::to_string(RTGO_MAX_SCENE_PRIMS) + "]");
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = check_prims_device(c, nullptr, d_prims, d_aabbs, n, 0, "rtgo_set_large_scene_device")) return rc;
+    return set_large(c, d_prims, d_aabbs, n, true, "rtgo_set_large_scene_device");
+}
+
+int rtgo_update_prims_device(rtgo_ctx* c, const void* d_indices, const void* d_prims, const void* d_aabbs, uint32_t n_updates, uint32_t flags)
+{
+    const std::string what = "rtgo_update_prims_device";
+    if (!c) return fail(c, RTGO_E_INVALID, what + ": NULL context");
+    if (flags & ~(uint32_t)RTGO_UPDATE_REBUILD) return fail(c, RTGO_E_INVALID, what + ": unknown flag bits");
+    const uint32_t n = c->scene.n_prims;
+    if (n == 0) return fail(c, RTGO_E_STATE, what + ": no analytic scene (rtgo_set_scene or rtgo_set_large_scene first)");
+    if (n_updates == 0) return RTGO_OK;
+    if (!d_indices || !d_prims) return fail(c, RTGO_E_INVALID, what + ": NULL argument");
+    if (!aligned4(d_indices) || !aligned4(d_prims) || !aligned4(d_aabbs)) return fail(c, RTGO_E_INVALID, what + ": a pointer is not 4-byte aligned");
+    if ((d_aabbs != nullptr) != c->scene.have_aabbs)
+        return fail(c, RTGO_E_INVALID, what + (c->scene.have_aabbs ? ": the scene was set with boxes, the updates need theirs"
+                                                                   : ": the scene was set without boxes, the updates cannot bring any"));
+    if (n_updates > n)   // (by pigeonhole an index repeats or lies beyond the scene)
+        return fail(c, RTGO_E_INVALID, what + ": " + std::to_string(n_updates) + " updates for a scene of " + std::to_string(n) + " primitives");
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = check_prims_device(c, d_indices, d_prims, d_aabbs, n_updates, n, what)) return rc;
+    const UpdateRefs u = {static_cast<const unsigned int*>(d_indices), static_cast<const PrimIn*>(d_prims), static_cast<const float*>(d_aabbs), n_updates, nullptr,
+                          nullptr};
+    return apply_updates(c, u, (flags & RTGO_UPDATE_REBUILD) != 0, what);
 }
 
 int rtgo_set_camera(rtgo_ctx* c, const float eye[3], const float U[3], const float V[3], const float W[3])

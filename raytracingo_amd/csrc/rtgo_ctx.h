@@ -99,6 +99,12 @@ struct AnalyticScene {
         DeviceArray<unsigned int> mark;    // per internal node: the refit that last changed a box below it (`epoch` then; 0: none)
         unsigned int epoch = 0;
     } keep;
+    // rtgo_update_prims_device: one word per primitive, the call that last named it (`epoch` then; 0: none) -- how prims_check_kernel
+    // finds an index named twice.  Allocated by the scene's first such call, 4 bytes per primitive; outlives a rebuild.
+    struct Claim {
+        DeviceArray<unsigned int> d;
+        unsigned int epoch = 0;
+    } claim;
 };
 
 // An instanced scene's top level (rtgo_whitted_set_instances replaces it alone)
@@ -153,6 +159,7 @@ struct rtgo_ctx {
     DeviceArray<LightRec> d_lights;
     int n_lights = 0;
     DeviceArray<int> d_meta;               // build_kernel's meta words (one build at a time)
+    DeviceArray<unsigned int> d_verdict;   // prims_check_kernel's verdict (kVerdictWords; allocated by the first device-pointer call)
     int leaf_budget = kDefaultLeafBudget;
     bool have_camera = false;
     v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};

@@ -18,6 +18,8 @@
 //                         per level again, for the same reason
 //   large_restore_kernel  puts back the records and boxes large_update_kernel saved (a rebuild that is refused)
 //   prims_patch_kernel    a scene of rtgo_set_scene: the updates scattered into build_kernel's inputs
+// and the checks of the calls that take records, boxes and indices from device memory:
+//   prims_check_kernel    per entry: the host's check_prims rules and the index rules of rtgo_update_prims, into a verdict of a few words
 #pragma once
 
 #include "rtgo_device.h"
@@ -189,6 +191,70 @@ __global__ __launch_bounds__(256) void prims_patch_kernel(const unsigned int* __
     const size_t i = idx[j];
     prims[i] = upd[j];
     for (int a = 0; upd_aabb && a < 6; ++a) aabb[6 * i + a] = upd_aabb[6 * (size_t)j + a];
+}
+
+// ---- the checks of the device-pointer calls (rtgo_set_scene_device, rtgo_set_large_scene_device, rtgo_update_prims_device):
+// what check_prims and rtgo_update_prims decide on the host, decided where the caller's arrays lie.  The verdict is one word per kind of
+// fault, the lowest offending entry (kNoFault: none); the host fills it with kNoFault before the launch and reads it back once.
+constexpr int kPrimDwords = 27;
+static_assert(sizeof(PrimIn) == kPrimDwords * sizeof(unsigned int), "rtgo_prim is 27 dwords");
+enum { kBadType = 0, kBadFloat = 1, kBadMatrix = 2, kBadBox = 3, kBadIndex = 4, kBadTwice = 5, kVerdictKinds = 6, kVerdictWords = 8 };
+constexpr unsigned int kNoFault = 0xFFFFFFFFu;
+
+// Entry j < k: record prims[j] (27 dwords), box aabbs[j] (aabbs nullable), index idx[j] (idx nullable: the set calls).
+// A thread that read its own record from global memory would read at a stride of 27 dwords, a wave's load touching 64 scattered lines; the
+// workgroup loads its 256 records (and boxes) with coalesced dword loads into LDS instead and each thread checks its record there -- at
+// stride 27, odd, so free of bank conflicts.  The last workgroup loads the dwords of its own entries only: nothing beyond the caller's
+// k entries is read.  An index is compared with n before anything else is done with it; one in range is claimed by writing `epoch` into
+// claim[index] (n words of the scene's, stamped per call like LargeKeep::mark): whoever finds `epoch` there already is the second to name it.
+__global__ __launch_bounds__(256) void prims_check_kernel(const unsigned int* __restrict__ prims, const float* __restrict__ aabbs,
+                                                          const unsigned int* __restrict__ idx, unsigned int k, unsigned int n, unsigned int epoch,
+                                                          unsigned int* __restrict__ claim, unsigned int* __restrict__ verdict)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned int s_prim[256 * kPrimDwords];
+    __shared__ float s_box[256 * 6];
+    const unsigned int tid = threadIdx.x, base = blockIdx.x * 256u;
+    if (base >= k) return;
+    const unsigned int here = k - base < 256u ? k - base : 256u;   // this workgroup's entries
+    const unsigned int* src = prims + (size_t)base * kPrimDwords;
+    for (unsigned int d = tid; d < here * kPrimDwords; d += 256u) s_prim[d] = src[d];
+    if (aabbs) {
+        const float* bsrc = aabbs + (size_t)base * 6;
+        for (unsigned int d = tid; d < here * 6u; d += 256u) s_box[d] = bsrc[d];
+    }
+    __syncthreads();
+    const unsigned int j = base + tid;
+    unsigned int bad = 0;
+    if (tid < here) {
+        const unsigned int* r = s_prim + tid * kPrimDwords;
+        if (r[0] > 3u) bad |= 1u << kBadType;
+        bool finite = true;
+        for (int q = 1; q < kPrimDwords; ++q) finite = finite && (r[q] & 0x7F800000u) != 0x7F800000u;
+        if (!finite) bad |= 1u << kBadFloat;
+        // check_prims' determinant: the model matrix' 3x3 in double, mat3_det_inverse's expression, one rounding per operation
+        const double a00 = __uint_as_float(r[1]), a01 = __uint_as_float(r[2]), a02 = __uint_as_float(r[3]);
+        const double a10 = __uint_as_float(r[5]), a11 = __uint_as_float(r[6]), a12 = __uint_as_float(r[7]);
+        const double a20 = __uint_as_float(r[9]), a21 = __uint_as_float(r[10]), a22 = __uint_as_float(r[11]);
+        const double det = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
+        if (!isfinite(det) || fabs(det) < 1e-30) bad |= 1u << kBadMatrix;
+        if (aabbs) {
+            const float* b = s_box + tid * 6;
+            if (!(b[0] <= b[3] && b[1] <= b[4] && b[2] <= b[5]) || !isfinite(b[0] + b[1] + b[2] + b[3] + b[4] + b[5])) bad |= 1u << kBadBox;
+        }
+        if (idx) {
+            const unsigned int i = idx[j];
+            if (i >= n) bad |= 1u << kBadIndex;
+            else if (atomicExch(&claim[i], epoch) == epoch) bad |= 1u << kBadTwice;
+        }
+    }
+    // the lowest offending entry of the wave, one atomic per wave and kind
+    if (!__any(bad != 0)) return;
+    const unsigned int lane = tid & 63u;
+    for (int kind = 0; kind < kVerdictKinds; ++kind) {
+        const unsigned long long m = __ballot((bad >> kind) & 1u);
+        if (m != 0 && lane == (unsigned int)(__ffsll((long long)m) - 1)) atomicMin(&verdict[kind], j);
+    }
 }
 
 }  // namespace rtgo

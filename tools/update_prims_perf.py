@@ -6,8 +6,11 @@ CubeBox rule on the device.
       set      ms of rtgo_set_large_scene over the edited array (the yardstick: the only way to edit before rtgo_update_prims)
       refit    ms of rtgo_update_prims(RTGO_UPDATE_REFIT) over the k records
       rebuild  ms of rtgo_update_prims(RTGO_UPDATE_REBUILD) over the k records
-   All three are WALL-CLOCK times of the synchronous C call on records packed beforehand (no Python packing inside), medians of REPS calls
-   after WARM.
+      set_device, refit_device, rebuild_device
+               the same three through rtgo_set_large_scene_device and rtgo_update_prims_device, the records and indices in device memory
+               beforehand (a second line per k, each with the least and the largest of its samples; `set` again with its spread)
+   All are WALL-CLOCK times of the synchronous C call on records packed beforehand (no Python packing inside), medians of REPS calls
+   after WARM, host and device calls in the same run.
 2. Per n: a fraction of the spheres scattered to random places of the field by a refit, then the same scene rebuilt: ms per frame at W x H,
    path mode, 1 spp -- HIP-EVENT times (rtgo_stats' total_launch_ms over K launches).  The fractions grow tenfold and stop once a refitted
    frame takes over 30 ms: a refit keeps the topology chosen for the old places, every ancestor of a scattered leaf spans the way it went,
@@ -45,15 +48,23 @@ def field(n):
     return rec, side
 
 
-def median_ms(call):
-    for _ in range(WARM):
-        call(0)
+def samples_ms(call):
+    for k in range(WARM):   # (the calls alternate between two inputs: the warm-up goes through both)
+        call(k)
     ts = []
     for k in range(REPS):
         t0 = time.perf_counter()
-        call(k + 1)
+        call(WARM + k)
         ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
+    return ts
+
+
+def median_ms(call):
+    return float(np.median(samples_ms(call)))
+
+
+def spread(ts):
+    return "%8.3f ms [%.3f, %.3f]" % (float(np.median(ts)), min(ts), max(ts))
 
 
 def c_set(L, ctx, rec):
@@ -64,6 +75,29 @@ def c_set(L, ctx, rec):
 
 def c_update(L, ctx, idx, rec, flags):
     rc = L.rtgo_update_prims(ctx._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), rec.ctypes.data_as(C.POINTER(capi.Prim)), None, len(idx), flags)
+    assert rc == 0, L.rtgo_last_error(ctx._h)
+
+
+class DeviceCopy:
+    """a numpy array's bytes in device memory of the process's HIP runtime, freed with the object"""
+
+    def __init__(self, a):
+        self.H, self.p = capi.hip_runtime(), C.c_void_p()
+        a = np.ascontiguousarray(a)
+        assert self.H.hipMalloc(C.byref(self.p), a.nbytes) == 0 and self.H.hipMemcpy(self.p, a.ctypes.data, a.nbytes, 1) == 0
+
+    def __del__(self):
+        self.H.hipFree(self.p)
+
+
+def c_set_device(L, ctx, d_rec, n):
+    rc = L.rtgo_set_large_scene_device(ctx._h, d_rec.p, None, n)
+    assert rc == 0, L.rtgo_last_error(ctx._h)
+    ctx.n_prims = n
+
+
+def c_update_device(L, ctx, d_idx, d_rec, k, flags):
+    rc = L.rtgo_update_prims_device(ctx._h, d_idx.p, d_rec.p, None, k, flags)
     assert rc == 0, L.rtgo_last_error(ctx._h)
 
 
@@ -103,9 +137,20 @@ for n in (1 << 10, 1 << 18, 1 << 20):
         t_refit = median_ms(lambda j: c_update(L, ctx, idx, edits[j % 2], capi.UPDATE_REFIT))
         c_set(L, ctx, rec)
         t_rebuild = median_ms(lambda j: c_update(L, ctx, idx, edits[j % 2], capi.UPDATE_REBUILD))
-        t_set = median_ms(lambda j: c_set(L, ctx, whole[j % 2]))
+        s_set = samples_ms(lambda j: c_set(L, ctx, whole[j % 2]))
+        t_set = float(np.median(s_set))
         print("    k = %-8d set %8.3f ms   refit %8.3f ms   rebuild %8.3f ms   set/refit %6.1fx   set/rebuild %5.2fx" %
               (k, t_set, t_refit, t_rebuild, t_set / t_refit, t_set / t_rebuild), flush=True)
+        # the same calls from device memory
+        d_idx, d_edits, d_whole = DeviceCopy(idx), [DeviceCopy(e) for e in edits], [DeviceCopy(w) for w in whole]
+        c_set(L, ctx, rec)
+        s_refit_d = samples_ms(lambda j: c_update_device(L, ctx, d_idx, d_edits[j % 2], k, capi.UPDATE_REFIT))
+        c_set(L, ctx, rec)
+        s_rebuild_d = samples_ms(lambda j: c_update_device(L, ctx, d_idx, d_edits[j % 2], k, capi.UPDATE_REBUILD))
+        s_set_d = samples_ms(lambda j: c_set_device(L, ctx, d_whole[j % 2], n))
+        print("                 set %s   set_device %s   refit_device %s   rebuild_device %s" %
+              (spread(s_set), spread(s_set_d), spread(s_refit_d), spread(s_rebuild_d)), flush=True)
+        del d_idx, d_edits, d_whole
     frac, last_k = 1e-4, 0
     while frac <= 0.011:
         k = max(int(n * frac), 1)
