@@ -68,6 +68,10 @@ static RenderKernel find_kernel(bool path, bool canon, int wpe, bool stream, boo
 // five-waves forms were not built (profiles/r22a)
 static RenderKernel find_slab_kernel(int wpe) { return wpe == 7 ? render_slab7_kernel : nullptr; }
 
+// ... and the form of it that is compiled for 16 samples per pixel in workgroups of 256 threads (UNIT16, rtgo_render_body.inc): the kernel takes
+// both for granted, so the launch has to have them
+static RenderKernel find_unit16_kernel(int wpe, uint32_t nn, int block) { return (wpe == 7 && nn == 16u && block == 256) ? render_unit16_kernel : nullptr; }
+
 // window rows below y that this rank owns under the band interleave
 static uint32_t owned_rows_below(uint32_t y, uint32_t band_h, uint32_t n_ranks, uint32_t rank)
 {
@@ -100,6 +104,7 @@ struct Knobs {
     bool no_last_emitter = std::getenv("RTGO_NO_LAST_EMITTER") != nullptr;   // launches go without the last-ray certificate
     bool no_pair = std::getenv("RTGO_NO_PAIR") != nullptr;          // two-leaf trees are walked by fast_tree like every other (render_pair_kernel is not taken)
     bool no_slab = std::getenv("RTGO_NO_SLAB") != nullptr;          // the pair kernels keep cuboid_range (render_slab7_kernel is not taken)
+    bool no_unit16 = std::getenv("RTGO_NO_UNIT16") != nullptr;      // 16 spp launches of the slab kernel keep render_slab7_kernel (render_unit16_kernel is not taken)
     bool pin_big = std::getenv("RTGO_BIG_PERCENT") != nullptr;      // one fast-walk structure, of big_percent (else 36 % and 15 %)
     unsigned int big_percent = env_uint("RTGO_BIG_PERCENT", 36);
     unsigned int max_wpe = env_uint("RTGO_MAX_WPE", 0);             // cap of the waves-per-SIMD variant; 0: by the work
@@ -1967,15 +1972,19 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     // ... and with cuboid_slab where the room and both leaves also hold the slab certificate and the waves have such a kernel.  RTGO_NO_SLAB: off.
     const AnalyticScene::FastTree& walked = c->scene.tree[use_alt ? 1 : 0];
     const RenderKernel slab_kernel = (pair_kernel && !kn.no_slab && walked.slab_list && walked.slab_leaves == 3) ? find_slab_kernel(b.wpe) : nullptr;
-    const RenderKernel kernel = slab_kernel ? slab_kernel : (pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch));
+    // ... and, at 16 samples per pixel in workgroups of 256 threads, its form with both compiled in.  RTGO_NO_UNIT16: off.
+    const RenderKernel unit16_kernel = (slab_kernel && !kn.no_unit16) ? find_unit16_kernel(b.wpe, nn, b.block) : nullptr;
+    const RenderKernel kernel = unit16_kernel ? unit16_kernel : (slab_kernel ? slab_kernel : (pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch)));
     if (pair_kernel) p.stack_depth = 0;   // (fast_pair has no stack: pick_block reserved none, and the lights follow the scene directly)
     if (pair_kernel) pair_words(p);
     const bool pair7 = pair_kernel && b.wpe == 7;
     if (kn.debug) {
-        char kname[96];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
+        char kname[160];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
         // (the slab kernel is named with the pair kernel whose body it is and which RTGO_NO_SLAB=1 would run: readers of this line that
         // ask which walk a launch took -- the pair walk at these waves -- find it where they found it)
-        if (slab_kernel) std::snprintf(kname, sizeof kname, "render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
+        // (likewise the 16 spp form, named with the slab kernel whose body it is and which RTGO_NO_UNIT16=1 would run)
+        if (unit16_kernel) std::snprintf(kname, sizeof kname, "render_unit16_kernel, the 16 spp form of kernel render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
+        else if (slab_kernel) std::snprintf(kname, sizeof kname, "render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
         else if (pair7) std::snprintf(kname, sizeof kname, "render_pair7_kernel");
         else std::snprintf(kname, sizeof kname, "%s<%d>", pair_kernel ? "render_pair_kernel" : (batch ? "render_frames_kernel" : "render_kernel"), b.wpe);
         std::fprintf(stderr, "rtgo_launch: %u frame(s), %s walk%s, grid %u x %d threads, %zu B LDS, %d waves/SIMD variant, %d workgroups/CU, %u strips of %u px (%u x %u at %u,%u), %u cold segments in chunks of %u, stack %d, cuboid margin %g, guard reach %g quadric %g, kernel %s\n",
@@ -1992,6 +2001,7 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     if (pair_kernel) c->last_variant |= 256u;
     if (pair7) c->last_variant |= 512u;
     if (slab_kernel) c->last_variant |= 1024u;
+    if (unit16_kernel) c->last_variant |= 2048u;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
         c->seeds.read = 1 - c->seeds.read;

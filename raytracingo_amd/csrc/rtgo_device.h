@@ -1384,6 +1384,25 @@ __device__ __forceinline__ unsigned int opaque_lane()
     return l;
 }
 
+// x of lane Q of the caller's DPP row (the 16 lanes lane & ~15 .. lane | 15): row_newbcast, which the compiler folds into the
+// instruction that consumes it (v_add_f32_dpp).  Every lane of the wave must be enabled where it is called.
+template <int Q>
+__device__ __forceinline__ float row_bcast(float x)
+{
+    static_assert(Q >= 0 && Q < 16, "a DPP row is 16 lanes");
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + Q, 0xF, 0xF, false));
+}
+
+// color += r of lane 0, 1, ... 15 of the row, in that order (kernel.cu:232 for a pixel whose 16 samples are the row's lanes)
+template <int Q = 0>
+__device__ __forceinline__ void row_sum16(v3& color, const v3 r)
+{
+    if constexpr (Q < 16) {
+        color = vadd(color, mk(row_bcast<Q>(r.x), row_bcast<Q>(r.y), row_bcast<Q>(r.z)));
+        row_sum16<Q + 1>(color, r);
+    }
+}
+
 // The launch parameters at their place in the kernel-argument segment, through an address the compiler cannot hoist out of the
 // scope it is taken in: every field read through it is a scalar load there (SMEM, no vector issue slot).  Read through the kernel
 // argument itself, every field is loaded once at the kernel's start and held in an SGPR to the end; the 6-waves variant holds more of
@@ -1540,7 +1559,7 @@ __device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned
 template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false, bool GLOBAL = false>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = false, PAIR = false, SLAB = false;
+    constexpr bool BATCH = false, PAIR = false, SLAB = false, UNIT16 = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1548,7 +1567,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <bool PATH, int WPE, bool FRAMES>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_frames_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false, SLAB = false;
+    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false, SLAB = false, UNIT16 = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1558,7 +1577,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <int WPE>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_pair_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false, UNIT16 = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1567,7 +1586,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 // template above stays at its two instantiations.
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_pair7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false, UNIT16 = false;
     constexpr int WPE = 7;
 #include "rtgo_render_body.inc"
 }
@@ -1576,7 +1595,19 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7)
 // leaves hold the slab certificate (rtgo_build.h).  The one form of the cuboid test in the kernel is the slab's.
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_slab7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = false;
+    constexpr int WPE = 7;
+#include "rtgo_render_body.inc"
+}
+
+// render_slab7_kernel for launches of 16 samples per pixel in workgroups of 256 threads (the host checks both: rtgo_capi.hip), with what
+// such a launch fixes as compile-time values (UNIT16): a unit is 4 pixels x 16 samples in one pass, so a lane's pixel and sample are a
+// shift and a mask, a sample's start is the table's, and a pixel's 16 samples are one DPP row -- the in-order sum is 16 row-broadcast
+// additions per channel (row_sum16) in place of 16 dependent LDS round trips; a level record's three words lie at fixed offsets from
+// one address.  The same float operations on the same values in the same order: the same bits.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_unit16_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
+{
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = true;
     constexpr int WPE = 7;
 #include "rtgo_render_body.inc"
 }

@@ -46,7 +46,12 @@
                         } else if (depth < p.max_depth) {
                             const v3 Ra = hemisphere<true>(N, N, 0.0f, seed, FRAMES, Xf);
                             const v3 wk = vadd(mk(0.0f, 0.0f, 0.0f), vscale(mk(m3.x, m3.y, m3.z), vdot(N, Ra)));
-                            if constexpr (LVLDS) {
+                            if constexpr (UNIT16) {
+                                float* lv = s_lv + depth * (LVW * 256);   // (bshift is 8: one address, the three words at fixed offsets)
+                                lv[0] = wk.x;
+                                lv[256] = wk.y;
+                                lv[512] = wk.z;
+                            } else if constexpr (LVLDS) {
                                 s_lv[(depth * LVW + 0) << bshift] = wk.x;
                                 s_lv[(depth * LVW + 1) << bshift] = wk.y;
                                 s_lv[(depth * LVW + 2) << bshift] = wk.z;

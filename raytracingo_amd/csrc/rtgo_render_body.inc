@@ -1,7 +1,8 @@
 // rtgo_render_body.inc -- the body of the render megakernel (rtgo_device.h has the account of it), a textual fragment like the three it
-// includes: render_kernel, render_frames_kernel, render_pair_kernel and render_slab7_kernel are this text under their own template parameters.  Expects
-// p_arg, g_fprims and the constants PATH, STATS, WPE, STREAM, COUNT, FRAMES, GRID, GLOBAL, BATCH, PAIR, SLAB in scope (SLAB: the pair kernels' cuboid
-// tests are cuboid_slab's; render_slab7_kernel alone sets it).
+// includes: render_kernel, render_frames_kernel, render_pair_kernel, render_slab7_kernel and render_unit16_kernel are this text under their own template
+// parameters.  Expects p_arg, g_fprims and the constants PATH, STATS, WPE, STREAM, COUNT, FRAMES, GRID, GLOBAL, BATCH, PAIR, SLAB, UNIT16 in scope (SLAB:
+// the pair kernels' cuboid tests are cuboid_slab's; render_slab7_kernel and render_unit16_kernel set it.  UNIT16: the launch has 16 samples per pixel and
+// workgroups of 256 threads, and what follows from the two is compile-time; render_unit16_kernel alone sets it).
     const LaunchParams& p = p_arg;
     static_assert(!BATCH || (!STATS && !STREAM && !GRID && WPE <= 5), "frames are batched by the lock-step kernels over a tree, at 4 and 5 waves");
     static_assert(!GLOBAL || (STATS && !FRAMES && !GRID && !STREAM), "the global-memory scene is walked by the canonical walk alone");
@@ -19,8 +20,9 @@
     const float4* s_frame = s_frame_w;
     float2* s_stack_base = reinterpret_cast<float2*>(s_end);
     const int stack_depth = (STATS && !GLOBAL) ? kStackDepth : p.stack_depth;
-    const int kBlock = (int)blockDim.x;           // 256, 512 or 1024
-    const int bshift = 31 - __clz(kBlock);        // per-lane stack entry e lives at [e << bshift]
+    static_assert(!UNIT16 || (PAIR && PATH && !STREAM && !BATCH && !STATS && WPE >= 6), "16 samples in one DPP row: the lean lock-step pair kernels");
+    const int kBlock = UNIT16 ? 256 : (int)blockDim.x;           // 256, 512 or 1024
+    const int bshift = UNIT16 ? 8 : 31 - __clz(kBlock);          // per-lane stack entry e lives at [e << bshift]
     // (entries x workgroup size x 8 bytes for the canonical walk, x 4 for the fast walk's packed words: a multiple of 1 KiB either way)
     LightRec* s_lights = reinterpret_cast<LightRec*>(reinterpret_cast<unsigned char*>(s_stack_base) + (size_t)stack_depth * kBlock * (STATS ? 8 : 4));
     const float4* s_mat = s_mat_w;
@@ -51,7 +53,8 @@
     // k alone: a table instead of ~70 instructions of squaring loop and an integer division wherever a sample starts (most of a primary ray's
     // cost where primary rays are most rays: plateau 4K spp 256 17.2 -> 16.4 ms, mirror_spheres 4K spp 64 14.6 -> 14.3, cornell -1 %)
     uint4* s_tab = reinterpret_cast<uint4*>(s_cam + CAMW);
-    const unsigned int n_tab = (unsigned int)(p.sqrt_spp * p.sqrt_spp) < (unsigned int)kSampleTab ? (unsigned int)(p.sqrt_spp * p.sqrt_spp) : (unsigned int)kSampleTab;
+    const unsigned int n_tab = UNIT16 ? 16u : ((unsigned int)(p.sqrt_spp * p.sqrt_spp) < (unsigned int)kSampleTab ? (unsigned int)(p.sqrt_spp * p.sqrt_spp) : (unsigned int)kSampleTab);
+    static_assert(kSampleTab >= 16, "UNIT16 starts every sample from the table");
     float* s_lv = s_cam + CAMW + 4 * n_tab + threadIdx.x;
     // STREAM: the payload window of this wave (4 passes x 3 channels x 64 lanes), behind the level records
     float* s_sh = s_cam + CAMW + 4 * n_tab + (int)blockDim.x * LVW * kMaxLevels + 9 * threadIdx.x;
@@ -107,8 +110,8 @@
     constexpr bool SEEDS = kernel_has_seed_pass(STATS, WPE, STREAM);
     auto lane_index = [&]() { return LEAN ? opaque_lane() : (unsigned int)lane; };
     auto frame_ratio = [&]() { return LEAN ? s_cam[16] : 1.0f / (float)(p.frame + 1); };
-    const unsigned int nn = (unsigned int)(p.sqrt_spp * p.sqrt_spp);
-    auto inv_nn = [&]() { return LEAN ? s_cam[17] : 1.0f / (float)nn; };
+    const unsigned int nn = UNIT16 ? 16u : (unsigned int)(p.sqrt_spp * p.sqrt_spp);
+    auto inv_nn = [&]() { return UNIT16 ? 0.0625f : (LEAN ? s_cam[17] : 1.0f / (float)nn); };   // (1.0f / 16.0f, as s_cam[17] holds it)
     // Work decomposition: ONE LANE = ONE PATH.  A wave takes "units" of 64/nn_eff neighbouring pixels of a row and runs
     // nn_eff = min(nn, 16) samples of each side by side, in ceil(nn / nn_eff) passes.  The samples of a pixel are independent
     // given the LCG state their jitter starts from (trace passes the seed by value, kernel.cu:46-79), which is the pixel's
@@ -116,7 +119,9 @@
     // for bit what the reference's sequential loop gives.  Against one-lane-per-pixel this keeps the 64 lanes at the same
     // bounce, and makes the unit of scheduling 16x smaller at 16 spp (the frame has only ~2 in-scene 64-pixel tiles per
     // resident wave: whole waves idle behind the last ones, and with the frame split over 8 GPUs most waves never get one).
-    const unsigned int nn_eff = nn < (unsigned int)kSamplesPerPass ? nn : (unsigned int)kSamplesPerPass;  // samples of one pixel that share a pass
+    // (UNIT16: nn_eff = 16, P = 4 and passes = 1 are constants: the divisions below are shifts and masks, pl < P always holds, the pass loop is gone)
+    static_assert(!UNIT16 || kSamplesPerPass == 16, "UNIT16: a pixel's samples of a pass are one DPP row");
+    const unsigned int nn_eff = UNIT16 ? 16u : (nn < (unsigned int)kSamplesPerPass ? nn : (unsigned int)kSamplesPerPass);  // samples of one pixel that share a pass
     const unsigned int P = 64u / nn_eff;                        // pixels per unit
     const unsigned int passes = (nn + nn_eff - 1u) / nn_eff;
     const unsigned int pl0 = (unsigned int)lane / nn_eff;        // this lane's pixel within the unit (LEAN: derived where used)
@@ -241,7 +246,7 @@
         const unsigned int lane_p = lane_index();
         const unsigned int pl = LEAN ? lane_p / nn_eff : pl0, kl = LEAN ? lane_p - pl * nn_eff : kl0;
         const unsigned int lx = LEAN ? strip_x0 + ui * P + pl : lx_u;
-        const bool in_range = LEAN ? (pl < P && lx < p.w) : in_range_u;
+        const bool in_range = LEAN ? ((UNIT16 || pl < P) && lx < p.w) : in_range_u;
         const float fx = LEAN ? (float)(p.x0 + lx) : fx_u;
         const unsigned int pix0 = LEAN ? (unsigned int)__shfl((int)strip_seed, (int)((ui * P + pl) & 63u), 64) : pix0_u;
         const unsigned int k = pass * nn_eff + kl;   // sample index: i-major, k = i*N + j (kernel.cu:206-208)
@@ -286,6 +291,12 @@
                 const float4 m5 = s_mat[MS * ended_in + 2];
                 term = mk(m5.x, m5.y, m5.z);
             }
+            if constexpr (UNIT16) {
+                // (bshift is 8: level k's words are s_lv[768 k], [768 k + 256], [768 k + 512], fixed offsets from the lane's own address)
+#pragma unroll
+                for (int k = kMaxLevels - 1; k >= 0; --k)
+                    if (k < depth) term = vmul(mk(s_lv[(k * LVW + 0) * 256], s_lv[(k * LVW + 1) * 256], s_lv[(k * LVW + 2) * 256]), term);
+            } else
             for (int k = depth - 1; k >= 0; --k)
                 term = vmul(mk(s_lv[(k * LVW + 0) << bshift], s_lv[(k * LVW + 1) << bshift], s_lv[(k * LVW + 2) << bshift]), term);
             result = term;
@@ -298,11 +309,21 @@
             // every primary ray of the unit missed: all payloads are the background colour, no lane exchange needed
             for (unsigned int q = 0; q < cnt; ++q) color = vadd(color, p.bg);
         } else {
+            if constexpr (UNIT16) {
+                // a pixel's 16 samples are the 16 lanes of a DPP row: the same 16 additions in the same order, the addend read from the
+                // row's lane q by the addition itself -- no LDS exchange, no wait.  All 64 lanes run this (the vote above is wave-uniform).
+                // (one pass: the sum starts from zero, from a VGPR -- the DPP form of an addition takes no constant for its second operand)
+                float zero = 0.0f;
+                asm volatile("" : "+v"(zero));
+                color = mk(zero, zero, zero);
+                row_sum16(color, result);
+            } else {
             const unsigned int lane_f = lane_index(), pl_f = LEAN ? lane_f / nn_eff : pl0;
             const unsigned int group_base = LEAN ? (pl_f < P ? pl_f : 0u) * nn_eff : group_base0;
             for (unsigned int q = 0; q < cnt; ++q) {
                 const int src = (int)(group_base + q);
                 color = vadd(color, mk(__shfl(result.x, src, 64), __shfl(result.y, src, 64), __shfl(result.z, src, 64)));
+            }
             }
         }
         }
@@ -434,7 +455,7 @@
             const LaunchParams& p = params_here<LEAN>(p_arg);
             const unsigned int lane_w = lane_index(), pl = LEAN ? lane_w / nn_eff : pl0, kl = LEAN ? lane_w - pl * nn_eff : kl0;
             const unsigned int lx = LEAN ? strip_x0 + ui * P + pl : lx_u;
-            if ((LEAN ? (pl < P && lx < p.w) : in_range_u) && kl == 0) {
+            if ((LEAN ? ((UNIT16 || pl < P) && lx < p.w) : in_range_u) && kl == 0) {
                 // kernel.cu:236-246.  float3 / float multiplies by the reciprocal (vec_math.h:479-483)
                 write_pixel(p, (size_t)lr * p.w + lx, vscale(color, inv_nn()), frame_ratio());
             }

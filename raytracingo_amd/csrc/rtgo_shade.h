@@ -51,6 +51,7 @@ __global__ __launch_bounds__(kMaxBlock) void shade_rays_kernel(const ShadeParams
     constexpr bool FRAMES = false;      // (the per-hit frame: the same bits as the precomputed one, and no frame table to stage)
     constexpr bool LVLDS = false;
     constexpr bool FOLDLATE = false;    // (a path folds its level records where it ends)
+    constexpr bool UNIT16 = false;      // (... and there are no LDS records to address)
     constexpr int LVW = PATH ? 3 : 4;
     const int tid = (int)threadIdx.x, block = (int)blockDim.x;
     float4* s_scene = reinterpret_cast<float4*>(sh_smem);
