@@ -156,7 +156,7 @@ int rtgo_set_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs
    A scene within RTGO_MAX_PRIMS renders the same pixels bit for bit through rtgo_set_scene, and faster there. */
 int rtgo_set_large_scene(rtgo_ctx* ctx, const rtgo_prim* prims, const rtgo_aabb* aabbs, uint32_t n);
 
-/* flags of rtgo_update_prims and rtgo_whitted_update_meshes_device */
+/* flags of rtgo_update_prims, rtgo_whitted_update_meshes_device and rtgo_whitted_set_instances_device */
 enum { RTGO_UPDATE_REFIT = 0, RTGO_UPDATE_REBUILD = 1 };
 
 /* optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE (RTGO_UPDATE_REFIT) or _BUILD (RTGO_UPDATE_REBUILD) over the custom-primitive AABBs,
@@ -496,6 +496,38 @@ int rtgo_whitted_rebuild_meshes(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* u
    their data runs before anything of the context is written, and a refusal known only after a clustered refit or a build puts the
    saved arrays back, as in the twins.  Synchronous. */
 int rtgo_whitted_update_meshes_device(rtgo_ctx* ctx, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, uint32_t flags);
+
+/* rtgo_whitted_set_instances for instances that are already on the device (under OptiX the OptixInstance buffer of an IAS build input
+   is a device pointer, sutil/Scene.cpp:985-1010): a rigid-body or particle step's output, a PyTorch-ROCm tensor.  d_instances is
+   rtgo_whitted_instance[n_instances], 56 bytes each in the host struct's layout, DEVICE memory of the context's device, caller-owned,
+   4-byte aligned, overlapping nothing of the context; the call reads it and never writes to it.  The caller's writes to it must be
+   complete, or ordered on the context's stream (rtgo_set_stream), before the call.  Beyond NULL and alignment the call cannot tell
+   whether the pointer is good: that it is device memory of the size given is the caller's to vouch for, as in
+   rtgo_whitted_update_meshes_device.
+   flags = RTGO_UPDATE_REBUILD (optixAccelBuild of the IAS with OPTIX_BUILD_OPERATION_BUILD): the twin of rtgo_whitted_set_instances.
+   Afterwards the context holds, array for array, what that call holds after the same instances, so frames, rtgo_whitted_trace_rays and
+   rtgo_whitted_shade_rays are equal bit for bit; what the twin keeps stays (meshes, clusters, materials, textures, lights, miss
+   colour).  The new top level is built aside and swapped in only once all of it succeeded.
+   flags = RTGO_UPDATE_REFIT (OPTIX_BUILD_OPERATION_UPDATE): n_instances must be the scene's count and every instance must name the mesh
+   it names now; transforms and material offsets may change.  The top level keeps its topology, its leaf order and its depth; its
+   records are refitted in place to the new instance boxes, and the per-instance records are rewritten.  Frames, closest hits and shaded
+   rays are bit for bit those of a context that took the same instances through rtgo_whitted_set_instances (any tree over the same
+   instances returns the same closest hit, lowest (instance, triangle) on ties); what a refit cannot keep is the quality of the tree, so
+   after instances have moved far among each other the walk slows down and RTGO_UPDATE_REBUILD pays.
+   Every instance is checked where it lies, in double and operation for operation as rtgo_whitted_set_instances checks it, and the
+   InstShade records, world boxes and InstWalk records are made on the device; the rebuilt top level's leaf order is read where the
+   build wrote it.  What crosses the host: a verdict of a few words, the build's (or refit's) nine meta words, the mesh table up
+   (48 bytes per mesh), and the caller's n_instances x 56 bytes read back once (at most 458 KB) -- the allowance rtgo_set_scene_device
+   takes for its host copy of the records: the mesh-update calls lay the instances out again from that copy.  Nothing else in proportion
+   to n_instances crosses the host.  Every other update call works afterwards as after rtgo_whitted_set_instances.
+   RTGO_E_INVALID: NULL ctx, unknown flag bits, d_instances NULL or not 4-byte aligned; an instance whose mesh index lies beyond the
+   meshes, whose material_offset + the mesh's largest material index lies beyond the material table, whose transform is non-finite or
+   not invertible, or that places its mesh beyond the float range (rtgo_last_error names the lowest such instance and the reason the
+   twin would give); under RTGO_UPDATE_REFIT also another count than the scene's, or an instance that names another mesh.
+   RTGO_E_STATE: no instanced scene (a scene of rtgo_whitted_set_mesh does not count).  RTGO_E_UNSUPPORTED: n_instances == 0 or beyond
+   RTGO_WHITTED_MAX_INSTANCES; under RTGO_UPDATE_REBUILD a top level deeper than the walk's stack, known after the build.  Every other
+   refusal is known before anything of the scene is written; a refused call leaves the scene as it was.  Synchronous. */
+int rtgo_whitted_set_instances_device(rtgo_ctx* ctx, const void* d_instances, uint32_t n_instances, uint32_t flags);
 
 /* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
    rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */

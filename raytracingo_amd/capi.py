@@ -28,7 +28,7 @@ SYMBOLS = [
     "rtgo_whitted_launch_frame", "rtgo_launch_frames", "rtgo_trace_rays", "rtgo_whitted_trace_rays", "rtgo_whitted_update_mesh",
     "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
     "rtgo_shade_rays", "rtgo_update_prims", "rtgo_whitted_update_meshes_device",
-    "rtgo_set_scene_device", "rtgo_set_large_scene_device", "rtgo_update_prims_device",
+    "rtgo_set_scene_device", "rtgo_set_large_scene_device", "rtgo_update_prims_device", "rtgo_whitted_set_instances_device",
 ]
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
@@ -189,6 +189,7 @@ def load():
     L.rtgo_whitted_update_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_rebuild_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_update_meshes_device.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32, C.c_uint32]
+    L.rtgo_whitted_set_instances_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
     L.rtgo_whitted_launch_frames.argtypes = [vp, C.POINTER(WhittedFrame), C.c_uint32]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
@@ -495,6 +496,16 @@ class Context:
         self._check(self._lib.rtgo_whitted_update_meshes_device(self._h, arr, len(updates), UPDATE_REBUILD if rebuild else UPDATE_REFIT),
                     "rtgo_whitted_update_meshes_device")
 
+    def whitted_set_instances_device(self, instances, refit=False):
+        """rtgo_whitted_set_instances_device: instances a contiguous tensor of n rtgo_whitted_instance records (instances_tensor's
+        layout: uint8 [n, 56], or float32 / int32 [n, 14]) on the context's device.  refit=False: the top level built again, as
+        whitted_set_instances builds it; refit=True: RTGO_UPDATE_REFIT, the same count and mesh choices as the scene holds, the top
+        level refitted in place.  The tensor's writes must be complete (torch.cuda.synchronize()) or ordered on the context's stream.
+        Synchronous."""
+        n, ptr = device_instances_args("whitted_set_instances_device", self.device, instances)
+        self._check(self._lib.rtgo_whitted_set_instances_device(self._h, C.c_void_p(ptr), n, UPDATE_REFIT if refit else UPDATE_REBUILD),
+                    "rtgo_whitted_set_instances_device")
+
     def whitted_set_texcoords(self, uv):
         if uv is None:
             self._check(self._lib.rtgo_whitted_set_texcoords(self._h, None, 0), "rtgo_whitted_set_texcoords")
@@ -766,6 +777,39 @@ def whitted_instances(instances):
         arr[i].mesh = int(mesh)
         arr[i].material_offset = int(off)
     return arr
+
+
+def device_instances_args(who, device, t):
+    """The checks of Context.whitted_set_instances_device on its tensor (needs no context): contiguous, n * 56 bytes, uint8 [n, 56] or
+    int32 / float32 [n, 14], on device `device`.  Returns (n, pointer); ValueError otherwise."""
+    if not hasattr(t, "data_ptr"):
+        raise ValueError("%s: instances must be a torch tensor" % who)
+    if not t.is_contiguous():
+        raise ValueError("%s: instances must be contiguous" % who)
+    cols = {"torch.uint8": 56, "torch.int32": 14, "torch.float32": 14}.get(str(t.dtype))
+    if cols is None or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("%s: instances must be uint8 [n, 56] or int32 / float32 [n, 14] (56 bytes per record), not %s %s"
+                         % (who, t.dtype, tuple(t.shape)))
+    if not t.is_cuda or t.device.index != device:
+        raise ValueError("%s: instances must lie on device %d, not on %s" % (who, device, t.device))
+    return t.shape[0], t.data_ptr()
+
+
+def instances_tensor(transforms, meshes, material_offsets):
+    """rtgo_whitted_instance records packed with torch ops on whatever device the inputs live on: transforms [n, 12] or [n, 3, 4]
+    (row-major object-to-world), meshes [n] and material_offsets [n] (integers up to 2^32 - 1: their low 32 bits are stored).  Returns
+    float32 [n, 14] with the two integers' bits in columns 12 and 13: byte for byte whitted_instances()'s array, and what
+    Context.whitted_set_instances_device takes."""
+    import torch
+    transforms = transforms.reshape(-1, 12).to(torch.float32)
+    n = transforms.shape[0]
+    out = torch.empty((n, 14), dtype=torch.float32, device=transforms.device)
+    out[:, :12] = transforms
+    words = out.view(torch.int32)
+    for col, v in ((12, meshes), (13, material_offsets)):
+        v = v.reshape(n).to(device=transforms.device, dtype=torch.int64)
+        words[:, col] = torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32)
+    return out
 
 
 def device_prims_args(who, device, indices, prims, aabbs):

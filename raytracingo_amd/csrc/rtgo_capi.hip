@@ -2158,6 +2158,19 @@ int rtgo_whitted_update_meshes_device(rtgo_ctx* c, const rtgo_whitted_mesh_updat
     return whitted_update_meshes_device(c, updates, n_updates, (flags & RTGO_UPDATE_REBUILD) != 0);
 }
 
+int rtgo_whitted_set_instances_device(rtgo_ctx* c, const void* d_instances, uint32_t n_instances, uint32_t flags)
+{
+    const std::string w = "rtgo_whitted_set_instances_device";
+    if (!c) return RTGO_E_INVALID;
+    if (flags & ~(uint32_t)RTGO_UPDATE_REBUILD) return fail(c, RTGO_E_INVALID, w + ": unknown flag bits");
+    if (!d_instances) return fail(c, RTGO_E_INVALID, w + ": NULL instance array");
+    if (!aligned4(d_instances)) return fail(c, RTGO_E_INVALID, w + ": the instance array is not 4-byte aligned");
+    if (!c->wm.instanced) return fail(c, RTGO_E_STATE, w + ": no instanced scene (call rtgo_whitted_set_scene first)");
+    if (n_instances == 0 || n_instances > RTGO_WHITTED_MAX_INSTANCES)
+        return fail(c, RTGO_E_UNSUPPORTED, w + ": instance count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_INSTANCES) + "]");
+    return whitted_set_instances_device(c, d_instances, n_instances, (flags & RTGO_UPDATE_REBUILD) != 0);
+}
+
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)
 {
     if (!c) return RTGO_E_INVALID;

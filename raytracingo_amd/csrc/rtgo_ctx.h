@@ -159,7 +159,7 @@ struct rtgo_ctx {
     DeviceArray<LightRec> d_lights;
     int n_lights = 0;
     DeviceArray<int> d_meta;               // build_kernel's meta words (one build at a time)
-    DeviceArray<unsigned int> d_verdict;   // prims_check_kernel's verdict (kVerdictWords; allocated by the first device-pointer call)
+    DeviceArray<unsigned int> d_verdict;   // prims_check_kernel's or inst_prepare_kernel's verdict (kVerdictWords; allocated by the first device-pointer call)
     int leaf_budget = kDefaultLeafBudget;
     bool have_camera = false;
     v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};
@@ -351,9 +351,10 @@ static const unsigned long long* radix_sort_keys(rtgo_ctx* c, unsigned long long
     return src;
 }
 
-// The determinant of the 3x3 in the first three columns of a, expanded along its first row; with `inv`, also the inverse (adj(a) / det)
+// The determinant of the 3x3 in the first three columns of a, expanded along its first row; with `inv`, also the inverse (adj(a) / det).
+// One text for the host and for inst_prepare_kernel (rtgo_whitted_inst_update.h): both compiles round once per operation.
 template <int S>
-static double mat3_det_inverse(const double (&a)[3][S], double (*inv)[S] = nullptr)
+__host__ __device__ static double mat3_det_inverse(const double (&a)[3][S], double (*inv)[S] = nullptr)
 {
     const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
                        a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "rtgo_ctx.h"
+#include "rtgo_whitted_inst_update.h"
 
 using whitted::WhittedBuildMeta;
 
@@ -1245,6 +1246,110 @@ static int whitted_update_meshes_device(rtgo_ctx* c, const rtgo_whitted_mesh_upd
     if (const int rc = whitted_check_on_device(c, c->wm, w, updates, n_updates, report)) return rc;
     const WhittedUpdateSource src = {hipMemcpyDeviceToDevice, report.data()};
     return rebuild ? whitted_rebuild_named(c, what, updates, n_updates, src) : whitted_refit_named(c, what, updates, n_updates, src);
+}
+
+// ---- instances on the device (rtgo_whitted_set_instances_device) ----------------------------------------------------------------------
+// rtgo_whitted_set_instances for instances in device memory (rebuild), or the top level refitted to them in place, once the arguments
+// have passed the checks the host can make.  Launches: inst_prepare_kernel (checks, InstShade records, boxes and index triples into
+// buffers of the call), the verdict read back -- every refusal but a rebuilt top level's depth is known here, before anything of the
+// scene is written -- then whitted_build over the boxes into a top level built aside (rebuild) or refit_kernel over the scene's
+// records as the mid-level refit launches it (refit: topology, leaf order and depth stay, so nothing needs saving), then
+// inst_gather_kernel for the InstWalk records.  The instances themselves are read back beside the verdict (56 B each): the mesh-update
+// calls lay the instances out again from wm.instances.  Nothing else in proportion to n crosses the host.
+static int whitted_set_instances_device(rtgo_ctx* c, const void* d_instances, uint32_t n, bool rebuild)
+{
+    using namespace whitted;
+    const char* what = "rtgo_whitted_set_instances_device";
+    const std::string w(what);
+    WhittedMesh& wm = c->wm;
+    if (!rebuild && n != (uint32_t)wm.top.n_instances)
+        return fail(c, RTGO_E_INVALID, w + ": a refit takes the scene's " + std::to_string(wm.top.n_instances) + " instances");
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<InstMesh> table(wm.meshes.size());
+    for (size_t k = 0; k < table.size(); ++k) {
+        const WhittedMeshInfo& mi = wm.meshes[k];
+        table[k] = {{mi.lo[0], mi.lo[1], mi.lo[2]}, {mi.hi[0], mi.hi[1], mi.hi[2]}, mi.rec_base, mi.tri_base, mi.vert_base, mi.root, mi.flags, mi.max_material};
+    }
+    const unsigned int* d_inst = static_cast<const unsigned int*>(d_instances);
+    const unsigned int blocks = (n + 255u) / 256u;
+    const int n_recs = wm.top.n_recs;   // (refit)
+    DeviceArray<InstMesh> d_table;
+    DeviceArray<InstShade> shade;
+    DeviceArray<float> boxes;
+    DeviceArray<unsigned int> idx;
+    DeviceArray<float4> tris;       // rebuild: what the build writes beside the records (the leaf order); refit: the leaf order refit_kernel reads
+    DeviceArray<uint4> qrecs;
+    if (!c->d_verdict.get()) RTGO_HIP(c, c->d_verdict.alloc(kVerdictWords));
+    RTGO_HIP(c, d_table.upload(table.data(), table.size(), c->stream));
+    RTGO_HIP(c, shade.alloc(n));
+    RTGO_HIP(c, boxes.alloc((size_t)6 * n));
+    RTGO_HIP(c, idx.alloc((size_t)3 * n));
+    RTGO_HIP(c, tris.alloc((size_t)3 * n));
+    RTGO_HIP(c, qrecs.alloc((size_t)2 * n));
+    RTGO_HIP(c, hipMemsetAsync(c->d_verdict.get(), 0xFF, kVerdictWords * sizeof(unsigned int), c->stream));
+    hipLaunchKernelGGL(inst_prepare_kernel, dim3(blocks), dim3(256), 0, c->stream, d_inst, n, reinterpret_cast<const unsigned int*>(d_table.get()),
+                       (unsigned int)table.size(), (unsigned int)wm.n_materials, rebuild ? nullptr : (const InstShade*)wm.top.shade.get(),
+                       rebuild ? nullptr : (const InstWalk*)wm.top.inst.get(), shade.get(), boxes.get(), idx.get(), tris.get(), c->d_verdict.get());
+    RTGO_HIP(c, hipGetLastError());
+    unsigned int v[kVerdictWords];
+    std::vector<rtgo_whitted_instance> instances(n);
+    RTGO_HIP(c, hipMemcpyAsync(v, c->d_verdict.get(), sizeof v, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipMemcpyAsync(instances.data(), d_instances, (size_t)n * sizeof(rtgo_whitted_instance), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    static const char* const kFault[kInstVerdictKinds] = {" names a mesh beyond the meshes array", " names another mesh than it names in the scene (a refit keeps the mesh choices)",
+                                                          ": material offset + material index beyond the material array",
+                                                          " has a non-finite or singular transform", " places its mesh beyond the float range"};
+    int kind = -1;
+    for (int q = 0; q < kInstVerdictKinds; ++q)
+        if (v[q] != kNoFault && (kind < 0 || v[q] < v[kind])) kind = q;
+    if (kind >= 0) return fail(c, RTGO_E_INVALID, w + ": instance " + std::to_string(v[kind]) + kFault[kind]);
+    if (rebuild) {
+        WhittedTop top;
+        DeviceArray<uint2> tidx;
+        WhittedBuildScratch scratch;
+        RTGO_HIP(c, top.recs.alloc((size_t)n * 4));
+        RTGO_HIP(c, top.inst.alloc(n));
+        RTGO_HIP(c, tidx.alloc(n));
+        RTGO_HIP(c, scratch.alloc(n));
+        if (const int rc = whitted_build(c, boxes.get(), idx.get(), (int)n, {top.recs.get(), tris.get(), qrecs.get(), tidx.get()}, scratch, top.meta, what)) return rc;
+        const int depth = (top.meta.n_recs > 0 ? top.meta.walk_depth : 0) + wm.mesh_depth;
+        if (depth > kMaxInstWalkDepth)
+            return fail(c, RTGO_E_UNSUPPORTED, w + ": the two-level walk needs " + std::to_string(depth) + " stack entries (limit " + std::to_string(kMaxInstWalkDepth) + ")");
+        hipLaunchKernelGGL(inst_gather_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)tris.get(), (const InstShade*)shade.get(), d_inst,
+                           (const InstMesh*)d_table.get(), n, top.inst.get());
+        RTGO_HIP(c, hipGetLastError());
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        top.shade = std::move(shade);
+        top.n_recs = top.meta.n_recs;
+        top.n_instances = (int)n;
+        wm.instances = std::move(instances);
+        whitted_install_top(wm, std::move(top), depth);
+        return RTGO_OK;
+    }
+    // refit: a top level of one leaf has no records, only the two arrays change
+    DeviceArray<int> done;
+    DeviceArray<WhittedBuildMeta> d_meta;
+    v3 grid[2];
+    if (n_recs > 0) {
+        RTGO_HIP(c, done.alloc((size_t)n_recs));
+        RTGO_HIP(c, d_meta.alloc(1));
+        hipLaunchKernelGGL(refit_kernel, dim3(1), dim3(kBuildThreads), 0, c->stream, (const float*)boxes.get(), (const unsigned int*)idx.get(), (int)n, n_recs,
+                           wm.top.meta.walk_depth, wm.top.recs.get(), tris.get(), qrecs.get(), done.get(), d_meta.get());
+        RTGO_HIP(c, hipGetLastError());
+        RTGO_HIP(c, hipMemcpyAsync(grid, &d_meta.get()->grid_lo, sizeof grid, hipMemcpyDeviceToHost, c->stream));
+    }
+    hipLaunchKernelGGL(inst_gather_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)nullptr, (const InstShade*)shade.get(), d_inst,
+                       (const InstMesh*)d_table.get(), n, wm.top.inst.get());
+    RTGO_HIP(c, hipGetLastError());
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (n_recs > 0) {
+        wm.top.meta.grid_lo = grid[0];
+        wm.top.meta.grid_step = grid[1];
+    }
+    wm.top.shade = std::move(shade);
+    wm.instances = std::move(instances);
+    return RTGO_OK;
 }
 
 // The launches.  What a launch over one mesh (rtgo_whitted_set_mesh) reads of the scene: everything of Params but the frame
