@@ -529,6 +529,49 @@ int rtgo_whitted_update_meshes_device(rtgo_ctx* ctx, const rtgo_whitted_mesh_upd
    refusal is known before anything of the scene is written; a refused call leaves the scene as it was.  Synchronous. */
 int rtgo_whitted_set_instances_device(rtgo_ctx* ctx, const void* d_instances, uint32_t n_instances, uint32_t flags);
 
+/* rtgo_whitted_set_scene for meshes that are already on the device (under OptiX the vertex and index buffers of a build input are
+   device pointers): a marching-cubes or simulation step's output, a PyTorch-ROCm tensor.  `meshes`, `instances` and `materials` are
+   host arrays, as in the twin (they are small, and the context keeps a host copy of the instances anyway; a caller whose instances
+   are on the device follows up with rtgo_whitted_set_instances_device).  The pointers inside each rtgo_whitted_mesh -- positions,
+   normals, texcoords, indices, material_of_triangle, of the sizes the twin reads -- are DEVICE memory of the context's device,
+   caller-owned, 4-byte aligned, overlapping nothing of the context; the call reads them and never writes to them, and two meshes may
+   name the same buffer.  The caller's writes to them must be complete, or ordered on the context's stream (rtgo_set_stream), before
+   the call.  Beyond NULL and alignment the call cannot tell whether a pointer is good: that the buffers are device memory of the sizes
+   given is the caller's to vouch for, as in rtgo_whitted_update_meshes_device.
+   Afterwards the context holds, array for array, what the twin holds after the same data, so frames, rtgo_whitted_trace_rays and
+   rtgo_whitted_shade_rays are equal bit for bit, and every later call (rtgo_whitted_set_instances and its _device form, the mesh
+   updates on host and device, rtgo_whitted_set_material_textures) behaves as after the twin.  What the twin drops is dropped alike: the
+   old scene and every texture.
+   No copy in proportion to a mesh crosses the host in either direction.  Every element of every array is checked where it lies, named
+   by a triangle or not, and the meshes' boxes and largest material indices are taken there (one pair of launches over a table of all
+   meshes; no vertex is read through an index that has not been compared with n_vertices first); then one launch packs every mesh into
+   the context's arrays, and the builds are the twin's.  What crosses: the table up (64 bytes per mesh), a report back (32 bytes per
+   mesh, one wait), and what the twin's builds read back per structure.
+   Refusals are the twin's, with its codes and its messages under this call's name.  RTGO_E_INVALID: a NULL argument, a mesh without
+   positions or indices, a pointer that is not 4-byte aligned; found on the device: an index beyond the vertex array, non-finite
+   positions or normals, a non-finite texture coordinate, a material index beyond the table; every refusal of an instance.
+   RTGO_E_UNSUPPORTED: every count and limit of the twin.  Where several faults are present the refusal is the one the twin gives: the
+   first mesh at fault, and of its faults the first in the twin's order (counts, indices, vertex data, texture coordinates, materials).
+   Every check of every mesh runs, and its report is read, before the old scene is dropped: a refused call leaves the scene and the
+   caller's buffers as they were.  The one refusal known only after a build -- a structure deeper than the walk's stack -- leaves no
+   scene, as in the twin.  Synchronous. */
+int rtgo_whitted_set_scene_device(rtgo_ctx* ctx, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances,
+                                  uint32_t n_instances, const rtgo_pbr* materials, uint32_t n_materials);
+
+/* rtgo_whitted_set_mesh for a mesh that is already on the device: the one-mesh scene of rtgo_whitted_set_scene_device, under the
+   same contract for d_positions, d_normals (or NULL), d_indices and d_material_of_triangle (or NULL) -- DEVICE memory of the context's
+   device, caller-owned, 4-byte aligned, overlapping nothing of the context, read and never written, the caller's writes complete or
+   ordered on the context's stream; beyond NULL and alignment the call cannot tell whether a pointer is good.  `materials` is a host
+   array.  Limits (RTGO_MAX_TRIANGLES), refusals and what the context holds afterwards are rtgo_whitted_set_mesh's; the data is checked
+   on the device before the old scene is dropped, and moves device to device.  Synchronous. */
+int rtgo_whitted_set_mesh_device(rtgo_ctx* ctx, const void* d_positions, const void* d_normals, uint32_t n_vertices, const void* d_indices,
+                                 const void* d_material_of_triangle, uint32_t n_triangles, const rtgo_pbr* materials, uint32_t n_materials);
+
+/* rtgo_whitted_set_texcoords for coordinates that are already on the device: d_uv is n_vertices x 2 floats of DEVICE memory under the
+   contract above (4-byte aligned: RTGO_E_INVALID otherwise), or NULL, which removes the coordinates.  State and count refusals are
+   rtgo_whitted_set_texcoords's; the finite check runs on the device, before the old coordinates go.  Synchronous. */
+int rtgo_whitted_set_texcoords_device(rtgo_ctx* ctx, const void* d_uv, uint32_t n_vertices);
+
 /* ---- ray queries: optixTrace for rays of the caller's own (under OptiX the caller writes a raygen program; here it fills a buffer of
    rays -- picking, visibility between two points, a camera model of its own, baking -- and reads the hits back) ---- */
 

@@ -29,6 +29,7 @@ SYMBOLS = [
     "rtgo_whitted_update_meshes", "rtgo_whitted_launch_frames", "rtgo_whitted_shade_rays", "rtgo_whitted_rebuild_meshes",
     "rtgo_shade_rays", "rtgo_update_prims", "rtgo_whitted_update_meshes_device",
     "rtgo_set_scene_device", "rtgo_set_large_scene_device", "rtgo_update_prims_device", "rtgo_whitted_set_instances_device",
+    "rtgo_whitted_set_scene_device", "rtgo_whitted_set_mesh_device", "rtgo_whitted_set_texcoords_device",
 ]
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
@@ -190,6 +191,9 @@ def load():
     L.rtgo_whitted_rebuild_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_update_meshes_device.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32, C.c_uint32]
     L.rtgo_whitted_set_instances_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.rtgo_whitted_set_scene_device.argtypes = [vp, C.POINTER(WhittedMesh), C.c_uint32, C.POINTER(WhittedInstance), C.c_uint32, vp, C.c_uint32]
+    L.rtgo_whitted_set_mesh_device.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32]
+    L.rtgo_whitted_set_texcoords_device.argtypes = [vp, vp, C.c_uint32]
     L.rtgo_whitted_launch_frame.argtypes = [vp, C.POINTER(WhittedFrame)]
     L.rtgo_whitted_launch_frames.argtypes = [vp, C.POINTER(WhittedFrame), C.c_uint32]
     L.rtgo_trace_rays.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
@@ -506,6 +510,38 @@ class Context:
         self._check(self._lib.rtgo_whitted_set_instances_device(self._h, C.c_void_p(ptr), n, UPDATE_REFIT if refit else UPDATE_REBUILD),
                     "rtgo_whitted_set_instances_device")
 
+    def whitted_set_scene_device(self, meshes, instances, materials):
+        """rtgo_whitted_set_scene_device: whitted_set_scene's arguments with contiguous torch tensors on the context's device in place
+        of the meshes' arrays (positions / normals float32 [nv, 3], texcoords float32 [nv, 2], indices int32 or uint32 [nt, 3],
+        tri_material int32 or uint32 [nt]; normals, texcoords and tri_material optional); instances and materials stay host data.  The
+        tensors' writes must be complete (torch.cuda.synchronize()) or ordered on the context's stream.  Synchronous."""
+        who = "whitted_set_scene_device"
+        ms = (WhittedMesh * max(len(meshes), 1))()
+        for k, m in enumerate(meshes):
+            nv, nt, p = device_mesh_args("%s: mesh %d" % (who, k), self.device, m["positions"], m.get("normals"), m.get("texcoords"), m["indices"],
+                                         m.get("tri_material"))
+            ms[k] = WhittedMesh(p[0], p[1], p[2], nv, p[3], p[4], nt)
+        inst = whitted_instances(instances)
+        mats = np.ascontiguousarray(materials, dtype=np.float32).reshape(-1, 6)
+        self._check(self._lib.rtgo_whitted_set_scene_device(self._h, ms, len(meshes), inst, len(instances), mats.ctypes.data, len(mats)),
+                    "rtgo_whitted_set_scene_device")
+
+    def whitted_set_mesh_device(self, positions, normals, indices, tri_material, materials):
+        """rtgo_whitted_set_mesh_device: whitted_set_mesh's arguments with torch tensors on the context's device (see
+        whitted_set_scene_device) for positions, normals (or None), indices and tri_material (or None)"""
+        nv, nt, p = device_mesh_args("whitted_set_mesh_device", self.device, positions, normals, None, indices, tri_material)
+        mats = np.ascontiguousarray(materials, dtype=np.float32).reshape(-1, 6)
+        self._check(self._lib.rtgo_whitted_set_mesh_device(self._h, p[0], p[1], nv, p[3], p[4], nt, mats.ctypes.data, len(mats)),
+                    "rtgo_whitted_set_mesh_device")
+
+    def whitted_set_texcoords_device(self, uv):
+        """rtgo_whitted_set_texcoords_device: uv a contiguous float32 torch tensor [nv, 2] on the context's device, or None (removes them)"""
+        if uv is None:
+            self._check(self._lib.rtgo_whitted_set_texcoords_device(self._h, None, 0), "rtgo_whitted_set_texcoords_device")
+            return
+        device_mesh_tensor("whitted_set_texcoords_device", self.device, "uv", uv, ("torch.float32",), 2)
+        self._check(self._lib.rtgo_whitted_set_texcoords_device(self._h, C.c_void_p(uv.data_ptr()), uv.shape[0]), "rtgo_whitted_set_texcoords_device")
+
     def whitted_set_texcoords(self, uv):
         if uv is None:
             self._check(self._lib.rtgo_whitted_set_texcoords(self._h, None, 0), "rtgo_whitted_set_texcoords")
@@ -793,6 +829,41 @@ def device_instances_args(who, device, t):
     if not t.is_cuda or t.device.index != device:
         raise ValueError("%s: instances must lie on device %d, not on %s" % (who, device, t.device))
     return t.shape[0], t.data_ptr()
+
+
+def device_mesh_tensor(who, device, name, t, dtypes, cols):
+    """One tensor of Context.whitted_set_scene_device / whitted_set_mesh_device / whitted_set_texcoords_device (needs no context): a
+    contiguous torch tensor of one of `dtypes`, [n, cols] (cols = 0: [n]), on device `device`.  Layout first, then where it lies, as
+    device_prims_args.  ValueError otherwise."""
+    if not hasattr(t, "data_ptr"):
+        raise ValueError("%s: %s must be a torch tensor" % (who, name))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+    if str(t.dtype) not in dtypes or t.dim() != (2 if cols else 1) or (cols and t.shape[1] != cols):
+        raise ValueError("%s: %s must be %s %s, not %s %s" % (who, name, " or ".join(d[6:] for d in dtypes), "[n, %d]" % cols if cols else "[n]",
+                                                              t.dtype, tuple(t.shape)))
+    if not t.is_cuda or t.device.index != device:
+        raise ValueError("%s: %s must lie on device %d, not on %s" % (who, name, device, t.device))
+
+
+def device_mesh_args(who, device, positions, normals, texcoords, indices, tri_material):
+    """The checks of Context.whitted_set_scene_device (one mesh of it) and whitted_set_mesh_device on their tensors (needs no context):
+    positions / normals float32 [nv, 3], texcoords float32 [nv, 2], indices int32 or uint32 [nt, 3], tri_material int32 or uint32 [nt];
+    normals, texcoords and tri_material may be None.  Returns (nv, nt, the five pointers or None, in rtgo_whitted_mesh's order);
+    ValueError for anything that is not a contiguous tensor of that dtype and shape on device `device`, or whose count disagrees."""
+    f32, u32 = ("torch.float32",), ("torch.int32", "torch.uint32")
+    spec = (("positions", positions, f32, 3), ("normals", normals, f32, 3), ("texcoords", texcoords, f32, 2), ("indices", indices, u32, 3),
+            ("tri_material", tri_material, u32, 0))
+    for name, t, dtypes, cols in spec:
+        if t is None and name in ("positions", "indices"):
+            raise ValueError("%s: %s must be a torch tensor" % (who, name))
+        if t is not None:
+            device_mesh_tensor(who, device, name, t, dtypes, cols)
+    nv, nt = positions.shape[0], indices.shape[0]
+    for name, t, want in (("normals", normals, nv), ("texcoords", texcoords, nv), ("tri_material", tri_material, nt)):
+        if t is not None and t.shape[0] != want:
+            raise ValueError("%s: %s has %d rows, the mesh has %d" % (who, name, t.shape[0], want))
+    return nv, nt, [None if t is None else t.data_ptr() for _, t, _, _ in spec]
 
 
 def instances_tensor(transforms, meshes, material_offsets):

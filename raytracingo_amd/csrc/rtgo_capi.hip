@@ -2074,47 +2074,41 @@ int rtgo_whitted_set_mesh(rtgo_ctx* c, const float* positions, const float* norm
     if (n_triangles == 0 || n_triangles > RTGO_MAX_TRIANGLES || n_vertices == 0 || n_materials == 0)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_mesh: triangle count must be in [1, " + std::to_string(RTGO_MAX_TRIANGLES) + "], vertices and materials non-empty");
     const rtgo_whitted_mesh mesh = {positions, normals, nullptr, n_vertices, indices, material_of_triangle, n_triangles};
-    uint32_t max_material;
-    if (const int rc = whitted_check_mesh(c, mesh, n_materials, "rtgo_whitted_set_mesh", max_material)) return rc;
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    c->wm = WhittedMesh();   // (the old scene goes before the new one is allocated; a failure from here on leaves none)
-    WhittedMesh next;
-    if (const int rc = whitted_build_single(c, next, mesh, materials, n_materials, "rtgo_whitted_set_mesh")) return rc;
-    if (const int rc = whitted_tile_heads(c)) return rc;
-    next.triangles = (int)n_triangles;
-    c->wm = std::move(next);
-    return RTGO_OK;
+    return whitted_set_mesh(c, "rtgo_whitted_set_mesh", mesh, materials, n_materials, false);
 }
 
-// (rtgo_whitted_host.h's stages over a scene built aside: a refusal by the host checks leaves the old scene; once that is dropped, a failure leaves none)
+int rtgo_whitted_set_mesh_device(rtgo_ctx* c, const void* d_positions, const void* d_normals, uint32_t n_vertices, const void* d_indices,
+                                 const void* d_material_of_triangle, uint32_t n_triangles, const rtgo_pbr* materials, uint32_t n_materials)
+{
+    const std::string w = "rtgo_whitted_set_mesh_device";
+    if (!c || !d_positions || !d_indices || !materials) return fail(c, RTGO_E_INVALID, w + ": NULL argument");
+    if (!aligned4(d_positions) || !aligned4(d_normals) || !aligned4(d_indices) || !aligned4(d_material_of_triangle))
+        return fail(c, RTGO_E_INVALID, w + ": a pointer is not 4-byte aligned");
+    if (n_triangles == 0 || n_triangles > RTGO_MAX_TRIANGLES || n_vertices == 0 || n_materials == 0)
+        return fail(c, RTGO_E_UNSUPPORTED, w + ": triangle count must be in [1, " + std::to_string(RTGO_MAX_TRIANGLES) + "], vertices and materials non-empty");
+    const rtgo_whitted_mesh mesh = {static_cast<const float*>(d_positions), static_cast<const float*>(d_normals), nullptr, n_vertices,
+                                    static_cast<const uint32_t*>(d_indices), static_cast<const uint32_t*>(d_material_of_triangle), n_triangles};
+    return whitted_set_mesh(c, w.c_str(), mesh, materials, n_materials, true);
+}
+
+// (rtgo_whitted_host.h's stages over a scene built aside: a refusal by the checks leaves the old scene; once that is dropped, a failure leaves none)
 int rtgo_whitted_set_scene(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances, uint32_t n_instances,
                            const rtgo_pbr* materials, uint32_t n_materials)
 {
-    const char* what = "rtgo_whitted_set_scene";
     if (!c || !meshes || !instances || !materials) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_scene: NULL argument");
     if (n_meshes == 0 || n_meshes > RTGO_WHITTED_MAX_MESHES || n_materials == 0)
         return fail(c, RTGO_E_UNSUPPORTED, "rtgo_whitted_set_scene: mesh count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESHES) + "], materials non-empty");
-    WhittedLayout lay;
-    std::vector<whitted::InstShade> shade;
-    std::vector<float> box_pos;
-    if (const int rc = whitted_layout_meshes(c, meshes, n_meshes, n_materials, lay)) return rc;
-    if (const int rc = whitted_prepare_instances(c, lay.info, n_materials, instances, n_instances, shade, box_pos, what)) return rc;
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    c->wm = WhittedMesh();
-    WhittedMesh next;
-    if (const int rc = whitted_upload_meshes(c, next, lay, materials, n_materials)) return rc;
-    if (const int rc = whitted_build_meshes(c, next, lay, what)) return rc;
-    // the clustered meshes' boxes took in their mid levels' boxes: the instance boxes again from them (the checks passed above)
-    if (next.clusters.get())
-        if (const int rc = whitted_prepare_instances(c, next.meshes, n_materials, instances, n_instances, shade, box_pos, what)) return rc;
-    if (const int rc = whitted_build_top(c, next, shade, box_pos, instances, what)) return rc;
-    if (const int rc = whitted_tile_heads(c)) return rc;
-    next.instanced = true;
-    next.triangles = (int)std::min(lay.n_tri, (size_t)0x7FFFFFFF);
-    c->wm = std::move(next);
-    return RTGO_OK;
+    return whitted_set_scene(c, "rtgo_whitted_set_scene", meshes, n_meshes, instances, n_instances, materials, n_materials, false);
+}
+
+int rtgo_whitted_set_scene_device(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances, uint32_t n_instances,
+                                  const rtgo_pbr* materials, uint32_t n_materials)
+{
+    const std::string w = "rtgo_whitted_set_scene_device";
+    if (!c || !meshes || !instances || !materials) return fail(c, RTGO_E_INVALID, w + ": NULL argument");
+    if (n_meshes == 0 || n_meshes > RTGO_WHITTED_MAX_MESHES || n_materials == 0)
+        return fail(c, RTGO_E_UNSUPPORTED, w + ": mesh count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESHES) + "], materials non-empty");
+    return whitted_set_scene(c, w.c_str(), meshes, n_meshes, instances, n_instances, materials, n_materials, true);
 }
 
 int rtgo_whitted_set_instances(rtgo_ctx* c, const rtgo_whitted_instance* instances, uint32_t n_instances)
@@ -2177,17 +2171,18 @@ int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices
     if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: no mesh (call rtgo_whitted_set_mesh first)");
     if (c->wm.instanced) return fail(c, RTGO_E_STATE, "rtgo_whitted_set_texcoords: an instanced scene takes its texture coordinates per mesh (rtgo_whitted_set_scene)");
     if (uv && n_vertices != (uint32_t)c->wm.n_vertices) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_texcoords: one (u, v) per vertex of the mesh");
-    if (uv)
-        for (size_t k = 0; k < (size_t)n_vertices * 2; ++k)
-            if (!std::isfinite(uv[k])) return fail(c, RTGO_E_INVALID, "rtgo_whitted_set_texcoords: non-finite coordinate");
-    RTGO_HIP(c, hipSetDevice(c->device));
-    RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    c->wm.texcoords.reset();
-    if (uv) {
-        RTGO_HIP(c, c->wm.texcoords.upload(uv, (size_t)n_vertices * 2, c->stream));
-        RTGO_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    return RTGO_OK;
+    return whitted_set_texcoords(c, "rtgo_whitted_set_texcoords", uv, n_vertices, false);
+}
+
+int rtgo_whitted_set_texcoords_device(rtgo_ctx* c, const void* d_uv, uint32_t n_vertices)
+{
+    const std::string w = "rtgo_whitted_set_texcoords_device";
+    if (!c) return RTGO_E_INVALID;
+    if (!aligned4(d_uv)) return fail(c, RTGO_E_INVALID, w + ": the pointer is not 4-byte aligned");
+    if (c->wm.triangles == 0) return fail(c, RTGO_E_STATE, w + ": no mesh (call rtgo_whitted_set_mesh first)");
+    if (c->wm.instanced) return fail(c, RTGO_E_STATE, w + ": an instanced scene takes its texture coordinates per mesh (rtgo_whitted_set_scene)");
+    if (d_uv && n_vertices != (uint32_t)c->wm.n_vertices) return fail(c, RTGO_E_INVALID, w + ": one (u, v) per vertex of the mesh");
+    return whitted_set_texcoords(c, w.c_str(), static_cast<const float*>(d_uv), n_vertices, true);
 }
 
 int rtgo_whitted_set_material_textures(rtgo_ctx* c, uint32_t material, const rtgo_texture* base_color, const rtgo_texture* metallic_roughness,

@@ -5,6 +5,7 @@
 
 #include "rtgo_ctx.h"
 #include "rtgo_whitted_inst_update.h"
+#include "rtgo_whitted_mesh_device.h"
 
 using whitted::WhittedBuildMeta;
 
@@ -114,33 +115,43 @@ static int whitted_build_boxes(rtgo_ctx* c, const float* d_boxes, int n, float4*
 
 // The checks every mesh of the whitted path passes (rtgo_whitted_set_mesh, rtgo_whitted_set_scene; `at` names it in the messages): vertex
 // indices inside the vertex array, finite vertex data, material indices inside the table.  Also finds the mesh's largest material index.
+// (kMeshFault: its refusals, in its order -- the kinds mesh_check_kernel reports of a mesh on the device)
+static const char* const kMeshFault[whitted::kMeshFaultKinds] = {": index beyond the vertex array", ": non-finite vertex data", ": non-finite texture coordinate",
+                                                                 ": material index beyond the material array"};
 static int whitted_check_mesh(rtgo_ctx* c, const rtgo_whitted_mesh& q, uint32_t n_materials, const std::string& at, uint32_t& max_material)
 {
+    using namespace whitted;
     for (uint32_t i = 0; i < 3 * q.n_triangles; ++i)
-        if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + ": index beyond the vertex array");
+        if (q.indices[i] >= q.n_vertices) return fail(c, RTGO_E_INVALID, at + kMeshFault[kMeshBadIndex]);
     for (uint32_t i = 0; i < 3 * q.n_vertices; ++i)
-        if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + ": non-finite vertex data");
+        if (!std::isfinite(q.positions[i]) || (q.normals && !std::isfinite(q.normals[i]))) return fail(c, RTGO_E_INVALID, at + kMeshFault[kMeshBadVertex]);
     if (q.texcoords)
         for (uint32_t i = 0; i < 2 * q.n_vertices; ++i)
-            if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + ": non-finite texture coordinate");
+            if (!std::isfinite(q.texcoords[i])) return fail(c, RTGO_E_INVALID, at + kMeshFault[kMeshBadTexcoord]);
     max_material = 0;
     if (q.material_of_triangle)
         for (uint32_t i = 0; i < q.n_triangles; ++i) {
-            if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + ": material index beyond the material array");
+            if (q.material_of_triangle[i] >= n_materials) return fail(c, RTGO_E_INVALID, at + kMeshFault[kMeshBadMaterial]);
             max_material = std::max(max_material, q.material_of_triangle[i]);
         }
     return RTGO_OK;
 }
 
-// The one mesh of rtgo_whitted_set_mesh into `wm` (empty): uploads, the build, and what the launches read of its meta
-static int whitted_build_single(rtgo_ctx* c, WhittedMesh& wm, const rtgo_whitted_mesh& q, const rtgo_pbr* materials, uint32_t n_materials, const char* what)
+// The one mesh of rtgo_whitted_set_mesh into `wm` (empty): uploads, the build, and what the launches read of its meta.  kind: where q's
+// arrays lie (rtgo_whitted_set_mesh_device: the device, and they move device to device)
+static int whitted_build_single(rtgo_ctx* c, WhittedMesh& wm, const rtgo_whitted_mesh& q, const rtgo_pbr* materials, uint32_t n_materials, const char* what,
+                                hipMemcpyKind kind = hipMemcpyHostToDevice)
 {
     const size_t n = q.n_triangles;
     WhittedBuildScratch scratch;
-    RTGO_HIP(c, wm.positions.upload(q.positions, (size_t)q.n_vertices * 3, c->stream));
-    if (q.normals) RTGO_HIP(c, wm.normals.upload(q.normals, (size_t)q.n_vertices * 3, c->stream));
-    RTGO_HIP(c, wm.indices.upload(q.indices, n * 3, c->stream));
-    if (q.material_of_triangle) RTGO_HIP(c, wm.tri_material.upload(q.material_of_triangle, n, c->stream));
+    auto put = [&](auto& keep, const auto* src, size_t count) -> hipError_t {
+        const hipError_t e = keep.alloc(count);
+        return e != hipSuccess ? e : hipMemcpyAsync(keep.get(), src, count * sizeof *src, kind, c->stream);
+    };
+    RTGO_HIP(c, put(wm.positions, q.positions, (size_t)q.n_vertices * 3));
+    if (q.normals) RTGO_HIP(c, put(wm.normals, q.normals, (size_t)q.n_vertices * 3));
+    RTGO_HIP(c, put(wm.indices, q.indices, n * 3));
+    if (q.material_of_triangle) RTGO_HIP(c, put(wm.tri_material, q.material_of_triangle, n));
     RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
     RTGO_HIP(c, wm.recs.alloc(n * 4));
     RTGO_HIP(c, wm.tris.alloc(n * 3));
@@ -505,6 +516,10 @@ struct WhittedLayout {
     // the meshes back to back (indices stay relative to their mesh's vertices: each build reads its own slice)
     std::vector<float> pos, nrm, uv;
     std::vector<unsigned int> idx, tmat;
+    // ... or (rtgo_whitted_set_scene_device) the vectors stay empty and the meshes lie on the device: the table mesh_pack_kernel packs them from
+    std::vector<whitted::MeshSource> source;
+    int source_blocks = 0;
+    bool on_device() const { return !source.empty(); }
 };
 
 // The box an instanced mesh's instances are laid out from (WhittedMeshInfo::lo / hi), from the bounds of the vertices its triangles name:
@@ -535,38 +550,54 @@ static void whitted_mesh_box(const float* positions, const uint32_t* indices, ui
     whitted_pad_mesh_box(lo, hi, out_lo, out_hi);
 }
 
+// What the host decides of mesh q of a scene from its pointers and counts alone (`at` names it in the messages; on_device: its arrays
+// are device memory, rtgo_whitted_set_scene_device -- a NULL or misaligned pointer never reaches a launch), lay.n_tri triangles before it
+static int whitted_admit_mesh(rtgo_ctx* c, const rtgo_whitted_mesh& q, const std::string& at, const WhittedLayout& lay, bool on_device)
+{
+    if (!q.positions || !q.indices) return fail(c, RTGO_E_INVALID, at + ": NULL positions or indices");
+    if (on_device && !(aligned4(q.positions) && aligned4(q.normals) && aligned4(q.texcoords) && aligned4(q.indices) && aligned4(q.material_of_triangle)))
+        return fail(c, RTGO_E_INVALID, at + ": a pointer is not 4-byte aligned");
+    if (q.n_triangles == 0 || q.n_triangles > RTGO_WHITTED_MAX_MESH_TRIANGLES || q.n_vertices == 0)
+        return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESH_TRIANGLES) + "], vertices non-empty");
+    if (lay.n_tri + q.n_triangles > RTGO_WHITTED_MAX_SCENE_TRIANGLES)
+        return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
+    return RTGO_OK;
+}
+
+// ... and, once it has passed its checks, where it will sit in the arrays (mi: box and max_material are set already)
+static void whitted_place_mesh(const rtgo_whitted_mesh& q, WhittedLayout& lay, WhittedMeshInfo& mi)
+{
+    mi.rec_base = (int)lay.n_tri;   // (a mesh of n triangles has fewer than n records)
+    mi.tri_base = (int)lay.n_tri;
+    mi.vert_base = (int)lay.n_vert;
+    mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
+    mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
+    mi.n_tris = (int)q.n_triangles;
+    mi.n_verts = (int)q.n_vertices;
+    lay.n_vert += q.n_vertices;
+    lay.n_tri += q.n_triangles;
+    if (mi.clustered) {
+        // one workgroup's builds: clusters of at most kClusterTris triangles and a mid level of ncl boxes
+        const int ncl = ((int)q.n_triangles + whitted::kClusterTris - 1) / whitted::kClusterTris;
+        lay.max_tri = std::max(lay.max_tri, std::max(whitted::kClusterTris, ncl));
+        lay.max_big = std::max(lay.max_big, (int)q.n_triangles);
+    } else {
+        lay.max_tri = std::max(lay.max_tri, (int)q.n_triangles);
+    }
+}
+
 // The stages of rtgo_whitted_set_scene.  Stage 1 (host only): every mesh as rtgo_whitted_set_mesh checks it, its padded box, where it will sit in the arrays, and packed there
-static int whitted_layout_meshes(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, uint32_t n_materials, WhittedLayout& lay)
+static int whitted_layout_meshes(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, uint32_t n_materials, WhittedLayout& lay, const char* what)
 {
     lay.info.assign(n_meshes, WhittedMeshInfo());
     for (uint32_t k = 0; k < n_meshes; ++k) {
         const rtgo_whitted_mesh& q = meshes[k];
-        const std::string at = "rtgo_whitted_set_scene: mesh " + std::to_string(k);
-        if (!q.positions || !q.indices) return fail(c, RTGO_E_INVALID, at + ": NULL positions or indices");
-        if (q.n_triangles == 0 || q.n_triangles > RTGO_WHITTED_MAX_MESH_TRIANGLES || q.n_vertices == 0)
-            return fail(c, RTGO_E_UNSUPPORTED, at + ": triangle count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_MESH_TRIANGLES) + "], vertices non-empty");
-        if (lay.n_tri + q.n_triangles > RTGO_WHITTED_MAX_SCENE_TRIANGLES)
-            return fail(c, RTGO_E_UNSUPPORTED, at + ": the meshes hold more than " + std::to_string(RTGO_WHITTED_MAX_SCENE_TRIANGLES) + " triangles together");
+        const std::string at = std::string(what) + ": mesh " + std::to_string(k);
+        if (const int rc = whitted_admit_mesh(c, q, at, lay, false)) return rc;
         WhittedMeshInfo& mi = lay.info[k];
         if (const int rc = whitted_check_mesh(c, q, n_materials, at, mi.max_material)) return rc;
         whitted_mesh_box(q.positions, q.indices, q.n_triangles, mi.lo, mi.hi);
-        mi.rec_base = (int)lay.n_tri;   // (a mesh of n triangles has fewer than n records)
-        mi.tri_base = (int)lay.n_tri;
-        mi.vert_base = (int)lay.n_vert;
-        mi.flags = (q.normals ? whitted::kHasNormals : 0) | (q.texcoords ? whitted::kHasTexcoords : 0);
-        mi.clustered = q.n_triangles > (uint32_t)whitted::kMaxTriangles;
-        mi.n_tris = (int)q.n_triangles;
-        mi.n_verts = (int)q.n_vertices;
-        lay.n_vert += q.n_vertices;
-        lay.n_tri += q.n_triangles;
-        if (mi.clustered) {
-            // one workgroup's builds: clusters of at most kClusterTris triangles and a mid level of ncl boxes
-            const int ncl = ((int)q.n_triangles + whitted::kClusterTris - 1) / whitted::kClusterTris;
-            lay.max_tri = std::max(lay.max_tri, std::max(whitted::kClusterTris, ncl));
-            lay.max_big = std::max(lay.max_big, (int)q.n_triangles);
-        } else {
-            lay.max_tri = std::max(lay.max_tri, (int)q.n_triangles);
-        }
+        whitted_place_mesh(q, lay, mi);
     }
     // the meshes' arrays back to back, zero where a mesh has no normals, texture coordinates or materials
     lay.pos.assign(3 * lay.n_vert, 0.0f);
@@ -586,14 +617,110 @@ static int whitted_layout_meshes(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, u
     return RTGO_OK;
 }
 
-// Stage 2: the packed meshes and the materials to the device, and the arrays the builds write
+// ---- meshes on the device (rtgo_whitted_set_scene_device, rtgo_whitted_set_mesh_device, rtgo_whitted_set_texcoords_device) ------------
+// mesh_check_kernel and mesh_check_final_kernel over a table of the call's meshes (first_block / n_blocks are set here: a workgroup per
+// kMeshCheckThreads vertices or triangles, whichever are more, at most 1024 per mesh): what whitted_check_mesh and whitted_mesh_box
+// find of each in host loops, as report[k].  Up: 64 B per mesh; back: 32 B per mesh, one wait.  Nothing of the context is written.
+// n_blocks: the workgroups of the table (mesh_pack_kernel's grid too).
+static int whitted_check_meshes_on_device(rtgo_ctx* c, std::vector<whitted::MeshSource>& table, uint32_t n_materials, std::vector<whitted::MeshReport>& report,
+                                          int& n_blocks)
+{
+    using namespace whitted;
+    n_blocks = 0;
+    for (MeshSource& m : table) {
+        const size_t work = std::max<size_t>(std::max(m.n_verts, m.n_tris), 1);
+        m.first_block = n_blocks;
+        m.n_blocks = (int)std::min<size_t>(1024, (work + kMeshCheckThreads - 1) / kMeshCheckThreads);
+        n_blocks += m.n_blocks;
+    }
+    DeviceArray<MeshSource> d_table;
+    DeviceArray<float> partial;
+    DeviceArray<unsigned int> part_words;
+    DeviceArray<MeshReport> d_report;
+    RTGO_HIP(c, d_table.upload(table.data(), table.size(), c->stream));
+    RTGO_HIP(c, partial.alloc((size_t)6 * n_blocks));
+    RTGO_HIP(c, part_words.alloc((size_t)2 * n_blocks));
+    RTGO_HIP(c, d_report.alloc(table.size()));
+    hipLaunchKernelGGL(mesh_check_kernel, dim3(n_blocks), dim3(kMeshCheckThreads), 0, c->stream, (const MeshSource*)d_table.get(), (int)table.size(), n_materials,
+                       partial.get(), part_words.get());
+    hipLaunchKernelGGL(mesh_check_final_kernel, dim3((unsigned int)table.size()), dim3(kMeshCheckThreads), 0, c->stream, (const MeshSource*)d_table.get(),
+                       (const float*)partial.get(), (const unsigned int*)part_words.get(), d_report.get());
+    RTGO_HIP(c, hipGetLastError());
+    report.assign(table.size(), MeshReport{});
+    RTGO_HIP(c, hipMemcpyAsync(report.data(), d_report.get(), table.size() * sizeof(MeshReport), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    return RTGO_OK;
+}
+
+// the refusal whitted_check_mesh gives a mesh with these kinds of fault: the first in its order
+static int whitted_mesh_verdict(rtgo_ctx* c, const whitted::MeshReport& r, const std::string& at)
+{
+    for (int kind = 0; kind < whitted::kMeshFaultKinds; ++kind)
+        if (r.faults >> kind & 1u) return fail(c, RTGO_E_INVALID, at + kMeshFault[kind]);
+    return RTGO_OK;
+}
+
+// Stage 1 of rtgo_whitted_set_scene_device: whitted_layout_meshes for meshes whose arrays are device memory.  The host walks the meshes
+// in the twin's order and decides what pointers and counts decide; the data of every mesh before the first it refuses (of all, when it
+// refuses none) is checked where it lies, and the refusal is the twin's: the first mesh with a fault, and of its faults the first in
+// whitted_check_mesh's order.  The boxes and largest material indices come back with the verdict; nothing is packed yet
+// (lay.source: whitted_upload_meshes packs on the device, once the old scene is gone).  The stream has drained.
+static int whitted_layout_meshes_device(rtgo_ctx* c, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, uint32_t n_materials, WhittedLayout& lay, const char* what)
+{
+    using namespace whitted;
+    lay.info.assign(n_meshes, WhittedMeshInfo());
+    std::vector<MeshSource> table;
+    int refused = RTGO_OK;   // what the host refuses of mesh table.size(), kept until the meshes before it are known to be sound
+    std::string refusal;
+    for (uint32_t k = 0; k < n_meshes && !refused; ++k) {
+        const rtgo_whitted_mesh& q = meshes[k];
+        refused = whitted_admit_mesh(c, q, std::string(what) + ": mesh " + std::to_string(k), lay, true);
+        if (refused) {
+            refusal = c->err;
+            break;
+        }
+        table.push_back({q.positions, q.normals, q.texcoords, q.indices, q.material_of_triangle, q.n_vertices, q.n_triangles, 0, 0, (unsigned int)lay.n_vert,
+                         (unsigned int)lay.n_tri});
+        whitted_place_mesh(q, lay, lay.info[k]);
+    }
+    std::vector<MeshReport> report;
+    if (!table.empty())
+        if (const int rc = whitted_check_meshes_on_device(c, table, n_materials, report, lay.source_blocks)) return rc;
+    for (size_t k = 0; k < table.size(); ++k) {
+        if (const int rc = whitted_mesh_verdict(c, report[k], std::string(what) + ": mesh " + std::to_string(k))) return rc;
+        WhittedMeshInfo& mi = lay.info[k];
+        mi.max_material = report[k].max_material;
+        whitted_pad_mesh_box(report[k].lo, report[k].hi, mi.lo, mi.hi);
+    }
+    if (refused) return fail(c, refused, refusal);
+    lay.source = std::move(table);
+    return RTGO_OK;
+}
+
+// Stage 2: the packed meshes and the materials to the device, and the arrays the builds write.  Meshes on the device: one launch packs
+// them all (mesh_pack_kernel), whatever their number
 static int whitted_upload_meshes(rtgo_ctx* c, WhittedMesh& wm, const WhittedLayout& lay, const rtgo_pbr* materials, uint32_t n_materials)
 {
-    RTGO_HIP(c, wm.positions.upload(lay.pos.data(), lay.pos.size(), c->stream));
-    RTGO_HIP(c, wm.normals.upload(lay.nrm.data(), lay.nrm.size(), c->stream));
-    RTGO_HIP(c, wm.texcoords.upload(lay.uv.data(), lay.uv.size(), c->stream));
-    RTGO_HIP(c, wm.indices.upload(lay.idx.data(), lay.idx.size(), c->stream));
-    RTGO_HIP(c, wm.tri_material.upload(lay.tmat.data(), lay.tmat.size(), c->stream));
+    if (lay.on_device()) {
+        using namespace whitted;
+        DeviceArray<MeshSource> d_table;
+        RTGO_HIP(c, d_table.upload(lay.source.data(), lay.source.size(), c->stream));
+        RTGO_HIP(c, wm.positions.alloc(3 * lay.n_vert));
+        RTGO_HIP(c, wm.normals.alloc(3 * lay.n_vert));
+        RTGO_HIP(c, wm.texcoords.alloc(2 * lay.n_vert));
+        RTGO_HIP(c, wm.indices.alloc(3 * lay.n_tri));
+        RTGO_HIP(c, wm.tri_material.alloc(lay.n_tri));
+        hipLaunchKernelGGL(mesh_pack_kernel, dim3(lay.source_blocks), dim3(kMeshCheckThreads), 0, c->stream, (const MeshSource*)d_table.get(),
+                           (int)lay.source.size(), wm.positions.get(), wm.normals.get(), wm.texcoords.get(), wm.indices.get(), wm.tri_material.get());
+        RTGO_HIP(c, hipGetLastError());
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));   // (the table goes with this scope)
+    } else {
+        RTGO_HIP(c, wm.positions.upload(lay.pos.data(), lay.pos.size(), c->stream));
+        RTGO_HIP(c, wm.normals.upload(lay.nrm.data(), lay.nrm.size(), c->stream));
+        RTGO_HIP(c, wm.texcoords.upload(lay.uv.data(), lay.uv.size(), c->stream));
+        RTGO_HIP(c, wm.indices.upload(lay.idx.data(), lay.idx.size(), c->stream));
+        RTGO_HIP(c, wm.tri_material.upload(lay.tmat.data(), lay.tmat.size(), c->stream));
+    }
     RTGO_HIP(c, wm.materials.upload((const whitted::Pbr*)materials, n_materials, c->stream));
     RTGO_HIP(c, wm.recs.alloc(lay.n_tri * 4));
     RTGO_HIP(c, wm.tris.alloc(lay.n_tri * 3));
@@ -685,6 +812,93 @@ static int whitted_build_meshes(rtgo_ctx* c, WhittedMesh& wm, WhittedLayout& lay
     for (const WhittedMeshInfo& mi : lay.info) wm.mesh_depth = std::max(wm.mesh_depth, mi.depth);
     if (!table.empty()) RTGO_HIP(c, wm.clusters.upload(table.data(), table.size(), c->stream));
     wm.meshes = lay.info;
+    return RTGO_OK;
+}
+
+// rtgo_whitted_set_scene and rtgo_whitted_set_scene_device (`what`, for the messages; on_device: the meshes' arrays are device memory)
+// once the arguments themselves are known to be there: the stages above over a scene built aside.  A refusal by the checks, on the host or
+// on the device, leaves the old scene; once that is dropped, a failure leaves none.
+static int whitted_set_scene(rtgo_ctx* c, const char* what, const rtgo_whitted_mesh* meshes, uint32_t n_meshes, const rtgo_whitted_instance* instances,
+                             uint32_t n_instances, const rtgo_pbr* materials, uint32_t n_materials, bool on_device)
+{
+    WhittedLayout lay;
+    std::vector<whitted::InstShade> shade;
+    std::vector<float> box_pos;
+    if (on_device) {   // (the checks launch: the device current and the stream drained before them)
+        RTGO_HIP(c, hipSetDevice(c->device));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        if (const int rc = whitted_layout_meshes_device(c, meshes, n_meshes, n_materials, lay, what)) return rc;
+    } else if (const int rc = whitted_layout_meshes(c, meshes, n_meshes, n_materials, lay, what)) {
+        return rc;
+    }
+    if (const int rc = whitted_prepare_instances(c, lay.info, n_materials, instances, n_instances, shade, box_pos, what)) return rc;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    c->wm = WhittedMesh();
+    WhittedMesh next;
+    if (const int rc = whitted_upload_meshes(c, next, lay, materials, n_materials)) return rc;
+    if (const int rc = whitted_build_meshes(c, next, lay, what)) return rc;
+    // the clustered meshes' boxes took in their mid levels' boxes: the instance boxes again from them (the checks passed above)
+    if (next.clusters.get())
+        if (const int rc = whitted_prepare_instances(c, next.meshes, n_materials, instances, n_instances, shade, box_pos, what)) return rc;
+    if (const int rc = whitted_build_top(c, next, shade, box_pos, instances, what)) return rc;
+    if (const int rc = whitted_tile_heads(c)) return rc;
+    next.instanced = true;
+    next.triangles = (int)std::min(lay.n_tri, (size_t)0x7FFFFFFF);
+    c->wm = std::move(next);
+    return RTGO_OK;
+}
+
+// rtgo_whitted_set_mesh and rtgo_whitted_set_mesh_device (`what`; on_device: the mesh's arrays are device memory, checked where they
+// lie by the scene call's kernels over a table of this one mesh) once pointers and counts have passed
+static int whitted_set_mesh(rtgo_ctx* c, const char* what, const rtgo_whitted_mesh& mesh, const rtgo_pbr* materials, uint32_t n_materials, bool on_device)
+{
+    if (on_device) {
+        RTGO_HIP(c, hipSetDevice(c->device));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        std::vector<whitted::MeshSource> table = {{mesh.positions, mesh.normals, nullptr, mesh.indices, mesh.material_of_triangle, mesh.n_vertices, mesh.n_triangles, 0, 0, 0, 0}};
+        std::vector<whitted::MeshReport> report;
+        int n_blocks = 0;
+        if (const int rc = whitted_check_meshes_on_device(c, table, n_materials, report, n_blocks)) return rc;
+        if (const int rc = whitted_mesh_verdict(c, report[0], what)) return rc;
+    } else {
+        uint32_t max_material;
+        if (const int rc = whitted_check_mesh(c, mesh, n_materials, what, max_material)) return rc;
+    }
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    c->wm = WhittedMesh();   // (the old scene goes before the new one is allocated; a failure from here on leaves none)
+    WhittedMesh next;
+    if (const int rc = whitted_build_single(c, next, mesh, materials, n_materials, what, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) return rc;
+    if (const int rc = whitted_tile_heads(c)) return rc;
+    next.triangles = (int)mesh.n_triangles;
+    c->wm = std::move(next);
+    return RTGO_OK;
+}
+
+// rtgo_whitted_set_texcoords and rtgo_whitted_set_texcoords_device (`what`; on_device: uv is device memory) once state and count have
+// passed: the finite check (on the device: mesh_check_kernel over a table that has texture coordinates alone), then the copy
+static int whitted_set_texcoords(rtgo_ctx* c, const char* what, const float* uv, uint32_t n_vertices, bool on_device)
+{
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    bool bad = false;
+    if (uv && on_device) {
+        std::vector<whitted::MeshSource> table = {{nullptr, nullptr, uv, nullptr, nullptr, n_vertices, 0, 0, 0, 0, 0}};
+        std::vector<whitted::MeshReport> report;
+        int n_blocks = 0;
+        if (const int rc = whitted_check_meshes_on_device(c, table, 1, report, n_blocks)) return rc;
+        bad = report[0].faults != 0;
+    } else if (uv) {
+        for (size_t k = 0; k < (size_t)n_vertices * 2 && !bad; ++k) bad = !std::isfinite(uv[k]);
+    }
+    if (bad) return fail(c, RTGO_E_INVALID, std::string(what) + ": non-finite coordinate");
+    c->wm.texcoords.reset();
+    if (uv) {
+        RTGO_HIP(c, c->wm.texcoords.alloc((size_t)n_vertices * 2));
+        RTGO_HIP(c, hipMemcpyAsync(c->wm.texcoords.get(), uv, (size_t)n_vertices * 2 * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    }
     return RTGO_OK;
 }
 
