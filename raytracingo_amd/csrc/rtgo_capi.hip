@@ -1737,7 +1737,13 @@ static int update_hot_mask(rtgo_ctx* c, uint32_t strip_px, LaunchParams& p, unsi
             all_hot = hot_bits == (size_t)p.n_hot;
         }
         if (!all_hot) {
-            if (words > hm.d.size()) RTGO_HIP(c, hm.d.alloc(words));
+            if (words > hm.d.size()) {
+                // (launches still queued were given the old buffer, and freeing it would wait for the whole device: it is set aside
+                // until rtgo_sync has waited for the stream.  Growing to at least twice the size keeps what is set aside below what is held)
+                const size_t grown = words > 2 * hm.d.size() ? words : 2 * hm.d.size();
+                if (hm.d.get()) hm.retired.push_back(std::move(hm.d));
+                RTGO_HIP(c, hm.d.alloc(grown));
+            }
             // (the previous launch may still be reading the old mask: stream order takes care of it.)  The copy leaves from pinned
             // memory the context keeps, so nothing here waits for the stream; a slot is reused two rebuilds later, by when its copy
             // has long completed (the event wait is a formality)
@@ -2624,6 +2630,7 @@ int rtgo_sync(rtgo_ctx* c)
     if (!c) return RTGO_E_INVALID;
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    c->mask.retired.clear();   // (no launch reads an outgrown hot mask any more)
     return harvest_events(c, c->ev_pending);
 }
 

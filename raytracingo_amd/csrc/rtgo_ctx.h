@@ -204,6 +204,7 @@ struct rtgo_ctx {
     // outlive a scene
     struct HotMask {
         DeviceArray<unsigned int> d;
+        std::vector<DeviceArray<unsigned int>> retired;   // masks outgrown while launches that read them may be queued; freed by rtgo_sync
         // pinned staging for its upload, two slots used in turn with an event each: a camera change (every frame of an interactive
         // drag) rebuilds the mask, and the upload must not make the host wait for the stream
         PinnedArray<unsigned int> h[2];
