@@ -211,6 +211,51 @@ int rtgo_set_scene_device(rtgo_ctx* ctx, const void* d_prims, const void* d_aabb
 int rtgo_set_large_scene_device(rtgo_ctx* ctx, const void* d_prims, const void* d_aabbs, uint32_t n);
 int rtgo_update_prims_device(rtgo_ctx* ctx, const void* d_indices, const void* d_prims, const void* d_aabbs, uint32_t n_updates, uint32_t flags);
 
+/* What became of an update of rtgo_update_prims_device_async */
+enum { RTGO_UPDATE_PENDING = 0, RTGO_UPDATE_APPLIED = 1, RTGO_UPDATE_REFUSED = 2 };
+typedef struct rtgo_update_status {   /* 16 bytes */
+    uint32_t state;   /* RTGO_UPDATE_* */
+    uint32_t fault;   /* 0 none; 1 unknown type, 2 value not finite, 3 singular matrix, 4 bad box,
+                         5 index beyond the scene, 6 index named twice, 7 box outside `reach` */
+    uint32_t entry;   /* REFUSED: the lowest offending entry of the lowest-numbered kind that
+                         rtgo_update_prims_device's message would name */
+    uint32_t reserved;
+} rtgo_update_status;
+
+/* rtgo_update_prims_device with RTGO_UPDATE_REFIT over a scene of rtgo_set_large_scene or rtgo_set_large_scene_device, enqueued on the
+   context's stream: it waits for nothing on the host -- not for the stream, a verdict, the refit's `changed` word or the root box -- so a
+   loop of "step the simulation, refit, rtgo_launch" on one stream never drains the GPU.  d_indices, d_prims, d_aabbs:
+   DEVICE memory of the context's device, caller-owned, 4-byte aligned, overlapping nothing of the context; the call reads them and never
+   writes to them.  The caller's writes to them must be complete, or ordered on the context's stream (rtgo_set_stream), before the call;
+   they must stay as they are until the update has run (rtgo_sync, or anything later on the stream).
+   Decided on the host, at once; each returns its code, enqueues nothing and issues no ticket -- RTGO_E_INVALID: NULL ctx, d_prims,
+   d_indices or ticket, a pointer that is not 4-byte aligned, d_aabbs given or NULL against the scene, n_updates above the scene's count,
+   a reach that is not finite or has min > max on an axis; RTGO_E_STATE: no analytic scene; RTGO_E_UNSUPPORTED: a scene of rtgo_set_scene
+   (its update is a whole build with host readers -- the emitter certificates, the quadric list, the grid -- and stays with the
+   synchronous call).  n_updates == 0 with a large scene: RTGO_OK and *ticket = 0, nothing is enqueued.
+   Every other call returns RTGO_OK and a ticket, and the six faults rtgo_update_prims_device finds on the device, with a seventh, are
+   decided there later.  An update with a fault changes NOTHING of the scene -- no record, box, leaf or mark -- and says so through
+   rtgo_update_prims_status; the kernels that write the scene read the check's verdict on the device first.  Updates enqueued after it
+   are judged by their own verdicts alone.  An update without a fault leaves, bit for bit, what rtgo_update_prims_device leaves.
+   reach replaces the read-back of the root box: a box inside which every updated primitive's box stays (the simulation's domain); NULL:
+   the bounds the context holds now.  An entry whose box -- the given one, or without boxes the CubeBox rule's -- does not lie inside it is
+   fault 7.  The context's bounds become the union of its bounds and reach, whatever the verdict: pixels, hits, shaded rays and the ray
+   counts are unaffected (a pixel culled by the screen rectangle and a pixel traced to a miss are the same bits and the same count);
+   rtgo_stats.rays_culled and the collect_stats == 2 counters may differ from those after rtgo_update_prims_device, and nothing else may.
+   A later synchronous update that moves a box, or a set call, makes the bounds tight again.  The screen-rectangle mask, the pre-hashed
+   seeds and the launch-time trial are dropped as by rtgo_update_prims.
+   Allocations: a context's first call allocates its ring of 64 tickets (device words, their pinned copy, events), a scene's first call
+   the index check's word per primitive; no other call allocates or frees anything. */
+int rtgo_update_prims_device_async(rtgo_ctx* ctx, const void* d_indices, const void* d_prims, const void* d_aabbs, uint32_t n_updates,
+                                   const rtgo_aabb* reach, uint64_t* ticket);
+
+/* The state of a ticket of rtgo_update_prims_device_async.  Never blocks: one event query.  PENDING: the check has not finished.
+   APPLIED: the check found no fault, and the update is done or ordered on the stream ahead of everything enqueued after its call.
+   REFUSED: fault and entry say why; the scene is as it was.  Ticket 0 is APPLIED.  The context keeps its last 64 tickets: an older one, or
+   one never issued, is RTGO_E_INVALID (as are a NULL ctx or out); a 65th update enqueued while 64 are in flight waits once for the oldest
+   ticket's check, as rtgo_launch's ring of event pairs does.  After rtgo_sync every ticket the context keeps is APPLIED or REFUSED. */
+int rtgo_update_prims_status(rtgo_ctx* ctx, uint64_t ticket, rtgo_update_status* out);
+
 /* raygen SBT record: Renderer::CreateRayGen / SyncCameraToSbt (renderer.cpp:321-336, 719-731); device::CameraData */
 int rtgo_set_camera(rtgo_ctx* ctx, const float eye[3], const float U[3], const float V[3], const float W[3]);
 

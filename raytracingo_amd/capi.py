@@ -30,7 +30,9 @@ SYMBOLS = [
     "rtgo_shade_rays", "rtgo_update_prims", "rtgo_whitted_update_meshes_device",
     "rtgo_set_scene_device", "rtgo_set_large_scene_device", "rtgo_update_prims_device", "rtgo_whitted_set_instances_device",
     "rtgo_whitted_set_scene_device", "rtgo_whitted_set_mesh_device", "rtgo_whitted_set_texcoords_device",
+    "rtgo_update_prims_device_async", "rtgo_update_prims_status",
 ]
+UPDATE_PENDING, UPDATE_APPLIED, UPDATE_REFUSED = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 TRACE_CLOSEST, TRACE_ANY_HIT = 0, 1
 HIT_MISS, HIT_INVALID = -1, -2
@@ -94,6 +96,10 @@ class WhittedInstance(C.Structure):
 
 class WhittedMeshUpdate(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("n_vertices", C.c_uint32)]
+
+
+class UpdateStatus(C.Structure):
+    _fields_ = [("state", C.c_uint32), ("fault", C.c_uint32), ("entry", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -161,6 +167,8 @@ def load():
     L.rtgo_set_scene_device.argtypes = [vp, vp, vp, C.c_uint32]
     L.rtgo_set_large_scene_device.argtypes = [vp, vp, vp, C.c_uint32]
     L.rtgo_update_prims_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32]
+    L.rtgo_update_prims_device_async.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(Aabb), C.POINTER(C.c_uint64)]
+    L.rtgo_update_prims_status.argtypes = [vp, C.c_uint64, C.POINTER(UpdateStatus)]
     L.rtgo_set_camera.argtypes = [vp, fp, fp, fp, fp]
     L.rtgo_set_background.argtypes = [vp, fp]
     L.rtgo_set_lights.argtypes = [vp, C.POINTER(Light), C.c_int]
@@ -356,6 +364,25 @@ class Context:
         aabbs: given exactly when the scene was set with boxes.  rebuild: RTGO_UPDATE_REBUILD, else a refit.  Synchronous."""
         k, (i, p, b) = self._device_args("update_prims_device", indices, prims, aabbs)
         self._check(self._lib.rtgo_update_prims_device(self._h, i, p, b, k, UPDATE_REBUILD if rebuild else UPDATE_REFIT), "rtgo_update_prims_device")
+
+    def update_prims_device_async(self, indices, prims, aabbs=None, reach=None):
+        """rtgo_update_prims_device_async: update_prims_device's refit of a scene of set_large_scene[_device], enqueued on the context's
+        stream with no wait on the host -- none here either: the tensors' writes must be complete or ordered on that stream.  reach: six
+        floats (min xyz, max xyz), a box every updated primitive's box stays inside; None: the bounds the context holds.  Returns the
+        ticket update_prims_status takes."""
+        k, (i, p, b) = device_prims_args("update_prims_device_async", self.device, indices, prims, aabbs)
+        box = None if reach is None else Aabb(*[float(x) for x in np.asarray(reach, dtype=np.float32).reshape(6)])
+        ticket = C.c_uint64(0)
+        self._check(self._lib.rtgo_update_prims_device_async(self._h, i, p, b, k, None if box is None else C.byref(box), C.byref(ticket)),
+                    "rtgo_update_prims_device_async")
+        return ticket.value
+
+    def update_prims_status(self, ticket):
+        """rtgo_update_prims_status: {"state": UPDATE_PENDING / UPDATE_APPLIED / UPDATE_REFUSED, "fault": 0 or the kind 1 .. 7, "entry": the
+        offending entry of a refused update}; never blocks"""
+        st = UpdateStatus()
+        self._check(self._lib.rtgo_update_prims_status(self._h, int(ticket), C.byref(st)), "rtgo_update_prims_status")
+        return {"state": st.state, "fault": st.fault, "entry": st.entry}
 
     def set_camera(self, eye, U, V, W):
         a = [_f3(x) for x in (eye, U, V, W)]
@@ -884,7 +911,7 @@ def instances_tensor(transforms, meshes, material_offsets):
 
 
 def device_prims_args(who, device, indices, prims, aabbs):
-    """The checks of Context.set_scene_device / set_large_scene_device / update_prims_device on their tensors (needs no context).
+    """The checks of Context.set_scene_device / set_large_scene_device / update_prims_device[_async] on their tensors (needs no context).
     prims: contiguous, k * 108 bytes, uint8 [k, 108] or int32 / float32 [k, 27]; aabbs: contiguous float32 [k, 6] or None; indices:
     contiguous int32 [k] or None (the set calls); all on device `device`.  Returns (k, [indices pointer or None, prims pointer, aabbs
     pointer or None]); ValueError for a tensor that is not on that device, is not contiguous, or has another dtype, shape or byte count."""

@@ -1138,6 +1138,18 @@ static int update_resident(rtgo_ctx* c, const AnalyticScene& old, const UpdateRe
     return rc;
 }
 
+// The stamp of one refit over the large scene's mark words
+static int next_mark_epoch(rtgo_ctx* c, unsigned int& epoch)
+{
+    AnalyticScene::LargeKeep& keep = c->scene.keep;
+    if (++keep.epoch == 0) {   // (the counter wrapped: start over with clean marks)
+        RTGO_HIP(c, hipMemsetAsync(keep.mark.get(), 0, keep.mark.size() * sizeof(unsigned int), c->stream));
+        keep.epoch = 1;
+    }
+    epoch = keep.epoch;
+    return RTGO_OK;
+}
+
 // A scene of rtgo_set_large_scene, refitted or rebuilt in place (`what`: the entry point, for the message)
 static int update_large(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const std::string& what)
 {
@@ -1149,11 +1161,8 @@ static int update_large(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const st
     RTGO_HIP(c, d_changed.alloc(1));
     RTGO_HIP(c, hipMemsetAsync(d_changed.get(), 0, sizeof(int), c->stream));
     if (!rebuild) {
-        if (++sc.keep.epoch == 0) {   // (the counter wrapped: start over with clean marks)
-            RTGO_HIP(c, hipMemsetAsync(sc.keep.mark.get(), 0, sc.keep.mark.size() * sizeof(unsigned int), c->stream));
-            sc.keep.epoch = 1;
-        }
-        const unsigned int epoch = sc.keep.epoch;
+        unsigned int epoch = 0;
+        if (const int rc = next_mark_epoch(c, epoch)) return rc;
         hipLaunchKernelGGL(large_update_kernel, g_upd, dim3(256), 0, c->stream, u.idx, u.prims, u.aabbs, (int)k, (const int*)sc.keep.leaf_of.get(),
                            (const int*)sc.keep.parent.get(), epoch, sc.keep.mark.get(), sc.d_prims.get(), sc.d_aabb.get(), sc.d_nodes.get(), (float4*)nullptr,
                            (float*)nullptr, d_changed.get());
@@ -1197,6 +1206,14 @@ static int update_large(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const st
     return RTGO_OK;
 }
 
+// What was cached for the scene as it was (drop_scene's list): a primitive moved outside the old screen rectangle must not be culled
+static void drop_launch_caches(rtgo_ctx* c)
+{
+    c->seeds = rtgo_ctx::Seeds();
+    c->mask.key.clear();
+    c->trial = rtgo_ctx::Trial();
+}
+
 // The tail of rtgo_update_prims and rtgo_update_prims_device, for updates that passed every check (the stream idle): the large / resident
 // split, the old scene set aside and put back when the build is refused, and what was cached for the scene as it was dropped
 static int apply_updates(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const std::string& what)
@@ -1215,10 +1232,7 @@ static int apply_updates(rtgo_ctx* c, const UpdateRefs& u, bool rebuild, const s
             return rc;
         }
     }
-    // what was cached for the scene as it was (drop_scene's list): a primitive moved outside the old screen rectangle must not be culled
-    c->seeds = rtgo_ctx::Seeds();
-    c->mask.key.clear();
-    c->trial = rtgo_ctx::Trial();
+    drop_launch_caches(c);
     return RTGO_OK;
 }
 
@@ -1251,24 +1265,31 @@ int rtgo_update_prims(rtgo_ctx* c, const uint32_t* indices, const rtgo_prim* pri
 
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
+// The stamp of one index check over the scene's n claim words (allocated by the scene's first such check), the words cleared on the
+// stream when the array is fresh or the counter wrapped
+static int next_claim_epoch(rtgo_ctx* c, uint32_t n, unsigned int& epoch)
+{
+    AnalyticScene::Claim& cl = c->scene.claim;
+    if (cl.d.size() != n) {
+        RTGO_HIP(c, cl.d.alloc(n));
+        cl.epoch = 0;
+    }
+    if (cl.epoch == 0 || ++cl.epoch == 0) {   // (a fresh array, or the counter wrapped: start over with clean words)
+        RTGO_HIP(c, hipMemsetAsync(cl.d.get(), 0, (size_t)n * sizeof(unsigned int), c->stream));
+        cl.epoch = 1;
+    }
+    epoch = cl.epoch;
+    return RTGO_OK;
+}
+
 // check_prims, and with d_idx rtgo_update_prims' index rules over a scene of n primitives, for k entries in device memory: one launch of
 // prims_check_kernel, its verdict read back with one wait.  Nothing of the scene is written; the stream is idle when it returns.
 static int check_prims_device(rtgo_ctx* c, const void* d_idx, const void* d_prims, const void* d_aabbs, uint32_t k, uint32_t n, const std::string& what)
 {
     if (!c->d_verdict.get()) RTGO_HIP(c, c->d_verdict.alloc(kVerdictWords));
     unsigned int epoch = 0;
-    if (d_idx) {
-        AnalyticScene::Claim& cl = c->scene.claim;
-        if (cl.d.size() != n) {
-            RTGO_HIP(c, cl.d.alloc(n));
-            cl.epoch = 0;
-        }
-        if (cl.epoch == 0 || ++cl.epoch == 0) {   // (a fresh array, or the counter wrapped: start over with clean words)
-            RTGO_HIP(c, hipMemsetAsync(cl.d.get(), 0, (size_t)n * sizeof(unsigned int), c->stream));
-            cl.epoch = 1;
-        }
-        epoch = cl.epoch;
-    }
+    if (d_idx)
+        if (const int rc = next_claim_epoch(c, n, epoch)) return rc;
     RTGO_HIP(c, hipMemsetAsync(c->d_verdict.get(), 0xFF, kVerdictWords * sizeof(unsigned int), c->stream));
     hipLaunchKernelGGL(prims_check_kernel, dim3((k + 255) / 256), dim3(256), 0, c->stream, static_cast<const unsigned int*>(d_prims),
                        static_cast<const float*>(d_aabbs), static_cast<const unsigned int*>(d_idx), k, n, epoch, c->scene.claim.d.get(), c->d_verdict.get());
@@ -1331,6 +1352,116 @@ int rtgo_update_prims_device(rtgo_ctx* c, const void* d_indices, const void* d_p
     const UpdateRefs u = {static_cast<const unsigned int*>(d_indices), static_cast<const PrimIn*>(d_prims), static_cast<const float*>(d_aabbs), n_updates, nullptr,
                           nullptr};
     return apply_updates(c, u, (flags & RTGO_UPDATE_REBUILD) != 0, what);
+}
+
+// ---- the refit that waits for nothing on the host ----
+
+// The first call's allocations: the ring's device words (the `changed` words zero; every call fills its verdict itself), their pinned
+// copy and the events
+static int alloc_update_ring(rtgo_ctx* c)
+{
+    rtgo_ctx::UpdateRing& ring = c->updates;
+    const size_t slots = rtgo_ctx::UpdateRing::kSlots;
+    RTGO_HIP(c, ring.d.alloc(slots * (kVerdictWords + 1)));
+    RTGO_HIP(c, ring.h.alloc(slots * kVerdictWords));
+    for (size_t s = 0; s < slots; ++s)
+        if (!ring.done[s].get()) RTGO_HIP(c, ring.done[s].create(hipEventDisableTiming));
+    return RTGO_OK;
+}
+
+int rtgo_update_prims_device_async(rtgo_ctx* c, const void* d_indices, const void* d_prims, const void* d_aabbs, uint32_t n_updates,
+                                   const rtgo_aabb* reach, uint64_t* ticket)
+{
+    const std::string what = "rtgo_update_prims_device_async";
+    if (!c) return fail(c, RTGO_E_INVALID, what + ": NULL context");
+    if (!ticket) return fail(c, RTGO_E_INVALID, what + ": NULL ticket");
+    AnalyticScene& sc = c->scene;
+    const uint32_t n = sc.n_prims, k = n_updates;
+    if (n == 0) return fail(c, RTGO_E_STATE, what + ": no analytic scene (rtgo_set_large_scene first)");
+    if (!sc.large)
+        return fail(c, RTGO_E_UNSUPPORTED, what + ": a scene of rtgo_set_scene is built again by its update, with host readers (rtgo_update_prims_device)");
+    if (k == 0) {
+        *ticket = 0;
+        return RTGO_OK;
+    }
+    if (!d_indices || !d_prims) return fail(c, RTGO_E_INVALID, what + ": NULL argument");
+    if (!aligned4(d_indices) || !aligned4(d_prims) || !aligned4(d_aabbs)) return fail(c, RTGO_E_INVALID, what + ": a pointer is not 4-byte aligned");
+    if ((d_aabbs != nullptr) != sc.have_aabbs)
+        return fail(c, RTGO_E_INVALID, what + (sc.have_aabbs ? ": the scene was set with boxes, the updates need theirs"
+                                                             : ": the scene was set without boxes, the updates cannot bring any"));
+    if (k > n)   // (by pigeonhole an index repeats or lies beyond the scene)
+        return fail(c, RTGO_E_INVALID, what + ": " + std::to_string(k) + " updates for a scene of " + std::to_string(n) + " primitives");
+    ReachBox rb;
+    const float* r = reach ? &reach->minX : sc.bounds;
+    for (int a = 0; a < 3; ++a) {
+        rb.lo[a] = r[a];
+        rb.hi[a] = r[3 + a];
+        if (!std::isfinite(r[a]) || !std::isfinite(r[3 + a]) || r[a] > r[3 + a]) return fail(c, RTGO_E_INVALID, what + ": reach is empty or not finite");
+    }
+    RTGO_HIP(c, hipSetDevice(c->device));
+    rtgo_ctx::UpdateRing& ring = c->updates;
+    if (!ring.d.get())
+        if (const int rc = alloc_update_ring(c)) return rc;
+    const uint64_t t = ring.next;
+    const unsigned int slot = rtgo_ctx::UpdateRing::slot(t);
+    // the slot's last ticket leaves the ring; a ring full of updates in flight waits here for the oldest, as timed_launch's does
+    if (ring.next_reuses_a_slot()) RTGO_HIP(c, hipEventSynchronize(ring.done[slot].get()));
+    unsigned int *d_verdict = ring.d.get() + (size_t)slot * kVerdictWords, *d_changed = ring.d.get() + rtgo_ctx::UpdateRing::kSlots * kVerdictWords + slot;
+    unsigned int claim_epoch = 0, mark_epoch = 0;
+    if (const int rc = next_claim_epoch(c, n, claim_epoch)) return rc;
+    if (const int rc = next_mark_epoch(c, mark_epoch)) return rc;
+    RTGO_HIP(c, hipMemsetAsync(d_verdict, 0xFF, kVerdictWords * sizeof(unsigned int), c->stream));
+    RTGO_HIP(c, hipMemsetAsync(d_changed, 0, sizeof(unsigned int), c->stream));
+    const unsigned int *idx = static_cast<const unsigned int*>(d_indices), *prims = static_cast<const unsigned int*>(d_prims);
+    const float* boxes = static_cast<const float*>(d_aabbs);
+    const int n_internal = (int)n - 1;
+    const dim3 g_upd((k + 255) / 256), g_int((std::max(n_internal, 1) + 255) / 256);
+    hipLaunchKernelGGL(prims_check_reach_kernel, g_upd, dim3(256), 0, c->stream, prims, boxes, idx, k, n, claim_epoch, sc.claim.d.get(), d_verdict, rb);
+    RTGO_HIP(c, hipMemcpyAsync(ring.h.get() + (size_t)slot * kVerdictWords, d_verdict, kVerdictWords * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipEventRecord(ring.done[slot].get(), c->stream));
+    // the gated kernels: all of them, every time -- neither the verdict nor `changed` is known here
+    hipLaunchKernelGGL(large_update_staged_kernel, g_upd, dim3(256), 0, c->stream, (const unsigned int*)d_verdict, idx, prims, boxes, k,
+                       (const int*)sc.keep.leaf_of.get(), (const int*)sc.keep.parent.get(), mark_epoch, sc.keep.mark.get(), sc.d_prims.get(), sc.d_aabb.get(),
+                       sc.d_nodes.get(), d_changed);
+    for (int level = sc.lbvh_depth - 1; level >= 0; --level)
+        hipLaunchKernelGGL(large_refit_gated_kernel, g_int, dim3(256), 0, c->stream, (const unsigned int*)d_verdict, (const unsigned int*)d_changed,
+                           (const int*)sc.keep.depth.get(), (const unsigned int*)sc.keep.mark.get(), mark_epoch, n_internal, level, sc.d_nodes.get());
+    RTGO_HIP(c, hipGetLastError());
+    // the root box is not read back: from now on the scene lies inside the old bounds or inside `reach`, applied or refused
+    for (int a = 0; a < 3; ++a) {
+        sc.bounds[a] = std::fmin(sc.bounds[a], rb.lo[a]);
+        sc.bounds[3 + a] = std::fmax(sc.bounds[3 + a], rb.hi[a]);
+    }
+    drop_launch_caches(c);   // (a large scene's launches keep no seed buffers: nothing is freed here)
+    ring.next = t + 1;
+    *ticket = t;
+    return RTGO_OK;
+}
+
+int rtgo_update_prims_status(rtgo_ctx* c, uint64_t ticket, rtgo_update_status* out)
+{
+    const std::string what = "rtgo_update_prims_status";
+    if (!c || !out) return fail(c, RTGO_E_INVALID, what + ": NULL argument");
+    *out = rtgo_update_status{RTGO_UPDATE_APPLIED, 0, 0, 0};
+    if (ticket == 0) return RTGO_OK;
+    const rtgo_ctx::UpdateRing& ring = c->updates;
+    if (!ring.holds(ticket)) return fail(c, RTGO_E_INVALID, what + ": ticket " + std::to_string(ticket) + " was never issued or has left the ring of the last 64");
+    const unsigned int slot = rtgo_ctx::UpdateRing::slot(ticket);
+    RTGO_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = hipEventQuery(ring.done[slot].get());
+    if (e == hipErrorNotReady) {
+        (void)hipGetLastError();   // (not an error: the next call's hipGetLastError must not find it)
+        out->state = RTGO_UPDATE_PENDING;
+        return RTGO_OK;
+    }
+    RTGO_HIP(c, e);
+    // the lowest offending entry, of the lowest-numbered kind that names it: check_prims_device's choice for its message
+    const unsigned int* v = ring.h.get() + (size_t)slot * kVerdictWords;
+    int kind = -1;
+    for (int q = 0; q < kAsyncVerdictKinds; ++q)
+        if (v[q] != kNoFault && (kind < 0 || v[q] < v[kind])) kind = q;
+    if (kind >= 0) *out = rtgo_update_status{RTGO_UPDATE_REFUSED, (uint32_t)kind + 1u, v[kind], 0};
+    return RTGO_OK;
 }
 
 int rtgo_set_camera(rtgo_ctx* c, const float eye[3], const float U[3], const float V[3], const float W[3])

@@ -7,6 +7,7 @@
 #include "rtgo_large.h"
 #include "rtgo_owners.h"
 #include "rtgo_shade.h"
+#include "rtgo_ticket_ring.h"
 #include "rtgo_trace.h"
 #include "rtgo_whitted_big.h"
 #include "rtgo_whitted_inst.h"
@@ -160,6 +161,13 @@ struct rtgo_ctx {
     int n_lights = 0;
     DeviceArray<int> d_meta;               // build_kernel's meta words (one build at a time)
     DeviceArray<unsigned int> d_verdict;   // prims_check_kernel's or inst_prepare_kernel's verdict (kVerdictWords; allocated by the first device-pointer call)
+    // rtgo_update_prims_device_async: the tickets (rtgo_ticket_ring.h) and what each slot holds.  Allocated by the
+    // context's first such call, then reused: no call after it allocates or frees.
+    struct UpdateRing : TicketRing {
+        DeviceArray<unsigned int> d;       // kSlots verdicts of kVerdictWords words, then kSlots `changed` words
+        PinnedArray<unsigned int> h;       // the verdicts as copied back behind each check
+        LazyEvent done[kSlots];            // recorded behind that copy: what rtgo_update_prims_status queries
+    } updates;
     int leaf_budget = kDefaultLeafBudget;
     bool have_camera = false;
     v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};

@@ -20,6 +20,10 @@
 //   prims_patch_kernel    a scene of rtgo_set_scene: the updates scattered into build_kernel's inputs
 // and the checks of the calls that take records, boxes and indices from device memory:
 //   prims_check_kernel    per entry: the host's check_prims rules and the index rules of rtgo_update_prims, into a verdict of a few words
+// and the refit that waits for nothing on the host (rtgo_update_prims_device_async):
+//   prims_check_reach_kernel    prims_check_kernel plus the test of each entry's box against the caller's `reach`
+//   large_update_staged_kernel  large_update_kernel's refit behind the verdict's gate, its records staged in LDS
+//   large_refit_gated_kernel    large_refit_kernel behind the gate and the ticket's `changed` word
 #pragma once
 
 #include "rtgo_device.h"
@@ -159,16 +163,22 @@ __global__ __launch_bounds__(256) void large_update_kernel(const unsigned int* _
     }
 }
 
+// internal node i: large_fit_kernel's box, the links read from the node itself
+__device__ __forceinline__ void refit_node(int i, float4* __restrict__ nodes)
+{
+    const int L = __float_as_int(nodes[2 * (size_t)i].w), R = __float_as_int(nodes[2 * (size_t)i + 1].w);
+    const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
+    nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
+    nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+}
+
 // the marked internal nodes at depth `level`: large_fit_kernel's box, from children an earlier launch (or large_update_kernel) wrote
 __global__ __launch_bounds__(256) void large_refit_kernel(const int* __restrict__ depth, const unsigned int* __restrict__ mark, unsigned int epoch,
                                                           int n_internal, int level, float4* __restrict__ nodes)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_internal || mark[i] != epoch || depth[i] != level) return;
-    const int L = __float_as_int(nodes[2 * (size_t)i].w), R = __float_as_int(nodes[2 * (size_t)i + 1].w);
-    const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
-    nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
-    nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+    refit_node(i, nodes);
 }
 
 __global__ __launch_bounds__(256) void large_restore_kernel(const unsigned int* __restrict__ idx, const float4* __restrict__ old_prims,
@@ -199,6 +209,7 @@ __global__ __launch_bounds__(256) void prims_patch_kernel(const unsigned int* __
 constexpr int kPrimDwords = 27;
 static_assert(sizeof(PrimIn) == kPrimDwords * sizeof(unsigned int), "rtgo_prim is 27 dwords");
 enum { kBadType = 0, kBadFloat = 1, kBadMatrix = 2, kBadBox = 3, kBadIndex = 4, kBadTwice = 5, kVerdictKinds = 6, kVerdictWords = 8 };
+enum { kBadReach = 6, kAsyncVerdictKinds = 7 };   // the seventh kind, of rtgo_update_prims_device_async's check alone
 constexpr unsigned int kNoFault = 0xFFFFFFFFu;
 
 // Entry j < k: record prims[j] (27 dwords), box aabbs[j] (aabbs nullable), index idx[j] (idx nullable: the set calls).
@@ -207,15 +218,15 @@ constexpr unsigned int kNoFault = 0xFFFFFFFFu;
 // stride 27, odd, so free of bank conflicts.  The last workgroup loads the dwords of its own entries only: nothing beyond the caller's
 // k entries is read.  An index is compared with n before anything else is done with it; one in range is claimed by writing `epoch` into
 // claim[index] (n words of the scene's, stamped per call like LargeKeep::mark): whoever finds `epoch` there already is the second to name it.
-__global__ __launch_bounds__(256) void prims_check_kernel(const unsigned int* __restrict__ prims, const float* __restrict__ aabbs,
-                                                          const unsigned int* __restrict__ idx, unsigned int k, unsigned int n, unsigned int epoch,
-                                                          unsigned int* __restrict__ claim, unsigned int* __restrict__ verdict)
+
+// The staging: the workgroup's entries [base, base + here) of prims (and of aabbs, nullable) into s_prim [256 * kPrimDwords] and s_box
+// [256 * 6]; every thread of the workgroup calls it.  Returns `here`, at most 256; 0 for a workgroup beyond the k entries (nothing is
+// loaded and no barrier passed: the whole workgroup leaves).
+__device__ __forceinline__ unsigned int stage_entries(const unsigned int* __restrict__ prims, const float* __restrict__ aabbs, unsigned int k,
+                                                      unsigned int* s_prim, float* s_box)
 {
-#pragma clang fp contract(off)
-    __shared__ unsigned int s_prim[256 * kPrimDwords];
-    __shared__ float s_box[256 * 6];
     const unsigned int tid = threadIdx.x, base = blockIdx.x * 256u;
-    if (base >= k) return;
+    if (base >= k) return 0;
     const unsigned int here = k - base < 256u ? k - base : 256u;   // this workgroup's entries
     const unsigned int* src = prims + (size_t)base * kPrimDwords;
     for (unsigned int d = tid; d < here * kPrimDwords; d += 256u) s_prim[d] = src[d];
@@ -224,7 +235,23 @@ __global__ __launch_bounds__(256) void prims_check_kernel(const unsigned int* __
         for (unsigned int d = tid; d < here * 6u; d += 256u) s_box[d] = bsrc[d];
     }
     __syncthreads();
-    const unsigned int j = base + tid;
+    return here;
+}
+
+// what rtgo_update_prims_device_async's caller vouches for: every updated primitive's box lies inside
+struct ReachBox {
+    float lo[3], hi[3];
+};
+
+// The checks of the staged entries.  REACH: also kBadReach, for an entry whose box -- the given one, or without boxes the cube_aabb of its
+// matrix, the box the update would write -- does not lie inside `reach` (a box that is not finite lies inside nothing).
+template <bool REACH>
+__device__ __forceinline__ void check_entries(unsigned int here, const unsigned int* s_prim, const float* s_box, bool have_boxes,
+                                              const unsigned int* __restrict__ idx, unsigned int n, unsigned int epoch,
+                                              unsigned int* __restrict__ claim, unsigned int* __restrict__ verdict, const ReachBox& reach)
+{
+#pragma clang fp contract(off)
+    const unsigned int tid = threadIdx.x, j = blockIdx.x * 256u + tid;
     unsigned int bad = 0;
     if (tid < here) {
         const unsigned int* r = s_prim + tid * kPrimDwords;
@@ -238,9 +265,22 @@ __global__ __launch_bounds__(256) void prims_check_kernel(const unsigned int* __
         const double a20 = __uint_as_float(r[9]), a21 = __uint_as_float(r[10]), a22 = __uint_as_float(r[11]);
         const double det = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
         if (!isfinite(det) || fabs(det) < 1e-30) bad |= 1u << kBadMatrix;
-        if (aabbs) {
+        if (have_boxes) {
             const float* b = s_box + tid * 6;
             if (!(b[0] <= b[3] && b[1] <= b[4] && b[2] <= b[5]) || !isfinite(b[0] + b[1] + b[2] + b[3] + b[4] + b[5])) bad |= 1u << kBadBox;
+        }
+        if (REACH) {
+            float bb[6];
+            if (have_boxes) {
+                for (int a = 0; a < 6; ++a) bb[a] = s_box[tid * 6 + a];
+            } else {
+                float M[16];
+                for (int q = 0; q < 16; ++q) M[q] = __uint_as_float(r[1 + q]);
+                cube_aabb(M, bb);
+            }
+            bool inside = true;
+            for (int a = 0; a < 3; ++a) inside = inside && bb[a] >= reach.lo[a] && bb[3 + a] <= reach.hi[a];
+            if (!inside) bad |= 1u << kBadReach;
         }
         if (idx) {
             const unsigned int i = idx[j];
@@ -251,10 +291,105 @@ __global__ __launch_bounds__(256) void prims_check_kernel(const unsigned int* __
     // the lowest offending entry of the wave, one atomic per wave and kind
     if (!__any(bad != 0)) return;
     const unsigned int lane = tid & 63u;
-    for (int kind = 0; kind < kVerdictKinds; ++kind) {
+    for (int kind = 0; kind < (REACH ? kAsyncVerdictKinds : kVerdictKinds); ++kind) {
         const unsigned long long m = __ballot((bad >> kind) & 1u);
         if (m != 0 && lane == (unsigned int)(__ffsll((long long)m) - 1)) atomicMin(&verdict[kind], j);
     }
+}
+
+__global__ __launch_bounds__(256) void prims_check_kernel(const unsigned int* __restrict__ prims, const float* __restrict__ aabbs,
+                                                          const unsigned int* __restrict__ idx, unsigned int k, unsigned int n, unsigned int epoch,
+                                                          unsigned int* __restrict__ claim, unsigned int* __restrict__ verdict)
+{
+    __shared__ unsigned int s_prim[256 * kPrimDwords];
+    __shared__ float s_box[256 * 6];
+    const unsigned int here = stage_entries(prims, aabbs, k, s_prim, s_box);
+    if (here == 0) return;
+    check_entries<false>(here, s_prim, s_box, aabbs != nullptr, idx, n, epoch, claim, verdict, ReachBox{});
+}
+
+// ---- the refit of rtgo_update_prims_device_async: the check, the update and the refit enqueued back to back, no verdict
+// read by the host in between.  The verdict is a slot of the context's ring (kVerdictWords words, filled with kNoFault ahead of the check);
+// the kernels that write the scene read it first and leave at once unless it is clean.  The kernel boundary after the check is what makes
+// the verdict complete and visible to them, large_fit_kernel's argument for one launch per level.
+
+// prims_check_kernel with the reach test, for the updates of a scene of rtgo_set_large_scene (idx is not nullable here)
+__global__ __launch_bounds__(256) void prims_check_reach_kernel(const unsigned int* __restrict__ prims, const float* __restrict__ aabbs,
+                                                                const unsigned int* __restrict__ idx, unsigned int k, unsigned int n,
+                                                                unsigned int epoch, unsigned int* __restrict__ claim,
+                                                                unsigned int* __restrict__ verdict, ReachBox reach)
+{
+    __shared__ unsigned int s_prim[256 * kPrimDwords];
+    __shared__ float s_box[256 * 6];
+    const unsigned int here = stage_entries(prims, aabbs, k, s_prim, s_box);
+    if (here == 0) return;
+    check_entries<true>(here, s_prim, s_box, aabbs != nullptr, idx, n, epoch, claim, verdict, reach);
+}
+
+// the gate: the same address in every lane, so eight scalar loads per wave
+__device__ __forceinline__ bool verdict_clean(const unsigned int* __restrict__ verdict)
+{
+    unsigned int all = kNoFault;
+    for (int q = 0; q < kVerdictWords; ++q) all &= verdict[q];
+    return all == kNoFault;
+}
+
+// large_update_kernel's refit for checked updates that lie in device memory, behind the gate.  large_update_kernel reads its 108-byte
+// records at a stride of 27 dwords (a wave's load touches 64 lines, 27 times); here the workgroup stages its 256 records and boxes in LDS
+// as the check does and each thread takes its record from there.  The record, the box, the leaf, the bitwise `moved` test and the mark
+// walk are large_update_kernel's, function for function: what the two write is equal bit for bit.  *changed: the ticket's word.
+__global__ __launch_bounds__(256) void large_update_staged_kernel(const unsigned int* __restrict__ verdict, const unsigned int* __restrict__ idx,
+                                                                  const unsigned int* __restrict__ upd, const float* __restrict__ upd_aabb,
+                                                                  unsigned int k, const int* __restrict__ leaf_of, const int* __restrict__ parent,
+                                                                  unsigned int epoch, unsigned int* __restrict__ mark,
+                                                                  float4* __restrict__ out_prims, float* __restrict__ aabb,
+                                                                  float4* __restrict__ nodes, unsigned int* __restrict__ changed)
+{
+    __shared__ unsigned int s_prim[256 * kPrimDwords];
+    __shared__ float s_box[256 * 6];
+    if (!verdict_clean(verdict)) return;
+    const unsigned int tid = threadIdx.x;
+    const unsigned int here = stage_entries(upd, upd_aabb, k, s_prim, s_box);
+    if (tid >= here) return;
+    const size_t i = idx[blockIdx.x * 256u + tid];
+    PrimIn P;
+    __builtin_memcpy(&P, s_prim + tid * kPrimDwords, sizeof P);
+    float inv[12];
+    inverse_rows012(P.M, inv);
+    store_prim_record(out_prims + 6 * i, P, inv);
+    float bb[6];
+    if (upd_aabb) {
+        for (int a = 0; a < 6; ++a) bb[a] = s_box[tid * 6 + a];
+    } else {
+        cube_aabb(P.M, bb);
+    }
+    bool moved = false;
+    for (int a = 0; a < 6; ++a) {
+        moved = moved || __float_as_uint(bb[a]) != __float_as_uint(aabb[6 * i + a]);
+        aabb[6 * i + a] = bb[a];
+    }
+    const int leaf = leaf_of[i];
+    nodes[2 * (size_t)leaf + 0] = make_float4(bb[0], bb[1], bb[2], __int_as_float((int)i));
+    nodes[2 * (size_t)leaf + 1] = make_float4(bb[3], bb[4], bb[5], __int_as_float(-1));
+    if (!moved) return;
+    *changed = 1u;
+    int q = parent[leaf];
+    for (int d = 0; q >= 0 && d <= kLargeMaxDepth; ++d) {   // (large_update_kernel's walk: whoever marks an ancestor first goes on to the root)
+        if (atomicExch(&mark[q], epoch) == epoch) break;
+        q = parent[q];
+    }
+}
+
+// large_refit_kernel behind the gate: the host cannot skip these launches (it no longer knows *changed), so each leaves at once for a
+// refused update and for one that moved no box -- the node array then stays bitwise as it was
+__global__ __launch_bounds__(256) void large_refit_gated_kernel(const unsigned int* __restrict__ verdict, const unsigned int* __restrict__ changed,
+                                                                const int* __restrict__ depth, const unsigned int* __restrict__ mark,
+                                                                unsigned int epoch, int n_internal, int level, float4* __restrict__ nodes)
+{
+    if (!verdict_clean(verdict) || *changed == 0u) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_internal || mark[i] != epoch || depth[i] != level) return;
+    refit_node(i, nodes);
 }
 
 }  // namespace rtgo

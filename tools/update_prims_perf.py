@@ -9,7 +9,11 @@ CubeBox rule on the device.
       set_device, refit_device, rebuild_device
                the same three through rtgo_set_large_scene_device and rtgo_update_prims_device, the records and indices in device memory
                beforehand (a second line per k, each with the least and the largest of its samples; `set` again with its spread)
-   All are WALL-CLOCK times of the synchronous C call on records packed beforehand (no Python packing inside), medians of REPS calls
+      refit_async
+               rtgo_update_prims_device_async over the same device buffers (a third line per k), its `reach` the field's box: `host`, the
+               wall clock of the C call over an idle stream (it only enqueues), and `device`, the HIP-event time on the stream from before the
+               call to after its last kernel; then host / refit_device and device against refit_device's median and least sample
+   All but `device` are WALL-CLOCK times of the C call on records packed beforehand (no Python packing inside), medians of REPS calls
    after WARM, host and device calls in the same run.
 2. Per n: a fraction of the spheres scattered to random places of the field by a refit, then the same scene rebuilt: ms per frame at W x H,
    path mode, 1 spp -- HIP-EVENT times (rtgo_stats' total_launch_ms over K launches).  The fractions grow tenfold and stop once a refitted
@@ -101,6 +105,48 @@ def c_update_device(L, ctx, d_idx, d_rec, k, flags):
     assert rc == 0, L.rtgo_last_error(ctx._h)
 
 
+class Timer:
+    """a stream of the process's HIP runtime for the context and two events on it"""
+
+    def __init__(self, ctx):
+        self.H, self.ctx, self.stream, self.ev = capi.hip_runtime(), ctx, C.c_void_p(), [C.c_void_p(), C.c_void_p()]
+        H = self.H
+        H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+        H.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+        H.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+        H.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+        for fn in (H.hipEventSynchronize, H.hipEventDestroy, H.hipStreamDestroy):
+            fn.argtypes = [C.c_void_p]
+        assert H.hipStreamCreate(C.byref(self.stream)) == 0 and all(H.hipEventCreate(C.byref(e)) == 0 for e in self.ev)
+        ctx.set_stream(self.stream.value)
+
+    def close(self):
+        self.ctx.set_stream(None)
+        for e in self.ev:
+            self.H.hipEventDestroy(e)
+        self.H.hipStreamDestroy(self.stream)
+
+
+def samples_async(L, ctx, timer, d_idx, d_edits, k, reach):
+    """per call of rtgo_update_prims_device_async over an idle stream: ([host ms], [device ms]), the warm-up calls left out"""
+    H, ticket, status, ms = timer.H, C.c_uint64(), capi.UpdateStatus(), C.c_float()
+    host, device = [], []
+    for j in range(WARM + REPS):
+        ctx.sync()
+        H.hipEventRecord(timer.ev[0], timer.stream)
+        t0 = time.perf_counter()
+        rc = L.rtgo_update_prims_device_async(ctx._h, d_idx.p, d_edits[j % 2].p, None, k, C.byref(reach), C.byref(ticket))
+        dt = (time.perf_counter() - t0) * 1e3
+        H.hipEventRecord(timer.ev[1], timer.stream)
+        assert rc == 0, L.rtgo_last_error(ctx._h)
+        assert H.hipEventSynchronize(timer.ev[1]) == 0 and H.hipEventElapsedTime(C.byref(ms), timer.ev[0], timer.ev[1]) == 0
+        assert L.rtgo_update_prims_status(ctx._h, ticket, C.byref(status)) == 0 and status.state == capi.UPDATE_APPLIED, (status.state, status.fault, status.entry)
+        if j >= WARM:
+            host.append(dt)
+            device.append(ms.value)
+    return host, device
+
+
 def frame_ms(ctx):
     for f in range(2):
         ctx.launch(capi.make_frame(W, H, 1, f, True))
@@ -125,6 +171,8 @@ for n in (1 << 10, 1 << 18, 1 << 20):
     ctx.set_lights(t["lights"])
     ctx.resize(W * H)
     depth = ctx.stats()["lbvh_depth"]
+    centre, r_max = rec["model"][:, [3, 7, 11]], 2.0 * rec["model"][:, 0].max() + 0.01   # (a sphere and its nudge by a radius; the CubeBox pad)
+    reach = capi.Aabb(*[float(x) for x in np.concatenate([centre.min(axis=0) - r_max, centre.max(axis=0) + r_max])])
     print("n = %d  LBVH depth %d  as built %.3f ms/frame" % (n, depth, frame_ms(ctx)), flush=True)
     for k in sorted({1, max(n // 100, 1), n}):
         idx = np.ascontiguousarray(np.linspace(0, n - 1, k).astype(np.uint32))
@@ -150,6 +198,14 @@ for n in (1 << 10, 1 << 18, 1 << 20):
         s_set_d = samples_ms(lambda j: c_set_device(L, ctx, d_whole[j % 2], n))
         print("                 set %s   set_device %s   refit_device %s   rebuild_device %s" %
               (spread(s_set), spread(s_set_d), spread(s_refit_d), spread(s_rebuild_d)), flush=True)
+        # the refit that waits for nothing, over the same buffers
+        c_set(L, ctx, rec)
+        timer = Timer(ctx)
+        s_host, s_dev = samples_async(L, ctx, timer, d_idx, d_edits, k, reach)
+        timer.close()
+        print("                 refit_async host %s   device %s   host / refit_device %.4f   device / refit_device median %.3f, least %.3f" %
+              (spread(s_host), spread(s_dev), float(np.median(s_host)) / float(np.median(s_refit_d)), float(np.median(s_dev)) / float(np.median(s_refit_d)),
+               float(np.median(s_dev)) / min(s_refit_d)), flush=True)
         del d_idx, d_edits, d_whole
     frac, last_k = 1e-4, 0
     while frac <= 0.011:
