@@ -1,7 +1,6 @@
 // rtgo_large.h -- the device-wide build of a scene of rtgo_set_large_scene (beyond build_kernel's one workgroup of kMaxPrims threads).
 // It builds the canonical LBVH of build_kernel / oracle_lbvh_build bit for bit, in global memory, with the same __device__ functions:
-//   large_prep_kernel     per primitive: the 6-float4 record (inverse_rows012, store_prim_record) and, without caller boxes, the CubeBox
-//                         box (cube_aabb)
+//   large_prep_kernel     per primitive: the 6-float4 record and, without caller boxes, the CubeBox box (prim_record_and_box, below)
 //   whitted::big_bounds_final_kernel over the boxes: the scene bounds (exact min / max)
 //   large_keys_kernel     the 30-bit Morton code of each box centre (morton_cell, morton3), key = code << 32 | index; then the four stable
 //                         radix passes of rtgo_whitted_big.h over the code's bytes: the (code, index) order
@@ -11,19 +10,22 @@
 //                         operand order.  The kernel boundary between two levels is what makes a child box written by another
 //                         workgroup (on another XCD's L2) visible to its parent's: no inter-workgroup hand-off inside a launch.
 // and the edit of such a scene in place (rtgo_update_prims), over what the build keeps on the device -- every node's
-// parent, the internal nodes' depths, each primitive's leaf node and a mark word per internal node:
-//   large_update_kernel   per update: the new record and box, with the functions large_prep_kernel calls; for a refit also the leaf node,
-//                         and a mark on every ancestor of a leaf whose box changed
-//   large_refit_kernel    large_fit_kernel over the marked nodes of one level (the links are read from the node itself): one launch
-//                         per level again, for the same reason
+// parent, the internal nodes' depths, each primitive's leaf node and a mark word per internal node.  What an edit does to one primitive
+// is written once, in __device__ functions every kernel below calls:
+//   prim_record_and_box   the 6-float4 record (inverse_rows012, store_prim_record) and the box: the caller's, or the CubeBox rule's (cube_aabb)
+//   write_box_and_leaf    the box into the scene's array and into the primitive's leaf node; whether it changed bitwise (`moved`)
+//   mark_ancestors        the walk from a moved leaf to the root, every node on it stamped with the refit's epoch
+//   refit_marked_node     large_fit_kernel's box (fit_node) for a marked node of one level, the links read from the node itself
+//   large_update_kernel   per update, the record read from global memory: the first three; a rebuild also keeps what it overwrites
+//   large_refit_kernel    refit_marked_node: one launch per level again, for large_fit_kernel's reason
 //   large_restore_kernel  puts back the records and boxes large_update_kernel saved (a rebuild that is refused)
 //   prims_patch_kernel    a scene of rtgo_set_scene: the updates scattered into build_kernel's inputs
 // and the checks of the calls that take records, boxes and indices from device memory:
 //   prims_check_kernel    per entry: the host's check_prims rules and the index rules of rtgo_update_prims, into a verdict of a few words
 // and the refit that waits for nothing on the host (rtgo_update_prims_device_async):
 //   prims_check_reach_kernel    prims_check_kernel plus the test of each entry's box against the caller's `reach`
-//   large_update_staged_kernel  large_update_kernel's refit behind the verdict's gate, its records staged in LDS
-//   large_refit_gated_kernel    large_refit_kernel behind the gate and the ticket's `changed` word
+//   large_update_staged_kernel  the three functions behind the verdict's gate, the record taken from the workgroup's staged copy in LDS
+//   large_refit_gated_kernel    refit_marked_node behind the gate and the ticket's `changed` word
 #pragma once
 
 #include "rtgo_device.h"
@@ -33,20 +35,30 @@ namespace rtgo {
 
 constexpr int kLargeMaxDepth = 64;   // per-lane LDS stack entries of the global-memory walk: deeper trees are refused
 
+// Primitive P's 6-float4 record into out_prims at i, and its box: bb = entry e of the caller's boxes `given` (global memory or LDS), or,
+// given == nullptr, the CubeBox rule's.  The build, the synchronous and the asynchronous edit write the same bits because all call this.
+__device__ __forceinline__ void prim_record_and_box(const PrimIn& P, const float* given, size_t e, float4* out_prims, size_t i, float bb[6])
+{
+    float inv[12];
+    inverse_rows012(P.M, inv);
+    store_prim_record(out_prims + 6 * i, P, inv);
+    if (given) {
+        for (int a = 0; a < 6; ++a) bb[a] = given[6 * e + a];
+    } else {
+        cube_aabb(P.M, bb);
+    }
+}
+
 __global__ __launch_bounds__(256) void large_prep_kernel(const PrimIn* __restrict__ prims, float* __restrict__ aabb_io, int have_aabb, int n,
                                                          float4* __restrict__ out_prims)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const PrimIn P = prims[i];
-    float inv[12];
-    inverse_rows012(P.M, inv);
-    store_prim_record(out_prims + 6 * (size_t)i, P, inv);
-    if (!have_aabb) {
-        float bb[6];
-        cube_aabb(P.M, bb);
+    float bb[6];   // (the caller's boxes are in place already: only the rule's box is of use here)
+    prim_record_and_box(P, nullptr, 0, out_prims, i, bb);
+    if (!have_aabb)
         for (int a = 0; a < 6; ++a) aabb_io[6 * (size_t)i + a] = bb[a];
-    }
 }
 
 __global__ __launch_bounds__(256) void large_keys_kernel(const float* __restrict__ aabb, int n, const float* __restrict__ bounds,
@@ -105,23 +117,50 @@ __global__ __launch_bounds__(256) void large_depth_kernel(const unsigned long lo
     if (threadIdx.x == 0) atomicMax(max_depth, s_max);
 }
 
+// internal node i over its children L and R: the box of their boxes, and the links
+__device__ __forceinline__ void fit_node(int i, int L, int R, float4* __restrict__ nodes)
+{
+    const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
+    nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
+    nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+}
+
 // the internal nodes at depth `level`: their children (deeper) were written by earlier launches
 __global__ __launch_bounds__(256) void large_fit_kernel(const int* __restrict__ left, const int* __restrict__ right, const int* __restrict__ depth,
                                                         int n_internal, int level, float4* __restrict__ nodes)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_internal || depth[i] != level) return;
-    const int L = left[i], R = right[i];
-    const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
-    nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
-    nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+    fit_node(i, left[i], right[i], nodes);
 }
 
-// Update j: primitive idx[j] becomes upd[j], its box upd_aabb[j] (or, upd_aabb == nullptr, the CubeBox rule's).  The record and the box are
-// large_prep_kernel's bit for bit.  old_prims / old_aabb (nullable): what they replace, kept at j.  nodes (nullable: a rebuild writes its
-// leaves itself): the primitive's leaf is rewritten, and where the box changed bitwise *changed is set and every ancestor of the leaf is
-// marked with `epoch`.  A thread that finds an ancestor marked stops: whoever marked it first goes on to the root.  The indices are
-// distinct and below n (the host checked): no two threads write the same record.
+// Primitive i's box becomes bb: into the scene's array and into its leaf node, `leaf`.  Returns `moved`: the box changed bitwise, so the
+// leaf's ancestors have to be fitted again.
+__device__ __forceinline__ bool write_box_and_leaf(const float bb[6], size_t i, float* __restrict__ aabb, const int* __restrict__ leaf_of, float4* __restrict__ nodes, int& leaf)
+{
+    bool moved = false;
+    for (int a = 0; a < 6; ++a) {
+        moved = moved || __float_as_uint(bb[a]) != __float_as_uint(aabb[6 * i + a]);
+        aabb[6 * i + a] = bb[a];
+    }
+    leaf = leaf_of[i];
+    nodes[2 * (size_t)leaf + 0] = make_float4(bb[0], bb[1], bb[2], __int_as_float((int)i));
+    nodes[2 * (size_t)leaf + 1] = make_float4(bb[3], bb[4], bb[5], __int_as_float(-1));
+    return moved;
+}
+
+// Every ancestor of `leaf` is marked with `epoch`; a thread that finds one marked stops: whoever marked it first goes on to the root
+__device__ __forceinline__ void mark_ancestors(int leaf, const int* parent, unsigned int epoch, unsigned int* mark)
+{
+    int q = parent[leaf];
+    for (int d = 0; q >= 0 && d <= kLargeMaxDepth; ++d) {   // (a chain is at most kLargeMaxDepth long: the build refused deeper trees)
+        if (atomicExch(&mark[q], epoch) == epoch) break;
+        q = parent[q];
+    }
+}
+
+// Update j: primitive idx[j] becomes upd[j], its box upd_aabb[j] (nullable).  old_prims / old_aabb (nullable): what they replace, kept
+// at j.  nodes (nullable): a rebuild, which stops after the box.  Where a box moved *changed is set.  The indices are distinct and below n (the host checked): no two threads write the same record.
 __global__ __launch_bounds__(256) void large_update_kernel(const unsigned int* __restrict__ idx, const PrimIn* __restrict__ upd,
                                                            const float* __restrict__ upd_aabb, int k, const int* __restrict__ leaf_of,
                                                            const int* __restrict__ parent, unsigned int epoch, unsigned int* __restrict__ mark,
@@ -136,49 +175,30 @@ __global__ __launch_bounds__(256) void large_update_kernel(const unsigned int* _
         for (int q = 0; q < 6; ++q) old_prims[6 * (size_t)j + q] = out_prims[6 * i + q];
         for (int a = 0; a < 6; ++a) old_aabb[6 * (size_t)j + a] = aabb[6 * i + a];
     }
-    float inv[12];
-    inverse_rows012(P.M, inv);
-    store_prim_record(out_prims + 6 * i, P, inv);
     float bb[6];
-    if (upd_aabb) {
-        for (int a = 0; a < 6; ++a) bb[a] = upd_aabb[6 * (size_t)j + a];
-    } else {
-        cube_aabb(P.M, bb);
+    prim_record_and_box(P, upd_aabb, j, out_prims, i, bb);
+    if (!nodes) {   // (a rebuild writes its leaves itself, from the boxes)
+        for (int a = 0; a < 6; ++a) aabb[6 * i + a] = bb[a];
+        return;
     }
-    bool moved = false;
-    for (int a = 0; a < 6; ++a) {
-        moved = moved || __float_as_uint(bb[a]) != __float_as_uint(aabb[6 * i + a]);
-        aabb[6 * i + a] = bb[a];
-    }
-    if (!nodes) return;
-    const int leaf = leaf_of[i];
-    nodes[2 * (size_t)leaf + 0] = make_float4(bb[0], bb[1], bb[2], __int_as_float((int)i));
-    nodes[2 * (size_t)leaf + 1] = make_float4(bb[3], bb[4], bb[5], __int_as_float(-1));
-    if (!moved) return;
+    int leaf;
+    if (!write_box_and_leaf(bb, i, aabb, leaf_of, nodes, leaf)) return;
     *changed = 1;
-    int q = parent[leaf];
-    for (int d = 0; q >= 0 && d <= kLargeMaxDepth; ++d) {   // (a chain is at most kLargeMaxDepth long: the build refused deeper trees)
-        if (atomicExch(&mark[q], epoch) == epoch) break;
-        q = parent[q];
-    }
+    mark_ancestors(leaf, parent, epoch, mark);
 }
 
-// internal node i: large_fit_kernel's box, the links read from the node itself
-__device__ __forceinline__ void refit_node(int i, float4* __restrict__ nodes)
+// node i, if it is a marked internal node at depth `level`: fit_node again, the links read from the node itself, over children an earlier launch wrote
+__device__ __forceinline__ void refit_marked_node(int i, const int* __restrict__ depth, const unsigned int* __restrict__ mark, unsigned int epoch, int n_internal, int level,
+                                                  float4* __restrict__ nodes)
 {
-    const int L = __float_as_int(nodes[2 * (size_t)i].w), R = __float_as_int(nodes[2 * (size_t)i + 1].w);
-    const float4 l0 = nodes[2 * (size_t)L], l1 = nodes[2 * (size_t)L + 1], r0 = nodes[2 * (size_t)R], r1 = nodes[2 * (size_t)R + 1];
-    nodes[2 * (size_t)i + 0] = make_float4(fminf(l0.x, r0.x), fminf(l0.y, r0.y), fminf(l0.z, r0.z), __int_as_float(L));
-    nodes[2 * (size_t)i + 1] = make_float4(fmaxf(l1.x, r1.x), fmaxf(l1.y, r1.y), fmaxf(l1.z, r1.z), __int_as_float(R));
+    if (i >= n_internal || mark[i] != epoch || depth[i] != level) return;
+    fit_node(i, __float_as_int(nodes[2 * (size_t)i].w), __float_as_int(nodes[2 * (size_t)i + 1].w), nodes);
 }
 
-// the marked internal nodes at depth `level`: large_fit_kernel's box, from children an earlier launch (or large_update_kernel) wrote
 __global__ __launch_bounds__(256) void large_refit_kernel(const int* __restrict__ depth, const unsigned int* __restrict__ mark, unsigned int epoch,
                                                           int n_internal, int level, float4* __restrict__ nodes)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_internal || mark[i] != epoch || depth[i] != level) return;
-    refit_node(i, nodes);
+    refit_marked_node(blockIdx.x * 256 + threadIdx.x, depth, mark, epoch, n_internal, level, nodes);
 }
 
 __global__ __launch_bounds__(256) void large_restore_kernel(const unsigned int* __restrict__ idx, const float4* __restrict__ old_prims,
@@ -336,8 +356,8 @@ __device__ __forceinline__ bool verdict_clean(const unsigned int* __restrict__ v
 
 // large_update_kernel's refit for checked updates that lie in device memory, behind the gate.  large_update_kernel reads its 108-byte
 // records at a stride of 27 dwords (a wave's load touches 64 lines, 27 times); here the workgroup stages its 256 records and boxes in LDS
-// as the check does and each thread takes its record from there.  The record, the box, the leaf, the bitwise `moved` test and the mark
-// walk are large_update_kernel's, function for function: what the two write is equal bit for bit.  *changed: the ticket's word.
+// as the check does and each thread takes its record from there.  From there on the two call the same functions: what they write is
+// equal bit for bit.  *changed: the ticket's word.
 __global__ __launch_bounds__(256) void large_update_staged_kernel(const unsigned int* __restrict__ verdict, const unsigned int* __restrict__ idx,
                                                                   const unsigned int* __restrict__ upd, const float* __restrict__ upd_aabb,
                                                                   unsigned int k, const int* __restrict__ leaf_of, const int* __restrict__ parent,
@@ -354,30 +374,12 @@ __global__ __launch_bounds__(256) void large_update_staged_kernel(const unsigned
     const size_t i = idx[blockIdx.x * 256u + tid];
     PrimIn P;
     __builtin_memcpy(&P, s_prim + tid * kPrimDwords, sizeof P);
-    float inv[12];
-    inverse_rows012(P.M, inv);
-    store_prim_record(out_prims + 6 * i, P, inv);
     float bb[6];
-    if (upd_aabb) {
-        for (int a = 0; a < 6; ++a) bb[a] = s_box[tid * 6 + a];
-    } else {
-        cube_aabb(P.M, bb);
-    }
-    bool moved = false;
-    for (int a = 0; a < 6; ++a) {
-        moved = moved || __float_as_uint(bb[a]) != __float_as_uint(aabb[6 * i + a]);
-        aabb[6 * i + a] = bb[a];
-    }
-    const int leaf = leaf_of[i];
-    nodes[2 * (size_t)leaf + 0] = make_float4(bb[0], bb[1], bb[2], __int_as_float((int)i));
-    nodes[2 * (size_t)leaf + 1] = make_float4(bb[3], bb[4], bb[5], __int_as_float(-1));
-    if (!moved) return;
+    prim_record_and_box(P, upd_aabb ? s_box : nullptr, tid, out_prims, i, bb);
+    int leaf;
+    if (!write_box_and_leaf(bb, i, aabb, leaf_of, nodes, leaf)) return;
     *changed = 1u;
-    int q = parent[leaf];
-    for (int d = 0; q >= 0 && d <= kLargeMaxDepth; ++d) {   // (large_update_kernel's walk: whoever marks an ancestor first goes on to the root)
-        if (atomicExch(&mark[q], epoch) == epoch) break;
-        q = parent[q];
-    }
+    mark_ancestors(leaf, parent, epoch, mark);
 }
 
 // large_refit_kernel behind the gate: the host cannot skip these launches (it no longer knows *changed), so each leaves at once for a
@@ -387,9 +389,7 @@ __global__ __launch_bounds__(256) void large_refit_gated_kernel(const unsigned i
                                                                 unsigned int epoch, int n_internal, int level, float4* __restrict__ nodes)
 {
     if (!verdict_clean(verdict) || *changed == 0u) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_internal || mark[i] != epoch || depth[i] != level) return;
-    refit_node(i, nodes);
+    refit_marked_node(blockIdx.x * 256 + threadIdx.x, depth, mark, epoch, n_internal, level, nodes);
 }
 
 }  // namespace rtgo
