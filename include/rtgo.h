@@ -574,6 +574,42 @@ int rtgo_whitted_update_meshes_device(rtgo_ctx* ctx, const rtgo_whitted_mesh_upd
    refusal is known before anything of the scene is written; a refused call leaves the scene as it was.  Synchronous. */
 int rtgo_whitted_set_instances_device(rtgo_ctx* ctx, const void* d_instances, uint32_t n_instances, uint32_t flags);
 
+/* rtgo_whitted_set_instances_device with RTGO_UPDATE_REFIT, enqueued on the context's stream: it waits for nothing on the host -- not for
+   the stream, a verdict, the instances' read-back or the refit's grid words -- so a loop of "step the bodies, refit the top level,
+   rtgo_whitted_launch" on one stream never drains the GPU ("The refit that waits for nothing").  d_instances: the twin's
+   contract -- rtgo_whitted_instance[n_instances], DEVICE memory of the context's device, caller-owned, 4-byte aligned, overlapping
+   nothing of the context, read and never written; the caller's writes to it complete, or ordered on the context's stream
+   (rtgo_set_stream), before the call -- and one rule more: it must stay as it is until the update has run (rtgo_sync, or anything later
+   on the stream).
+   Decided on the host, at once; each returns its code, enqueues nothing and issues no ticket (*ticket is not written) --
+   RTGO_E_INVALID: NULL ctx, d_instances or ticket, a pointer that is not 4-byte aligned, another count than the scene's;
+   RTGO_E_STATE: no instanced scene (a scene of rtgo_whitted_set_mesh does not count); RTGO_E_UNSUPPORTED: n_instances == 0 or beyond
+   RTGO_WHITTED_MAX_INSTANCES.
+   Every other call returns RTGO_OK and a ticket, and the five faults the twin finds on the device are decided there later and reported
+   by rtgo_whitted_refit_instances_status.  An update with a fault changes NOTHING of the scene -- no top-level record, no per-instance
+   record, nothing of what the context keeps of the instances; the kernels that write the scene read the check's verdict on the device
+   first.  Updates enqueued after it are judged by their own verdicts alone.  An update without a fault leaves, array for array, what
+   the synchronous refit leaves after the same instances on the same scene: frames, rtgo_whitted_trace_rays, rtgo_whitted_shade_rays and
+   the ray counters are equal bit for bit, and launches and ray queries enqueued after the call see the refitted top level.  Every
+   synchronous call works afterwards as after the twin; the first that needs the instances on the host (a mesh update, a rebuild) waits
+   for the stream -- as it does anyway -- and reads them back then.
+   Allocations: a context's first call allocates its ring of 64 tickets (device words, their pinned copy, events), a scene's first call
+   the staging the scene keeps until its top level or the scene is replaced (288 bytes per instance, 4 per top-level record, and 12 KB each for the mesh table and its pinned image);
+   no other call allocates or frees anything. */
+int rtgo_whitted_refit_instances_device_async(rtgo_ctx* ctx, const void* d_instances, uint32_t n_instances, uint64_t* ticket);
+
+/* The state of a ticket of rtgo_whitted_refit_instances_device_async, in rtgo_update_status as it stands.  Never blocks: one event query.
+   PENDING: the check has not finished.  APPLIED: it found no fault, and the update is done or ordered on the stream ahead of everything
+   enqueued after its call.  REFUSED: the scene is as it was; fault is 1 a mesh index beyond the meshes, 2 an instance names another mesh
+   than it names in the scene, 3 material offset + the mesh's largest material index beyond the table, 4 a non-finite or singular
+   transform, 5 a box beyond the float range; entry is the instance rtgo_whitted_set_instances_device's message would name (the lowest
+   offending one, of the lowest-numbered kind that names it).  The context keeps its last 64 tickets: an older one, one never issued and
+   ticket 0 (never issued) are RTGO_E_INVALID, as are a NULL ctx or out; a 65th update enqueued while 64 are in flight waits once for
+   the oldest ticket's check.  After rtgo_sync every ticket the context keeps is APPLIED or REFUSED.
+   These tickets and rtgo_update_prims_device_async's come from two rings that count separately: a ticket of one call is RTGO_E_INVALID
+   to the other call's status function unless that ring happens to hold the same number, which then names another update. */
+int rtgo_whitted_refit_instances_status(rtgo_ctx* ctx, uint64_t ticket, rtgo_update_status* out);
+
 /* rtgo_whitted_set_scene for meshes that are already on the device (under OptiX the vertex and index buffers of a build input are
    device pointers): a marching-cubes or simulation step's output, a PyTorch-ROCm tensor.  `meshes`, `instances` and `materials` are
    host arrays, as in the twin (they are small, and the context keeps a host copy of the instances anyway; a caller whose instances

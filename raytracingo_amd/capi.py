@@ -31,6 +31,7 @@ SYMBOLS = [
     "rtgo_set_scene_device", "rtgo_set_large_scene_device", "rtgo_update_prims_device", "rtgo_whitted_set_instances_device",
     "rtgo_whitted_set_scene_device", "rtgo_whitted_set_mesh_device", "rtgo_whitted_set_texcoords_device",
     "rtgo_update_prims_device_async", "rtgo_update_prims_status",
+    "rtgo_whitted_refit_instances_device_async", "rtgo_whitted_refit_instances_status",
 ]
 UPDATE_PENDING, UPDATE_APPLIED, UPDATE_REFUSED = 0, 1, 2
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
@@ -199,6 +200,8 @@ def load():
     L.rtgo_whitted_rebuild_meshes.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32]
     L.rtgo_whitted_update_meshes_device.argtypes = [vp, C.POINTER(WhittedMeshUpdate), C.c_uint32, C.c_uint32]
     L.rtgo_whitted_set_instances_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.rtgo_whitted_refit_instances_device_async.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.rtgo_whitted_refit_instances_status.argtypes = [vp, C.c_uint64, C.POINTER(UpdateStatus)]
     L.rtgo_whitted_set_scene_device.argtypes = [vp, C.POINTER(WhittedMesh), C.c_uint32, C.POINTER(WhittedInstance), C.c_uint32, vp, C.c_uint32]
     L.rtgo_whitted_set_mesh_device.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32]
     L.rtgo_whitted_set_texcoords_device.argtypes = [vp, vp, C.c_uint32]
@@ -536,6 +539,24 @@ class Context:
         n, ptr = device_instances_args("whitted_set_instances_device", self.device, instances)
         self._check(self._lib.rtgo_whitted_set_instances_device(self._h, C.c_void_p(ptr), n, UPDATE_REFIT if refit else UPDATE_REBUILD),
                     "rtgo_whitted_set_instances_device")
+
+    def whitted_refit_instances_device_async(self, instances):
+        """rtgo_whitted_refit_instances_device_async: whitted_set_instances_device's refit (refit=True: the same tensor, count and mesh
+        choices), enqueued on the context's stream with no wait on the host -- none here either: the tensor's writes must be complete
+        or ordered on that stream, and it must stay as it is until the update has run.  Returns the ticket
+        whitted_refit_instances_status takes."""
+        n, ptr = device_instances_args("whitted_refit_instances_device_async", self.device, instances)
+        ticket = C.c_uint64(0)
+        self._check(self._lib.rtgo_whitted_refit_instances_device_async(self._h, C.c_void_p(ptr), n, C.byref(ticket)),
+                    "rtgo_whitted_refit_instances_device_async")
+        return ticket.value
+
+    def whitted_refit_instances_status(self, ticket):
+        """rtgo_whitted_refit_instances_status: {"state": UPDATE_PENDING / UPDATE_APPLIED / UPDATE_REFUSED, "fault": 0 or the kind 1 .. 5,
+        "entry": the offending instance of a refused update}; never blocks"""
+        st = UpdateStatus()
+        self._check(self._lib.rtgo_whitted_refit_instances_status(self._h, int(ticket), C.byref(st)), "rtgo_whitted_refit_instances_status")
+        return {"state": st.state, "fault": st.fault, "entry": st.entry}
 
     def whitted_set_scene_device(self, meshes, instances, materials):
         """rtgo_whitted_set_scene_device: whitted_set_scene's arguments with contiguous torch tensors on the context's device in place

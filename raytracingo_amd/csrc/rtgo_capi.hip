@@ -249,8 +249,12 @@ struct BuildSpan {
 //     of each build}; then the top level's recs and inst, then clusters.  Then, in the clear: per mesh its info {rec_base, tri_base,
 //     vert_base, root, depth, clustered, n_tris, builds, then per build rec0, n_recs, tri0 and WhittedBuildMeta's words}, and top.meta
 //     (WhittedBuildMeta's words of the top level, then {n_recs, n_instances, the scene's walk_depth, mesh_depth}).
+static int whitted_refresh_host(rtgo_ctx* c);   // (rtgo_whitted_host.h: top.meta's grid may wait on the device for its first reader)
+
 static int build_spans(rtgo_ctx* c, int whitted, std::vector<BuildSpan>& out)
 {
+    if (whitted)
+        if (const int rc = whitted_refresh_host(c)) return rc;
     auto span = [&](const std::string& name) -> BuildSpan& {
         out.push_back(BuildSpan{name, {}});
         return out.back();
@@ -526,6 +530,8 @@ int rtgo_destroy(rtgo_ctx* c)
     if (!c) return RTGO_OK;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
+    // (a caller's stream may still carry a refit of rtgo_whitted_refit_instances_device_async, which writes what `delete c` frees)
+    if (c->stream && c->stream != c->own_stream && c->wm.staging.stale) (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < rtgo_ctx::kEvRing; ++i) {
         if (c->ev_start[i]) (void)hipEventDestroy(c->ev_start[i]);
         if (c->ev_stop[i]) (void)hipEventDestroy(c->ev_stop[i]);
@@ -1505,12 +1511,40 @@ int rtgo_whitted_set_instances_device(rtgo_ctx* c, const void* d_instances, uint
     const std::string w = "rtgo_whitted_set_instances_device";
     if (!c) return RTGO_E_INVALID;
     if (flags & ~(uint32_t)RTGO_UPDATE_REBUILD) return fail(c, RTGO_E_INVALID, w + ": unknown flag bits");
-    if (!d_instances) return fail(c, RTGO_E_INVALID, w + ": NULL instance array");
-    if (!aligned4(d_instances)) return fail(c, RTGO_E_INVALID, w + ": the instance array is not 4-byte aligned");
-    if (!c->wm.instanced) return fail(c, RTGO_E_STATE, w + ": no instanced scene (call rtgo_whitted_set_scene first)");
-    if (n_instances == 0 || n_instances > RTGO_WHITTED_MAX_INSTANCES)
-        return fail(c, RTGO_E_UNSUPPORTED, w + ": instance count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_INSTANCES) + "]");
-    return whitted_set_instances_device(c, d_instances, n_instances, (flags & RTGO_UPDATE_REBUILD) != 0);
+    const bool rebuild = (flags & RTGO_UPDATE_REBUILD) != 0;
+    if (const int rc = whitted_check_instances_args(c, w, d_instances, n_instances, !rebuild)) return rc;
+    return whitted_set_instances_device(c, d_instances, n_instances, rebuild);
+}
+
+int rtgo_whitted_refit_instances_device_async(rtgo_ctx* c, const void* d_instances, uint32_t n_instances, uint64_t* ticket)
+{
+    const std::string w = "rtgo_whitted_refit_instances_device_async";
+    if (!c) return RTGO_E_INVALID;
+    if (!ticket) return fail(c, RTGO_E_INVALID, w + ": NULL ticket");
+    if (const int rc = whitted_check_instances_args(c, w, d_instances, n_instances, true)) return rc;
+    return whitted_refit_instances_async(c, d_instances, n_instances, ticket);
+}
+
+int rtgo_whitted_refit_instances_status(rtgo_ctx* c, uint64_t ticket, rtgo_update_status* out)
+{
+    const std::string w = "rtgo_whitted_refit_instances_status";
+    if (!c || !out) return fail(c, RTGO_E_INVALID, w + ": NULL argument");
+    *out = rtgo_update_status{RTGO_UPDATE_APPLIED, 0, 0, 0};
+    const rtgo_ctx::UpdateRing& ring = c->w_updates;
+    if (!ring.holds(ticket)) return fail(c, RTGO_E_INVALID, w + ": ticket " + std::to_string(ticket) + " was never issued or has left the ring of the last 64");
+    const unsigned int slot = rtgo_ctx::UpdateRing::slot(ticket);
+    RTGO_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = hipEventQuery(ring.done[slot].get());
+    if (e == hipErrorNotReady) {
+        (void)hipGetLastError();   // (not an error: the next call's hipGetLastError must not find it)
+        out->state = RTGO_UPDATE_PENDING;
+        return RTGO_OK;
+    }
+    RTGO_HIP(c, e);
+    const unsigned int* v = ring.h.get() + (size_t)slot * kVerdictWords;
+    const int kind = lowest_fault(v, whitted::kInstVerdictKinds);   // (rtgo_whitted_set_instances_device's choice for its message)
+    if (kind >= 0) *out = rtgo_update_status{RTGO_UPDATE_REFUSED, (uint32_t)kind + 1u, v[kind], 0};
+    return RTGO_OK;
 }
 
 int rtgo_whitted_set_texcoords(rtgo_ctx* c, const float* uv, uint32_t n_vertices)

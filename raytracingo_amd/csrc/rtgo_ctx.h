@@ -117,6 +117,30 @@ struct WhittedTop {
     whitted::WhittedBuildMeta meta = {};       // what its build reported (rtgo_debug_read_build)
 };
 
+// What rtgo_whitted_refit_instances_device_async keeps with an instanced scene ("The refit that waits for nothing"):
+// allocated by the scene's first such call, reused by every later one (they are ordered on one stream), dropped with the top level or
+// the scene.  n: the scene's instances.
+struct WhittedInstStaging {
+    DeviceArray<whitted::InstShade> shade;     // inst_prepare_kernel's records [n], copied into top.shade behind the gate
+    DeviceArray<float> boxes;                  // ... its boxes [6 n]
+    DeviceArray<unsigned int> idx;             // ... and index triples [3 n]
+    DeviceArray<float4> tris;                  // the leaf order refit_structure reads, and the corners it writes [3 n]
+    DeviceArray<uint4> qrecs;                  // the refit's compact records [2 n] (no launch reads a top level's)
+    DeviceArray<int> done;                     // the refit's stamps [n_recs]
+    // kMetaWords words for the refit's WhittedBuildMeta, then the count of applied updates; read back by whitted_refresh_host
+    static constexpr int kMetaWords = 12, kWords = 16;
+    DeviceArray<unsigned int> words;
+    DeviceArray<unsigned int> kept;            // the instances of the last applied update [14 n]: wm.instances, not yet read back
+    // the mesh table inst_prepare_kernel reads (InstMesh, 12 words per mesh) and its pinned image: uploaded when the image differs from
+    // wm.meshes, which change only in calls that have drained the stream
+    DeviceArray<unsigned int> table;
+    PinnedArray<unsigned int> h_table;
+    size_t table_words = 0;                    // words uploaded (0: nothing yet)
+    // wm.instances and wm.top.meta's grid are behind the device by the updates applied since `adopted`, the count at the last refresh
+    unsigned int adopted = 0;
+    bool stale = false;                        // an update was enqueued since the last refresh
+};
+
 // The whitted triangle path's scene (rtgo_whitted.h; rtgo_whitted_set_mesh, rtgo_whitted_set_scene): replaced as a whole
 struct WhittedMesh {
     DeviceArray<float> positions, normals;
@@ -139,6 +163,7 @@ struct WhittedMesh {
     std::vector<WhittedMeshInfo> meshes;
     int mesh_depth = 0;                        // the deepest mesh walk
     WhittedTop top;
+    WhittedInstStaging staging;                // (while staging.stale, `instances` and top.meta's grid wait for whitted_refresh_host)
     std::vector<rtgo_whitted_instance> instances;   // the caller's instances as last given (rtgo_whitted_update_mesh lays them out again)
     DeviceArray<int4> clusters;                // the clustered meshes' cluster tables (InstParams::clusters), or empty when there are none
 };
@@ -168,6 +193,9 @@ struct rtgo_ctx {
         PinnedArray<unsigned int> h;       // the verdicts as copied back behind each check
         LazyEvent done[kSlots];            // recorded behind that copy: what rtgo_update_prims_status queries
     } updates;
+    // rtgo_whitted_refit_instances_device_async: a ring of its own, of the same shape (d: kSlots verdicts alone).  The two rings count
+    // their tickets separately: a number means one update here and another there.
+    UpdateRing w_updates;
     int leaf_budget = kDefaultLeafBudget;
     bool have_camera = false;
     v3 eye{0, 0, 0}, U{0, 0, 0}, V{0, 0, 0}, W{0, 0, 0}, bg{0, 0, 0};

@@ -263,9 +263,41 @@ static int whitted_make_top(rtgo_ctx* c, const WhittedMesh& wm, const std::vecto
     return whitted_make_top_over(c, wm.meshes, wm.mesh_depth, shade, box_pos, inst, what, top, depth);
 }
 
-// ... and that top level in wm's place
+// What rtgo_whitted_refit_instances_device_async leaves for later: wm.instances and wm.top.meta's grid as the device holds them.  Every
+// synchronous reader or writer of either calls this first.  It waits for the stream, then adopts what the applied updates since the last
+// refresh wrote: if their count has not moved, every update in between was refused, the host's fields are current as they stand, and the
+// kept instances and the meta block (which nothing may have filled yet) are not read.
+static int whitted_refresh_host(rtgo_ctx* c)
+{
+    WhittedMesh& wm = c->wm;
+    WhittedInstStaging& st = wm.staging;
+    if (!st.stale) return RTGO_OK;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned int w[WhittedInstStaging::kWords];
+    RTGO_HIP(c, hipMemcpyAsync(w, st.words.get(), sizeof w, hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    st.stale = false;
+    const unsigned int applied = w[WhittedInstStaging::kMetaWords];
+    if (applied == st.adopted) return RTGO_OK;
+    std::vector<rtgo_whitted_instance> instances((size_t)wm.top.n_instances);
+    RTGO_HIP(c, hipMemcpyAsync(instances.data(), st.kept.get(), instances.size() * sizeof(rtgo_whitted_instance), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    wm.instances = std::move(instances);
+    if (wm.top.n_recs > 0) {   // (a top level of one leaf has no refit: its grid stays, as under the synchronous call)
+        whitted::WhittedBuildMeta m;
+        std::memcpy(&m, w, sizeof m);
+        wm.top.meta.grid_lo = m.grid_lo;
+        wm.top.meta.grid_step = m.grid_step;
+    }
+    st.adopted = applied;
+    return RTGO_OK;
+}
+
+// ... and that top level in wm's place (the refit staging went with the old one's size; the stream has drained)
 static void whitted_install_top(WhittedMesh& wm, WhittedTop&& top, int depth)
 {
+    wm.staging = WhittedInstStaging();
     wm.top = std::move(top);
     wm.walk_depth = depth < 1 ? 1 : depth;
 }
@@ -952,6 +984,7 @@ static int whitted_update_mesh(rtgo_ctx* c, uint32_t mesh, const float* position
         if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) return fail(c, RTGO_E_INVALID, w + ": non-finite vertex data");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = whitted_refresh_host(c)) return rc;
     if (!wm.instanced) {
         if (const int rc = whitted_refit(c, wm, m, positions, normals)) return rc;
         wm.meta = m.meta;
@@ -1246,6 +1279,7 @@ static int whitted_refit_named(rtgo_ctx* c, const char* what, const rtgo_whitted
         wm.meta = one[0].meta;
         return RTGO_OK;
     }
+    if (const int rc = whitted_refresh_host(c)) return rc;
     // stage 2
     std::vector<WhittedMeshInfo> meshes = wm.meshes;
     std::vector<std::vector<uint32_t>> idx(n_updates);
@@ -1339,6 +1373,7 @@ struct WhittedRebuildSave {
 static int whitted_rebuild_named(rtgo_ctx* c, const char* what, const rtgo_whitted_mesh_update* updates, uint32_t n_updates, const WhittedUpdateSource& src)
 {
     WhittedMesh& wm = c->wm;
+    if (const int rc = whitted_refresh_host(c)) return rc;
     std::vector<WhittedMeshInfo> meshes = wm.meshes;
     if (!wm.instanced) {   // a scene of rtgo_whitted_set_mesh: its one mesh, at the start of every array
         WhittedMeshInfo mi = WhittedMeshInfo();
@@ -1470,21 +1505,40 @@ static int whitted_update_meshes_device(rtgo_ctx* c, const rtgo_whitted_mesh_upd
 // records as the mid-level refit launches it (refit: topology, leaf order and depth stay, so nothing needs saving), then
 // inst_gather_kernel for the InstWalk records.  The instances themselves are read back beside the verdict (56 B each): the mesh-update
 // calls lay the instances out again from wm.instances.  Nothing else in proportion to n crosses the host.
+// What the host decides of the arguments of rtgo_whitted_set_instances_device and rtgo_whitted_refit_instances_device_async (`w`: the
+// entry point; c is not NULL), in their order of precedence.  refit: RTGO_UPDATE_REFIT, which keeps the scene's count.
+static int whitted_check_instances_args(rtgo_ctx* c, const std::string& w, const void* d_instances, uint32_t n, bool refit)
+{
+    if (!d_instances) return fail(c, RTGO_E_INVALID, w + ": NULL instance array");
+    if (!aligned4(d_instances)) return fail(c, RTGO_E_INVALID, w + ": the instance array is not 4-byte aligned");
+    if (!c->wm.instanced) return fail(c, RTGO_E_STATE, w + ": no instanced scene (call rtgo_whitted_set_scene first)");
+    if (n == 0 || n > RTGO_WHITTED_MAX_INSTANCES)
+        return fail(c, RTGO_E_UNSUPPORTED, w + ": instance count must be in [1, " + std::to_string(RTGO_WHITTED_MAX_INSTANCES) + "]");
+    if (refit && n != (uint32_t)c->wm.top.n_instances)
+        return fail(c, RTGO_E_INVALID, w + ": a refit takes the scene's " + std::to_string(c->wm.top.n_instances) + " instances");
+    return RTGO_OK;
+}
+
+// the table inst_prepare_kernel and the gather read of wm's meshes, InstMesh for WhittedMeshInfo
+static void whitted_mesh_table(const WhittedMesh& wm, whitted::InstMesh* table)
+{
+    for (size_t k = 0; k < wm.meshes.size(); ++k) {
+        const WhittedMeshInfo& mi = wm.meshes[k];
+        table[k] = {{mi.lo[0], mi.lo[1], mi.lo[2]}, {mi.hi[0], mi.hi[1], mi.hi[2]}, mi.rec_base, mi.tri_base, mi.vert_base, mi.root, mi.flags, mi.max_material};
+    }
+}
+
 static int whitted_set_instances_device(rtgo_ctx* c, const void* d_instances, uint32_t n, bool rebuild)
 {
     using namespace whitted;
     const char* what = "rtgo_whitted_set_instances_device";
     const std::string w(what);
     WhittedMesh& wm = c->wm;
-    if (!rebuild && n != (uint32_t)wm.top.n_instances)
-        return fail(c, RTGO_E_INVALID, w + ": a refit takes the scene's " + std::to_string(wm.top.n_instances) + " instances");
     RTGO_HIP(c, hipSetDevice(c->device));
     RTGO_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = whitted_refresh_host(c)) return rc;   // (what this call writes of the host's fields must not be overtaken by an older update's)
     std::vector<InstMesh> table(wm.meshes.size());
-    for (size_t k = 0; k < table.size(); ++k) {
-        const WhittedMeshInfo& mi = wm.meshes[k];
-        table[k] = {{mi.lo[0], mi.lo[1], mi.lo[2]}, {mi.hi[0], mi.hi[1], mi.hi[2]}, mi.rec_base, mi.tri_base, mi.vert_base, mi.root, mi.flags, mi.max_material};
-    }
+    whitted_mesh_table(wm, table.data());
     const unsigned int* d_inst = static_cast<const unsigned int*>(d_instances);
     const unsigned int blocks = (n + 255u) / 256u;
     const int n_recs = wm.top.n_recs;   // (refit)
@@ -1563,6 +1617,78 @@ static int whitted_set_instances_device(rtgo_ctx* c, const void* d_instances, ui
     }
     wm.top.shade = std::move(shade);
     wm.instances = std::move(instances);
+    return RTGO_OK;
+}
+
+// ---- the refit that waits for nothing on the host (rtgo_whitted_refit_instances_device_async) ---------------------------
+// The refit above once the arguments have passed whitted_check_instances_args, enqueued: a slot of the context's ring, then
+// inst_prepare_kernel into the scene's staging with its verdict in the slot, the verdict's copy and the slot's event, then the gated
+// kernels -- inst_commit_kernel, and for a top level with records inst_refit_gated_kernel -- every time: the verdict is not known here.
+// Nothing is read back; wm.instances and wm.top.meta's grid are marked stale instead (whitted_refresh_host).  A context's first call
+// allocates the ring, a scene's first call the staging; no other call allocates, frees or waits (but a 65th update in flight, once).
+static int whitted_refit_instances_async(rtgo_ctx* c, const void* d_instances, uint32_t n, uint64_t* ticket)
+{
+    using namespace whitted;
+    WhittedMesh& wm = c->wm;
+    WhittedInstStaging& st = wm.staging;
+    RTGO_HIP(c, hipSetDevice(c->device));
+    rtgo_ctx::UpdateRing& ring = c->w_updates;
+    const size_t slots = rtgo_ctx::UpdateRing::kSlots;
+    if (!ring.d.get()) {
+        RTGO_HIP(c, ring.d.alloc(slots * kVerdictWords));
+        RTGO_HIP(c, ring.h.alloc(slots * kVerdictWords));
+        for (size_t s = 0; s < slots; ++s)
+            if (!ring.done[s].get()) RTGO_HIP(c, ring.done[s].create(hipEventDisableTiming));
+    }
+    const int n_recs = wm.top.n_recs;
+    if (!st.shade.get()) {
+        st = WhittedInstStaging();
+        RTGO_HIP(c, st.boxes.alloc((size_t)6 * n));
+        RTGO_HIP(c, st.idx.alloc((size_t)3 * n));
+        RTGO_HIP(c, st.tris.alloc((size_t)3 * n));
+        RTGO_HIP(c, st.qrecs.alloc((size_t)2 * n));
+        RTGO_HIP(c, st.done.alloc((size_t)std::max(n_recs, 1)));
+        RTGO_HIP(c, st.words.alloc(WhittedInstStaging::kWords));
+        RTGO_HIP(c, st.kept.alloc((size_t)kInstDwords * n));
+        RTGO_HIP(c, st.table.alloc((size_t)kMaxMeshes * kInstMeshDwords));
+        RTGO_HIP(c, st.h_table.alloc((size_t)kMaxMeshes * kInstMeshDwords));
+        RTGO_HIP(c, hipMemsetAsync(st.words.get(), 0, WhittedInstStaging::kWords * sizeof(unsigned int), c->stream));
+        RTGO_HIP(c, st.shade.alloc(n));   // (last: what says the staging is there)
+    }
+    // the mesh table, up again only when the meshes have changed under it (in a call that drained the stream: no copy of the image is in flight)
+    InstMesh table[kMaxMeshes];
+    const size_t n_meshes = wm.meshes.size(), table_words = n_meshes * kInstMeshDwords;
+    whitted_mesh_table(wm, table);
+    if (st.table_words != table_words || std::memcmp(st.h_table.get(), table, table_words * sizeof(unsigned int)) != 0) {
+        std::memcpy(st.h_table.get(), table, table_words * sizeof(unsigned int));
+        RTGO_HIP(c, hipMemcpyAsync(st.table.get(), st.h_table.get(), table_words * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+        st.table_words = table_words;
+    }
+    const uint64_t t = ring.next;
+    const unsigned int slot = rtgo_ctx::UpdateRing::slot(t);
+    // the slot's last ticket leaves the ring; a ring full of updates in flight waits here for the oldest, as timed_launch's does
+    if (ring.next_reuses_a_slot()) RTGO_HIP(c, hipEventSynchronize(ring.done[slot].get()));
+    unsigned int* d_verdict = ring.d.get() + (size_t)slot * kVerdictWords;
+    const unsigned int* d_inst = static_cast<const unsigned int*>(d_instances);
+    const unsigned int blocks = (n + 255u) / 256u;
+    unsigned int* d_applied = st.words.get() + WhittedInstStaging::kMetaWords;
+    RTGO_HIP(c, hipMemsetAsync(d_verdict, 0xFF, kVerdictWords * sizeof(unsigned int), c->stream));
+    hipLaunchKernelGGL(inst_prepare_kernel, dim3(blocks), dim3(256), 0, c->stream, d_inst, n, (const unsigned int*)st.table.get(), (unsigned int)n_meshes,
+                       (unsigned int)wm.n_materials, (const InstShade*)wm.top.shade.get(), (const InstWalk*)wm.top.inst.get(), st.shade.get(), st.boxes.get(),
+                       st.idx.get(), st.tris.get(), d_verdict);
+    RTGO_HIP(c, hipGetLastError());
+    RTGO_HIP(c, hipMemcpyAsync(ring.h.get() + (size_t)slot * kVerdictWords, d_verdict, kVerdictWords * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    RTGO_HIP(c, hipEventRecord(ring.done[slot].get(), c->stream));
+    hipLaunchKernelGGL(inst_commit_kernel, dim3(blocks), dim3(256), 0, c->stream, (const unsigned int*)d_verdict, d_inst, (const InstShade*)st.shade.get(),
+                       reinterpret_cast<const InstMesh*>(st.table.get()), n, wm.top.shade.get(), wm.top.inst.get(), st.kept.get(), d_applied);
+    if (n_recs > 0)
+        hipLaunchKernelGGL(inst_refit_gated_kernel, dim3(1), dim3(kBuildThreads), 0, c->stream, (const unsigned int*)d_verdict, (const float*)st.boxes.get(),
+                           (const unsigned int*)st.idx.get(), (int)n, n_recs, wm.top.meta.walk_depth, wm.top.recs.get(), st.tris.get(), st.qrecs.get(), st.done.get(),
+                           reinterpret_cast<WhittedBuildMeta*>(st.words.get()));
+    RTGO_HIP(c, hipGetLastError());
+    st.stale = true;
+    ring.next = t + 1;
+    *ticket = t;
     return RTGO_OK;
 }
 

@@ -155,5 +155,64 @@ __global__ __launch_bounds__(256) void inst_gather_kernel(const float4* __restri
     out[3] = make_float4(__int_as_float(m.rec_base), __int_as_float(m.tri_base), __int_as_float(m.root), __int_as_float(i));
 }
 
+// ---- the refit of rtgo_whitted_refit_instances_device_async: inst_prepare_kernel into buffers the scene owns, its verdict
+// in a slot of the context's ring and never read by the host in between; the two kernels below do every write to the scene, and each reads
+// that verdict first.  The kernel boundary after inst_prepare_kernel is what makes the verdict complete and visible to them
+// (rtgo_large.h's argument for large_update_staged_kernel).
+
+// the gate: the same address in every lane, so five scalar loads per wave
+__device__ __forceinline__ bool inst_verdict_clean(const unsigned int* __restrict__ verdict)
+{
+    unsigned int all = kNoFault;
+    for (int q = 0; q < kInstVerdictKinds; ++q) all &= verdict[q];
+    return all == kNoFault;
+}
+
+constexpr int kInstShadeQuads = 7;   // InstShade: seven float4
+static_assert(sizeof(InstShade) == kInstShadeQuads * sizeof(float4), "InstShade is seven float4");
+
+// What a clean verdict lets into the scene, everything but the top level's records: shade[0, n) = staged[0, n) (inst_prepare_kernel's
+// records); walk[pos] as inst_gather_kernel writes it under RTGO_UPDATE_REFIT (the leaf order stays: walk[pos].instance as it is, read by
+// the lane that rewrites it); kept[0, 14 n) = the caller's records, the copy the host adopts when it next needs the instances; and
+// *applied, which counts the updates that got this far, bumped once.  The two copies are flat streams -- the 112-byte records as float4,
+// the 56-byte ones as dwords (the caller's buffer is 4-byte aligned, no more) -- lane after lane over the arrays, not a lane per record
+// at a stride of 28 or 14 dwords; so nothing is staged in LDS.  The grid is inst_prepare_kernel's: one lane per instance.
+__global__ __launch_bounds__(256) void inst_commit_kernel(const unsigned int* __restrict__ verdict, const unsigned int* __restrict__ inst,
+                                                          const InstShade* __restrict__ staged, const InstMesh* __restrict__ meshes, unsigned int n,
+                                                          InstShade* __restrict__ shade, InstWalk* walk, unsigned int* __restrict__ kept,
+                                                          unsigned int* __restrict__ applied)
+{
+    if (!inst_verdict_clean(verdict)) return;
+    const unsigned int g = blockIdx.x * 256u + threadIdx.x, lanes = gridDim.x * 256u;
+    const float4* __restrict__ src = reinterpret_cast<const float4*>(staged);
+    float4* __restrict__ dst = reinterpret_cast<float4*>(shade);
+    for (unsigned int k = g; k < n * kInstShadeQuads; k += lanes) dst[k] = src[k];
+    for (unsigned int k = g; k < n * kInstDwords; k += lanes) kept[k] = inst[k];
+    if (g == 0) atomicAdd(applied, 1u);
+    if (g >= n) return;
+    const int i = walk[g].instance;
+    if ((unsigned int)i >= n) return;   // (a leaf order is a permutation of [0, n): never taken)
+    const InstMesh m = meshes[inst[(size_t)i * kInstDwords + 12]];
+    const InstShade& sh = staged[i];
+    float4* out = reinterpret_cast<float4*>(walk + g);
+    out[0] = sh.w2o[0];
+    out[1] = sh.w2o[1];
+    out[2] = sh.w2o[2];
+    out[3] = make_float4(__int_as_float(m.rec_base), __int_as_float(m.tri_base), __int_as_float(m.root), __int_as_float(i));
+}
+
+// refit_kernel behind the gate, over the staged boxes and index triples and the scene's top-level records: one workgroup of
+// kBuildThreads, launched only for a top level that has records.  refit_structure clears done[0, n_recs) itself before its first pass,
+// and writes out_meta (a block the scene owns) like everything else only once the verdict has been read clean.
+__global__ __launch_bounds__(kBuildThreads) void inst_refit_gated_kernel(const unsigned int* __restrict__ verdict, const float* __restrict__ boxes,
+                                                                         const unsigned int* __restrict__ idx, int n, int n_recs, int walk_depth,
+                                                                         float4* recs, float4* tris, uint4* qrecs, int* done,
+                                                                         WhittedBuildMeta* __restrict__ out_meta)
+{
+    __shared__ float s_red[6][kBuildThreads];
+    if (!inst_verdict_clean(verdict)) return;
+    refit_structure<false>({boxes, idx, n, n_recs, walk_depth, recs, tris, qrecs, done, out_meta}, s_red);
+}
+
 }  // namespace whitted
 }  // namespace rtgo
