@@ -121,7 +121,8 @@ typedef struct rtgo_stats {
                                  bit 8 the straight-line walk of a two-leaf tree (render_pair_kernel),
                                  bit 9 that walk's kernel at seven waves per SIMD (render_pair7_kernel; always with bit 8),
                                  bit 10 that walk with the slab test of a certified cuboid (render_slab7_kernel; always with bits 8 and 9),
-                                 bit 11 that kernel's form for 16 samples per pixel in workgroups of 256 threads (render_unit16_kernel; always with bits 8, 9 and 10) */
+                                 bit 11 that kernel's form for 16 samples per pixel in workgroups of 256 threads (render_unit16_kernel; always with bits 8, 9 and 10),
+                                 bit 12 that kernel with the room steered in world axes (render_roomw_kernel; always with bits 8 to 11; RTGO_NO_ROOMW=1: off) */
     uint32_t launches_trial;  /* launches since rtgo_reset_stats that were trial launches */
 } rtgo_stats;
 

@@ -219,6 +219,14 @@ static int build_fast_tree(rtgo_ctx* c, uint32_t n, int have_aabbs, float big_fr
         // (which of the pair kernels' two leaves also hold the slab certificate: bit 0 node 1, bit 1 node 2)
         if (t.pair) t.slab_leaves = ((leaf_cuboid(link(3)) & kSlabBit) ? 1 : 0) | ((leaf_cuboid(link(5)) & kSlabBit) ? 2 : 0);
     }
+    // the world-axis form of the list's room (render_roomw_kernel): from the group's six records, read back here, once per build
+    t.room_world = rtgo::RoomWorld();
+    if (t.pair && t.slab_list && t.list_cub == 2 && (uint32_t)meta.n_small + 6u <= n) {
+        float rec[6][16];
+        RTGO_HIP(c, hipMemcpyAsync(rec, t.d_fprims.get() + 4 * (size_t)meta.n_small, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+        RTGO_HIP(c, hipStreamSynchronize(c->stream));
+        room_world_certify(rec, true, true, t.room_world);
+    }
     return RTGO_OK;
 }
 

@@ -72,6 +72,9 @@ static RenderKernel find_slab_kernel(int wpe) { return wpe == 7 ? render_slab7_k
 // both for granted, so the launch has to have them
 static RenderKernel find_unit16_kernel(int wpe, uint32_t nn, int block) { return (wpe == 7 && nn == 16u && block == 256) ? render_unit16_kernel : nullptr; }
 
+// ... and the form of THAT whose room is steered in world axes (ROOMW, room_world): for launches that would take render_unit16_kernel
+static RenderKernel find_roomw_kernel(RenderKernel unit16) { return unit16 == render_unit16_kernel ? render_roomw_kernel : nullptr; }
+
 // window rows below y that this rank owns under the band interleave
 static uint32_t owned_rows_below(uint32_t y, uint32_t band_h, uint32_t n_ranks, uint32_t rank)
 {
@@ -105,6 +108,7 @@ struct Knobs {
     bool no_pair = std::getenv("RTGO_NO_PAIR") != nullptr;          // two-leaf trees are walked by fast_tree like every other (render_pair_kernel is not taken)
     bool no_slab = std::getenv("RTGO_NO_SLAB") != nullptr;          // the pair kernels keep cuboid_range (render_slab7_kernel is not taken)
     bool no_unit16 = std::getenv("RTGO_NO_UNIT16") != nullptr;      // 16 spp launches of the slab kernel keep render_slab7_kernel (render_unit16_kernel is not taken)
+    bool no_roomw = std::getenv("RTGO_NO_ROOMW") != nullptr;        // the room keeps its frame's slab test (render_roomw_kernel is not taken: render_unit16_kernel runs)
     bool pin_big = std::getenv("RTGO_BIG_PERCENT") != nullptr;      // one fast-walk structure, of big_percent (else 36 % and 15 %)
     unsigned int big_percent = env_uint("RTGO_BIG_PERCENT", 36);
     unsigned int max_wpe = env_uint("RTGO_MAX_WPE", 0);             // cap of the waves-per-SIMD variant; 0: by the work
@@ -984,11 +988,22 @@ static void last_ray_params(const rtgo_ctx* c, const AnalyticScene::FastTree& ft
 // A launch that takes a pair kernel: the three words a ray of those kernels reads before its walk (PairWords), from the fields walk_params
 // and last_ray_params have set.  They lie in the grid's space (a pair launch walks no grid), so this is the last write to that space:
 // call it once the kernel is chosen, and write p.grid no more after it.
-static void pair_words(LaunchParams& p)
+// rw, room_mu: the room in world axes and this launch's margin for it (room_world_margin), for render_roomw_kernel; null: zeros, read by no kernel.
+static void pair_words(LaunchParams& p, const rtgo::RoomWorld* rw, float room_mu)
 {
+    p.pair = PairWords();
     p.pair.cub_mu = p.cub_mu;
     p.pair.n_prims = p.n_prims;
     p.pair.last_depth = p.emit_n != 0 ? p.max_depth : -1;
+    if (rw) {
+        p.pair.room_map = rw->map;
+        for (int j = 0; j < 3; ++j) {
+            p.pair.room_lo[j] = rw->lo[j];
+            p.pair.room_hi[j] = rw->hi[j];
+        }
+        p.pair.room_mu = room_mu;
+        p.pair.room_thr = rw->thr;
+    }
 }
 
 // Scheduling: units of 64 paths = the N*N samples of `unit_px` neighbouring pixels of one row; the queue hands out STRIPS of
@@ -1328,16 +1343,22 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     const RenderKernel slab_kernel = (pair_kernel && !kn.no_slab && walked.slab_list && walked.slab_leaves == 3) ? find_slab_kernel(b.wpe) : nullptr;
     // ... and, at 16 samples per pixel in workgroups of 256 threads, its form with both compiled in.  RTGO_NO_UNIT16: off.
     const RenderKernel unit16_kernel = (slab_kernel && !kn.no_unit16) ? find_unit16_kernel(b.wpe, nn, b.block) : nullptr;
-    const RenderKernel kernel = unit16_kernel ? unit16_kernel : (slab_kernel ? slab_kernel : (pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch)));
+    // ... and, where the room also holds the world-axis certificate with a margin below 2 % of its thinnest slab at this launch's reach
+    // (rtgo_room_world.h), the form of that kernel that steers the room in world axes.  RTGO_NO_ROOMW: off.
+    const float room_mu = (unit16_kernel && !kn.no_roomw) ? room_world_margin(walked.room_world, p.cub_mu, c->guard_reach) : -1.0f;
+    const RenderKernel roomw_kernel = room_mu > 0.0f ? find_roomw_kernel(unit16_kernel) : nullptr;
+    const RenderKernel kernel = roomw_kernel ? roomw_kernel : unit16_kernel ? unit16_kernel : (slab_kernel ? slab_kernel : (pair_kernel ? pair_kernel : find_kernel(path, canon, b.wpe, pk.stream, stats, frames, use_grid, false, batch)));
     if (pair_kernel) p.stack_depth = 0;   // (fast_pair has no stack: pick_block reserved none, and the lights follow the scene directly)
-    if (pair_kernel) pair_words(p);
+    if (pair_kernel) pair_words(p, roomw_kernel ? &walked.room_world : nullptr, room_mu);
     const bool pair7 = pair_kernel && b.wpe == 7;
     if (kn.debug) {
-        char kname[160];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
+        char kname[256];   // (the 7-waves pair kernel is no template instantiation: its name carries its waves)
         // (the slab kernel is named with the pair kernel whose body it is and which RTGO_NO_SLAB=1 would run: readers of this line that
         // ask which walk a launch took -- the pair walk at these waves -- find it where they found it)
         // (likewise the 16 spp form, named with the slab kernel whose body it is and which RTGO_NO_UNIT16=1 would run)
-        if (unit16_kernel) std::snprintf(kname, sizeof kname, "render_unit16_kernel, the 16 spp form of kernel render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
+        // (and the world-room form, named with the 16 spp kernel whose body it is and which RTGO_NO_ROOMW=1 would run)
+        if (roomw_kernel) std::snprintf(kname, sizeof kname, "render_roomw_kernel, the world-room form of kernel render_unit16_kernel, the 16 spp form of kernel render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
+        else if (unit16_kernel) std::snprintf(kname, sizeof kname, "render_unit16_kernel, the 16 spp form of kernel render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
         else if (slab_kernel) std::snprintf(kname, sizeof kname, "render_slab%d_kernel, the slab form of kernel render_pair%d_kernel", b.wpe, b.wpe);
         else if (pair7) std::snprintf(kname, sizeof kname, "render_pair7_kernel");
         else std::snprintf(kname, sizeof kname, "%s<%d>", pair_kernel ? "render_pair_kernel" : (batch ? "render_frames_kernel" : "render_kernel"), b.wpe);
@@ -1356,6 +1377,7 @@ static int launch_frame(rtgo_ctx* c, const rtgo_frame* f, uint32_t n_frames, boo
     if (pair7) c->last_variant |= 512u;
     if (slab_kernel) c->last_variant |= 1024u;
     if (unit16_kernel) c->last_variant |= 2048u;
+    if (roomw_kernel) c->last_variant |= 4096u;
     c->seeds_last = (p.seeds ? 1u : 0u) | (p.seeds_next ? 2u : 0u);
     if (p.seeds_next) {
         c->seeds.read = 1 - c->seeds.read;

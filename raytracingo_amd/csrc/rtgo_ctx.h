@@ -6,6 +6,7 @@
 #include "rtgo_device.h"
 #include "rtgo_large.h"
 #include "rtgo_owners.h"
+#include "rtgo_room_world.h"
 #include "rtgo_shade.h"
 #include "rtgo_ticket_ring.h"
 #include "rtgo_trace.h"
@@ -65,6 +66,7 @@ struct AnalyticScene {
         int list_cub = 0, n_big_pairs = 0; // the up-front list starts with a certified box (1) / room (2): cuboid_range
         bool slab_list = false;            // the list's cuboid also holds the slab certificate (cuboid_slab)
         int slab_leaves = 0;               // ... and so do the pair kernels' leaves: bit 0 node 1, bit 1 node 2 (0 when `pair` is false)
+        rtgo::RoomWorld room_world;        // the list's room in world axes (rtgo_room_world.h; ok = false: it does not hold); a launch adds its reach
         float cub_a = 0.0f, cub_b = 0.0f;  // its margin = kCuboidTol + K (cub_a R + cub_b), R = reach of the launch's rays
         // the last-ray certificate's scene half (emitter_cert): the emitters, the list's records after the room (emit_n = 0: no certificate), and
         // for each (emitter, wall) pair k = 6 e + g the least y_g over the emitter's corners and the coefficients of the margin it

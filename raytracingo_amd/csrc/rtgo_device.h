@@ -78,10 +78,17 @@ __host__ __device__ constexpr int leaf_cuboid(int link) { return (-link) >> 20; 
 // last (max_depth) when the launch has the certificate (emit_n != 0), -1 (no depth) when it has not -- the host decides once what every
 // ray would otherwise decide from two fields.  The other kernels read LaunchParams' own fields, as they did; the words lie where a GRID
 // launch has its grid, so that no field of LaunchParams moves and every other kernel compiles to the instructions it had.
+// The words from room_map on are read by render_roomw_kernel alone (room_world): the room's slab certificate in WORLD axes
+// (rtgo_room_world.h), filled when the walked tree holds it at this launch's reach.  room_lo / room_hi: the room's planes per world axis;
+// room_mu: the margin in world units; room_thr: |d_j| at or below it counts as parallel to the walls of axis j; room_map: three bits per
+// plane, the face's offset in the group, plane = 2 * world axis + (0: low, 1: high).
 struct PairWords {
     float cub_mu;
     int last_depth;
     int n_prims;
+    int room_map;
+    float room_lo[3], room_hi[3];
+    float room_mu, room_thr;
 };
 
 struct LaunchParams {
@@ -927,6 +934,69 @@ __device__ __forceinline__ void cuboid_slab(Ptr fp, const float4* __restrict__ l
     }
 }
 
+// What a ROOMW walk hands from closest_hit_fast to the list and to fast_pair: the launch's words and the ray's reciprocals.
+struct RoomRay {
+    const PairWords* words;
+    v3 id, noid;
+};
+// cuboid_slab<true, kCubRoom> for a room whose slab certificate also holds in WORLD axes (rtgo_room_world.h: the frame rows of the room's
+// first face are s e_j plus a residue the margin covers), so that the steering needs no transform and no reciprocal of its own: id and
+// noid are the walk's (closest_hit_fast), the planes and the margin arrive in world units through PairWords.  A room needs no entry side:
+// the candidate is the face of the axis left first, and leaving the compare against the latest entry out can only add candidates.  Per
+// axis: the parallel threshold, the exit as two fma and a max, w = mu id, the earliest exit X, and "not certainly past X".  The side is
+// the sign of id (w carries it); the candidate loop, the flat lanes and the compare sense (a NaN makes candidates) are cuboid_slab's,
+// and the chosen face gets the reference's whole test through rect_commit: the bits are made there, this only steers.
+template <bool MASK>
+__device__ __forceinline__ void room_world(const RoomRay& rr, const float4* __restrict__ lds, int first, v3 wo, v3 wd, float tmin, FastHit& best)
+{
+    typedef Pred<MASK> P;
+    typedef typename P::T B;
+    const PairWords& rw = *rr.words;
+    const v3 id = rr.id, noid = rr.noid;
+    const int map = rw.room_map;
+    const float mu = rw.room_mu, thr = rw.room_thr;
+    const float dd[3] = {wd.x, wd.y, wd.z}, ii[3] = {id.x, id.y, id.z}, nn[3] = {noid.x, noid.y, noid.z};
+    float tp[3], ws[3], X = INFINITY;
+    B flat = P::off();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        flat = flat | P::le(fabsf(dd[a]), thr);
+        tp[a] = fmaxf(fmaf(rw.room_lo[a], ii[a], nn[a]), fmaf(rw.room_hi[a], ii[a], nn[a]));
+        ws[a] = mu * ii[a];
+        X = fminf(X, tp[a] + fabsf(ws[a]));
+    }
+    B s0, s1, s2;
+    s0 = P::andnot(P::not_lt(X, tp[0] - fabsf(ws[0])), flat);
+    s1 = P::andnot(P::not_lt(X, tp[1] - fabsf(ws[1])), flat);
+    s2 = P::andnot(P::not_lt(X, tp[2] - fabsf(ws[2])), flat);
+#pragma unroll 1
+    for (;;) {
+        const B any = s0 | s1 | s2;
+        if (P::none(any)) break;
+        // the lowest candidate axis; a room is left through the side the ray goes to (d_j > 0: the high plane)
+        const int sg = __float_as_int(P::lane(s0) ? ws[0] : (P::lane(s1) ? ws[1] : ws[2])) >> 31;   // (-1: d_j < 0)
+        const int sh = (P::lane(s0) ? 0 : (P::lane(s1) ? 6 : 12)) + (~sg & 3);
+        const int ps = first + ((map >> sh) & 7);
+        s2 = s2 & (s0 | s1);
+        s1 = s1 & s0;
+        s0 = P::off();
+        const float4 r1 = lds[4 * ps + 1];
+        const int orig = __float_as_int(lds[4 * ps + 3].y);
+        const float dy = r1.x * wd.x + r1.y * wd.y + r1.z * wd.z;
+        rect_commit<MASK>(lds + 4 * ps, r1, dy, any & P::lt(dy, 0.0f), ps, orig, wo, wd, tmin, best);
+    }
+    if (P::any(flat)) {
+#pragma unroll 1
+        for (int k = 0; k < 6; ++k) {
+            const int ps = first + k;
+            const float4 r1 = lds[4 * ps + 1];
+            const int orig = __float_as_int(lds[4 * ps + 3].y);
+            const float dy = r1.x * wd.x + r1.y * wd.y + r1.z * wd.z;
+            rect_commit<MASK>(lds + 4 * ps, r1, dy, flat & P::lt(dy, 0.0f), ps, orig, wo, wd, tmin, best);
+        }
+    }
+}
+
 // conservative slab test: t = fma(b, 1/d, -o/d) with the hardware reciprocal
 template <bool MASK = false>
 __device__ __forceinline__ typename Pred<MASK>::T box_fast(const float4 q0, const float4 q1, v3 id, v3 noid, float tmin, float tmax, float& tn_out)
@@ -957,10 +1027,13 @@ __device__ __forceinline__ typename Pred<MASK>::T box_fast(const float4 q0, cons
 // lane than the other two: profiles/r02f/README.md).  fast_list: the up-front list, which also gives the ray its first closest-hit bound.
 // LAST, `last`: the lane's ray is the last of its path under the last-ray certificate (closest_hit_fast): it skips the room.
 // KIND: kCubRoom when the launch vouches for a list that starts with a certified room (the pair kernels), else kCubEither (list_cub says).
-template <bool LAST = false, CubKind KIND = kCubEither, bool MASK = false, bool SLAB = false>
+// ROOMW: the room's steering is the world-axis form (room_world) on the walk's id and noid, which `rr` holds with the launch's words.
+template <bool LAST = false, CubKind KIND = kCubEither, bool MASK = false, bool SLAB = false, bool ROOMW = false>
 __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, const float4* __restrict__ g_fprims, int n_small, int n_prims, int n_big_pairs,
-                                          int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, typename Pred<MASK>::T last = Pred<MASK>::off())
+                                          int list_cub, float cub_mu, v3 o, v3 d, float tmin, FastHit& best, typename Pred<MASK>::T last = Pred<MASK>::off(),
+                                          const RoomRay* rr = nullptr)
 {
+    static_assert(!ROOMW || (SLAB && KIND == kCubRoom), "the world form replaces the slab test of a room");
     // the few "big" primitives (walls, floors; the whole scene when it is tiny) first.  The loop index is wave-uniform and
     // g_fprims is a read-only kernel argument, so the records arrive by scalar loads (s_load_dwordx4) into SGPRs: no LDS
     // traffic, no VGPRs for the matrices, and the loads of the next primitives overlap the tests of the current ones.
@@ -969,7 +1042,9 @@ __device__ __forceinline__ void fast_list(const float4* __restrict__ s_fprims, c
         // the room's six walls (or one big box) as a cuboid, the rest of the list after them
         if (!LAST || Pred<MASK>::any(Pred<MASK>::inv(last))) {
             const bool box = KIND == kCubEither && list_cub == 1;
-            if constexpr (SLAB) {
+            if constexpr (ROOMW) {
+                if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) room_world<MASK>(*rr, s_fprims, n_small, o, d, tmin, best);
+            } else if constexpr (SLAB) {
                 if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) cuboid_slab<true, KIND, MASK>(g_fprims, s_fprims, n_small, cub_mu, o, d, tmin, best);
             } else if (!LAST || Pred<MASK>::lane(Pred<MASK>::inv(last))) cuboid_range<true, KIND, MASK>(g_fprims, s_fprims, n_small, box ? cub_mu : INFINITY, box ? -INFINITY : -cub_mu, o, d, tmin, best);
         }
@@ -1083,14 +1158,15 @@ __device__ __forceinline__ void fast_tree(const float4* __restrict__ s_fnodes, c
 // <= the closest hit.  What is gone is the machinery of a deep tree: the root's own box test (the root box is the union of the two, and
 // fma(q, id, noid) is monotone in q: a lane that passes a child's slab test passes the root's), the while-while loop, the stack word
 // in LDS, the pop loop with its dependent reads of a node's links, and the leaf's dispatch on tree_spheres / leaf_cuboid / cub_mu.
-template <bool MASK, bool SLAB = false>
+// HAVEID: the caller made id and noid, by these same operations, for the list's room test and hands them over in `rr` (ROOMW, closest_hit_fast).
+template <bool MASK, bool SLAB = false, bool HAVEID = false>
 __device__ __forceinline__ void fast_pair(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims, float cub_mu, v3 o, v3 d, float tmin, FastHit& best,
-                                          unsigned int& dbg_boxes, unsigned int& dbg_tests)
+                                          unsigned int& dbg_boxes, unsigned int& dbg_tests, const RoomRay* rr = nullptr)
 {
     typedef Pred<MASK> P;
     auto safe_rcp = [](float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(x), -1e30f, 1e30f); };   // (see fast_tree on 1 / 0)
-    const v3 id = mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
-    const v3 noid = mk(-(o.x * id.x), -(o.y * id.y), -(o.z * id.z));
+    const v3 id = HAVEID ? rr->id : mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+    const v3 noid = HAVEID ? rr->noid : mk(-(o.x * id.x), -(o.y * id.y), -(o.z * id.z));
     // (wave-uniform addresses: four reads under one wait; a leaf's first record comes with its box)
     const float4 l0 = s_fnodes[2], l1 = s_fnodes[3], h0 = s_fnodes[4], h1 = s_fnodes[5];
     float tl, tr;
@@ -1253,20 +1329,37 @@ __device__ __forceinline__ bool fast_winner(const float4* __restrict__ s_fprims,
 // order in which candidates are met (closer()).  LAST: the instantiation has this path at all (else `last` is ignored).
 // PAIR (render_pair_kernel): the tree is a root over two cuboid leaves, walked by fast_pair.
 // MASK: the carrier of `last` and of the walk's predicates from here down (Pred); the pair kernels' ray loop alone sets it.
-template <bool GRID, bool LAST = false, bool PAIR = false, bool MASK = false, bool SLAB = false>
+// ROOMW (render_roomw_kernel): the list's room takes the world-axis form on id and noid, made here once for it and for fast_pair; `rw`: its words.
+template <bool GRID, bool LAST = false, bool PAIR = false, bool MASK = false, bool SLAB = false, bool ROOMW = false>
 __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims,
                                                  const float4* __restrict__ g_fprims, const GridParams grid,
  unsigned int* __restrict__ s_stack, int bshift,
                                                  int n_small, int n_prims, int n_big_pairs, int list_cub, float cub_mu, bool tree_spheres, v3 o, v3 d, float tmin, float tmax, Hit& out,
-                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, typename Pred<MASK>::T last, Timeline& tl)
+                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, typename Pred<MASK>::T last, Timeline& tl, const PairWords* rw)
 {
     static_assert(!MASK || PAIR, "the lane-mask predicates are the pair kernels'");
+    static_assert(!ROOMW || (PAIR && SLAB), "the world-axis room serves the slab launches of the pair kernels");
     static_assert(!SLAB || PAIR, "the slab test serves the pair kernels' launches");
     tl.walk_begin();
     FastHit best;
     best.t = tmax;
     best.pos = -1;
     best.orig = -1;
+    if constexpr (ROOMW) {
+        // (1 / d and -o / d as fast_pair makes them, see fast_tree on 1 / 0: made once, before the list, for the room and for the two boxes)
+        auto safe_rcp = [](float x) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(x), -1e30f, 1e30f); };
+        RoomRay rr;
+        rr.words = rw;
+        rr.id = mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+        rr.noid = mk(-(o.x * rr.id.x), -(o.y * rr.id.y), -(o.z * rr.id.z));
+        fast_list<LAST, kCubRoom, MASK, SLAB, true>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last, &rr);
+        const bool walk = Pred<MASK>::lane(Pred<MASK>::either(Pred<MASK>::inv(last), Pred<MASK>::ige(best.pos, 0)));
+        FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (Pred<MASK>::lane(last) ? 6 : 0)));
+        tl.list_done(best.pos);
+        if (!LAST || walk) fast_pair<MASK, SLAB, true>(s_fnodes, s_fprims, cub_mu, o, d, tmin, best, dbg_boxes, dbg_tests, &rr);
+        tl.walk_done(best.pos);
+        return fast_winner(s_fprims, o, d, tmax, best, out);
+    }
     fast_list<LAST, PAIR ? kCubRoom : kCubEither, MASK, SLAB>(s_fprims, g_fprims, n_small, n_prims, n_big_pairs, list_cub, cub_mu, o, d, tmin, best, last);
     const bool walk = Pred<MASK>::lane(Pred<MASK>::either(Pred<MASK>::inv(last), Pred<MASK>::ige(best.pos, 0)));
     FastCounters::lane_only(dbg_tests, (unsigned int)(n_prims - n_small - (Pred<MASK>::lane(last) ? 6 : 0)));
@@ -1559,7 +1652,7 @@ __device__ __forceinline__ void next_frame_seeds(const LaunchParams& p, unsigned
 template <bool PATH, bool STATS, int WPE, bool STREAM, bool COUNT = STATS, bool FRAMES = false, bool GRID = false, bool GLOBAL = false>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = false, PAIR = false, SLAB = false, UNIT16 = false;
+    constexpr bool BATCH = false, PAIR = false, SLAB = false, UNIT16 = false, ROOMW = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1567,7 +1660,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <bool PATH, int WPE, bool FRAMES>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_frames_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false, SLAB = false, UNIT16 = false;
+    constexpr bool BATCH = true, STATS = false, STREAM = false, COUNT = false, GRID = false, GLOBAL = false, PAIR = false, SLAB = false, UNIT16 = false, ROOMW = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1577,7 +1670,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 template <int WPE>
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void render_pair_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false, UNIT16 = false;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false, UNIT16 = false, ROOMW = false;
 #include "rtgo_render_body.inc"
 }
 
@@ -1586,7 +1679,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE, 
 // template above stays at its two instantiations.
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_pair7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false, UNIT16 = false;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = false, UNIT16 = false, ROOMW = false;
     constexpr int WPE = 7;
 #include "rtgo_render_body.inc"
 }
@@ -1595,7 +1688,7 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7)
 // leaves hold the slab certificate (rtgo_build.h).  The one form of the cuboid test in the kernel is the slab's.
 __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_slab7_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = false;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = false, ROOMW = false;
     constexpr int WPE = 7;
 #include "rtgo_render_body.inc"
 }
@@ -1607,7 +1700,16 @@ __global__ __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(7, 7)
 // one address.  The same float operations on the same values in the same order: the same bits.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_unit16_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
 {
-    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = true;
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = true, ROOMW = false;
+    constexpr int WPE = 7;
+#include "rtgo_render_body.inc"
+}
+
+// render_unit16_kernel with the room's slab test steered in world axes (ROOMW: room_world on the walk's own reciprocals, no transform into
+// the first wall's frame): launches whose room also holds the world-axis certificate at their reach (rtgo_room_world.h, rtgo_capi.hip).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void render_roomw_kernel(const LaunchParams p_arg, const float4* __restrict__ g_fprims)
+{
+    constexpr bool PATH = true, STATS = false, STREAM = false, COUNT = false, FRAMES = true, GRID = false, GLOBAL = false, BATCH = false, PAIR = true, SLAB = true, UNIT16 = true, ROOMW = true;
     constexpr int WPE = 7;
 #include "rtgo_render_body.inc"
 }

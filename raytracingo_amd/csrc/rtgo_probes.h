@@ -218,11 +218,11 @@ struct FastCounters {
 
 // ---- -DRTGO_CMPWALK: both walks on every ray of a canonical launch (tools/cmp_walks.py, tools/fuzz_farfield.py) -----------------------
 #ifdef RTGO_CMPWALK
-template <bool GRID, bool LAST, bool PAIR, bool MASK, bool SLAB>
+template <bool GRID, bool LAST, bool PAIR, bool MASK, bool SLAB, bool ROOMW>
 __device__ __forceinline__ bool closest_hit_fast(const float4* __restrict__ s_fnodes, const float4* __restrict__ s_fprims, const float4* __restrict__ g_fprims,
                                                  const GridParams grid, unsigned int* __restrict__ s_stack, int bshift, int n_small, int n_prims, int n_big_pairs,
                                                  int list_cub, float cub_mu, bool tree_spheres, v3 o, v3 d, float tmin, float tmax, Hit& out,
-                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, typename Pred<MASK>::T last, Timeline& tl);   // (rtgo_device.h)
+                                                 unsigned int& dbg_boxes, unsigned int& dbg_tests, typename Pred<MASK>::T last, Timeline& tl, const PairWords* rw);   // (rtgo_device.h)
 struct CmpWalk {
     // the fast walk on the ray the canonical walk has just answered (hit, h), straight from global memory; a disagreement is counted in
     // p.cmp[0] and the first 255 are recorded, 16 floats each
@@ -234,8 +234,8 @@ struct CmpWalk {
         // (this lane's canonical stack is idle here: its own 8-byte slots serve as the fast walk's one-word entries)
         // (RTGO_TREE=2 hands this launch the grid in p.fnodes: p.grid.n_cells > 0 then)
         const bool hitf = p.grid.n_cells > 0
-            ? closest_hit_fast<true, false, false, false, false>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1, false, tl)
-            : closest_hit_fast<false, false, false, false, false>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1, false, tl);
+            ? closest_hit_fast<true, false, false, false, false, false>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1, false, tl, nullptr)
+            : closest_hit_fast<false, false, false, false, false, false>(p.fnodes, p.fprims, p.fprims, p.grid, reinterpret_cast<unsigned int*>(s_stack), bshift + 1, p.n_small, p.n_prims, p.n_big_pairs, p.list_cub, p.cub_mu, p.tree_spheres != 0, ro, rd, tmin, tmax, hf, d0, d1, false, tl, nullptr);
         const bool same = hit == hitf && (!hit || (h.t == hf.t && h.prim == hf.prim && h.n.x == hf.n.x && h.n.y == hf.n.y && h.n.z == hf.n.z));
         if (!same) {
             const unsigned int slot = atomicAdd(reinterpret_cast<unsigned int*>(p.cmp), 1u);

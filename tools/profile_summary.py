@@ -6,11 +6,12 @@ KERNEL = "render_kernel<true, false"   # any register-budget variant of the time
 PAIR = "render_pair_kernel<"           # ... or of the one that walks a two-leaf tree (cornell)
 PAIR7 = "render_pair7_kernel"          # ... at seven waves per SIMD
 SLAB = "render_slab"                   # ... with the slab test of a certified cuboid
-UNIT16 = "render_unit16_kernel"        # ... compiled for 16 samples per pixel in workgroups of 256 threads (the bench launch)
+UNIT16 = "render_unit16_kernel"        # ... compiled for 16 samples per pixel in workgroups of 256 threads
+ROOMW = "render_roomw_kernel"          # ... with the room steered in world axes (the bench launch)
 
 
 def timed(name):
-    return KERNEL in name or PAIR in name or PAIR7 in name or SLAB in name or UNIT16 in name
+    return KERNEL in name or PAIR in name or PAIR7 in name or SLAB in name or UNIT16 in name or ROOMW in name
 
 
 head = os.environ.get("RTGO_HEAD")   # the commit the profiled tree is (the GPU box has no .git); a re-run of this script keeps what the first run recorded
